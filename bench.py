@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the ray-marching path on MI355X, BASELINE.json's metric and config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--generator Rectilinear|Fast]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--generator Rectilinear|Fast] [--full] [--dump-outputs DIR]
+
+A plain run times the K steps of --generator and prints its line.  --full adds the secondary measurements: the reference's other
+two generators on the same workload (skipped with --only) and the CPU oracle baseline (skipped with --no-cpu-baseline).
+--dump-outputs DIR writes the planes of the last timed frame to DIR (dump_outputs below).
 
 A "step" is one full frame of the headline workload (4096x2048 panorama, 3x3 synthetic DTED level-2
 tiles, simulation_step 100 m, max_distance 200 km, spherical Earth + US-76 refraction) through the C ABI
@@ -75,6 +79,48 @@ def cpu_baseline(tiles, level):
             "fast": {k: out["Fast"][k] for k in ("value", "unit", "mpixels_per_s", "seconds", "pixels")}}
 
 
+# 11 pixel planes + the 15 arrays of a frame with trace-point lists, plus the sample's indices, at 8 B x 2^18 each: 57 MB at most
+DUMP_SAMPLE = 1 << 18
+DUMP_SEED = 20260101
+
+
+def dump_outputs(out_dir, image, hits):
+    """What the timed path hands its caller after the last timed frame, as float64 DIR/<name>.npy: every [H][W] plane of `image`
+    at a fixed, seeded sample of DUMP_SAMPLE pixels (every pixel of a smaller frame; pixel_index.npy holds their row-major indices,
+    normal.npy is [3][n]) and, where the step also gathered the trace-point lists, those at a seeded sample of their points
+    (hits_*.npy; hits_hit_offset.npy at the sampled pixels).  The sample depends on the frame's size alone.  The first-hit planes
+    are NaN where a pixel has no hit (include/atmrt.h), which hit_count.npy already says: they are written at the sampled pixels
+    with hit_count > 0 only, so every value written is a result and must be finite."""
+    import numpy as np
+    import torch
+
+    def sample(n):
+        if n <= DUMP_SAMPLE:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float64).cpu().numpy())
+
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = image["hit_count"].shape
+    px = sample(H * W)
+    px_dev = torch.from_numpy(px).to(image["hit_count"].device)
+    np.save(os.path.join(out_dir, "pixel_index.npy"), px.astype(np.float64))
+    hit = image["hit_count"].reshape(-1).index_select(0, px_dev) > 0
+    for k, v in image.items():
+        s = v.reshape(-1, H * W).index_select(1, px_dev).squeeze(0)  # normal is [3][H][W]
+        save(k, s if k in ("azimuth", "elevation_angle", "hit_count") else s[..., hit])
+    if hits is not None:
+        save("hits_hit_offset", hits["hit_offset"].reshape(-1).index_select(0, px_dev))
+        pts = sample(int(hits["lat"].shape[0]))
+        np.save(os.path.join(out_dir, "hits_point_index.npy"), pts.astype(np.float64))
+        pts_dev = torch.from_numpy(pts).to(hits["lat"].device)
+        for k, v in hits.items():
+            if k != "hit_offset":
+                save("hits_" + k, v.index_select(0, pts_dev))  # normal [n][3], rgba [n][4]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -84,14 +130,18 @@ def main():
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=2048)
     ap.add_argument("--dted-level", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--also-fast", action="store_true", help="(default behaviour) also time the Fast generator and report it under 'fast'")
-    ap.add_argument("--only", action="store_true", help="time only --generator, skip the secondary generators")
+    ap.add_argument("--full", action="store_true", help="also the secondary generators and the CPU oracle baseline (off: time --generator only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the planes of the last timed frame (a fixed, seeded sample) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--also-fast", action="store_true", help="(default behaviour of --full) also time the Fast generator and report it under 'fast'")
+    ap.add_argument("--only", action="store_true", help="with --full: time only --generator, skip the secondary generators")
     ap.add_argument("--objects", type=int, default=0, help="BASELINE config 5: add N scene objects (70%% frusta, 30%% billboards)")
     ap.add_argument("--terrain-alpha", type=float, default=1.0)
     ap.add_argument("--scene", default="headline", choices=["headline", "S2", "S3", "S4"], help="SURVEY §8(d) scene (tiles, observer, fov)")
     ap.add_argument("--step", type=float, default=None, help="simulation_step override [m]")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` on its own: one process per GPU is the contract, so start the N ranks as a child
@@ -376,6 +426,8 @@ def main():
         return out
 
     elapsed, marched, phase = timed(args.generator, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # before --full's other generators overwrite the planes
+        dump_outputs(args.dump_outputs, image, gathered_hits[0])
     result = {
         "metric": "ray-steps/sec/GPU (and Mpixels/sec) at 4096x2048, step=100 m, max_dist=200 km",
         "value": marched / elapsed, "unit": "ray-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -399,7 +451,7 @@ def main():
         result["tile_columns"] = list(ctx.tile_columns())  # this rank's tile in the last frame (the library re-cuts unbalanced tilings)
         result["world_size_seen"] = dist.get_world_size()
         result["comm"] = {k: comm_info.get(k) for k in ("route", "world", "bytes_per_rank", "gather_ms", "assemble_ms", "tile_ms_max")}
-    if not args.only and args.generator == "Rectilinear":
+    if args.full and not args.only and args.generator == "Rectilinear":
         # the reference's other two generators on the same workload (secondary lines; `value` above is the per-pixel march)
         e2, m2, ph2 = timed("Fast", args.steps, 1)
         result["fast"] = {"value": m2 / e2, "unit": "ray-steps/s", "ms_per_step": e2 / args.steps * 1e3,
@@ -409,7 +461,7 @@ def main():
         result["interpolating_rectilinear"] = {"value": m3 / e3, "unit": "ray-steps/s", "ms_per_step": e3 / args.steps * 1e3,
                                                "mpixels_per_s": W * H * args.steps / e3 / 1e6,
                                                "note": "lattice of Fast-style pixels + 4-corner blend (interpolating_rectilinear.rs)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(tiles, args.dted_level)
         except Exception as exc:  # the oracle is a checker, never a fallback: report, do not hide

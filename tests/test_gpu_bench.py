@@ -44,6 +44,39 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     assert line["n_gpus"] == 1 and line["dtype"] == "f64" and line["roofline"]["kernel"] == "k_rect_march"
 
 
+def test_bench_plain_run_dumps_the_last_frame(tmp_path, gpu_ctx):
+    """A plain run times --generator alone (no secondary generators, no CPU baseline) and --dump-outputs leaves the planes of its
+    last frame: float64, under 64 MB, and equal to the same scene generated through atmrt_generate."""
+    import numpy as np
+    from atm_raytracer_amd import synth
+    from util import bits, run_gpu
+    out = tmp_path / "dump"
+    line, _ = run_bench("--steps", "2", "--warmup", "1", "--width", "512", "--height", "256", "--dted-level", "1", "--dump-outputs", str(out))
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert not {"fast", "interpolating_rectilinear", "cpu_baseline"} & set(line), sorted(line)
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64 << 20
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in files.values()), [k for k, a in files.items() if not np.isfinite(a).all()]
+    assert set(files) == {"pixel_index", "azimuth", "elevation_angle", "hit_count", "lat", "lon", "distance", "elevation", "path_length", "normal"}
+    cfg, tiles = synth.scene("headline", 512, 256, generator="Rectilinear", level=1)
+    want = run_gpu(gpu_ctx, cfg, tiles)
+    px = files["pixel_index"].astype(np.int64)
+    assert np.array_equal(px, np.arange(512 * 256))
+    for k in ("azimuth", "elevation_angle", "hit_count"):
+        assert np.array_equal(bits(files[k]), bits(want[k].ravel().astype(np.float64))), k
+    hit = want["hit_count"].ravel() > 0
+    first = want["hit_offset"].ravel()[hit].astype(np.int64)
+    assert 0 < hit.sum() < hit.size  # the frame has sky pixels: their NaN first-hit values must not reach the dump
+    for k in ("lat", "lon", "distance", "elevation", "path_length"):  # written at the pixels with a hit only
+        assert np.array_equal(files[k], want[k][first]), k
+    assert np.array_equal(files["normal"], want["normal"][first].T)
+
+
+def test_bench_full_adds_the_secondary_generators():
+    line, _ = run_bench("--full", "--no-cpu-baseline", "--steps", "1", "--warmup", "0", "--width", "512", "--height", "256", "--dted-level", "1")
+    assert line["fast"]["value"] > 0 and line["interpolating_rectilinear"]["value"] > 0 and "cpu_baseline" not in line
+
+
 def run_under_torchrun(nproc, *args, env=None, timeout=600):
     import socket
     with socket.socket() as sock:

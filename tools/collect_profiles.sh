@@ -15,7 +15,7 @@ GENS=${2:-Rectilinear Fast InterpolatingRectilinear}
 PASSES=${3:-bench trace hbm sq mix}
 has() { [[ " $PASSES " == *" $1 "* ]]; }
 if has bench; then
-    python3 $REPO/bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+    python3 $REPO/bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
     echo "[profiles] default bench done"
 fi
 SQ1="SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_THREAD_CYCLES_VALU SQ_WAVES SQ_WAVE_CYCLES"
