@@ -623,9 +623,6 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   return ATMRT_OK;
 }
 
-static PackedHits carve_packed(void* base, size_t n);
-static size_t packed_bytes(size_t n);
-
 static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
   size_t npx = (size_t)f.wl * f.h;
   HIP_TRY(c, c->d_counters.reserve(N_COUNTERS * sizeof(uint64_t)));
@@ -662,8 +659,7 @@ static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
     if (f.p.generator == ATMRT_GEN_RECTILINEAR) HIP_TRY(c, c->d_slot_rec.reserve(4 * (size_t)RECT_SLOTS * npx * sizeof(double)));
     if (f.n_objects > 0) {
       HIP_TRY(c, c->d_slot_pixel.reserve((size_t)RECT_SLOTS * npx * sizeof(uint32_t)));
-      HIP_TRY(c, c->d_slot_packed.reserve(packed_bytes((size_t)RECT_SLOTS * npx)));
-      ws->slot_packed = carve_packed(c->d_slot_packed.ptr, (size_t)RECT_SLOTS * npx);
+      HIP_TRY(c, reserve_carved(c->d_slot_packed, [&](Carve& k) { ws->slot_packed = carve_packed(k, (size_t)RECT_SLOTS * npx); }));
     }
   }
   ws->slot_pixel = c->d_slot_pixel.as<uint32_t>();
@@ -716,10 +712,10 @@ static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
       return e ? atol(e) : -1L;
     }();
     ws->overflow_cap = forced_cap >= 0 ? (size_t)forced_cap : std::max<size_t>(65536, npx / 4);
-    const size_t rec_bytes = (overflow_arena_bytes(ws->overflow_cap) + 255) / 256 * 256;
-    HIP_TRY(c, c->d_overflow_arena.reserve(rec_bytes + (f.n_objects ? packed_bytes(ws->overflow_cap) : 0)));
-    ws->overflow_arena = c->d_overflow_arena.as<char>();
-    if (f.n_objects) ws->overflow_packed = carve_packed(ws->overflow_arena + rec_bytes, ws->overflow_cap);
+    HIP_TRY(c, reserve_carved(c->d_overflow_arena, [&](Carve& k) {
+      k(ws->overflow_arena, overflow_arena_bytes(ws->overflow_cap));
+      if (f.n_objects) ws->overflow_packed = carve_packed(k, ws->overflow_cap);
+    }));
   }
   ws->slice_state = nullptr;
   SliceLayout slices;
@@ -730,46 +726,11 @@ static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
   return ATMRT_OK;
 }
 
-static DensePlanes carve_dense(void* base, size_t npx) {
-  DensePlanes d;
-  char* p = static_cast<char*>(base);
-  auto take = [&](size_t bytes) {
-    void* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  d.azimuth = (double*)take(npx * 8);
-  d.elevation_angle = (double*)take(npx * 8);
-  d.lat = (double*)take(npx * 8);
-  d.lon = (double*)take(npx * 8);
-  d.distance = (double*)take(npx * 8);
-  d.elevation = (double*)take(npx * 8);
-  d.path_length = (double*)take(npx * 8);
-  d.normal = (double*)take(npx * 24);
-  d.hit_count = (uint32_t*)take(npx * 4);
-  return d;
+// The frame's counter block on the host, after everything enqueued on `s` so far.
+static hipError_t read_counters(const Workspace& ws, hipStream_t s, uint64_t (&cnt)[N_COUNTERS]) {
+  const hipError_t e = hipMemcpyAsync(cnt, ws.counters, sizeof cnt, hipMemcpyDeviceToHost, s);
+  return e == hipSuccess ? hipStreamSynchronize(s) : e;
 }
-static size_t dense_bytes(size_t npx) { return 10 * (npx * 8 + 256) + npx * 4 + 512; }
-
-static PackedHits carve_packed(void* base, size_t n) {
-  PackedHits h;
-  char* p = static_cast<char*>(base);
-  auto take = [&](size_t bytes) {
-    void* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  h.lat = (double*)take(n * 8);
-  h.lon = (double*)take(n * 8);
-  h.distance = (double*)take(n * 8);
-  h.elevation = (double*)take(n * 8);
-  h.path_length = (double*)take(n * 8);
-  h.normal = (double*)take(n * 24);
-  h.rgba = (double*)take(n * 32);
-  h.color_tag = (uint32_t*)take(n * 4);
-  return h;
-}
-static size_t packed_bytes(size_t n) { return n * (5 * 8 + 24 + 32 + 4) + 8 * 256 + 256; }
 
 // One frame of the Fast or Rectilinear generator into `dense` (device memory).  When `want_packed` (or whenever
 // a pixel can hold several trace points) the packed trace points are left in c->d_packed and their offsets in
@@ -785,10 +746,9 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
   if (fast && general) {
     launch_fast_caches(f, ws, s, c->stream2, c->ev_fork, c->ev_join, ev);
     launch_close_count(f, ws, s);
-    uint64_t cnt[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(cnt, ws.counters, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, c->d_clist.reserve((cnt[3] + 1) * sizeof(uint32_t)));
+    uint64_t cnt[N_COUNTERS];
+    HIP_TRY(c, read_counters(ws, s, cnt));
+    HIP_TRY(c, c->d_clist.reserve((cnt[CTR_CLOSE_TOTAL] + 1) * sizeof(uint32_t)));
     ws.clist = c->d_clist.as<uint32_t>();
     launch_close_fill(f, ws, s);
     HIP_TRY(c, hipEventRecord(ev[4], s));
@@ -800,14 +760,16 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     // lists them), then the tracer over that list
     HIP_TRY(c, c->d_object_rays.reserve((size_t)f.wl * f.h * sizeof(uint32_t)));
     ws.object_rays = c->d_object_rays.as<uint32_t>();
-    HIP_TRY(c, c->d_step_ctx.reserve((sizeof(Frame) + 255) / 256 * 256 + OBJECT_STEP_SINKS_MAX_BYTES));
-    ws.step_ctx = c->d_step_ctx.as<char>();
+    HIP_TRY(c, reserve_carved(c->d_step_ctx, [&](Carve& k) { // a copy of the Frame, then ObjectStepSinks (launch_rect_trace_count)
+      char* sinks;
+      k(ws.step_ctx, sizeof(Frame));
+      k(sinks, OBJECT_STEP_SINKS_MAX_BYTES);
+    }));
     HIP_TRY(c, hipEventRecord(ev[4], s));
     launch_trace_count(f, ws, dense, s);
-    uint64_t cnt[N_COUNTERS] = {};
-    HIP_TRY(c, hipMemcpyAsync(cnt, ws.counters, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    launch_rect_trace_objects(f, ws, dense, cnt[11], s);
+    uint64_t cnt[N_COUNTERS];
+    HIP_TRY(c, read_counters(ws, s, cnt));
+    launch_rect_trace_objects(f, ws, dense, cnt[CTR_OBJECT_RAYS], s);
     HIP_TRY(c, hipEventRecord(ev[5], s));
     HIP_TRY(c, hipEventRecord(ev[6], s));
   } else if (fast) {
@@ -823,17 +785,15 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
   HIP_TRY(c, hipEventRecord(ev[7], s));
   PackedHits packed{};
   if (want_packed || !f.opaque) {
-    uint64_t counters[N_COUNTERS] = {};
+    uint64_t counters[N_COUNTERS];
     launch_scan_counts(f, ws, dense.hit_count, s);
-    HIP_TRY(c, hipMemcpyAsync(counters, ws.counters, sizeof counters, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    uint64_t n_hits = counters[1];
-    if (counters[6]) { // some step produced more trace points than StepHits keeps: the fill pass sorts those in place by `prop`
+    HIP_TRY(c, read_counters(ws, s, counters));
+    uint64_t n_hits = counters[CTR_HITS];
+    if (counters[CTR_BIG_STEPS]) { // some step produced more trace points than StepHits keeps: the fill pass sorts those in place by `prop`
       HIP_TRY(c, c->d_step_prop.reserve((n_hits + 1) * sizeof(double)));
       ws.step_prop = c->d_step_prop.as<double>();
     }
-    HIP_TRY(c, c->d_packed.reserve(packed_bytes(n_hits)));
-    packed = carve_packed(c->d_packed.ptr, n_hits);
+    HIP_TRY(c, reserve_carved(c->d_packed, [&](Carve& k) { packed = carve_packed(k, n_hits); }));
     if (f.opaque) {
       launch_pack_first_hits(f, ws, dense, packed, s);
     } else {
@@ -846,11 +806,11 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
         ws.rect_rec = c->d_rect_rec.as<double>();
       }
       if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
-        ws.n_overflow = counters[3]; // pixels whose points did not fit the slots: marched a second time if the arena overflowed too
-        ws.n_overflow_records = counters[13];
+        ws.n_overflow = counters[CTR_OVERFLOW_PIXELS]; // pixels whose points did not fit the slots: marched a second time if the arena overflowed too
+        ws.n_overflow_records = counters[CTR_OVERFLOW_RECORDS];
         HIP_TRY(c, c->d_overflow.reserve((ws.n_overflow + 1) * sizeof(uint32_t)));
         ws.overflow = c->d_overflow.as<uint32_t>();
-        HIP_TRY(c, hipMemsetAsync(ws.counters + 3, 0, sizeof(uint64_t), s)); // now the gather kernel's list cursor
+        HIP_TRY(c, hipMemsetAsync(&ws.counters[CTR_OVERFLOW_CURSOR], 0, sizeof(uint64_t), s));
       }
       if (general) {
         launch_trace_fill(f, ws, n_hits, dense, packed, s);
@@ -876,28 +836,11 @@ static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const 
   hipStream_t s = c->stream;
   const size_t W = f.p.width, H = f.p.height, npx = (size_t)f.wl * f.h;
   // gen_fov_data :453-522
-  size_t bytes = 2 * W * H * 8 + (W + H) * 8 + npx * (4 + 4 + 8 + 8) + 64 + 4096;
-  HIP_TRY(c, c->d_interp.reserve(bytes));
   InterpBuffers ib{};
-  {
-    char* p = c->d_interp.as<char>();
-    auto take = [&](size_t b) {
-      void* r = p;
-      p += (b + 255) / 256 * 256;
-      return r;
-    };
-    HIP_TRY(c, c->d_interp.reserve(bytes + 16 * 256));
-    p = c->d_interp.as<char>();
-    ib.dir = (double*)take(W * H * 8);
-    ib.elev = (double*)take(W * H * 8);
-    ib.colmin = (double*)take(W * 8);
-    ib.rowmin = (double*)take(H * 8);
-    ib.rem_e = (double*)take(npx * 8);
-    ib.rem_d = (double*)take(npx * 8);
-    ib.key_e = (int32_t*)take(npx * 4);
-    ib.key_d = (int32_t*)take(npx * 4);
-    ib.bounds = (int32_t*)take(16);
-  }
+  HIP_TRY(c, reserve_carved(c->d_interp, [&](Carve& k) {
+    k(ib.dir, W * H * 8), k(ib.elev, W * H * 8), k(ib.colmin, W * 8), k(ib.rowmin, H * 8);
+    k(ib.rem_e, npx * 8), k(ib.rem_d, npx * 8), k(ib.key_e, npx * 4), k(ib.key_d, npx * 4), k(ib.bounds, 16);
+  }));
   launch_fov_table(f, ib, s);
   std::vector<double> mins(W + H);
   HIP_TRY(c, hipMemcpyAsync(mins.data(), ib.colmin, W * 8, hipMemcpyDeviceToHost, s));
@@ -943,8 +886,8 @@ static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const 
   wsl.px_steps = c->d_px_steps.as<uint32_t>();
   ib.referenced = reinterpret_cast<uint8_t*>(wsl.px_steps + nlat);
   HIP_TRY(c, hipMemsetAsync(ib.referenced, 0, nlat, s));
-  HIP_TRY(c, c->d_lat_dense.reserve(dense_bytes(nlat)));
-  DensePlanes ldense = carve_dense(c->d_lat_dense.ptr, nlat);
+  DensePlanes ldense;
+  HIP_TRY(c, reserve_carved(c->d_lat_dense, [&](Carve& k) { ldense = carve_dense(k, nlat); }));
   PackedHits lpacked{};
   uint64_t lhits = 0;
   if ((rc = run_core(c, fl, wsl, ldense, true, &lpacked, &lhits))) return rc;
@@ -961,39 +904,28 @@ static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const 
   lr.ne = (int32_t)ne;
   // blend: count -> scan -> fill
   if ((rc = prepare_workspace(c, f, &ws))) return rc;
-  HIP_TRY(c, hipMemsetAsync(ws.counters, 0, sizeof(uint64_t), s)); // ray-steps: only referenced lattice pixels count
+  HIP_TRY(c, hipMemsetAsync(&ws.counters[CTR_RAY_STEPS], 0, sizeof(uint64_t), s)); // only referenced lattice pixels count
   PackedHits none{};
   Frame fb = f;
   fb.di0 = fl.di0;
   fb.ei0 = fl.ei0;
   launch_interp_blend(fb, ws, ib, lr, false, dense, none, s);
   launch_scan_counts(f, ws, dense.hit_count, s);
-  uint64_t counters[N_COUNTERS] = {};
-  HIP_TRY(c, hipMemcpyAsync(counters, ws.counters, sizeof counters, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  uint64_t counters[N_COUNTERS];
+  HIP_TRY(c, read_counters(ws, s, counters));
   BlendArena arena{};
-  if (counters[7]) { // pixels whose four corners hold more points than the in-register member list: blended over an HBM arena
-    const size_t n = (size_t)counters[8];
-    HIP_TRY(c, c->d_blend_arena.reserve(n * (8 + 8 + 4 + 1 + 1) + 4 * 256));
-    char* a = c->d_blend_arena.as<char>();
-    auto take = [&](size_t b) {
-      void* r = a;
-      a += (b + 255) / 256 * 256;
-      return r;
-    };
-    arena.k = (uint64_t*)take(n * 8);
-    arena.dist = (double*)take(n * 8);
-    arena.group = (uint32_t*)take(n * 4);
-    arena.corner = (uint8_t*)take(n);
-    arena.tag = (uint8_t*)take(n);
+  if (counters[CTR_BIG_BLEND_PIXELS]) { // pixels whose four corners hold more points than the in-register member list: blended over an HBM arena
+    const size_t n = (size_t)counters[CTR_BIG_BLEND_POINTS];
+    HIP_TRY(c, reserve_carved(c->d_blend_arena, [&](Carve& k) {
+      k(arena.k, n * 8), k(arena.dist, n * 8), k(arena.group, n * 4), k(arena.corner, n), k(arena.tag, n);
+    }));
     launch_interp_blend_big(fb, ws, ib, lr, false, dense, none, arena, s);
     launch_scan_counts(f, ws, dense.hit_count, s); // again, now that every pixel has its count
-    HIP_TRY(c, hipMemcpyAsync(counters, ws.counters, sizeof counters, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, read_counters(ws, s, counters));
   }
-  uint64_t n_hits = counters[1];
-  HIP_TRY(c, c->d_packed.reserve(packed_bytes(n_hits)));
-  PackedHits packed = carve_packed(c->d_packed.ptr, n_hits);
+  uint64_t n_hits = counters[CTR_HITS];
+  PackedHits packed;
+  HIP_TRY(c, reserve_carved(c->d_packed, [&](Carve& k) { packed = carve_packed(k, n_hits); }));
   launch_interp_blend(fb, ws, ib, lr, true, dense, packed, s);
   if (arena.k) launch_interp_blend_big(fb, ws, ib, lr, true, dense, packed, arena, s);
   launch_interp_finish(f, ws, ib, lr, dense, packed, s);
@@ -1026,10 +958,9 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
     (void)hipStreamSynchronize(s);
     return c->fail(ATMRT_ERR_HIP, "failure injected by atmrt_debug_fail_next_frame");
   }
-  uint64_t counters[N_COUNTERS] = {};
+  uint64_t counters[N_COUNTERS];
   HIP_TRY(c, hipEventRecord(c->ev_t1, s));
-  HIP_TRY(c, hipMemcpyAsync(counters, ws.counters, sizeof counters, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, read_counters(ws, s, counters));
   HIP_TRY(c, hipGetLastError());
   float ms = 0.f;
   HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
@@ -1059,23 +990,23 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
     t.finalize_ms = v;
     HIP_TRY(c, hipEventElapsedTime(&v, ev[7], ev[8]));
     t.pack_ms = v;
-    t.ray_steps = counters[0];
-    t.n_hits = counters[1];
+    t.ray_steps = counters[CTR_RAY_STEPS];
+    t.n_hits = counters[CTR_HITS];
     c->timings = t;
   }
   (void)fast;
-  if (counters[12])
-    return c->fail(ATMRT_ERR_HIP, "the time-sliced march left %llu of its ray groups unfinished", (unsigned long long)counters[12] - 1);
-  c->stats.unlisted_rays = counters[4];
-  c->stats.unlisted_columns = counters[5];
-  c->stats.big_steps = counters[6];
-  c->stats.big_blend_pixels += counters[7];
+  if (counters[CTR_SLICE_UNFINISHED])
+    return c->fail(ATMRT_ERR_HIP, "the time-sliced march left %llu of its ray groups unfinished", (unsigned long long)counters[CTR_SLICE_UNFINISHED] - 1);
+  c->stats.unlisted_rays = counters[CTR_UNLISTED_RAYS];
+  c->stats.unlisted_columns = counters[CTR_UNLISTED_COLUMNS];
+  c->stats.big_steps = counters[CTR_BIG_STEPS];
+  c->stats.big_blend_pixels += counters[CTR_BIG_BLEND_PIXELS];
   c->stats.retraced_pixels += ws.n_overflow;
-  c->stats.terrain_lookups = counters[10];
-  c->stats.object_rays = counters[11];
-  c->stats.object_steps = counters[14];
+  c->stats.terrain_lookups = counters[CTR_TERRAIN_LOOKUPS];
+  c->stats.object_rays = counters[CTR_OBJECT_RAYS];
+  c->stats.object_steps = counters[CTR_OBJECT_STEPS];
   if (ms_out) *ms_out = ms;
-  if (ray_steps_out) *ray_steps_out = counters[0];
+  if (ray_steps_out) *ray_steps_out = counters[CTR_RAY_STEPS];
   if (packed_out) *packed_out = packed;
   c->last_valid = true;
   c->last_packed = want_packed || !f.opaque || f.p.generator == ATMRT_GEN_INTERPOLATING_RECTILINEAR;
@@ -1087,7 +1018,7 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   c->last_dense = dense;
   c->last_hits = packed;
   c->last_offset = ws.hit_offset;
-  c->last_nhits = c->last_packed ? counters[1] : 0;
+  c->last_nhits = c->last_packed ? counters[CTR_HITS] : 0;
   return ATMRT_OK;
 }
 
@@ -1151,31 +1082,19 @@ extern "C" int atmrt_internal_result_alloc(atmrt_result_t* out, uint32_t width, 
   memset(out, 0, sizeof *out);
   const size_t npx = (size_t)width * height;
   const size_t nh = n_hits ? n_hits : 1, np1 = npx ? npx : 1;
-  auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t total = 3 * pad(np1 * 8) + pad(np1 * 4) + 5 * pad(nh * 8) + pad(nh * 24) + pad(nh * 4) + pad(nh * 32);
-  char* base = static_cast<char*>(g_host_blocks.take(total));
-  if (!base) return -1;
-  auto carve = [&](size_t bytes) {
-    void* r = base;
-    base += pad(bytes);
-    return r;
+  auto layout = [&](Carve& k) { // azimuth first: atmrt_result_free returns the block by this pointer
+    k(out->azimuth, np1 * 8), k(out->elevation_angle, np1 * 8), k(out->hit_offset, np1 * 8), k(out->hit_count, np1 * 4);
+    packed_fields([&](size_t b, auto*& a) { k(a, nh * b); }, *out);
   };
+  Carve size(nullptr);
+  layout(size);
+  Carve block(g_host_blocks.take(size.bytes));
+  if (!block.base) return -1;
+  layout(block);
   out->width = width;
   out->height = height;
   out->n_pixels = npx;
   out->n_hits = n_hits;
-  out->azimuth = (double*)carve(np1 * 8); // first: atmrt_result_free returns the block by this pointer
-  out->elevation_angle = (double*)carve(np1 * 8);
-  out->hit_offset = (uint64_t*)carve(np1 * 8);
-  out->hit_count = (uint32_t*)carve(np1 * 4);
-  out->lat = (double*)carve(nh * 8);
-  out->lon = (double*)carve(nh * 8);
-  out->distance = (double*)carve(nh * 8);
-  out->elevation = (double*)carve(nh * 8);
-  out->path_length = (double*)carve(nh * 8);
-  out->normal = (double*)carve(nh * 24);
-  out->rgba = (double*)carve(nh * 32);
-  out->color_tag = (uint32_t*)carve(nh * 4);
   return 0;
 }
 
@@ -1197,9 +1116,7 @@ int atmrt::api_generate_tile(atmrt_ctx* c, const DensePlanes* dense_in, bool wan
   if (dense_in) {
     dense = *dense_in;
   } else {
-    const size_t npx = (size_t)f.wl * f.h;
-    HIP_TRY(c, c->d_dense.reserve(dense_bytes(npx)));
-    dense = carve_dense(c->d_dense.ptr, npx);
+    HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, (size_t)f.wl * f.h); }));
   }
   uint64_t nh = 0;
   rc = run_generator(c, f, ws, dense, want_packed, nullptr, &nh, ray_steps, device_ms);
@@ -1217,8 +1134,8 @@ extern "C" int atmrt_generate(atmrt_ctx* c, atmrt_result_t* out) {
   Workspace ws{};
   if ((rc = prepare_workspace(c, f, &ws))) return rc;
   size_t npx = (size_t)f.wl * f.h;
-  HIP_TRY(c, c->d_dense.reserve(dense_bytes(npx)));
-  DensePlanes dense = carve_dense(c->d_dense.ptr, npx);
+  DensePlanes dense;
+  HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, npx); }));
   PackedHits packed{};
   uint64_t n_hits = 0, steps = 0;
   double ms = 0;
@@ -1234,16 +1151,7 @@ extern "C" int atmrt_generate(atmrt_ctx* c, atmrt_result_t* out) {
   if (e == hipSuccess) e = d2h(out->elevation_angle, dense.elevation_angle, npx * 8);
   if (e == hipSuccess) e = d2h(out->hit_count, dense.hit_count, npx * 4);
   if (e == hipSuccess) e = d2h(out->hit_offset, ws.hit_offset, npx * 8);
-  if (n_hits) {
-    if (e == hipSuccess) e = d2h(out->lat, packed.lat, n_hits * 8);
-    if (e == hipSuccess) e = d2h(out->lon, packed.lon, n_hits * 8);
-    if (e == hipSuccess) e = d2h(out->distance, packed.distance, n_hits * 8);
-    if (e == hipSuccess) e = d2h(out->elevation, packed.elevation, n_hits * 8);
-    if (e == hipSuccess) e = d2h(out->path_length, packed.path_length, n_hits * 8);
-    if (e == hipSuccess) e = d2h(out->normal, packed.normal, n_hits * 24);
-    if (e == hipSuccess) e = d2h(out->color_tag, packed.color_tag, n_hits * 4);
-    if (e == hipSuccess) e = d2h(out->rgba, packed.rgba, n_hits * 32);
-  }
+  if (e == hipSuccess) e = copy_packed(*out, packed, n_hits, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     atmrt_result_free(out);
@@ -1256,24 +1164,13 @@ extern "C" int atmrt_generate_device(atmrt_ctx* c, const atmrt_device_planes_t* 
                                      double* device_ms) {
   if (!c || !planes) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context leaves its frame in HBM through atmrt_generate_image_device");
-  if (!planes->azimuth || !planes->elevation_angle || !planes->hit_count || !planes->lat || !planes->lon ||
-      !planes->distance || !planes->elevation || !planes->path_length || !planes->normal)
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every plane pointer must be a device allocation");
+  DensePlanes dense;
+  if (!planes_from_abi(*planes, &dense)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every plane pointer must be a device allocation");
   Frame f;
   int rc = prepare_frame(c, &f);
   if (rc) return rc;
   Workspace ws{};
   if ((rc = prepare_workspace(c, f, &ws))) return rc;
-  DensePlanes dense;
-  dense.azimuth = planes->azimuth;
-  dense.elevation_angle = planes->elevation_angle;
-  dense.hit_count = planes->hit_count;
-  dense.lat = planes->lat;
-  dense.lon = planes->lon;
-  dense.distance = planes->distance;
-  dense.elevation = planes->elevation;
-  dense.path_length = planes->path_length;
-  dense.normal = planes->normal;
   uint64_t n_hits = 0;
   return run_generator(c, f, ws, dense, false, nullptr, &n_hits, ray_steps, device_ms);
 }
@@ -1291,22 +1188,13 @@ extern "C" int atmrt_last_hits_device(atmrt_ctx* c, const atmrt_device_hits_t* d
   if (dst->capacity < n)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "capacity %llu is less than the %llu trace points of the frame",
                    (unsigned long long)dst->capacity, (unsigned long long)n);
-  if (!dst->hit_offset || !dst->lat || !dst->lon || !dst->distance || !dst->elevation || !dst->path_length || !dst->normal ||
-      !dst->color_tag || !dst->rgba)
+  PackedHits to;
+  if (!hits_from_abi(*dst, &to) || !dst->hit_offset)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every array pointer must be a device allocation");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const PackedHits& h = c->last_hits;
-  auto d2d = [&](void* to, const void* from, size_t bytes) { return bytes ? hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess; };
-  HIP_TRY(c, d2d(dst->hit_offset, c->last_offset, c->last_npx * 8));
-  HIP_TRY(c, d2d(dst->lat, h.lat, n * 8));
-  HIP_TRY(c, d2d(dst->lon, h.lon, n * 8));
-  HIP_TRY(c, d2d(dst->distance, h.distance, n * 8));
-  HIP_TRY(c, d2d(dst->elevation, h.elevation, n * 8));
-  HIP_TRY(c, d2d(dst->path_length, h.path_length, n * 8));
-  HIP_TRY(c, d2d(dst->normal, h.normal, n * 24));
-  HIP_TRY(c, d2d(dst->color_tag, h.color_tag, n * 4));
-  HIP_TRY(c, d2d(dst->rgba, h.rgba, n * 32));
+  if (c->last_npx) HIP_TRY(c, hipMemcpyAsync(dst->hit_offset, c->last_offset, c->last_npx * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(c, copy_packed(to, c->last_hits, n, hipMemcpyDeviceToDevice, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return ATMRT_OK;
 }

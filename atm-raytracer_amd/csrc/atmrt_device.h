@@ -255,7 +255,7 @@ static __device__ __forceinline__ void step_object(StepHits& sh, const Frame& f,
 }
 
 // ---- big steps: more trace points in one step than StepHits keeps ------------------------------------------------------------
-// Fill pass only (the counting pass counts them exactly and raises counters[6]; such a pixel always exceeds its slots, so it is
+// Fill pass only (the counting pass counts them exactly and raises CTR_BIG_STEPS; such a pixel always exceeds its slots, so it is
 // traced again by the fill pass).  The step's points are produced a second time, written straight to their pixel's range of the
 // output list in production order with their `prop` beside them (Workspace::step_prop), and stable-sorted there by prop —
 // the same order as the reference's `step_result.sort_by(prop)` over its push order (utils.rs:279).

@@ -74,26 +74,109 @@ struct PackedHits {
   double* rgba;   // [n][4]
 };
 
+// The arrays of DensePlanes in carving order, with the bytes of one pixel's entry: f(bytes, s.array...) for each, over any number
+// of structs that name them alike (atmrt_device_planes_t does).
+template <class F, class... S>
+ATMRT_HD void dense_fields(F&& f, S&... s) {
+  f(8, s.azimuth...), f(8, s.elevation_angle...), f(8, s.lat...), f(8, s.lon...), f(8, s.distance...), f(8, s.elevation...);
+  f(8, s.path_length...), f(24, s.normal...), f(4, s.hit_count...);
+}
+// The same for the arrays of PackedHits and one trace point's entry (atmrt_result_t and atmrt_device_hits_t name them alike).
+template <class F, class... S>
+ATMRT_HD void packed_fields(F&& f, S&... s) {
+  f(8, s.lat...), f(8, s.lon...), f(8, s.distance...), f(8, s.elevation...), f(8, s.path_length...), f(24, s.normal...);
+  f(32, s.rgba...), f(4, s.color_tag...);
+}
+
+// 256-byte-aligned bump allocation in one buffer: k(ptr, n) points `ptr` at the next free byte and moves on by n bytes rounded up
+// to 256.  Over a null base every pointer is null and `bytes` ends as the size of the layout: sizing and carving are one code.
+struct Carve {
+  char* base;
+  size_t bytes = 0;
+  ATMRT_HD static size_t pad(size_t n) { return (n + 255) / 256 * 256; }
+  ATMRT_HD Carve(void* b) : base(static_cast<char*>(b)) {}
+  template <class T>
+  ATMRT_HD void operator()(T*& ptr, size_t n) {
+    ptr = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+    bytes += pad(n);
+  }
+};
+// `buf` reserved for what layout(Carve&) carves, then carved by it
+template <class Buf, class Layout>
+hipError_t reserve_carved(Buf& buf, Layout&& layout) {
+  Carve size(nullptr);
+  layout(size);
+  const hipError_t e = buf.reserve(size.bytes);
+  if (e != hipSuccess) return e;
+  Carve k(buf.ptr);
+  layout(k);
+  return hipSuccess;
+}
+ATMRT_HD DensePlanes carve_dense(Carve& k, size_t npx) {
+  DensePlanes d;
+  dense_fields([&](size_t b, auto*& a) { k(a, npx * b); }, d);
+  return d;
+}
+ATMRT_HD PackedHits carve_packed(Carve& k, size_t n) {
+  PackedHits h;
+  packed_fields([&](size_t b, auto*& a) { k(a, n * b); }, h);
+  return h;
+}
+// The caller's device arrays as the library's views: false when one of them is missing.
+static inline bool planes_from_abi(const atmrt_device_planes_t& p, DensePlanes* d) {
+  bool all = true;
+  dense_fields([&](size_t, auto*& to, auto* from) { to = from, all = all && from; }, *d, p);
+  return all;
+}
+static inline bool hits_from_abi(const atmrt_device_hits_t& h, PackedHits* p) {
+  bool all = true;
+  packed_fields([&](size_t, auto*& to, auto* from) { to = from, all = all && from; }, *p, h);
+  return all;
+}
+// n entries of every array of `src` to the same array of `dst` (any struct with PackedHits' names), enqueued on `s`
+template <class D>
+hipError_t copy_packed(D& dst, const PackedHits& src, uint64_t n, hipMemcpyKind kind, hipStream_t s) {
+  hipError_t e = hipSuccess;
+  if (n) packed_fields([&](size_t b, auto* to, auto* from) { if (e == hipSuccess) e = hipMemcpyAsync(to, from, n * b, kind, s); }, dst, src);
+  return e;
+}
+
 // State of one row's path integration at a segment boundary (k_fast_paths runs in segments, see launch_fast_pipeline)
 struct PathSegState {
   double x, a, b, px, ph, path_length;
   int32_t hint, n, done, n_final;
 };
 
-// Device counters of a frame (Workspace::counters): [0] ray-steps, [1] total of the last scan (trace points), [2] error flags,
-// [3] scan total of the close lists / pixels that overflowed their slots / cursor of the overflow list, [4] rays whose candidate
-// list overflowed, [5] columns whose candidate list overflowed, [6] steps with more trace points than StepHits holds,
-// [7] InterpolatingRectilinear pixels with more corner points than the in-register member list, [8] their corner points
-// together (size of the member arena), [9] cursor of that arena, [10] terrain lookups performed by the Rectilinear march,
-// [11] rays of a scene with objects that the lean march left to the general tracer
-constexpr int N_COUNTERS = 16; // [14]: ray-steps handed to the lean march's out-of-line object step; [12]: groups the time-sliced march left unfinished (must be 0: atmrt_api.hip checks); [13]: records appended to the overflow arena
+// Device counters of a frame (Workspace::counters), by slot.  Slot 3 has three uses: in a Fast frame with objects, the scan total
+// of the close lists (launch_close_count; the host reads it at once); in a Rectilinear frame, first the pixels that overflowed
+// their slots (counted by the counting passes), then, reset by the host once it has read that count, the cursor of the list of
+// those pixels (the gather kernels append to it).
+enum Counter : int {
+  CTR_RAY_STEPS = 0,
+  CTR_HITS = 1, // total of the last launch_scan_counts: trace points of the frame
+  CTR_CLOSE_TOTAL = 3, // entries of the close lists
+  CTR_OVERFLOW_PIXELS = 3, // pixels with more trace points than RECT_SLOTS
+  CTR_OVERFLOW_CURSOR = 3, // cursor of the list of those pixels
+  CTR_UNLISTED_RAYS = 4, // rays whose candidate list overflowed
+  CTR_UNLISTED_COLUMNS = 5, // columns whose candidate list overflowed
+  CTR_BIG_STEPS = 6, // steps with more trace points than StepHits holds
+  CTR_BIG_BLEND_PIXELS = 7, // InterpolatingRectilinear pixels with more corner points than the in-register member list
+  CTR_BIG_BLEND_POINTS = 8, // their corner points together (size of the member arena)
+  CTR_BLEND_CURSOR = 9, // cursor of that arena
+  CTR_TERRAIN_LOOKUPS = 10, // terrain lookups performed by the Rectilinear march
+  CTR_OBJECT_RAYS = 11, // rays of a scene with objects that the lean march left to the general tracer
+  CTR_SLICE_UNFINISHED = 12, // groups the time-sliced march left unfinished, + 1 (must be 0: atmrt_api.hip checks)
+  CTR_OVERFLOW_RECORDS = 13, // records appended to the overflow arena
+  CTR_OBJECT_STEPS = 14, // ray-steps handed to the lean march's out-of-line object step
+};
+constexpr int N_COUNTERS = 16;
 
 // Scratch owned by the context, sized for the current frame.
 // crossings per pixel recorded by the counting march (4096x2048 headline at terrain_alpha 0.5: 99.3 % of the pixels have <= 4)
 constexpr int RECT_SLOTS = 4;
 
 // Trace points beyond a pixel's RECT_SLOTS slots (translucent terrain, scenes with objects): appended by the counting passes in any
-// order, each with its pixel and its ordinal among the pixel's trace points; counters[13] = records appended (more than `cap`: the
+// order, each with its pixel and its ordinal among the pixel's trace points; CTR_OVERFLOW_RECORDS counts them (more than `cap`: the
 // arena is not used and the overflowing pixels are marched / traced a second time, as before round 3).  44 B per record, + a
 // PackedHits entry (100 B) in scenes with objects, where a record is a complete object point or a terrain record with its tag.
 // `lean_source`: set in the records of the lean march of an object scene — those of a ray the march later hands to the general
@@ -187,7 +270,7 @@ struct Workspace {
   int32_t* hit_step;      // [h][wl] first hit: index of the older sample of the pair, or -1
   uint64_t* hit_offset;   // [h][wl] exclusive scan of hit_count
   uint64_t* scan_tmp;     // block sums for the scan
-  uint64_t* counters;     // [0] ray-steps, [1] total hits
+  uint64_t* counters;     // [N_COUNTERS], indexed by Counter
   uint32_t* list_step;    // multi-hit: per trace point, the step index and ...
   uint32_t* list_pixel;   // ... its pixel
   double* rect_rec;       // Rectilinear: [4][n] ray elevation / path length at the two bracketing samples
@@ -198,7 +281,7 @@ struct Workspace {
   uint32_t* overflow;     // pixels with more than RECT_SLOTS crossings
   uint32_t* slot_pixel;   // scenes with objects: [h][wl][RECT_SLOTS] (written by step_emit, not read)
   PackedHits slot_packed; // scenes with objects: trace points of the slots, entry p * RECT_SLOTS + j
-  uint64_t n_overflow;    // their number (host copy of counters[3] after the counting march)
+  uint64_t n_overflow;    // their number (host copy of CTR_OVERFLOW_PIXELS after the counting march)
   // scenes with objects (Fast): geodesic point of every sample and the objects close to it (utils.rs:74-80)
   double* plat;           // [n_t][wl]
   double* plon;           // [n_t][wl]
@@ -217,7 +300,7 @@ struct Workspace {
   char* overflow_arena;   // Rectilinear, translucent terrain or objects: trace points beyond the slots (OverflowArena), or null
   PackedHits overflow_packed; // scenes with objects: the arena's complete points
   size_t overflow_cap;    // its capacity in records
-  uint64_t n_overflow_records; // host copy of counters[13] after the counting march
+  uint64_t n_overflow_records; // host copy of CTR_OVERFLOW_RECORDS after the counting march
   char* slice_state;      // time-sliced march (march_slice_layout): ray state between two slices + the FIFO of groups, or null
 };
 
@@ -265,6 +348,7 @@ void launch_resolve(const Frame& f, Workspace& ws, ObjectDev* objects_mut, hipSt
 void launch_fast_profile_ll(const Frame& f, Workspace& ws, hipStream_t stream);
 void launch_close_count(const Frame& f, Workspace& ws, hipStream_t stream);
 void launch_close_fill(const Frame& f, Workspace& ws, hipStream_t stream);
+// exclusive scan of in[0, n) into out; the grand total into *total (and nothing else)
 void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* tmp, uint64_t* out, unsigned long long* total, hipStream_t stream);
 void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_trace_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,

@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void k_fast_intersect(Frame f, const double* _
     }
   }
   steps = wave_sum(steps); // one atomic per wavefront: 16 K of them at the headline size, spread over the kernel's 2 ms
-  if (lane == 0 && steps) atomicAdd(&counters[0], steps);
+  if (lane == 0 && steps) atomicAdd(&counters[CTR_RAY_STEPS], steps);
 }
 
 // The two samples that bracket step s of pixel (x, y), from the caches
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(64) void k_column_candidates(Frame f, const DirCalc
   int n = 0;
   const bool ok = ray_candidates<CALC, COL_CAND>(f, f.earth, colcalc[x], cand, n, lo, hi);
   ncand[x] = ok ? n : -1;
-  if (!ok && n == COL_CAND) atomicAdd(&counters[5], 1ull); // statistics only (atmrt_last_stats)
+  if (!ok && n == COL_CAND) atomicAdd(&counters[CTR_UNLISTED_COLUMNS], 1ull); // statistics only (atmrt_last_stats)
   if (ok)
     for (int q = 0; q < n; q++) {
       ccand[(size_t)x * COL_CAND + q] = cand[q];
@@ -650,7 +650,7 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
         const double d0 = i == 1 ? 0.0 : f.xs[i - 1], pl0 = i == 1 ? 0.0 : plen_t[(size_t)(i - 1) * hh + y];
         if (!FILL) {
           k = (uint64_t)p * RECT_SLOTS + count;
-          if (sh.n > STEP_CANDIDATES) atomicAdd(&counters[6], 1ull); // the fill pass will need Workspace::step_prop
+          if (sh.n > STEP_CANDIDATES) atomicAdd(&counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
         }
         if (FILL && sh.n > STEP_CANDIDATES) { // big step: produce the points again, straight into the list, and sort them there
           const StepGeom g{lat0, lon0, re0, d0, pl0, lat1, lon1, re1, f.xs[i], plen_t[(size_t)i * hh + y]};
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
   }
   if (!FILL) {
     unsigned long long steps = wave_sum((unsigned long long)(row_ok && mine ? stp : 0u));
-    if (lane == 0 && steps) atomicAdd(&counters[0], steps);
+    if (lane == 0 && steps) atomicAdd(&counters[CTR_RAY_STEPS], steps);
   }
 }
 
@@ -749,7 +749,7 @@ __global__ __launch_bounds__(256) void k_scan_block_sums(const uint32_t* __restr
   if (threadIdx.x == 0) block_sums[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 __global__ __launch_bounds__(256) void k_scan_sums(uint64_t* __restrict__ block_sums, size_t n_blocks,
-                                                   unsigned long long* __restrict__ counters) {
+                                                   unsigned long long* __restrict__ total) {
   __shared__ unsigned long long sh[256];
   size_t per = (n_blocks + 255) / 256;
   size_t b0 = (size_t)threadIdx.x * per, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
@@ -769,7 +769,7 @@ __global__ __launch_bounds__(256) void k_scan_sums(uint64_t* __restrict__ block_
     block_sums[b] = run;
     run += t;
   }
-  if (threadIdx.x == 255) counters[1] = sh[255];
+  if (threadIdx.x == 255) *total = sh[255];
 }
 __global__ __launch_bounds__(256) void k_scan_apply(const uint32_t* __restrict__ in, size_t n,
                                                     const uint64_t* __restrict__ block_sums,
@@ -1125,8 +1125,8 @@ __global__ __launch_bounds__(256) void k_interp_blend(Frame f, InterpBuffers ib,
                      a3 * rem_elev * rem_dir;
   }
   if (!FILL && CAP == 4 && total > (uint32_t)INTERP_MEMBERS) { // k_interp_blend_big's pixel: size its member arena
-    atomicAdd(&counters[7], 1ull);
-    atomicAdd(&counters[8], (unsigned long long)total);
+    atomicAdd(&counters[CTR_BIG_BLEND_PIXELS], 1ull);
+    atomicAdd(&counters[CTR_BIG_BLEND_POINTS], (unsigned long long)total);
   }
   if (CAP == 4 ? total > 4u : (total <= 4u || total > (uint32_t)INTERP_MEMBERS)) return; // another instance's pixel
   uint64_t member_k[CAP];
@@ -1155,7 +1155,7 @@ __global__ __launch_bounds__(256) void k_interp_blend_big(Frame f, InterpBuffers
     total += lr.hit_count[corner[s]];
   }
   if (total <= (uint32_t)INTERP_MEMBERS) return;
-  const unsigned long long base = atomicAdd(&counters[9], (unsigned long long)total);
+  const unsigned long long base = atomicAdd(&counters[CTR_BLEND_CURSOR], (unsigned long long)total);
   const unsigned count = blend_members<FILL>(lr, corner, ib.rem_e[p], ib.rem_d[p], f.p.simulation_step, arena.k + base, arena.dist + base,
                                              arena.corner + base, arena.tag + base, arena.group + base, FILL ? hit_offset[p] : 0, packed);
   if (!FILL) out.hit_count[p] = count;
@@ -1176,7 +1176,7 @@ __global__ __launch_bounds__(256) void k_lattice_steps(size_t n, const uint8_t* 
   __syncthreads();
   if (threadIdx.x == 0) {
     v = sh[0] + sh[1] + sh[2] + sh[3];
-    if (v) atomicAdd(&counters[0], v);
+    if (v) atomicAdd(&counters[CTR_RAY_STEPS], v);
   }
 }
 
@@ -1211,7 +1211,7 @@ void launch_interp_blend(const Frame& f, Workspace& ws, const InterpBuffers& ib,
 void launch_interp_blend_big(const Frame& f, Workspace& ws, const InterpBuffers& ib, const LatticeResult& lr, bool fill,
                              const DensePlanes& dense, const PackedHits& packed, const BlendArena& arena, hipStream_t stream) {
   dim3 grid(cdiv(f.wl, 256), f.h);
-  (void)hipMemsetAsync(ws.counters + 9, 0, sizeof(uint64_t), stream); // the arena cursor
+  (void)hipMemsetAsync(&ws.counters[CTR_BLEND_CURSOR], 0, sizeof(uint64_t), stream);
   if (fill)
     hipLaunchKernelGGL((k_interp_blend_big<true>), grid, dim3(256), 0, stream, f, ib, lr, dense, ws.hit_offset, packed, arena,
                        (unsigned long long*)ws.counters);
@@ -1494,7 +1494,7 @@ void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* tmp, uint64_t* out,
 }
 
 void launch_scan_counts(const Frame& f, Workspace& ws, const uint32_t* hit_count, hipStream_t stream) {
-  launch_scan_u32(hit_count, (size_t)f.wl * f.h, ws.scan_tmp, ws.hit_offset, (unsigned long long*)ws.counters, stream);
+  launch_scan_u32(hit_count, (size_t)f.wl * f.h, ws.scan_tmp, ws.hit_offset, (unsigned long long*)&ws.counters[CTR_HITS], stream);
 }
 
 void launch_close_count(const Frame& f, Workspace& ws, hipStream_t stream) {
@@ -1504,8 +1504,7 @@ void launch_close_count(const Frame& f, Workspace& ws, hipStream_t stream) {
                                                         (unsigned long long*)ws.counters));
   hipLaunchKernelGGL((k_close_objects<false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, f, ws.plat, ws.plon, ws.col_cand,
                      ws.col_ncand, ws.ccount, (const uint64_t*)nullptr, (uint32_t*)nullptr);
-  // total number of list entries -> counters[3]
-  launch_scan_u32(ws.ccount, n, ws.scan_tmp, ws.coffset, (unsigned long long*)ws.counters + 2, stream);
+  launch_scan_u32(ws.ccount, n, ws.scan_tmp, ws.coffset, (unsigned long long*)&ws.counters[CTR_CLOSE_TOTAL], stream);
 }
 
 void launch_close_fill(const Frame& f, Workspace& ws, hipStream_t stream) {

@@ -101,7 +101,7 @@ constexpr unsigned drain_max_blocks() {
 static __device__ __forceinline__ void overflow_append(const OverflowArena& ovf, unsigned long long* counters, uint32_t p, unsigned ordinal,
                                                        uint32_t step, double re0, double pl0, double re1, double pl1) {
   if (!ovf.cap) return;
-  const unsigned long long k = atomicAdd(&counters[13], 1ull);
+  const unsigned long long k = atomicAdd(&counters[CTR_OVERFLOW_RECORDS], 1ull);
   if (k < ovf.cap) {
     ovf.pixel[k] = p;
     ovf.ordinal[k] = ovf.color_tag ? ordinal | OVERFLOW_LEAN : ordinal;
@@ -173,7 +173,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
   // emission: the counting pass of the general tracer (k_rect_trace<false>)
   const unsigned count = io->count;
   const uint32_t p = io->pixel;
-  if (hits.n > STEP_CANDIDATES) atomicAdd(&sk->counters[6], 1ull); // the fill pass will need Workspace::step_prop
+  if (hits.n > STEP_CANDIDATES) atomicAdd(&sk->counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
   if (hits.n && count + (unsigned)hits.n <= (unsigned)RECT_SLOTS) {
     uint64_t k = (uint64_t)p * RECT_SLOTS + count;
     const uint64_t k0 = k;
@@ -185,7 +185,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
       sk->slots.pl1[q] = path_length;
     }
   } else if (hits.n && hits.n <= STEP_CANDIDATES && sk->ovf.cap) { // beyond the slots: the step's points into the overflow arena
-    const unsigned long long base = atomicAdd(&sk->counters[13], (unsigned long long)hits.n);
+    const unsigned long long base = atomicAdd(&sk->counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
     if (base + (unsigned long long)hits.n <= sk->ovf.cap) {
       uint64_t kk = base;
       step_emit(hits, sk->ovf_packed, sk->ovf.step, sk->ovf.pixel, kk, p, io->step_index, lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length);
@@ -198,7 +198,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
       }
     }
   }
-  atomicAdd(&sk->counters[14], 1ull); // statistics (atmrt_last_stats().object_steps)
+  atomicAdd(&sk->counters[CTR_OBJECT_STEPS], 1ull); // statistics (atmrt_last_stats().object_steps)
   io->count = count + (unsigned)hits.n;
   io->finish = hits.finish ? 1 : 0;
   io->diff1 = diff2;
@@ -436,14 +436,14 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
       out.hit_count[p] = count;
     }
     if (MODE == 0) hit_step[p] = first;
-    if ((MODE == 1 || (MODE == 3 && !object_ray)) && count > (unsigned)RECT_SLOTS) atomicAdd(&counters[3], 1ull);
+    if ((MODE == 1 || (MODE == 3 && !object_ray)) && count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
   }
   if (MODE != 2) {
     steps = wave_sum(steps);
     lookups = wave_sum(lookups);
     if ((threadIdx.x & 63) == 0 && steps) {
-      atomicAdd(&counters[0], steps);
-      atomicAdd(&counters[10], lookups);
+      atomicAdd(&counters[CTR_RAY_STEPS], steps);
+      atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
     }
   }
 #ifdef ATMRT_TIMELINE
@@ -645,7 +645,7 @@ static __device__ __forceinline__ void slice_finish(const DensePlanes& out, cons
   } else {
     out.hit_count[p] = count;
     if (MODE == 3) sinks.hit_step[p] = 0; // the ray stayed with the march: its overflow records count (k_rect_scatter_trace_overflow)
-    if (count > (unsigned)RECT_SLOTS) atomicAdd(&counters[3], 1ull);
+    if (count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
   }
 }
 
@@ -796,8 +796,8 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
   }
 #endif
   if ((threadIdx.x & 63) == 0 && steps) {
-    atomicAdd(&counters[0], steps);
-    atomicAdd(&counters[10], lookups);
+    atomicAdd(&counters[CTR_RAY_STEPS], steps);
+    atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
   }
 }
 
@@ -926,14 +926,14 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
   steps = wave_sum(steps);
   lookups = wave_sum(lookups);
   if (lane == 0 && steps) {
-    atomicAdd(&counters[0], steps);
-    atomicAdd(&counters[10], lookups);
+    atomicAdd(&counters[CTR_RAY_STEPS], steps);
+    atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
   }
 }
 
-// every group must have finished: anything else is reported through counters[12] and fails the frame (atmrt_api.hip)
+// every group must have finished: anything else is reported through CTR_SLICE_UNFINISHED and fails the frame (atmrt_api.hip)
 static __global__ void k_slice_check(const unsigned long long* __restrict__ ctl, uint32_t n_groups, unsigned long long* __restrict__ counters) {
-  counters[12] = ctl[2] == n_groups ? 0ull : 1ull + (n_groups > ctl[2] ? n_groups - ctl[2] : ctl[2] - n_groups);
+  counters[CTR_SLICE_UNFINISHED] = ctl[2] == n_groups ? 0ull : 1ull + (n_groups > ctl[2] ? n_groups - ctl[2] : ctl[2] - n_groups);
 }
 
 // TracePoint of a recorded crossing of pixel (x, y) at step s
@@ -1057,7 +1057,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
       // candidates, or a DirectionalCalc without the pre-filter) test every object against both samples of a step.
       // x_wake: the first stepper distance at which any candidate can be close — before it the proximity filter is skipped.
       const bool use_cand = ray_candidates<CALC, CAND_CAP>(f, e, c, cand, ncand, clo, chi);
-      if (!FILL && !use_cand && ncand == CAND_CAP) atomicAdd(&counters[4], 1ull); // statistics only (atmrt_last_stats)
+      if (!FILL && !use_cand && ncand == CAND_CAP) atomicAdd(&counters[CTR_UNLISTED_RAYS], 1ull); // statistics only (atmrt_last_stats)
       unsigned m0 = use_cand ? close_mask(f, e, lat0, lon0, cand, ncand) : 0u, m1 = 0u;
       double x_wake = dm_inf();
       for (int q = 0; q < ncand; q++)
@@ -1149,7 +1149,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
         if (any_object) for_each_object([&](int j) { step_object(hits, f, j, pos1, pos2); });
         if (!FILL) {
           k = (uint64_t)p * RECT_SLOTS + count;
-          if (hits.n > STEP_CANDIDATES) atomicAdd(&counters[6], 1ull); // the fill pass will need Workspace::step_prop
+          if (hits.n > STEP_CANDIDATES) atomicAdd(&counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
         }
         if (FILL && hits.n > STEP_CANDIDATES) { // big step: produce the points again, straight into the list, and sort them there
           const StepGeom g{lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx, path_length};
@@ -1177,7 +1177,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
           }
         }
         else if (!FILL && hits.n && hits.n <= STEP_CANDIDATES && ovf.cap) { // beyond the slots: the step's points into the overflow arena
-          const unsigned long long base = atomicAdd(&counters[13], (unsigned long long)hits.n);
+          const unsigned long long base = atomicAdd(&counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
           if (base + (unsigned long long)hits.n <= ovf.cap) {
             uint64_t kk = base;
             step_emit(hits, ovf_packed, ovf.step, ovf.pixel, kk, (uint32_t)p, i - 1, lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx,
@@ -1202,12 +1202,12 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
       out.azimuth[p] = dm_to_degrees(direction);
       out.elevation_angle[p] = dm_to_degrees(elevation);
       out.hit_count[p] = count;
-      if (count > (unsigned)RECT_SLOTS) atomicAdd(&counters[3], 1ull);
+      if (count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
     }
   }
   if (!FILL) {
     steps = wave_sum(steps);
-    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(&counters[0], steps);
+    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(&counters[CTR_RAY_STEPS], steps);
   }
 }
 
@@ -1241,7 +1241,7 @@ static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DenseP
   st.ctl = (unsigned long long*)q; q += 64;
   st.queue = (uint32_t*)q;
   st.cap = (uint32_t)L.cap;
-  st.glist = f.n_objects ? (char*)(((uintptr_t)(st.queue + L.cap) + 255) / 256 * 256) : nullptr;
+  st.glist = f.n_objects ? ws.slice_state + Carve::pad((size_t)((char*)(st.queue + L.cap) - ws.slice_state)) : nullptr;
   (void)hipMemsetAsync(st.ctl, 0, 64, stream);
   ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_first<MODE, CALC, CUBIC>), dim3(cdiv(n, 256)), dim3(256), 0, stream, f,
                                                         out, sinks, (unsigned long long*)ws.counters, st, L.n_groups, slice, frame_dev, sinks_dev));
@@ -1287,7 +1287,7 @@ void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, 
 }
 
 // The crossings the counting march kept in its slots, moved to their places in the pixel-ordered list; pixels with more
-// crossings than slots are collected for a second march (counters[3] was reset by the host and hands out list positions).
+// crossings than slots are collected for a second march (CTR_OVERFLOW_CURSOR was reset by the host and hands out list positions).
 static __global__ __launch_bounds__(256) void k_rect_gather_slots(Frame f, const uint32_t* __restrict__ hit_count,
                                                            const uint64_t* __restrict__ hit_offset,
                                                            const uint32_t* __restrict__ slot_step, RectRec slots,
@@ -1300,7 +1300,7 @@ static __global__ __launch_bounds__(256) void k_rect_gather_slots(Frame f, const
   if (arena) { // the crossings beyond the slots are in the overflow arena (k_rect_scatter_overflow): the slots of every pixel count
     n = n < (uint32_t)RECT_SLOTS ? n : (uint32_t)RECT_SLOTS;
   } else {
-    wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[3]); // the pixels the second march visits
+    wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[CTR_OVERFLOW_CURSOR]); // the pixels the second march visits
     if (n > (uint32_t)RECT_SLOTS) return;
   }
   if (p >= plane) return;
@@ -1364,11 +1364,11 @@ void launch_multi_fill_t(const Frame& f, Workspace& ws, uint64_t n_hits, const D
 }
 
 
-// the rays k_rect_march<3> left to the tracer, collected into a list (order irrelevant: every ray is independent); counters[11] = their number
+// the rays k_rect_march<3> left to the tracer, collected into a list (order irrelevant: every ray is independent); CTR_OBJECT_RAYS counts them
 static __global__ __launch_bounds__(256) void k_collect_object_rays(size_t n, const uint32_t* __restrict__ hit_count,
                                                                     uint32_t* __restrict__ list, unsigned long long* __restrict__ counters) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  wave_compact_append(p < n && hit_count[p] == OBJECT_RAY, (uint32_t)p, list, &counters[11]); // the rays the general tracer visits
+  wave_compact_append(p < n && hit_count[p] == OBJECT_RAY, (uint32_t)p, list, &counters[CTR_OBJECT_RAYS]); // the rays the general tracer visits
 }
 
 // the overflow arena of a scene with objects: records + complete points
@@ -1393,10 +1393,13 @@ void launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes&
   sinks.ovf = trace_overflow_arena(ws);
   sinks.ovf_packed = ws.overflow_packed;
   sinks.counters = (unsigned long long*)ws.counters;
-  const Frame* frame_dev = reinterpret_cast<const Frame*>(ws.step_ctx);
-  const ObjectStepSinks* sinks_dev = reinterpret_cast<const ObjectStepSinks*>(ws.step_ctx + (sizeof(Frame) + 255) / 256 * 256);
-  (void)hipMemcpyAsync(ws.step_ctx, &f, sizeof f, hipMemcpyHostToDevice, stream);
-  (void)hipMemcpyAsync(const_cast<ObjectStepSinks*>(sinks_dev), &sinks, sizeof sinks, hipMemcpyHostToDevice, stream);
+  Frame* frame_dev;
+  ObjectStepSinks* sinks_dev;
+  Carve ctx(ws.step_ctx); // the layout run_core reserves
+  ctx(frame_dev, sizeof(Frame));
+  ctx(sinks_dev, OBJECT_STEP_SINKS_MAX_BYTES);
+  (void)hipMemcpyAsync(frame_dev, &f, sizeof f, hipMemcpyHostToDevice, stream);
+  (void)hipMemcpyAsync(sinks_dev, &sinks, sizeof sinks, hipMemcpyHostToDevice, stream);
   (void)hipStreamSynchronize(stream); // both sources are on this stack frame
   // a small launch (a column tile): the time-sliced march, its groups carrying their candidate lists; else the whole grid at once
   if (!launch_rect_march_sliced<3, CUBIC>(f, ws, out, SliceSinks{ws.hit_step, slots, ws.slot_step, trace_overflow_arena(ws), ws.slot_packed.color_tag},
@@ -1436,7 +1439,7 @@ static __global__ __launch_bounds__(256) void k_rect_gather_trace_slots(Frame f,
     // a step whose points did not all fit went to the arena whole — k_rect_scatter_trace_overflow, which runs next, overwrites them.)
     n = n < (uint32_t)RECT_SLOTS ? n : (uint32_t)RECT_SLOTS;
   } else {
-    wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[3]); // the pixels the tracer's fill pass visits
+    wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[CTR_OVERFLOW_CURSOR]); // the pixels the tracer's fill pass visits
     if (n > (uint32_t)RECT_SLOTS) return;
   }
   if (p >= plane) return;

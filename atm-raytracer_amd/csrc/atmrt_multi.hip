@@ -110,10 +110,6 @@ struct HostBuf {
   ~HostBuf() { release(); }
 };
 
-constexpr int N_F64_PLANES = 10; // azimuth, elevation_angle, lat, lon, distance, elevation, path_length, normal x / y / z
-
-size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -375,10 +371,10 @@ __device__ __forceinline__ int tile_of_column(int x, const int* __restrict__ col
   return lo;
 }
 
-// gathered: [G] slabs of `slab_bytes`; the slab of tile g is exactly what the generators write for a tile of H x wl_g pixels: 10 f64
-// planes [H][wl_g] back to back (the planar normal is the last three) and the u32 hit_count plane.  One thread per image pixel,
-// lanes = adjacent columns: reads and writes are coalesced inside a tile.
-__global__ __launch_bounds__(256) void k_assemble_image(const char* __restrict__ gathered, size_t slab_bytes, int W, int H, int G,
+// gathered: [G] slabs of `slab_bytes`; the slab of tile g is exactly what the generators write for a tile of H x wl_g pixels: the
+// planes of carve_dense (the normal planar [3][H][wl_g]).  One thread per image pixel, lanes = adjacent columns: reads and writes
+// are coalesced inside a tile.
+__global__ __launch_bounds__(256) void k_assemble_image(char* __restrict__ gathered, size_t slab_bytes, int W, int H, int G,
                                                          const int* __restrict__ cols, DensePlanes image) {
   const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
   const size_t npx = (size_t)W * H;
@@ -387,18 +383,11 @@ __global__ __launch_bounds__(256) void k_assemble_image(const char* __restrict__
   const int g = tile_of_column(x, cols, G);
   const int c0 = cols[g], wl = cols[g + 1] - c0;
   const size_t si = (size_t)y * wl + (size_t)(x - c0), plane_stride = (size_t)H * wl;
-  const double* src = reinterpret_cast<const double*>(gathered + (size_t)g * slab_bytes);
-  image.azimuth[p] = src[0 * plane_stride + si];
-  image.elevation_angle[p] = src[1 * plane_stride + si];
-  image.lat[p] = src[2 * plane_stride + si];
-  image.lon[p] = src[3 * plane_stride + si];
-  image.distance[p] = src[4 * plane_stride + si];
-  image.elevation[p] = src[5 * plane_stride + si];
-  image.path_length[p] = src[6 * plane_stride + si];
-  image.normal[p] = src[7 * plane_stride + si];
-  image.normal[npx + p] = src[8 * plane_stride + si];
-  image.normal[2 * npx + p] = src[9 * plane_stride + si];
-  image.hit_count[p] = reinterpret_cast<const uint32_t*>(src + N_F64_PLANES * plane_stride)[si];
+  Carve slab(gathered + (size_t)g * slab_bytes);
+  DensePlanes src = carve_dense(slab, plane_stride);
+  dense_fields([&](size_t b, auto* to, auto* from) {
+    for (size_t k = 0; k < b / sizeof *to; k++) to[k * npx + p] = from[k * plane_stride + si];
+  }, image, src);
 }
 
 __global__ __launch_bounds__(256) void k_assemble_rgb(const uint8_t* __restrict__ gathered, size_t tile_bytes, int W, int H, int G,
@@ -414,15 +403,9 @@ __global__ __launch_bounds__(256) void k_assemble_rgb(const uint8_t* __restrict_
   rgb[3 * p + 2] = s[2];
 }
 
-// The packed lists of one rank, laid out for a capacity of n entries (the largest rank's count): what is all-gathered.
-struct HitBlock {
-  __host__ __device__ static size_t bytes(size_t n) { return (n * (12 * 8 + 4) + 255) / 256 * 256; }
-  __host__ __device__ static size_t off_f64(int field, size_t n) { return (size_t)field * n * 8; } // lat 0 lon 1 distance 2 elevation 3 path_length 4 normal 5 rgba 8
-  __host__ __device__ static size_t off_tag(size_t n) { return 12 * n * 8; }
-};
-
-// One thread per image pixel: its trace points move from its rank's block (at the rank's own offsets) to the image's offsets.
-__global__ __launch_bounds__(256) void k_gather_hits(const char* __restrict__ blocks, size_t block_bytes, size_t n_cap,
+// One thread per image pixel: its trace points move from its rank's block (carve_packed for n_cap entries, the largest rank's
+// count) at the rank's own offsets to the image's offsets.
+__global__ __launch_bounds__(256) void k_gather_hits(char* __restrict__ blocks, size_t block_bytes, size_t n_cap,
                                                       const uint64_t* __restrict__ loc_off, size_t off_stride, int W, int H, int G,
                                                       const int* __restrict__ cols, const uint32_t* __restrict__ hit_count,
                                                       const uint64_t* __restrict__ img_off, PackedHits out) {
@@ -435,25 +418,14 @@ __global__ __launch_bounds__(256) void k_gather_hits(const char* __restrict__ bl
   const int c0 = cols[g], wl = cols[g + 1] - c0;
   const uint64_t s0 = loc_off[(size_t)g * off_stride + (size_t)y * wl + (size_t)(x - c0)];
   const uint64_t d0 = img_off[p];
-  const char* blk = blocks + (size_t)g * block_bytes;
-  const double* lat = reinterpret_cast<const double*>(blk + HitBlock::off_f64(0, n_cap));
-  const double* lon = reinterpret_cast<const double*>(blk + HitBlock::off_f64(1, n_cap));
-  const double* dist = reinterpret_cast<const double*>(blk + HitBlock::off_f64(2, n_cap));
-  const double* elev = reinterpret_cast<const double*>(blk + HitBlock::off_f64(3, n_cap));
-  const double* plen = reinterpret_cast<const double*>(blk + HitBlock::off_f64(4, n_cap));
-  const double* nrm = reinterpret_cast<const double*>(blk + HitBlock::off_f64(5, n_cap));
-  const double* rgba = reinterpret_cast<const double*>(blk + HitBlock::off_f64(8, n_cap));
-  const uint32_t* tag = reinterpret_cast<const uint32_t*>(blk + HitBlock::off_tag(n_cap));
+  Carve blk(blocks + (size_t)g * block_bytes);
+  const PackedHits src = carve_packed(blk, n_cap);
   for (uint32_t j = 0; j < cnt; j++) {
     const uint64_t s = s0 + j, d = d0 + j;
-    out.lat[d] = lat[s];
-    out.lon[d] = lon[s];
-    out.distance[d] = dist[s];
-    out.elevation[d] = elev[s];
-    out.path_length[d] = plen[s];
-    for (int k = 0; k < 3; k++) out.normal[3 * d + k] = nrm[3 * s + k];
-    for (int k = 0; k < 4; k++) out.rgba[4 * d + k] = rgba[4 * s + k];
-    out.color_tag[d] = tag[s];
+    packed_fields([&](size_t b, auto* to, auto* from) {
+      const size_t m = b / sizeof *to;
+      for (size_t k = 0; k < m; k++) to[m * d + k] = from[m * s + k];
+    }, out, src);
   }
 }
 
@@ -614,11 +586,13 @@ int frame_geometry(atmrt_ctx* c) {
   int wl_max = 0;
   for (int g = 0; g < G; g++) wl_max = std::max(wl_max, cm->cols[(size_t)g + 1] - cm->cols[(size_t)g]);
   cm->W = W, cm->H = H, cm->wl_max = wl_max;
-  cm->slab_bytes = pad256((size_t)H * wl_max * (N_F64_PLANES * 8 + 4)) + SLAB_TRAILER_BYTES;
+  Carve slab(nullptr);
+  carve_dense(slab, (size_t)H * wl_max);
+  cm->slab_bytes = slab.bytes + SLAB_TRAILER_BYTES;
   return ATMRT_OK;
 }
 
-// Phase A of a shared frame: this rank's tile into its slab — the nine planes the generators write, back to back in ONE buffer
+// Phase A of a shared frame: this rank's tile into its slab — the nine planes the generators write, carved from ONE buffer
 // (84 B per pixel), so that one collective moves them all.  Every buffer the frame's exchange will need is reserved HERE, before
 // any rank can be inside a collective (group_gate).
 int tile_generate(atmrt_ctx* c, uint64_t* ray_steps, double* device_ms) {
@@ -634,12 +608,8 @@ int tile_generate(atmrt_ctx* c, uint64_t* ray_steps, double* device_ms) {
   HIP_TRY(c, cm->d_tiling.reserve(4 * ((size_t)cm->world + 1)));
   HIP_TRY(c, cm->d_small.reserve(512 + 8 * (size_t)cm->world));
   const int c0 = cm->cols_frame[(size_t)cm->rank], c1 = cm->cols_frame[(size_t)cm->rank + 1];
-  const size_t ps = (size_t)cm->H * (size_t)(c1 - c0);
-  double* base = cm->d_slab.as<double>();
-  DensePlanes& d = cm->slab_planes;
-  d.azimuth = base, d.elevation_angle = base + ps, d.lat = base + 2 * ps, d.lon = base + 3 * ps, d.distance = base + 4 * ps;
-  d.elevation = base + 5 * ps, d.path_length = base + 6 * ps, d.normal = base + 7 * ps; // planar [3][H][wl]
-  d.hit_count = reinterpret_cast<uint32_t*>(base + N_F64_PLANES * ps);
+  Carve slab(cm->d_slab.ptr);
+  cm->slab_planes = carve_dense(slab, (size_t)cm->H * (size_t)(c1 - c0));
   uint64_t nh = 0;
   return api_generate_tile(c, &cm->slab_planes, false, &nh, ray_steps, device_ms);
 }
@@ -683,9 +653,7 @@ int tile_exchange(atmrt_ctx* c, const atmrt_device_planes_t* image) {
   HIP_TRY(c, hipEventRecord(cm->ev_g1, s));
   if (image && image->azimuth) {
     DensePlanes img;
-    img.azimuth = image->azimuth, img.elevation_angle = image->elevation_angle, img.hit_count = image->hit_count;
-    img.lat = image->lat, img.lon = image->lon, img.distance = image->distance, img.elevation = image->elevation;
-    img.path_length = image->path_length, img.normal = image->normal;
+    (void)planes_from_abi(*image, &img); // complete: atmrt_generate_image_device checked
     hipLaunchKernelGGL(k_assemble_image, dim3(blocks_for((size_t)cm->W * cm->H)), dim3(256), 0, s, cm->d_gathered.as<char>(),
                        cm->slab_bytes, cm->W, cm->H, G, (const int*)cm->d_tiling.as<int>(), img);
     cm->last_image = img;
@@ -733,10 +701,6 @@ int tile_exchange(atmrt_ctx* c, const atmrt_device_planes_t* image) {
   return ATMRT_OK;
 }
 
-bool image_planes_complete(const atmrt_device_planes_t& p) {
-  return p.azimuth && p.elevation_angle && p.hit_count && p.lat && p.lon && p.distance && p.elevation && p.path_length && p.normal;
-}
-
 // The lists of the last shared frame on this rank.  dst == NULL: the image's total only — known to every rank since the frame's own
 // collective (SlabTrailer), no communication.  dst != NULL: ONE collective, the all-gather of the packed lists, in which every
 // rank takes part whatever it wants for itself (dst->hit_offset == NULL: nothing; an error of its own — capacity too small, a missing
@@ -766,34 +730,25 @@ int tile_hits(atmrt_ctx* c, const atmrt_device_hits_t* dst, uint64_t* n_total_ou
   }
   // this rank's own troubles, reported after it has done its part
   const char* trouble = nullptr;
+  PackedHits out;
   if (wants) {
     if (!cm->image_valid) trouble = "the image planes of the last frame were not assembled on this device";
     else if (dst->capacity < n_total) trouble = "capacity is less than the trace points of the image";
-    else if (!dst->lat || !dst->lon || !dst->distance || !dst->elevation || !dst->path_length || !dst->normal || !dst->color_tag || !dst->rgba)
-      trouble = "every array pointer must be a device allocation";
+    else if (!hits_from_abi(*dst, &out)) trouble = "every array pointer must be a device allocation";
   }
   // (1) this rank's lists into a block laid out for the largest rank, (2) one all-gather of the blocks
-  const size_t bb = HitBlock::bytes(n_cap);
+  Carve block(nullptr); // a rank's lists laid out for the largest rank's count: what is all-gathered
+  carve_packed(block, n_cap);
+  const size_t bb = block.bytes;
   const size_t ps = (size_t)cm->H * cm->wl_max; // stride of the per-rank offset tables
   HIP_TRY(c, cm->d_hits_send.reserve(bb));
   HIP_TRY(c, cm->d_hits_recv.reserve(bb * (size_t)G));
   HIP_TRY(c, cm->d_loc_off.reserve(ps * (size_t)G * 8));
   HIP_TRY(c, cm->d_scan_tmp.reserve((std::max(npx, ps) / 2048 + 4) * 8 + 64));
-  char* blk = cm->d_hits_send.as<char>();
-  const PackedHits& h = c->last_hits;
-  const uint64_t n_local = c->last_nhits;
-  auto d2d = [&](size_t off, const void* from, size_t bytes) {
-    return bytes ? hipMemcpyAsync(blk + off, from, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
-  };
-  HIP_TRY(c, d2d(HitBlock::off_f64(0, n_cap), h.lat, n_local * 8));
-  HIP_TRY(c, d2d(HitBlock::off_f64(1, n_cap), h.lon, n_local * 8));
-  HIP_TRY(c, d2d(HitBlock::off_f64(2, n_cap), h.distance, n_local * 8));
-  HIP_TRY(c, d2d(HitBlock::off_f64(3, n_cap), h.elevation, n_local * 8));
-  HIP_TRY(c, d2d(HitBlock::off_f64(4, n_cap), h.path_length, n_local * 8));
-  HIP_TRY(c, d2d(HitBlock::off_f64(5, n_cap), h.normal, n_local * 24));
-  HIP_TRY(c, d2d(HitBlock::off_f64(8, n_cap), h.rgba, n_local * 32));
-  HIP_TRY(c, d2d(HitBlock::off_tag(n_cap), h.color_tag, n_local * 4));
-  int rc = comm_all_gather(c, blk, cm->d_hits_recv.ptr, bb);
+  Carve send(cm->d_hits_send.ptr);
+  PackedHits mine = carve_packed(send, n_cap);
+  HIP_TRY(c, copy_packed(mine, c->last_hits, c->last_nhits, hipMemcpyDeviceToDevice, s));
+  int rc = comm_all_gather(c, cm->d_hits_send.ptr, cm->d_hits_recv.ptr, bb);
   if (rc) return rc;
   cm->tm.collectives = 2;
   if (wants && !trouble) {
@@ -802,13 +757,10 @@ int tile_hits(atmrt_ctx* c, const atmrt_device_hits_t* dst, uint64_t* n_total_ou
     unsigned long long* total = reinterpret_cast<unsigned long long*>(cm->d_small.as<uint64_t>() + 8); // scratch: the scans' grand totals are not needed
     for (int g = 0; g < G; g++) {
       const size_t n = (size_t)cm->H * (size_t)(cm->cols_frame[(size_t)g + 1] - cm->cols_frame[(size_t)g]);
-      const uint32_t* counts = reinterpret_cast<const uint32_t*>(cm->d_gathered.as<char>() + (size_t)g * cm->slab_bytes + N_F64_PLANES * n * 8);
-      launch_scan_u32(counts, n, tmp, cm->d_loc_off.as<uint64_t>() + (size_t)g * ps, total, s);
+      Carve slab(cm->d_gathered.as<char>() + (size_t)g * cm->slab_bytes);
+      launch_scan_u32(carve_dense(slab, n).hit_count, n, tmp, cm->d_loc_off.as<uint64_t>() + (size_t)g * ps, total, s);
     }
     launch_scan_u32(cm->last_image.hit_count, npx, tmp, dst->hit_offset, total, s);
-    PackedHits out;
-    out.lat = dst->lat, out.lon = dst->lon, out.distance = dst->distance, out.elevation = dst->elevation;
-    out.path_length = dst->path_length, out.normal = dst->normal, out.color_tag = dst->color_tag, out.rgba = dst->rgba;
     hipLaunchKernelGGL(k_gather_hits, dim3(blocks_for(npx)), dim3(256), 0, s, cm->d_hits_recv.as<char>(), bb, (size_t)n_cap,
                        cm->d_loc_off.as<uint64_t>(), ps, cm->W, cm->H, G, (const int*)cm->d_tiling.as<int>(),
                        (const uint32_t*)cm->last_image.hit_count, (const uint64_t*)dst->hit_offset, out);
@@ -828,7 +780,7 @@ int tile_draw(atmrt_ctx* c, const atmrt_coloring_t* coloring, uint8_t* rgb_image
   if (!cm->exchanged || !c->last_valid)
     return c->fail(ATMRT_ERR_STATE, "atmrt_draw_image_gathered_device needs a frame: call atmrt_generate_image_device first");
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t tile_bytes = pad256(3 * (size_t)cm->H * cm->wl_max);
+  const size_t tile_bytes = Carve::pad(3 * (size_t)cm->H * cm->wl_max);
   HIP_TRY(c, cm->d_rgb_tile.reserve(tile_bytes));
   HIP_TRY(c, cm->d_rgb_all.reserve(tile_bytes * (size_t)cm->world));
   int rc = atmrt_draw_image_device(c, coloring, cm->d_rgb_tile.as<uint8_t>());
@@ -1071,11 +1023,12 @@ extern "C" int atmrt_ctx_create_multi(atmrt_ctx** out, const int32_t* devices, i
 
 extern "C" int atmrt_generate_image_device(atmrt_ctx* c, const atmrt_device_planes_t* image, uint64_t* ray_steps, double* device_ms) {
   if (!c || !image) return ATMRT_ERR_INVALID_ARGUMENT;
+  DensePlanes unused;
   if (c->multi) {
     MultiGroup* g = c->multi;
     const size_t n = g->kids.size();
     for (size_t i = 0; i < n; i++)
-      if (image[i].azimuth && !image_planes_complete(image[i]))
+      if (image[i].azimuth && !planes_from_abi(image[i], &unused))
         return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "image %zu: every plane pointer must be a device allocation (or azimuth NULL to skip the device)", i);
     std::vector<uint64_t> steps(n, 0);
     std::vector<double> ms(n, 0.0);
@@ -1104,7 +1057,7 @@ extern "C" int atmrt_generate_image_device(atmrt_ctx* c, const atmrt_device_plan
     if (device_ms) *device_ms = *std::max_element(ms.begin(), ms.end());
     return ATMRT_OK;
   }
-  if (!image_planes_complete(*image)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every plane pointer must be a device allocation");
+  if (!planes_from_abi(*image, &unused)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every plane pointer must be a device allocation");
   if (!c->comm) return atmrt_generate_device(c, image, ray_steps, device_ms); // one device: the image is the tile
   int rc = tile_generate(c, ray_steps, device_ms);
   if (rc) return rc;
@@ -1247,6 +1200,11 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
   for (uint64_t v : nh) n_hits += v;
   if (atmrt_internal_result_alloc(out, (uint32_t)W, (uint32_t)H, n_hits))
     return parent->fail(ATMRT_ERR_INVALID_ARGUMENT, "out of host memory for %dx%d pixels / %llu hits", W, H, (unsigned long long)n_hits);
+  // a device's staging in host memory: its local offsets [H][wl], then its lists
+  auto stage = [&](Carve& k, atmrt_ctx* kid, uint64_t** loc, PackedHits* lists) {
+    k(*loc, (size_t)kid->last_wl * H * 8);
+    *lists = carve_packed(k, nh[(size_t)kid->comm->rank]);
+  };
   // (2) planes: strided copies straight into the [H][W] block; lists: into this device's staging; row totals for the merge
   rc = multi_forward(parent, [&](atmrt_ctx* k) {
     Comm* cm = k->comm;
@@ -1261,22 +1219,13 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
     HIP_TRY(k, hipMemcpy2DAsync(out->elevation_angle + c0, (size_t)W * 8, d.elevation_angle, (size_t)wl * 8, (size_t)wl * 8, (size_t)H, hipMemcpyDeviceToHost, s));
     HIP_TRY(k, hipMemcpy2DAsync(out->hit_count + c0, (size_t)W * 4, d.hit_count, (size_t)wl * 4, (size_t)wl * 4, (size_t)H, hipMemcpyDeviceToHost, s));
     const uint64_t m = nh[i];
-    // staging: local offsets [H * wl] + the eight list arrays
-    const size_t off_bytes = pad256(tile_px * 8);
-    HIP_TRY(k, cm->h_stage.reserve(off_bytes + 5 * pad256(m * 8) + pad256(m * 24) + pad256(m * 32) + pad256(m * 4) + 256));
-    char* st = cm->h_stage.as<char>();
-    HIP_TRY(k, hipMemcpyAsync(st, k->last_offset, tile_px * 8, hipMemcpyDeviceToHost, s));
-    char* p = st + off_bytes;
-    const PackedHits& h = k->last_hits;
-    const void* src[8] = {h.lat, h.lon, h.distance, h.elevation, h.path_length, h.normal, h.rgba, h.color_tag};
-    const size_t width[8] = {8, 8, 8, 8, 8, 24, 32, 4};
-    for (int a = 0; a < 8; a++) {
-      if (m) HIP_TRY(k, hipMemcpyAsync(p, src[a], m * width[a], hipMemcpyDeviceToHost, s));
-      p += pad256(m * width[a]);
-    }
+    uint64_t* loc;
+    PackedHits lists;
+    HIP_TRY(k, reserve_carved(cm->h_stage, [&](Carve& st) { stage(st, k, &loc, &lists); }));
+    HIP_TRY(k, hipMemcpyAsync(loc, k->last_offset, tile_px * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(k, copy_packed(lists, k->last_hits, m, hipMemcpyDeviceToHost, s));
     HIP_TRY(k, hipEventRecord(cm->ev_g1, s));
     HIP_TRY(k, hipStreamSynchronize(s));
-    const uint64_t* loc = reinterpret_cast<const uint64_t*>(st);
     cm->row_total.resize((size_t)H);
     for (int y = 0; y < H; y++) {
       const uint64_t end = y + 1 < H ? loc[(size_t)(y + 1) * wl] : m;
@@ -1302,22 +1251,14 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
     Comm* cm = k->comm;
     const size_t i = (size_t)cm->rank;
     const int c0 = k->last_c0, wl = k->last_wl;
-    const uint64_t m = nh[i];
-    const char* st = cm->h_stage.as<char>();
-    const uint64_t* loc = reinterpret_cast<const uint64_t*>(st);
-    const char* p = st + pad256((size_t)wl * H * 8);
-    char* dstv[8] = {(char*)out->lat, (char*)out->lon, (char*)out->distance, (char*)out->elevation, (char*)out->path_length,
-                     (char*)out->normal, (char*)out->rgba, (char*)out->color_tag};
-    const size_t width[8] = {8, 8, 8, 8, 8, 24, 32, 4};
-    const char* srcv[8];
-    for (int a = 0; a < 8; a++) {
-      srcv[a] = p;
-      p += pad256(m * width[a]);
-    }
+    uint64_t* loc;
+    PackedHits lists;
+    Carve st(cm->h_stage.ptr);
+    stage(st, k, &loc, &lists);
     for (int y = 0; y < H; y++) {
       const uint64_t s0 = loc[(size_t)y * wl], cnt = cm->row_total[(size_t)y], d0 = seg[(size_t)y * n + i];
       if (cnt)
-        for (int a = 0; a < 8; a++) memcpy(dstv[a] + d0 * width[a], srcv[a] + s0 * width[a], cnt * width[a]);
+        packed_fields([&](size_t b, auto* to, auto* from) { memcpy((char*)to + d0 * b, (const char*)from + s0 * b, cnt * b); }, *out, lists);
       uint64_t* o = out->hit_offset + (size_t)y * W + c0;
       for (int x = 0; x < wl; x++) o[x] = d0 + (loc[(size_t)y * wl + x] - s0);
     }
