@@ -530,6 +530,143 @@ extern "C" int atmrt_objects_set(atmrt_ctx* c, const atmrt_object_t* objects, si
 }
 
 // ---------------------------------------------------------------------------------------------
+// escape certificate
+// ---------------------------------------------------------------------------------------------
+// The spherical stepper integrates r'' = r + (2 r'^2 n + (r^2 + r'^2) r n') / (r n) in phi.  Where r |n'| / n <= 1/2, r'' >= r / 2 +
+// 3 r'^2 / (2 r) > 0 whatever r' is: a ray with r' > 0 stays ascending, and so does every RK4 stage of it (all four stage slopes are
+// positive), so the sign test has nothing left to find once it is above the mosaic's top and the objects' bands.  The factor 2 is the
+// margin for the central difference of n' (points 1 cm apart), the truncation of RK4 and the rounding of r'.
+//
+// Upper bound of (R + h) |n'(h)| / n(h) over [u, v], from segment k's closed form (u, v may lie a centimetre outside the segment: the
+// stencil of the right-hand side): n - 1 = K pt / Z, pt = p / T and Z Ciddor's compressibility (ciddor_z).  pt and its derivative are
+// monotone on a Linear or isothermal segment, and bounded through the coefficients on a Spline knot interval.  Where the temperature
+// of a Linear segment is <= 0 the evaluations are NaN (dm_pow of a negative base) and a ray that gets there never crosses anything
+// again: no constraint.  +inf: no bound.
+static double escape_piece_bound(const AtmTable& t, int k, double u, double v, double radius) {
+  const AtmSeg& s = t.seg(k);
+  const double a0 = 1.58123e-6, a1 = 2.9331e-8, a2 = 1.1043e-10, zd = 1.83e-11; // |coefficients| of ciddor_z
+  double pt_max, dpt_max, t_lo, t_hi, dt_max;
+  if (s.cubic) {
+    const double du = u - s.hb, dv = v - s.hb, m = std::max(std::fabs(du), std::fabs(dv));
+    dt_max = std::fabs(s.lapse) + 2.0 * std::fabs(s.c2) * m + 3.0 * std::fabs(s.c3) * m * m;
+    const double tu = seg_temperature(s.tb, s.lapse, s.c2, s.c3, du);
+    t_lo = tu - dt_max * (v - u);
+    t_hi = tu + dt_max * (v - u);
+    if (!(t_lo > 1.0) || !(s.expo < 0.0)) return INFINITY;
+    // p decreases with h (expo < 0, T > 0): its largest value is at u
+    const double p_max = s.pb * seg_pressure_ratio(1, s.hb, s.tb, s.gtb, s.lapse, s.c2, s.c3, s.expo, u) * (1.0 + 1.0e-9);
+    pt_max = p_max / t_lo;
+    dpt_max = pt_max * (std::fabs(s.expo) + dt_max) / t_lo; // d(p/T)/dh = (p/T) (expo - T') / T
+  } else if (s.lapse != 0.0) {
+    const double xu = std::fma(s.gtb, u - s.hb, 1.0), xv = std::fma(s.gtb, v - s.hb, 1.0);
+    double x_lo = std::min(xu, xv), x_hi = std::max(xu, xv);
+    if (!(x_hi > 0.0)) return s.expo1 > 1.0 ? 0.0 : INFINITY; // T <= 0 throughout: NaN
+    if (!(x_lo > 0.0)) {
+      if (!(s.expo1 > 1.0)) return INFINITY; // pt' = ptb expo1 gtb x^(expo1 - 1) unbounded as T -> 0
+      x_lo = 0.0;
+    }
+    // pt = ptb x^expo1, |pt'| = ptb |expo1 gtb| x^(expo1 - 1): both monotone in x
+    pt_max = std::max(s.ptb * std::pow(x_lo, s.expo1), s.ptb * std::pow(x_hi, s.expo1));
+    const double g = s.ptb * std::fabs(s.expo1 * s.gtb);
+    dpt_max = std::max(g * std::pow(x_lo, s.expo1 - 1.0), g * std::pow(x_hi, s.expo1 - 1.0));
+    t_lo = s.tb * x_lo;
+    t_hi = s.tb * x_hi;
+    dt_max = std::fabs(s.lapse);
+  } else { // isothermal: pt = ptb exp(expo1 (h - hb))
+    pt_max = std::max(s.ptb * std::exp(s.expo1 * (u - s.hb)), s.ptb * std::exp(s.expo1 * (v - s.hb)));
+    dpt_max = std::fabs(s.expo1) * pt_max;
+    t_lo = t_hi = s.tb;
+    dt_max = 0.0;
+  }
+  pt_max *= 1.0 + 1.0e-9;
+  dpt_max *= 1.0 + 1.0e-9;
+  const double ta = std::max(std::fabs(t_lo - 273.15), std::fabs(t_hi - 273.15));
+  const double a_max = a0 + a1 * ta + a2 * ta * ta;
+  const double z_min = 1.0 - pt_max * a_max;
+  if (!(z_min >= 0.5)) return INFINITY;
+  // Z' = -pt' A - pt A'(t) T' + 2 pt pt' d;  n' = K (pt' / Z - pt Z' / Z^2);  n >= 1
+  const double dz_max = dpt_max * (a_max + 2.0 * pt_max * zd) + pt_max * (a1 + 2.0 * a2 * ta) * dt_max;
+  const double dn_max = std::fabs(t.k_refr) * (dpt_max / z_min + pt_max * dz_max / (z_min * z_min));
+  const double b = (radius + std::max(std::fabs(u), std::fabs(v))) * dn_max * (1.0 + 1.0e-6);
+  return b >= 0.0 ? b : INFINITY;
+}
+
+constexpr double ESCAPE_BOUND = 0.5;
+// The lowest altitude `from` >= lo such that (R + h) |n'| / n <= ESCAPE_BOUND for every h >= from, or +inf; *worst: the largest bound
+// above `from`.  Sweeps every segment's part of [lo, 1e7 m) in pieces of 50 m growing by 2 % of the height above lo; a jump of n at a
+// segment boundary enters the central difference of a stencil across it as 50 |jump|.  Above 1e7 m the last segment must make the
+// bound decreasing: isothermal with expo1 (R + h) <= -1, Linear warming with expo1 < -1, or Linear cooling to T = 0 below 1e7 m.
+static double escape_certified_from(const AtmTable& t, double radius, double lo, double* worst) {
+  constexpr double H_END = 1.0e7, EPS = 0.01;
+  double from = lo, w = 0.0;
+  std::vector<double> pieces; // (top, bound) of every piece, bottom up
+  auto jump = [&](int k) { // |n| jump at the lower boundary of segment k >= 1, + the rounding of the two values
+    const double h = t.seg(k).from;
+    const double d = std::fabs(refr_n_layer<true, false>(t.k_refr, t.seg(k), h) - refr_n_layer<true, false>(t.k_refr, t.seg(k - 1), h));
+    return (d == d ? d : INFINITY) + 1.0e-15;
+  };
+  for (int k = 0; k < t.n; k++) {
+    const double s_lo = k > 0 ? t.seg(k).from : -INFINITY, s_hi = k + 1 < t.n ? t.seg(k + 1).from : INFINITY;
+    const double a = std::max(s_lo, lo), b = std::min(s_hi, H_END);
+    for (double u = a; u < b;) {
+      const double v = std::min(b, u + 50.0 + 0.02 * (u - lo));
+      double bound = escape_piece_bound(t, k, u - EPS, v + EPS, radius);
+      if (k > 0 && u == s_lo) bound += (radius + u + EPS) * 50.0 * jump(k);
+      if (k + 1 < t.n && v == s_hi) bound += (radius + v + EPS) * 50.0 * jump(k + 1);
+      pieces.push_back(v);
+      pieces.push_back(bound);
+      u = v;
+    }
+    if (k + 1 == t.n) { // the tail above H_END
+      const AtmSeg& s = t.seg(k);
+      bool ok;
+      if (s.cubic) ok = false;
+      else if (s.lapse == 0.0) ok = s.expo1 * (radius + std::max(a, H_END)) <= -1.0;
+      else if (s.gtb > 0.0) ok = s.expo1 < -1.0;
+      else ok = s.gtb < 0.0 && s.hb - 1.0 / s.gtb < H_END && s.expo1 > 1.0;
+      pieces.push_back(INFINITY);
+      pieces.push_back(ok ? 0.0 : INFINITY);
+    }
+  }
+  for (size_t q = 0; q < pieces.size(); q += 2)
+    if (!(pieces[q + 1] <= ESCAPE_BOUND)) from = pieces[q];
+  for (size_t q = 0; q < pieces.size(); q += 2)
+    if (pieces[q] > from && pieces[q + 1] > w) w = pieces[q + 1];
+  if (worst) *worst = w;
+  return from;
+}
+
+// What the march gets: the floor above which an ascending ray may leave (Frame::esc_floor), +inf for none.  `top`: the mosaic's
+// skip_above (every post is below it; lookups outside the mosaic are 0 m, and it is at least 1 m).
+static double escape_floor(const AtmTable& t, bool spherical, double radius, bool straight, double top, double step, double* from_out,
+                           double* worst) {
+  if (worst) *worst = 0.0;
+  if (from_out) *from_out = top - step;
+  if (straight) return top;        // h(x) is linear (flat) or convex (spherical, while the ray's angle stays below 90 degrees)
+  if (!spherical) return INFINITY; // flat earth, refracted: n' < 0 bends every ray down
+  const double from = escape_certified_from(t, radius, top - step, worst);
+  if (from_out) *from_out = from;
+  return std::max(top, from + step); // the stages of a step reach no lower than its start; one step of margin below that
+}
+
+static bool escape_enabled() {
+  const char* e = getenv("ATMRT_ESCAPE");
+  return !(e && !strcmp(e, "off"));
+}
+
+extern "C" int atmrt_escape_certificate(const atmrt_atmosphere_t* atmosphere, double wavelength, int32_t spherical, double radius,
+                                        int32_t straight, double simulation_step, double top, double out[3]) {
+  if (!atmosphere || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  AtmTableBuf buf;
+  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
+  double from = 0.0, worst = 0.0;
+  out[0] = escape_floor(buf.table(), spherical != 0, radius, straight != 0, top, simulation_step, &from, &worst);
+  out[1] = from;
+  out[2] = worst;
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // frame set-up
 // ---------------------------------------------------------------------------------------------
 static int prepare_frame(atmrt_ctx* c, Frame* out) {
@@ -569,6 +706,10 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
       if (c->xs.size() > 5000000) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "distance table too long");
     }
     c->n_t = n_t;
+    c->march_steps = 0;
+    for (size_t k = 1; k < c->xs.size(); k++) // the march's own rule: step k is taken while x_k <= max_distance (rectilinear.rs:178)
+      if (c->xs[k] <= p.frame.max_distance) c->march_steps = (int)k;
+      else break;
     c->n_path_cap = (int)c->xs.size();
     HIP_TRY(c, c->d_xs.reserve(c->xs.size() * sizeof(double)));
     HIP_TRY(c, hipMemcpy(c->d_xs.ptr, c->xs.data(), c->xs.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -605,6 +746,28 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   f.n_objects = (int32_t)c->objects.size();
   f.n_t = c->n_t;
   f.n_path_cap = c->n_path_cap;
+  f.march_steps = c->march_steps;
+  // the escape certificate: cached with the table (atm_key) for the mosaic's top
+  if (atm_fresh || !c->esc_valid || c->esc_lo != c->tv.skip_above) {
+    double from = 0.0, worst = 0.0;
+    (void)escape_floor(c->atm.table(), true, c->earth.shape_radius, false, c->tv.skip_above, p.simulation_step, &from, &worst);
+    c->esc_lo = c->tv.skip_above;
+    c->esc_from = from;
+    c->esc_bound = worst;
+    c->esc_valid = true;
+  }
+  f.esc_floor = INFINITY;
+  f.esc_ang_max = INFINITY;
+  if (escape_enabled() && p.generator == ATMRT_GEN_RECTILINEAR) {
+    if (p.straight_rays) {
+      f.esc_floor = c->tv.skip_above;
+      // spherical: h = r0 cos(ang) / cos(ang + x / R) - R is convex while ang + x / R stays below 90 degrees (then it turns negative
+      // and the reference stops the ray at -1000 m): with 0.05 rad of margin for the rounding of the angle
+      if (c->earth.spherical) f.esc_ang_max = 1.5207963267948966 - p.frame.max_distance * f.inv_shape_radius;
+    } else if (c->earth.spherical) {
+      f.esc_floor = std::max(c->tv.skip_above, c->esc_from + p.simulation_step);
+    }
+  }
   {
     int c0 = (p.col_begin == 0 && p.col_end == 0) ? 0 : p.col_begin;
     int c1 = (p.col_begin == 0 && p.col_end == 0) ? p.width : p.col_end;
@@ -1005,6 +1168,9 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   c->stats.terrain_lookups = counters[CTR_TERRAIN_LOOKUPS];
   c->stats.object_rays = counters[CTR_OBJECT_RAYS];
   c->stats.object_steps = counters[CTR_OBJECT_STEPS];
+  c->last_ray_steps = counters[CTR_RAY_STEPS];
+  c->last_escaped_steps = counters[CTR_ESCAPED_STEPS];
+  c->last_escaped_rays = counters[CTR_ESCAPED_RAYS];
   if (ms_out) *ms_out = ms;
   if (ray_steps_out) *ray_steps_out = counters[CTR_RAY_STEPS];
   if (packed_out) *packed_out = packed;
@@ -1237,6 +1403,14 @@ extern "C" int atmrt_last_stats(atmrt_ctx* c, atmrt_frame_stats_t* out) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) return multi_last_stats(c, out);
   *out = c->stats;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_march_work(atmrt_ctx* c, uint64_t* integrated_steps, uint64_t* escaped_rays) {
+  if (!c || !integrated_steps || !escaped_rays) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (c->multi) return multi_last_march_work(c, integrated_steps, escaped_rays);
+  *integrated_steps = c->last_ray_steps - c->last_escaped_steps;
+  *escaped_rays = c->last_escaped_rays;
   return ATMRT_OK;
 }
 

@@ -127,10 +127,15 @@ struct atmrt_ctx {
     int32_t _pad = 0;
   } atm_key{};
   bool atm_key_valid = false;
+  // the escape certificate of the table under atm_key (prepare_frame, escape_floor): the lowest altitude from which it holds,
+  // computed for the altitudes from esc_lo up (the mosaic's top minus a step)
+  double esc_lo = 0.0, esc_from = 0.0, esc_bound = 0.0;
+  bool esc_valid = false;
   atmrt::Earth earth{};
   atmrt::Pinhole pinhole{};
   std::vector<double> xs;
   int n_t = 0, n_path_cap = 0;
+  int march_steps = 0; // #{k >= 1 : xs[k] <= max_distance}: the steps of a ray that marches to the end
   bool xs_dirty = true;
 
   // last generated frame (for atmrt_draw_image)
@@ -142,6 +147,7 @@ struct atmrt_ctx {
   atmrt::PackedHits last_hits{};
   const uint64_t* last_offset = nullptr;
   uint64_t last_nhits = 0;
+  uint64_t last_ray_steps = 0, last_escaped_steps = 0, last_escaped_rays = 0; // atmrt_last_march_work
 
   std::vector<atmrt::ObjectDev> objects; // host image of the device table (altitude kind in _pad until k_resolve)
   std::vector<uint8_t> textures;         // RGBA8 pool

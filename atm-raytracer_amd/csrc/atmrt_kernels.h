@@ -33,6 +33,14 @@ struct Frame {
   int32_t di0, ei0;
   double dir_step, elev_step;
   double inv_shape_radius;  // RN(1 / earth.shape_radius) (0 on a flat earth): calc_dist divides the step length by the radius (dm_div_r)
+  // The escape certificate (atmrt_api.hip, escape_floor): a Rectilinear ray whose last sample lies above
+  // esc_floor and which is ascending (refracted: the stepper's dr/dphi > 0; straight: the sample above the one before, and its
+  // elevation angle below esc_ang_max) provably crosses neither the terrain nor an object of its wavefront's list again before
+  // max_distance: the march credits the rest of its march_steps and leaves.  esc_floor = +inf: no certificate (ATMRT_ESCAPE=off,
+  // flat-earth refraction, an atmosphere that can bend an ascending ray back down).
+  double esc_floor;
+  double esc_ang_max;
+  int32_t march_steps;      // steps of a ray that marches to max_distance: #{k >= 1 : xs[k] <= max_distance}
 };
 
 // column azimuth / row elevation in degrees, as handed to gen_terrain_cache / gen_path_cache
@@ -154,6 +162,7 @@ struct PathSegState {
 enum Counter : int {
   CTR_RAY_STEPS = 0,
   CTR_HITS = 1, // total of the last launch_scan_counts: trace points of the frame
+  CTR_ESCAPED_RAYS = 2, // Rectilinear rays that left the march under the escape certificate (Frame::esc_floor)
   CTR_CLOSE_TOTAL = 3, // entries of the close lists
   CTR_OVERFLOW_PIXELS = 3, // pixels with more trace points than RECT_SLOTS
   CTR_OVERFLOW_CURSOR = 3, // cursor of the list of those pixels
@@ -168,6 +177,7 @@ enum Counter : int {
   CTR_SLICE_UNFINISHED = 12, // groups the time-sliced march left unfinished, + 1 (must be 0: atmrt_api.hip checks)
   CTR_OVERFLOW_RECORDS = 13, // records appended to the overflow arena
   CTR_OBJECT_STEPS = 14, // ray-steps handed to the lean march's out-of-line object step
+  CTR_ESCAPED_STEPS = 15, // ray-steps those rays were credited without integrating them: CTR_RAY_STEPS - this = steps integrated
 };
 constexpr int N_COUNTERS = 16;
 

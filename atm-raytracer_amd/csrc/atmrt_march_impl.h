@@ -114,6 +114,30 @@ static __device__ __forceinline__ void overflow_append(const OverflowArena& ovf,
   }
 }
 
+// The escape test, after a step's sign test (Frame::esc_floor; the certificate is atmrt_api.hip's escape_floor).  The last sample
+// is above the mosaic's top and the bands of the wavefront's objects, and the ray is ascending: refracted, dr/dphi > 0, which the
+// certificate keeps positive to max_distance; straight, the sample above the one before (h(x) is convex while the ray's angle
+// stays below esc_ang_max).  From here on every sample is above the floor: no sign change, no object step, no lookup.
+static __device__ __forceinline__ bool escapes(const Frame& f, const Stepper& s, bool straight, double sh, double re0, double floor) {
+  if (!(sh > floor)) return false;
+  return straight ? sh > re0 && s.ang < f.esc_ang_max : s.b > 0.0;
+}
+// MODE 3: the floor also clears the height band [vlo, vhi] of every object in the wavefront's candidate list (a ray can only meet
+// an object of that list); + 1 m against the rounding of the samples
+static __device__ __forceinline__ double escape_floor_objects(double floor, const double* w_vhi, int n_e) {
+  for (int q = 0; q < n_e; q++) floor = w_vhi[q] + 1.0 > floor ? w_vhi[q] + 1.0 : floor;
+  return floor;
+}
+// the rays that escaped and the steps they were credited (CTR_ESCAPED_RAYS / CTR_ESCAPED_STEPS), one atomic per wavefront
+static __device__ __forceinline__ void escape_count(unsigned long long* counters, int esc_credit) {
+  const unsigned long long rays = wave_sum(esc_credit >= 0 ? 1ull : 0ull);
+  const unsigned long long credit = wave_sum(esc_credit > 0 ? (unsigned long long)esc_credit : 0ull);
+  if ((threadIdx.x & 63) == 0 && rays) {
+    atomicAdd(&counters[CTR_ESCAPED_RAYS], rays);
+    atomicAdd(&counters[CTR_ESCAPED_STEPS], credit);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // MODE 3, the rare step.  Until round 3 a ray of the lean march that reached a step which could involve an object was abandoned
 // there and traced again from x = 0 by the general tracer k_rect_trace — 11 % of config 5's rays, 38 ms of 333 for the frame and a
@@ -229,6 +253,7 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
   const bool live = pixel_list ? tid < n_list : tid < plane;
   const size_t p = pixel_list ? (live ? pixel_list[tid] : 0) : tid;
   unsigned long long steps = 0, lookups = 0;
+  int esc_credit = -1; // >= 0: the ray escaped and was credited this many steps (escapes below)
   if (live) {
     const Earth e = earth_for<CALC>(f);
     const int y = (int)(p / (size_t)f.wl), x = (int)(p % (size_t)f.wl);
@@ -251,6 +276,7 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
     bool object_ray = false; // MODE 3: this ray is left to the general tracer
     int w_n = 0;             // MODE 3: entries of the wavefront's candidate list
     double x_wake = dm_inf();
+    double esc_floor = f.esc_floor; // MODE 3: raised to the tops of the wavefront's candidate objects
     __shared__ double w_lo[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1], w_hi[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1],
         w_vlo[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1], w_vhi[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1];
     __shared__ int w_obj[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1];
@@ -295,6 +321,7 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         for (int q = 0; q < w_n && q < WAVE_CAND; q++) // first interval that is not behind the start
           if (w_hi[wv][q] >= 0.0) x_wake = w_lo[wv][q] < x_wake ? w_lo[wv][q] : x_wake;
+        esc_floor = escape_floor_objects(esc_floor, w_vhi[wv], w_n < WAVE_CAND ? w_n : WAVE_CAND);
       }
     }
     // first sample (PathIterator::next at the start state); the reference would panic on an empty stream
@@ -414,6 +441,10 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
           count++;
           if (opaque) break; // utils.rs:237-239, 283-285
         }
+        if (escapes(f, s, straight, sh, re0, esc_floor)) { // nothing left to find: credit the rest of the march and leave
+          esc_credit = f.march_steps - i;
+          break;
+        }
         diff0 = diff1;
         re0 = sh;
         pl0 = path_length;
@@ -426,10 +457,12 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
       }
     }
     if (MODE == 3) hit_step[p] = object_ray ? 1 : 0; // voids the ray's overflow records (k_rect_scatter_trace_overflow)
+    if (esc_credit >= 0) steps += (unsigned)esc_credit;
     if (MODE == 3 && object_ray) { // nothing of this ray counts: k_rect_trace starts it again
       out.hit_count[p] = OBJECT_RAY;
       steps = 0;
       lookups = 0;
+      esc_credit = -1;
     } else if (MODE != 2) {
       out.azimuth[p] = dm_to_degrees(direction); // not wrapped, rectilinear.rs:110-113
       out.elevation_angle[p] = dm_to_degrees(elevation);
@@ -445,6 +478,7 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
       atomicAdd(&counters[CTR_RAY_STEPS], steps);
       atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
     }
+    escape_count(counters, esc_credit);
   }
 #ifdef ATMRT_TIMELINE
   if (MODE == 0 && (threadIdx.x & 63) == 0) {
@@ -546,7 +580,7 @@ static __device__ __forceinline__ bool march_slice(const Frame& f, const Earth& 
                                                    double& path_length, double& diff0, double& re0, double& pl0, int i0, int slice,
                                                    int& first, unsigned& count, const SliceSinks& sinks, unsigned long long* counters, size_t p,
                                                    size_t plane, unsigned long long& steps, unsigned long long& lookups,
-                                                   const SliceObjects& so, double& x_wake) {
+                                                   const SliceObjects& so, double& x_wake, int& esc_credit) {
   const bool sph = e.spherical != 0;
   const double radius = e.shape_radius;
   const bool straight = f.p.straight_rays != 0;
@@ -554,6 +588,7 @@ static __device__ __forceinline__ bool march_slice(const Frame& f, const Earth& 
   const double skip_above = f.tv.skip_above;
   double sx = s.x, lat, lon;
   const int i_end = i0 + slice;
+  const double esc_floor = MODE == 3 ? escape_floor_objects(f.esc_floor, so.w_vhi, so.n_e) : f.esc_floor;
   for (int i = i0 + 1;; i++) {
     bool tame;
     RayState nx = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step, tame);
@@ -622,6 +657,10 @@ static __device__ __forceinline__ bool march_slice(const Frame& f, const Earth& 
       count++;
       if (MODE == 3 && f.p.terrain_alpha == 1.0) return false; // opaque terrain ends the ray (utils.rs:237-239)
     }
+    if (escapes(f, s, straight, sh, re0, esc_floor)) { // as in k_rect_march: the ray has finished
+      esc_credit = f.march_steps - i;
+      return false;
+    }
     diff0 = diff1;
     re0 = sh;
     pl0 = path_length;
@@ -676,6 +715,7 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
   const size_t plane = (size_t)f.wl * f.h;
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long steps = 0, lookups = 0;
+  int esc_credit = -1;
   bool alive = false;
   if (p < plane) {
     const Earth e = earth_for<CALC>(f);
@@ -744,7 +784,8 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
       diff0 = alt - terrain_elev_or_zero(f.tv, lat, lon);
       lookups++;
       alive = march_slice<MODE, CALC, CUBIC>(f, e, c, s, sh, path_length, diff0, re0, pl0, 0, slice, first, count, sinks, counters, p, plane,
-                                             steps, lookups, so, x_wake);
+                                             steps, lookups, so, x_wake, esc_credit);
+      if (esc_credit >= 0) steps += (unsigned)esc_credit;
     }
     if (MODE == 3 && st.glist && __any(alive)) { // the group marches on: its list and wake distance for the slices to come
       const GroupList gl = group_list(st.glist, (uint32_t)(p >> 6));
@@ -768,6 +809,7 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
       sinks.hit_step[p] = 1;
       steps = 0;
       lookups = 0;
+      esc_credit = -1;
     } else if (alive) {
       st.x[p] = s.x;
       st.a[p] = s.a;
@@ -799,6 +841,7 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
     atomicAdd(&counters[CTR_RAY_STEPS], steps);
     atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
   }
+  escape_count(counters, esc_credit);
 }
 
 // the later slices: one single-wavefront workgroup per queue entry.  NOT a persistent grid: the SIMD issues oldest-wavefront-first,
@@ -845,6 +888,7 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
   const unsigned long long tl_slice_t0 = wall_clock64();
 #endif
   unsigned long long steps = 0, lookups = 0;
+  int esc_credit = -1;
   const size_t p = (size_t)item * 64 + lane;
   bool alive = false;
   const int32_t i0 = p < plane ? st.step[p] : -1;
@@ -884,7 +928,8 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
     int first = -1;
     unsigned count = MODE == 1 || MODE == 3 ? st.count[p] : 0u;
     alive = march_slice<MODE, CALC, CUBIC>(f, e, c, s, sh, path_length, diff0, re0, pl0, i0, slice, first, count, sinks, counters, p, plane,
-                                           steps, lookups, so, x_wake);
+                                           steps, lookups, so, x_wake, esc_credit);
+    if (esc_credit >= 0) steps += (unsigned)esc_credit;
     if (alive) {
       st.x[p] = s.x;
       st.a[p] = s.a;
@@ -929,6 +974,7 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
     atomicAdd(&counters[CTR_RAY_STEPS], steps);
     atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
   }
+  escape_count(counters, esc_credit);
 }
 
 // every group must have finished: anything else is reported through CTR_SLICE_UNFINISHED and fails the frame (atmrt_api.hip)

@@ -26,6 +26,7 @@ int multi_generate(atmrt_ctx* parent, atmrt_result_t* out);
 int multi_draw_image(atmrt_ctx* parent, const atmrt_coloring_t* coloring, uint8_t* rgb);
 int multi_last_timings(atmrt_ctx* parent, atmrt_timings_t* out);
 int multi_last_stats(atmrt_ctx* parent, atmrt_frame_stats_t* out);
+int multi_last_march_work(atmrt_ctx* parent, uint64_t* integrated_steps, uint64_t* escaped_rays);
 
 // implemented in atmrt_api.hip, used by atmrt_multi.hip
 int api_create_plain(atmrt_ctx** out, int device_ordinal);

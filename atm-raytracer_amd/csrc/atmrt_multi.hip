@@ -1347,3 +1347,12 @@ int atmrt::multi_last_stats(atmrt_ctx* parent, atmrt_frame_stats_t* out) {
   *out = t;
   return ATMRT_OK;
 }
+
+int atmrt::multi_last_march_work(atmrt_ctx* parent, uint64_t* integrated_steps, uint64_t* escaped_rays) {
+  *integrated_steps = *escaped_rays = 0;
+  for (atmrt_ctx* k : parent->multi->kids) {
+    *integrated_steps += k->last_ray_steps - k->last_escaped_steps;
+    *escaped_rays += k->last_escaped_rays;
+  }
+  return ATMRT_OK;
+}

@@ -294,6 +294,17 @@ typedef struct atmrt_frame_stats {
                                  (the step lies inside a candidate object's distance interval and enters its height band) */
 } atmrt_frame_stats_t;
 int atmrt_last_stats(atmrt_ctx* ctx, atmrt_frame_stats_t* out);
+/* The work of the last frame's Rectilinear march beside its ray_steps.  ray_steps counts every sample pair under the reference's
+ * termination rule; a ray that is above the mosaic's top (and the objects' height bands) and provably ascending to max_distance
+ * leaves the march early and is credited the steps it did not integrate (the escape certificate).
+ * *integrated_steps = the steps actually integrated, *escaped_rays = the rays that left early.  ATMRT_ESCAPE=off in the environment
+ * (read at every frame) turns the shortcut off: then *integrated_steps = ray_steps.  A multi-device context sums its devices. */
+int atmrt_last_march_work(atmrt_ctx* ctx, uint64_t* integrated_steps, uint64_t* escaped_rays);
+/* The escape certificate for an atmosphere, without a device: out[0] = the altitude above which an ascending Rectilinear ray leaves
+ * the march (+inf: never), out[1] = the lowest altitude from which (R + h) |dn/dh| / n <= 1/2 holds everywhere above it (refracted
+ * spherical stepper; +inf: nowhere), out[2] = the largest value of that bound above out[1].  `top` is the mosaic's top + 1 m. */
+int atmrt_escape_certificate(const atmrt_atmosphere_t* atmosphere, double wavelength, int32_t spherical, double radius,
+                             int32_t straight, double simulation_step, double top, double out[3]);
 /* Fault injection for tests of the error paths: the next atmrt_generate / atmrt_generate_device on ctx runs its kernels and then
  * fails with ATMRT_ERR_HIP (once).  After ANY failed frame atmrt_draw_image* and atmrt_last_hits_device return ATMRT_ERR_STATE
  * until a frame succeeds: the failed frame has already reused the buffers of the one before it. */
