@@ -586,14 +586,18 @@ static double escape_piece_bound(const AtmTable& t, int k, double u, double v, d
   if (!(z_min >= 0.5)) return INFINITY;
   // Z' = -pt' A - pt A'(t) T' + 2 pt pt' d;  n' = K (pt' / Z - pt Z' / Z^2);  n >= 1
   const double dz_max = dpt_max * (a_max + 2.0 * pt_max * zd) + pt_max * (a1 + 2.0 * a2 * ta) * dt_max;
-  const double dn_max = std::fabs(t.k_refr) * (dpt_max / z_min + pt_max * dz_max / (z_min * z_min));
+  double dn_max = std::fabs(t.k_refr) * (dpt_max / z_min + pt_max * dz_max / (z_min * z_min));
+  // What the stepper differences is the computed n: on a Linear segment pt = ptb x^(expo1) carries the rounding of x (2^-53) times
+  // |expo1| (3e7 for a gradient of 1e-9 K/m) besides pow's own, and the central difference divides two such errors by 2 cm
+  if (!s.cubic && s.lapse != 0.0) dn_max += 100.0 * std::fabs(t.k_refr) * pt_max / z_min * (std::fabs(s.expo1) + 4.0) * 0x1p-52;
   const double b = (radius + std::max(std::fabs(u), std::fabs(v))) * dn_max * (1.0 + 1.0e-6);
   return b >= 0.0 ? b : INFINITY;
 }
 
 constexpr double ESCAPE_BOUND = 0.5;
 // The lowest altitude `from` >= lo such that (R + h) |n'| / n <= ESCAPE_BOUND for every h >= from, or +inf; *worst: the largest bound
-// above `from`.  Sweeps every segment's part of [lo, 1e7 m) in pieces of 50 m growing by 2 % of the height above lo; a jump of n at a
+// above `from`.  Sweeps every segment's part of [lo, 1e7 m) in pieces of 50 m growing by 2 % of the height above the segment's lower
+// boundary (above 0 m in the first segment); a jump of n at a
 // segment boundary enters the central difference of a stencil across it as 50 |jump|.  Above 1e7 m the last segment must make the
 // bound decreasing: isothermal with expo1 (R + h) <= -1, Linear warming with expo1 < -1, or Linear cooling to T = 0 below 1e7 m.
 static double escape_certified_from(const AtmTable& t, double radius, double lo, double* worst) {
@@ -607,14 +611,22 @@ static double escape_certified_from(const AtmTable& t, double radius, double lo,
   };
   for (int k = 0; k < t.n; k++) {
     const double s_lo = k > 0 ? t.seg(k).from : -INFINITY, s_hi = k + 1 < t.n ? t.seg(k + 1).from : INFINITY;
-    const double a = std::max(s_lo, lo), b = std::min(s_hi, H_END);
-    for (double u = a; u < b;) {
-      const double v = std::min(b, u + 50.0 + 0.02 * (u - lo));
-      double bound = escape_piece_bound(t, k, u - EPS, v + EPS, radius);
-      if (k > 0 && u == s_lo) bound += (radius + u + EPS) * 50.0 * jump(k);
-      if (k + 1 < t.n && v == s_hi) bound += (radius + v + EPS) * 50.0 * jump(k + 1);
-      pieces.push_back(v);
-      pieces.push_back(bound);
+    const double a = std::max(s_lo, lo - 2.0 * EPS), b = std::min(s_hi, H_END);
+    // the pieces are a lattice of the segment, not of `lo` (anchored at its lower boundary; the first segment's at 0 m, in 50 m pieces
+    // below), and a piece that reaches above `lo` counts whole: a higher `lo` sees a subset of the same pieces, so the floor never
+    // comes down when the mosaic's top goes up
+    const double anchor = k > 0 ? s_lo : 0.0;
+    double u = anchor;
+    if (k == 0 && a < 0.0) u = a > -1.0e6 ? -50.0 * std::ceil(-a / 50.0) : a;
+    while (u < b) {
+      const double v = std::min(b, u + 50.0 + 0.02 * std::max(u - anchor, 0.0));
+      if (v > a) {
+        double bound = escape_piece_bound(t, k, u - EPS, v + EPS, radius);
+        if (k > 0 && u == s_lo) bound += (radius + u + EPS) * 50.0 * jump(k);
+        if (k + 1 < t.n && v == s_hi) bound += (radius + v + EPS) * 50.0 * jump(k + 1);
+        pieces.push_back(v);
+        pieces.push_back(bound);
+      }
       u = v;
     }
     if (k + 1 == t.n) { // the tail above H_END
@@ -629,7 +641,7 @@ static double escape_certified_from(const AtmTable& t, double radius, double lo,
     }
   }
   for (size_t q = 0; q < pieces.size(); q += 2)
-    if (!(pieces[q + 1] <= ESCAPE_BOUND)) from = pieces[q];
+    if (!(pieces[q + 1] <= ESCAPE_BOUND)) from = pieces[q] + 2.0 * EPS; // a stencil centred here no longer reaches into the refused piece
   for (size_t q = 0; q < pieces.size(); q += 2)
     if (pieces[q] > from && pieces[q + 1] > w) w = pieces[q + 1];
   if (worst) *worst = w;

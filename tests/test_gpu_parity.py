@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import atmospheres
 from atm_raytracer_amd import synth
 from util import bits, assert_bitexact, assert_close, run_gpu, run_oracle
 
@@ -313,20 +314,7 @@ def test_randomised_configurations(gpu_ctx, oracle_det, seed):
     }
     if seed % 3 == 1 or seed >= 24:
         ra = np.random.default_rng(7000 + seed)
-        if ra.uniform() < 0.3:
-            knots = np.sort(ra.uniform(-500.0, 30_000.0, int(ra.integers(3, 7))))
-            knots[0] = -500.0
-            temps = 288.0 - 0.0055 * knots + ra.uniform(-6.0, 6.0, knots.size)
-            first = {"Spline": {"boundary_condition": "Natural", "points": [[float(a), float(t)] for a, t in zip(knots, temps)]}}
-            doc["atmosphere"] = {"pressure": {"altitude": 0.0, "pressure": float(ra.uniform(950.0, 1040.0)) * 100.0},
-                                 "first_temperature_function": first}
-        else:
-            grads = [float(ra.choice([-0.0065, -0.0098, 0.0, 0.003, -0.002, float(ra.uniform(-0.009, 0.004))])) for _ in range(int(ra.integers(1, 5)))]
-            alts = np.sort(ra.uniform(300.0, 25_000.0, len(grads) - 1))
-            doc["atmosphere"] = {"pressure": {"altitude": float(ra.uniform(0.0, 500.0)), "pressure": float(ra.uniform(950.0, 1040.0)) * 100.0},
-                                 "temperature_fixed_point": {"altitude": float(ra.uniform(0.0, 2000.0)), "temperature": float(ra.uniform(255.0, 305.0))},
-                                 "first_temperature_function": {"Linear": {"gradient": grads[0]}},
-                                 "next_functions": [{"altitude": float(a), "function": {"Linear": {"gradient": g}}} for a, g in zip(alts, grads[1:])]}
+        doc["atmosphere"] = atmospheres.configuration_atmosphere(ra)
     from atm_raytracer_amd import config
     cfg = config.Config.from_dict(doc)
     if seed % 4 == 3 or seed >= 36:  # scene objects in a quarter of the sweep (every generator, opaque and translucent terrain)
@@ -385,23 +373,9 @@ def test_randomised_extremes(gpu_ctx, oracle_det, seed):
         "scene": {"terrain_alpha": float(rng.choice([1.0, 0.5, 0.0, 0.999]))},
         "output": {"width": w, "height": h, "generator": gen},
     }
-    u = rng.uniform()
-    if u < 0.35:
-        n_knots = int(rng.integers(2, 9))
-        knots = np.sort(rng.uniform(-1000.0, 40_000.0, n_knots))
-        temps = 288.0 - 0.006 * knots + rng.uniform(-15.0, 15.0, n_knots)
-        bc = rng.choice(["Natural", "Derivatives", "SecondDerivatives"])
-        bcv = "Natural" if bc == "Natural" else {str(bc): [float(rng.uniform(-0.01, 0.01)) if bc == "Derivatives" else float(rng.uniform(-1e-6, 1e-6)),
-                                                           float(rng.uniform(-0.01, 0.01)) if bc == "Derivatives" else float(rng.uniform(-1e-6, 1e-6))]}
-        doc["atmosphere"] = {"pressure": {"altitude": float(rng.uniform(-200.0, 3000.0)), "pressure": float(rng.uniform(300.0, 1100.0)) * 100.0},
-                             "first_temperature_function": {"Spline": {"boundary_condition": bcv, "points": [[float(a), float(t)] for a, t in zip(knots, temps)]}}}
-    elif u < 0.7:
-        grads = [float(rng.choice([-0.0065, 0.0, 0.05, -0.05, -0.0342, float(rng.uniform(-0.02, 0.02)), 1e-9])) for _ in range(int(rng.integers(1, 7)))]
-        alts = np.sort(rng.uniform(-500.0, 50_000.0, len(grads) - 1))
-        doc["atmosphere"] = {"pressure": {"altitude": float(rng.uniform(-300.0, 5000.0)), "pressure": float(rng.uniform(200.0, 1100.0)) * 100.0},
-                             "temperature_fixed_point": {"altitude": float(rng.uniform(-300.0, 12000.0)), "temperature": float(rng.uniform(180.0, 330.0))},
-                             "first_temperature_function": {"Linear": {"gradient": grads[0]}},
-                             "next_functions": [{"altitude": float(a), "function": {"Linear": {"gradient": g}}} for a, g in zip(alts, grads[1:])]}
+    atm = atmospheres.extreme_atmosphere(rng)
+    if atm is not None:
+        doc["atmosphere"] = atm
     cfg = config.Config.from_dict(doc)
     if rng.uniform() < 0.5:  # a column shard of the frame
         c0 = int(rng.integers(0, w))
@@ -452,26 +426,7 @@ def test_randomised_long_atmospheres(gpu_ctx, oracle_det, seed):
     layer search; the certificate runs over every segment.  GPU == oracle in every bit."""
     from atm_raytracer_amd import config, generators
     rng = np.random.default_rng(900_000 + seed)
-    n_fn = int(rng.integers(9, 71)) if rng.uniform() < 0.7 else int(rng.integers(1, 4))
-    tops = np.sort(rng.uniform(0.0, 45_000.0, n_fn - 1)) + np.arange(n_fn - 1) * 0.5
-    functions, t_here = [], float(rng.uniform(270.0, 310.0))
-    for j in range(n_fn):
-        lo = -2000.0 if j == 0 else float(tops[j - 1])
-        hi = float(tops[j]) if j < n_fn - 1 else lo + float(rng.uniform(2000.0, 30_000.0))
-        if rng.uniform() < (0.25 if n_fn > 3 else 0.9):  # a Spline over (and a little beyond) this function's range
-            n_k = int(rng.integers(2, 121 if n_fn <= 3 else 25))
-            ks = np.sort(rng.uniform(lo - 50.0, hi + 50.0, n_k)) + np.arange(n_k) * 1e-2
-            ts = np.clip(t_here - 0.005 * (ks - lo) + rng.normal(0.0, 1.0, n_k), 150.0, 340.0)
-            functions.append({"Spline": {"boundary_condition": "Natural", "points": [[float(a), float(t)] for a, t in zip(ks, ts)]}})
-            t_here = float(ts[-1])
-        else:
-            g = float(rng.choice([-0.0065, 0.0, 0.003, -0.0098, float(rng.uniform(-0.012, 0.012))]))
-            functions.append({"Linear": {"gradient": g}})
-            t_here = float(np.clip(t_here + g * (hi - max(lo, 0.0)), 160.0, 330.0))
-    atm = {"pressure": {"altitude": float(rng.uniform(0.0, 1500.0)), "pressure": float(rng.uniform(700.0, 1050.0)) * 100.0},
-           "temperature_fixed_point": {"altitude": float(rng.uniform(0.0, 3000.0)), "temperature": float(rng.uniform(250.0, 300.0))},
-           "first_temperature_function": functions[0],
-           "next_functions": [{"altitude": float(a), "function": f} for a, f in zip(tops, functions[1:])]}
+    atm = atmospheres.long_atmosphere(rng)
     gen = ["Fast", "Rectilinear", "InterpolatingRectilinear"][seed % 3]
     w, h = (int(rng.integers(8, 40)), int(rng.integers(6, 24))) if gen != "Rectilinear" else (int(rng.integers(4, 20)), int(rng.integers(4, 14)))
     cfg, tiles = synth.scene("S2", w, h, generator=gen, atmosphere=atm, tilt=float(rng.uniform(-3.0, 25.0)), fov=float(rng.uniform(2.0, 60.0)),
@@ -550,18 +505,7 @@ def test_randomised_harnesses(gpu_ctx, oracle_det, seed):
         gpu_ctx.check(gpu_ctx.lib.atmrt_set_params(gpu_ctx.handle, C.byref(d0.params)))
 
 
-WILD_SPLINE = {"pressure": {"altitude": 0.0, "pressure": 102390.63927278577},
-               "first_temperature_function": {"Spline": {"boundary_condition": "Natural", "points": [
-                   [-500.0, 295.22010975963303], [16672.2152178729, 192.93808594359285], [16688.49864235047, 195.36762037322703],
-                   [21728.827855811145, 170.01112581350702], [28892.825051123004, 125.19791348512327]]}}}
-
-
-# seed 31148 of the sweep: the same kind of spline, steeper — the pressure at the base of its upper knot intervals is inf / NaN.
-# Until round 2 atmrt_set_atmosphere rejected it ("non-positive temperature or pressure"); the reference has no such check.
-OVERFLOWING_SPLINE = {"pressure": {"altitude": 0.0, "pressure": 99730.24971796537},
-                      "first_temperature_function": {"Spline": {"boundary_condition": "Natural", "points": [
-                          [-500.0, 295.9785296912339], [13886.76872258016, 216.67442822116288], [13916.894125578941, 207.95894584371578],
-                          [22713.29131575354, 163.34485706767265], [27617.68202733401, 130.8150959041496]]}}}
+from atmospheres import OVERFLOWING_SPLINE, WILD_SPLINE  # noqa: E402  (seeds 4899 and 31148 of the first sweep)
 
 
 @pytest.mark.parametrize("atmosphere", [WILD_SPLINE, OVERFLOWING_SPLINE], ids=["seed4899", "seed31148"])
