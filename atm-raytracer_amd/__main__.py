@@ -6,8 +6,10 @@
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
 
 Column formats follow src/atm_printer.rs:37-46, src/ray_path.rs:65-103 and src/elev_profile.rs:43-64.  `gen` writes the
-image of renderer::draw_image (no ticks / labels: those stay CPU-side in the reference, renderer/mod.rs:28-323) and, on
-request, the per-pixel metadata as a compressed .npz (the reference's bincode+gzip layout depends on crates that are absent).
+image of renderer::output_image: draw_image, then — on the device image, before its one download — the azimuth / elevation
+ticks, the flat-horizon line and the eye-level line of `output` (renderer/mod.rs:416-431); the tick labels are drawn on the
+host with Pillow in DejaVu Sans where the machine has that font (a warning and no labels where not).  On request it also
+writes the per-pixel metadata as a compressed .npz (the reference's bincode+gzip layout depends on crates that are absent).
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -33,6 +35,41 @@ def _configure(ctx, cfg):
     ctx.check(ctx.lib.atmrt_set_atmosphere(ctx.handle, C.byref(cfg.atmosphere)))
 
 
+def find_label_font():
+    """DejaVuSans.ttf (the reference embeds its own copy, renderer/mod.rs:20) from the system fonts or matplotlib's data; None if absent."""
+    import glob
+    dirs = ["/usr/share/fonts", "/usr/local/share/fonts", os.path.expanduser("~/.fonts"), os.path.expanduser("~/.local/share/fonts")]
+    try:
+        import matplotlib
+        dirs.append(os.path.join(matplotlib.get_data_path(), "fonts", "ttf"))
+    except ImportError:
+        pass
+    for d in dirs:
+        hits = sorted(glob.glob(os.path.join(d, "**", "DejaVuSans.ttf"), recursive=True))
+        if hits:
+            return hits[0]
+    return None
+
+
+def draw_labels(img, ticks):
+    """draw_text_mut of draw_ticks (renderer/mod.rs:292-321): white, 15 px high, a horizontal tick's label at (x - 8, size + 5), a
+    vertical tick's at (size + 5, y - 7); strings and positions come from the library.  Glyph pixels are Pillow's, not rusttype's."""
+    labelled = [t for t in ticks if t["labelled"]]
+    if not labelled:
+        return
+    path = find_label_font()
+    if path is None:
+        print("WARNING: DejaVuSans.ttf not found on this machine: tick labels are left off", file=sys.stderr)
+        return
+    from PIL import ImageDraw, ImageFont
+    # rusttype's Scale is ascent - descent in pixels: 15 px over DejaVu Sans's (1901 + 483) / 2048 em is an em of 12.9 px
+    font = ImageFont.truetype(path, 13)
+    draw = ImageDraw.Draw(img)
+    for t in labelled:
+        xy = (t["size"] + 5, t["pos"] - 7) if t["vertical"] else (t["pos"] - 8, t["size"] + 5)
+        draw.text(xy, t["label"], fill=(255, 255, 255), font=font, anchor="la")
+
+
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
@@ -46,9 +83,15 @@ def cmd_gen(a):
     stamp("Done calculating")
     stamp("Outputting image...")
     col = generators.into_coloring(ctx.lib, cfg.params, cfg.coloring)
-    rgb = generators.draw_image(ctx, col, res["width"], res["height"])
+    import torch
     from PIL import Image
-    Image.fromarray(rgb, "RGB").save(a.output)
+    w, h = res["width"], res["height"]
+    rgb_dev = torch.empty((h, w, 3), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
+    ticks, _ = generators.draw_overlay_device(ctx, generators.into_overlay(cfg.output), rgb_dev.data_ptr(), w, h)
+    img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
+    draw_labels(img, ticks)
+    img.save(a.output)
     meta_path = a.metadata or cfg.output["file_metadata"]  # `if let Some(ref filename) = params.output.file_metadata`, generator/mod.rs:88-94
     if meta_path:
         stamp("Outputting metadata...")

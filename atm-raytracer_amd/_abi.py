@@ -113,6 +113,35 @@ class Coloring(C.Structure):
 COLORING_SIMPLE, COLORING_SHADING = 0, 1
 PALETTES = {"Legacy": 0, "Improved": 1}
 
+# atmrt_tick_kind
+TICK_SINGLE, TICK_MULTIPLE = 0, 1
+TICK_LABEL_BYTES = 32
+
+
+class Tick(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("size", C.c_uint32), ("angle", C.c_double), ("bias", C.c_double), ("step", C.c_double),
+                ("labelled", C.c_int32), ("_pad", C.c_int32)]
+
+
+class Overlay(C.Structure):
+    """atmrt_overlay_t.  The tick arrays are borrowed pointers: build with Overlay.new(), which keeps them alive on the object."""
+    _fields_ = [("ticks", C.POINTER(Tick)), ("vertical_ticks", C.POINTER(Tick)), ("n_ticks", C.c_uint32), ("n_vertical_ticks", C.c_uint32),
+                ("show_eye_level", C.c_int32), ("show_flat_horizon", C.c_int32)]
+
+    @classmethod
+    def new(cls, ticks=(), vertical_ticks=(), show_eye_level=False, show_flat_horizon=False):
+        o = cls()
+        o._arrays = ((Tick * max(1, len(ticks)))(*ticks), (Tick * max(1, len(vertical_ticks)))(*vertical_ticks))
+        o.ticks, o.vertical_ticks = C.cast(o._arrays[0], C.POINTER(Tick)), C.cast(o._arrays[1], C.POINTER(Tick))
+        o.n_ticks, o.n_vertical_ticks = len(ticks), len(vertical_ticks)
+        o.show_eye_level, o.show_flat_horizon = int(bool(show_eye_level)), int(bool(show_flat_horizon))
+        return o
+
+
+class DrawnTick(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("size", C.c_uint32), ("labelled", C.c_int32), ("vertical", C.c_int32),
+                ("label", C.c_char * TICK_LABEL_BYTES)]
+
 
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""

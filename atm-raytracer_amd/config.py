@@ -3,9 +3,9 @@
 `parse_config(path)` / `Config.from_dict` mirror `params::parse_config` (params.rs:678-692): every
 field has the reference's serde default; enums use serde's externally tagged form
 (`earth_shape: {Spherical: {radius: 6371000}}`, `altitude: {Relative: 2}`, `generator: Fast`).
-Only the part of the schema that reaches the generators is interpreted; renderer-only keys
-(coloring, ticks, fog, file names) are accepted and ignored, unknown top-level keys raise like
-serde's `deny`-less parse would not — they are ignored too.
+The schema that reaches the generators and the renderer (coloring, fog, ticks, the eye-level and
+flat-horizon lines) is interpreted; unknown top-level keys raise like serde's `deny`-less parse
+would not — they are ignored.
 """
 import ctypes as C
 
@@ -149,7 +149,7 @@ def _object(node, load_texture):  # ConfObject, object/mod.rs:156-161
 
 def _ticks(nodes, angle_key):
     """Vec<Tick> / Vec<VerticalTick> (params.rs:306-367): externally tagged `Single{azimuth|elevation, size, labelled}` or
-    `Multiple{bias, step, size, labelled}`; every field is required (no serde default).  Kept for the metadata file only."""
+    `Multiple{bias, step, size, labelled}`; every field is required (no serde default).  generators.into_overlay turns them into atmrt_tick_t."""
     out = []
     for node in nodes or []:
         (k, v), = node.items()

@@ -134,6 +134,9 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 11: return sizeof(atmrt_device_hits_t);
     case 12: return sizeof(atmrt_comm_timings_t);
     case 13: return sizeof(atmrt_temp_function_t);
+    case 14: return sizeof(atmrt_tick_t);
+    case 15: return sizeof(atmrt_overlay_t);
+    case 16: return sizeof(atmrt_drawn_tick_t);
     default: return 0;
   }
 }
@@ -1193,6 +1196,7 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   c->last_h = f.h;
   c->last_c0 = f.c0;
   c->last_alpha = f.p.terrain_alpha;
+  c->last_params = f.p;
   c->last_dense = dense;
   c->last_hits = packed;
   c->last_offset = ws.hit_offset;
@@ -1465,6 +1469,264 @@ extern "C" int atmrt_draw_image(atmrt_ctx* c, const atmrt_coloring_t* coloring, 
   if (rc) return rc;
   HIP_TRY(c, hipMemcpy(rgb, c->d_io.ptr, 3 * c->last_npx, hipMemcpyDeviceToHost));
   return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the annotations of renderer::output_image: ticks resolved on the host (W + H values), lines searched and drawn on the device
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+double diff_azimuth(double az1, double az2) { // renderer/mod.rs:28-37
+  const double diff = az1 - az2;
+  if (diff < -180.0) return diff + 360.0;
+  if (diff > 180.0) return diff - 360.0;
+  return diff;
+}
+
+// Iterator::min_by keeps the first of equal minima: strict `<` in ascending index.  (A NaN makes the reference panic in
+// partial_cmp().unwrap(); here it never wins.)
+bool azimuth_to_x(double azimuth, const double* row, int w, uint32_t* x) { // :39-59
+  int candidate = 0;
+  double best = std::fabs(diff_azimuth(azimuth, row[0]));
+  for (int i = 1; i < w; i++) {
+    const double d = std::fabs(diff_azimuth(azimuth, row[i]));
+    if (d < best || best != best) best = d, candidate = i;
+  }
+  const int neighbour = candidate == 0 ? 1 : candidate - 1;
+  const double diff_per_pixel = std::fabs(diff_azimuth(row[candidate], row[neighbour]));
+  *x = (uint32_t)candidate;
+  return std::fabs(diff_azimuth(row[candidate], azimuth)) < diff_per_pixel * 1.5;
+}
+
+bool elevation_to_y(double elevation, const double* col, int h, uint32_t* y) { // :61-80
+  int candidate = 0;
+  double best = std::fabs(elevation - col[0]);
+  for (int i = 1; i < h; i++) {
+    const double d = std::fabs(elevation - col[i]);
+    if (d < best || best != best) best = d, candidate = i;
+  }
+  const int neighbour = candidate == 0 ? 1 : candidate - 1;
+  const double diff_per_pixel = std::fabs(col[candidate] - col[neighbour]);
+  *y = (uint32_t)candidate;
+  return std::fabs(col[candidate] - elevation) < diff_per_pixel * 1.5;
+}
+
+int num_decimals(double x) { // :208-216; f64::round is half away from zero, like round()
+  double mul = 1.0;
+  for (int i = 0; i < 10; i++, mul *= 10.0) { // 10^i is exact below 10^23
+    const double mul_x = x * mul;
+    if (std::fabs(std::round(mul_x) - mul_x) < 0.001) return i;
+  }
+  return 10;
+}
+
+int round_decimals(const atmrt_tick_t* ticks, uint32_t n) { // :218-225; TickLike::angle is the step of a Multiple (params.rs:347-352)
+  int decimals = 0;
+  for (uint32_t i = 0; i < n; i++)
+    if (ticks[i].labelled) decimals = std::max(decimals, num_decimals(ticks[i].kind == ATMRT_TICK_SINGLE ? ticks[i].angle : ticks[i].step));
+  return decimals;
+}
+
+constexpr int OVERLAY_MAX_TICKS_PER_DEF = 1 << 20;
+
+const char* overlay_check(const atmrt_overlay_t& o) {
+  if ((o.n_ticks && !o.ticks) || (o.n_vertical_ticks && !o.vertical_ticks)) return "a tick list is NULL";
+  for (int v = 0; v < 2; v++) {
+    const atmrt_tick_t* t = v ? o.vertical_ticks : o.ticks;
+    for (uint32_t i = 0, n = v ? o.n_vertical_ticks : o.n_ticks; i < n; i++) {
+      if (t[i].kind != ATMRT_TICK_SINGLE && t[i].kind != ATMRT_TICK_MULTIPLE) return "unknown tick kind";
+      if (t[i].kind == ATMRT_TICK_MULTIPLE && !(t[i].step > 0.0 && t[i].step < INFINITY)) return "the step of a Multiple tick must be positive and finite";
+    }
+  }
+  return nullptr;
+}
+
+// gen_ticks (:227-268) over row 0 of the azimuth plane (w values) and column 0 of the elevation plane (h values); `out` sorted by
+// (vertical, pos).  The label is glibc's %.*f: correctly rounded from the binary value and signed like Rust's {:.N}.
+const char* resolve_ticks(const atmrt_params_t& p, const atmrt_overlay_t& o, const double* az, int w, const double* el, int h,
+                          std::vector<atmrt_drawn_tick_t>* out) {
+  out->clear();
+  for (int v = 0; v < 2; v++) {
+    const atmrt_tick_t* ticks = v ? o.vertical_ticks : o.ticks;
+    const uint32_t n = v ? o.n_vertical_ticks : o.n_ticks;
+    const int decimals = round_decimals(ticks, n);
+    std::map<uint32_t, atmrt_drawn_tick_t> at; // HashMap<u32, DrawTick>: the larger size stays, the earlier one when equal (:237-246)
+    auto put = [&](uint32_t pos, const atmrt_tick_t& t, double angle) {
+      atmrt_drawn_tick_t d{};
+      d.pos = pos, d.size = t.size, d.labelled = t.labelled ? 1 : 0, d.vertical = v;
+      snprintf(d.label, sizeof d.label, "%.*f", decimals, angle);
+      auto it = at.find(pos);
+      if (it == at.end()) at.emplace(pos, d);
+      else if (it->second.size < d.size) it->second = d;
+    };
+    for (uint32_t i = 0; i < n; i++) {
+      const atmrt_tick_t& t = ticks[i];
+      uint32_t pos;
+      if (t.kind == ATMRT_TICK_SINGLE) { // :89-106, :149-166
+        if (v ? elevation_to_y(t.angle, el, h, &pos) : azimuth_to_x(t.angle, az, w, &pos)) put(pos, t, t.angle);
+        continue;
+      }
+      int count = 0;
+      if (!v) { // :107-138: the UNWRAPPED current_az goes to azimuth_to_x, the wrapped one into the label
+        const double min_az = p.frame.direction - p.frame.fov / 2.0, max_az = p.frame.direction + p.frame.fov / 2.0;
+        for (double current_az = std::ceil((min_az - t.bias) / t.step) * t.step + t.bias; current_az < max_az; current_az += t.step) {
+          if (++count > OVERLAY_MAX_TICKS_PER_DEF) return "a Multiple tick yields more than 2^20 ticks";
+          const double azimuth = current_az < 0.0 ? current_az + 360.0 : current_az >= 360.0 ? current_az - 360.0 : current_az;
+          if (azimuth_to_x(current_az, az, w, &pos)) put(pos, t, azimuth);
+        }
+      } else { // :167-199: the folded elevation goes to elevation_to_y and into the label
+        const double aspect = (double)p.height / (double)p.width;
+        const double min_elev = p.frame.tilt - p.frame.fov * aspect / 2.0, max_elev = p.frame.tilt + p.frame.fov * aspect / 2.0;
+        for (double current_elev = std::ceil((min_elev - t.bias) / t.step) * t.step + t.bias; current_elev < max_elev; current_elev += t.step) {
+          if (++count > OVERLAY_MAX_TICKS_PER_DEF) return "a Multiple tick yields more than 2^20 ticks";
+          const double elevation = current_elev < -90.0 ? -180.0 - current_elev : current_elev > 90.0 ? 180.0 - current_elev : current_elev;
+          if (elevation_to_y(elevation, el, h, &pos)) put(pos, t, elevation);
+        }
+      }
+    }
+    for (const auto& kv : at) out->push_back(kv.second);
+  }
+  return nullptr;
+}
+
+bool earth_shape_is_flat(int32_t kind) { // EarthModel::to_shape, earth_model/mod.rs:95-112
+  return kind == ATMRT_EARTH_AZIMUTHAL_EQUIDISTANT || kind == ATMRT_EARTH_FLAT_DISTORTED || kind == ATMRT_EARTH_OBSERVER_AE ||
+         kind == ATMRT_EARTH_SIMPLE_OBSERVER_AE;
+}
+
+// output_image's annotations (:419-431) over the planes `az`, `el` ([h][w], memory of c's device) of a frame c has generated with
+// the position and atmosphere still set (its observer altitude is in d_alt, its atmosphere table in d_atm).
+int draw_overlay_on(atmrt_ctx* c, atmrt_ctx* report, const atmrt_params_t& p, const atmrt_overlay_t& o, const double* az, const double* el,
+                    int w, int h, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
+#define OVERLAY_TRY(expr)                                                                                      \
+  do {                                                                                                         \
+    hipError_t e_ = (expr);                                                                                    \
+    if (e_ != hipSuccess) return report->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+  if (flat_horizon_deg) *flat_horizon_deg = NAN;
+  if (n_drawn) *n_drawn = 0;
+  if (w < 2 || h < 2) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "the overlay needs an image of at least 2 x 2 pixels, not %d x %d", w, h);
+  if (const char* msg = overlay_check(o)) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  OVERLAY_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  std::vector<atmrt_drawn_tick_t> ticks;
+  if (o.n_ticks || o.n_vertical_ticks) { // row 0 and column 0: W + H doubles to the host
+    std::vector<double> az0(w), el0(h);
+    OVERLAY_TRY(hipMemcpyAsync(az0.data(), az, (size_t)w * 8, hipMemcpyDeviceToHost, s));
+    OVERLAY_TRY(hipMemcpy2DAsync(el0.data(), 8, el, (size_t)w * 8, 8, (size_t)h, hipMemcpyDeviceToHost, s));
+    OVERLAY_TRY(hipStreamSynchronize(s));
+    if (const char* msg = resolve_ticks(p, o, az0.data(), w, el0.data(), h, &ticks)) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  }
+  if (n_drawn) *n_drawn = ticks.size();
+  if (drawn && capacity < ticks.size())
+    return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "capacity %zu is less than the %zu ticks of the frame", capacity, ticks.size());
+  if (drawn) std::copy(ticks.begin(), ticks.end(), drawn);
+  const bool flat = o.show_flat_horizon && earth_shape_is_flat(p.earth.kind) && !p.straight_rays; // :420-422
+  const bool eye = o.show_eye_level != 0;
+  int n_cu = 0;
+  OVERLAY_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+  const int bands = overlay_bands(w, h, n_cu);
+  struct DevTick {
+    uint32_t pos, size;
+    int32_t vertical, _pad;
+  };
+  const size_t tick_bytes = Carve::pad(ticks.size() * sizeof(DevTick)), sample_bytes = Carve::pad(4 * sizeof(double));
+  OVERLAY_TRY(c->d_overlay.reserve(tick_bytes + sample_bytes + overlay_workspace_bytes(w, bands)));
+  char* base = c->d_overlay.as<char>();
+  double target = NAN;
+  if (flat) { // n at the observer's altitude through the library's own refr_n (k_atm_sample); acos and the degrees on the host
+    Frame f{};
+    f.atm = c->d_atm.as<AtmTable>();
+    double* d = reinterpret_cast<double*>(base + tick_bytes);
+    launch_atm_sample(f, 1, c->d_alt.as<double>(), d, d + 1, d + 2, d + 3, s);
+    double n_at_observer = 0.0;
+    OVERLAY_TRY(hipMemcpyAsync(&n_at_observer, d + 2, 8, hipMemcpyDeviceToHost, s));
+    OVERLAY_TRY(hipStreamSynchronize(s));
+    target = std::acos(1.0 / n_at_observer) * (180.0 / M_PI); // f64::to_degrees
+    if (flat_horizon_deg) *flat_horizon_deg = target;
+  }
+  if (!ticks.empty()) {
+    std::vector<DevTick> dt(ticks.size());
+    for (size_t i = 0; i < ticks.size(); i++) dt[i] = DevTick{ticks[i].pos, ticks[i].size, ticks[i].vertical, 0};
+    OVERLAY_TRY(hipMemcpyAsync(base, dt.data(), dt.size() * sizeof(DevTick), hipMemcpyHostToDevice, s));
+    OVERLAY_TRY(hipStreamSynchronize(s)); // dt goes out of scope
+    launch_overlay_ticks(base, (int)dt.size(), w, h, rgb, s);
+  }
+  if (flat || eye) { // a NaN target is never close to anything: its line is all None
+    int32_t* y_of_x = nullptr;
+    launch_overlay_find_elev(el, w, h, bands, target, eye ? 0.0 : NAN, base + tick_bytes + sample_bytes, &y_of_x, s);
+    const uint8_t flat_color[3] = {0, 128, 255}, eye_color[3] = {255, 128, 255};
+    if (flat) launch_overlay_lines(y_of_x, w, h, rgb, flat_color, s);
+    if (eye) launch_overlay_lines(y_of_x + w, w, h, rgb, eye_color, s);
+  }
+  OVERLAY_TRY(hipStreamSynchronize(s));
+  OVERLAY_TRY(hipGetLastError());
+  return ATMRT_OK;
+#undef OVERLAY_TRY
+}
+
+} // namespace
+
+extern "C" int atmrt_overlay_resolve_ticks(const atmrt_params_t* params, const atmrt_overlay_t* overlay, const double* azimuth_row0,
+                                           const double* elevation_col0, atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn) {
+  if (!params || !overlay || !azimuth_row0 || !elevation_col0 || !n_drawn) return ATMRT_ERR_INVALID_ARGUMENT;
+  *n_drawn = 0;
+  const bool whole = params->col_begin == 0 && params->col_end == 0;
+  const int w = whole ? params->width : (int)params->col_end - (int)params->col_begin, h = params->height;
+  if (w < 2 || h < 2 || overlay_check(*overlay)) return ATMRT_ERR_INVALID_ARGUMENT;
+  std::vector<atmrt_drawn_tick_t> ticks;
+  if (resolve_ticks(*params, *overlay, azimuth_row0, w, elevation_col0, h, &ticks)) return ATMRT_ERR_INVALID_ARGUMENT;
+  *n_drawn = ticks.size();
+  if (!drawn) return ATMRT_OK;
+  if (capacity < ticks.size()) return ATMRT_ERR_INVALID_ARGUMENT;
+  std::copy(ticks.begin(), ticks.end(), drawn);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_draw_overlay_device(atmrt_ctx* c, const atmrt_overlay_t* overlay, uint8_t* rgb_device, atmrt_drawn_tick_t* drawn,
+                                         size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
+  if (!c || !overlay || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device");
+  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay needs a frame: call atmrt_generate first");
+  return draw_overlay_on(c, c, c->last_params, *overlay, c->last_dense.azimuth, c->last_dense.elevation_angle, c->last_wl, c->last_h,
+                         rgb_device, drawn, capacity, n_drawn, flat_horizon_deg);
+}
+
+extern "C" int atmrt_draw_overlay(atmrt_ctx* c, const atmrt_overlay_t* overlay, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity,
+                                  size_t* n_drawn, double* flat_horizon_deg) {
+  if (!c || !overlay || !rgb) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device");
+  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay needs a frame: call atmrt_generate first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->d_io.reserve(3 * c->last_npx + 256));
+  HIP_TRY(c, hipMemcpy(c->d_io.ptr, rgb, 3 * c->last_npx, hipMemcpyHostToDevice));
+  int rc = atmrt_draw_overlay_device(c, overlay, c->d_io.as<uint8_t>(), drawn, capacity, n_drawn, flat_horizon_deg);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpy(rgb, c->d_io.ptr, 3 * c->last_npx, hipMemcpyDeviceToHost));
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_draw_overlay_planes_device(atmrt_ctx* c, const atmrt_overlay_t* overlay, const double* azimuth,
+                                                const double* elevation_angle, uint32_t width, uint32_t height, uint8_t* rgb_device,
+                                                atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
+  if (!c || !overlay || !azimuth || !elevation_angle || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_set_params has not been called");
+  atmrt_ctx* k = c;
+  if (c->multi) { // the device context that owns the memory: its stream, its workspace, its copy of the observer altitude
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, rgb_device) != hipSuccess) {
+      (void)hipGetLastError();
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "rgb_device is not a device allocation");
+    }
+    k = nullptr;
+    for (int i = 0; i < multi_size(c) && !k; i++)
+      if (multi_child(c, i)->device == attr.device) k = multi_child(c, i);
+    if (!k) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "rgb_device is in the memory of device %d, which is not a device of this context", attr.device);
+  }
+  if (!k->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay_planes_device needs a frame: call atmrt_generate_image_device first");
+  return draw_overlay_on(k, c, c->params, *overlay, azimuth, elevation_angle, (int)width, (int)height, rgb_device, drawn, capacity, n_drawn,
+                         flat_horizon_deg);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -389,6 +389,16 @@ void launch_draw_image(size_t n_pixels, const atmrt_coloring_t& col, double terr
                        const uint32_t* hit_count, const uint64_t* hit_offset, const PackedHits& hits, const DensePlanes& dense,
                        uint8_t* rgb, hipStream_t stream);
 
+// The annotations of renderer::output_image (kernels in atmrt_overlay.h).  find_elev for every column of the [h][w] plane `elev` and
+// the targets t0, t1 in one pass over `bands` row bands (overlay_bands; workspace of overlay_workspace_bytes): *y_of_x points at
+// [2][w] rows, -1 = None.  Ticks: an array of {u32 pos, u32 size, i32 vertical, i32 pad}.
+int overlay_bands(int w, int h, int n_cu);
+size_t overlay_workspace_bytes(int w, int bands);
+void launch_overlay_find_elev(const double* elev, int w, int h, int bands, double t0, double t1, void* workspace, int32_t** y_of_x,
+                              hipStream_t stream);
+void launch_overlay_lines(const int32_t* y_of_x, int w, int h, uint8_t* rgb, const uint8_t color[3], hipStream_t stream);
+void launch_overlay_ticks(const void* ticks, int n, int w, int h, uint8_t* rgb, hipStream_t stream);
+
 void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream);
 void launch_rect_trace_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,

@@ -15,6 +15,7 @@
 // 73.4 -> 67.7 ms (InterpolatingRectilinear); 4 waves 26.9 ms.
 #define ATMRT_OBJ_FN __attribute__((noinline))
 #include "atmrt_device.h"
+#include "atmrt_overlay.h"
 #include "atmrt_render.h"
 
 namespace atmrt {
@@ -1280,6 +1281,49 @@ void launch_draw_image(size_t n_pixels, const atmrt_coloring_t& col, double terr
   else
     hipLaunchKernelGGL((k_draw_image<false>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, col, terrain_alpha,
                        hit_count, hit_offset, hits, dense, rgb);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the annotations of renderer::output_image (kernels: atmrt_overlay.h)
+// ---------------------------------------------------------------------------------------------
+// Bands of k_overlay_find_elev.  The scan is a pure stream, so what matters is bytes in flight: a wavefront holds 4 row loads of
+// 512 B, and 6.3 TB/s over a miss latency of the order of a microsecond is some 6 MB in flight, 24 KB per CU of 256 — 12 wavefronts
+// per CU; 16 are asked for (half of the 32 a CU can hold, this kernel needs few registers).  W / 64 wavefronts per band give
+// bands = 16 CUs / (W / 64): 64 bands of 32 rows at 4096 x 2048, 32 bands of 128 rows at 8192 x 4096.  A band is at least 32 rows,
+// so that the 24 B of partials a lane writes per band stay below a tenth of the 256 B it reads, and there are at most 256 bands.
+int overlay_bands(int w, int h, int n_cu) {
+  const int groups = (w + 63) / 64;
+  int bands = (16 * (n_cu > 0 ? n_cu : 256) + groups - 1) / groups;
+  if (bands > h / 32) bands = h / 32;
+  if (bands > 256) bands = 256;
+  if (bands < 1) bands = 1;
+  const int rows = (h + bands - 1) / bands;
+  return (h + rows - 1) / rows; // no empty band
+}
+size_t overlay_workspace_bytes(int w, int bands) {
+  return Carve::pad((size_t)OVERLAY_TARGETS * bands * w * sizeof(double)) + Carve::pad((size_t)OVERLAY_TARGETS * bands * w * sizeof(int32_t)) +
+         Carve::pad((size_t)OVERLAY_TARGETS * w * sizeof(int32_t));
+}
+void launch_overlay_find_elev(const double* elev, int w, int h, int bands, double t0, double t1, void* workspace, int32_t** y_of_x,
+                              hipStream_t stream) {
+  Carve k(workspace);
+  double* part_d;
+  int32_t* part_y;
+  k(part_d, (size_t)OVERLAY_TARGETS * bands * w * sizeof(double));
+  k(part_y, (size_t)OVERLAY_TARGETS * bands * w * sizeof(int32_t));
+  k(*y_of_x, (size_t)OVERLAY_TARGETS * w * sizeof(int32_t));
+  const int rows = (h + bands - 1) / bands;
+  hipLaunchKernelGGL(k_overlay_find_elev, dim3(cdiv((size_t)w, 64), bands), dim3(64), 0, stream, elev, w, h, rows, t0, t1, part_d, part_y);
+  hipLaunchKernelGGL(k_overlay_pick_elev, dim3(cdiv((size_t)w, 256)), dim3(256), 0, stream, elev, w, h, bands, t0, t1, part_d, part_y,
+                     *y_of_x);
+}
+void launch_overlay_lines(const int32_t* y_of_x, int w, int h, uint8_t* rgb, const uint8_t color[3], hipStream_t stream) {
+  if (w > 1)
+    hipLaunchKernelGGL(k_overlay_lines, dim3(cdiv((size_t)w - 1, 256)), dim3(256), 0, stream, y_of_x, w, h, rgb, color[0], color[1], color[2]);
+}
+void launch_overlay_ticks(const void* ticks, int n, int w, int h, uint8_t* rgb, hipStream_t stream) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_overlay_ticks, dim3(cdiv((size_t)n, 64)), dim3(64), 0, stream, static_cast<const OverlayTick*>(ticks), n, w, h, rgb);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -362,6 +362,70 @@ def draw_image(ctx, coloring, width, height):
     return rgb
 
 
+# ---- the annotations of renderer::output_image (src/renderer/mod.rs:28-365, 416-431) on the device -----------------------
+def into_overlay(output):
+    """output.ticks / vertical_ticks / show_eye_level / show_flat_horizon as config.Config.output holds them -> atmrt_overlay_t."""
+    def tick(t):
+        if t[0] == "Single":
+            _, angle, size, labelled = t
+            return _abi.Tick(kind=_abi.TICK_SINGLE, size=size, angle=angle, labelled=int(labelled))
+        _, bias, step, size, labelled = t
+        return _abi.Tick(kind=_abi.TICK_MULTIPLE, size=size, bias=bias, step=step, labelled=int(labelled))
+    return _abi.Overlay.new([tick(t) for t in output.get("ticks", [])], [tick(t) for t in output.get("vertical_ticks", [])],
+                            output.get("show_eye_level", False), output.get("show_flat_horizon", False))
+
+
+def _drawn_ticks(arr, n):
+    return [{"pos": t.pos, "size": t.size, "labelled": bool(t.labelled), "vertical": bool(t.vertical), "label": t.label.decode()}
+            for t in arr[:n]]
+
+
+def resolve_ticks(params_pod, overlay, azimuth_row0, elevation_col0, lib=None):
+    """atmrt_overlay_resolve_ticks (host code, no device): the ticks gen_ticks would draw, sorted by (vertical, pos)."""
+    lib = lib or _lib.load()
+    az = np.ascontiguousarray(azimuth_row0, dtype=np.float64)
+    el = np.ascontiguousarray(elevation_col0, dtype=np.float64)
+    n = C.c_size_t()
+    rc = lib.atmrt_overlay_resolve_ticks(C.byref(params_pod), C.byref(overlay), az.ctypes.data, el.ctypes.data, None, 0, C.byref(n))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_overlay_resolve_ticks refused its arguments")
+    arr = (_abi.DrawnTick * max(1, n.value))()
+    rc = lib.atmrt_overlay_resolve_ticks(C.byref(params_pod), C.byref(overlay), az.ctypes.data, el.ctypes.data, arr, n.value, C.byref(n))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_overlay_resolve_ticks refused its arguments")
+    return _drawn_ticks(arr, n.value)
+
+
+def _max_ticks(overlay, width, height):
+    # one tick per pixel position at most: two definitions on one pixel leave one tick
+    return (width if overlay.n_ticks else 0) + (height if overlay.n_vertical_ticks else 0)
+
+
+def draw_overlay(ctx, overlay, rgb):
+    """Ticks, flat-horizon and eye-level lines of the last generate() on `ctx` drawn over `rgb` ([height][width][3] uint8, e.g. of
+    draw_image).  Returns (image, ticks, flat_horizon_deg): the resolved ticks carry the label strings for the host to
+    rasterise; flat_horizon_deg is NaN when that line is not drawn."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8).copy()
+    cap = _max_ticks(overlay, rgb.shape[1], rgb.shape[0])
+    arr, n, deg = (_abi.DrawnTick * max(1, cap))(), C.c_size_t(), C.c_double()
+    ctx.check(ctx.lib.atmrt_draw_overlay(ctx.handle, C.byref(overlay), rgb.ctypes.data, arr, cap, C.byref(n), C.byref(deg)))
+    return rgb, _drawn_ticks(arr, n.value), deg.value
+
+
+def draw_overlay_device(ctx, overlay, rgb_ptr, width, height, planes=None):
+    """The same on a device image (a raw pointer, e.g. tensor.data_ptr()); planes = (azimuth_ptr, elevation_angle_ptr) draws on
+    explicit [height][width] device planes (a gathered multi-device frame) instead of the context's last frame.
+    Returns (ticks, flat_horizon_deg)."""
+    cap = _max_ticks(overlay, width, height)
+    arr, n, deg = (_abi.DrawnTick * max(1, cap))(), C.c_size_t(), C.c_double()
+    if planes is None:
+        ctx.check(ctx.lib.atmrt_draw_overlay_device(ctx.handle, C.byref(overlay), rgb_ptr, arr, cap, C.byref(n), C.byref(deg)))
+    else:
+        ctx.check(ctx.lib.atmrt_draw_overlay_planes_device(ctx.handle, C.byref(overlay), planes[0], planes[1], width, height, rgb_ptr,
+                                                           arr, cap, C.byref(n), C.byref(deg)))
+    return _drawn_ticks(arr, n.value), deg.value
+
+
 # ---- integrator / sampler harnesses (ray_path.rs, atm_printer.rs, elev_profile.rs) -------------
 def ray_paths(ctx, h0, angles_deg, step, n_steps, straight=False):
     ang = np.ascontiguousarray(angles_deg, dtype=np.float64)

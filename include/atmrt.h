@@ -340,6 +340,69 @@ int atmrt_draw_image(atmrt_ctx* ctx, const atmrt_coloring_t* coloring, uint8_t* 
 /* Same, into caller-provided device memory (3 B per pixel instead of 88 B per pixel to gather across GPUs). */
 int atmrt_draw_image_device(atmrt_ctx* ctx, const atmrt_coloring_t* coloring, uint8_t* rgb_device);
 
+/* ---- the annotations of renderer::output_image (src/renderer/mod.rs:28-365, 416-431) on the device image: azimuth / elevation
+ * ticks, the flat-Earth "horizon" line and the eye-level line, drawn over the RGB8 image of atmrt_draw_image*.  Tick labels are
+ * text: the library resolves their strings and positions, the host rasterises them (anchors: renderer/mod.rs:292-321). */
+typedef enum atmrt_tick_kind { ATMRT_TICK_SINGLE = 0, ATMRT_TICK_MULTIPLE = 1 } atmrt_tick_kind;
+/* Tick / VerticalTick, params.rs:325-368. */
+typedef struct atmrt_tick {
+  int32_t kind;     /* atmrt_tick_kind */
+  uint32_t size;    /* length of the tick line [px] */
+  double angle;     /* Single: azimuth (ticks) or elevation (vertical_ticks) [deg] */
+  double bias;      /* Multiple: ticks at bias + k step inside the frame */
+  double step;      /* Multiple: > 0 and finite (the reference would never leave its loop otherwise) */
+  int32_t labelled; /* bool */
+  int32_t _pad;
+} atmrt_tick_t;
+/* output.ticks, output.vertical_ticks, output.show_eye_level, output.show_flat_horizon (params.rs:403-410); the arrays are
+ * borrowed for the duration of the call. */
+typedef struct atmrt_overlay {
+  const atmrt_tick_t* ticks;          /* [n_ticks] */
+  const atmrt_tick_t* vertical_ticks; /* [n_vertical_ticks] */
+  uint32_t n_ticks;
+  uint32_t n_vertical_ticks;
+  int32_t show_eye_level;    /* bool: the line of elevation 0, colour [255,128,255] */
+  int32_t show_flat_horizon; /* bool: drawn only on a flat earth shape with refraction (see atmrt_draw_overlay_device), [0,128,255] */
+} atmrt_overlay_t;
+#define ATMRT_TICK_LABEL_BYTES 32
+/* One tick as it is drawn: a white line (pos, 0) -> (pos, size), or (0, pos) -> (size, pos) when vertical. */
+typedef struct atmrt_drawn_tick {
+  uint32_t pos;      /* x of a horizontal tick, y of a vertical one */
+  uint32_t size;
+  int32_t labelled;  /* the host draws `label` at (pos - 8, size + 5), a vertical tick's at (size + 5, pos - 7) */
+  int32_t vertical;
+  char label[ATMRT_TICK_LABEL_BYTES]; /* format!("{:.1$}", angle, decimals), NUL-terminated (cut to 31 bytes) */
+} atmrt_drawn_tick_t;
+/* gen_ticks (renderer/mod.rs:227-268) with into_draw_ticks[_vertical], azimuth_to_x, elevation_to_y and round_decimals: host
+ * code, no device, ctx-free.  azimuth_row0 is row 0 of the azimuth plane, elevation_col0 column 0 of the elevation plane; their
+ * lengths are the image's: params->height and params->width, or the width of the column shard when col_begin / col_end are set
+ * — a shard is an image of its own to the overlay, while the ranges of `Multiple` ticks (and the aspect ratio of the vertical
+ * ones) keep coming from params->frame and params->width / height.  drawn[0 .. *n_drawn) comes out sorted by (vertical, pos): two
+ * definitions that land on one pixel leave the larger size, the earlier one when equal.  drawn == NULL only counts; capacity
+ * < *n_drawn, an image narrower or lower than 2 pixels, a step that is not positive and finite, or more than 2^20 ticks of one
+ * definition: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_overlay_resolve_ticks(const atmrt_params_t* params, const atmrt_overlay_t* overlay, const double* azimuth_row0,
+                                const double* elevation_col0, atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn);
+/* draw_ticks, then the flat horizon, then eye level (output_image, renderer/mod.rs:416-431; a later layer overwrites an earlier
+ * one) onto rgb_device, [height][width][3] of the frame — or column shard — of the last atmrt_generate / atmrt_generate_device on
+ * ctx, whose azimuth / elevation planes are still in HBM: same rules as atmrt_draw_image_device (ATMRT_ERR_STATE without a
+ * frame or after a failed one).  Each line takes its row per column from find_elev (:325-343) and joins neighbouring columns with
+ * Bresenham segments; pixels outside the image are skipped.  The flat horizon is drawn when show_flat_horizon is
+ * set, the earth model's shape is flat (earth_model/mod.rs:95-112) and straight_rays is off, at the elevation
+ * degrees(acos(1 / n(observer altitude))): *flat_horizon_deg returns it, NaN when the line is not drawn.  drawn / capacity /
+ * n_drawn as above (all three optional).  An image narrower or lower than 2 pixels: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_draw_overlay_device(atmrt_ctx* ctx, const atmrt_overlay_t* overlay, uint8_t* rgb_device, atmrt_drawn_tick_t* drawn,
+                              size_t capacity, size_t* n_drawn, double* flat_horizon_deg);
+/* The same onto a host image (in and out), staged through the context's device. */
+int atmrt_draw_overlay(atmrt_ctx* ctx, const atmrt_overlay_t* overlay, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity,
+                       size_t* n_drawn, double* flat_horizon_deg);
+/* The same with explicit [height][width] device planes: the route of a gathered multi-device frame (every device holds the whole
+ * planes after atmrt_generate_image_device; pass one device's planes and its image of atmrt_draw_image_gathered_device).  All
+ * three pointers must be memory of one device of ctx.  Frame and position are those set on ctx. */
+int atmrt_draw_overlay_planes_device(atmrt_ctx* ctx, const atmrt_overlay_t* overlay, const double* azimuth,
+                                     const double* elevation_angle, uint32_t width, uint32_t height, uint8_t* rgb_device,
+                                     atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —

@@ -239,4 +239,33 @@ inline std::unique_ptr<Generator> make_generator(const Params& params, const Ter
   }
 }
 
+// Output's annotations (params.rs:403-410): ticks, vertical_ticks, show_eye_level, show_flat_horizon.
+struct Tick { // Tick / VerticalTick, params.rs:325-368
+  atmrt_tick_t pod{};
+  static Tick Single(double angle, uint32_t size, bool labelled) { return Tick{atmrt_tick_t{ATMRT_TICK_SINGLE, size, angle, 0.0, 0.0, labelled ? 1 : 0, 0}}; }
+  static Tick Multiple(double bias, double step, uint32_t size, bool labelled) { return Tick{atmrt_tick_t{ATMRT_TICK_MULTIPLE, size, 0.0, bias, step, labelled ? 1 : 0, 0}}; }
+};
+struct Overlay {
+  std::vector<Tick> ticks, vertical_ticks;
+  bool show_eye_level = false, show_flat_horizon = false;
+};
+struct DrawnOverlay {
+  std::vector<atmrt_drawn_tick_t> ticks; // with the label strings for the host's text renderer, sorted by (vertical, pos)
+  double flat_horizon_deg;               // NaN when the flat-horizon line is not drawn
+};
+// renderer::output_image's draw_ticks / draw_const_elev (renderer/mod.rs:419-431) for the frame the last generate() on `terrain`
+// produced, over rgb = [height][width][3] (e.g. of atmrt_draw_image); the labels' text is left to the host.
+inline DrawnOverlay draw_overlay(const Terrain& terrain, const Overlay& overlay, uint8_t* rgb, uint32_t width, uint32_t height) {
+  std::vector<atmrt_tick_t> h, v;
+  for (const Tick& t : overlay.ticks) h.push_back(t.pod);
+  for (const Tick& t : overlay.vertical_ticks) v.push_back(t.pod);
+  atmrt_overlay_t pod{h.data(), v.data(), (uint32_t)h.size(), (uint32_t)v.size(), overlay.show_eye_level ? 1 : 0, overlay.show_flat_horizon ? 1 : 0};
+  DrawnOverlay out;
+  out.ticks.resize((h.empty() ? 0 : width) + (v.empty() ? 0 : height) + 1); // at most one tick per pixel position
+  size_t n = 0;
+  terrain.check(atmrt_draw_overlay(terrain.ctx(), &pod, rgb, out.ticks.data(), out.ticks.size(), &n, &out.flat_horizon_deg));
+  out.ticks.resize(n);
+  return out;
+}
+
 } // namespace atmrt_host
