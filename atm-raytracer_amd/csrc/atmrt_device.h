@@ -375,6 +375,21 @@ static inline RectRec carve_rec(double* base, size_t n) {
   r.pl1 = base + 3 * n;
   return r;
 }
+// the four values of a crossing into entry k of a record (RectRec, or an OverflowArena: the same four arrays), and from one to another
+template <class Rec>
+static __device__ __forceinline__ void rec_store(const Rec& r, size_t k, double re0, double pl0, double re1, double pl1) {
+  r.re0[k] = re0;
+  r.pl0[k] = pl0;
+  r.re1[k] = re1;
+  r.pl1[k] = pl1;
+}
+template <class Dst, class Src>
+static __device__ __forceinline__ void rec_copy(const Dst& dst, size_t k, const Src& src, size_t q) {
+  dst.re0[k] = src.re0[q];
+  dst.pl0[k] = src.pl0[q];
+  dst.re1[k] = src.re1[q];
+  dst.pl1[k] = src.pl1[q];
+}
 
 // where the out-of-line object step of the lean march (object_step_impl, atmrt_march_impl.h) writes: the general tracer's arenas of
 // the counting pass.  A copy lives in HBM beside a copy of the Frame (Workspace::step_ctx): an out-of-line device function cannot

@@ -106,10 +106,7 @@ static __device__ __forceinline__ void overflow_append(const OverflowArena& ovf,
     ovf.pixel[k] = p;
     ovf.ordinal[k] = ovf.color_tag ? ordinal | OVERFLOW_LEAN : ordinal;
     ovf.step[k] = step;
-    ovf.re0[k] = re0;
-    ovf.pl0[k] = pl0;
-    ovf.re1[k] = re1;
-    ovf.pl1[k] = pl1;
+    rec_store(ovf, k, re0, pl0, re1, pl1);
     if (ovf.color_tag) ovf.color_tag[k] = ATMRT_COLOR_TERRAIN;
   }
 }
@@ -202,12 +199,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
     uint64_t k = (uint64_t)p * RECT_SLOTS + count;
     const uint64_t k0 = k;
     step_emit(hits, sk->slot_packed, sk->slot_step, sk->slot_pixel, k, p, io->step_index, lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length);
-    for (uint64_t q = k0; q < k; q++) { // terrain points: what k_rect_finalize_list needs
-      sk->slots.re0[q] = re0;
-      sk->slots.pl0[q] = pl0;
-      sk->slots.re1[q] = sh;
-      sk->slots.pl1[q] = path_length;
-    }
+    for (uint64_t q = k0; q < k; q++) rec_store(sk->slots, q, re0, pl0, sh, path_length); // terrain points: what k_rect_finalize_list needs
   } else if (hits.n && hits.n <= STEP_CANDIDATES && sk->ovf.cap) { // beyond the slots: the step's points into the overflow arena
     const unsigned long long base = atomicAdd(&sk->counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
     if (base + (unsigned long long)hits.n <= sk->ovf.cap) {
@@ -215,10 +207,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
       step_emit(hits, sk->ovf_packed, sk->ovf.step, sk->ovf.pixel, kk, p, io->step_index, lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length);
       for (uint64_t q = base; q < kk; q++) {
         sk->ovf.ordinal[q] = count + (unsigned)(q - base);
-        sk->ovf.re0[q] = re0;
-        sk->ovf.pl0[q] = pl0;
-        sk->ovf.re1[q] = sh;
-        sk->ovf.pl1[q] = path_length;
+        rec_store(sk->ovf, q, re0, pl0, sh, path_length);
       }
     }
   }
@@ -233,265 +222,342 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
 // wavefront of the last k_rect_march launch, read back through atmrt_debug_timeline.
 static __device__ unsigned long long g_timeline[3 * 65536 + 4 * 32768];
 static __device__ unsigned long long g_slices[4 * 262144 + 8]; // [0] = count; then {group | i0 << 32, start, end, wave | hw_id << 32}
+static __device__ __forceinline__ int timeline_wave_max(int v) {
+  for (int o = 32; o; o >>= 1) {
+    const int u = __shfl_xor(v, o, 64);
+    v = u > v ? u : v;
+  }
+  return v;
+}
 #endif
+
+// Where a lean march (k_rect_march, k_rect_march_first / _cont) leaves its results, by MODE
+struct MarchSinks {
+  int32_t* hit_step;    // MODE 0: [plane] step of the first crossing, or -1; MODE 3: [plane] 1 = the ray is left to the general tracer
+                        // (which voids the ray's overflow records, k_rect_scatter_trace_overflow)
+  RectRec rec;          // MODE 0: [plane]; MODE 1: slot-major [RECT_SLOTS][plane]; MODE 2: the pixel-ordered list;
+                        // MODE 3: pixel-major [plane][RECT_SLOTS] (the general tracer's slot arena)
+  uint32_t* step;       // MODE 1 - 3: the step of every entry of rec
+  OverflowArena ovf;    // MODE 1, 3: crossings beyond the slots
+  uint32_t* slot_tag;   // MODE 3: the slot arena's colour tags (the march writes TERRAIN)
+  // MODE 2: the crossings of pixel p are entries hit_offset[p] ... of the list; the launch may be restricted to a list of pixels
+  // (those whose crossings did not fit the slots of the counting march)
+  const uint64_t* hit_offset;
+  uint32_t* list_pixel;
+  const uint32_t* pixel_list; // or null: every pixel of the plane
+  uint32_t n_list;
+  // MODE 3: copies of the frame and of the tracer's arenas in HBM, for the out-of-line object step (object_step_impl)
+  const Frame* frame_dev;
+  const ObjectStepSinks* step_sinks_dev;
+};
+
+// Pixel p of the frame -> its ray: direction and elevation angle, geodesic calculator, stepper at the observer
+static __device__ __forceinline__ void rect_ray_setup(const Frame& f, const Earth& e, size_t p, double alt, double& direction, double& elevation,
+                                                      DirCalc& c, Stepper& s) {
+  const int y = (int)(p / (size_t)f.wl), x = (int)(p % (size_t)f.wl);
+  rect_ray_params(f.p, f.ph, f.c0 + x, y, direction, elevation);
+  dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
+  stepper_init(s, e.spherical != 0, e.shape_radius, alt, elevation);
+}
+static __device__ __forceinline__ void store_ray_angles(const DensePlanes& out, size_t p, double direction, double elevation) {
+  out.azimuth[p] = dm_to_degrees(direction); // not wrapped, rectilinear.rs:110-113
+  out.elevation_angle[p] = dm_to_degrees(elevation);
+}
+
+// MODE 3: the candidate list of one wavefront (arrays in LDS) and the distance at which the march looks at it next
+struct WaveList {
+  double *lo, *hi, *vlo, *vhi; // the union of the rays' intervals [lo, hi] of an object and its height band [vlo, vhi]
+  int* obj;
+  int n;
+  double x_wake;
+};
+// the lists of a workgroup of WAVES wavefronts: a __shared__ object of the kernel (nothing of it is touched unless MODE == 3)
+template <int MODE, int WAVES>
+struct WaveListLds {
+  static constexpr int W = MODE == 3 ? WAVES : 1, N = MODE == 3 ? WAVE_CAND : 1;
+  double lo[W][N], hi[W][N], vlo[W][N], vhi[W][N];
+  int obj[W][N];
+  __device__ __forceinline__ WaveList wave(int wv) { return WaveList{lo[wv], hi[wv], vlo[wv], vhi[wv], obj[wv], 0, dm_inf()}; }
+};
+// Builds the list of this wavefront from the rays of its active lanes (c: this lane's); false: the wavefront's rays are left to the
+// general tracer (no geometric pre-filter for this earth model: every ray tests every object; or more than WAVE_CAND candidates)
+template <int CALC>
+static __device__ __forceinline__ bool wave_list_build(const Frame& f, const Earth& e, const DirCalc& c, WaveList& wl) {
+  if (!candidates_supported<CALC>(e)) return false;
+  const Vec3 nrm = track_normal<CALC>(c);
+  int w_n = 0;
+  for (int j = 0; j < f.n_objects; j++) { // wave-uniform loop; the object's fields are scalar loads
+    double lo = dm_inf(), hi = -dm_inf();
+    double l, h;
+    if (candidate_interval<CALC>(e, c, nrm, f.objects[j], true, l, h)) lo = l, hi = h;
+    unsigned long long holders = __ballot(lo <= hi); // the active lanes for which the object is a candidate
+    if (holders) {
+      double wlo = dm_inf(), whi = -dm_inf();
+      for (; holders; holders &= holders - 1) { // union of their intervals (reads active lanes only)
+        const int src = __builtin_ctzll(holders);
+        const double l2 = __shfl(lo, src, 64), h2 = __shfl(hi, src, 64);
+        wlo = l2 < wlo ? l2 : wlo;
+        whi = h2 > whi ? h2 : whi;
+      }
+      if (w_n < WAVE_CAND && (threadIdx.x & 63) == 0) {
+        wl.lo[w_n] = wlo;
+        wl.hi[w_n] = whi;
+        wl.vlo[w_n] = f.objects[j].vlo;
+        wl.vhi[w_n] = f.objects[j].vhi;
+        wl.obj[w_n] = j;
+      }
+      w_n++;
+    }
+  }
+  wl.n = w_n < WAVE_CAND ? w_n : WAVE_CAND;
+  // lane 0 wrote the list, every lane of the wavefront reads it from here on: DS operations of one wave issue in order, but the
+  // dependence has to exist for the compiler too — a wavefront-scope release / acquire pair around a wave barrier
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int q = 0; q < wl.n; q++) // first interval that is not behind the start
+    if (wl.hi[q] >= 0.0) wl.x_wake = wl.lo[q] < wl.x_wake ? wl.lo[q] : wl.x_wake;
+  return w_n <= WAVE_CAND; // overflowed: the whole wavefront goes to the tracer
+}
+// The step with the samples at x - step and x (elevations re0, sh) against the list — wave-uniform: x and the list are the same for
+// every ray of the wavefront.  Inside an entry's interval and inside its height band: the step may involve that object (true).
+// Next wake: the nearest interval start ahead, or the next step while an interval is being crossed.
+static __device__ __forceinline__ bool wave_list_wake(WaveList& wl, double x_prev, double sx, double re0, double sh) {
+  double next = dm_inf();
+  bool object_step = false;
+  for (int q = 0; q < wl.n; q++) {
+    const double lo = wl.lo[q], hi = wl.hi[q];
+    if (hi < x_prev) continue;               // behind the step
+    if (lo > sx) {                           // ahead of it
+      next = lo < next ? lo : next;
+      continue;
+    }
+    next = sx;                               // being crossed: look again at the next step
+    const double vlo = wl.vlo[q], vhi = wl.vhi[q];
+    if (!((re0 < vlo && sh < vlo) || (re0 > vhi && sh > vhi))) object_step = true; // object_out_of_band is false
+  }
+  wl.x_wake = next;
+  return object_step;
+}
+
+// The state of one ray of the lean march between two steps (SliceState is its form in HBM between two slices)
+struct MarchRay {
+  Stepper s;
+  double sh, path_length;  // the newest sample (its x is s.x): ray elevation, path length
+  double diff0, re0, pl0;  // the sample before it: ray - terrain, ray elevation, path length
+  int first;               // MODE 0: step of the first crossing, or -1
+  unsigned count;          // crossings so far
+  uint64_t k;              // MODE 2: the ray's cursor in the pixel-ordered list
+};
+// what a lane adds to the device counters at the end of its kernel (count_wave_steps)
+struct MarchCount {
+  unsigned long long steps = 0, lookups = 0;
+  int esc_credit = -1; // >= 0: the ray escaped and was credited this many steps (escapes)
+};
+enum MarchEnd {
+  MARCH_ENDED,   // the ray has finished
+  MARCH_ON,      // the slice has ended, the ray marches on
+  MARCH_GIVEN_UP // MODE 3: the ray is left to the general tracer
+};
+
+// The start state and the first sample (PathIterator::next at the start state); false: an empty stream (the reference would panic)
+static __device__ __forceinline__ bool march_begin(const Frame& f, const Earth& e, const DirCalc& c, double alt, MarchRay& r, MarchCount& n) {
+  r.sh = r.re0 = alt; // TracingState::new(.., first_path.elev, 0.0, 0.0), utils.rs:208
+  r.path_length = r.pl0 = r.diff0 = 0.0;
+  r.first = -1;
+  r.count = 0;
+  if (0.0 > f.p.frame.max_distance || alt < -1000.0) return false;
+  double lat, lon;
+  coords_at_dist(e, c, 0.0, lat, lon);
+  r.diff0 = alt - terrain_elev_or_zero(f.tv, lat, lon);
+  n.lookups++;
+  return true;
+}
+
+// A crossing between the ray's last two samples, MODE 1 - 3 (MODE 0 keeps the four values in registers: march_finish)
+template <int MODE>
+static __device__ __forceinline__ void crossing_store(const Frame& f, const MarchSinks& sinks, unsigned long long* counters, size_t p, MarchRay& r,
+                                                      uint32_t step) {
+  if (MODE == 2) {
+    sinks.step[r.k] = step;
+    sinks.list_pixel[r.k] = (uint32_t)p;
+    rec_store(sinks.rec, r.k, r.re0, r.pl0, r.sh, r.path_length);
+    r.k++;
+  } else if (r.count < (unsigned)RECT_SLOTS) {
+    const size_t q = MODE == 3 ? p * RECT_SLOTS + r.count : (size_t)r.count * ((size_t)f.wl * f.h) + p;
+    sinks.step[q] = step;
+    if (MODE == 3) sinks.slot_tag[q] = ATMRT_COLOR_TERRAIN;
+    rec_store(sinks.rec, q, r.re0, r.pl0, r.sh, r.path_length);
+  } else {
+    overflow_append(sinks.ovf, counters, (uint32_t)p, r.count, step, r.re0, r.pl0, r.sh, r.path_length);
+  }
+}
+
+// THE step loop of the lean march: steps i0 + 1 ... of ray p, whose state is in registers.  SLICED: at most `slice` steps
+// (k_rect_march_first / _cont), else to the end of the ray (k_rect_march; a whole-ray march is a slice that never ends).  DRAIN: the
+// small-launch variant of k_rect_march (the priority ladder; object steps out of line, as in the slices).
+template <int MODE, int CALC, bool CUBIC, bool SLICED, bool DRAIN>
+static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Earth& e, const DirCalc& c, MarchRay& r, MarchCount& n, int i0, int slice,
+                                                       const MarchSinks& sinks, unsigned long long* counters, size_t p, WaveList& wl) {
+  const bool sph = e.spherical != 0;
+  const double radius = e.shape_radius;
+  const bool straight = f.p.straight_rays != 0;
+  const double step = f.p.simulation_step, max_dist = f.p.frame.max_distance;
+  const double skip_above = f.tv.skip_above;
+  const bool opaque = f.p.terrain_alpha == 1.0; // (MODE 0 is launched over opaque terrain only, MODE 1 over translucent only)
+  const double esc_floor = MODE == 3 ? escape_floor_objects(f.esc_floor, wl.vhi, wl.n) : f.esc_floor;
+  const int i_end = i0 + slice;
+  double sx = r.s.x, lat, lon;
+  for (int i = i0 + 1;; i++) {
+    if (DRAIN && (i & (DRAIN_PRIO_BAND - 1)) == 0) { // see DRAIN_PRIO_MAX_BLOCKS
+      const int band = i / DRAIN_PRIO_BAND;
+      if (band == 1) __builtin_amdgcn_s_setprio(2);
+      else if (band == 2) __builtin_amdgcn_s_setprio(1);
+      else if (band == 3) __builtin_amdgcn_s_setprio(0);
+    }
+    bool tame;
+    RayState nx = stepper_next<CUBIC>(r.s, *f.atm, sph, radius, straight, step, tame);
+    if (straight) tame = __all(calc_dist_in_band(*f.atm, r.sh) && calc_dist_in_band(*f.atm, nx.h));
+    r.path_length += calc_dist(sph, radius, sx, r.sh, nx.x, nx.h, tame, f.inv_shape_radius);
+    sx = nx.x;
+    r.sh = nx.h;
+    if (sx > max_dist || r.sh < -1000.0 || !(sx <= max_dist)) return MARCH_ENDED; // rectilinear.rs:178 (+ NaN guard)
+    // x_prev: a little before the older sample (its x is sx - step up to rounding)
+    if (MODE == 3 && sx >= wl.x_wake && wave_list_wake(wl, sx - step * 1.000001, sx, r.re0, r.sh)) {
+      // A launch of many resident sets (the whole frame: neither SLICED nor DRAIN) abandons the ray here and leaves it to the general
+      // tracer, whose own launch is then large enough to fill the chip (config 5: 38 ms of VALU-saturated work for 11 % of the rays —
+      // there is nothing to hide, and the out-of-line steps would only add their call overhead: 308 against 328 ms per frame).
+      // A small launch (a column tile of a multi-GPU frame) keeps the ray and does the step out of line: the tracer's launch
+      // for a tile would be under two wavefronts per SIMD, 12 ms whatever the tile's size (8 tiles: 54 -> 43 ms).
+      if (!SLICED && !DRAIN) return MARCH_GIVEN_UP;
+      ObjectStepIO io; // this lane's step in full, out of line (object_step_impl above); the others wait
+      io.c = c;
+      io.d0 = f.xs[i - 1]; // the stepper's x of the older sample: 0 + step + ... (the same additions as xs)
+      io.sx = sx, io.re0 = r.re0, io.sh = r.sh, io.pl0 = r.pl0, io.path_length = r.path_length;
+      io.pixel = (uint32_t)p, io.step_index = i - 1, io.count = r.count;
+      object_step_impl<CALC>(sinks.frame_dev, sinks.step_sinks_dev, &io, wl.lo, wl.hi, wl.obj, wl.n);
+      r.count = io.count;
+      n.lookups += 2;
+      n.steps++;
+      if (io.finish) return MARCH_ENDED;
+      r.diff0 = io.diff1;
+      r.re0 = r.sh;
+      r.pl0 = r.path_length;
+      if (SLICED && i == i_end) return MARCH_ON;
+      continue;
+    }
+    // A sample above every post of the mosaic is above the terrain, whatever its geodesic point: ray - terrain is positive and
+    // only its SIGN enters the test below (the epilogue rebuilds the bracketing samples in full), so the geodesic point and
+    // the lookup are skipped and any positive number stands for the difference.  Wavefronts are 64 columns of one row: sky
+    // rows leave the terrain's height range together.  NaN heights take the full path.
+    double diff1 = 1.0;
+    if (!(r.sh > skip_above)) {
+      coords_at_dist(e, c, sx, lat, lon);
+      diff1 = r.sh - terrain_elev_or_zero(f.tv, lat, lon);
+      n.lookups++;
+    }
+    n.steps++;
+    if (r.diff0 * diff1 < 0.0) { // utils.rs:222
+      // MODE 0: the record is stored after the march (march_finish): opaque terrain ends the ray here, the four values stay as they are
+      if (MODE == 0) r.first = i - 1;
+      else crossing_store<MODE>(f, sinks, counters, p, r, (uint32_t)(i - 1));
+      r.count++;
+      if (opaque) return MARCH_ENDED; // utils.rs:237-239, 283-285
+    }
+    if (escapes(f, r.s, straight, r.sh, r.re0, esc_floor)) { // nothing left to find: credit the rest of the march and leave
+      n.esc_credit = f.march_steps - i;
+      if (n.esc_credit >= 0) n.steps += (unsigned)n.esc_credit;
+      return MARCH_ENDED;
+    }
+    r.diff0 = diff1;
+    r.re0 = r.sh;
+    r.pl0 = r.path_length;
+    if (SLICED && i == i_end) return MARCH_ON;
+  }
+}
+
+// the ray has ended with the march: its per-pixel results
+template <int MODE>
+static __device__ __forceinline__ void march_finish(const DensePlanes& out, const MarchSinks& sinks, unsigned long long* counters, size_t p,
+                                                    const MarchRay& r) {
+  if (MODE == 0) {
+    // ray elevation and path length at the two samples that bracket the crossing
+    if (r.first >= 0) rec_store(sinks.rec, p, r.re0, r.pl0, r.sh, r.path_length);
+    out.hit_count[p] = r.first >= 0 ? 1u : 0u;
+    sinks.hit_step[p] = r.first;
+  } else if (MODE != 2) {
+    out.hit_count[p] = r.count;
+    if (MODE == 3) sinks.hit_step[p] = 0; // the ray stayed with the march: its overflow records count (k_rect_scatter_trace_overflow)
+    if (r.count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
+  }
+}
+
+// End of a marching kernel: the wavefront's ray-steps in one atomic — LEAN (the lean march): also its terrain lookups and the
+// escape counters.  Returns the wavefront's steps.
+template <bool LEAN>
+static __device__ __forceinline__ unsigned long long count_wave_steps(unsigned long long* counters, unsigned long long steps,
+                                                                      unsigned long long lookups, int esc_credit) {
+  steps = wave_sum(steps);
+  if (LEAN) lookups = wave_sum(lookups);
+  if ((threadIdx.x & 63) == 0 && steps) {
+    atomicAdd(&counters[CTR_RAY_STEPS], steps);
+    if (LEAN) atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
+  }
+  if (LEAN) escape_count(counters, esc_credit);
+  return steps;
+}
+
 template <int MODE, int CALC, bool CUBIC, bool DRAIN>
-__global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMRT_MARCH_WAVES_SMALL : ATMRT_MARCH_WAVES) void k_rect_march(Frame f, DensePlanes out, int32_t* __restrict__ hit_step,
-                                                    const uint64_t* __restrict__ hit_offset, RectRec rec,
-                                                    uint32_t* __restrict__ list_step, uint32_t* __restrict__ list_pixel,
-                                                    unsigned long long* __restrict__ counters,
-                                                    const uint32_t* __restrict__ pixel_list, uint32_t n_list, OverflowArena ovf,
-                                                    const Frame* __restrict__ frame_dev, const ObjectStepSinks* __restrict__ sinks_dev) {
+__global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMRT_MARCH_WAVES_SMALL : ATMRT_MARCH_WAVES) void k_rect_march(
+    Frame f, DensePlanes out, MarchSinks sinks, unsigned long long* __restrict__ counters) {
 #ifdef ATMRT_TIMELINE
   const unsigned long long tl_t0 = wall_clock64();
 #endif
   stage_dm_tables();
-  constexpr bool drain_prio = DRAIN;
-  if (drain_prio) __builtin_amdgcn_s_setprio(3);
+  if (DRAIN) __builtin_amdgcn_s_setprio(3);
   const size_t plane = (size_t)f.wl * f.h;
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  // MODE 2 may be restricted to a list of pixels (those whose crossings did not fit the slots of the counting march)
-  const bool live = pixel_list ? tid < n_list : tid < plane;
-  const size_t p = pixel_list ? (live ? pixel_list[tid] : 0) : tid;
-  unsigned long long steps = 0, lookups = 0;
-  int esc_credit = -1; // >= 0: the ray escaped and was credited this many steps (escapes below)
+  const bool live = sinks.pixel_list ? tid < sinks.n_list : tid < plane;
+  const size_t p = sinks.pixel_list ? (live ? sinks.pixel_list[tid] : 0) : tid;
+  MarchCount n;
+  __shared__ WaveListLds<MODE, 4> lists;
   if (live) {
     const Earth e = earth_for<CALC>(f);
-    const int y = (int)(p / (size_t)f.wl), x = (int)(p % (size_t)f.wl);
-    const bool sph = e.spherical != 0;
-    const double radius = e.shape_radius;
-    const bool straight = f.p.straight_rays != 0;
-    const double step = f.p.simulation_step, max_dist = f.p.frame.max_distance;
-    const double skip_above = f.tv.skip_above;
-    const bool opaque = f.p.terrain_alpha == 1.0;
     const double alt = *f.alt;
     double direction, elevation;
-    rect_ray_params(f.p, f.ph, f.c0 + x, y, direction, elevation);
     DirCalc c;
-    dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
-    Stepper s;
-    stepper_init(s, sph, radius, alt, elevation);
-    unsigned count = 0;
-    int first = -1;
-    uint64_t k = MODE == 2 ? hit_offset[p] : 0;
-    bool object_ray = false; // MODE 3: this ray is left to the general tracer
-    int w_n = 0;             // MODE 3: entries of the wavefront's candidate list
-    double x_wake = dm_inf();
-    double esc_floor = f.esc_floor; // MODE 3: raised to the tops of the wavefront's candidate objects
-    __shared__ double w_lo[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1], w_hi[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1],
-        w_vlo[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1], w_vhi[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1];
-    __shared__ int w_obj[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1];
-    const int wv = threadIdx.x >> 6;
-    if (MODE == 3) {
-      if (!candidates_supported<CALC>(e)) {
-        object_ray = true; // no geometric pre-filter for this earth model: every ray tests every object
-      } else {
-        const Vec3 nrm = track_normal<CALC>(c);
-        for (int j = 0; j < f.n_objects; j++) { // wave-uniform loop; the object's fields are scalar loads
-          double lo = dm_inf(), hi = -dm_inf();
-          double l, h;
-          if (candidate_interval<CALC>(e, c, nrm, f.objects[j], true, l, h)) lo = l, hi = h;
-          unsigned long long holders = __ballot(lo <= hi); // the active lanes for which the object is a candidate
-          if (holders) {
-            double wlo = dm_inf(), whi = -dm_inf();
-            for (; holders; holders &= holders - 1) { // union of their intervals (reads active lanes only)
-              const int src = __builtin_ctzll(holders);
-              const double l2 = __shfl(lo, src, 64), h2 = __shfl(hi, src, 64);
-              wlo = l2 < wlo ? l2 : wlo;
-              whi = h2 > whi ? h2 : whi;
-            }
-            lo = wlo;
-            hi = whi;
-            if (w_n < WAVE_CAND) {
-              if ((threadIdx.x & 63) == 0) {
-                w_lo[wv][w_n] = lo;
-                w_hi[wv][w_n] = hi;
-                w_vlo[wv][w_n] = f.objects[j].vlo;
-                w_vhi[wv][w_n] = f.objects[j].vhi;
-                w_obj[wv][w_n] = j;
-              }
-            }
-            w_n++;
-          }
-        }
-        if (w_n > WAVE_CAND) object_ray = true; // the list overflowed: leave the whole wavefront to the tracer
-        // lane 0 wrote the list, every lane of the wavefront reads it from here on: DS operations of one wave issue in order, but the
-        // dependence has to exist for the compiler too — a wavefront-scope release / acquire pair around a wave barrier
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int q = 0; q < w_n && q < WAVE_CAND; q++) // first interval that is not behind the start
-          if (w_hi[wv][q] >= 0.0) x_wake = w_lo[wv][q] < x_wake ? w_lo[wv][q] : x_wake;
-        esc_floor = escape_floor_objects(esc_floor, w_vhi[wv], w_n < WAVE_CAND ? w_n : WAVE_CAND);
-      }
-    }
-    // first sample (PathIterator::next at the start state); the reference would panic on an empty stream
-    if (!(0.0 > max_dist || alt < -1000.0) && !object_ray) {
-      double lat, lon;
-      coords_at_dist(e, c, 0.0, lat, lon);
-      double diff0 = alt - terrain_elev_or_zero(f.tv, lat, lon);
-      lookups++;
-      double re0 = alt, pl0 = 0.0; // TracingState::new(.., first_path.elev, 0.0, 0.0), utils.rs:208
-      double sx = 0.0, sh = alt, path_length = 0.0;
-      for (int i = 1;; i++) {
-        if (drain_prio && (i & (DRAIN_PRIO_BAND - 1)) == 0) { // see DRAIN_PRIO_MAX_BLOCKS
-          const int band = i / DRAIN_PRIO_BAND;
-          if (band == 1) __builtin_amdgcn_s_setprio(2);
-          else if (band == 2) __builtin_amdgcn_s_setprio(1);
-          else if (band == 3) __builtin_amdgcn_s_setprio(0);
-        }
-        bool tame;
-        RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step, tame);
-        if (straight) tame = __all(calc_dist_in_band(*f.atm, sh) && calc_dist_in_band(*f.atm, st.h));
-        path_length += calc_dist(sph, radius, sx, sh, st.x, st.h, tame, f.inv_shape_radius);
-        sx = st.x;
-        sh = st.h;
-        if (sx > max_dist || sh < -1000.0 || !(sx <= max_dist)) break; // rectilinear.rs:178 (+ NaN guard)
-        if (MODE == 3 && sx >= x_wake) { // wave-uniform: x and the list are the same for every ray of the wavefront
-          // this step (the samples at x - step and x) against the list: inside an entry's interval and inside its height band ->
-          // the step may involve that object: the ray goes to the tracer.  Next wake: the nearest interval start ahead, or the
-          // next step while an interval is being crossed.
-          const double x_prev = sx - step * 1.000001; // a little before the older sample (its x is sx - step up to rounding)
-          double next = dm_inf();
-          const int n_e = w_n < WAVE_CAND ? w_n : WAVE_CAND;
-          bool object_step = false;
-          for (int q = 0; q < n_e; q++) {
-            const double lo = w_lo[wv][q], hi = w_hi[wv][q];
-            if (hi < x_prev) continue;               // behind the step
-            if (lo > sx) {                           // ahead of it
-              next = lo < next ? lo : next;
-              continue;
-            }
-            next = sx;                               // being crossed: look again at the next step
-            const double vlo = w_vlo[wv][q], vhi = w_vhi[wv][q];
-            if (!((re0 < vlo && sh < vlo) || (re0 > vhi && sh > vhi))) object_step = true; // object_out_of_band is false
-          }
-          x_wake = next;
-          // A launch of many resident sets (the whole frame: DRAIN false) abandons the ray here and leaves it to the general tracer,
-          // whose own launch is then large enough to fill the chip (config 5: 38 ms of VALU-saturated work for 11 % of the rays —
-          // there is nothing to hide, and the out-of-line steps would only add their call overhead: 308 against 328 ms per frame).
-          // A small launch (a column tile of a multi-GPU frame: DRAIN true) keeps the ray and does the step out of line: the
-          // tracer's launch for a tile would be under two wavefronts per SIMD, 12 ms whatever the tile's size (8 tiles: 54 -> 43 ms).
-          if (object_step && !DRAIN) {
-            object_ray = true;
-            break;
-          }
-          if (object_step) { // this lane's step in full, out of line (object_step_impl above); the others wait
-            ObjectStepIO io;
-            io.c = c;
-            io.d0 = f.xs[i - 1]; // the stepper's x of the older sample: 0 + step + ... (the same additions as xs)
-            io.sx = sx, io.re0 = re0, io.sh = sh, io.pl0 = pl0, io.path_length = path_length;
-            io.pixel = (uint32_t)p, io.step_index = i - 1, io.count = count;
-            object_step_impl<CALC>(frame_dev, sinks_dev, &io, w_lo[wv], w_hi[wv], w_obj[wv], n_e);
-            count = io.count;
-            lookups += 2;
-            steps++;
-            if (io.finish) break;
-            diff0 = io.diff1;
-            re0 = sh;
-            pl0 = path_length;
-            continue;
-          }
-        }
-        // A sample above every post of the mosaic is above the terrain, whatever its geodesic point: ray - terrain is positive and
-        // only its SIGN enters the test below (the epilogue rebuilds the bracketing samples in full), so the geodesic point and
-        // the lookup are skipped and any positive number stands for the difference.  Wavefronts are 64 columns of one row: sky
-        // rows leave the terrain's height range together.  NaN heights take the full path.
-        double diff1 = 1.0;
-        if (!(sh > skip_above)) {
-          coords_at_dist(e, c, sx, lat, lon);
-          diff1 = sh - terrain_elev_or_zero(f.tv, lat, lon);
-          lookups++;
-        }
-        steps++;
-        if (diff0 * diff1 < 0.0) { // utils.rs:222
-          if (MODE == 0) {
-            first = i - 1; // the record is stored after the loop: opaque terrain ends the march here, the four values stay as they are
-          } else if (MODE == 1) {
-            if (count < (unsigned)RECT_SLOTS) { // slot arrays come in through list_step / rec, slot-major
-              const size_t q = (size_t)count * plane + p;
-              list_step[q] = (uint32_t)(i - 1);
-              rec.re0[q] = re0;
-              rec.pl0[q] = pl0;
-              rec.re1[q] = sh;
-              rec.pl1[q] = path_length;
-            } else {
-              overflow_append(ovf, counters, (uint32_t)p, count, (uint32_t)(i - 1), re0, pl0, sh, path_length);
-            }
-          } else if (MODE == 2) {
-            list_step[k] = (uint32_t)(i - 1);
-            list_pixel[k] = (uint32_t)p;
-            rec.re0[k] = re0;
-            rec.pl0[k] = pl0;
-            rec.re1[k] = sh;
-            rec.pl1[k] = path_length;
-            k++;
-          } else if (MODE == 3) {
-            if (count < (unsigned)RECT_SLOTS) { // the general tracer's slot arena, pixel-indexed; list_pixel carries its color_tag array
-              const size_t q = p * RECT_SLOTS + count;
-              list_step[q] = (uint32_t)(i - 1);
-              list_pixel[q] = ATMRT_COLOR_TERRAIN;
-              rec.re0[q] = re0;
-              rec.pl0[q] = pl0;
-              rec.re1[q] = sh;
-              rec.pl1[q] = path_length;
-            } else {
-              overflow_append(ovf, counters, (uint32_t)p, count, (uint32_t)(i - 1), re0, pl0, sh, path_length);
-            }
-          }
-          count++;
-          if (opaque) break; // utils.rs:237-239, 283-285
-        }
-        if (escapes(f, s, straight, sh, re0, esc_floor)) { // nothing left to find: credit the rest of the march and leave
-          esc_credit = f.march_steps - i;
-          break;
-        }
-        diff0 = diff1;
-        re0 = sh;
-        pl0 = path_length;
-      }
-      if (MODE == 0 && first >= 0) { // ray elevation and path length at the two samples that bracket the crossing
-        rec.re0[p] = re0;
-        rec.pl0[p] = pl0;
-        rec.re1[p] = sh;
-        rec.pl1[p] = path_length;
-      }
-    }
-    if (MODE == 3) hit_step[p] = object_ray ? 1 : 0; // voids the ray's overflow records (k_rect_scatter_trace_overflow)
-    if (esc_credit >= 0) steps += (unsigned)esc_credit;
+    MarchRay r;
+    rect_ray_setup(f, e, p, alt, direction, elevation, c, r.s);
+    r.k = MODE == 2 ? sinks.hit_offset[p] : 0;
+    WaveList wl = lists.wave(threadIdx.x >> 6);
+    bool object_ray = MODE == 3 && !wave_list_build<CALC>(f, e, c, wl); // MODE 3: this ray is left to the general tracer
+    if (!object_ray && march_begin(f, e, c, alt, r, n))
+      object_ray = march_steps<MODE, CALC, CUBIC, false, DRAIN>(f, e, c, r, n, 0, 0, sinks, counters, p, wl) == MARCH_GIVEN_UP;
     if (MODE == 3 && object_ray) { // nothing of this ray counts: k_rect_trace starts it again
       out.hit_count[p] = OBJECT_RAY;
-      steps = 0;
-      lookups = 0;
-      esc_credit = -1;
+      sinks.hit_step[p] = 1;
+      n = MarchCount{};
     } else if (MODE != 2) {
-      out.azimuth[p] = dm_to_degrees(direction); // not wrapped, rectilinear.rs:110-113
-      out.elevation_angle[p] = dm_to_degrees(elevation);
-      out.hit_count[p] = count;
+      store_ray_angles(out, p, direction, elevation);
+      march_finish<MODE>(out, sinks, counters, p, r);
     }
-    if (MODE == 0) hit_step[p] = first;
-    if ((MODE == 1 || (MODE == 3 && !object_ray)) && count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
   }
   if (MODE != 2) {
-    steps = wave_sum(steps);
-    lookups = wave_sum(lookups);
-    if ((threadIdx.x & 63) == 0 && steps) {
-      atomicAdd(&counters[CTR_RAY_STEPS], steps);
-      atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
-    }
-    escape_count(counters, esc_credit);
-  }
+    const unsigned long long steps = count_wave_steps<true>(counters, n.steps, n.lookups, n.esc_credit);
+    (void)steps;
 #ifdef ATMRT_TIMELINE
-  if (MODE == 0 && (threadIdx.x & 63) == 0) {
-    const size_t w = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (w < 65536) {
-      g_timeline[3 * w] = tl_t0;
-      g_timeline[3 * w + 1] = wall_clock64();
-      // steps | HW_ID[15:0] (wave, simd, pipe, cu, sh, se) << 24 | XCC_ID << 40
-      g_timeline[3 * w + 2] = steps | ((unsigned long long)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xffffu) << 24) |
-                              ((unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xfu) << 40);
+    if (MODE == 0 && (threadIdx.x & 63) == 0) {
+      const size_t w = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+      if (w < 65536) {
+        g_timeline[3 * w] = tl_t0;
+        g_timeline[3 * w + 1] = wall_clock64();
+        // steps | HW_ID[15:0] (wave, simd, pipe, cu, sh, se) << 24 | XCC_ID << 40
+        g_timeline[3 * w + 2] = steps | ((unsigned long long)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xffffu) << 24) |
+                                ((unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xfu) << 40);
+      }
     }
-  }
 #endif
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -541,151 +607,23 @@ static __device__ __forceinline__ GroupList group_list(char* base, uint32_t grou
   g.obj = (int32_t*)(g.vhi + WAVE_CAND);
   return g;
 }
-// what a slice of a scene with objects needs besides the ray: the wavefront's list (LDS), its wake distance, and where the
-// out-of-line object step finds the frame and the tracer's arenas
-struct SliceObjects {
-  const double *w_lo, *w_hi, *w_vlo, *w_vhi;
-  const int* w_obj;
-  int n_e;
-  const Frame* frame_dev;
-  const ObjectStepSinks* sinks_dev;
-};
 constexpr uint32_t SLICE_EMPTY = 0xffffffffu, SLICE_EXIT = 0xfffffffeu;
 #ifndef ATMRT_SLICE_WAVES
 #define ATMRT_SLICE_WAVES 5 // per SIMD, like the plain march (round 4: 2 x 93.3 -> 90.0 ms, 4 x 47.8 -> 46.2, 8 x 24.24 -> 24.01; 6: slower)
 #endif
 
-#ifdef ATMRT_TIMELINE
-static __device__ __forceinline__ int timeline_wave_max(int v) {
-  for (int o = 32; o; o >>= 1) {
-    const int u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-#endif
-
-// What a slice leaves behind besides the state: MODE 0 the first crossing, MODE 1 the slots of the counting march (k_rect_march<1>)
-struct SliceSinks {
-  int32_t* hit_step;   // MODE 0; MODE 3: 1 = the ray is left to the general tracer
-  RectRec rec;         // MODE 0: [plane]; MODE 1: slot-major [RECT_SLOTS][plane]; MODE 3: pixel-major [plane][RECT_SLOTS] (the tracer's arena)
-  uint32_t* slot_step; // MODE 1, MODE 3
-  OverflowArena ovf;   // MODE 1, MODE 3: crossings beyond the slots
-  uint32_t* slot_tag;  // MODE 3: the slot arena's colour tags (the march writes TERRAIN)
-};
-
-// one slice of the march of a ray whose state is in registers; returns true when the ray is still marching after step i0 + slice
-template <int MODE, int CALC, bool CUBIC>
-static __device__ __forceinline__ bool march_slice(const Frame& f, const Earth& e, const DirCalc& c, Stepper& s, double& sh,
-                                                   double& path_length, double& diff0, double& re0, double& pl0, int i0, int slice,
-                                                   int& first, unsigned& count, const SliceSinks& sinks, unsigned long long* counters, size_t p,
-                                                   size_t plane, unsigned long long& steps, unsigned long long& lookups,
-                                                   const SliceObjects& so, double& x_wake, int& esc_credit) {
-  const bool sph = e.spherical != 0;
-  const double radius = e.shape_radius;
-  const bool straight = f.p.straight_rays != 0;
-  const double step = f.p.simulation_step, max_dist = f.p.frame.max_distance;
-  const double skip_above = f.tv.skip_above;
-  double sx = s.x, lat, lon;
-  const int i_end = i0 + slice;
-  const double esc_floor = MODE == 3 ? escape_floor_objects(f.esc_floor, so.w_vhi, so.n_e) : f.esc_floor;
-  for (int i = i0 + 1;; i++) {
-    bool tame;
-    RayState nx = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step, tame);
-    if (straight) tame = __all(calc_dist_in_band(*f.atm, sh) && calc_dist_in_band(*f.atm, nx.h));
-    path_length += calc_dist(sph, radius, sx, sh, nx.x, nx.h, tame, f.inv_shape_radius);
-    sx = nx.x;
-    sh = nx.h;
-    if (sx > max_dist || sh < -1000.0 || !(sx <= max_dist)) return false; // rectilinear.rs:178 (+ NaN guard)
-    if (MODE == 3 && sx >= x_wake) { // wave-uniform, as in k_rect_march<3>: this step against the group's candidate list
-      const double x_prev = sx - step * 1.000001;
-      double next = dm_inf();
-      bool object_step = false;
-      for (int q = 0; q < so.n_e; q++) {
-        const double lo = so.w_lo[q], hi = so.w_hi[q];
-        if (hi < x_prev) continue;
-        if (lo > sx) {
-          next = lo < next ? lo : next;
-          continue;
-        }
-        next = sx;
-        const double vlo = so.w_vlo[q], vhi = so.w_vhi[q];
-        if (!((re0 < vlo && sh < vlo) || (re0 > vhi && sh > vhi))) object_step = true;
-      }
-      x_wake = next;
-      if (object_step) { // this lane's step in full, out of line (object_step_impl)
-        ObjectStepIO io;
-        io.c = c;
-        io.d0 = f.xs[i - 1];
-        io.sx = sx, io.re0 = re0, io.sh = sh, io.pl0 = pl0, io.path_length = path_length;
-        io.pixel = (uint32_t)p, io.step_index = i - 1, io.count = count;
-        object_step_impl<CALC>(so.frame_dev, so.sinks_dev, &io, so.w_lo, so.w_hi, so.w_obj, so.n_e);
-        count = io.count;
-        lookups += 2;
-        steps++;
-        if (io.finish) return false;
-        diff0 = io.diff1;
-        re0 = sh;
-        pl0 = path_length;
-        if (i == i_end) return true;
-        continue;
-      }
-    }
-    double diff1 = 1.0; // above every post of the mosaic: see k_rect_march
-    if (!(sh > skip_above)) {
-      coords_at_dist(e, c, sx, lat, lon);
-      diff1 = sh - terrain_elev_or_zero(f.tv, lat, lon);
-      lookups++;
-    }
-    steps++;
-    if (diff0 * diff1 < 0.0) { // utils.rs:222
-      if (MODE == 0) { // opaque terrain ends the march here (utils.rs:237-239)
-        first = i - 1;
-        return false;
-      }
-      if (count < (unsigned)RECT_SLOTS) { // as k_rect_march<1> / <3>
-        const size_t q = MODE == 3 ? p * RECT_SLOTS + count : (size_t)count * plane + p;
-        sinks.slot_step[q] = (uint32_t)(i - 1);
-        if (MODE == 3) sinks.slot_tag[q] = ATMRT_COLOR_TERRAIN;
-        sinks.rec.re0[q] = re0;
-        sinks.rec.pl0[q] = pl0;
-        sinks.rec.re1[q] = sh;
-        sinks.rec.pl1[q] = path_length;
-      } else {
-        overflow_append(sinks.ovf, counters, (uint32_t)p, count, (uint32_t)(i - 1), re0, pl0, sh, path_length);
-      }
-      count++;
-      if (MODE == 3 && f.p.terrain_alpha == 1.0) return false; // opaque terrain ends the ray (utils.rs:237-239)
-    }
-    if (escapes(f, s, straight, sh, re0, esc_floor)) { // as in k_rect_march: the ray has finished
-      esc_credit = f.march_steps - i;
-      return false;
-    }
-    diff0 = diff1;
-    re0 = sh;
-    pl0 = path_length;
-    if (i == i_end) return true;
-  }
-}
-
-// the ray has ended: its per-pixel results (azimuth and elevation angle were written by the first slice)
+// the ray marches on after step `step`: what changes from slice to slice (its elevation angle and geodesic calculator are written once)
 template <int MODE>
-static __device__ __forceinline__ void slice_finish(const DensePlanes& out, const SliceSinks& sinks, unsigned long long* counters, size_t p,
-                                                    int first, unsigned count, double re0, double pl0, double sh, double path_length) {
-  if (MODE == 0) {
-    if (first >= 0) { // ray elevation and path length at the two samples that bracket the crossing
-      sinks.rec.re0[p] = re0;
-      sinks.rec.pl0[p] = pl0;
-      sinks.rec.re1[p] = sh;
-      sinks.rec.pl1[p] = path_length;
-    }
-    out.hit_count[p] = first >= 0 ? 1u : 0u;
-    sinks.hit_step[p] = first;
-  } else {
-    out.hit_count[p] = count;
-    if (MODE == 3) sinks.hit_step[p] = 0; // the ray stayed with the march: its overflow records count (k_rect_scatter_trace_overflow)
-    if (count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
-  }
+static __device__ __forceinline__ void slice_save(const SliceState& st, size_t p, const MarchRay& r, int step) {
+  st.x[p] = r.s.x;
+  st.a[p] = r.s.a;
+  st.b[p] = r.s.b;
+  st.hint[p] = r.s.hint;
+  st.sh[p] = r.sh;
+  st.pl[p] = r.path_length;
+  st.diff0[p] = r.diff0;
+  st.step[p] = step;
+  if (MODE == 1 || MODE == 3) st.count[p] = r.count;
 }
 
 // wave-uniform end of a group's slice: announce the group again, or count it as finished
@@ -704,132 +642,63 @@ static __device__ __forceinline__ void slice_requeue(const SliceState& st, uint3
 
 // slice 0 of every group: an ordinary grid (it is short: the launch drains in a fraction of a slice)
 template <int MODE, int CALC, bool CUBIC>
-__global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Frame f, DensePlanes out, SliceSinks sinks,
+__global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Frame f, DensePlanes out, MarchSinks sinks,
                                                                              unsigned long long* __restrict__ counters, SliceState st,
-                                                                             uint32_t n_groups, int slice, const Frame* __restrict__ frame_dev,
-                                                                             const ObjectStepSinks* __restrict__ sinks_dev) {
+                                                                             uint32_t n_groups, int slice) {
 #ifdef ATMRT_TIMELINE
   const unsigned long long tl_t0 = wall_clock64();
 #endif
   stage_dm_tables();
   const size_t plane = (size_t)f.wl * f.h;
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned long long steps = 0, lookups = 0;
-  int esc_credit = -1;
+  MarchCount n;
   bool alive = false;
+  __shared__ WaveListLds<MODE, 4> lists; // MODE 3: built here and kept in HBM for the group's later slices
   if (p < plane) {
     const Earth e = earth_for<CALC>(f);
-    const int y = (int)(p / (size_t)f.wl), x = (int)(p % (size_t)f.wl);
     const double alt = *f.alt;
     double direction, elevation;
-    rect_ray_params(f.p, f.ph, f.c0 + x, y, direction, elevation);
     DirCalc c;
-    dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
-    Stepper s;
-    stepper_init(s, e.spherical != 0, e.shape_radius, alt, elevation);
-    out.azimuth[p] = dm_to_degrees(direction); // not wrapped, rectilinear.rs:110-113
-    out.elevation_angle[p] = dm_to_degrees(elevation);
-    int first = -1;
-    unsigned count = 0;
-    double sh = alt, path_length = 0.0, re0 = alt, pl0 = 0.0, diff0 = 0.0;
-    // MODE 3: the wavefront's candidate list, built as k_rect_march<3> builds it (LDS) and kept in HBM for the group's later slices
-    __shared__ double w_lo[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1], w_hi[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1],
-        w_vlo[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1], w_vhi[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1];
-    __shared__ int w_obj[MODE == 3 ? 4 : 1][MODE == 3 ? WAVE_CAND : 1];
-    const int wv = threadIdx.x >> 6;
-    int w_n = 0;
-    double x_wake = dm_inf();
-    bool object_ray = false; // MODE 3: the list overflowed (or the earth model has no pre-filter): the wavefront's rays go to the tracer
-    if (MODE == 3) {
-      if (!candidates_supported<CALC>(e)) {
-        object_ray = true;
-      } else {
-        const Vec3 nrm = track_normal<CALC>(c);
-        for (int j = 0; j < f.n_objects; j++) { // wave-uniform loop; the object's fields are scalar loads
-          double lo = dm_inf(), hi = -dm_inf();
-          double l, h;
-          if (candidate_interval<CALC>(e, c, nrm, f.objects[j], true, l, h)) lo = l, hi = h;
-          unsigned long long holders = __ballot(lo <= hi);
-          if (holders) {
-            double wlo = dm_inf(), whi = -dm_inf();
-            for (; holders; holders &= holders - 1) {
-              const int src = __builtin_ctzll(holders);
-              const double l2 = __shfl(lo, src, 64), h2 = __shfl(hi, src, 64);
-              wlo = l2 < wlo ? l2 : wlo;
-              whi = h2 > whi ? h2 : whi;
-            }
-            if (w_n < WAVE_CAND && (threadIdx.x & 63) == 0) {
-              w_lo[wv][w_n] = wlo;
-              w_hi[wv][w_n] = whi;
-              w_vlo[wv][w_n] = f.objects[j].vlo;
-              w_vhi[wv][w_n] = f.objects[j].vhi;
-              w_obj[wv][w_n] = j;
-            }
-            w_n++;
-          }
-        }
-        if (w_n > WAVE_CAND) object_ray = true;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int q = 0; q < w_n && q < WAVE_CAND; q++)
-          if (w_hi[wv][q] >= 0.0) x_wake = w_lo[wv][q] < x_wake ? w_lo[wv][q] : x_wake;
-      }
-    }
-    const int n_e = w_n < WAVE_CAND ? w_n : WAVE_CAND;
-    const SliceObjects so{w_lo[wv], w_hi[wv], w_vlo[wv], w_vhi[wv], w_obj[wv], n_e, frame_dev, sinks_dev};
-    if (!(0.0 > f.p.frame.max_distance || alt < -1000.0) && !object_ray) { // the reference would panic on an empty stream
-      double lat, lon;
-      coords_at_dist(e, c, 0.0, lat, lon);
-      diff0 = alt - terrain_elev_or_zero(f.tv, lat, lon);
-      lookups++;
-      alive = march_slice<MODE, CALC, CUBIC>(f, e, c, s, sh, path_length, diff0, re0, pl0, 0, slice, first, count, sinks, counters, p, plane,
-                                             steps, lookups, so, x_wake, esc_credit);
-      if (esc_credit >= 0) steps += (unsigned)esc_credit;
-    }
+    MarchRay r;
+    rect_ray_setup(f, e, p, alt, direction, elevation, c, r.s);
+    store_ray_angles(out, p, direction, elevation);
+    WaveList wl = lists.wave(threadIdx.x >> 6);
+    const bool object_ray = MODE == 3 && !wave_list_build<CALC>(f, e, c, wl); // MODE 3: the wavefront's rays go to the tracer
+    if (!object_ray && march_begin(f, e, c, alt, r, n))
+      alive = march_steps<MODE, CALC, CUBIC, true, false>(f, e, c, r, n, 0, slice, sinks, counters, p, wl) == MARCH_ON;
     if (MODE == 3 && st.glist && __any(alive)) { // the group marches on: its list and wake distance for the slices to come
       const GroupList gl = group_list(st.glist, (uint32_t)(p >> 6));
       const int lane = threadIdx.x & 63;
-      for (int q = lane; q < n_e; q += 64) {
-        gl.lo[q] = w_lo[wv][q];
-        gl.hi[q] = w_hi[wv][q];
-        gl.vlo[q] = w_vlo[wv][q];
-        gl.vhi[q] = w_vhi[wv][q];
-        gl.obj[q] = w_obj[wv][q];
+      for (int q = lane; q < wl.n; q += 64) {
+        gl.lo[q] = wl.lo[q];
+        gl.hi[q] = wl.hi[q];
+        gl.vlo[q] = wl.vlo[q];
+        gl.vhi[q] = wl.vhi[q];
+        gl.obj[q] = wl.obj[q];
       }
       const unsigned long long still = __ballot(alive); // (a lane that ended inside the slice holds an older wake distance)
       if (lane == __builtin_ctzll(still)) {
-        gl.n_and_wake[0] = (double)n_e;
-        gl.n_and_wake[1] = x_wake;
+        gl.n_and_wake[0] = (double)wl.n;
+        gl.n_and_wake[1] = wl.x_wake;
       }
     }
     if (MODE == 3 && object_ray) { // left to the general tracer (k_collect_object_rays, k_rect_trace)
       st.step[p] = -1;
       out.hit_count[p] = OBJECT_RAY;
       sinks.hit_step[p] = 1;
-      steps = 0;
-      lookups = 0;
-      esc_credit = -1;
+      n = MarchCount{};
     } else if (alive) {
-      st.x[p] = s.x;
-      st.a[p] = s.a;
-      st.b[p] = s.b;
-      st.hint[p] = s.hint;
-      st.ang[p] = s.ang;
-      st.sh[p] = sh;
-      st.pl[p] = path_length;
-      st.diff0[p] = diff0;
-      st.step[p] = slice;
-      if (MODE == 1 || MODE == 3) st.count[p] = count;
+      slice_save<MODE>(st, p, r, slice);
+      st.ang[p] = r.s.ang;
       st.calc[p] = c;
     } else {
       st.step[p] = -1;
-      slice_finish<MODE>(out, sinks, counters, p, first, count, re0, pl0, sh, path_length);
+      march_finish<MODE>(out, sinks, counters, p, r);
     }
   }
   if ((p >> 6) < n_groups) slice_requeue(st, (uint32_t)(p >> 6), alive); // (the last block may hold wavefronts past the last group)
-  steps = wave_sum(steps);
-  lookups = wave_sum(lookups);
+  const unsigned long long steps = count_wave_steps<true>(counters, n.steps, n.lookups, n.esc_credit);
+  (void)steps;
 #ifdef ATMRT_TIMELINE
   if ((threadIdx.x & 63) == 0 && (p >> 6) < 32768) {
     g_timeline[3 * (p >> 6)] = tl_t0;
@@ -837,11 +706,6 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
     g_timeline[3 * (p >> 6) + 2] = steps;
   }
 #endif
-  if ((threadIdx.x & 63) == 0 && steps) {
-    atomicAdd(&counters[CTR_RAY_STEPS], steps);
-    atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
-  }
-  escape_count(counters, esc_credit);
 }
 
 // the later slices: one single-wavefront workgroup per queue entry.  NOT a persistent grid: the SIMD issues oldest-wavefront-first,
@@ -850,10 +714,9 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
 // five rounds behind and were a 4.5 ms tail; s_setprio per quarter slice did not change that.  A wavefront that lives for one slice
 // starts youngest and ends oldest: every slice sees every rank and the groups stay in step.
 template <int MODE, int CALC, bool CUBIC>
-__global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame f, DensePlanes out, SliceSinks sinks,
+__global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame f, DensePlanes out, MarchSinks sinks,
                                                                            unsigned long long* __restrict__ counters, SliceState st,
-                                                                           uint32_t n_groups, int slice, const Frame* __restrict__ frame_dev,
-                                                                           const ObjectStepSinks* __restrict__ sinks_dev) {
+                                                                           uint32_t n_groups, int slice) {
   const size_t plane = (size_t)f.wl * f.h;
   const int lane = threadIdx.x;
   uint32_t item = 0;
@@ -887,67 +750,53 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
 #ifdef ATMRT_TIMELINE
   const unsigned long long tl_slice_t0 = wall_clock64();
 #endif
-  unsigned long long steps = 0, lookups = 0;
-  int esc_credit = -1;
+  MarchCount n;
   const size_t p = (size_t)item * 64 + lane;
   bool alive = false;
   const int32_t i0 = p < plane ? st.step[p] : -1;
-  // MODE 3: the group's candidate list back into LDS (what its first slice built)
-  __shared__ double w_lo[MODE == 3 ? WAVE_CAND : 1], w_hi[MODE == 3 ? WAVE_CAND : 1], w_vlo[MODE == 3 ? WAVE_CAND : 1], w_vhi[MODE == 3 ? WAVE_CAND : 1];
-  __shared__ int w_obj[MODE == 3 ? WAVE_CAND : 1];
-  int n_e = 0;
-  double x_wake = dm_inf();
-  if (MODE == 3) {
+  __shared__ WaveListLds<MODE, 1> lists;
+  WaveList wl = lists.wave(0);
+  if (MODE == 3) { // the group's candidate list back into LDS (what its first slice built)
     const GroupList gl = group_list(st.glist, item);
-    n_e = (int)gl.n_and_wake[0];
-    x_wake = gl.n_and_wake[1];
-    for (int q = lane; q < n_e; q += 64) {
-      w_lo[q] = gl.lo[q];
-      w_hi[q] = gl.hi[q];
-      w_vlo[q] = gl.vlo[q];
-      w_vhi[q] = gl.vhi[q];
-      w_obj[q] = gl.obj[q];
+    wl.n = (int)gl.n_and_wake[0];
+    wl.x_wake = gl.n_and_wake[1];
+    for (int q = lane; q < wl.n; q += 64) {
+      wl.lo[q] = gl.lo[q];
+      wl.hi[q] = gl.hi[q];
+      wl.vlo[q] = gl.vlo[q];
+      wl.vhi[q] = gl.vhi[q];
+      wl.obj[q] = gl.obj[q];
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  const SliceObjects so{w_lo, w_hi, w_vlo, w_vhi, w_obj, n_e, frame_dev, sinks_dev};
   if (i0 >= 0) {
     const Earth e = earth_for<CALC>(f);
-    Stepper s;
-    s.x = st.x[p];
-    s.a = st.a[p];
-    s.b = st.b[p];
-    s.hint = st.hint[p];
-    s.h0 = *f.alt;
-    s.ang = st.ang[p];
-    double sh = st.sh[p], path_length = st.pl[p], diff0 = st.diff0[p];
+    MarchRay r;
+    r.s.x = st.x[p];
+    r.s.a = st.a[p];
+    r.s.b = st.b[p];
+    r.s.hint = st.hint[p];
+    r.s.h0 = *f.alt;
+    r.s.ang = st.ang[p];
+    r.sh = r.re0 = st.sh[p];
+    r.path_length = r.pl0 = st.pl[p];
+    r.diff0 = st.diff0[p];
     const DirCalc c = st.calc[p];
-    double re0 = sh, pl0 = path_length;
-    int first = -1;
-    unsigned count = MODE == 1 || MODE == 3 ? st.count[p] : 0u;
-    alive = march_slice<MODE, CALC, CUBIC>(f, e, c, s, sh, path_length, diff0, re0, pl0, i0, slice, first, count, sinks, counters, p, plane,
-                                           steps, lookups, so, x_wake, esc_credit);
-    if (esc_credit >= 0) steps += (unsigned)esc_credit;
+    r.first = -1;
+    r.count = MODE == 1 || MODE == 3 ? st.count[p] : 0u;
+    alive = march_steps<MODE, CALC, CUBIC, true, false>(f, e, c, r, n, i0, slice, sinks, counters, p, wl) == MARCH_ON;
     if (alive) {
-      st.x[p] = s.x;
-      st.a[p] = s.a;
-      st.b[p] = s.b;
-      st.hint[p] = s.hint;
-      st.sh[p] = sh;
-      st.pl[p] = path_length;
-      st.diff0[p] = diff0;
-      st.step[p] = i0 + slice;
-      if (MODE == 1 || MODE == 3) st.count[p] = count;
+      slice_save<MODE>(st, p, r, i0 + slice);
     } else {
       st.step[p] = -1;
-      slice_finish<MODE>(out, sinks, counters, p, first, count, re0, pl0, sh, path_length);
+      march_finish<MODE>(out, sinks, counters, p, r);
     }
   }
   if (MODE == 3) { // the group's next wake distance, from a lane that is still marching (the value is the same in all of them)
     const unsigned long long still = __ballot(alive); // (a lane that ended inside the slice holds an older one)
-    if (still && lane == __builtin_ctzll(still)) group_list(st.glist, item).n_and_wake[1] = x_wake;
+    if (still && lane == __builtin_ctzll(still)) group_list(st.glist, item).n_and_wake[1] = wl.x_wake;
   }
   slice_requeue(st, item, alive);
 #ifdef ATMRT_TIMELINE
@@ -968,13 +817,7 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
     }
   }
 #endif
-  steps = wave_sum(steps);
-  lookups = wave_sum(lookups);
-  if (lane == 0 && steps) {
-    atomicAdd(&counters[CTR_RAY_STEPS], steps);
-    atomicAdd(&counters[CTR_TERRAIN_LOOKUPS], lookups);
-  }
-  escape_count(counters, esc_credit);
+  count_wave_steps<true>(counters, n.steps, n.lookups, n.esc_credit);
 }
 
 // every group must have finished: anything else is reported through CTR_SLICE_UNFINISHED and fails the frame (atmrt_api.hip)
@@ -1076,7 +919,6 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
   unsigned long long steps = 0;
   if (live) {
     const Earth e = earth_for<CALC>(f);
-    const int y = (int)(p / (size_t)f.wl), x = (int)(p % (size_t)f.wl);
     const bool sph = e.spherical != 0;
     const double radius = e.shape_radius;
     const bool straight = f.p.straight_rays != 0;
@@ -1085,11 +927,9 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
     const double skip_above = f.tv.skip_above;
     const double alt = *f.alt;
     double direction, elevation;
-    rect_ray_params(f.p, f.ph, f.c0 + x, y, direction, elevation);
     DirCalc c;
-    dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
     Stepper s;
-    stepper_init(s, sph, radius, alt, elevation);
+    rect_ray_setup(f, e, p, alt, direction, elevation, c, s);
     unsigned count = 0;
     uint64_t k = FILL ? hit_offset[p] : 0;
     if (!(0.0 > max_dist || alt < -1000.0)) {
@@ -1206,21 +1046,13 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
           for (uint64_t q = k0; q < k; q++) {
             list_step[q] = (uint32_t)(i - 1);
             list_pixel[q] = (uint32_t)p;
-            rec.re0[q] = re0;
-            rec.pl0[q] = pl0;
-            rec.re1[q] = sh_;
-            rec.pl1[q] = path_length;
+            rec_store(rec, q, re0, pl0, sh_, path_length);
           }
         } else if (hits.n && (FILL || count + (unsigned)hits.n <= (unsigned)RECT_SLOTS)) {
           uint64_t k0 = k;
           step_emit(hits, packed, list_step, list_pixel, k, (uint32_t)p, i - 1, lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx,
                     path_length);
-          for (uint64_t q = k0; q < k; q++) { // terrain points: what k_rect_finalize_list needs
-            rec.re0[q] = re0;
-            rec.pl0[q] = pl0;
-            rec.re1[q] = sh_;
-            rec.pl1[q] = path_length;
-          }
+          for (uint64_t q = k0; q < k; q++) rec_store(rec, q, re0, pl0, sh_, path_length); // terrain points: what k_rect_finalize_list needs
         }
         else if (!FILL && hits.n && hits.n <= STEP_CANDIDATES && ovf.cap) { // beyond the slots: the step's points into the overflow arena
           const unsigned long long base = atomicAdd(&counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
@@ -1230,10 +1062,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
                       path_length);
             for (uint64_t q = base; q < kk; q++) {
               ovf.ordinal[q] = count + (unsigned)(q - base);
-              ovf.re0[q] = re0;
-              ovf.pl0[q] = pl0;
-              ovf.re1[q] = sh_;
-              ovf.pl1[q] = path_length;
+              rec_store(ovf, q, re0, pl0, sh_, path_length);
             }
           }
         }
@@ -1245,16 +1074,12 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
       }
     }
     if (!FILL) {
-      out.azimuth[p] = dm_to_degrees(direction);
-      out.elevation_angle[p] = dm_to_degrees(elevation);
+      store_ray_angles(out, p, direction, elevation);
       out.hit_count[p] = count;
       if (count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
     }
   }
-  if (!FILL) {
-    steps = wave_sum(steps);
-    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(&counters[CTR_RAY_STEPS], steps);
-  }
+  if (!FILL) count_wave_steps<false>(counters, steps, 0, -1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1265,8 +1090,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
 // marching (it bounds the entries the later slices can write: the grid of the second kernel), then one wavefront per entry.
 // false: the frame is not sliced (march_slice_layout) and the caller launches k_rect_march.
 template <int MODE, bool CUBIC>
-static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DensePlanes& out, const SliceSinks& sinks, hipStream_t stream,
-                                     const Frame* frame_dev = nullptr, const ObjectStepSinks* sinks_dev = nullptr) {
+static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
   SliceLayout L;
   if (!ws.slice_state || !march_slice_layout(f, L)) return false;
   const size_t n = (size_t)f.wl * f.h;
@@ -1290,7 +1114,7 @@ static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DenseP
   st.glist = f.n_objects ? ws.slice_state + Carve::pad((size_t)((char*)(st.queue + L.cap) - ws.slice_state)) : nullptr;
   (void)hipMemsetAsync(st.ctl, 0, 64, stream);
   ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_first<MODE, CALC, CUBIC>), dim3(cdiv(n, 256)), dim3(256), 0, stream, f,
-                                                        out, sinks, (unsigned long long*)ws.counters, st, L.n_groups, slice, frame_dev, sinks_dev));
+                                                        out, sinks, (unsigned long long*)ws.counters, st, L.n_groups, slice));
   unsigned long long ctl_host[4] = {0, 0, 0, 0};
   if (hipMemcpyAsync(ctl_host, st.ctl, sizeof ctl_host, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
@@ -1300,7 +1124,7 @@ static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DenseP
   if (entries) {
     (void)hipMemsetAsync(st.queue + ctl_host[1], 0xff, (entries - (size_t)ctl_host[1]) * sizeof(uint32_t), stream);
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_cont<MODE, CALC, CUBIC>), dim3((unsigned)entries), dim3(64), 0, stream,
-                                                          f, out, sinks, (unsigned long long*)ws.counters, st, L.n_groups, slice, frame_dev, sinks_dev));
+                                                          f, out, sinks, (unsigned long long*)ws.counters, st, L.n_groups, slice));
   }
   hipLaunchKernelGGL(k_slice_check, dim3(1), dim3(1), 0, stream, (const unsigned long long*)st.ctl, L.n_groups,
                      (unsigned long long*)ws.counters);
@@ -1311,23 +1135,19 @@ template <bool CUBIC>
 void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched) {
   size_t n = (size_t)f.wl * f.h;
   RectRec rec = carve_rec(ws.rect_rec, n);
+  MarchSinks sinks{};
   if (f.opaque) {
-    if (!launch_rect_march_sliced<0, CUBIC>(f, ws, out, SliceSinks{ws.hit_step, rec, nullptr, OverflowArena{}, nullptr}, stream)) {
-      ATMRT_LAUNCH_MARCH(0, n, stream, f, out, ws.hit_step, (const uint64_t*)nullptr, rec, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                         (unsigned long long*)ws.counters, (const uint32_t*)nullptr, 0u, OverflowArena{}, (const Frame*)nullptr,
-                         (const ObjectStepSinks*)nullptr);
-    }
+    sinks.hit_step = ws.hit_step;
+    sinks.rec = rec;
+    if (!launch_rect_march_sliced<0, CUBIC>(f, ws, out, sinks, stream)) ATMRT_LAUNCH_MARCH(0, n, stream, f, out, sinks, (unsigned long long*)ws.counters);
     (void)hipEventRecord(ev_marched, stream);
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_finalize<CALC>), dim3(cdiv(n, 256)), dim3(256), 0, stream,
                                                           f, ws.hit_step, rec, out));
   } else {
-    RectRec slots = carve_rec(ws.slot_rec, n * RECT_SLOTS);
-    const OverflowArena ovf = carve_overflow(ws.overflow_arena, ws.overflow_cap);
-    if (!launch_rect_march_sliced<1, CUBIC>(f, ws, out, SliceSinks{nullptr, slots, ws.slot_step, ovf, nullptr}, stream)) {
-      ATMRT_LAUNCH_MARCH(1, n, stream, f, out, ws.hit_step, (const uint64_t*)nullptr, slots, ws.slot_step, (uint32_t*)nullptr,
-                         (unsigned long long*)ws.counters, (const uint32_t*)nullptr, 0u, ovf, (const Frame*)nullptr,
-                         (const ObjectStepSinks*)nullptr);
-    }
+    sinks.rec = carve_rec(ws.slot_rec, n * RECT_SLOTS);
+    sinks.step = ws.slot_step;
+    sinks.ovf = carve_overflow(ws.overflow_arena, ws.overflow_cap);
+    if (!launch_rect_march_sliced<1, CUBIC>(f, ws, out, sinks, stream)) ATMRT_LAUNCH_MARCH(1, n, stream, f, out, sinks, (unsigned long long*)ws.counters);
     (void)hipEventRecord(ev_marched, stream);
   }
 }
@@ -1355,10 +1175,7 @@ static __global__ __launch_bounds__(256) void k_rect_gather_slots(Frame f, const
     const size_t q = (size_t)j * plane + p;
     list_step[k + j] = slot_step[q];
     list_pixel[k + j] = (uint32_t)p;
-    rec.re0[k + j] = slots.re0[q];
-    rec.pl0[k + j] = slots.pl0[q];
-    rec.re1[k + j] = slots.re1[q];
-    rec.pl1[k + j] = slots.pl1[q];
+    rec_copy(rec, k + j, slots, q);
   }
 }
 
@@ -1373,10 +1190,7 @@ static __global__ __launch_bounds__(256) void k_rect_scatter_overflow(uint32_t n
   const uint64_t k = hit_offset[p] + ovf.ordinal[r];
   list_step[k] = ovf.step[r];
   list_pixel[k] = p;
-  rec.re0[k] = ovf.re0[r];
-  rec.pl0[k] = ovf.pl0[r];
-  rec.re1[k] = ovf.re1[r];
-  rec.pl1[k] = ovf.pl1[r];
+  rec_copy(rec, k, ovf, r);
 }
 
 // terrain_alpha < 1, Rectilinear: gather the recorded crossings, march the overflow pixels again listing every crossing,
@@ -1398,9 +1212,14 @@ void launch_multi_fill_t(const Frame& f, Workspace& ws, uint64_t n_hits, const D
                          (uint32_t)ws.n_overflow_records, carve_overflow(ws.overflow_arena, ws.overflow_cap), ws.hit_offset, ws.list_step,
                          ws.list_pixel, rec);
   } else if (ws.n_overflow) {
-    ATMRT_LAUNCH_MARCH(2, ws.n_overflow, stream, f, dense, ws.hit_step, ws.hit_offset, rec, ws.list_step, ws.list_pixel,
-                       (unsigned long long*)ws.counters, (const uint32_t*)ws.overflow, (uint32_t)ws.n_overflow, OverflowArena{},
-                       (const Frame*)nullptr, (const ObjectStepSinks*)nullptr);
+    MarchSinks sinks{};
+    sinks.rec = rec;
+    sinks.step = ws.list_step;
+    sinks.list_pixel = ws.list_pixel;
+    sinks.hit_offset = ws.hit_offset;
+    sinks.pixel_list = ws.overflow;
+    sinks.n_list = (uint32_t)ws.n_overflow;
+    ATMRT_LAUNCH_MARCH(2, ws.n_overflow, stream, f, dense, sinks, (unsigned long long*)ws.counters);
   }
   if (n_hits) {
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_finalize_list<CALC>), dim3(cdiv(n_hits, 256)), dim3(256), 0,
@@ -1448,11 +1267,15 @@ void launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes&
   (void)hipMemcpyAsync(sinks_dev, &sinks, sizeof sinks, hipMemcpyHostToDevice, stream);
   (void)hipStreamSynchronize(stream); // both sources are on this stack frame
   // a small launch (a column tile): the time-sliced march, its groups carrying their candidate lists; else the whole grid at once
-  if (!launch_rect_march_sliced<3, CUBIC>(f, ws, out, SliceSinks{ws.hit_step, slots, ws.slot_step, trace_overflow_arena(ws), ws.slot_packed.color_tag},
-                                          stream, frame_dev, sinks_dev)) {
-    ATMRT_LAUNCH_MARCH(3, n, stream, f, out, ws.hit_step, (const uint64_t*)nullptr, slots, ws.slot_step, ws.slot_packed.color_tag,
-                       (unsigned long long*)ws.counters, (const uint32_t*)nullptr, 0u, trace_overflow_arena(ws), frame_dev, sinks_dev);
-  }
+  MarchSinks msinks{};
+  msinks.hit_step = ws.hit_step;
+  msinks.rec = slots;
+  msinks.step = ws.slot_step;
+  msinks.ovf = sinks.ovf;
+  msinks.slot_tag = ws.slot_packed.color_tag;
+  msinks.frame_dev = frame_dev;
+  msinks.step_sinks_dev = sinks_dev;
+  if (!launch_rect_march_sliced<3, CUBIC>(f, ws, out, msinks, stream)) ATMRT_LAUNCH_MARCH(3, n, stream, f, out, msinks, (unsigned long long*)ws.counters);
   hipLaunchKernelGGL(k_collect_object_rays, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, (const uint32_t*)out.hit_count, ws.object_rays,
                      (unsigned long long*)ws.counters);
 }
@@ -1495,10 +1318,7 @@ static __global__ __launch_bounds__(256) void k_rect_gather_trace_slots(Frame f,
     const uint64_t k = k0 + j;
     list_step[k] = slot_step[q];
     list_pixel[k] = (uint32_t)p;
-    rec.re0[k] = slots.re0[q];
-    rec.pl0[k] = slots.pl0[q];
-    rec.re1[k] = slots.re1[q];
-    rec.pl1[k] = slots.pl1[q];
+    rec_copy(rec, k, slots, q);
     const uint32_t tag = sp.color_tag[q];
     packed.color_tag[k] = tag;
     if (tag != ATMRT_COLOR_TERRAIN) { // terrain points are completed by k_rect_finalize_list
@@ -1530,10 +1350,7 @@ static __global__ __launch_bounds__(256) void k_rect_scatter_trace_overflow(uint
   const uint64_t k = hit_offset[p] + ordinal;
   list_step[k] = ovf.step[r];
   list_pixel[k] = p;
-  rec.re0[k] = ovf.re0[r];
-  rec.pl0[k] = ovf.pl0[r];
-  rec.re1[k] = ovf.re1[r];
-  rec.pl1[k] = ovf.pl1[r];
+  rec_copy(rec, k, ovf, r);
   const uint32_t tag = ap.color_tag[r];
   packed.color_tag[k] = tag;
   if (tag != ATMRT_COLOR_TERRAIN) { // terrain points are completed by k_rect_finalize_list

@@ -1,9 +1,10 @@
-"""The Rectilinear march exists in three builds — the plain k_rect_march (4 wavefronts per SIMD, no scratch: launches above 16384
-workgroups, i.e. the headline frame), the small-launch one (wave priorities that fall with progress, 5 wavefronts per SIMD: shards
-and test frames with translucent terrain or objects) and, for small launches over opaque terrain, the time-sliced march
-(k_rect_march_first / _cont: ray state through HBM between slices of 128 steps, a FIFO of ray groups) — picked by the size and kind
-of the launch (atmrt_kernels.h march_slice_layout, atmrt_march_impl.h ATMRT_LAUNCH_MARCH).  Every test frame below 4 Mpixel runs the
-second or third, so this test forces each variant in a child process (ATMRT_MARCH_VARIANT is read once per process) and requires
+"""The Rectilinear march exists in three builds, all of them around one step loop (atmrt_march_impl.h march_steps) and all at
+5 wavefronts per SIMD — the plain k_rect_march (large launches, i.e. the headline frame), the small-launch one (wave priorities that
+fall with progress, object steps out of line: shards and test frames with translucent terrain or objects) and the time-sliced march
+(k_rect_march_first / _cont: ray state through HBM between slices of 128 steps, a FIFO of ray groups), which small launches over
+opaque terrain take by default and ATMRT_MARCH_VARIANT=sliced forces for translucent terrain and object scenes too — picked by the
+size and kind of the launch (atmrt_kernels.h march_slice_layout, atmrt_march_impl.h ATMRT_LAUNCH_MARCH).  Every test frame below
+4 Mpixel runs the second or third, so this test forces each variant in a child process (ATMRT_MARCH_VARIANT is read once per process) and requires
 the same bits from all for opaque, translucent and object scenes; the opaque scene comes in a second size whose pixel count is not
 a multiple of a workgroup, and with a step that gives rays of 18 slices."""
 import hashlib

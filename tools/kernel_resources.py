@@ -1,25 +1,43 @@
 #!/usr/bin/env python3
-"""Print VGPR / SGPR / scratch / occupancy per kernel of atmrt_kernels.hip (hipcc -Rpass-analysis)."""
+"""Print VGPR / SGPR / scratch / occupancy per kernel of the given units of csrc/ (hipcc -Rpass-analysis).
+
+    tools/kernel_resources.py [unit.hip ...] [extra hipcc flags]
+
+The compile line of a unit is the one csrc/Makefile would run for its object (`make -n`), so the per-unit flags (MARCH_EXTRA,
+CALL_EXTRA, MARCH_RA / TRACE_RA, ...) are the shipped library's by construction."""
 import re
+import shlex
 import subprocess
 import sys
 import os
+import tempfile
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+csrc = os.path.join(root, "atm-raytracer_amd", "csrc")
 units = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["atmrt_kernels.hip", "atmrt_paths.hip", "atmrt_march_linear.hip"]
 flags = [a for a in sys.argv[1:] if not a.endswith(".hip")]
+
+
+def compile_line(unit, obj_out):
+    """the Makefile's own command for <unit>.o, writing to obj_out instead"""
+    obj = unit[:-len(".hip")] + ".o"
+    dry = subprocess.run(["make", "-n", "-W", unit, obj], cwd=csrc, capture_output=True, text=True, check=True).stdout
+    lines = [l for l in dry.splitlines() if unit in l and " -c " in l]
+    if len(lines) != 1:
+        sys.exit(f"kernel_resources: `make -n {obj}` gave no single compile line for {unit}:\n{dry}")
+    cmd = shlex.split(lines[0])
+    cmd[cmd.index("-o") + 1] = obj_out
+    return cmd
+
+
 out = ""
-for unit in units:
-    src = os.path.join(root, "atm-raytracer_amd", "csrc", unit)
-    # the per-unit flags of csrc/Makefile (MARCH_EXTRA, CALL_EXTRA): without them the numbers are not those of the shipped library
-    extra = []
-    if unit.startswith(("atmrt_march_", "atmrt_trace_")):
-        extra += ["-mllvm", "-disable-machine-licm"]
-    if unit.startswith("atmrt_trace_") or unit == "atmrt_kernels.hip":
-        extra += ["-mllvm", "-enable-ipra=0"]
-    cmd = ["/opt/rocm/bin/hipcc", "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-c", src,
-           "-o", "/tmp/atmrt_k.o", "-Rpass-analysis=kernel-resource-usage"] + extra + flags
-    out += subprocess.run(cmd, capture_output=True, text=True).stderr
+with tempfile.TemporaryDirectory() as tmp:
+    for unit in units:
+        cmd = compile_line(unit, os.path.join(tmp, "unit.o")) + ["-Rpass-analysis=kernel-resource-usage"] + flags
+        run = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
+        if run.returncode:
+            sys.exit(run.stderr)
+        out += run.stderr
 cur, rows = None, {}
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
