@@ -221,13 +221,6 @@ extern "C" void atmrt_ctx_destroy(atmrt_ctx* c) {
   if (c->comm) comm_destroy(c);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  for (DevBuf* b : {&c->d_posts, &c->d_tiles, &c->d_cells, &c->d_xs, &c->d_alt, &c->d_colcalc, &c->d_prof, &c->d_pelev,
-                    &c->d_plen, &c->d_npath, &c->d_hit_step, &c->d_hit_offset, &c->d_scan_tmp, &c->d_counters,
-                    &c->d_list_step, &c->d_list_pixel, &c->d_rect_rec, &c->d_objects, &c->d_textures, &c->d_plat, &c->d_plon,
-                    &c->d_ccount, &c->d_coffset, &c->d_clist, &c->d_px_steps, &c->d_atm, &c->d_interp, &c->d_lat_dense, &c->d_lat_packed,
-                    &c->d_lat_offset, &c->d_dense, &c->d_packed, &c->d_io, &c->d_slot_step, &c->d_slot_rec, &c->d_overflow, &c->d_slot_pixel, &c->d_slot_packed, &c->d_pelev_t, &c->d_plen_t, &c->d_col_cand, &c->d_col_ncand, &c->d_path_seg, &c->d_dprev, &c->d_step_prop, &c->d_blend_arena,
-                    &c->d_object_rays, &c->d_slice, &c->d_overflow_arena})
-    b->release(); // (a buffer missing from this list is released by its destructor when the context is deleted below)
   for (hipEvent_t ev : c->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : c->ev_seg)
@@ -240,7 +233,7 @@ extern "C" void atmrt_ctx_destroy(atmrt_ctx* c) {
   if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  delete c;
+  delete c; // its DevBufs free themselves, in no particular order: the streams are idle and this device is current
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -801,106 +794,24 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   return ATMRT_OK;
 }
 
+// The scratch of frame `f`: the context's workspace allocation grown to workspace_layout(f) and carved by it, and the three arrays
+// that outlive it (atmrt_ctx.h).  The allocation moves when it grows, so the rule is: NOTHING OF THIS FRAME IS LIVE IN IT WHEN IT IS
+// RESERVED.  Every call comes before the frame's first launch, but for the second one of run_interpolating: it prepares the frame
+// that the entry point prepared already, so it cannot grow the allocation, and what the blend still needs of the lattice pass lies
+// in buffers of its own.  No pointer into the allocation is kept in the context across frames.
 static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
-  size_t npx = (size_t)f.wl * f.h;
-  HIP_TRY(c, c->d_counters.reserve(N_COUNTERS * sizeof(uint64_t)));
-  HIP_TRY(c, c->d_hit_step.reserve(npx * sizeof(int32_t)));
-  HIP_TRY(c, c->d_hit_offset.reserve(npx * sizeof(uint64_t)));
-  size_t nsamples = f.n_objects && f.p.generator != ATMRT_GEN_RECTILINEAR ? (size_t)f.n_t * f.wl : 0;
-  HIP_TRY(c, c->d_scan_tmp.reserve((std::max(npx, nsamples) / 2048 + 2) * sizeof(uint64_t)));
-  if (nsamples) {
-    HIP_TRY(c, c->d_plat.reserve(nsamples * sizeof(double)));
-    HIP_TRY(c, c->d_plon.reserve(nsamples * sizeof(double)));
-    HIP_TRY(c, c->d_ccount.reserve(nsamples * sizeof(uint32_t)));
-    HIP_TRY(c, c->d_coffset.reserve(nsamples * sizeof(uint64_t)));
-  }
-  ws->plat = c->d_plat.as<double>();
-  ws->plon = c->d_plon.as<double>();
-  ws->ccount = c->d_ccount.as<uint32_t>();
-  ws->coffset = c->d_coffset.as<uint64_t>();
-  ws->clist = c->d_clist.as<uint32_t>();
-  ws->px_steps = nullptr;
-  if (f.p.generator != ATMRT_GEN_RECTILINEAR) {
-    HIP_TRY(c, c->d_colcalc.reserve((size_t)f.wl * sizeof(DirCalc)));
-    HIP_TRY(c, c->d_prof.reserve((size_t)f.n_t * f.wl * sizeof(double)));
-    HIP_TRY(c, c->d_pelev.reserve((size_t)f.h * f.n_path_cap * sizeof(double)));
-    HIP_TRY(c, c->d_plen.reserve((size_t)f.h * f.n_path_cap * sizeof(double)));
-    HIP_TRY(c, c->d_npath.reserve((size_t)f.h * sizeof(int32_t)));
-    HIP_TRY(c, c->d_path_seg.reserve((size_t)f.h * sizeof(PathSegState)));
-    if (f.n_objects == 0) HIP_TRY(c, c->d_dprev.reserve(npx * sizeof(double)));
-  }
-  if (f.p.generator == ATMRT_GEN_RECTILINEAR) HIP_TRY(c, c->d_rect_rec.reserve(4 * npx * sizeof(double)));
-  ws->rect_rec = c->d_rect_rec.as<double>();
-  ws->slot_packed = PackedHits{};
-  if (!f.opaque || f.n_objects > 0) { // slots of the counting march / scan / trace passes
-    HIP_TRY(c, c->d_slot_step.reserve((size_t)RECT_SLOTS * npx * sizeof(uint32_t)));
-    if (f.p.generator == ATMRT_GEN_RECTILINEAR) HIP_TRY(c, c->d_slot_rec.reserve(4 * (size_t)RECT_SLOTS * npx * sizeof(double)));
-    if (f.n_objects > 0) {
-      HIP_TRY(c, c->d_slot_pixel.reserve((size_t)RECT_SLOTS * npx * sizeof(uint32_t)));
-      HIP_TRY(c, reserve_carved(c->d_slot_packed, [&](Carve& k) { ws->slot_packed = carve_packed(k, (size_t)RECT_SLOTS * npx); }));
-    }
-  }
-  ws->slot_pixel = c->d_slot_pixel.as<uint32_t>();
-  ws->slot_step = c->d_slot_step.as<uint32_t>();
-  ws->slot_rec = c->d_slot_rec.as<double>();
-  ws->overflow = c->d_overflow.as<uint32_t>();
-  ws->n_overflow = 0;
-  ws->alt = c->d_alt.as<double>();
-  ws->colcalc = c->d_colcalc.as<DirCalc>();
-  ws->prof = c->d_prof.as<double>();
-  ws->pelev = c->d_pelev.as<double>();
-  ws->plen = c->d_plen.as<double>();
-  if (f.p.generator != ATMRT_GEN_RECTILINEAR && f.n_objects > 0) {
-    HIP_TRY(c, c->d_pelev_t.reserve((size_t)f.h * f.n_path_cap * sizeof(double)));
-    HIP_TRY(c, c->d_plen_t.reserve((size_t)f.h * f.n_path_cap * sizeof(double)));
-  }
-  if (f.p.generator != ATMRT_GEN_RECTILINEAR && f.n_objects > 0) {
-    HIP_TRY(c, c->d_col_cand.reserve((size_t)f.wl * 64 * sizeof(int32_t)));
-    HIP_TRY(c, c->d_col_ncand.reserve((size_t)f.wl * sizeof(int32_t)));
-    HIP_TRY(c, c->d_col_lo.reserve((size_t)f.wl * 64 * sizeof(double)));
-    HIP_TRY(c, c->d_col_hi.reserve((size_t)f.wl * 64 * sizeof(double)));
-    HIP_TRY(c, c->d_traced.reserve(npx));
-  }
-  ws->col_cand = c->d_col_cand.as<int32_t>();
-  ws->col_ncand = c->d_col_ncand.as<int32_t>();
-  ws->col_lo = c->d_col_lo.as<double>();
-  ws->col_hi = c->d_col_hi.as<double>();
-  ws->traced = c->d_traced.as<uint8_t>();
-  ws->pelev_t = c->d_pelev_t.as<double>();
-  ws->plen_t = c->d_plen_t.as<double>();
-  ws->npath = c->d_npath.as<int32_t>();
-  ws->path_seg = c->d_path_seg.as<PathSegState>();
-  ws->dprev = c->d_dprev.as<double>();
-  ws->hit_step = c->d_hit_step.as<int32_t>();
-  ws->hit_offset = c->d_hit_offset.as<uint64_t>();
-  ws->scan_tmp = c->d_scan_tmp.as<uint64_t>();
-  ws->counters = c->d_counters.as<uint64_t>();
-  ws->list_step = nullptr;
-  ws->list_pixel = nullptr;
-  ws->step_prop = nullptr;
-  ws->object_rays = nullptr;
-  ws->step_ctx = nullptr;
-  ws->overflow_arena = nullptr;
-  ws->overflow_cap = 0;
-  ws->n_overflow_records = 0;
-  ws->overflow_packed = PackedHits{};
+  *ws = Workspace{};
   if (f.p.generator == ATMRT_GEN_RECTILINEAR && !f.opaque) { // the counting passes' trace points beyond the slots
     static const long forced_cap = [] { // test hook: a tiny arena forces the second-pass route (tests/test_gpu_march_variants.py)
       const char* e = getenv("ATMRT_OVERFLOW_CAP");
       return e ? atol(e) : -1L;
     }();
-    ws->overflow_cap = forced_cap >= 0 ? (size_t)forced_cap : std::max<size_t>(65536, npx / 4);
-    HIP_TRY(c, reserve_carved(c->d_overflow_arena, [&](Carve& k) {
-      k(ws->overflow_arena, overflow_arena_bytes(ws->overflow_cap));
-      if (f.n_objects) ws->overflow_packed = carve_packed(k, ws->overflow_cap);
-    }));
+    ws->overflow_cap = forced_cap >= 0 ? (size_t)forced_cap : std::max<size_t>(65536, (size_t)f.wl * f.h / 4);
   }
-  ws->slice_state = nullptr;
-  SliceLayout slices;
-  if (march_slice_layout(f, slices)) { // a small Rectilinear launch without scene objects: the time-sliced march
-    HIP_TRY(c, c->d_slice.reserve(slices.bytes));
-    ws->slice_state = c->d_slice.as<char>();
-  }
+  HIP_TRY(c, reserve_carved(c->d_workspace, [&](Carve& k) { workspace_layout(f, k, *ws); }));
+  HIP_TRY(c, reserve_into(c->d_alt, ws->alt, 1));
+  HIP_TRY(c, reserve_into(c->d_hit_offset, ws->hit_offset, (size_t)f.wl * f.h));
+  HIP_TRY(c, reserve_into(c->d_counters, ws->counters, N_COUNTERS));
   return ATMRT_OK;
 }
 
@@ -926,8 +837,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     launch_close_count(f, ws, s);
     uint64_t cnt[N_COUNTERS];
     HIP_TRY(c, read_counters(ws, s, cnt));
-    HIP_TRY(c, c->d_clist.reserve((cnt[CTR_CLOSE_TOTAL] + 1) * sizeof(uint32_t)));
-    ws.clist = c->d_clist.as<uint32_t>();
+    HIP_TRY(c, reserve_into(c->d_clist, ws.clist, cnt[CTR_CLOSE_TOTAL] + 1));
     launch_close_fill(f, ws, s);
     HIP_TRY(c, hipEventRecord(ev[4], s));
     launch_trace_count(f, ws, dense, s);
@@ -936,13 +846,6 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
   } else if (general) {
     // Rectilinear with scene objects: the lean march first (it leaves the rays that can meet an object to the general tracer and
     // lists them), then the tracer over that list
-    HIP_TRY(c, c->d_object_rays.reserve((size_t)f.wl * f.h * sizeof(uint32_t)));
-    ws.object_rays = c->d_object_rays.as<uint32_t>();
-    HIP_TRY(c, reserve_carved(c->d_step_ctx, [&](Carve& k) { // a copy of the Frame, then ObjectStepSinks (launch_rect_trace_count)
-      char* sinks;
-      k(ws.step_ctx, sizeof(Frame));
-      k(sinks, OBJECT_STEP_SINKS_MAX_BYTES);
-    }));
     HIP_TRY(c, hipEventRecord(ev[4], s));
     launch_trace_count(f, ws, dense, s);
     uint64_t cnt[N_COUNTERS];
@@ -967,45 +870,30 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     launch_scan_counts(f, ws, dense.hit_count, s);
     HIP_TRY(c, read_counters(ws, s, counters));
     uint64_t n_hits = counters[CTR_HITS];
-    if (counters[CTR_BIG_STEPS]) { // some step produced more trace points than StepHits keeps: the fill pass sorts those in place by `prop`
-      HIP_TRY(c, c->d_step_prop.reserve((n_hits + 1) * sizeof(double)));
-      ws.step_prop = c->d_step_prop.as<double>();
+    const bool rect = f.p.generator == ATMRT_GEN_RECTILINEAR;
+    if (rect && !f.opaque) {
+      ws.n_overflow = counters[CTR_OVERFLOW_PIXELS]; // pixels whose points did not fit the slots: marched a second time if the arena overflowed too
+      ws.n_overflow_records = counters[CTR_OVERFLOW_RECORDS];
+      HIP_TRY(c, hipMemsetAsync(&ws.counters[CTR_OVERFLOW_CURSOR], 0, sizeof(uint64_t), s));
     }
+    HIP_TRY(c, reserve_carved(c->d_hit_lists, [&](Carve& k) { // what the fill pass needs per trace point, now that their number is known
+      // some step produced more trace points than StepHits keeps: the fill pass sorts those in place by `prop`
+      if (counters[CTR_BIG_STEPS]) k(ws.step_prop, (n_hits + 1) * sizeof(double));
+      if (f.opaque) return;
+      k(ws.list_step, (n_hits + 1) * sizeof(uint32_t)), k(ws.list_pixel, (n_hits + 1) * sizeof(uint32_t));
+      if (rect) k(ws.rect_rec, 4 * (n_hits + 1) * sizeof(double)), k(ws.overflow, (ws.n_overflow + 1) * sizeof(uint32_t));
+    }));
     HIP_TRY(c, reserve_carved(c->d_packed, [&](Carve& k) { packed = carve_packed(k, n_hits); }));
-    if (f.opaque) {
-      launch_pack_first_hits(f, ws, dense, packed, s);
-    } else {
-      HIP_TRY(c, c->d_list_step.reserve((n_hits + 1) * sizeof(uint32_t)));
-      HIP_TRY(c, c->d_list_pixel.reserve((n_hits + 1) * sizeof(uint32_t)));
-      ws.list_step = c->d_list_step.as<uint32_t>();
-      ws.list_pixel = c->d_list_pixel.as<uint32_t>();
-      if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
-        HIP_TRY(c, c->d_rect_rec.reserve(4 * (n_hits + 1) * sizeof(double)));
-        ws.rect_rec = c->d_rect_rec.as<double>();
-      }
-      if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
-        ws.n_overflow = counters[CTR_OVERFLOW_PIXELS]; // pixels whose points did not fit the slots: marched a second time if the arena overflowed too
-        ws.n_overflow_records = counters[CTR_OVERFLOW_RECORDS];
-        HIP_TRY(c, c->d_overflow.reserve((ws.n_overflow + 1) * sizeof(uint32_t)));
-        ws.overflow = c->d_overflow.as<uint32_t>();
-        HIP_TRY(c, hipMemsetAsync(&ws.counters[CTR_OVERFLOW_CURSOR], 0, sizeof(uint64_t), s));
-      }
-      if (general) {
-        launch_trace_fill(f, ws, n_hits, dense, packed, s);
-      } else if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
-        launch_multi_fill(f, ws, n_hits, dense, packed, s);
-      } else {
-        launch_multi_fill_fast(f, ws, n_hits, dense, packed, s);
-      }
-    }
+    if (f.opaque) launch_pack_first_hits(f, ws, dense, packed, s);
+    else if (general) launch_trace_fill(f, ws, n_hits, dense, packed, s);
+    else if (rect) launch_multi_fill(f, ws, n_hits, dense, packed, s);
+    else launch_multi_fill_fast(f, ws, n_hits, dense, packed, s);
     if (n_hits_out) *n_hits_out = n_hits;
   }
   HIP_TRY(c, hipEventRecord(ev[8], s));
   if (packed_out) *packed_out = packed;
   return ATMRT_OK;
 }
-
-static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws);
 
 // InterpolatingRectilinearGenerator::generate (interpolating_rectilinear.rs:110-162): ray table -> lattice steps ->
 // lattice frame through the Fast pipeline -> 4-corner blend (count -> scan -> fill).
@@ -1060,9 +948,7 @@ static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const 
   Workspace wsl{};
   int rc = prepare_workspace(c, fl, &wsl);
   if (rc) return rc;
-  HIP_TRY(c, c->d_px_steps.reserve(nlat * 4 + nlat + 256));
-  wsl.px_steps = c->d_px_steps.as<uint32_t>();
-  ib.referenced = reinterpret_cast<uint8_t*>(wsl.px_steps + nlat);
+  HIP_TRY(c, reserve_carved(c->d_px_steps, [&](Carve& k) { k(wsl.px_steps, nlat * sizeof(uint32_t)), k(ib.referenced, nlat); }));
   HIP_TRY(c, hipMemsetAsync(ib.referenced, 0, nlat, s));
   DensePlanes ldense;
   HIP_TRY(c, reserve_carved(c->d_lat_dense, [&](Carve& k) { ldense = carve_dense(k, nlat); }));
@@ -1118,7 +1004,6 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
                          PackedHits* packed_out, uint64_t* n_hits_out, uint64_t* ray_steps_out, double* ms_out) {
   hipStream_t s = c->stream;
   hipEvent_t* ev = c->ev;
-  const bool fast = f.p.generator == ATMRT_GEN_FAST;
   // the buffers of the previous frame are about to be reused (or reallocated): until this frame has succeeded there is nothing
   // atmrt_draw_image / atmrt_last_hits_device may touch
   c->last_valid = false;
@@ -1172,7 +1057,6 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
     t.n_hits = counters[CTR_HITS];
     c->timings = t;
   }
-  (void)fast;
   if (counters[CTR_SLICE_UNFINISHED])
     return c->fail(ATMRT_ERR_HIP, "the time-sliced march left %llu of its ray groups unfinished", (unsigned long long)counters[CTR_SLICE_UNFINISHED] - 1);
   c->stats.unlisted_rays = counters[CTR_UNLISTED_RAYS];

@@ -62,6 +62,13 @@ struct DevBuf {
   }
   ~DevBuf() { release(); } // atmrt_ctx_destroy makes the context's device current before the context (and its buffers) goes
 };
+// `buf` grown to n elements and `field` pointed at it in one statement: a reservation and its pointer cannot drift apart
+template <class T>
+hipError_t reserve_into(DevBuf& buf, T*& field, size_t n) {
+  const hipError_t e = buf.reserve(n * sizeof(T));
+  field = buf.as<T>();
+  return e;
+}
 
 // An owning copy of an atmrt_atmosphere_t (the ABI struct borrows its function table and spline points from the caller).
 struct AtmDef {
@@ -111,7 +118,7 @@ struct atmrt_ctx {
 
   std::shared_ptr<atmrt::TileStore> terrain = std::make_shared<atmrt::TileStore>();
   uint64_t terrain_uploaded = 0; // generation of the mosaic in d_posts (0: none)
-  atmrt::DevBuf d_posts, d_tiles, d_cells;
+  atmrt::DevBuf d_posts, d_tiles, d_cells; // the mosaic: survives the frame, uploaded when the store's generation changes
   atmrt::TerrainView tv{};
 
   bool have_params = false;
@@ -158,12 +165,24 @@ struct atmrt_ctx {
   atmrt::MultiGroup* multi = nullptr; // this is the PARENT of a multi-device context: every entry point forwards to its children
   atmrt::Comm* comm = nullptr;        // this context computes one column tile of a frame shared with other ranks
 
-  // workspace
-  atmrt::DevBuf d_xs, d_alt, d_colcalc, d_prof, d_pelev, d_plen, d_npath, d_hit_step, d_hit_offset, d_scan_tmp, d_counters,
-      d_list_step, d_list_pixel, d_rect_rec, d_dense, d_packed, d_io, d_objects, d_textures, d_plat, d_plon,
-      d_ccount, d_coffset, d_clist, d_px_steps, d_atm, d_interp, d_lat_dense, d_lat_packed, d_lat_offset, d_slot_step, d_slot_rec,
-      d_overflow, d_slot_pixel, d_slot_packed, d_pelev_t, d_plen_t, d_col_cand, d_col_ncand, d_path_seg, d_dprev, d_step_prop,
-      d_blend_arena, d_object_rays, d_col_lo, d_col_hi, d_traced, d_slice, d_overflow_arena, d_step_ctx, d_overlay;
+  // Device memory.  The scratch of a frame is ONE allocation, d_workspace, carved by workspace_layout (atmrt_kernels.h) and re-carved
+  // by every prepare_workspace.  A buffer of its own needs a reason:
+  // ... it survives the frame
+  atmrt::DevBuf d_xs, d_atm;               // the distance table and the compiled atmosphere: uploaded when their inputs change
+  atmrt::DevBuf d_alt;                     // the observer's altitude (k_resolve): atmrt_draw_overlay* samples the atmosphere there
+  atmrt::DevBuf d_objects, d_textures;     // the scene: textures are uploaded when the objects change
+  atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last_dense, last_hits, last_offset): draw, overlay, hits
+  atmrt::DevBuf d_io, d_overlay;           // staging of the entry points that run between frames
+  // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
+  atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
+  atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend
+  atmrt::DevBuf d_px_steps;                // the lattice's ray-steps and its referenced flags, read by the blend
+  atmrt::DevBuf d_lat_dense, d_lat_packed, d_lat_offset; // the lattice result (the last two trade places with d_packed / d_hit_offset)
+  // ... it is sized by a count the host reads back in mid-frame, while the workspace is live and must not move
+  atmrt::DevBuf d_clist;                   // CTR_CLOSE_TOTAL: the close lists of a Fast frame with objects
+  atmrt::DevBuf d_hit_lists;               // CTR_HITS, CTR_OVERFLOW_PIXELS: the fill pass's lists, carved in run_core
+  atmrt::DevBuf d_blend_arena;             // CTR_BIG_BLEND_POINTS: BlendArena
+  atmrt::DevBuf d_workspace;
 
   int fail(int code, const char* fmt, ...) {
     char buf[1024];

@@ -181,7 +181,6 @@ enum Counter : int {
 };
 constexpr int N_COUNTERS = 16;
 
-// Scratch owned by the context, sized for the current frame.
 // crossings per pixel recorded by the counting march (4096x2048 headline at terrain_alpha 0.5: 99.3 % of the pixels have <= 4)
 constexpr int RECT_SLOTS = 4;
 
@@ -266,53 +265,110 @@ static inline bool march_slice_layout(const Frame& f, SliceLayout& L) {
   return true;
 }
 
+// Scratch of one frame.  Three owners (atmrt_ctx.h): the context's one workspace allocation, carved by workspace_layout below (array
+// shapes, conditions and sizes are stated there); buffers of their own that outlive the frame or a second preparation within it; and
+// buffers sized by a count the host reads back in mid-frame.  A field nobody set is null / zero.
 struct Workspace {
-  double* alt;            // [1]
-  DirCalc* colcalc;       // [wl]   Fast: per-column DirectionalCalc
-  double* prof;           // [n_t][wl] Fast: terrain profile, sample-major so a wavefront reads 64 columns coalesced
-  double* pelev;          // [h][n_path_cap] Fast: ray elevation per row
-  double* plen;           // [h][n_path_cap] Fast: running path length per row
-  int32_t* npath;         // [h]
-  PathSegState* path_seg; // [h] Fast: integration state between path segments
-  double* dprev;          // [h][wl] Fast: ray-minus-terrain difference at the last sample of the previous intersect segment
-  double* pelev_t;        // [n_path_cap][h] scenes with objects: pelev / plen sample-major for k_fast_trace (lanes = rows)
-  double* plen_t;
-  int32_t* hit_step;      // [h][wl] first hit: index of the older sample of the pair, or -1
-  uint64_t* hit_offset;   // [h][wl] exclusive scan of hit_count
+  // --- carved by workspace_layout
+  int32_t* hit_step;      // first hit: index of the older sample of the pair, or -1
   uint64_t* scan_tmp;     // block sums for the scan
-  uint64_t* counters;     // [N_COUNTERS], indexed by Counter
-  uint32_t* list_step;    // multi-hit: per trace point, the step index and ...
-  uint32_t* list_pixel;   // ... its pixel
-  double* rect_rec;       // Rectilinear: [4][n] ray elevation / path length at the two bracketing samples
-  // Rectilinear with translucent terrain: the counting march keeps the first RECT_SLOTS crossings of every pixel, so that only
-  // pixels with more crossings are marched a second time
-  uint32_t* slot_step;    // [RECT_SLOTS][h][wl]
-  double* slot_rec;       // [4][RECT_SLOTS][h][wl]
-  uint32_t* overflow;     // pixels with more than RECT_SLOTS crossings
-  uint32_t* slot_pixel;   // scenes with objects: [h][wl][RECT_SLOTS] (written by step_emit, not read)
-  PackedHits slot_packed; // scenes with objects: trace points of the slots, entry p * RECT_SLOTS + j
-  uint64_t n_overflow;    // their number (host copy of CTR_OVERFLOW_PIXELS after the counting march)
+  DirCalc* colcalc;       // Fast: per-column DirectionalCalc
+  double* prof;           // Fast: terrain profile, sample-major so a wavefront reads 64 columns coalesced
+  double* pelev;          // Fast: ray elevation per row
+  double* plen;           // Fast: running path length per row
+  int32_t* npath;
+  PathSegState* path_seg; // Fast: integration state between path segments
+  double* dprev;          // Fast: ray-minus-terrain difference at the last sample of the previous intersect segment
   // scenes with objects (Fast): geodesic point of every sample and the objects close to it (utils.rs:74-80)
-  double* plat;           // [n_t][wl]
-  double* plon;           // [n_t][wl]
-  uint32_t* ccount;       // [n_t][wl] number of close objects
-  uint64_t* coffset;      // [n_t][wl] exclusive scan of ccount
-  uint32_t* clist;        // object indices, ascending per sample
-  int32_t* col_cand;      // [wl][64] objects that can be close to any sample of the column (ascending), and ...
+  double* plat;
+  double* plon;
+  uint32_t* ccount;       // number of close objects
+  uint64_t* coffset;      // exclusive scan of ccount
+  double* pelev_t;        // pelev / plen sample-major for k_fast_trace (lanes = rows)
+  double* plen_t;
+  int32_t* col_cand;      // objects that can be close to any sample of the column (ascending), and ...
   int32_t* col_ncand;     // ... their number; -1 = no list, test every object
-  double* col_lo;         // [wl][64] distances between which a sample of the column can be close to the candidate ...
+  double* col_lo;         // distances between which a sample of the column can be close to the candidate ...
   double* col_hi;
-  uint8_t* traced;        // [h][wl] Fast with objects: 1 = the pixel can have a step with an object (k_fast_flag_rows)
-  uint32_t* object_rays;  // Rectilinear, scenes with objects: pixels the lean march left to the general tracer
-  char* step_ctx;         // Rectilinear, scenes with objects: Frame + ObjectStepSinks in HBM for the lean march's out-of-line object step
-  double* step_prop;      // fill pass, frames with big steps only: `prop` of every listed trace point (big_step_sort)
-  uint32_t* px_steps;     // optional [h][wl]: ray-steps of each pixel (InterpolatingRectilinear counts referenced lattice pixels only)
+  uint8_t* traced;        // 1 = the pixel can have a step with an object (k_fast_flag_rows)
+  // translucent terrain or objects: the counting passes keep the first RECT_SLOTS trace points of every pixel, so that only pixels
+  // with more are visited a second time
+  uint32_t* slot_step;
+  double* slot_rec;       // Rectilinear
+  uint32_t* slot_pixel;   // scenes with objects (written by step_emit, not read)
+  PackedHits slot_packed; // scenes with objects: trace points of the slots, entry p * RECT_SLOTS + j
   char* overflow_arena;   // Rectilinear, translucent terrain or objects: trace points beyond the slots (OverflowArena), or null
   PackedHits overflow_packed; // scenes with objects: the arena's complete points
-  size_t overflow_cap;    // its capacity in records
-  uint64_t n_overflow_records; // host copy of CTR_OVERFLOW_RECORDS after the counting march
+  size_t overflow_cap;    // its capacity in records (set before the layout runs: prepare_workspace)
+  uint32_t* object_rays;  // Rectilinear, scenes with objects: pixels the lean march left to the general tracer
+  char* step_ctx;         // Rectilinear, scenes with objects: Frame + ObjectStepSinks in HBM for the lean march's out-of-line object step
   char* slice_state;      // time-sliced march (march_slice_layout): ray state between two slices + the FIFO of groups, or null
+  // --- carved by workspace_layout in an opaque frame (the march's first hits, [4][h][wl]), else sized by the frame's trace points
+  double* rect_rec;       // Rectilinear: [4][n] ray elevation / path length at the two bracketing samples
+  // --- buffers of their own
+  double* alt;            // [1]
+  uint64_t* hit_offset;   // [h][wl] exclusive scan of hit_count
+  uint64_t* counters;     // [N_COUNTERS], indexed by Counter
+  uint32_t* px_steps;     // optional [h][wl]: ray-steps of each pixel (InterpolatingRectilinear counts referenced lattice pixels only)
+  // --- sized by a count read back in mid-frame
+  uint32_t* clist;        // Fast, scenes with objects: object indices, ascending per sample
+  uint32_t* list_step;    // multi-hit: per trace point, the step index and ...
+  uint32_t* list_pixel;   // ... its pixel
+  uint32_t* overflow;     // pixels with more than RECT_SLOTS crossings
+  double* step_prop;      // fill pass, frames with big steps only: `prop` of every listed trace point (big_step_sort)
+  // --- host copies of counters, after the counting march
+  uint64_t n_overflow;         // CTR_OVERFLOW_PIXELS
+  uint64_t n_overflow_records; // CTR_OVERFLOW_RECORDS
 };
+
+// The context's workspace allocation: every array of Workspace whose size follows from the Frame before its first launch, each with
+// its condition and its bytes, once.  Run over a null base it sizes the allocation (reserve_carved); an array it does not carve for
+// this frame stays null, so no kernel can see what another frame left there.
+static inline void workspace_layout(const Frame& f, Carve& k, Workspace& ws) {
+  const bool rect = f.p.generator == ATMRT_GEN_RECTILINEAR, objects = f.n_objects > 0;
+  const size_t wl = (size_t)f.wl, h = (size_t)f.h, npx = wl * h;
+  const size_t path = h * (size_t)f.n_path_cap;                        // [h][n_path_cap], or transposed
+  const size_t samples = !rect && objects ? (size_t)f.n_t * wl : 0;    // [n_t][wl]
+  k(ws.hit_step, npx * sizeof(int32_t));                                // [h][wl]
+  k(ws.scan_tmp, ((npx > samples ? npx : samples) / 2048 + 2) * sizeof(uint64_t));
+  if (!rect) { // Fast, and both frames of InterpolatingRectilinear
+    k(ws.colcalc, wl * sizeof(DirCalc));                                // [wl]
+    k(ws.prof, (size_t)f.n_t * wl * sizeof(double));                    // [n_t][wl]
+    k(ws.pelev, path * sizeof(double)), k(ws.plen, path * sizeof(double));
+    k(ws.npath, h * sizeof(int32_t)), k(ws.path_seg, h * sizeof(PathSegState)); // [h]
+    if (!objects) {
+      k(ws.dprev, npx * sizeof(double));                                // [h][wl]
+    } else { // the close lists of every terrain sample, the paths transposed, the columns' candidates
+      k(ws.plat, samples * sizeof(double)), k(ws.plon, samples * sizeof(double));
+      k(ws.ccount, samples * sizeof(uint32_t)), k(ws.coffset, samples * sizeof(uint64_t));
+      k(ws.pelev_t, path * sizeof(double)), k(ws.plen_t, path * sizeof(double));
+      k(ws.col_cand, wl * 64 * sizeof(int32_t)), k(ws.col_ncand, wl * sizeof(int32_t)); // [wl][64], [wl]
+      k(ws.col_lo, wl * 64 * sizeof(double)), k(ws.col_hi, wl * 64 * sizeof(double));
+      k(ws.traced, npx);                                                // [h][wl]
+    }
+  }
+  // rect_rec of a frame with several trace points per pixel is sized by their number, after the scan (run_core): the counting march
+  // writes the slots and only the fill pass writes rect_rec
+  if (rect && f.opaque) k(ws.rect_rec, 4 * npx * sizeof(double));
+  if (!f.opaque) {
+    k(ws.slot_step, RECT_SLOTS * npx * sizeof(uint32_t));               // [RECT_SLOTS][h][wl]; with objects [h][wl][RECT_SLOTS]
+    if (rect) k(ws.slot_rec, 4 * RECT_SLOTS * npx * sizeof(double));    // [4][RECT_SLOTS][h][wl]
+    if (objects) {
+      k(ws.slot_pixel, RECT_SLOTS * npx * sizeof(uint32_t));            // [h][wl][RECT_SLOTS]
+      ws.slot_packed = carve_packed(k, RECT_SLOTS * npx);
+    }
+    if (rect) {
+      k(ws.overflow_arena, overflow_arena_bytes(ws.overflow_cap));
+      if (objects) ws.overflow_packed = carve_packed(k, ws.overflow_cap);
+    }
+  }
+  if (rect && objects) {
+    k(ws.object_rays, npx * sizeof(uint32_t));
+    k(ws.step_ctx, Carve::pad(sizeof(Frame)) + OBJECT_STEP_SINKS_MAX_BYTES); // launch_rect_trace_count carves the two out of it
+  }
+  SliceLayout slices;
+  if (march_slice_layout(f, slices)) k(ws.slice_state, slices.bytes);   // a small Rectilinear launch: the time-sliced march
+}
 
 // InterpolatingRectilinear scratch
 struct InterpBuffers {
@@ -355,7 +411,6 @@ void launch_interp_finish(const Frame& f, Workspace& ws, const InterpBuffers& ib
 // All launches go to `stream`; none of them synchronises or allocates.
 void launch_resolve(const Frame& f, Workspace& ws, ObjectDev* objects_mut, hipStream_t stream);
 // scenes with objects / translucent terrain + objects: general tracer (count -> scan -> fill)
-void launch_fast_profile_ll(const Frame& f, Workspace& ws, hipStream_t stream);
 void launch_close_count(const Frame& f, Workspace& ws, hipStream_t stream);
 void launch_close_fill(const Frame& f, Workspace& ws, hipStream_t stream);
 // exclusive scan of in[0, n) into out; the grand total into *total (and nothing else)

@@ -9,7 +9,7 @@ import pytest
 
 from atm_raytracer_amd import _abi, config, generators, synth
 from atm_raytracer_amd._lib import AtmrtError
-from util import assert_bitexact, run_gpu, run_oracle
+from util import FIELDS_HIT, FIELDS_PIXEL, assert_bitexact, frame_stats, run_gpu, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -262,3 +262,84 @@ def test_failed_frame_invalidates_the_last_frame(gpu_ctx):
     assert gpu_ctx.lib.atmrt_last_hits_device(gpu_ctx.handle, None, C.byref(n)) == _abi.ERR_STATE
     run_gpu(gpu_ctx, cfg, tiles)  # and the context recovers
     gpu_ctx.check(gpu_ctx.lib.atmrt_draw_image(gpu_ctx.handle, C.byref(col), rgb.ctypes.data))
+
+
+def _everything_of_a_frame(ctx, cfg, tiles):
+    """What a frame hands its caller, through both entry points: atmrt_generate (pixel planes, hit_offset, the packed arrays,
+    ray_steps), atmrt_generate_device (every dense plane; the lists it leaves in HBM where the frame has any), atmrt_last_stats."""
+    import torch
+    ctx.check(ctx.lib.atmrt_terrain_clear(ctx.handle))
+    g = generators.make_generator(generators.Params(cfg), generators.Terrain.from_tiles(tiles, ctx))
+    h, w = cfg.params.height, cfg.params.width
+    planes, pod = generators.image_planes(h, w, torch.device("cuda", 0))
+    for v in planes.values():
+        v.zero_()
+    steps, _ = g.generate_device(pod)
+    out = {"dense " + k: v.cpu().numpy() for k, v in planes.items()}
+    out["device ray_steps"] = np.array([steps], dtype=np.uint64)
+    out["device stats"] = np.array(list(frame_stats(ctx).values()), dtype=np.uint64)
+    if cfg.params.terrain_alpha < 1.0 or cfg.objects or cfg.params.generator == _abi.GENERATORS["InterpolatingRectilinear"]:
+        out.update({"device " + k: v.cpu().numpy() for k, v in g.last_hits_device(h, w).items()})
+    host = g.generate()  # last, so that the context's last frame lies in its own memory (atmrt_draw_image)
+    out.update({k: host[k] for k in FIELDS_PIXEL + FIELDS_HIT})
+    out["n_hits, ray_steps"] = np.array([host["n_hits"], host["ray_steps"]], dtype=np.uint64)
+    out["stats"] = np.array(list(frame_stats(ctx).values()), dtype=np.uint64)
+    return out
+
+
+def test_one_context_across_frames_that_move_the_workspace():
+    """A context's scratch memory is sized per frame, and which of its arrays exist depends on the generator, the terrain's alpha,
+    the scene's objects and the march variant.  One context renders a sequence in which that memory grows, is needed less, changes
+    which arrays exist and goes through InterpolatingRectilinear's two preparations per frame; after every frame, everything the
+    frame hands its caller must equal, byte for byte, what a context that has seen nothing else returns for that frame.  The sizes
+    are no multiples of the 64-column tile or of a row group.  (A frame with ATMRT_OVERFLOW_CAP is not in the sequence: the
+    variable is read once per process; tests/test_gpu_march_variants.py runs such frames in child processes.)"""
+    near = dict(tilt=-4.0, max_distance=12_000.0, level=301)  # 120 steps: a ray is shorter than one slice of the sliced march
+    _, tiles = synth.scene("S2", 8, 8, **near)
+
+    def frame(gen, w, h, objects=False, **over):
+        cfg, _ = synth.scene("S2", w, h, generator=gen, **dict(near, **over))
+        if objects:  # a cylinder, a cone and a billboard, large enough to cover pixels of an image this small
+            synth.add_objects(cfg, n_cyl=2, n_bill=1, dist=(1_500.0, 9_000.0), spread_deg=20.0, radius=(60.0, 150.0),
+                              height=(100.0, 300.0), bill_w=(200.0, 400.0), bill_h=(100.0, 300.0))
+        return cfg
+
+    sequence = [frame("Rectilinear", 70, 36),
+                frame("Rectilinear", 70, 36, terrain_alpha=0.5),
+                frame("Rectilinear", 130, 44, objects=True),
+                frame("Fast", 130, 44),
+                frame("Fast", 130, 44, objects=True, terrain_alpha=0.5),
+                frame("InterpolatingRectilinear", 70, 36),
+                frame("Rectilinear", 130, 44, max_distance=40_000.0)]  # 400 steps, a small launch: the time-sliced march
+    assert sequence[6].params.frame.max_distance / sequence[6].params.simulation_step > 128 > \
+        sequence[0].params.frame.max_distance / sequence[0].params.simulation_step + 2  # MARCH_SLICE_STEPS
+    sequence += [sequence[0], sequence[5]]
+    numbers = [1, 2, 3, 4, 5, 6, 7, 9, 10]  # (8 is the ATMRT_OVERFLOW_CAP frame)
+
+    def alone(cfg):
+        ctx = generators.Context(0)
+        try:
+            return _everything_of_a_frame(ctx, cfg, tiles)
+        finally:
+            ctx.close()
+
+    want = [alone(cfg) for cfg in sequence[:7]]
+    want += [want[0], want[5]]
+    object_steps = [k for k, _ in _abi.FrameStats._fields_].index("object_steps")  # (object_rays stays 0 below 96 candidates)
+    assert want[2]["stats"][object_steps] > 0 and want[4]["n_hits, ray_steps"][0] > want[3]["n_hits, ray_steps"][0] > 0
+
+    ctx = generators.Context(0)
+    try:
+        images = {}
+        for i, cfg, w in zip(numbers, sequence, want):
+            got = _everything_of_a_frame(ctx, cfg, tiles)
+            assert got.keys() == w.keys()
+            for k in w:
+                assert got[k].dtype == w[k].dtype and got[k].shape == w[k].shape and got[k].tobytes() == w[k].tobytes(), \
+                    f"frame {i}: {k} differs from a fresh context's"
+            if i in (1, 9):
+                col = generators.into_coloring(ctx.lib, cfg.params, cfg.coloring)
+                images[i] = generators.draw_image(ctx, col, cfg.params.width, cfg.params.height)
+        assert images[1].any() and np.array_equal(images[1], images[9])
+    finally:
+        ctx.close()
