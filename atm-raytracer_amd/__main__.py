@@ -1,6 +1,7 @@
 """Command line mirroring the reference's subcommands (src/main.rs:17-39) over the C ABI:
 
     python -m atm_raytracer_amd gen -c CONFIG.yaml [--output OUT.png] [--metadata OUT.npz|OUT.dat]
+                                    [--visibility-map OUT.npz [--map-cell ARCSEC] [--map-all]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -10,6 +11,10 @@ image of renderer::output_image: draw_image, then — on the device image, befor
 ticks, the flat-horizon line and the eye-level line of `output` (renderer/mod.rs:416-431); the tick labels are drawn on the
 host with Pillow in DejaVu Sans where the machine has that font (a warning and no labels where not).  On request it also
 writes the per-pixel metadata as a compressed .npz (the reference's bincode+gzip layout depends on crates that are absent).
+`--visibility-map` (no reference counterpart) bins the frame's trace points over a latitude / longitude grid on the device — the
+frame's bounds snapped outward to multiples of the cell, 3 arcseconds unless --map-cell says otherwise; the first trace point of
+every pixel, or all of them with --map-all — and writes count, min_distance, lat0, lon0, cell_lat, cell_lon, n_points, n_binned,
+n_outside, n_skipped and n_updates to an .npz.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -70,6 +75,19 @@ def draw_labels(img, ticks):
         draw.text(xy, t["label"], fill=(255, 255, 255), font=font, anchor="la")
 
 
+def write_visibility_map(ctx, path, cell_arcsec, mode):
+    """The visibility map of the context's last frame over its own bounds, as an .npz (an empty 1 x 1 map for a frame of sky)."""
+    if not (cell_arcsec > 0 and np.isfinite(cell_arcsec)):
+        raise config.ConfigError("--map-cell must be a positive number of arcseconds")
+    cell = cell_arcsec / 3600.0
+    grid = generators.snap_grid(generators.frame_bounds(ctx, mode), cell) or generators.GeoGrid(0.0, 0.0, cell, cell, 1, 1)
+    count, mind, stats = generators.visibility_map_device(ctx, grid, mode)
+    count = count.cpu().numpy().view(np.uint32)
+    with open(path, "wb") as f:  # a file object: numpy appends no extension to the name the user gave
+        np.savez_compressed(f, count=count, min_distance=mind.cpu().numpy(), lat0=grid.lat0, lon0=grid.lon0, cell_lat=grid.cell_lat,
+                            cell_lon=grid.cell_lon, **{k: np.uint64(v) for k, v in stats.items()})
+
+
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
@@ -89,6 +107,9 @@ def cmd_gen(a):
     rgb_dev = torch.empty((h, w, 3), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
     ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
     ticks, _ = generators.draw_overlay_device(ctx, generators.into_overlay(cfg.output), rgb_dev.data_ptr(), w, h)
+    if a.visibility_map:  # on the device, while the frame is still in HBM
+        stamp("Binning the visibility map...")
+        write_visibility_map(ctx, a.visibility_map, a.map_cell, "all" if a.map_all else "first")
     img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
     draw_labels(img, ticks)
     img.save(a.output)
@@ -168,6 +189,9 @@ def main(argv=None):
     g.add_argument("-c", "--config", required=True)
     g.add_argument("--output", default="./output.png")
     g.add_argument("--metadata", default=None)
+    g.add_argument("--visibility-map", default=None, metavar="OUT.npz")
+    g.add_argument("--map-cell", type=float, default=3.0, metavar="ARCSEC")
+    g.add_argument("--map-all", action="store_true")
     g.set_defaults(fn=cmd_gen)
     p = sub.add_parser("output-atm")
     p.add_argument("config")

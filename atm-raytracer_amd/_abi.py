@@ -143,6 +143,21 @@ class DrawnTick(C.Structure):
                 ("label", C.c_char * TICK_LABEL_BYTES)]
 
 
+# atmrt_visibility_mode
+VIS_FIRST, VIS_ALL = 0, 1
+VIS_MODES = {"first": VIS_FIRST, "all": VIS_ALL}
+
+
+class GeoGrid(C.Structure):
+    """atmrt_geo_grid_t: cell (i, j) covers [lat0 + i cell_lat, + cell_lat) x [lon0 + j cell_lon, + cell_lon), plain degrees."""
+    _fields_ = [("lat0", C.c_double), ("lon0", C.c_double), ("cell_lat", C.c_double), ("cell_lon", C.c_double),
+                ("n_lat", C.c_uint32), ("n_lon", C.c_uint32)]
+
+
+class VisibilityStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_binned", "n_outside", "n_skipped", "n_updates")]
+
+
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""
     import numpy as np

@@ -137,6 +137,9 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 14: return sizeof(atmrt_tick_t);
     case 15: return sizeof(atmrt_overlay_t);
     case 16: return sizeof(atmrt_drawn_tick_t);
+    // 17 stays 0
+    case 18: return sizeof(atmrt_geo_grid_t);
+    case 19: return sizeof(atmrt_visibility_stats_t);
     default: return 0;
   }
 }
@@ -1611,6 +1614,134 @@ extern "C" int atmrt_draw_overlay_planes_device(atmrt_ctx* c, const atmrt_overla
   if (!k->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay_planes_device needs a frame: call atmrt_generate_image_device first");
   return draw_overlay_on(k, c, c->params, *overlay, azimuth, elevation_angle, (int)width, (int)height, rgb_device, drawn, capacity, n_drawn,
                          flat_horizon_deg);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the visibility map: the frame's trace points binned over a latitude / longitude grid (kernels: atmrt_vismap.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int atmrt_geo_grid_cell(const atmrt_geo_grid_t* g, double lat, double lon, int64_t* cell) {
+  if (!g || !cell) return ATMRT_ERR_INVALID_ARGUMENT;
+  *cell = -1;
+  if (geo_grid_check(*g)) return ATMRT_ERR_INVALID_ARGUMENT;
+  *cell = geo_grid_cell(*g, lat, lon);
+  return ATMRT_OK;
+}
+
+namespace {
+
+// The trace points a mode reads: entry p of the planes, or the lists (hit_offset set).
+struct VisSource {
+  size_t n_pixels;
+  const uint32_t* hit_count;
+  const uint64_t* hit_offset;
+  const double *lat, *lon, *dist;
+};
+
+// ATMRT_VIS_ALL reads the packed lists where the last frame has them; a frame without lists holds one point per pixel at most, in
+// its planes, and ALL is FIRST.
+VisSource vis_source_of_last_frame(const atmrt_ctx* c, int32_t mode) {
+  if (mode == ATMRT_VIS_ALL && c->last_packed)
+    return VisSource{c->last_npx, c->last_dense.hit_count, c->last_offset, c->last_hits.lat, c->last_hits.lon, c->last_hits.distance};
+  return VisSource{c->last_npx, c->last_dense.hit_count, nullptr, c->last_dense.lat, c->last_dense.lon, c->last_dense.distance};
+}
+
+bool vis_aggregate() { // read at every call, like ATMRT_ESCAPE
+  const char* e = getenv("ATMRT_VIS_AGGREGATE");
+  return !(e && !strcmp(e, "off"));
+}
+
+// k: the context whose device holds the memory; report: the context the caller handed in (its parent on a multi-device context).
+// grid == nullptr: only the bounds.
+int vis_run(atmrt_ctx* k, atmrt_ctx* report, const VisSource& src, const atmrt_geo_grid_t* grid, uint32_t* count, double* min_distance,
+            atmrt_visibility_stats_t* stats, double* bounds) {
+#define VIS_TRY(expr)                                                                                        \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess) return report->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+  VIS_TRY(hipSetDevice(k->device));
+  hipStream_t s = k->stream;
+  VIS_TRY(k->d_vis.reserve(vis_block_bytes()));
+  launch_vis_reset(k->d_vis.ptr, s);
+  if (grid) launch_vis_map(src.n_pixels, *grid, src.hit_count, src.hit_offset, src.lat, src.lon, src.dist, vis_aggregate(), count, min_distance, k->d_vis.ptr, s);
+  else launch_vis_bounds(src.n_pixels, src.hit_count, src.hit_offset, src.lat, src.lon, src.dist, k->d_vis.ptr, s);
+  uint64_t block[16] = {};
+  VIS_TRY(hipMemcpyAsync(block, k->d_vis.ptr, vis_block_bytes(), hipMemcpyDeviceToHost, s));
+  VIS_TRY(hipStreamSynchronize(s));
+  VIS_TRY(hipGetLastError());
+  vis_block_decode(block, stats, bounds);
+  return ATMRT_OK;
+#undef VIS_TRY
+}
+
+// the checks every map entry point shares; 0 or a status with the message set
+int vis_check(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, const void* count) {
+  if (!grid) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "grid is NULL");
+  if (!count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count is NULL");
+  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
+  if (const char* msg = geo_grid_check(*grid)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  return ATMRT_OK;
+}
+int vis_check_state(atmrt_ctx* c, const char* what) {
+  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context has no frame of its own: %s works on the gathered planes through atmrt_visibility_map_planes_device", what);
+  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "%s needs a frame: call atmrt_generate first", what);
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_frame_bounds(atmrt_ctx* c, int32_t mode, double out[4]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
+  if (int rc = vis_check_state(c, "atmrt_frame_bounds")) return rc;
+  return vis_run(c, c, vis_source_of_last_frame(c, mode), nullptr, nullptr, nullptr, nullptr, out);
+}
+
+extern "C" int atmrt_visibility_map_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count_device,
+                                           double* min_distance_device, atmrt_visibility_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = vis_check(c, grid, mode, count_device)) return rc;
+  if (int rc = vis_check_state(c, "atmrt_visibility_map")) return rc;
+  return vis_run(c, c, vis_source_of_last_frame(c, mode), grid, count_device, min_distance_device, stats, nullptr);
+}
+
+extern "C" int atmrt_visibility_map(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count, double* min_distance,
+                                    atmrt_visibility_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = vis_check(c, grid, mode, count)) return rc;
+  if (int rc = vis_check_state(c, "atmrt_visibility_map")) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n_cells = (size_t)grid->n_lat * grid->n_lon, count_bytes = Carve::pad(n_cells * sizeof(uint32_t));
+  HIP_TRY(c, c->d_io.reserve(count_bytes + n_cells * sizeof(double)));
+  uint32_t* d_count = c->d_io.as<uint32_t>();
+  double* d_min = min_distance ? reinterpret_cast<double*>(c->d_io.as<char>() + count_bytes) : nullptr;
+  if (int rc = atmrt_visibility_map_device(c, grid, mode, d_count, d_min, stats)) return rc;
+  HIP_TRY(c, hipMemcpy(count, d_count, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (min_distance) HIP_TRY(c, hipMemcpy(min_distance, d_min, n_cells * sizeof(double), hipMemcpyDeviceToHost));
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_visibility_map_planes_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, const double* lat, const double* lon,
+                                                  const double* distance, const uint32_t* hit_count, uint32_t width, uint32_t height,
+                                                  uint32_t* count_device, double* min_distance_device, atmrt_visibility_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = vis_check(c, grid, ATMRT_VIS_FIRST, count_device)) return rc;
+  if (!lat || !lon || !distance || !hit_count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a plane is NULL");
+  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
+  atmrt_ctx* k = c;
+  if (c->multi) { // the device context that owns the memory: its stream, its statistics block
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, count_device) != hipSuccess) {
+      (void)hipGetLastError();
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count_device is not a device allocation");
+    }
+    k = nullptr;
+    for (int i = 0; i < multi_size(c) && !k; i++)
+      if (multi_child(c, i)->device == attr.device) k = multi_child(c, i);
+    if (!k) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count_device is in the memory of device %d, which is not a device of this context", attr.device);
+  }
+  return vis_run(k, c, VisSource{(size_t)width * height, hit_count, nullptr, lat, lon, distance}, grid, count_device, min_distance_device, stats,
+                 nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

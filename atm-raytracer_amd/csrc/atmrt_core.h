@@ -1426,4 +1426,22 @@ ATMRT_HD void rect_ray_params(const atmrt_params_t& p, const Pinhole& ph, int px
 // TracingState::interpolate for one scalar, utils.rs:108-125
 ATMRT_HD double lerp_ts(double a, double b, double prop) { return a + (b - a) * prop; }
 
+// The binning rule of the visibility map (include/atmrt.h, atmrt_geo_grid_t): IEEE subtraction and division — `/`, not the dm_div*
+// shortcuts, whose operand range a caller's grid need not respect — and floor, nothing contracted; numpy's
+// np.floor((lat - lat0) / cell).  The index tests are made on the doubles, before any conversion: NaN, infinities and 1e300 are
+// outside.  Longitudes are plain degrees, no antimeridian handling.  Returns i * n_lon + j, or -1.
+ATMRT_HD int64_t geo_grid_cell(const atmrt_geo_grid_t& g, double lat, double lon) {
+  const double fi = dm_floor((lat - g.lat0) / g.cell_lat), fj = dm_floor((lon - g.lon0) / g.cell_lon);
+  if (!(fi >= 0.0 && fi < (double)g.n_lat && fj >= 0.0 && fj < (double)g.n_lon)) return -1;
+  return (int64_t)fi * (int64_t)g.n_lon + (int64_t)fj;
+}
+// What the entry points refuse (atmrt_geo_grid_t): nullptr when the grid is fine.
+ATMRT_HD const char* geo_grid_check(const atmrt_geo_grid_t& g) {
+  if (!(g.cell_lat > 0.0 && g.cell_lat < __builtin_inf() && g.cell_lon > 0.0 && g.cell_lon < __builtin_inf())) return "the cell size of the grid must be finite and positive";
+  if (!(g.lat0 > -__builtin_inf() && g.lat0 < __builtin_inf() && g.lon0 > -__builtin_inf() && g.lon0 < __builtin_inf())) return "the corner of the grid must be finite";
+  if (g.n_lat == 0 || g.n_lon == 0) return "n_lat and n_lon of the grid must be at least 1";
+  if ((uint64_t)g.n_lat * g.n_lon > (1ull << 31)) return "the grid has more than 2^31 cells";
+  return nullptr;
+}
+
 } // namespace atmrt

@@ -454,6 +454,19 @@ void launch_overlay_find_elev(const double* elev, int w, int h, int bands, doubl
 void launch_overlay_lines(const int32_t* y_of_x, int w, int h, uint8_t* rgb, const uint8_t color[3], hipStream_t stream);
 void launch_overlay_ticks(const void* ticks, int n, int w, int h, uint8_t* rgb, hipStream_t stream);
 
+// The visibility map (kernels in atmrt_vismap.h).  `block` is the call's device block of vis_block_bytes(): launch_vis_reset
+// initialises it, the scatter adds its statistics and the bounds kernel its keys, vis_block_decode reads a host copy of it.  The
+// points are entry p of the planes lat / lon / dist where hit_count[p] != 0 (hit_offset null), or entries [hit_offset[p],
+// + hit_count[p]) of the lists.  min_distance may be null.
+size_t vis_block_bytes();
+void vis_block_decode(const void* block_host, atmrt_visibility_stats_t* stats, double bounds[4]);
+void launch_vis_reset(void* block, hipStream_t stream);
+void launch_vis_map(size_t n_pixels, const atmrt_geo_grid_t& grid, const uint32_t* hit_count, const uint64_t* hit_offset,
+                    const double* lat, const double* lon, const double* dist, bool aggregate, uint32_t* count, double* min_distance,
+                    void* block, hipStream_t stream);
+void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_t* hit_offset, const double* lat, const double* lon,
+                       const double* dist, void* block, hipStream_t stream);
+
 void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream);
 void launch_rect_trace_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,

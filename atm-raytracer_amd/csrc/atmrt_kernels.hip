@@ -17,6 +17,7 @@
 #include "atmrt_device.h"
 #include "atmrt_overlay.h"
 #include "atmrt_render.h"
+#include "atmrt_vismap.h"
 
 namespace atmrt {
 
@@ -1324,6 +1325,54 @@ void launch_overlay_lines(const int32_t* y_of_x, int w, int h, uint8_t* rgb, con
 void launch_overlay_ticks(const void* ticks, int n, int w, int h, uint8_t* rgb, hipStream_t stream) {
   if (n > 0)
     hipLaunchKernelGGL(k_overlay_ticks, dim3(cdiv((size_t)n, 64)), dim3(64), 0, stream, static_cast<const OverlayTick*>(ticks), n, w, h, rgb);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the visibility map (kernels: atmrt_vismap.h)
+// ---------------------------------------------------------------------------------------------
+size_t vis_block_bytes() { return VIS_N * sizeof(unsigned long long); }
+void vis_block_decode(const void* block_host, atmrt_visibility_stats_t* stats, double bounds[4]) {
+  const unsigned long long* b = static_cast<const unsigned long long*>(block_host);
+  if (stats) *stats = atmrt_visibility_stats_t{b[VIS_POINTS], b[VIS_BINNED], b[VIS_OUTSIDE], b[VIS_SKIPPED], b[VIS_UPDATES]};
+  if (bounds)
+    for (int i = 0; i < 4; i++) { // the inverse of vis_key; no point at all: the maxima are still 0
+      const unsigned long long k = b[VIS_LAT_MIN + i], bits = (k >> 63) ? k & 0x7fffffffffffffffull : ~k;
+      double v;
+      memcpy(&v, &bits, sizeof v);
+      bounds[i] = b[VIS_LAT_MAX] == 0ull ? NAN : v;
+    }
+}
+void launch_vis_reset(void* block, hipStream_t stream) {
+  hipLaunchKernelGGL(k_vis_reset, dim3(1), dim3(64), 0, stream, static_cast<unsigned long long*>(block));
+}
+void launch_vis_map(size_t n_pixels, const atmrt_geo_grid_t& grid, const uint32_t* hit_count, const uint64_t* hit_offset,
+                    const double* lat, const double* lon, const double* dist, bool aggregate, uint32_t* count, double* min_distance,
+                    void* block, hipStream_t stream) {
+  const size_t n_cells = (size_t)grid.n_lat * grid.n_lon;
+  unsigned long long* mind = reinterpret_cast<unsigned long long*>(min_distance);
+  unsigned long long* ctr = static_cast<unsigned long long*>(block);
+  hipLaunchKernelGGL(k_vis_clear, dim3(cdiv(n_cells, 256)), dim3(256), 0, stream, n_cells, count, mind);
+  if (!n_pixels) return;
+  const dim3 grd(cdiv(n_pixels, 256)), blk(256);
+#define VIS_LAUNCH(PACKED, AGG) \
+  hipLaunchKernelGGL((k_vis_scatter<PACKED, AGG>), grd, blk, 0, stream, n_pixels, grid, hit_count, hit_offset, lat, lon, dist, count, mind, ctr)
+  if (hit_offset) {
+    if (aggregate) VIS_LAUNCH(true, true);
+    else VIS_LAUNCH(true, false);
+  } else {
+    if (aggregate) VIS_LAUNCH(false, true);
+    else VIS_LAUNCH(false, false);
+  }
+#undef VIS_LAUNCH
+}
+void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_t* hit_offset, const double* lat, const double* lon,
+                       const double* dist, void* block, hipStream_t stream) {
+  if (!n_pixels) return;
+  unsigned long long* ctr = static_cast<unsigned long long*>(block);
+  if (hit_offset)
+    hipLaunchKernelGGL((k_vis_bounds<true>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, hit_count, hit_offset, lat, lon, dist, ctr);
+  else
+    hipLaunchKernelGGL((k_vis_bounds<false>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, hit_count, hit_offset, lat, lon, dist, ctr);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -426,6 +426,91 @@ def draw_overlay_device(ctx, overlay, rgb_ptr, width, height, planes=None):
     return _drawn_ticks(arr, n.value), deg.value
 
 
+# ---- the visibility map: the frame's trace points binned over a latitude / longitude grid (no reference counterpart) ------
+GeoGrid = _abi.GeoGrid
+
+
+def geo_grid_cell(grid, lat, lon, lib=None):
+    """atmrt_geo_grid_cell (host code, no device) for scalars or arrays: the cell index i * n_lon + j of every point, -1 outside."""
+    lib = lib or _lib.load()
+    lat, lon = np.broadcast_arrays(np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64))
+    out = np.empty(lat.shape, dtype=np.int64)
+    cell = C.c_int64()
+    flat = out.reshape(-1)
+    for i, (a, b) in enumerate(zip(lat.ravel().tolist(), lon.ravel().tolist())):
+        rc = lib.atmrt_geo_grid_cell(C.byref(grid), a, b, C.byref(cell))
+        if rc != 0:
+            raise AtmrtError(rc, "atmrt_geo_grid_cell refused the grid")
+        flat[i] = cell.value
+    return out if out.ndim else int(out)
+
+
+def snap_grid(bounds, cell_lat, cell_lon=None):
+    """The grid that covers bounds = (lat_min, lat_max, lon_min, lon_max), snapped outward to multiples of the cell size; a point
+    exactly on the snapped top or right edge gets a row / column of its own.  None when the bounds are NaN (no trace point)."""
+    cell_lon = cell_lat if cell_lon is None else cell_lon
+    if any(np.isnan(b) for b in bounds):
+        return None
+
+    def axis(lo, hi, cell):  # first cell index and cell count; the binning rule itself has the last word on both ends
+        i0 = int(np.floor(lo / cell))
+        while np.floor((lo - i0 * cell) / cell) < 0:
+            i0 -= 1
+        n = int(np.floor(hi / cell)) - i0 + 1
+        while np.floor((hi - i0 * cell) / cell) >= n:
+            n += 1
+        return i0 * cell, n
+
+    (lat0, n_lat), (lon0, n_lon) = axis(bounds[0], bounds[1], cell_lat), axis(bounds[2], bounds[3], cell_lon)
+    return GeoGrid(lat0, lon0, cell_lat, cell_lon, n_lat, n_lon)
+
+
+def _vis_stats(st):
+    return {k: getattr(st, k) for k, _ in _abi.VisibilityStats._fields_}
+
+
+def frame_bounds(ctx, mode="first"):
+    """(lat_min, lat_max, lon_min, lon_max) over the trace points of the last generate() on `ctx` that `mode` ("first" / "all")
+    would bin; all NaN for a frame without one."""
+    out = (C.c_double * 4)()
+    ctx.check(ctx.lib.atmrt_frame_bounds(ctx.handle, _abi.VIS_MODES[mode], out))
+    return tuple(out)
+
+
+def visibility_map(ctx, grid, mode="first"):
+    """The visibility map of the last generate() on `ctx`: (count [n_lat][n_lon] uint32, min_distance [n_lat][n_lon] float64 with
+    +inf in empty cells, stats dict)."""
+    count = np.empty((grid.n_lat, grid.n_lon), dtype=np.uint32)
+    mind = np.empty((grid.n_lat, grid.n_lon), dtype=np.float64)
+    st = _abi.VisibilityStats()
+    ctx.check(ctx.lib.atmrt_visibility_map(ctx.handle, C.byref(grid), _abi.VIS_MODES[mode], count.ctypes.data, mind.ctypes.data, C.byref(st)))
+    return count, mind, _vis_stats(st)
+
+
+def visibility_map_device(ctx, grid, mode="first", planes=None, device=None):
+    """The same left in HBM as torch tensors (count int32 — the bits of the u32 counts — and min_distance float64).  planes = a dict
+    of [H][W] torch tensors lat, lon, distance, hit_count bins explicit planes (a gathered multi-device frame; "first" only)
+    instead of the context's last frame.  Returns (count, min_distance, stats)."""
+    import torch
+    if planes is not None:
+        dev = planes["lat"].device
+    else:
+        dev = torch.device("cuda", ctx.device if device is None else device)
+    count = torch.empty((grid.n_lat, grid.n_lon), dtype=torch.int32, device=dev)
+    mind = torch.empty((grid.n_lat, grid.n_lon), dtype=torch.float64, device=dev)
+    st = _abi.VisibilityStats()
+    if planes is None:
+        ctx.check(ctx.lib.atmrt_visibility_map_device(ctx.handle, C.byref(grid), _abi.VIS_MODES[mode], count.data_ptr(), mind.data_ptr(), C.byref(st)))
+    else:
+        if mode != "first":
+            raise ValueError("explicit planes hold the first trace point of every pixel: mode must be 'first'")
+        h, w = planes["lat"].shape
+        ctx.check(ctx.lib.atmrt_visibility_map_planes_device(ctx.handle, C.byref(grid), planes["lat"].data_ptr(), planes["lon"].data_ptr(),
+                                                             planes["distance"].data_ptr(), planes["hit_count"].data_ptr(), w, h,
+                                                             count.data_ptr(), mind.data_ptr(), C.byref(st)))
+    return count, mind, _vis_stats(st)
+
+
 # ---- integrator / sampler harnesses (ray_path.rs, atm_printer.rs, elev_profile.rs) -------------
 def ray_paths(ctx, h0, angles_deg, step, n_steps, straight=False):
     ang = np.ascontiguousarray(angles_deg, dtype=np.float64)

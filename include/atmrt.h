@@ -403,6 +403,57 @@ int atmrt_draw_overlay_planes_device(atmrt_ctx* ctx, const atmrt_overlay_t* over
                                      const double* elevation_angle, uint32_t width, uint32_t height, uint8_t* rgb_device,
                                      atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg);
 
+/* ---- the visibility map: the frame's trace points binned over a latitude / longitude grid (no reference counterpart: the
+ * reference's `view` window answers "what does this pixel see" one click at a time, viewer/app.rs:112-176; this is the inverse
+ * picture — which ground is visible from here, and how far away it is).  One scatter pass over the frame where it lies in HBM. */
+/* A regular grid in plain degrees.  Cell (i, j) covers [lat0 + i cell_lat, lat0 + (i + 1) cell_lat) x [lon0 + j cell_lon,
+ * lon0 + (j + 1) cell_lon): the south and west edges belong to it, the north and east ones to its neighbour, so the top and right
+ * edges of the grid are outside.  There is NO antimeridian handling: longitudes are binned as the plain numbers the generators
+ * emit (a frame across +-180 degrees needs two grids). */
+typedef struct atmrt_geo_grid {
+  double lat0, lon0;          /* south-west corner [deg], finite */
+  double cell_lat, cell_lon;  /* cell size [deg], finite and > 0 */
+  uint32_t n_lat, n_lon;      /* rows south -> north, columns west -> east; both >= 1, n_lat * n_lon <= 2^31 */
+} atmrt_geo_grid_t;
+/* The binning rule, host code, ctx-free: fi = floor((lat - lat0) / cell_lat), fj = floor((lon - lon0) / cell_lon) in IEEE
+ * arithmetic (numpy's np.floor((lat - lat0) / cell)); inside iff 0 <= fi < n_lat and 0 <= fj < n_lon, compared as doubles, so
+ * NaN, infinities and huge values are outside; *cell = i * n_lon + j, or -1 outside.  The kernels run the same function.
+ * A grid the rules above refuse: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_geo_grid_cell(const atmrt_geo_grid_t* g, double lat, double lon, int64_t* cell);
+typedef enum atmrt_visibility_mode {
+  ATMRT_VIS_FIRST = 0, /* the first trace point of every pixel, from the dense planes: any frame */
+  ATMRT_VIS_ALL = 1    /* every trace point of every pixel, from the packed lists where the frame has them, else as FIRST */
+} atmrt_visibility_mode;
+/* A trace point whose lat, lon or distance is NaN, or whose distance is negative, is skipped; every other one is looked up in
+ * the grid and is either binned or outside: n_points = n_binned + n_outside + n_skipped.  n_updates counts the pairs of atomic
+ * updates the kernel issued: within a wavefront (64 consecutive pixels p = y * width + x) a maximal run of consecutive lanes with
+ * the same cell makes ONE update carrying the run's point count and smallest distance, and a lane without a binned point ends
+ * a run.  ATMRT_VIS_AGGREGATE=off in the environment (read at every call) makes every lane update for itself: the same map,
+ * n_updates = n_binned. */
+typedef struct atmrt_visibility_stats {
+  uint64_t n_points, n_binned, n_outside, n_skipped, n_updates;
+} atmrt_visibility_stats_t;
+/* Minimum and maximum of lat and lon over the trace points `mode` would look up in a grid (the ones not skipped) of the last
+ * frame on ctx: out = {lat_min, lat_max, lon_min, lon_max}, all NaN when there is no such point.  State rules as below. */
+int atmrt_frame_bounds(atmrt_ctx* ctx, int32_t mode, double out[4]);
+/* The map of the last atmrt_generate / atmrt_generate_device frame on ctx (a column shard is a frame of its own), into
+ * caller-owned device memory, overwritten: count [n_lat][n_lon] u32 = binned trace points of the cell, min_distance (may be
+ * NULL) [n_lat][n_lon] f64 = the smallest TracePoint.distance among them (-0.0 counts as 0.0), +inf where count is 0.  Integer
+ * atomics only, so the map is the same to the bit at every call.  Same rules as atmrt_draw_image_device: ATMRT_ERR_STATE
+ * without a frame, after a failed one, and on a multi-device context (use atmrt_visibility_map_planes_device on the gathered
+ * planes).  A grid that breaks the rules of atmrt_geo_grid_t, an unknown mode, a NULL count: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_visibility_map_device(atmrt_ctx* ctx, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count_device,
+                                double* min_distance_device, atmrt_visibility_stats_t* stats /* may be NULL */);
+/* The same into host arrays, staged through the context's device. */
+int atmrt_visibility_map(atmrt_ctx* ctx, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count, double* min_distance,
+                         atmrt_visibility_stats_t* stats);
+/* The same over explicit [height][width] device planes (the route of a gathered multi-device frame: one device's planes of
+ * atmrt_generate_image_device), FIRST mode: pixel p has the point (lat[p], lon[p], distance[p]) when hit_count[p] != 0.  All
+ * pointers must be memory of one device of ctx. */
+int atmrt_visibility_map_planes_device(atmrt_ctx* ctx, const atmrt_geo_grid_t* grid, const double* lat, const double* lon,
+                                       const double* distance, const uint32_t* hit_count, uint32_t width, uint32_t height,
+                                       uint32_t* count_device, double* min_distance_device, atmrt_visibility_stats_t* stats);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —

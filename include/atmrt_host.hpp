@@ -268,4 +268,27 @@ inline DrawnOverlay draw_overlay(const Terrain& terrain, const Overlay& overlay,
   return out;
 }
 
+// The visibility map of the frame the last generate() on `terrain` produced (no reference counterpart): its trace points — the first
+// of every pixel, or all of them — binned over `grid`.  count and min_distance are [n_lat][n_lon], rows south to north;
+// min_distance is +inf where count is 0.
+struct VisibilityMap {
+  std::vector<uint32_t> count;
+  std::vector<double> min_distance;
+  atmrt_visibility_stats_t stats;
+};
+inline VisibilityMap visibility_map(const Terrain& terrain, const atmrt_geo_grid_t& grid, atmrt_visibility_mode mode = ATMRT_VIS_FIRST) {
+  VisibilityMap out;
+  const size_t n = (size_t)grid.n_lat * grid.n_lon;
+  out.count.resize(n);
+  out.min_distance.resize(n);
+  terrain.check(atmrt_visibility_map(terrain.ctx(), &grid, mode, out.count.data(), out.min_distance.data(), &out.stats));
+  return out;
+}
+// lat_min, lat_max, lon_min, lon_max of those trace points: the natural extent of a grid; all NaN for a frame of sky.
+inline std::array<double, 4> frame_bounds(const Terrain& terrain, atmrt_visibility_mode mode = ATMRT_VIS_FIRST) {
+  std::array<double, 4> out{};
+  terrain.check(atmrt_frame_bounds(terrain.ctx(), mode, out.data()));
+  return out;
+}
+
 } // namespace atmrt_host
