@@ -664,6 +664,11 @@ static bool escape_enabled() {
   const char* e = getenv("ATMRT_ESCAPE");
   return !(e && !strcmp(e, "off"));
 }
+// ATMRT_STEP_TRIG=off: no table of the geodesic's sin / cos (Frame::xs_sin), every sample computes them (A/B runs, tests/test_gpu_step_trig.py)
+static bool step_trig_enabled() {
+  const char* e = getenv("ATMRT_STEP_TRIG");
+  return !(e && !strcmp(e, "off"));
+}
 
 extern "C" int atmrt_escape_certificate(const atmrt_atmosphere_t* atmosphere, double wavelength, int32_t spherical, double radius,
                                         int32_t straight, double simulation_step, double top, double out[3]) {
@@ -725,6 +730,19 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
     HIP_TRY(c, c->d_xs.reserve(c->xs.size() * sizeof(double)));
     HIP_TRY(c, hipMemcpy(c->d_xs.ptr, c->xs.data(), c->xs.size() * sizeof(double), hipMemcpyHostToDevice));
     c->xs_dirty = false;
+    c->trig_valid = false;
+  }
+  // The Spherical calculator's sin / cos of xs[k] / calc_radius, by the device code the samples would run (k_step_trig): like xs they
+  // depend on nothing of the ray or the observer and survive the frame.  The kernels of this frame follow on the same stream.
+  const bool trig = c->earth.calc == 2 && step_trig_enabled();
+  const size_t n_trig = (size_t)c->march_steps + 1;
+  if (trig && !(c->trig_valid && c->trig_radius == c->earth.calc_radius && c->trig_fast_div == (c->earth.flat_dirs & EARTH_FAST_DIV))) {
+    HIP_TRY(c, c->d_xs_trig.reserve(2 * n_trig * sizeof(double)));
+    launch_step_trig(c->earth, n_trig, c->d_xs.as<double>(), c->d_xs_trig.as<double>(), c->d_xs_trig.as<double>() + n_trig, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    c->trig_radius = c->earth.calc_radius;
+    c->trig_fast_div = c->earth.flat_dirs & EARTH_FAST_DIV;
+    c->trig_valid = true;
   }
   Frame f{};
   f.p = p;
@@ -742,6 +760,8 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   HIP_TRY(c, c->d_alt.reserve(sizeof(double)));
   f.alt = c->d_alt.as<double>();
   f.xs = c->d_xs.as<double>();
+  f.xs_sin = trig ? c->d_xs_trig.as<double>() : nullptr;
+  f.xs_cos = trig ? c->d_xs_trig.as<double>() + n_trig : nullptr;
   // the device table is rewritten by k_resolve every frame (Altitude::abs depends on the terrain), so upload it each time
   if (!c->objects.empty()) {
     HIP_TRY(c, c->d_objects.reserve(c->objects.size() * sizeof(ObjectDev)));
@@ -1850,6 +1870,23 @@ extern "C" int atmrt_coords_at_dist(atmrt_ctx* c, double lat0, double lon0, doub
   launch_coords_at_dist(f, lat0, lon0, dir_deg, n, d, d + n, d + 2 * n, c->stream);
   HIP_TRY(c, hipMemcpyAsync(lat, d + n, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(lon, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_step_trig(atmrt_ctx* c, size_t cap, double* xs, double* sin_out, double* cos_out, size_t* n_out) {
+  if (!c || !n_out || (cap && (!xs || !sin_out || !cos_out))) return ATMRT_ERR_INVALID_ARGUMENT;
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_step_trig(k_, cap, xs, sin_out, cos_out, n_out));
+  Frame f;
+  int rc = harness_frame(c, &f);
+  if (rc) return rc;
+  *n_out = f.xs_sin ? (size_t)f.march_steps + 1 : 0;
+  const size_t n = *n_out < cap ? *n_out : cap;
+  if (!n) return ATMRT_OK;
+  HIP_TRY(c, hipMemcpyAsync(xs, f.xs, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(sin_out, f.xs_sin, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(cos_out, f.xs_cos, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
   return ATMRT_OK;

@@ -1020,17 +1020,29 @@ ATMRT_HD void dircalc_new(const Earth& e, double lat, double lon, double dir, Di
   }
 }
 
+// The angle dist / calc_radius of SphericalCalc::coords_at_dist and its sine and cosine: the part of the geodesic point that depends
+// on the distance only, not on the ray.  The marching kernels read it from a table over the stepper's distances (Frame::xs_sin /
+// xs_cos, filled by k_step_trig with this function: an entry is the bit pattern a lane computes here).
+ATMRT_HD void spherical_sincos(const Earth& e, double dist, double& sinang, double& cosang) {
+  double ang = (e.flat_dirs & EARTH_FAST_DIV) ? dm_div(dist, e.calc_radius) : dist / e.calc_radius;
+  dm_sincos(ang, &sinang, &cosang);
+}
+// SphericalCalc::coords_at_dist from the sine and cosine of dist / calc_radius on, directional_calc.rs:75-85
+ATMRT_HD void coords_at_dist_sc(const Earth& e, const DirCalc& c, double sinang, double cosang, double& lat, double& lon) {
+  (void)e;
+  double fx = c.pos.x * cosang + c.dir.x * sinang;
+  double fy = c.pos.y * cosang + c.dir.y * sinang;
+  double fz = c.pos.z * cosang + c.dir.z * sinang;
+  lat = dm_to_degrees(dm_asin(fz));
+  lon = dm_to_degrees(dm_atan2(fy, fx));
+}
+
 // DirectionalCalc::coords_at_dist
 ATMRT_HD void coords_at_dist(const Earth& e, const DirCalc& c, double dist, double& lat, double& lon) {
   if (e.calc == 2) { // SphericalCalc, directional_calc.rs:72-85
-    double ang = (e.flat_dirs & EARTH_FAST_DIV) ? dm_div(dist, e.calc_radius) : dist / e.calc_radius;
     double sinang, cosang;
-    dm_sincos(ang, &sinang, &cosang);
-    double fx = c.pos.x * cosang + c.dir.x * sinang;
-    double fy = c.pos.y * cosang + c.dir.y * sinang;
-    double fz = c.pos.z * cosang + c.dir.z * sinang;
-    lat = dm_to_degrees(dm_asin(fz));
-    lon = dm_to_degrees(dm_atan2(fy, fx));
+    spherical_sincos(e, dist, sinang, cosang);
+    coords_at_dist_sc(e, c, sinang, cosang, lat, lon);
   } else if (e.calc == 0) { // AzEqCalc, directional_calc.rs:20-28
     double px = c.pos.x + c.dir.x * dist, py = c.pos.y + c.dir.y * dist;
     lon = dm_to_degrees(dm_atan2(py, px));

@@ -144,6 +144,10 @@ struct atmrt_ctx {
   int n_t = 0, n_path_cap = 0;
   int march_steps = 0; // #{k >= 1 : xs[k] <= max_distance}: the steps of a ray that marches to the end
   bool xs_dirty = true;
+  // what the table in d_xs_trig (Frame::xs_sin / xs_cos) was built from besides xs itself (a new xs clears trig_valid)
+  double trig_radius = 0.0;
+  int32_t trig_fast_div = 0;
+  bool trig_valid = false;
 
   // last generated frame (for atmrt_draw_image)
   bool last_valid = false, last_packed = false;
@@ -169,6 +173,7 @@ struct atmrt_ctx {
   // by every prepare_workspace.  A buffer of its own needs a reason:
   // ... it survives the frame
   atmrt::DevBuf d_xs, d_atm;               // the distance table and the compiled atmosphere: uploaded when their inputs change
+  atmrt::DevBuf d_xs_trig;                 // Spherical calculator: sin, then cos, of xs[0 .. march_steps] / calc_radius (k_step_trig): rebuilt when xs, the radius or EARTH_FAST_DIV change
   atmrt::DevBuf d_alt;                     // the observer's altitude (k_resolve): atmrt_draw_overlay* samples the atmosphere there
   atmrt::DevBuf d_objects, d_textures;     // the scene: textures are uploaded when the objects change
   atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last_dense, last_hits, last_offset): draw, overlay, hits

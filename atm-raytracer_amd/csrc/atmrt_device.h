@@ -8,6 +8,17 @@ namespace atmrt {
 
 static __device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
+// The geodesic point of the sample after i steps: coords_at_dist(e, c, dist) for dist == f.xs[i], the stepper's x (0 + step + ... +
+// step, the additions of the table; i <= f.march_steps).  Spherical calculator: sin and cos of dist / calc_radius are the table's
+// (Frame::xs_sin), read through the constant address space like the atmosphere record — a scalar load where i is wave-uniform —
+// in place of a division and an argument reduction with two polynomials per lane.  Same bits: the table holds what
+// spherical_sincos returns for xs[i].  A distance that is not the table's (or no table) takes coords_at_dist.
+static __device__ __forceinline__ void coords_at_step(const Frame& f, const Earth& e, const DirCalc& c, int i, double dist, double& lat, double& lon) {
+  typedef const __attribute__((address_space(4))) double* ConstF64;
+  if (e.calc == 2 && f.xs_sin) coords_at_dist_sc(e, c, ((ConstF64)(uintptr_t)f.xs_sin)[i], ((ConstF64)(uintptr_t)f.xs_cos)[i], lat, lon);
+  else coords_at_dist(e, c, dist, lat, lon);
+}
+
 // TracePoint (generators/mod.rs:21-30) of a terrain hit
 struct TracePointDev {
   double lat, lon, distance, elevation, path_length;

@@ -41,6 +41,11 @@ struct Frame {
   double esc_floor;
   double esc_ang_max;
   int32_t march_steps;      // steps of a ray that marches to max_distance: #{k >= 1 : xs[k] <= max_distance}
+  // Spherical calculator (earth.calc == 2): sin and cos of xs[k] / calc_radius, k = 0 .. march_steps, as spherical_sincos computes
+  // them (k_step_trig) — the same for every ray of the frame, so a sample at the stepper's distance xs[k] reads them instead of
+  // dividing and reducing again (coords_at_step).  Null for the other calculators and under ATMRT_STEP_TRIG=off.
+  const double* xs_sin;
+  const double* xs_cos;
 };
 
 // column azimuth / row elevation in degrees, as handed to gen_terrain_cache / gen_path_cache
@@ -481,6 +486,7 @@ void launch_ray_paths(const Frame& f, double h0, size_t n_angles, const double* 
                       size_t n_steps, double* x, double* h, hipStream_t stream);
 void launch_atm_sample(const Frame& f, size_t n, const double* alt, double* t, double* p, double* nidx, double* dn,
                        hipStream_t stream);
+void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, double* c, hipStream_t stream);
 void launch_math_probe(int op, size_t n, const double* a, const double* b, double* out0, double* out1, hipStream_t stream);
 void launch_coords_at_dist(const Frame& f, double lat0, double lon0, double dir, size_t n, const double* dist,
                            double* lat, double* lon, hipStream_t stream);

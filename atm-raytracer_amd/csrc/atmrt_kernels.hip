@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_terrain_profile(Frame f, const DirCalc*
     int i = i0 + k;
     if (i >= f.n_t) break;
     double lat, lon;
-    coords_at_dist(e, c, f.xs[i], lat, lon);
+    coords_at_step(f, e, c, i, f.xs[i], lat, lon); // i < n_t <= march_steps + 1
     prof[(size_t)i * f.wl + x] = terrain_elev_or_zero(f.tv, lat, lon);
     if (STORE_LL) {
       plat[(size_t)i * f.wl + x] = lat;
@@ -1425,6 +1425,16 @@ __global__ void k_coords_at_dist(Frame f, double lat0, double lon0, double dir, 
   DirCalc c;
   dircalc_new(e, lat0, lon0, dir, c);
   coords_at_dist(e, c, dist[i], lat[i], lon[i]);
+}
+
+// Frame::xs_sin / xs_cos: the device code of coords_at_dist on the distance table, once per entry instead of once per ray and sample
+__global__ void k_step_trig(Earth e, size_t n, const double* __restrict__ xs, double* __restrict__ s, double* __restrict__ c) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  spherical_sincos(e, xs[i], s[i], c[i]);
+}
+void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, double* c, hipStream_t stream) {
+  if (n) hipLaunchKernelGGL(k_step_trig, dim3(cdiv(n, 256)), dim3(256), 0, stream, e, n, xs, s, c);
 }
 
 // detmath.h element-wise (atmrt_math_probe): the GPU's instruction sequences against the host's on arbitrary operands

@@ -168,8 +168,8 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
   const DirCalc& c = io->c;
   const double d0 = io->d0, sx = io->sx, re0 = io->re0, sh = io->sh, pl0 = io->pl0, path_length = io->path_length;
   double lat0, lon0, lat1, lon1;
-  coords_at_dist(e, c, d0, lat0, lon0);
-  coords_at_dist(e, c, sx, lat1, lon1);
+  coords_at_step(*fg, e, c, io->step_index, d0, lat0, lon0); // d0 = xs[step_index], sx = xs[step_index + 1] (march_steps)
+  coords_at_step(*fg, e, c, io->step_index + 1, sx, lat1, lon1);
   const double te0 = terrain_elev_or_zero(fg->tv, lat0, lon0), te1 = terrain_elev_or_zero(fg->tv, lat1, lon1);
   const double diff1 = re0 - te0, diff2 = sh - te1;
   StepHits hits;
@@ -368,7 +368,7 @@ static __device__ __forceinline__ bool march_begin(const Frame& f, const Earth& 
   r.count = 0;
   if (0.0 > f.p.frame.max_distance || alt < -1000.0) return false;
   double lat, lon;
-  coords_at_dist(e, c, 0.0, lat, lon);
+  coords_at_step(f, e, c, 0, 0.0, lat, lon);
   r.diff0 = alt - terrain_elev_or_zero(f.tv, lat, lon);
   n.lookups++;
   return true;
@@ -452,7 +452,12 @@ static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Ear
     // rows leave the terrain's height range together.  NaN heights take the full path.
     double diff1 = 1.0;
     if (!(r.sh > skip_above)) {
-      coords_at_dist(e, c, sx, lat, lon);
+      // sx = xs[i]: r.s.x starts at 0 (or at xs[i0], slice_save) and only ever advances by x + step (stepper_next_with), the
+      // additions of the table.  The rays of a wavefront march in step, so i is the same in every lane; a later slice reads its i0
+      // from the group's state (a vector register: every ray still marching was saved with the same step), hence the readfirstlane
+      // that makes the table read a scalar load there too.
+      const int iu = SLICED ? __builtin_amdgcn_readfirstlane(i) : i;
+      coords_at_step(f, e, c, iu, sx, lat, lon);
       diff1 = r.sh - terrain_elev_or_zero(f.tv, lat, lon);
       n.lookups++;
     }
@@ -836,8 +841,8 @@ static __device__ __forceinline__ TracePointDev rect_hit(const Frame& f, int x, 
   dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
   double d0 = f.xs[s], d1 = f.xs[s + 1]; // the stepper's x: 0 + step + ... (same additions as xs)
   double lat0, lon0, lat1, lon1;
-  coords_at_dist(e, c, d0, lat0, lon0);
-  coords_at_dist(e, c, d1, lat1, lon1);
+  coords_at_step(f, e, c, s, d0, lat0, lon0);
+  coords_at_step(f, e, c, s + 1, d1, lat1, lon1);
   double te0 = terrain_elev_or_zero(f.tv, lat0, lon0);
   double te1 = terrain_elev_or_zero(f.tv, lat1, lon1);
   return terrain_trace_point(f, e, lat0, lon0, te0, re0, d0, pl0, lat1, lon1, te1, re1, d1, pl1);
@@ -934,7 +939,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
     uint64_t k = FILL ? hit_offset[p] : 0;
     if (!(0.0 > max_dist || alt < -1000.0)) {
       double lat0, lon0;
-      coords_at_dist(e, c, 0.0, lat0, lon0);
+      coords_at_step(f, e, c, 0, 0.0, lat0, lon0);
       double te0 = terrain_elev_or_zero(f.tv, lat0, lon0);
       int cand[CAND_CAP];
       double clo[CAND_CAP], chi[CAND_CAP];
@@ -968,7 +973,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
         bool have1 = !use_cand || awake || !(sh_ > skip_above);
         double lat1 = 0.0, lon1 = 0.0, te1 = 0.0;
         if (have1) {
-          coords_at_dist(e, c, sx, lat1, lon1);
+          coords_at_step(f, e, c, i, sx, lat1, lon1); // sx = xs[i]: the stepper's x after i steps
           te1 = terrain_elev_or_zero(f.tv, lat1, lon1);
         }
         m1 = 0u;
@@ -1000,7 +1005,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
           for (int q = 0; q < 2; q++) { // rolled: one more instance of the geodesic code, not two (rare path)
             if (q == 0 ? have0 : have1) continue;
             double la, lo;
-            coords_at_dist(e, c, q == 0 ? d0 : sx, la, lo);
+            coords_at_step(f, e, c, q == 0 ? i - 1 : i, q == 0 ? d0 : sx, la, lo);
             const double te = terrain_elev_or_zero(f.tv, la, lo);
             if (q == 0) lat0 = la, lon0 = lo, te0 = te;
             else lat1 = la, lon1 = lo, te1 = te;

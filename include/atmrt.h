@@ -616,6 +616,11 @@ typedef enum atmrt_math_probe_op {
                                    out1 = dm_pow(a (1 - 2^-22), b) + dm_pow(a (1 + 2^-22), b) */
 } atmrt_math_probe_op;
 int atmrt_math_probe(atmrt_ctx* ctx, int32_t op, size_t n, const double* a, const double* b, double* out0, double* out1);
+/* The table the marching kernels read the Spherical geodesic's sin / cos from, for the parameters now set: *n = its entries
+ * (max over k of the stepper distances xs[k] <= max_distance, plus one; 0: no table — another calculator, or ATMRT_STEP_TRIG=off),
+ * and the first min(cap, *n) of xs[k], sin(xs[k] / radius), cos(xs[k] / radius).  tests/test_gpu_step_trig.py compares them with
+ * atmrt_math_probe's division and SINCOS: an entry must be the bit pattern a lane computes for that distance. */
+int atmrt_debug_step_trig(atmrt_ctx* ctx, size_t cap, double* xs, double* sin_out, double* cos_out, size_t* n);
 
 #ifdef __cplusplus
 }
