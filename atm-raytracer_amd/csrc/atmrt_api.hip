@@ -908,9 +908,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     }));
     HIP_TRY(c, reserve_carved(c->d_packed, [&](Carve& k) { packed = carve_packed(k, n_hits); }));
     if (f.opaque) launch_pack_first_hits(f, ws, dense, packed, s);
-    else if (general) launch_trace_fill(f, ws, n_hits, dense, packed, s);
-    else if (rect) launch_multi_fill(f, ws, n_hits, dense, packed, s);
-    else launch_multi_fill_fast(f, ws, n_hits, dense, packed, s);
+    else launch_list_fill(f, ws, n_hits, dense, packed, s);
     if (n_hits_out) *n_hits_out = n_hits;
   }
   HIP_TRY(c, hipEventRecord(ev[8], s));

@@ -401,6 +401,13 @@ static __device__ __forceinline__ void rec_copy(const Dst& dst, size_t k, const 
   dst.re1[k] = src.re1[q];
   dst.pl1[k] = src.pl1[q];
 }
+// one whole trace point, tag and colour included, from entry q of one PackedHits to entry k of another: every array packed_fields names
+static __device__ __forceinline__ void packed_copy(const PackedHits& dst, size_t k, const PackedHits& src, size_t q) {
+  packed_fields([&](size_t bytes, auto* to, const auto* from) {
+    const size_t n = bytes / sizeof *to; // values per entry
+    for (size_t c = 0; c < n; c++) to[n * k + c] = from[n * q + c];
+  }, dst, src);
+}
 
 // where the out-of-line object step of the lean march (object_step_impl, atmrt_march_impl.h) writes: the general tracer's arenas of
 // the counting pass.  A copy lives in HBM beside a copy of the Frame (Workspace::step_ctx): an out-of-line device function cannot

@@ -163,7 +163,7 @@ struct PathSegState {
 // Device counters of a frame (Workspace::counters), by slot.  Slot 3 has three uses: in a Fast frame with objects, the scan total
 // of the close lists (launch_close_count; the host reads it at once); in a Rectilinear frame, first the pixels that overflowed
 // their slots (counted by the counting passes), then, reset by the host once it has read that count, the cursor of the list of
-// those pixels (the gather kernels append to it).
+// those pixels (k_gather_slots appends to it, atmrt_kernels.hip).
 enum Counter : int {
   CTR_RAY_STEPS = 0,
   CTR_HITS = 1, // total of the last launch_scan_counts: trace points of the frame
@@ -188,6 +188,16 @@ constexpr int N_COUNTERS = 16;
 
 // crossings per pixel recorded by the counting march (4096x2048 headline at terrain_alpha 0.5: 99.3 % of the pixels have <= 4)
 constexpr int RECT_SLOTS = 4;
+// Where slot j of pixel p lies in the slot arena (Workspace::slot_step and the arrays beside it) of a frame of `plane` pixels.  Frames
+// without objects keep it slot-major, [RECT_SLOTS][plane]: their counting passes (k_fast_intersect, the lean march in MODE 1) run
+// one pixel per lane, so a wavefront's stores to one slot coalesce.  Scenes with objects keep it pixel-major, [plane][RECT_SLOTS]:
+// the general tracers (k_fast_trace, k_rect_trace, the lean march's object step) emit the points of one step into consecutive
+// entries (step_emit), and the counting passes around them (k_fast_intersect with slot_tag, the lean march in MODE 3) follow suit.
+enum class SlotLayout { SlotMajor, PixelMajor };
+template <SlotLayout LAYOUT>
+ATMRT_HD size_t slot_index(size_t p, size_t j, size_t plane) {
+  return LAYOUT == SlotLayout::PixelMajor ? p * RECT_SLOTS + j : j * plane + p;
+}
 
 // Trace points beyond a pixel's RECT_SLOTS slots (translucent terrain, scenes with objects): appended by the counting passes in any
 // order, each with its pixel and its ordinal among the pixel's trace points; CTR_OVERFLOW_RECORDS counts them (more than `cap`: the
@@ -297,11 +307,11 @@ struct Workspace {
   double* col_hi;
   uint8_t* traced;        // 1 = the pixel can have a step with an object (k_fast_flag_rows)
   // translucent terrain or objects: the counting passes keep the first RECT_SLOTS trace points of every pixel, so that only pixels
-  // with more are visited a second time
+  // with more are visited a second time — the slot arena, entry slot_index(p, j) of each array (k_gather_slots moves it to the list)
   uint32_t* slot_step;
   double* slot_rec;       // Rectilinear
   uint32_t* slot_pixel;   // scenes with objects (written by step_emit, not read)
-  PackedHits slot_packed; // scenes with objects: trace points of the slots, entry p * RECT_SLOTS + j
+  PackedHits slot_packed; // scenes with objects: trace points of the slots
   char* overflow_arena;   // Rectilinear, translucent terrain or objects: trace points beyond the slots (OverflowArena), or null
   PackedHits overflow_packed; // scenes with objects: the arena's complete points
   size_t overflow_cap;    // its capacity in records (set before the layout runs: prepare_workspace)
@@ -356,7 +366,7 @@ static inline void workspace_layout(const Frame& f, Carve& k, Workspace& ws) {
   // writes the slots and only the fill pass writes rect_rec
   if (rect && f.opaque) k(ws.rect_rec, 4 * npx * sizeof(double));
   if (!f.opaque) {
-    k(ws.slot_step, RECT_SLOTS * npx * sizeof(uint32_t));               // [RECT_SLOTS][h][wl]; with objects [h][wl][RECT_SLOTS]
+    k(ws.slot_step, RECT_SLOTS * npx * sizeof(uint32_t));               // slot_index: [RECT_SLOTS][h][wl]; with objects [h][wl][RECT_SLOTS]
     if (rect) k(ws.slot_rec, 4 * RECT_SLOTS * npx * sizeof(double));    // [4][RECT_SLOTS][h][wl]
     if (objects) {
       k(ws.slot_pixel, RECT_SLOTS * npx * sizeof(uint32_t));            // [h][wl][RECT_SLOTS]
@@ -421,8 +431,6 @@ void launch_close_fill(const Frame& f, Workspace& ws, hipStream_t stream);
 // exclusive scan of in[0, n) into out; the grand total into *total (and nothing else)
 void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* tmp, uint64_t* out, unsigned long long* total, hipStream_t stream);
 void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
-void launch_trace_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
-                       hipStream_t stream);
 void launch_fast_paths(const Frame& f, Workspace& ws, hipStream_t stream, int i_begin, int i_end); // atmrt_paths.hip
 #ifndef ATMRT_FAST_SEGMENTS
 #define ATMRT_FAST_SEGMENTS 4
@@ -438,12 +446,15 @@ void launch_rect_march(const Frame& f, Workspace& ws, const DensePlanes& out, hi
 void launch_scan_counts(const Frame& f, Workspace& ws, const uint32_t* hit_count, hipStream_t stream);
 void launch_pack_first_hits(const Frame& f, Workspace& ws, const DensePlanes& dense, const PackedHits& packed,
                             hipStream_t stream);
-// multi-hit (terrain_alpha < 1): count -> scan -> fill
-void launch_multi_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
-                       hipStream_t stream);
-
-void launch_multi_fill_fast(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense,
-                            const PackedHits& packed, hipStream_t stream);
+// several trace points per pixel (terrain_alpha < 1, scenes with objects), count -> scan -> fill: the fill of every route — what the
+// counting pass recorded to the pixel-ordered list, a second pass over the pixels that did not cover, the points completed
+void launch_list_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
+                      hipStream_t stream);
+// its Rectilinear parts (atmrt_march_linear.hip): all the points of the ws.n_overflow pixels listed in ws.overflow — a second lean
+// march, in scenes with objects the general tracer — and the terrain points of the list completed from their records
+void launch_rect_second_pass(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
+                             hipStream_t stream);
+void launch_rect_finalize_list(const Frame& f, Workspace& ws, uint64_t n_hits, const PackedHits& packed, hipStream_t stream);
 
 void launch_draw_image(size_t n_pixels, const atmrt_coloring_t& col, double terrain_alpha, bool packed_valid,
                        const uint32_t* hit_count, const uint64_t* hit_offset, const PackedHits& hits, const DensePlanes& dense,
@@ -474,8 +485,6 @@ void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_
 
 void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream);
-void launch_rect_trace_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
-                            hipStream_t stream);
 void launch_dense_from_packed(const Frame& f, Workspace& ws, const PackedHits& packed, const DensePlanes& dense, int fast_angles,
                               hipStream_t stream);
 

@@ -97,8 +97,8 @@ __global__ __launch_bounds__(256) void k_fast_intersect(Frame f, const double* _
                                                         unsigned long long* __restrict__ counters, double* __restrict__ dprev_state,
                                                         int i_begin, int i_end, int last_segment, uint32_t* __restrict__ slot_step,
                                                         uint32_t* __restrict__ slot_tag, const uint8_t* __restrict__ traced) {
-  // slot_tag != nullptr (scenes with objects, one launch over all samples): the slots are the general tracer's arena — entry
-  // p * RECT_SLOTS + j, tag ATMRT_COLOR_TERRAIN — and the pixels marked in `traced` are k_fast_trace's: their ray-steps are not
+  // slot_tag != nullptr (scenes with objects, one launch over all samples): the slots are the general tracer's arena — pixel-major (slot_index),
+  // tag ATMRT_COLOR_TERRAIN — and the pixels marked in `traced` are k_fast_trace's: their ray-steps are not
   // counted here (whatever this scan stores for them is overwritten).
   // Samples i_begin .. i_end - 1 (the frame is scanned in the segments in which its ray paths are integrated, so that the scan
   // of one segment overlaps the integration of the next); between segments a pixel's state is the difference at its last
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_fast_intersect(Frame f, const double* _
         unsigned c = cnt0;
         const size_t pp = (size_t)(y0 + r) * wl + x;
         for (unsigned hb = hitbits; hb && c < (unsigned)RECT_SLOTS; hb &= hb - 1, c++) {
-          const size_t q = slot_tag ? pp * RECT_SLOTS + c : (size_t)c * plane_px + pp;
+          const size_t q = slot_tag ? slot_index<SlotLayout::PixelMajor>(pp, c, plane_px) : slot_index<SlotLayout::SlotMajor>(pp, c, plane_px);
           slot_step[q] = (uint32_t)(i + __builtin_ctz(hb) - 1);
           if (slot_tag) slot_tag[q] = ATMRT_COLOR_TERRAIN;
         }
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void k_fast_intersect(Frame f, const double* _
           if (MODE != 0 && hit) {
             if (cnt[r] < (unsigned)RECT_SLOTS && xok && y0 + r < f.h) {
               const size_t pp = (size_t)(y0 + r) * wl + x;
-              const size_t q = slot_tag ? pp * RECT_SLOTS + cnt[r] : (size_t)cnt[r] * plane_px + pp;
+              const size_t q = slot_tag ? slot_index<SlotLayout::PixelMajor>(pp, cnt[r], plane_px) : slot_index<SlotLayout::SlotMajor>(pp, cnt[r], plane_px);
               slot_step[q] = (uint32_t)(i - 1);
               if (slot_tag) slot_tag[q] = ATMRT_COLOR_TERRAIN;
             }
@@ -246,8 +246,9 @@ __global__ __launch_bounds__(256) void k_fast_intersect(Frame f, const double* _
         hit_count[p] = first[r] >= 0 ? 1u : 0u;
         st = first[r] >= 0 ? (unsigned)(first[r] + 1) : (unsigned)(nrow[r] > 0 ? nrow[r] - 1 : 0);
         if (slot_tag && first[r] >= 0) { // opaque terrain in a scene with objects: the first crossing is the pixel's only slot
-          slot_step[p * RECT_SLOTS] = (uint32_t)first[r];
-          slot_tag[p * RECT_SLOTS] = ATMRT_COLOR_TERRAIN;
+          const size_t q = slot_index<SlotLayout::PixelMajor>(p, 0, plane_px);
+          slot_step[q] = (uint32_t)first[r];
+          slot_tag[q] = ATMRT_COLOR_TERRAIN;
         }
       } else {
         hit_count[p] = cnt[r];
@@ -300,23 +301,7 @@ __global__ __launch_bounds__(256) void k_fast_finalize(Frame f, const DirCalc* _
 }
 
 // terrain_alpha < 1: the list of every sign change of every pixel (step index + pixel).  The counting scan kept the first
-// RECT_SLOTS crossings of each pixel; k_fast_gather_steps moves those, and only pixels with more are scanned a second time.
-__global__ __launch_bounds__(256) void k_fast_gather_steps(Frame f, const uint32_t* __restrict__ hit_count,
-                                                           const uint64_t* __restrict__ hit_offset,
-                                                           const uint32_t* __restrict__ slot_step, uint32_t* __restrict__ list_step,
-                                                           uint32_t* __restrict__ list_pixel) {
-  const size_t plane = (size_t)f.wl * f.h;
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= plane) return;
-  const uint32_t n = hit_count[p];
-  if (n > (uint32_t)RECT_SLOTS) return;
-  const uint64_t k = hit_offset[p];
-  for (uint32_t j = 0; j < n; j++) {
-    list_step[k + j] = slot_step[(size_t)j * plane + p];
-    list_pixel[k + j] = (uint32_t)p;
-  }
-}
-
+// RECT_SLOTS crossings of each pixel; k_gather_slots moves those, and only pixels with more are scanned a second time.
 __global__ __launch_bounds__(256) void k_fast_list(Frame f, const double* __restrict__ prof,
                                                    const double* __restrict__ pelev,
                                                    const int32_t* __restrict__ npath,
@@ -330,7 +315,7 @@ __global__ __launch_bounds__(256) void k_fast_list(Frame f, const double* __rest
   int n = npath[y];
   n = n < f.n_t ? n : f.n_t;
   size_t p = (size_t)y * f.wl + x;
-  if (hit_count[p] <= (uint32_t)RECT_SLOTS) return; // listed from the slots of the counting scan (k_fast_gather_steps)
+  if (hit_count[p] <= (uint32_t)RECT_SLOTS) return; // listed from the slots of the counting scan (k_gather_slots)
   uint64_t k = hit_offset[p];
   const double* row = pelev + (size_t)y * f.n_path_cap;
   double dprev = row[0] - prof[x];
@@ -516,9 +501,9 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
   // traced (counting pass): only the rows marked by k_fast_flag_rows are traced here — the others cannot meet an object and keep
   // what the plain intersect scan found; a wavefront without a marked row leaves at once.
   // FILL = false: count the trace points of every pixel and keep those of pixels with <= RECT_SLOTS of them in the slot arena
-  // (packed / list_step / list_pixel then are that arena, entry p * RECT_SLOTS + j).  FILL = true: write every point at its
+  // (packed / list_step / list_pixel then are that arena, pixel-major: slot_index).  FILL = true: write every point at its
   // place in the pixel-ordered list — for the pixels that did not fit their slots (hit_count > RECT_SLOTS); the others were
-  // moved by k_fast_gather_trace_slots and their lanes are idle here (most wavefronts leave at once).
+  // moved by k_gather_slots and their lanes are idle here (most wavefronts leave at once).
   // caches written by earlier kernels, read-only here: through the constant address space a wave-uniform index is a scalar load
   typedef const __attribute__((address_space(4))) double* ConstF64;
   typedef const __attribute__((address_space(4))) uint32_t* ConstU32;
@@ -574,7 +559,7 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
           const double diff1 = re0 - te0, diff2 = re[q] - te[q];
           if (active && diff1 * diff2 < 0.0) {
             if (FILL || count < (unsigned)RECT_SLOTS) {
-              const uint64_t kw = FILL ? k : (uint64_t)p * RECT_SLOTS + count;
+              const uint64_t kw = FILL ? k : slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
               list_step[kw] = (uint32_t)(i + q - 1);
               list_pixel[kw] = (uint32_t)p;
               packed.color_tag[kw] = ATMRT_COLOR_TERRAIN;
@@ -603,7 +588,7 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
     if ((c0 | c1) == 0) { // wave-uniform: no close objects at either sample — terrain only (utils.rs:222-240)
       if (hit) {
         if (FILL || count < (unsigned)RECT_SLOTS) {
-          const uint64_t kw = FILL ? k : (uint64_t)p * RECT_SLOTS + count;
+          const uint64_t kw = FILL ? k : slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
           list_step[kw] = (uint32_t)(i - 1);
           list_pixel[kw] = (uint32_t)p;
           packed.color_tag[kw] = ATMRT_COLOR_TERRAIN;
@@ -651,7 +636,7 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
         for_each_object([&](int idx) { step_object(sh, f, idx, pos1, pos2); });
         const double d0 = i == 1 ? 0.0 : f.xs[i - 1], pl0 = i == 1 ? 0.0 : plen_t[(size_t)(i - 1) * hh + y];
         if (!FILL) {
-          k = (uint64_t)p * RECT_SLOTS + count;
+          k = slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
           if (sh.n > STEP_CANDIDATES) atomicAdd(&counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
         }
         if (FILL && sh.n > STEP_CANDIDATES) { // big step: produce the points again, straight into the list, and sort them there
@@ -689,35 +674,77 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
   }
 }
 
-// Trace points kept in the slot arena by the counting pass of k_fast_trace, moved to their places in the pixel-ordered list
-// (object points are complete; terrain points are completed by k_fast_finalize_list from list_step / list_pixel).
-__global__ __launch_bounds__(256) void k_fast_gather_trace_slots(Frame f, const uint32_t* __restrict__ hit_count,
-                                                                 const uint64_t* __restrict__ hit_offset,
-                                                                 const uint32_t* __restrict__ slot_step, PackedHits sp,
-                                                                 uint32_t* __restrict__ list_step, uint32_t* __restrict__ list_pixel,
-                                                                 PackedHits packed) {
-  const size_t plane = (size_t)f.wl * f.h;
+// ---------------------------------------------------------------------------------------------
+// From the counting pass to the pixel-ordered list (frames that can have several trace points per pixel; launch_list_fill).
+// The counting pass of every route kept the first RECT_SLOTS trace points of each pixel in the slot arena (slot_index), and a
+// Rectilinear one appended the points beyond them to the overflow arena (OverflowArena); the scan of hit_count then gave every
+// pixel its place in the list, hit_offset[p].  k_gather_slots moves the slots there, k_scatter_overflow the arena's records.  What
+// travels is fixed at compile time: the step and the pixel always; REC: the Rectilinear record (RectRec) k_rect_finalize_list
+// needs; POINTS (scenes with objects): the tag, and for object points the complete trace point — terrain points get only their tag
+// here, the *_finalize_list kernels complete them.
+// ---------------------------------------------------------------------------------------------
+// what the gather does with a pixel that has more trace points than slots
+enum class Beyond {
+  Skip,  // Fast: the second pass (k_fast_list, k_fast_trace<true>) finds such pixels by hit_count itself and lists all their points
+  List,  // Rectilinear without a usable arena: the same, but the second pass visits a list of them — appended here, in any order
+         // (CTR_OVERFLOW_CURSOR was reset by the host and hands out the positions)
+  Clamp, // Rectilinear with the arena: the points beyond the slots come out of it, so the slots of every pixel count.  In a scene
+         // with objects a pixel's last slots may be stale (a step whose points did not all fit went to the arena whole):
+         // k_scatter_overflow overwrites them, so it runs after this kernel on the same stream.
+};
+// one thread per pixel
+template <SlotLayout LAYOUT, bool REC, bool POINTS, Beyond BEYOND>
+__global__ __launch_bounds__(256) void k_gather_slots(size_t plane, const uint32_t* __restrict__ hit_count,
+                                                      const uint64_t* __restrict__ hit_offset,
+                                                      const uint32_t* __restrict__ slot_step, RectRec slot_rec, PackedHits slot_packed,
+                                                      uint32_t* __restrict__ list_step, uint32_t* __restrict__ list_pixel, RectRec rec,
+                                                      PackedHits packed, uint32_t* __restrict__ overflow,
+                                                      unsigned long long* __restrict__ counters) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= plane) return;
-  const uint32_t n = hit_count[p];
-  if (n > (uint32_t)RECT_SLOTS) return; // written by the fill pass
+  uint32_t n = p < plane ? hit_count[p] : 0u;
+  if (BEYOND == Beyond::Clamp) n = n < (uint32_t)RECT_SLOTS ? n : (uint32_t)RECT_SLOTS;
+  // every lane of the wavefront takes part, those past the plane included
+  if (BEYOND == Beyond::List) wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[CTR_OVERFLOW_CURSOR]);
+  if (p >= plane || n > (uint32_t)RECT_SLOTS) return;
   const uint64_t k0 = hit_offset[p];
   for (uint32_t j = 0; j < n; j++) {
-    const size_t q = p * RECT_SLOTS + j;
+    const size_t q = slot_index<LAYOUT>(p, j, plane);
     const uint64_t k = k0 + j;
     list_step[k] = slot_step[q];
     list_pixel[k] = (uint32_t)p;
-    const uint32_t tag = sp.color_tag[q];
-    packed.color_tag[k] = tag;
-    if (tag != ATMRT_COLOR_TERRAIN) {
-      packed.lat[k] = sp.lat[q];
-      packed.lon[k] = sp.lon[q];
-      packed.distance[k] = sp.distance[q];
-      packed.elevation[k] = sp.elevation[q];
-      packed.path_length[k] = sp.path_length[q];
-      for (int c = 0; c < 3; c++) packed.normal[3 * k + c] = sp.normal[3 * q + c];
-      for (int c = 0; c < 4; c++) packed.rgba[4 * k + c] = sp.rgba[4 * q + c];
+    if (REC) rec_copy(rec, k, slot_rec, q);
+    if (POINTS) {
+      const uint32_t tag = slot_packed.color_tag[q];
+      packed.color_tag[k] = tag;
+      if (tag != ATMRT_COLOR_TERRAIN) packed_copy(packed, k, slot_packed, q);
     }
+  }
+}
+
+// one thread per record of the overflow arena: trace point number `ordinal` of pixel p is entry hit_offset[p] + ordinal of the list.
+// POINTS: a record of the lean march (OVERFLOW_LEAN) is void if the march handed the ray to the general tracer afterwards
+// (handed_over = MarchSinks::hit_step) — the tracer appended that ray's points itself.
+template <bool POINTS>
+__global__ __launch_bounds__(256) void k_scatter_overflow(uint32_t n_records, OverflowArena ovf, PackedHits ovf_packed,
+                                                          const int32_t* __restrict__ handed_over,
+                                                          const uint64_t* __restrict__ hit_offset, uint32_t* __restrict__ list_step,
+                                                          uint32_t* __restrict__ list_pixel, RectRec rec, PackedHits packed) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_records) return;
+  const uint32_t p = ovf.pixel[r];
+  uint32_t ordinal = ovf.ordinal[r];
+  if (POINTS && (ordinal & OVERFLOW_LEAN)) {
+    if (handed_over[p]) return;
+    ordinal &= ~OVERFLOW_LEAN;
+  }
+  const uint64_t k = hit_offset[p] + ordinal;
+  list_step[k] = ovf.step[r];
+  list_pixel[k] = p;
+  rec_copy(rec, k, ovf, r);
+  if (POINTS) {
+    const uint32_t tag = ovf_packed.color_tag[r];
+    packed.color_tag[k] = tag;
+    if (tag != ATMRT_COLOR_TERRAIN) packed_copy(packed, k, ovf_packed, r);
   }
 }
 
@@ -1622,19 +1649,6 @@ void launch_pack_first_hits(const Frame& f, Workspace& ws, const DensePlanes& de
   hipLaunchKernelGGL(k_pack_first_hits, dim3(cdiv(n, 256)), dim3(256), 0, stream, f, ws.hit_offset, dense, packed);
 }
 
-void launch_multi_fill_fast(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense,
-                            const PackedHits& packed, hipStream_t stream) {
-  hipLaunchKernelGGL(k_fast_gather_steps, dim3(cdiv((size_t)f.wl * f.h, 256)), dim3(256), 0, stream, f, (const uint32_t*)dense.hit_count,
-                     ws.hit_offset, ws.slot_step, ws.list_step, ws.list_pixel);
-  hipLaunchKernelGGL(k_fast_list, dim3(cdiv(f.wl, 256), f.h), dim3(256), 0, stream, f, ws.prof, ws.pelev, ws.npath,
-                     ws.hit_offset, (const uint32_t*)dense.hit_count, ws.list_step, ws.list_pixel);
-  if (n_hits)
-    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_fast_finalize_list<CALC>), dim3(cdiv(n_hits, 256)), dim3(256), 0,
-                                                          stream, f, n_hits, ws.colcalc, ws.prof, ws.pelev, ws.plen,
-                                                          ws.list_step, ws.list_pixel, packed));
-  launch_dense_from_packed(f, ws, packed, dense, 1, stream);
-}
-
 void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream) {
   if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
     launch_rect_trace_count(f, ws, out, stream);
@@ -1665,24 +1679,65 @@ void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, h
                      (const uint8_t*)ws.traced);
 }
 
-void launch_trace_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
-                       hipStream_t stream) {
-  if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
-    launch_rect_trace_fill(f, ws, n_hits, dense, packed, stream);
-    return;
+template <SlotLayout LAYOUT, bool REC, bool POINTS, Beyond BEYOND>
+static void launch_gather_slots(size_t n, const uint32_t* hit_count, const Workspace& ws, const RectRec& slot_rec, const RectRec& rec,
+                                const PackedHits& packed, hipStream_t stream) {
+  hipLaunchKernelGGL((k_gather_slots<LAYOUT, REC, POINTS, BEYOND>), dim3(cdiv(n, 256)), dim3(256), 0, stream, n, hit_count, ws.hit_offset,
+                     ws.slot_step, slot_rec, ws.slot_packed, ws.list_step, ws.list_pixel, rec, packed, ws.overflow,
+                     (unsigned long long*)ws.counters);
+}
+
+// A frame that can have several trace points per pixel (translucent terrain, scenes with objects), after the scan of hit_count:
+// what the counting pass recorded goes to the pixel-ordered list (k_gather_slots, k_scatter_overflow), a second pass lists the
+// pixels that recording did not cover, one thread per trace point completes the terrain points, and the dense planes get the
+// first point of every pixel.  The route — generator, objects or not — picks the template arguments and the second pass only.
+void launch_list_fill(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
+                      hipStream_t stream) {
+  constexpr SlotLayout SM = SlotLayout::SlotMajor, PM = SlotLayout::PixelMajor;
+  const bool rect = f.p.generator == ATMRT_GEN_RECTILINEAR, objects = f.n_objects > 0;
+  const size_t n = (size_t)f.wl * f.h;
+  const RectRec rec = rect ? carve_rec(ws.rect_rec, (size_t)n_hits) : RectRec{};
+  const RectRec slot_rec = rect ? carve_rec(ws.slot_rec, n * RECT_SLOTS) : RectRec{};
+  // Rectilinear, the points beyond the slots: out of the overflow arena when all of them fitted it — and, with objects, no step had
+  // more points than the in-register step list (those are sorted in HBM by the fill pass).  Otherwise those pixels are visited a
+  // second time: a launch of one wavefront per SIMD at the speed of its dependency chain (headline at terrain_alpha 0.5: 12.8 ms
+  // for 0.7 % of the pixels, at any frame or tile size; config 5: 22.7 ms for 1.3 %).
+  const bool arena = rect && ws.overflow_arena && ws.overflow_cap && ws.n_overflow_records <= ws.overflow_cap && !(objects && ws.step_prop);
+  const uint32_t* hit_count = dense.hit_count;
+  if (!rect && !objects) launch_gather_slots<SM, false, false, Beyond::Skip>(n, hit_count, ws, slot_rec, rec, packed, stream);
+  else if (!rect) launch_gather_slots<PM, false, true, Beyond::Skip>(n, hit_count, ws, slot_rec, rec, packed, stream);
+  else if (!objects && arena) launch_gather_slots<SM, true, false, Beyond::Clamp>(n, hit_count, ws, slot_rec, rec, packed, stream);
+  else if (!objects) launch_gather_slots<SM, true, false, Beyond::List>(n, hit_count, ws, slot_rec, rec, packed, stream);
+  else if (arena) launch_gather_slots<PM, true, true, Beyond::Clamp>(n, hit_count, ws, slot_rec, rec, packed, stream);
+  else launch_gather_slots<PM, true, true, Beyond::List>(n, hit_count, ws, slot_rec, rec, packed, stream);
+  if (arena) {
+    const uint32_t n_records = (uint32_t)ws.n_overflow_records;
+    const OverflowArena ovf = carve_overflow(ws.overflow_arena, ws.overflow_cap);
+    if (n_records && objects)
+      hipLaunchKernelGGL((k_scatter_overflow<true>), dim3(cdiv((size_t)n_records, 256)), dim3(256), 0, stream, n_records, ovf,
+                         ws.overflow_packed, (const int32_t*)ws.hit_step, ws.hit_offset, ws.list_step, ws.list_pixel, rec, packed);
+    else if (n_records)
+      hipLaunchKernelGGL((k_scatter_overflow<false>), dim3(cdiv((size_t)n_records, 256)), dim3(256), 0, stream, n_records, ovf,
+                         PackedHits{}, (const int32_t*)nullptr, ws.hit_offset, ws.list_step, ws.list_pixel, rec, packed);
+  } else if (rect) {
+    if (ws.n_overflow) launch_rect_second_pass(f, ws, n_hits, dense, packed, stream);
+  } else if (objects) {
+    hipLaunchKernelGGL((k_fast_trace<true>), dim3(cdiv(f.wl, 4), cdiv(f.h, 64)), dim3(256), 0, stream, f, ws.prof, ws.plat, ws.plon,
+                       ws.ccount, ws.coffset, ws.clist, ws.pelev_t, ws.plen_t, ws.npath, dense.hit_count, ws.hit_offset, packed,
+                       ws.list_step, ws.list_pixel, (uint32_t*)nullptr, (unsigned long long*)ws.counters, ws.step_prop,
+                       (const uint8_t*)nullptr);
+  } else {
+    hipLaunchKernelGGL(k_fast_list, dim3(cdiv(f.wl, 256), f.h), dim3(256), 0, stream, f, ws.prof, ws.pelev, ws.npath,
+                       ws.hit_offset, (const uint32_t*)dense.hit_count, ws.list_step, ws.list_pixel);
   }
-  hipLaunchKernelGGL(k_fast_gather_trace_slots, dim3(cdiv((size_t)f.wl * f.h, 256)), dim3(256), 0, stream, f,
-                     (const uint32_t*)dense.hit_count, ws.hit_offset, ws.slot_step, ws.slot_packed, ws.list_step, ws.list_pixel, packed);
-  hipLaunchKernelGGL((k_fast_trace<true>), dim3(cdiv(f.wl, 4), cdiv(f.h, 64)), dim3(256), 0, stream, f, ws.prof, ws.plat, ws.plon,
-                     ws.ccount, ws.coffset, ws.clist, ws.pelev_t, ws.plen_t, ws.npath, dense.hit_count, ws.hit_offset, packed,
-                     ws.list_step, ws.list_pixel, (uint32_t*)nullptr, (unsigned long long*)ws.counters, ws.step_prop,
-                     (const uint8_t*)nullptr);
-  if (n_hits) {
+  if (n_hits && rect) {
+    launch_rect_finalize_list(f, ws, n_hits, packed, stream);
+  } else if (n_hits) {
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_fast_finalize_list<CALC>), dim3(cdiv(n_hits, 256)), dim3(256), 0,
                                                           stream, f, n_hits, ws.colcalc, ws.prof, ws.pelev, ws.plen,
                                                           ws.list_step, ws.list_pixel, packed));
   }
-  launch_dense_from_packed(f, ws, packed, dense, 1, stream);
+  launch_dense_from_packed(f, ws, packed, dense, rect ? 0 : 1, stream);
 }
 
 void launch_dense_from_packed(const Frame& f, Workspace& ws, const PackedHits& packed, const DensePlanes& dense, int fast_angles,

@@ -196,7 +196,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
   const uint32_t p = io->pixel;
   if (hits.n > STEP_CANDIDATES) atomicAdd(&sk->counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
   if (hits.n && count + (unsigned)hits.n <= (unsigned)RECT_SLOTS) {
-    uint64_t k = (uint64_t)p * RECT_SLOTS + count;
+    uint64_t k = slot_index<SlotLayout::PixelMajor>(p, count, (size_t)fg->wl * fg->h);
     const uint64_t k0 = k;
     step_emit(hits, sk->slot_packed, sk->slot_step, sk->slot_pixel, k, p, io->step_index, lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length);
     for (uint64_t q = k0; q < k; q++) rec_store(sk->slots, q, re0, pl0, sh, path_length); // terrain points: what k_rect_finalize_list needs
@@ -234,9 +234,8 @@ static __device__ __forceinline__ int timeline_wave_max(int v) {
 // Where a lean march (k_rect_march, k_rect_march_first / _cont) leaves its results, by MODE
 struct MarchSinks {
   int32_t* hit_step;    // MODE 0: [plane] step of the first crossing, or -1; MODE 3: [plane] 1 = the ray is left to the general tracer
-                        // (which voids the ray's overflow records, k_rect_scatter_trace_overflow)
-  RectRec rec;          // MODE 0: [plane]; MODE 1: slot-major [RECT_SLOTS][plane]; MODE 2: the pixel-ordered list;
-                        // MODE 3: pixel-major [plane][RECT_SLOTS] (the general tracer's slot arena)
+                        // (which voids the ray's overflow records, k_scatter_overflow)
+  RectRec rec;          // MODE 0: [plane]; MODE 1, 3: the slot arena (slot_index); MODE 2: the pixel-ordered list
   uint32_t* step;       // MODE 1 - 3: the step of every entry of rec
   OverflowArena ovf;    // MODE 1, 3: crossings beyond the slots
   uint32_t* slot_tag;   // MODE 3: the slot arena's colour tags (the march writes TERRAIN)
@@ -384,7 +383,7 @@ static __device__ __forceinline__ void crossing_store(const Frame& f, const Marc
     rec_store(sinks.rec, r.k, r.re0, r.pl0, r.sh, r.path_length);
     r.k++;
   } else if (r.count < (unsigned)RECT_SLOTS) {
-    const size_t q = MODE == 3 ? p * RECT_SLOTS + r.count : (size_t)r.count * ((size_t)f.wl * f.h) + p;
+    const size_t q = slot_index<MODE == 3 ? SlotLayout::PixelMajor : SlotLayout::SlotMajor>(p, r.count, (size_t)f.wl * f.h);
     sinks.step[q] = step;
     if (MODE == 3) sinks.slot_tag[q] = ATMRT_COLOR_TERRAIN;
     rec_store(sinks.rec, q, r.re0, r.pl0, r.sh, r.path_length);
@@ -492,7 +491,7 @@ static __device__ __forceinline__ void march_finish(const DensePlanes& out, cons
     sinks.hit_step[p] = r.first;
   } else if (MODE != 2) {
     out.hit_count[p] = r.count;
-    if (MODE == 3) sinks.hit_step[p] = 0; // the ray stayed with the march: its overflow records count (k_rect_scatter_trace_overflow)
+    if (MODE == 3) sinks.hit_step[p] = 0; // the ray stayed with the march: its overflow records count (k_scatter_overflow)
     if (r.count > (unsigned)RECT_SLOTS) atomicAdd(&counters[CTR_OVERFLOW_PIXELS], 1ull);
   }
 }
@@ -914,7 +913,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
                                                     const uint32_t* __restrict__ pixel_list, uint32_t n_list,
                                                     double* __restrict__ step_prop, OverflowArena ovf, PackedHits ovf_packed) {
   // FILL = false: count the trace points of every pixel and keep those of pixels with <= RECT_SLOTS of them in the slot arena
-  // (packed / rec / list_step then are that arena, entry p * RECT_SLOTS + j).  FILL = true: write every point at its place in
+  // (packed / rec / list_step then are that arena, pixel-major: slot_index).  FILL = true: write every point at its place in
   // the pixel-ordered list, for all pixels or for the listed ones (those that did not fit their slots).
   stage_dm_tables();
   const size_t plane = (size_t)f.wl * f.h;
@@ -1039,7 +1038,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
         };
         if (any_object) for_each_object([&](int j) { step_object(hits, f, j, pos1, pos2); });
         if (!FILL) {
-          k = (uint64_t)p * RECT_SLOTS + count;
+          k = slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * f.h);
           if (hits.n > STEP_CANDIDATES) atomicAdd(&counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
         }
         if (FILL && hits.n > STEP_CANDIDATES) { // big step: produce the points again, straight into the list, and sort them there
@@ -1157,82 +1156,19 @@ void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, 
   }
 }
 
-// The crossings the counting march kept in its slots, moved to their places in the pixel-ordered list; pixels with more
-// crossings than slots are collected for a second march (CTR_OVERFLOW_CURSOR was reset by the host and hands out list positions).
-static __global__ __launch_bounds__(256) void k_rect_gather_slots(Frame f, const uint32_t* __restrict__ hit_count,
-                                                           const uint64_t* __restrict__ hit_offset,
-                                                           const uint32_t* __restrict__ slot_step, RectRec slots,
-                                                           uint32_t* __restrict__ list_step, uint32_t* __restrict__ list_pixel,
-                                                           RectRec rec, uint32_t* __restrict__ overflow,
-                                                           unsigned long long* __restrict__ counters, int arena) {
-  const size_t plane = (size_t)f.wl * f.h;
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t n = p < plane ? hit_count[p] : 0u;
-  if (arena) { // the crossings beyond the slots are in the overflow arena (k_rect_scatter_overflow): the slots of every pixel count
-    n = n < (uint32_t)RECT_SLOTS ? n : (uint32_t)RECT_SLOTS;
-  } else {
-    wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[CTR_OVERFLOW_CURSOR]); // the pixels the second march visits
-    if (n > (uint32_t)RECT_SLOTS) return;
-  }
-  if (p >= plane) return;
-  const uint64_t k = hit_offset[p];
-  for (uint32_t j = 0; j < n; j++) {
-    const size_t q = (size_t)j * plane + p;
-    list_step[k + j] = slot_step[q];
-    list_pixel[k + j] = (uint32_t)p;
-    rec_copy(rec, k + j, slots, q);
-  }
-}
-
-// the arena's records to their places in the pixel-ordered list: crossing number `ordinal` of pixel p is entry hit_offset[p] + ordinal
-static __global__ __launch_bounds__(256) void k_rect_scatter_overflow(uint32_t n_records, OverflowArena ovf,
-                                                                      const uint64_t* __restrict__ hit_offset,
-                                                                      uint32_t* __restrict__ list_step, uint32_t* __restrict__ list_pixel,
-                                                                      RectRec rec) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_records) return;
-  const uint32_t p = ovf.pixel[r];
-  const uint64_t k = hit_offset[p] + ovf.ordinal[r];
-  list_step[k] = ovf.step[r];
-  list_pixel[k] = p;
-  rec_copy(rec, k, ovf, r);
-}
-
-// terrain_alpha < 1, Rectilinear: gather the recorded crossings, march the overflow pixels again listing every crossing,
-// then one thread per trace point
+// terrain_alpha < 1, no usable overflow arena (launch_list_fill): the pixels with more crossings than slots, listed in ws.overflow
+// by the gather, marched again — every crossing to its place in the pixel-ordered list
 template <bool CUBIC>
-void launch_multi_fill_t(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
-                         hipStream_t stream) {
-  size_t n = (size_t)f.wl * f.h;
-  RectRec rec = carve_rec(ws.rect_rec, (size_t)n_hits);
-  RectRec slots = carve_rec(ws.slot_rec, n * RECT_SLOTS);
-  // the crossings beyond the slots: out of the overflow arena when all of them fitted it — a second march of those pixels otherwise
-  // (0.7 % of the headline's pixels: a launch of one wavefront per SIMD, 12.8 ms at any frame or tile size, and most of the fill)
-  const bool arena = ws.overflow_arena && ws.overflow_cap && ws.n_overflow_records <= ws.overflow_cap;
-  hipLaunchKernelGGL(k_rect_gather_slots, dim3(cdiv(n, 256)), dim3(256), 0, stream, f, (const uint32_t*)dense.hit_count, ws.hit_offset,
-                     ws.slot_step, slots, ws.list_step, ws.list_pixel, rec, ws.overflow, (unsigned long long*)ws.counters, arena ? 1 : 0);
-  if (arena) {
-    if (ws.n_overflow_records)
-      hipLaunchKernelGGL(k_rect_scatter_overflow, dim3(cdiv((size_t)ws.n_overflow_records, 256)), dim3(256), 0, stream,
-                         (uint32_t)ws.n_overflow_records, carve_overflow(ws.overflow_arena, ws.overflow_cap), ws.hit_offset, ws.list_step,
-                         ws.list_pixel, rec);
-  } else if (ws.n_overflow) {
-    MarchSinks sinks{};
-    sinks.rec = rec;
-    sinks.step = ws.list_step;
-    sinks.list_pixel = ws.list_pixel;
-    sinks.hit_offset = ws.hit_offset;
-    sinks.pixel_list = ws.overflow;
-    sinks.n_list = (uint32_t)ws.n_overflow;
-    ATMRT_LAUNCH_MARCH(2, ws.n_overflow, stream, f, dense, sinks, (unsigned long long*)ws.counters);
-  }
-  if (n_hits) {
-    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_finalize_list<CALC>), dim3(cdiv(n_hits, 256)), dim3(256), 0,
-                                                          stream, f, n_hits, ws.list_step, ws.list_pixel, rec, packed));
-  }
-  launch_dense_from_packed(f, ws, packed, dense, 0, stream);
+void launch_rect_second_march_t(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, hipStream_t stream) {
+  MarchSinks sinks{};
+  sinks.rec = carve_rec(ws.rect_rec, (size_t)n_hits);
+  sinks.step = ws.list_step;
+  sinks.list_pixel = ws.list_pixel;
+  sinks.hit_offset = ws.hit_offset;
+  sinks.pixel_list = ws.overflow;
+  sinks.n_list = (uint32_t)ws.n_overflow;
+  ATMRT_LAUNCH_MARCH(2, ws.n_overflow, stream, f, dense, sinks, (unsigned long long*)ws.counters);
 }
-
 
 // the rays k_rect_march<3> left to the tracer, collected into a list (order irrelevant: every ray is independent); CTR_OBJECT_RAYS counts them
 static __global__ __launch_bounds__(256) void k_collect_object_rays(size_t n, const uint32_t* __restrict__ hit_count,
@@ -1296,120 +1232,26 @@ void launch_rect_trace_objects_t(const Frame& f, Workspace& ws, const DensePlane
                                                         trace_overflow_arena(ws), ws.overflow_packed));
 }
 
-// Trace points kept in the slot arena by the counting pass of k_rect_trace, moved to their places in the pixel-ordered list
-// (object points are complete; terrain points carry the record k_rect_finalize_list needs); overflow pixels are listed.
-static __global__ __launch_bounds__(256) void k_rect_gather_trace_slots(Frame f, const uint32_t* __restrict__ hit_count,
-                                                                        const uint64_t* __restrict__ hit_offset,
-                                                                        const uint32_t* __restrict__ slot_step, RectRec slots,
-                                                                        PackedHits sp, uint32_t* __restrict__ list_step,
-                                                                        uint32_t* __restrict__ list_pixel, RectRec rec,
-                                                                        PackedHits packed, uint32_t* __restrict__ overflow,
-                                                                        unsigned long long* __restrict__ counters, int arena) {
-  const size_t plane = (size_t)f.wl * f.h;
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t n = p < plane ? hit_count[p] : 0u;
-  if (arena) {
-    // the points beyond the slots are in the overflow arena: the slots of every pixel count.  (A pixel's last slots may be stale —
-    // a step whose points did not all fit went to the arena whole — k_rect_scatter_trace_overflow, which runs next, overwrites them.)
-    n = n < (uint32_t)RECT_SLOTS ? n : (uint32_t)RECT_SLOTS;
-  } else {
-    wave_compact_append(n > (uint32_t)RECT_SLOTS, (uint32_t)p, overflow, &counters[CTR_OVERFLOW_CURSOR]); // the pixels the tracer's fill pass visits
-    if (n > (uint32_t)RECT_SLOTS) return;
-  }
-  if (p >= plane) return;
-  const uint64_t k0 = hit_offset[p];
-  for (uint32_t j = 0; j < n; j++) {
-    const size_t q = p * RECT_SLOTS + j;
-    const uint64_t k = k0 + j;
-    list_step[k] = slot_step[q];
-    list_pixel[k] = (uint32_t)p;
-    rec_copy(rec, k, slots, q);
-    const uint32_t tag = sp.color_tag[q];
-    packed.color_tag[k] = tag;
-    if (tag != ATMRT_COLOR_TERRAIN) { // terrain points are completed by k_rect_finalize_list
-      packed.lat[k] = sp.lat[q];
-      packed.lon[k] = sp.lon[q];
-      packed.distance[k] = sp.distance[q];
-      packed.elevation[k] = sp.elevation[q];
-      packed.path_length[k] = sp.path_length[q];
-      for (int c = 0; c < 3; c++) packed.normal[3 * k + c] = sp.normal[3 * q + c];
-      for (int c = 0; c < 4; c++) packed.rgba[4 * k + c] = sp.rgba[4 * q + c];
-    }
-  }
-}
-
-// the arena's records to their places in the pixel-ordered list (scenes with objects)
-static __global__ __launch_bounds__(256) void k_rect_scatter_trace_overflow(uint32_t n_records, OverflowArena ovf, PackedHits ap,
-                                                                            const int32_t* __restrict__ handed_over,
-                                                                            const uint64_t* __restrict__ hit_offset,
-                                                                            uint32_t* __restrict__ list_step, uint32_t* __restrict__ list_pixel,
-                                                                            RectRec rec, PackedHits packed) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_records) return;
-  const uint32_t p = ovf.pixel[r];
-  uint32_t ordinal = ovf.ordinal[r];
-  if (ordinal & OVERFLOW_LEAN) { // a record of the lean march: void if the ray went to the tracer afterwards
-    if (handed_over[p]) return;
-    ordinal &= ~OVERFLOW_LEAN;
-  }
-  const uint64_t k = hit_offset[p] + ordinal;
-  list_step[k] = ovf.step[r];
-  list_pixel[k] = p;
-  rec_copy(rec, k, ovf, r);
-  const uint32_t tag = ap.color_tag[r];
-  packed.color_tag[k] = tag;
-  if (tag != ATMRT_COLOR_TERRAIN) { // terrain points are completed by k_rect_finalize_list
-    packed.lat[k] = ap.lat[r];
-    packed.lon[k] = ap.lon[r];
-    packed.distance[k] = ap.distance[r];
-    packed.elevation[k] = ap.elevation[r];
-    packed.path_length[k] = ap.path_length[r];
-    for (int c = 0; c < 3; c++) packed.normal[3 * k + c] = ap.normal[3 * r + c];
-    for (int c = 0; c < 4; c++) packed.rgba[4 * k + c] = ap.rgba[4 * r + c];
-  }
-}
-
+// the same in a scene with objects: the general tracer's fill pass over those pixels
 template <bool CUBIC>
-void launch_rect_trace_fill_t(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
-                              hipStream_t stream) {
-  size_t n = (size_t)f.wl * f.h;
-  RectRec rec = carve_rec(ws.rect_rec, (size_t)n_hits);
-  RectRec slots = carve_rec(ws.slot_rec, n * RECT_SLOTS);
-  // the points beyond the slots: out of the overflow arena — unless it overflowed itself or a step had more points than the
-  // in-register step list (those are sorted in HBM by the fill pass): then the general tracer visits those pixels a second time
-  // (config 5: 22.7 ms for 1.3 % of the pixels — one wavefront per SIMD, at the speed of its dependency chain)
-  const bool arena = ws.overflow_arena && ws.overflow_cap && ws.n_overflow_records <= ws.overflow_cap && !ws.step_prop;
-  hipLaunchKernelGGL(k_rect_gather_trace_slots, dim3(cdiv(n, 256)), dim3(256), 0, stream, f, (const uint32_t*)dense.hit_count,
-                     ws.hit_offset, ws.slot_step, slots, ws.slot_packed, ws.list_step, ws.list_pixel, rec, packed, ws.overflow,
-                     (unsigned long long*)ws.counters, arena ? 1 : 0);
-  if (arena) {
-    if (ws.n_overflow_records)
-      hipLaunchKernelGGL(k_rect_scatter_trace_overflow, dim3(cdiv((size_t)ws.n_overflow_records, 256)), dim3(256), 0, stream,
-                         (uint32_t)ws.n_overflow_records, trace_overflow_arena(ws), ws.overflow_packed, (const int32_t*)ws.hit_step,
-                         ws.hit_offset, ws.list_step, ws.list_pixel, rec, packed);
-  } else if (ws.n_overflow) {
-    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_trace<true, CALC, CUBIC>), dim3(cdiv((size_t)ws.n_overflow, 256)), dim3(256), 0,
-                                                          stream, f, dense, ws.hit_offset, packed, rec, ws.list_step, ws.list_pixel,
-                                                          (unsigned long long*)ws.counters, (const uint32_t*)ws.overflow,
-                                                          (uint32_t)ws.n_overflow, ws.step_prop, OverflowArena{}, PackedHits{}));
-  }
-  if (n_hits) {
-    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_finalize_list<CALC>), dim3(cdiv(n_hits, 256)), dim3(256), 0,
-                                                          stream, f, n_hits, ws.list_step, ws.list_pixel, rec, packed));
-  }
-  launch_dense_from_packed(f, ws, packed, dense, 0, stream);
+void launch_rect_second_trace_t(const Frame& f, Workspace& ws, uint64_t n_hits, const DensePlanes& dense, const PackedHits& packed,
+                                hipStream_t stream) {
+  ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_trace<true, CALC, CUBIC>), dim3(cdiv((size_t)ws.n_overflow, 256)), dim3(256), 0,
+                                                        stream, f, dense, ws.hit_offset, packed, carve_rec(ws.rect_rec, (size_t)n_hits),
+                                                        ws.list_step, ws.list_pixel, (unsigned long long*)ws.counters,
+                                                        (const uint32_t*)ws.overflow, (uint32_t)ws.n_overflow, ws.step_prop,
+                                                        OverflowArena{}, PackedHits{}));
 }
 
 // explicit instantiation of the launchers for one value of CUBIC, in two groups so that four translation units (march / trace x
 // linear / spline atmospheres) compile in parallel: the lean march (k_rect_march, all modes) and the general tracer (k_rect_trace)
 #define ATMRT_INSTANTIATE_MARCH(CUBIC)                                                                                        \
   template void launch_rect_march_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, hipStream_t, hipEvent_t);            \
-  template void launch_multi_fill_t<CUBIC>(const Frame&, Workspace&, uint64_t, const DensePlanes&, const PackedHits&,         \
-                                           hipStream_t);                                                                      \
+  template void launch_rect_second_march_t<CUBIC>(const Frame&, Workspace&, uint64_t, const DensePlanes&, hipStream_t);       \
   template void launch_rect_trace_count_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, hipStream_t);
 #define ATMRT_INSTANTIATE_TRACE(CUBIC)                                                                                        \
   template void launch_rect_trace_objects_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, uint64_t, hipStream_t);      \
-  template void launch_rect_trace_fill_t<CUBIC>(const Frame&, Workspace&, uint64_t, const DensePlanes&, const PackedHits&,    \
-                                                hipStream_t);
+  template void launch_rect_second_trace_t<CUBIC>(const Frame&, Workspace&, uint64_t, const DensePlanes&, const PackedHits&,  \
+                                                  hipStream_t);
 
 } // namespace atmrt

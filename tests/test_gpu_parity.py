@@ -99,7 +99,7 @@ def test_translucent_terrain_multi_hit(gpu_ctx, oracle_det, generator):
 
 def test_translucent_rectilinear_more_crossings_than_slots(gpu_ctx, oracle_det):
     """Rectilinear, terrain_alpha < 1: the counting march records the first 4 crossings of a pixel in slots and only pixels with
-    more are marched again (k_rect_gather_slots + the pixel-list form of k_rect_march).  A narrow grazing view of the headline
+    more are marched again (k_gather_slots lists them + the pixel-list form of k_rect_march).  A narrow grazing view of the headline
     terrain has both kinds of pixel (up to ~10 crossings), also inside one wavefront."""
     cfg, tiles = synth.scene("headline", 72, 72, generator="Rectilinear", terrain_alpha=0.3, fov=20.0, tilt=-1.0)
     got = run_gpu(gpu_ctx, cfg, tiles)
@@ -109,6 +109,33 @@ def test_translucent_rectilinear_more_crossings_than_slots(gpu_ctx, oracle_det):
     # a frame whose crossings all fit the slots right after one that overflowed (the overflow list must not leak)
     cfg2, tiles2 = synth.scene("S2", 48, 24, generator="Rectilinear", terrain_alpha=0.5, tilt=-4.0)
     assert_bitexact(run_gpu(gpu_ctx, cfg2, tiles2), run_oracle(oracle_det, cfg2, tiles2))
+
+
+def _assert_both_sides_of_the_slots(want, object_points=False):
+    """The oracle's frame has pixels with more than 4 trace points (the second pass) and pixels with 1 to 4 (the slot gather)."""
+    hc = want["hit_count"]
+    assert (hc > 4).any() and ((hc >= 1) & (hc <= 4)).any(), (int((hc > 4).sum()), int(hc.max()))
+    if object_points:  # complete object points inside the pixels the second pass lists
+        tags = np.repeat(hc.ravel() > 4, hc.ravel().astype(np.int64)) & (want["color_tag"] == 1)
+        assert tags.any()
+
+
+def _assert_nothing_leaks_into_a_frame_that_fits_the_slots(gpu_ctx, oracle_det):
+    cfg, tiles = synth.scene("S2", 48, 24, generator="Fast", terrain_alpha=0.5, tilt=-4.0)
+    want = run_oracle(oracle_det, cfg, tiles)
+    assert want["hit_count"].max() <= 4
+    assert_bitexact(run_gpu(gpu_ctx, cfg, tiles), want)
+
+
+def test_translucent_fast_more_crossings_than_slots(gpu_ctx, oracle_det):
+    """Fast, terrain_alpha < 1: the counting scan keeps the first 4 crossings of a pixel in slots (k_gather_slots moves them to
+    the list) and k_fast_list scans only the pixels with more.  The grazing view of the Rectilinear twin above has both kinds of
+    pixel; 72 x 72 pixels leave the gather's last block ragged."""
+    cfg, tiles = synth.scene("headline", 72, 72, generator="Fast", terrain_alpha=0.3, fov=20.0, tilt=-1.0)
+    want = run_oracle(oracle_det, cfg, tiles)
+    _assert_both_sides_of_the_slots(want)
+    assert_bitexact(run_gpu(gpu_ctx, cfg, tiles), want)
+    _assert_nothing_leaks_into_a_frame_that_fits_the_slots(gpu_ctx, oracle_det)
 
 
 def test_three_by_three_tiles_and_shards(gpu_ctx, oracle_det):
@@ -250,9 +277,21 @@ def test_objects_in_a_line_overflow_the_candidate_list(gpu_ctx, oracle_det):
     got = run_gpu(gpu_ctx, cfg, tiles)
     assert (got["color_tag"] == 1).sum() > 20
     # translucent objects behind one another: pixels with more trace points than the 4 slots of the counting pass AND pixels
-    # within them, i.e. both the slot gather and the listed re-trace of k_rect_trace run
+    # within them, i.e. both the slot gather (k_gather_slots) and what covers the rest run: the overflow arena's scatter, or the
+    # listed re-trace of k_rect_trace
     assert (got["hit_count"] > 4).any() and ((got["hit_count"] > 0) & (got["hit_count"] <= 4)).any(), got["hit_count"].max()
     assert_bitexact(got, run_oracle(oracle_det, cfg, tiles))
+
+
+def test_fast_objects_in_a_line_more_points_than_slots(gpu_ctx, oracle_det):
+    """The Fast twin of the scene above: pixels whose points fit the 4 slots of the counting pass (k_gather_slots copies their
+    complete object points to the list) beside pixels with more, object points among them (the fill pass of k_fast_trace)."""
+    cfg, tiles = synth.scene("S2", 48, 24, generator="Fast", terrain_alpha=0.5, max_distance=30_000.0, tilt=-2.0)
+    synth.add_objects(cfg, n_cyl=40, n_bill=0, dist=(500.0, 25_000.0), spread_deg=0.02, radius=(30.0, 60.0), height=(400.0, 900.0))
+    want = run_oracle(oracle_det, cfg, tiles)
+    _assert_both_sides_of_the_slots(want, object_points=True)
+    assert_bitexact(run_gpu(gpu_ctx, cfg, tiles), want)
+    _assert_nothing_leaks_into_a_frame_that_fits_the_slots(gpu_ctx, oracle_det)
 
 
 def test_more_close_objects_than_the_per_lane_list(gpu_ctx, oracle_det):

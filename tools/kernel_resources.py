@@ -30,6 +30,16 @@ def compile_line(unit, obj_out):
     return cmd
 
 
+def without_parameters(name):
+    """a demangled function name without its parameter list (template arguments may hold parentheses: `<(atmrt::SlotLayout)0>`)"""
+    depth = 0
+    for i in range(len(name) - 1, -1, -1):
+        depth += (name[i] == ")") - (name[i] == "(")
+        if depth == 0:
+            return name[:i] if name[i] == "(" else name
+    return name
+
+
 out = ""
 with tempfile.TemporaryDirectory() as tmp:
     for unit in units:
@@ -42,7 +52,7 @@ cur, rows = None, {}
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
     if m:
-        cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
+        cur = without_parameters(subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip())
         rows[cur] = {}
         continue
     m = re.search(r"remark:\s+([A-Za-z][^:]*): (\S+)", line)
