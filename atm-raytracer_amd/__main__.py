@@ -2,6 +2,7 @@
 
     python -m atm_raytracer_amd gen -c CONFIG.yaml [--output OUT.png] [--metadata OUT.npz|OUT.dat]
                                     [--visibility-map OUT.npz [--map-cell ARCSEC] [--map-all]]
+                                    [--landmarks FILE.csv [--landmark-radius ARCSEC] [--landmarks-all] [--landmarks-out OUT.csv]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -15,6 +16,11 @@ writes the per-pixel metadata as a compressed .npz (the reference's bincode+gzip
 frame's bounds snapped outward to multiples of the cell, 3 arcseconds unless --map-cell says otherwise; the first trace point of
 every pixel, or all of them with --map-all — and writes count, min_distance, lat0, lon0, cell_lat, cell_lon, n_points, n_binned,
 n_outside, n_skipped and n_updates to an .npz.
+`--landmarks` (no reference counterpart) reads name,lat,lon rows and finds, on the device, the trace point nearest to each within
+--landmark-radius (3 arcseconds unless said otherwise; lon_scale = cos(lat); the first trace point of every pixel, or all of them
+with --landmarks-all), writes name,lat,lon,found,x,y,point,offset_arcsec,distance_m,elevation_m,n_within to --landmarks-out or to
+stdout, and marks the found ones in the image with a short line and their name.  Not found means no trace point that near: outside
+the field of view and hidden behind terrain look the same.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -88,6 +94,37 @@ def write_visibility_map(ctx, path, cell_arcsec, mode):
                             cell_lon=grid.cell_lon, **{k: np.uint64(v) for k, v in stats.items()})
 
 
+def locate_landmarks(ctx, path, radius_arcsec, mode, out_path):
+    """The landmarks of the CSV file located in the context's last frame; the table to out_path or stdout.  -> (names, records)."""
+    if not (radius_arcsec > 0 and radius_arcsec <= 3600.0):
+        raise config.ConfigError("--landmark-radius must be a positive number of arcseconds, at most 3600")
+    names, lat, lon = generators.read_landmarks_csv(path)
+    if not names:
+        raise config.ConfigError(f"{path} holds no landmark")
+    hits, _ = generators.locate_landmarks(ctx, generators.landmarks(lat, lon), radius_arcsec / 3600.0, mode)
+    if out_path:
+        with open(out_path, "w", newline="") as f:
+            generators.write_landmarks_csv(f, names, lat, lon, hits)
+    else:
+        generators.write_landmarks_csv(sys.stdout, names, lat, lon, hits)
+    return names, hits
+
+
+def draw_landmarks(img, names, hits):
+    """A short vertical marker above every found landmark's pixel and its name, drawn on the host like the tick labels."""
+    from PIL import ImageDraw, ImageFont
+    draw = ImageDraw.Draw(img)
+    path = find_label_font()
+    font = ImageFont.truetype(path, 13) if path else None
+    for name, h in zip(names, hits):
+        if not h["n_within"]:
+            continue
+        x, y = int(h["x"]), int(h["y"])
+        draw.line([(x, y - 14), (x, y - 3)], fill=(255, 255, 255), width=1)
+        if font is not None:
+            draw.text((x + 3, y - 16), name, fill=(255, 255, 255), font=font, anchor="ls")
+
+
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
@@ -110,8 +147,14 @@ def cmd_gen(a):
     if a.visibility_map:  # on the device, while the frame is still in HBM
         stamp("Binning the visibility map...")
         write_visibility_map(ctx, a.visibility_map, a.map_cell, "all" if a.map_all else "first")
+    located = None
+    if a.landmarks:  # likewise
+        stamp("Locating landmarks...")
+        located = locate_landmarks(ctx, a.landmarks, a.landmark_radius, "all" if a.landmarks_all else "first", a.landmarks_out)
     img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
     draw_labels(img, ticks)
+    if located:
+        draw_landmarks(img, *located)
     img.save(a.output)
     meta_path = a.metadata or cfg.output["file_metadata"]  # `if let Some(ref filename) = params.output.file_metadata`, generator/mod.rs:88-94
     if meta_path:
@@ -192,6 +235,10 @@ def main(argv=None):
     g.add_argument("--visibility-map", default=None, metavar="OUT.npz")
     g.add_argument("--map-cell", type=float, default=3.0, metavar="ARCSEC")
     g.add_argument("--map-all", action="store_true")
+    g.add_argument("--landmarks", default=None, metavar="FILE.csv")
+    g.add_argument("--landmark-radius", type=float, default=3.0, metavar="ARCSEC")
+    g.add_argument("--landmarks-all", action="store_true")
+    g.add_argument("--landmarks-out", default=None, metavar="OUT.csv")
     g.set_defaults(fn=cmd_gen)
     p = sub.add_parser("output-atm")
     p.add_argument("config")

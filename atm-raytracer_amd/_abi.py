@@ -158,6 +158,20 @@ class VisibilityStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_binned", "n_outside", "n_skipped", "n_updates")]
 
 
+class Landmark(C.Structure):
+    """atmrt_landmark_t: degrees, and what a degree of longitude is worth against a degree of latitude there (1e-6 .. 1)."""
+    _fields_ = [("lat", C.c_double), ("lon", C.c_double), ("lon_scale", C.c_double)]
+
+
+class LandmarkHit(C.Structure):
+    _fields_ = [("n_within", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("point", C.c_uint32), ("d2", C.c_double),
+                ("distance", C.c_double), ("elevation", C.c_double)]
+
+
+class LandmarkStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_skipped", "n_tested", "n_within")]
+
+
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""
     import numpy as np

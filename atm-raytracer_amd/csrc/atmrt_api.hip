@@ -3,6 +3,7 @@
 // without a HIP device atmrt_ctx_create fails with ATMRT_ERR_NO_DEVICE.
 #include <dirent.h>
 
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -140,6 +141,9 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     // 17 stays 0
     case 18: return sizeof(atmrt_geo_grid_t);
     case 19: return sizeof(atmrt_visibility_stats_t);
+    case 20: return sizeof(atmrt_landmark_t);
+    case 21: return sizeof(atmrt_landmark_hit_t);
+    case 22: return sizeof(atmrt_landmark_stats_t);
     default: return 0;
   }
 }
@@ -1760,6 +1764,239 @@ extern "C" int atmrt_visibility_map_planes_device(atmrt_ctx* c, const atmrt_geo_
   }
   return vis_run(k, c, VisSource{(size_t)width * height, hit_count, nullptr, lat, lon, distance}, grid, count_device, min_distance_device, stats,
                  nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// landmarks: the nearest trace point of each latitude / longitude (kernels: atmrt_landmarks.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int atmrt_landmark_d2(const atmrt_landmark_t* l, double lat, double lon, double* d2) {
+  if (!l || !d2) return ATMRT_ERR_INVALID_ARGUMENT;
+  *d2 = landmark_d2(*l, lat, lon);
+  return ATMRT_OK;
+}
+
+namespace {
+
+constexpr size_t LM_MAX = (size_t)1 << 20;        // landmarks per call
+constexpr uint64_t LM_MAX_ITEMS = 1ull << 24;     // entries of the index: coarser cells above that
+constexpr double LM_WORLD = 1e300;                // the index looks no further than this many degrees (a frame's coordinates are degrees)
+
+// The bucket index of one call: cell c of `grid` lists the landmarks items[cell_start[c] .. cell_start[c + 1]), in ascending order.
+// It is a FILTER for the exact rule landmark_d2(l, lat, lon) <= r2 and may only ever add candidates:
+//  * a landmark's box is +-r in lat and +-r / lon_scale in lon, PADDED by far more than rounding can move a pair (d2 <= r2 bounds
+//    |lat - l.lat| by r (1 + a few 2^-53); the padding is r 1e-6, plus 1e-12 of the magnitudes involved for the rounding of the box's
+//    own corners, plus 1e-150 for a radius whose square underflows, where d2 <= 0 admits differences up to 1.6e-162);
+//  * the cells a box covers are found with the floor rule of geo_grid_cell itself, applied to the box's corners: the rule is
+//    monotone in lat and in lon, so every point inside the box falls into a cell between those of the corners.
+// Landmarks whose box misses `bounds` (the frame's, {lat_min, lat_max, lon_min, lon_max}; NaN: no point at all) are in no cell.
+// The grid covers the intersection of the bounds and the boxes' hull with cells of 2r x 2r / (largest lon_scale) or larger: at most
+// 2000 per axis (2^22 cells in all), about 64 cells per landmark, and doubled until the index holds at most LM_MAX_ITEMS entries.
+struct LandmarkIndex {
+  atmrt_geo_grid_t grid{0.0, 0.0, 1.0, 1.0, 1u, 1u};
+  std::vector<uint32_t> cell_start{0u, 0u}, items;
+};
+
+struct LmBox {
+  double lat_lo, lat_hi, lon_lo, lon_hi;
+};
+LmBox landmark_box(const atmrt_landmark_t& l, double r) {
+  const double w = r / l.lon_scale;
+  const double h_lat = r + (r * 1e-6 + (fabs(l.lat) + r) * 1e-12 + 1e-150), h_lon = w + (w * 1e-6 + (fabs(l.lon) + w) * 1e-12 + 1e-150);
+  return LmBox{l.lat - h_lat, l.lat + h_lat, l.lon - h_lon, l.lon + h_lon};
+}
+// the floor rule of geo_grid_cell on one axis, clamped to the grid's cells
+uint32_t lm_axis_cell(double v, double v0, double cell, uint32_t n) {
+  const double f = dm_floor((v - v0) / cell);
+  if (!(f > 0.0)) return 0u;
+  return f < (double)n ? (uint32_t)f : n - 1u;
+}
+
+LandmarkIndex landmark_index(const atmrt_landmark_t* lm, size_t n, double r, const double bounds[4]) {
+  LandmarkIndex ix;
+  std::vector<uint32_t> alive;
+  std::vector<LmBox> boxes;
+  double hull[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY}, scale_max = 0.0;
+  for (size_t i = 0; i < n; i++) {
+    const LmBox b = landmark_box(lm[i], r);
+    if (!(b.lat_hi >= bounds[0] && b.lat_lo <= bounds[1] && b.lon_hi >= bounds[2] && b.lon_lo <= bounds[3])) continue; // NaN bounds: none
+    alive.push_back((uint32_t)i), boxes.push_back(b);
+    hull[0] = fmin(hull[0], b.lat_lo), hull[1] = fmax(hull[1], b.lat_hi), hull[2] = fmin(hull[2], b.lon_lo), hull[3] = fmax(hull[3], b.lon_hi);
+    scale_max = fmax(scale_max, lm[i].lon_scale);
+  }
+  if (alive.empty()) return ix;
+  const double lat_lo = fmax(fmax(hull[0], bounds[0]), -LM_WORLD), lat_hi = fmin(fmin(hull[1], bounds[1]), LM_WORLD);
+  const double lon_lo = fmax(fmax(hull[2], bounds[2]), -LM_WORLD), lon_hi = fmin(fmin(hull[3], bounds[3]), LM_WORLD);
+  if (!(lat_lo <= lat_hi && lon_lo <= lon_hi)) return ix;
+  const double per_axis = fmin(2000.0, fmax(16.0, ceil(sqrt(64.0 * (double)alive.size()))));
+  double cell_lat = fmax(2.0 * r, (lat_hi - lat_lo) / per_axis), cell_lon = fmax(2.0 * r / scale_max, (lon_hi - lon_lo) / per_axis);
+  std::vector<uint32_t> i0(alive.size()), i1(alive.size()), j0(alive.size()), j1(alive.size());
+  for (;; cell_lat *= 2.0, cell_lon *= 2.0) {
+    atmrt_geo_grid_t& g = ix.grid;
+    g = atmrt_geo_grid_t{lat_lo, lon_lo, cell_lat, cell_lon, 1u, 1u};
+    // the rule's own answer for the far corner decides the cell counts: every point of the region falls into a cell
+    g.n_lat = (uint32_t)fmin(dm_floor((lat_hi - lat_lo) / cell_lat), 4095.0) + 1u;
+    g.n_lon = (uint32_t)fmin(dm_floor((lon_hi - lon_lo) / cell_lon), 4095.0) + 1u;
+    uint64_t total = 0;
+    for (size_t a = 0; a < alive.size(); a++) {
+      const LmBox& b = boxes[a];
+      i0[a] = lm_axis_cell(b.lat_lo, lat_lo, cell_lat, g.n_lat), i1[a] = lm_axis_cell(b.lat_hi, lat_lo, cell_lat, g.n_lat);
+      j0[a] = lm_axis_cell(b.lon_lo, lon_lo, cell_lon, g.n_lon), j1[a] = lm_axis_cell(b.lon_hi, lon_lo, cell_lon, g.n_lon);
+      total += (uint64_t)(i1[a] - i0[a] + 1u) * (j1[a] - j0[a] + 1u);
+    }
+    if (total <= LM_MAX_ITEMS || (g.n_lat == 1u && g.n_lon == 1u)) break;
+  }
+  const atmrt_geo_grid_t& g = ix.grid;
+  const size_t n_cells = (size_t)g.n_lat * g.n_lon;
+  ix.cell_start.assign(n_cells + 1, 0u);
+  for (size_t a = 0; a < alive.size(); a++)
+    for (uint32_t i = i0[a]; i <= i1[a]; i++)
+      for (uint32_t j = j0[a]; j <= j1[a]; j++) ix.cell_start[(size_t)i * g.n_lon + j + 1]++;
+  for (size_t c = 0; c < n_cells; c++) ix.cell_start[c + 1] += ix.cell_start[c];
+  ix.items.resize(ix.cell_start[n_cells]);
+  std::vector<uint32_t> fill(ix.cell_start.begin(), ix.cell_start.end() - 1);
+  for (size_t a = 0; a < alive.size(); a++)
+    for (uint32_t i = i0[a]; i <= i1[a]; i++)
+      for (uint32_t j = j0[a]; j <= j1[a]; j++) ix.items[fill[(size_t)i * g.n_lon + j]++] = alive[a];
+  return ix;
+}
+
+// what every landmark entry point refuses; nullptr when the arguments are fine
+const char* landmark_args_check(const atmrt_landmark_t* lm, size_t n, double radius_deg) {
+  if (!lm) return "landmarks is NULL";
+  if (n == 0 || n > LM_MAX) return "the number of landmarks must lie in [1, 2^20]";
+  if (!(radius_deg > 0.0 && radius_deg <= 1.0)) return "radius_deg must be finite, positive and at most 1 degree";
+  for (size_t i = 0; i < n; i++)
+    if (const char* msg = landmark_check(lm[i])) return msg;
+  return nullptr;
+}
+
+// k: the context whose device holds the frame; report: the context the caller handed in (vis_run).
+int landmarks_run(atmrt_ctx* k, atmrt_ctx* report, const LmSource& src, const atmrt_landmark_t* lm, size_t n, double radius_deg,
+                  atmrt_landmark_hit_t* hits, atmrt_landmark_stats_t* stats) {
+#define LM_TRY(expr)                                                                                         \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess) return report->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+  double bounds[4];
+  if (int rc = vis_run(k, report, VisSource{src.n_pixels, src.hit_count, src.hit_offset, src.lat, src.lon, src.dist}, nullptr, nullptr, nullptr,
+                       nullptr, bounds))
+    return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  const LandmarkIndex host = landmark_index(lm, n, radius_deg, bounds);
+  report->lm_timings[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  LM_TRY(hipSetDevice(k->device));
+  hipStream_t s = k->stream;
+  LmIndex ix{host.grid, nullptr, nullptr, nullptr, radius_deg * radius_deg};
+  LmState st{};
+  atmrt_landmark_hit_t* d_hits = nullptr;
+  uint32_t *d_start = nullptr, *d_items = nullptr;
+  atmrt_landmark_t* d_lm = nullptr;
+  LM_TRY(reserve_carved(k->d_landmarks, [&](Carve& c) {
+    c(d_lm, n * sizeof(atmrt_landmark_t)), c(d_start, host.cell_start.size() * sizeof(uint32_t)), c(d_items, host.items.size() * sizeof(uint32_t));
+    c(st.count, n * sizeof(uint32_t)), c(st.d2min, n * sizeof(unsigned long long)), c(st.key, n * sizeof(unsigned long long));
+    c(st.ctr, LM_N * sizeof(unsigned long long)), c(d_hits, n * sizeof(atmrt_landmark_hit_t));
+  }));
+  ix.cell_start = d_start, ix.items = d_items, ix.lm = d_lm;
+  LM_TRY(hipEventRecord(k->ev[0], s));
+  LM_TRY(hipMemcpyAsync(d_lm, lm, n * sizeof(atmrt_landmark_t), hipMemcpyHostToDevice, s));
+  LM_TRY(hipMemcpyAsync(d_start, host.cell_start.data(), host.cell_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  if (!host.items.empty()) LM_TRY(hipMemcpyAsync(d_items, host.items.data(), host.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  launch_lm_reset(n, st, s);
+  LM_TRY(hipEventRecord(k->ev[1], s));
+  launch_lm_pass(false, src, ix, st, s);
+  LM_TRY(hipEventRecord(k->ev[2], s));
+  launch_lm_pass(true, src, ix, st, s);
+  LM_TRY(hipEventRecord(k->ev[3], s));
+  launch_lm_finish(n, src, st, d_hits, s);
+  LM_TRY(hipEventRecord(k->ev[4], s));
+  unsigned long long block[LM_N] = {};
+  LM_TRY(hipMemcpyAsync(hits, d_hits, n * sizeof(atmrt_landmark_hit_t), hipMemcpyDeviceToHost, s));
+  LM_TRY(hipMemcpyAsync(block, st.ctr, sizeof block, hipMemcpyDeviceToHost, s));
+  LM_TRY(hipStreamSynchronize(s));
+  LM_TRY(hipGetLastError());
+  for (int i = 0; i < 4; i++) {
+    float ms = 0.0f;
+    LM_TRY(hipEventElapsedTime(&ms, k->ev[i], k->ev[i + 1]));
+    report->lm_timings[1 + i] = ms;
+  }
+  if (stats) *stats = atmrt_landmark_stats_t{block[LM_POINTS], block[LM_SKIPPED], block[LM_TESTED], block[LM_WITHIN]};
+  return ATMRT_OK;
+#undef LM_TRY
+}
+
+} // namespace
+
+extern "C" int atmrt_locate_landmarks(atmrt_ctx* c, const atmrt_landmark_t* landmarks, size_t n, double radius_deg, int32_t mode,
+                                      atmrt_landmark_hit_t* hits, atmrt_landmark_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (const char* msg = landmark_args_check(landmarks, n, radius_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  if (!hits) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "hits is NULL");
+  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
+  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context has no frame of its own: atmrt_locate_landmarks works on the gathered planes through atmrt_locate_landmarks_planes_device");
+  if (int rc = vis_check_state(c, "atmrt_locate_landmarks")) return rc;
+  const uint32_t width = (uint32_t)c->last_wl;
+  if (mode == ATMRT_VIS_ALL && c->last_packed)
+    return landmarks_run(c, c, LmSource{c->last_npx, width, c->last_dense.hit_count, c->last_offset, c->last_hits.lat, c->last_hits.lon, c->last_hits.distance, c->last_hits.elevation},
+                         landmarks, n, radius_deg, hits, stats);
+  return landmarks_run(c, c, LmSource{c->last_npx, width, c->last_dense.hit_count, nullptr, c->last_dense.lat, c->last_dense.lon, c->last_dense.distance, c->last_dense.elevation},
+                       landmarks, n, radius_deg, hits, stats);
+}
+
+extern "C" int atmrt_locate_landmarks_planes_device(atmrt_ctx* c, const atmrt_landmark_t* landmarks, size_t n, double radius_deg,
+                                                    const double* lat, const double* lon, const double* distance, const double* elevation,
+                                                    const uint32_t* hit_count, uint32_t width, uint32_t height, atmrt_landmark_hit_t* hits,
+                                                    atmrt_landmark_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (const char* msg = landmark_args_check(landmarks, n, radius_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  if (!hits) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "hits is NULL");
+  if (!lat || !lon || !distance || !elevation || !hit_count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a plane is NULL");
+  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
+  atmrt_ctx* k = c;
+  if (c->multi) { // the device context that owns the planes: its stream, its buffers
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, lat) != hipSuccess) {
+      (void)hipGetLastError();
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "lat is not a device allocation");
+    }
+    k = nullptr;
+    for (int i = 0; i < multi_size(c) && !k; i++)
+      if (multi_child(c, i)->device == attr.device) k = multi_child(c, i);
+    if (!k) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "lat is in the memory of device %d, which is not a device of this context", attr.device);
+  }
+  return landmarks_run(k, c, LmSource{(size_t)width * height, width, hit_count, nullptr, lat, lon, distance, elevation}, landmarks, n, radius_deg, hits,
+                       stats);
+}
+
+extern "C" int atmrt_last_landmark_timings(atmrt_ctx* c, double out[5]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memcpy(out, c->lm_timings, sizeof c->lm_timings);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_landmark_index_probe(const atmrt_landmark_t* landmarks, size_t n, double radius_deg, const double bounds[4],
+                                          const double* lat, const double* lon, size_t n_points, uint64_t* offsets, uint32_t* items,
+                                          size_t capacity, size_t* n_items) {
+  if (!n_items) return ATMRT_ERR_INVALID_ARGUMENT;
+  *n_items = 0;
+  if (landmark_args_check(landmarks, n, radius_deg) || !bounds || !offsets || (n_points && (!lat || !lon))) return ATMRT_ERR_INVALID_ARGUMENT;
+  const LandmarkIndex ix = landmark_index(landmarks, n, radius_deg, bounds);
+  std::vector<int64_t> cell(n_points);
+  size_t need = 0;
+  for (size_t i = 0; i < n_points; i++) {
+    cell[i] = geo_grid_cell(ix.grid, lat[i], lon[i]);
+    if (cell[i] >= 0) need += ix.cell_start[cell[i] + 1] - ix.cell_start[cell[i]];
+  }
+  *n_items = need;
+  if (need > capacity || (need && !items)) return ATMRT_ERR_INVALID_ARGUMENT;
+  size_t at = 0;
+  for (size_t i = 0; i < n_points; i++) {
+    offsets[i] = at;
+    if (cell[i] >= 0)
+      for (uint32_t k = ix.cell_start[cell[i]]; k < ix.cell_start[cell[i] + 1]; k++) items[at++] = ix.items[k];
+  }
+  offsets[n_points] = at;
+  return ATMRT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

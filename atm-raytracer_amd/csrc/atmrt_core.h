@@ -1456,4 +1456,18 @@ ATMRT_HD const char* geo_grid_check(const atmrt_geo_grid_t& g) {
   return nullptr;
 }
 
+// The rule of the landmark search (include/atmrt.h, atmrt_landmark_t): three subtractions / multiplications and a sum of two
+// squares, each an IEEE operation rounded on its own (the units are built with -ffp-contract=off: no FMA); numpy's
+// dlat * dlat + dlon * dlon.  A sum of squares is never negative, so among the values that are not NaN it orders like its bits.
+ATMRT_HD double landmark_d2(const atmrt_landmark_t& l, double lat, double lon) {
+  const double dlat = lat - l.lat, dlon = (lon - l.lon) * l.lon_scale;
+  return dlat * dlat + dlon * dlon;
+}
+// What the entry points refuse (atmrt_landmark_t): nullptr when the landmark is fine.
+ATMRT_HD const char* landmark_check(const atmrt_landmark_t& l) {
+  if (!(l.lat > -__builtin_inf() && l.lat < __builtin_inf() && l.lon > -__builtin_inf() && l.lon < __builtin_inf())) return "lat and lon of a landmark must be finite";
+  if (!(l.lon_scale >= 1e-6 && l.lon_scale <= 1.0)) return "lon_scale of a landmark must lie in [1e-6, 1]";
+  return nullptr;
+}
+
 } // namespace atmrt

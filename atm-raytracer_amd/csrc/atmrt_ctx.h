@@ -179,6 +179,8 @@ struct atmrt_ctx {
   atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last_dense, last_hits, last_offset): draw, overlay, hits
   atmrt::DevBuf d_io, d_overlay;           // staging of the entry points that run between frames
   atmrt::DevBuf d_vis;                     // atmrt_visibility_map* / atmrt_frame_bounds: the call's statistics block (72 B), read while the last frame's buffers are live
+  atmrt::DevBuf d_landmarks;               // atmrt_locate_landmarks*: the call's index, per-landmark state and records, sized by the call's landmarks
+  double lm_timings[5] = {};               // atmrt_last_landmark_timings
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
   atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
   atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend

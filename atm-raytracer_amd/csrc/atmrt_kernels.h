@@ -483,6 +483,35 @@ void launch_vis_map(size_t n_pixels, const atmrt_geo_grid_t& grid, const uint32_
 void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_t* hit_offset, const double* lat, const double* lon,
                        const double* dist, void* block, hipStream_t stream);
 
+// The landmark search (kernels in atmrt_landmarks.h).  LmSource: the trace points, as the visibility map reads them, with the
+// elevations the records quote and the width that turns a flat pixel index into (x, y).  LmIndex: the call's bucket index in
+// device memory — cell c of `grid` lists the landmarks items[cell_start[c] .. cell_start[c + 1]), indices into lm.  LmState: per
+// landmark the count, the smallest d2 (its bits) and the winner's key p << 32 | point index, and the statistics block (LM_N u64).
+struct LmSource {
+  size_t n_pixels;
+  uint32_t width;
+  const uint32_t* hit_count;
+  const uint64_t* hit_offset; // null: the planes
+  const double *lat, *lon, *dist, *elev;
+};
+struct LmIndex {
+  atmrt_geo_grid_t grid;
+  const uint32_t* cell_start; // [n_cells + 1]
+  const uint32_t* items;
+  const atmrt_landmark_t* lm;
+  double r2;
+};
+enum LmSlot : int { LM_POINTS = 0, LM_SKIPPED = 1, LM_TESTED = 2, LM_WITHIN = 3 };
+constexpr int LM_N = 4;
+struct LmState {
+  uint32_t* count;
+  unsigned long long *d2min, *key, *ctr;
+};
+// the call's kernels in order: reset, pass A (pass_b false), pass B, pass C; hits is device memory for n records
+void launch_lm_reset(size_t n, const LmState& state, hipStream_t stream);
+void launch_lm_pass(bool pass_b, const LmSource& src, const LmIndex& index, const LmState& state, hipStream_t stream);
+void launch_lm_finish(size_t n, const LmSource& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream);
+
 void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream);
 void launch_dense_from_packed(const Frame& f, Workspace& ws, const PackedHits& packed, const DensePlanes& dense, int fast_angles,

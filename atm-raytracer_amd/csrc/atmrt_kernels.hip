@@ -18,6 +18,7 @@
 #include "atmrt_overlay.h"
 #include "atmrt_render.h"
 #include "atmrt_vismap.h"
+#include "atmrt_landmarks.h"
 
 namespace atmrt {
 
@@ -1400,6 +1401,29 @@ void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_
     hipLaunchKernelGGL((k_vis_bounds<true>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, hit_count, hit_offset, lat, lon, dist, ctr);
   else
     hipLaunchKernelGGL((k_vis_bounds<false>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, hit_count, hit_offset, lat, lon, dist, ctr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the landmark search (kernels: atmrt_landmarks.h)
+// ---------------------------------------------------------------------------------------------
+void launch_lm_reset(size_t n, const LmState& state, hipStream_t stream) {
+  hipLaunchKernelGGL(k_lm_reset, dim3(cdiv(n > (size_t)LM_N ? n : (size_t)LM_N, 256)), dim3(256), 0, stream, n, state);
+}
+void launch_lm_pass(bool pass_b, const LmSource& src, const LmIndex& index, const LmState& state, hipStream_t stream) {
+  if (!src.n_pixels) return;
+  const dim3 grd(cdiv(src.n_pixels, 256)), blk(256);
+#define LM_LAUNCH(PACKED, PASS_B) hipLaunchKernelGGL((k_lm_pass<PACKED, PASS_B>), grd, blk, 0, stream, src, index, state)
+  if (src.hit_offset) {
+    if (pass_b) LM_LAUNCH(true, true);
+    else LM_LAUNCH(true, false);
+  } else {
+    if (pass_b) LM_LAUNCH(false, true);
+    else LM_LAUNCH(false, false);
+  }
+#undef LM_LAUNCH
+}
+void launch_lm_finish(size_t n, const LmSource& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream) {
+  hipLaunchKernelGGL(k_lm_finish, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, src, state, hits);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -511,6 +511,128 @@ def visibility_map_device(ctx, grid, mode="first", planes=None, device=None):
     return count, mind, _vis_stats(st)
 
 
+# ---- landmarks: the nearest trace point of each latitude / longitude (no reference counterpart) ---------------------------
+LANDMARK_HIT_DTYPE = np.dtype([("n_within", np.uint32), ("x", np.uint32), ("y", np.uint32), ("point", np.uint32), ("d2", np.float64),
+                               ("distance", np.float64), ("elevation", np.float64)])
+assert LANDMARK_HIT_DTYPE.itemsize == C.sizeof(_abi.LandmarkHit)
+
+
+def landmark_scale(lat):
+    """What a degree of longitude is worth against a degree of latitude at `lat`: cos(radians(lat)), the lon_scale the mirrors fill in."""
+    return np.cos(np.radians(lat))
+
+
+def landmarks(lat, lon, lon_scale=None):
+    """The ctypes array of atmrt_landmark_t for equally long sequences lat, lon [deg]; lon_scale defaults to landmark_scale(lat)."""
+    lat, lon = np.atleast_1d(np.asarray(lat, dtype=np.float64)), np.atleast_1d(np.asarray(lon, dtype=np.float64))
+    scale = landmark_scale(lat) if lon_scale is None else np.broadcast_to(np.asarray(lon_scale, dtype=np.float64), lat.shape)
+    if lat.shape != lon.shape or lat.ndim != 1:
+        raise ValueError("lat and lon must be sequences of one length")
+    packed = np.ascontiguousarray(np.stack([lat, lon, scale], axis=1))
+    arr = (_abi.Landmark * lat.size)()
+    C.memmove(arr, packed.ctypes.data, packed.nbytes)
+    return arr
+
+
+def landmark_d2(landmark, lat, lon, lib=None):
+    """atmrt_landmark_d2 (host code, no device) for scalars or arrays of trace-point coordinates."""
+    lib = lib or _lib.load()
+    lat, lon = np.broadcast_arrays(np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64))
+    out = np.empty(lat.shape, dtype=np.float64)
+    d2 = C.c_double()
+    flat = out.reshape(-1)
+    for i, (a, b) in enumerate(zip(lat.ravel().tolist(), lon.ravel().tolist())):
+        rc = lib.atmrt_landmark_d2(C.byref(landmark), a, b, C.byref(d2))
+        if rc != 0:
+            raise AtmrtError(rc, "atmrt_landmark_d2 refused its arguments")
+        flat[i] = d2.value
+    return out if out.ndim else float(out)
+
+
+def locate_landmarks(ctx, landmarks, radius_deg, mode="first", planes=None):
+    """Locates the landmarks (the array landmarks() makes) in the last generate() on `ctx`: per landmark the number of trace points
+    within radius_deg and the nearest of them.  planes = a dict of [H][W] torch tensors lat, lon, distance, elevation, hit_count
+    searches explicit planes (a gathered multi-device frame; "first" only).  "Not found" (n_within == 0) does not say whether the
+    landmark is outside the field of view or hidden behind terrain.  Returns (records, a structured array of LANDMARK_HIT_DTYPE; stats dict)."""
+    n = len(landmarks)
+    hits = np.empty(n, dtype=LANDMARK_HIT_DTYPE)
+    st = _abi.LandmarkStats()
+    if planes is None:
+        ctx.check(ctx.lib.atmrt_locate_landmarks(ctx.handle, landmarks, n, radius_deg, _abi.VIS_MODES[mode], hits.ctypes.data, C.byref(st)))
+    else:
+        if mode != "first":
+            raise ValueError("explicit planes hold the first trace point of every pixel: mode must be 'first'")
+        h, w = planes["lat"].shape
+        ctx.check(ctx.lib.atmrt_locate_landmarks_planes_device(ctx.handle, landmarks, n, radius_deg, planes["lat"].data_ptr(), planes["lon"].data_ptr(),
+                                                               planes["distance"].data_ptr(), planes["elevation"].data_ptr(),
+                                                               planes["hit_count"].data_ptr(), w, h, hits.ctypes.data, C.byref(st)))
+    return hits, {k: getattr(st, k) for k, _ in _abi.LandmarkStats._fields_}
+
+
+def landmark_timings(ctx):
+    """atmrt_last_landmark_timings: milliseconds of the last locate_landmarks on `ctx`."""
+    out = (C.c_double * 5)()
+    ctx.check(ctx.lib.atmrt_last_landmark_timings(ctx.handle, out))
+    return dict(zip(("index_build_ms", "upload_reset_ms", "pass_a_ms", "pass_b_ms", "pass_c_ms"), out))
+
+
+def landmark_index_probe(landmarks, radius_deg, bounds, lat, lon, lib=None):
+    """atmrt_landmark_index_probe (host code, a diagnostic): the candidate landmarks the library's filter yields for every point, for
+    a frame with bounds (lat_min, lat_max, lon_min, lon_max).  Returns (offsets [n_points + 1] uint64, items uint32)."""
+    lib = lib or _lib.load()
+    lat, lon = np.ascontiguousarray(lat, dtype=np.float64), np.ascontiguousarray(lon, dtype=np.float64)
+    b = (C.c_double * 4)(*bounds)
+    offsets = np.zeros(lat.size + 1, dtype=np.uint64)
+    need = C.c_size_t()
+    items = np.empty(max(4 * lat.size, 1), dtype=np.uint32)
+    for _ in range(2):
+        rc = lib.atmrt_landmark_index_probe(landmarks, len(landmarks), radius_deg, b, lat.ctypes.data, lon.ctypes.data, lat.size, offsets.ctypes.data,
+                                            items.ctypes.data, items.size, C.byref(need))
+        if rc == 0:
+            return offsets, items[:need.value].copy()
+        if need.value <= items.size:
+            raise AtmrtError(rc, "atmrt_landmark_index_probe refused its arguments")
+        items = np.empty(need.value, dtype=np.uint32)
+    raise AtmrtError(rc, "atmrt_landmark_index_probe refused its arguments")
+
+
+# ---- the landmark tables of the command line (gen --landmarks FILE.csv) -----------------------------------------------------
+LANDMARK_COLUMNS = ("name", "lat", "lon", "found", "x", "y", "point", "offset_arcsec", "distance_m", "elevation_m", "n_within")
+
+
+def read_landmarks_csv(path):
+    """name,lat,lon rows (a header line is optional: a first row whose lat and lon are no numbers) -> (names, lat, lon)."""
+    import csv
+    names, lat, lon = [], [], []
+    with open(path, newline="") as f:
+        for i, row in enumerate(csv.reader(f)):
+            if not row or not "".join(row).strip():
+                continue
+            if len(row) < 3:
+                raise ValueError(f"{path}: line {i + 1}: expected name,lat,lon")
+            try:
+                a, b = float(row[1]), float(row[2])
+            except ValueError:
+                if not names and i == 0:
+                    continue
+                raise ValueError(f"{path}: line {i + 1}: lat and lon must be numbers")
+            names.append(row[0].strip()), lat.append(a), lon.append(b)
+    return names, np.array(lat, dtype=np.float64), np.array(lon, dtype=np.float64)
+
+
+def write_landmarks_csv(f, names, lat, lon, hits):
+    """The located table, LANDMARK_COLUMNS, to the open text file f; floats in Python's repr.  offset_arcsec = 3600 sqrt(d2)."""
+    import csv
+    w = csv.writer(f, lineterminator="\n")
+    w.writerow(LANDMARK_COLUMNS)
+    for name, a, b, h in zip(names, lat.tolist(), lon.tolist(), hits):
+        if h["n_within"]:
+            w.writerow([name, repr(a), repr(b), 1, int(h["x"]), int(h["y"]), int(h["point"]), repr(float(np.sqrt(h["d2"]) * 3600.0)),
+                        repr(float(h["distance"])), repr(float(h["elevation"])), int(h["n_within"])])
+        else:
+            w.writerow([name, repr(a), repr(b), 0, "", "", "", "", "", "", 0])
+
+
 # ---- integrator / sampler harnesses (ray_path.rs, atm_printer.rs, elev_profile.rs) -------------
 def ray_paths(ctx, h0, angles_deg, step, n_steps, straight=False):
     ang = np.ascontiguousarray(angles_deg, dtype=np.float64)

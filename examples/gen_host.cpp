@@ -56,6 +56,17 @@ int main(int argc, char** argv) {
     fclose(f);
     printf("%zux%zu pixels, %zu with a trace point, %llu ray-steps\n", result[0].size(), result.size(), hits,
            (unsigned long long)generator->last_ray_steps);
+    if (devices.empty() && hits) { // where in the picture is this place?  (a multi-device context searches gathered planes instead)
+      atmrt_landmark_t mark{};
+      for (const auto& row : result)
+        for (const ResultPixel& px : row)
+          if (!px.trace_points.empty()) mark = landmark(px.trace_points[0].lat, px.trace_points[0].lon); // the last pixel that sees ground
+      const LocatedLandmarks found = locate_landmarks(terrain, {mark}, 3.0 / 3600.0);
+      const atmrt_landmark_hit_t& h = found.hits[0];
+      printf("landmark %.6f %.6f: %u trace points within 3 arcseconds, the nearest in pixel (%u, %u) at %.1f m\n", mark.lat, mark.lon, h.n_within,
+             h.x, h.y, h.distance);
+      if (h.n_within == 0 || h.d2 != 0.0) return 4;
+    }
     if (auto e = terrain.get_elev(46.5, 8.5)) printf("elevation under the observer: %.3f m\n", *e);
   } catch (const Error& e) {
     fprintf(stderr, "ERROR: %s\n", e.what()); // main.rs:36-38

@@ -454,6 +454,63 @@ int atmrt_visibility_map_planes_device(atmrt_ctx* ctx, const atmrt_geo_grid_t* g
                                        const double* distance, const uint32_t* hit_count, uint32_t width, uint32_t height,
                                        uint32_t* count_device, double* min_distance_device, atmrt_visibility_stats_t* stats);
 
+/* ---- landmarks: the nearest trace point of each latitude / longitude (no reference counterpart: the reference's `view` window
+ * answers "what does this pixel see" one click at a time, viewer/app.rs:112-176; this inverts it for points — where in the
+ * picture is this peak, and is it there at all).  "Not found" does NOT say why: a landmark outside the field of view and one
+ * hidden behind terrain both have no trace point near them; telling them apart is the refracted inverse problem, out of scope. */
+typedef struct atmrt_landmark {
+  double lat, lon;   /* degrees, finite */
+  double lon_scale;  /* what a degree of longitude is worth against a degree of latitude at this place: the caller's number (the
+                      * host mirrors fill in cos(lat)); finite, 1e-6 <= lon_scale <= 1 */
+} atmrt_landmark_t;
+/* The rule, host code, ctx-free — the same function the kernels run: dlat = lat - L.lat, dlon = (lon - L.lon) * L.lon_scale,
+ * *d2 = dlat * dlat + dlon * dlon, every operation an IEEE operation rounded on its own (no FMA), numpy's expression.  No
+ * trigonometry, no antimeridian handling (as the grid has none).  A trace point is WITHIN a landmark iff d2 <= r2, r2 =
+ * radius_deg * radius_deg computed once on the host; a NaN d2 is never within.  NULL: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_landmark_d2(const atmrt_landmark_t* landmark, double lat, double lon, double* d2);
+/* Per landmark: the winner is the within-point with the smallest d2; ties go to the smallest flat pixel index p = y * width + x,
+ * ties within a pixel to the smallest point index.  Equal landmarks get equal records, and the record does not depend on the
+ * order the wavefronts arrive in (integer atomics only): two calls on one frame return the same bytes. */
+typedef struct atmrt_landmark_hit {
+  uint32_t n_within;          /* trace points within the radius */
+  uint32_t x, y;              /* pixel of the winner in the frame's own coordinates (a column shard counts from its own first
+                               * column, as its planes do); UINT32_MAX, UINT32_MAX when n_within == 0 */
+  uint32_t point;             /* index of the winning trace point inside its pixel (0 in FIRST mode); 0 when none */
+  double d2;                  /* of the winner; +inf when none */
+  double distance, elevation; /* TracePoint.distance / .elevation of the winner, bits as the frame holds them; NaN when none */
+} atmrt_landmark_hit_t;
+/* n_points trace points were read, n_skipped of them skipped exactly as the visibility map skips them (lat, lon or distance NaN,
+ * or distance < 0).  n_tested counts the (point, landmark) pairs on which the rule was evaluated: it depends on the filter (a
+ * bucket index over the landmarks, built per call on the host; it only ever adds candidates), so only n_tested >= n_within is
+ * promised.  n_within is the sum of the landmarks' n_within. */
+typedef struct atmrt_landmark_stats {
+  uint64_t n_points, n_skipped, n_tested, n_within;
+} atmrt_landmark_stats_t;
+/* Locates n landmarks (host array in, host array out; 1 <= n <= 2^20) in the last atmrt_generate / atmrt_generate_device frame on
+ * ctx, mode as in atmrt_visibility_map (ALL reads the packed lists where the frame has them, else it is FIRST).  State rules of
+ * atmrt_visibility_map: ATMRT_ERR_STATE without a frame, after a failed one, and on a multi-device context.  n == 0 or n > 2^20,
+ * a NULL array, radius_deg not finite, <= 0 or > 1, a landmark that breaks the rules of atmrt_landmark_t, an unknown mode:
+ * ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_locate_landmarks(atmrt_ctx* ctx, const atmrt_landmark_t* landmarks, size_t n, double radius_deg, int32_t mode,
+                           atmrt_landmark_hit_t* hits, atmrt_landmark_stats_t* stats /* may be NULL */);
+/* The same over explicit [height][width] device planes (the route of a gathered multi-device frame), FIRST mode: pixel p has the
+ * point (lat[p], lon[p], distance[p], elevation[p]) when hit_count[p] != 0.  All planes must be memory of one device of ctx. */
+int atmrt_locate_landmarks_planes_device(atmrt_ctx* ctx, const atmrt_landmark_t* landmarks, size_t n, double radius_deg,
+                                         const double* lat, const double* lon, const double* distance, const double* elevation,
+                                         const uint32_t* hit_count, uint32_t width, uint32_t height, atmrt_landmark_hit_t* hits,
+                                         atmrt_landmark_stats_t* stats /* may be NULL */);
+/* Where the time of the last atmrt_locate_landmarks* call on ctx went, in milliseconds (tools/measure_landmarks.py): out = {the
+ * host's index build (host clock), upload of the index and reset, pass A (counts and smallest d2), pass B (the winner's key),
+ * pass C (the records)}, the last four between events on the library's stream. */
+int atmrt_last_landmark_timings(atmrt_ctx* ctx, double out[5]);
+/* A diagnostic in the spirit of atmrt_math_probe, host only, ctx-free — not a CPU path for the product: builds the bucket index
+ * exactly as the library would for a frame with bounds = {lat_min, lat_max, lon_min, lon_max} and returns, for n_points points, the
+ * candidate landmarks the filter yields: items[offsets[i] .. offsets[i + 1]) are the indices of point i's candidates.  *n_items is
+ * always set to the number of items needed; a capacity below it: ATMRT_ERR_INVALID_ARGUMENT and nothing else written. */
+int atmrt_landmark_index_probe(const atmrt_landmark_t* landmarks, size_t n, double radius_deg, const double bounds[4],
+                               const double* lat, const double* lon, size_t n_points, uint64_t* offsets /* n_points + 1 */,
+                               uint32_t* items, size_t capacity, size_t* n_items);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —

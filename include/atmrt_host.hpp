@@ -20,6 +20,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -288,6 +289,22 @@ inline VisibilityMap visibility_map(const Terrain& terrain, const atmrt_geo_grid
 inline std::array<double, 4> frame_bounds(const Terrain& terrain, atmrt_visibility_mode mode = ATMRT_VIS_FIRST) {
   std::array<double, 4> out{};
   terrain.check(atmrt_frame_bounds(terrain.ctx(), mode, out.data()));
+  return out;
+}
+
+// Landmarks located in the frame the last generate() on `terrain` produced (no reference counterpart; it inverts the `view` window's
+// click, viewer/app.rs:112-176): per landmark the number of trace points within radius_deg and the nearest of them, n_within == 0
+// when there is none — which does not say whether the landmark is outside the field of view or hidden behind terrain.
+inline atmrt_landmark_t landmark(double lat, double lon) { return atmrt_landmark_t{lat, lon, std::cos(lat * 3.14159265358979323846 / 180.0)}; }
+struct LocatedLandmarks {
+  std::vector<atmrt_landmark_hit_t> hits;
+  atmrt_landmark_stats_t stats;
+};
+inline LocatedLandmarks locate_landmarks(const Terrain& terrain, const std::vector<atmrt_landmark_t>& landmarks, double radius_deg,
+                                         atmrt_visibility_mode mode = ATMRT_VIS_FIRST) {
+  LocatedLandmarks out;
+  out.hits.resize(landmarks.size());
+  terrain.check(atmrt_locate_landmarks(terrain.ctx(), landmarks.data(), landmarks.size(), radius_deg, mode, out.hits.data(), &out.stats));
   return out;
 }
 
