@@ -3,6 +3,7 @@
     python -m atm_raytracer_amd gen -c CONFIG.yaml [--output OUT.png] [--metadata OUT.npz|OUT.dat]
                                     [--visibility-map OUT.npz [--map-cell ARCSEC] [--map-all]]
                                     [--landmarks FILE.csv [--landmark-radius ARCSEC] [--landmarks-all] [--landmarks-out OUT.csv]]
+                                    [--sight-lines FILE.csv [--sight-out OUT.csv] [--sight-fan LO HI] [--sight-rounds N]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -21,6 +22,13 @@ n_outside, n_skipped and n_updates to an .npz.
 with --landmarks-all), writes name,lat,lon,found,x,y,point,offset_arcsec,distance_m,elevation_m,n_within to --landmarks-out or to
 stdout, and marks the found ones in the image with a short line and their name.  Not found means no trace point that near: outside
 the field of view and hidden behind terrain look the same.
+`--sight-lines` (no reference counterpart) tells them apart: it reads name,lat,lon[,height] rows, turns each into an azimuth and a
+distance from the observer under the configured earth model, and solves on the device at which elevation angle the point `height`
+metres above the ground there appears (first fan --sight-fan, -5 5 unless said otherwise, narrowed --sight-rounds times, 3) or how
+many metres of it the terrain hides and where that terrain is.  The table — name, azimuth_deg, distance_m, status (seen, hidden,
+above_fan, below_fan), angle_deg, hidden_m, ground_m, resolution_deg, the blocking point's block_distance_m, block_lat, block_lon,
+block_elevation_m, and the Fast generator's pixel x, y that (azimuth, angle) falls in for the configured frame, empty outside it —
+goes to --sight-out or to stdout.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -110,6 +118,24 @@ def locate_landmarks(ctx, path, radius_arcsec, mode, out_path):
     return names, hits
 
 
+def solve_sight_lines(ctx, cfg, path, fan, rounds, out_path):
+    """The targets of the CSV file solved against the context's parameters, atmosphere and terrain; the table to out_path or stdout."""
+    names, lat, lon, height = generators.read_sight_csv(path)
+    if not names:
+        raise config.ConfigError(f"{path} holds no target")
+    try:
+        targets = generators.sight_targets(ctx, lat, lon, height)
+    except ValueError as exc:
+        raise config.ConfigError(f"{path}: {exc}")
+    sights = generators.sight_lines(ctx, targets, fan, rounds)
+    if out_path:
+        with open(out_path, "w", newline="") as f:
+            generators.write_sight_csv(f, names, targets, sights, cfg.params)
+    else:
+        generators.write_sight_csv(sys.stdout, names, targets, sights, cfg.params)
+    return targets, sights
+
+
 def draw_landmarks(img, names, hits):
     """A short vertical marker above every found landmark's pixel and its name, drawn on the host like the tick labels."""
     from PIL import ImageDraw, ImageFont
@@ -151,6 +177,9 @@ def cmd_gen(a):
     if a.landmarks:  # likewise
         stamp("Locating landmarks...")
         located = locate_landmarks(ctx, a.landmarks, a.landmark_radius, "all" if a.landmarks_all else "first", a.landmarks_out)
+    if a.sight_lines:  # needs no frame: the context's parameters, atmosphere and terrain
+        stamp("Solving sight lines...")
+        solve_sight_lines(ctx, cfg, a.sight_lines, tuple(a.sight_fan), a.sight_rounds, a.sight_out)
     img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
     draw_labels(img, ticks)
     if located:
@@ -239,6 +268,10 @@ def main(argv=None):
     g.add_argument("--landmark-radius", type=float, default=3.0, metavar="ARCSEC")
     g.add_argument("--landmarks-all", action="store_true")
     g.add_argument("--landmarks-out", default=None, metavar="OUT.csv")
+    g.add_argument("--sight-lines", default=None, metavar="FILE.csv")
+    g.add_argument("--sight-out", default=None, metavar="OUT.csv")
+    g.add_argument("--sight-fan", type=float, nargs=2, default=(-5.0, 5.0), metavar=("LO", "HI"))
+    g.add_argument("--sight-rounds", type=int, default=3, metavar="N")
     g.set_defaults(fn=cmd_gen)
     p = sub.add_parser("output-atm")
     p.add_argument("config")

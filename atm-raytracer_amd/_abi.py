@@ -172,6 +172,26 @@ class LandmarkStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_points", "n_skipped", "n_tested", "n_within")]
 
 
+# atmrt_sight_status
+SIGHT_SEEN, SIGHT_HIDDEN, SIGHT_ABOVE_FAN, SIGHT_BELOW_FAN = 0, 1, 2, 3
+SIGHT_STATUS = {SIGHT_SEEN: "seen", SIGHT_HIDDEN: "hidden", SIGHT_ABOVE_FAN: "above_fan", SIGHT_BELOW_FAN: "below_fan"}
+
+
+class SightTarget(C.Structure):
+    """atmrt_sight_target_t: azimuth [deg], surface distance [m] (> 0), metres above the ground at the target (>= 0)."""
+    _fields_ = [("azimuth_deg", C.c_double), ("distance", C.c_double), ("height", C.c_double)]
+
+
+class Sight(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rounds_done", C.c_int32), ("m", C.c_int32), ("block_index", C.c_int32)] + \
+        [(k, C.c_double) for k in ("angle", "arrival", "ground", "hidden", "resolution", "block_distance", "block_lat", "block_lon",
+                                   "block_elevation")]
+
+
+class SightRay(C.Structure):
+    _fields_ = [("block_index", C.c_int32), ("min_index", C.c_int32), ("arrival", C.c_double), ("min_clearance", C.c_double)]
+
+
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""
     import numpy as np

@@ -3,6 +3,7 @@
 // without a HIP device atmrt_ctx_create fails with ATMRT_ERR_NO_DEVICE.
 #include <dirent.h>
 
+#include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -21,6 +22,7 @@
 #include "atmrt_kernels.h"
 #include "atmrt_multi.h"
 #include "atmrt_render.h"
+#include "atmrt_sight.h"
 #include "atmrt_tiff.h"
 
 using namespace atmrt;
@@ -144,6 +146,10 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 20: return sizeof(atmrt_landmark_t);
     case 21: return sizeof(atmrt_landmark_hit_t);
     case 22: return sizeof(atmrt_landmark_stats_t);
+    // 23 stays 0
+    case 24: return sizeof(atmrt_sight_target_t);
+    case 25: return sizeof(atmrt_sight_t);
+    case 26: return sizeof(atmrt_sight_ray_t);
     default: return 0;
   }
 }
@@ -1996,6 +2002,197 @@ extern "C" int atmrt_landmark_index_probe(const atmrt_landmark_t* landmarks, siz
       for (uint32_t k = ix.cell_start[cell[i]]; k < ix.cell_start[cell[i] + 1]; k++) items[at++] = ix.items[k];
   }
   offsets[n_points] = at;
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sight lines (include/atmrt.h; kernels in atmrt_sight.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int atmrt_sight_fan_angles(double lo, double hi, double out[64]) {
+  if (!out) return ATMRT_ERR_INVALID_ARGUMENT;
+  const double delta = sight_fan_delta(lo, hi);
+  for (int k = 0; k < SIGHT_FAN; k++) out[k] = sight_fan_angle(lo, delta, k);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sight_pick(const uint8_t fails[64], int32_t* k_star) {
+  if (!fails || !k_star) return ATMRT_ERR_INVALID_ARGUMENT;
+  unsigned long long mask = 0;
+  for (int k = 0; k < SIGHT_FAN; k++)
+    if (fails[k]) mask |= 1ull << k;
+  *k_star = sight_pick(mask);
+  return ATMRT_OK;
+}
+
+namespace {
+
+// The call's sample lattice on the host: d_i by repeated addition as far as the farthest target, and every target's m.
+struct SightPlan {
+  std::vector<double> dtab;
+  std::vector<SightMeta> meta; // off counts from the start of the target's batch
+  std::vector<size_t> batch_begin; // first target of every batch, and n at the end
+  size_t entries_max = 0;          // profile entries of the largest batch
+};
+
+const char* sight_target_check(const atmrt_sight_target_t& t) {
+  if (!std::isfinite(t.azimuth_deg)) return "a target's azimuth_deg is not finite";
+  if (!(std::isfinite(t.distance) && t.distance > 0.0)) return "a target's distance must be finite and positive";
+  if (!(std::isfinite(t.height) && t.height >= 0.0)) return "a target's height must be finite and not negative";
+  return nullptr;
+}
+
+// everything a batch carves from d_sight; dtab first, so that it stays where the call put it
+template <class Out>
+void sight_carve(Carve& k, size_t n_dtab, size_t nb, size_t n_prof, size_t n_out, atmrt_sight_target_t*& targets, SightMeta*& meta,
+                 SightBatch& b, double*& dtab, Out*& out, double*& angles, size_t n_angles) {
+  k(dtab, n_dtab * sizeof(double)), k(b.alt, sizeof(double));
+  k(targets, nb * sizeof(atmrt_sight_target_t)), k(meta, nb * sizeof(SightMeta)), k(b.calc, nb * sizeof(DirCalc));
+  k(b.T, n_prof * sizeof(double)), k(b.lat, n_prof * sizeof(double)), k(b.lon, n_prof * sizeof(double));
+  k(out, n_out * sizeof(Out)), k(angles, n_angles * sizeof(double));
+}
+
+const char* sight_plan(const atmrt_ctx* c, const atmrt_sight_target_t* targets, size_t n, size_t limit, SightPlan& plan) {
+  const double step = c->params.simulation_step;
+  if (!(step > 0.0)) return "simulation_step must be positive";
+  double far = 0.0;
+  for (size_t t = 0; t < n; t++) {
+    if (const char* msg = sight_target_check(targets[t])) return msg;
+    far = std::max(far, targets[t].distance);
+  }
+  plan.dtab.assign(1, 0.0);
+  for (double d = 0.0; d < far;) { // utils.rs:191-196
+    d += step;
+    plan.dtab.push_back(d);
+    if (plan.dtab.size() > (size_t)SIGHT_M_MAX + 1) return "a target lies more than 65535 samples away";
+  }
+  plan.meta.resize(n);
+  plan.batch_begin.assign(1, 0);
+  size_t bytes = 0, entries = 0;
+  for (size_t t = 0; t < n; t++) { // m: the first index with d_m >= distance (the table ascends: step > 0)
+    const int m = (int)(std::lower_bound(plan.dtab.begin(), plan.dtab.end(), targets[t].distance) - plan.dtab.begin());
+    const size_t add = sight_target_bytes(m);
+    if (bytes && bytes + add > limit) { // a batch holds at least one target
+      plan.batch_begin.push_back(t);
+      bytes = entries = 0;
+    }
+    plan.meta[t] = SightMeta{entries, m, 0};
+    bytes += add, entries += (size_t)m + 1;
+    plan.entries_max = std::max(plan.entries_max, entries);
+  }
+  plan.batch_begin.push_back(n);
+  return nullptr;
+}
+
+size_t sight_scratch_limit() { // read at call time: tests lower it to force several batches
+  const char* e = getenv("ATMRT_SIGHT_SCRATCH_BYTES");
+  const long long v = e ? atoll(e) : 0;
+  return v > 0 && (size_t)v < SIGHT_SCRATCH_BYTES ? (size_t)v : SIGHT_SCRATCH_BYTES;
+}
+
+int sight_check_state(atmrt_ctx* c, const char* what) {
+  if (c->multi) return c->fail(ATMRT_ERR_STATE, "%s solves on one device: a multi-device context has none of its own", what);
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_sight_lines(atmrt_ctx* c, const atmrt_sight_target_t* targets, size_t n, double fan_lo_deg, double fan_hi_deg,
+                                 int32_t rounds, atmrt_sight_t* out) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!targets || !out) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "targets or out is NULL");
+  if (n == 0 || n > SIGHT_N_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "the number of targets must lie in [1, 65536]");
+  if (!(std::isfinite(fan_lo_deg) && std::isfinite(fan_hi_deg) && fan_lo_deg < fan_hi_deg && fan_hi_deg - fan_lo_deg <= 180.0))
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "the fan must be finite, increasing and at most 180 degrees wide");
+  if (rounds < 1 || rounds > 4) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "rounds must lie in [1, 4]");
+  if (int rc = sight_check_state(c, "atmrt_sight_lines")) return rc;
+  SightPlan plan;
+  if (const char* msg = sight_plan(c, targets, n, sight_scratch_limit(), plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  Frame f;
+  if (int rc = prepare_frame(c, &f)) return rc;
+  hipStream_t s = c->stream;
+  const size_t n_dtab = plan.dtab.size(), n_batches = plan.batch_begin.size() - 1;
+  size_t nb_max = 0;
+  for (size_t k = 0; k < n_batches; k++) nb_max = std::max(nb_max, plan.batch_begin[k + 1] - plan.batch_begin[k]);
+  // reserved once for the largest batch (every array at its largest), carved again by every batch: dtab keeps its place
+  atmrt_sight_target_t* d_targets = nullptr;
+  SightMeta* d_meta = nullptr;
+  SightBatch b{};
+  double *d_dtab = nullptr, *d_none = nullptr;
+  atmrt_sight_t* d_out = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { sight_carve(k, n_dtab, nb_max, plan.entries_max, nb_max, d_targets, d_meta, b, d_dtab, d_out, d_none, 0); }));
+  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
+  double ms_sum[3] = {};
+  for (size_t k = 0; k < n_batches; k++) {
+    const size_t t0 = plan.batch_begin[k], nb = plan.batch_begin[k + 1] - t0;
+    const size_t entries = (size_t)plan.meta[t0 + nb - 1].off + plan.meta[t0 + nb - 1].m + 1;
+    int m_max = 0;
+    for (size_t t = t0; t < t0 + nb; t++) m_max = std::max(m_max, plan.meta[t].m);
+    Carve carve(c->d_sight.ptr);
+    sight_carve(carve, n_dtab, nb, entries, nb, d_targets, d_meta, b, d_dtab, d_out, d_none, 0);
+    b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
+    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    HIP_TRY(c, hipMemcpyAsync(d_targets, targets + t0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_meta, plan.meta.data() + t0, nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
+    launch_sight_profile(f, b, m_max, s);
+    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    launch_sight_solve(f, b, fan_lo_deg, fan_hi_deg, rounds, d_out, s);
+    HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    HIP_TRY(c, hipMemcpyAsync(out + t0, d_out, nb * sizeof(atmrt_sight_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipEventRecord(c->ev[3], s));
+    HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes (and reads the host arrays again)
+    HIP_TRY(c, hipGetLastError());
+    for (int i = 0; i < 3; i++) {
+      float ms = 0.0f;
+      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
+      ms_sum[i] += ms;
+    }
+  }
+  memcpy(c->sight_timings, ms_sum, sizeof ms_sum);
+  c->sight_batches = (int32_t)n_batches;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sight_fan_probe(atmrt_ctx* c, const atmrt_sight_target_t* target, size_t n_angles, const double* angles_deg,
+                                     atmrt_sight_ray_t* rays) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!target || !angles_deg || !rays) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "target, angles_deg or rays is NULL");
+  if (n_angles == 0 || n_angles > SIGHT_PROBE_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "the number of angles must lie in [1, 4096]");
+  if (int rc = sight_check_state(c, "atmrt_sight_fan_probe")) return rc;
+  SightPlan plan;
+  if (const char* msg = sight_plan(c, target, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
+  Frame f;
+  if (int rc = prepare_frame(c, &f)) return rc;
+  hipStream_t s = c->stream;
+  const size_t n_dtab = plan.dtab.size(), entries = (size_t)plan.meta[0].m + 1;
+  atmrt_sight_target_t* d_targets = nullptr;
+  SightMeta* d_meta = nullptr;
+  SightBatch b{};
+  double *d_dtab = nullptr, *d_angles = nullptr;
+  atmrt_sight_ray_t* d_rays = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { sight_carve(k, n_dtab, 1, entries, n_angles, d_targets, d_meta, b, d_dtab, d_rays, d_angles, n_angles); }));
+  b.n = 1, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
+  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_targets, target, sizeof *target, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_meta, plan.meta.data(), sizeof(SightMeta), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_angles, angles_deg, n_angles * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_sight_profile(f, b, plan.meta[0].m, s);
+  launch_sight_probe(f, b, n_angles, d_angles, d_rays, s);
+  HIP_TRY(c, hipMemcpyAsync(rays, d_rays, n_angles * sizeof(atmrt_sight_ray_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_sight_timings(atmrt_ctx* c, double out[3]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memcpy(out, c->sight_timings, sizeof c->sight_timings);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_sight_batches(atmrt_ctx* c, int32_t* batches) {
+  if (!c || !batches) return ATMRT_ERR_INVALID_ARGUMENT;
+  *batches = c->sight_batches;
   return ATMRT_OK;
 }
 

@@ -181,6 +181,9 @@ struct atmrt_ctx {
   atmrt::DevBuf d_vis;                     // atmrt_visibility_map* / atmrt_frame_bounds: the call's statistics block (72 B), read while the last frame's buffers are live
   atmrt::DevBuf d_landmarks;               // atmrt_locate_landmarks*: the call's index, per-landmark state and records, sized by the call's landmarks
   double lm_timings[5] = {};               // atmrt_last_landmark_timings
+  atmrt::DevBuf d_sight;                   // atmrt_sight_lines / atmrt_sight_fan_probe: the call's distance table and one batch of targets, profiles and records
+  double sight_timings[3] = {};            // atmrt_last_sight_timings
+  int32_t sight_batches = 0;               // atmrt_last_sight_batches
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
   atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
   atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend

@@ -8,6 +8,12 @@ namespace atmrt {
 
 static __device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
+// Altitude::abs of the observer (params.rs:23-30)
+static __device__ __forceinline__ double observer_altitude(const Frame& f) {
+  const atmrt_position_t& pos = f.p.position;
+  return pos.altitude_kind == ATMRT_ALT_ABSOLUTE ? pos.altitude : terrain_elev_or_zero(f.tv, pos.latitude, pos.longitude) + pos.altitude;
+}
+
 // The geodesic point of the sample after i steps: coords_at_dist(e, c, dist) for dist == f.xs[i], the stepper's x (0 + step + ... +
 // step, the additions of the table; i <= f.march_steps).  Spherical calculator: sin and cos of dist / calc_radius are the table's
 // (Frame::xs_sin), read through the constant address space like the atmosphere record — a scalar load where i is wave-uniform —

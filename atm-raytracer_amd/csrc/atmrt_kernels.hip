@@ -27,12 +27,7 @@ namespace atmrt {
 // ---------------------------------------------------------------------------------------------
 __global__ void k_resolve(Frame f, double* alt, ObjectDev* objects) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) {
-    const atmrt_position_t& pos = f.p.position;
-    *alt = pos.altitude_kind == ATMRT_ALT_ABSOLUTE
-               ? pos.altitude
-               : terrain_elev_or_zero(f.tv, pos.latitude, pos.longitude) + pos.altitude;
-  }
+  if (i == 0) *alt = observer_altitude(f);
   if (i < f.n_objects) { // the host stores the altitude kind in _pad and the configured altitude in elev
     ObjectDev o = objects[i];
     if (o._pad == ATMRT_ALT_RELATIVE) o.elev = terrain_elev_or_zero(f.tv, o.lat, o.lon) + o.elev;

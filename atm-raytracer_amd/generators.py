@@ -231,6 +231,7 @@ class Generator:
         if self.KIND is not None:
             pod.generator = self.KIND
         self.ctx.check(self.ctx.lib.atmrt_set_params(self.ctx.handle, C.byref(pod)))
+        self.ctx.last_params = pod  # what sight_targets reads the observer and the earth model from
         self.ctx.check(self.ctx.lib.atmrt_set_atmosphere(self.ctx.handle, C.byref(self.params.atmosphere)))
         objs = self.params.objects
         arr = (_abi.Object * max(1, len(objs)))(*objs)
@@ -631,6 +632,194 @@ def write_landmarks_csv(f, names, lat, lon, hits):
                         repr(float(h["distance"])), repr(float(h["elevation"])), int(h["n_within"])])
         else:
             w.writerow([name, repr(a), repr(b), 0, "", "", "", "", "", "", 0])
+
+
+# ---- sight lines: where a target appears and what terrain hides it (include/atmrt.h, no reference counterpart) -------------
+SIGHT_DTYPE = np.dtype([("status", np.int32), ("rounds_done", np.int32), ("m", np.int32), ("block_index", np.int32)] +
+                       [(k, np.float64) for k in ("angle", "arrival", "ground", "hidden", "resolution", "block_distance", "block_lat",
+                                                  "block_lon", "block_elevation")])
+SIGHT_RAY_DTYPE = np.dtype([("block_index", np.int32), ("min_index", np.int32), ("arrival", np.float64), ("min_clearance", np.float64)])
+SIGHT_TARGET_DTYPE = np.dtype([("azimuth_deg", np.float64), ("distance", np.float64), ("height", np.float64)])
+assert SIGHT_DTYPE.itemsize == C.sizeof(_abi.Sight) and SIGHT_RAY_DTYPE.itemsize == C.sizeof(_abi.SightRay)
+assert SIGHT_TARGET_DTYPE.itemsize == C.sizeof(_abi.SightTarget)
+
+
+def _sight_target_array(targets):
+    """Targets as a contiguous array of SIGHT_TARGET_DTYPE: such an array, or a sequence of (azimuth_deg, distance, height)."""
+    if isinstance(targets, np.ndarray) and targets.dtype == SIGHT_TARGET_DTYPE:
+        return np.ascontiguousarray(targets.reshape(-1))
+    rows = np.asarray(targets, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(len(rows), dtype=SIGHT_TARGET_DTYPE)
+    out["azimuth_deg"], out["distance"], out["height"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return out
+
+
+def sight_fan_angles(lo, hi, lib=None):
+    """atmrt_sight_fan_angles (host code, no device): the 64 angles of the fan over [lo, hi]."""
+    lib = lib or _lib.load()
+    out = (C.c_double * 64)()
+    rc = lib.atmrt_sight_fan_angles(lo, hi, out)
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sight_fan_angles refused its arguments")
+    return np.array(out, dtype=np.float64)
+
+
+def sight_pick(fails, lib=None):
+    """atmrt_sight_pick (host code, no device): k* of a fan whose ray k fails where fails[k] is true."""
+    lib = lib or _lib.load()
+    f = np.ascontiguousarray(np.asarray(fails).astype(bool), dtype=np.uint8)
+    if f.shape != (64,):
+        raise ValueError("a fan has 64 rays")
+    k = C.c_int32()
+    rc = lib.atmrt_sight_pick(f.ctypes.data, C.byref(k))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sight_pick refused its arguments")
+    return k.value
+
+
+def sight_lines(ctx, targets, fan=(-5.0, 5.0), rounds=3):
+    """Solves the targets (sight_targets() makes them; or rows of (azimuth_deg, distance, height)) against the parameters,
+    atmosphere and terrain now set on `ctx`: at which elevation angle each appears, or which ridge hides it.  No frame is needed.
+    Returns a structured array of SIGHT_DTYPE."""
+    t = _sight_target_array(targets)
+    out = np.empty(len(t), dtype=SIGHT_DTYPE)
+    ctx.check(ctx.lib.atmrt_sight_lines(ctx.handle, t.ctypes.data, len(t), float(fan[0]), float(fan[1]), int(rounds), out.ctypes.data))
+    return out
+
+
+def sight_fan_probe(ctx, target, angles_deg):
+    """atmrt_sight_fan_probe: one ray per elevation angle against one target (azimuth_deg, distance, height), by the device functions
+    of the solve.  Returns a structured array of SIGHT_RAY_DTYPE."""
+    t = _sight_target_array([tuple(target)] if not isinstance(target, np.ndarray) else target)
+    pod = _abi.SightTarget(float(t["azimuth_deg"][0]), float(t["distance"][0]), float(t["height"][0]))
+    ang = np.ascontiguousarray(angles_deg, dtype=np.float64).reshape(-1)
+    rays = np.empty(ang.size, dtype=SIGHT_RAY_DTYPE)
+    ctx.check(ctx.lib.atmrt_sight_fan_probe(ctx.handle, C.byref(pod), ang.size, ang.ctypes.data, rays.ctypes.data))
+    return rays
+
+
+def sight_timings(ctx):
+    """atmrt_last_sight_timings / atmrt_last_sight_batches of the last sight_lines on `ctx`."""
+    out, n = (C.c_double * 3)(), C.c_int32()
+    ctx.check(ctx.lib.atmrt_last_sight_timings(ctx.handle, out))
+    ctx.check(ctx.lib.atmrt_last_sight_batches(ctx.handle, C.byref(n)))
+    return dict(zip(("profile_ms", "solve_ms", "download_ms"), out), batches=n.value)
+
+
+def _inverse_spherical(lat0, lon0, lat, lon, radius):
+    """Azimuth [deg] and great-circle distance [m] from (lat0, lon0) to (lat, lon) on a sphere, closed form."""
+    p0, p1, dl = np.radians(lat0), np.radians(lat), np.radians(lon - lon0)
+    az = np.degrees(np.arctan2(np.sin(dl) * np.cos(p1), np.cos(p0) * np.sin(p1) - np.sin(p0) * np.cos(p1) * np.cos(dl)))
+    a = np.sin((p1 - p0) / 2) ** 2 + np.cos(p0) * np.cos(p1) * np.sin(dl / 2) ** 2
+    return az, 2.0 * radius * np.arcsin(np.sqrt(a))
+
+
+def inverse_geodesic(forward, lat0, lon0, lat, lon, radius=6371000.0, exact=False, tolerance_deg=1e-9, max_corrections=20):
+    """(azimuth_deg, distance) arrays that lead from (lat0, lon0) to the points (lat, lon) under the earth model behind
+    forward(azimuth_deg, distance) -> (lat, lon).  The closed form of the sphere of `radius` is the answer when `exact`; otherwise it
+    seeds a correction: the miss of the forward point in metres north / east, resolved along and across the track where it arrives,
+    changes the distance and the azimuth — until the forward point lies within tolerance_deg of the asked one in latitude and in
+    longitude, for at most max_corrections corrections, else ValueError."""
+    az, dist = _inverse_spherical(lat0, lon0, lat, lon, radius)
+    if exact:
+        return az, dist
+    metres_per_deg = np.pi * radius / 180.0
+    for i in range(lat.size):
+        back = _inverse_spherical(lat[i], lon[i], lat0, lon0, radius)[0]
+        heading = np.radians(back + 180.0)  # of the track where it arrives
+        reach = max(radius * np.sin(dist[i] / radius), 1.0)  # metres across the track per radian of azimuth
+        for k in range(max_corrections + 1):
+            fl, fo = forward(float(az[i]), float(dist[i]))
+            dlat, dlon = lat[i] - fl, lon[i] - fo
+            if abs(dlat) <= tolerance_deg and abs(dlon) <= tolerance_deg:
+                break
+            if k == max_corrections:
+                raise ValueError(f"({lat[i]}, {lon[i]}) not reached within {tolerance_deg} degrees after {max_corrections} corrections")
+            north, east = dlat * metres_per_deg, dlon * metres_per_deg * np.cos(np.radians(lat[i]))
+            dist[i] += north * np.cos(heading) + east * np.sin(heading)
+            az[i] += np.degrees((east * np.cos(heading) - north * np.sin(heading)) / reach)
+    return az, dist
+
+
+def sight_targets(ctx, lat, lon, height=0.0):
+    """The inverse geodesic: targets (SIGHT_TARGET_DTYPE) whose azimuth and distance lead from the observer now set on `ctx` to the
+    points (lat, lon) [deg] under the context's earth model.  Closed form on the Spherical models; on every other model the closed
+    form is corrected through coords_at_dist on the context (inverse_geodesic)."""
+    lat, lon = np.atleast_1d(np.asarray(lat, dtype=np.float64)), np.atleast_1d(np.asarray(lon, dtype=np.float64))
+    if lat.shape != lon.shape or lat.ndim != 1:
+        raise ValueError("lat and lon must be sequences of one length")
+    p = ctx_params(ctx)
+    lat0, lon0 = p.position.latitude, p.position.longitude
+    spherical = p.earth.kind in (_abi.EARTH_KINDS["SimpleSphere"], _abi.EARTH_KINDS["Spherical"])
+    radius = p.earth.radius if p.earth.kind == _abi.EARTH_KINDS["Spherical"] else 6371000.0
+
+    def forward(az, dist):
+        fl, fo = coords_at_dist(ctx, lat0, lon0, az, [dist])
+        return fl[0], fo[0]
+
+    out = np.empty(lat.size, dtype=SIGHT_TARGET_DTYPE)
+    out["azimuth_deg"], out["distance"] = inverse_geodesic(forward, lat0, lon0, lat, lon, radius, exact=spherical)
+    out["height"] = np.broadcast_to(np.asarray(height, dtype=np.float64), lat.shape)
+    return out
+
+
+def ctx_params(ctx):
+    """The parameters last handed to atmrt_set_params through a Generator on `ctx` (Generator._configure records them)."""
+    p = getattr(ctx, "last_params", None)
+    if p is None:
+        raise AtmrtError(_abi.ERR_STATE, "no parameters have been set on this context")
+    return p
+
+
+# ---- the sight-line tables of the command line (gen --sight-lines FILE.csv) --------------------------------------------------
+SIGHT_COLUMNS = ("name", "azimuth_deg", "distance_m", "status", "angle_deg", "hidden_m", "ground_m", "resolution_deg", "block_distance_m",
+                 "block_lat", "block_lon", "block_elevation_m", "x", "y")
+
+
+def read_sight_csv(path):
+    """name,lat,lon[,height] rows (header optional, as read_landmarks_csv reads it) -> (names, lat, lon, height)."""
+    import csv
+    names, lat, lon = read_landmarks_csv(path)
+    height = []
+    with open(path, newline="") as f:
+        rows = [r for r in csv.reader(f) if r and "".join(r).strip()]
+    rows = rows[len(rows) - len(names):]  # the header, if any, is the first row
+    for i, row in enumerate(rows):
+        try:
+            height.append(float(row[3]) if len(row) > 3 and row[3].strip() else 0.0)
+        except ValueError:
+            raise ValueError(f"{path}: target {i + 1}: height must be a number")
+    return names, lat, lon, np.array(height, dtype=np.float64)
+
+
+def fast_pixel_of(params_pod, azimuth_deg, angle_deg):
+    """The Fast generator's pixel (x, y) that a ray of this azimuth and elevation angle falls in for the configured frame: the
+    inverse of get_ray_dir / get_ray_elev (fast.rs:111-125), the pixel whose own direction and angle are nearest; None outside."""
+    w, h = params_pod.width, params_pod.height
+    fov, direction, tilt = params_pod.frame.fov, params_pod.frame.direction, params_pod.frame.tilt
+    if not (np.isfinite(azimuth_deg) and np.isfinite(angle_deg)):
+        return None
+    rel = (azimuth_deg - direction + 180.0) % 360.0 - 180.0
+    # dir(x) = direction + (x - w // 2) * fov / w; elev(y) = tilt - (y - h // 2) * fov / w: the nearest pixel centre
+    x = int(np.floor(rel * w / fov + w // 2 + 0.5))
+    y = int(np.floor(h // 2 - (angle_deg - tilt) * w / fov + 0.5))
+    return (x, y) if 0 <= x < w and 0 <= y < h else None
+
+
+def write_sight_csv(f, names, targets, sights, params_pod):
+    """The solved table, SIGHT_COLUMNS, to the open text file f; floats in Python's repr, fields that do not apply left empty."""
+    import csv
+    w = csv.writer(f, lineterminator="\n")
+    w.writerow(SIGHT_COLUMNS)
+
+    def num(v):
+        return "" if np.isnan(v) else repr(float(v))
+
+    for name, t, s in zip(names, targets, sights):
+        px = fast_pixel_of(params_pod, float(t["azimuth_deg"]), float(s["angle"]))
+        w.writerow([name, repr(float(t["azimuth_deg"])), repr(float(t["distance"])), _abi.SIGHT_STATUS[int(s["status"])], num(s["angle"]),
+                    num(s["hidden"]), num(s["ground"]), num(s["resolution"]), num(s["block_distance"]), num(s["block_lat"]),
+                    num(s["block_lon"]), num(s["block_elevation"]), "" if px is None else px[0], "" if px is None else px[1]])
 
 
 # ---- integrator / sampler harnesses (ray_path.rs, atm_printer.rs, elev_profile.rs) -------------

@@ -67,6 +67,12 @@ int main(int argc, char** argv) {
              h.x, h.y, h.distance);
       if (h.n_within == 0 || h.d2 != 0.0) return 4;
     }
+    if (devices.empty()) { // at which angle does the ground 23.7 km to the east appear, and the top of an 1800 m mast on it?  (no frame needed)
+      const std::vector<atmrt_sight_t> sights = sight_lines(terrain, {{90.0, 23700.0, 0.0}, {90.0, 23700.0, 1800.0}}, -6.0, 6.0, 3);
+      for (const atmrt_sight_t& s : sights)
+        printf("sight status %d rounds %d m %d angle %.17g hidden %.17g ground %.17g resolution %.17g block %d %.17g %.17g\n", s.status, s.rounds_done,
+               s.m, s.angle, s.hidden, s.ground, s.resolution, s.block_index, s.block_distance, s.block_elevation);
+    }
     if (auto e = terrain.get_elev(46.5, 8.5)) printf("elevation under the observer: %.3f m\n", *e);
   } catch (const Error& e) {
     fprintf(stderr, "ERROR: %s\n", e.what()); // main.rs:36-38

@@ -457,7 +457,8 @@ int atmrt_visibility_map_planes_device(atmrt_ctx* ctx, const atmrt_geo_grid_t* g
 /* ---- landmarks: the nearest trace point of each latitude / longitude (no reference counterpart: the reference's `view` window
  * answers "what does this pixel see" one click at a time, viewer/app.rs:112-176; this inverts it for points — where in the
  * picture is this peak, and is it there at all).  "Not found" does NOT say why: a landmark outside the field of view and one
- * hidden behind terrain both have no trace point near them; telling them apart is the refracted inverse problem, out of scope. */
+ * hidden behind terrain both have no trace point near them; telling them apart is the refracted inverse problem, out of scope
+ * HERE: the section "sight lines" below solves it, one target at a time, without a frame. */
 typedef struct atmrt_landmark {
   double lat, lon;   /* degrees, finite */
   double lon_scale;  /* what a degree of longitude is worth against a degree of latitude at this place: the caller's number (the
@@ -510,6 +511,81 @@ int atmrt_last_landmark_timings(atmrt_ctx* ctx, double out[5]);
 int atmrt_landmark_index_probe(const atmrt_landmark_t* landmarks, size_t n, double radius_deg, const double bounds[4],
                                const double* lat, const double* lon, size_t n_points, uint64_t* offsets /* n_points + 1 */,
                                uint32_t* items, size_t capacity, size_t* n_items);
+
+/* ---- sight lines: at which elevation angle a target appears, and what terrain hides it (no reference counterpart: the refracted
+ * inverse problem the landmark search leaves open).  The solve needs the context's parameters, atmosphere and terrain only; it
+ * neither needs nor disturbs a generated frame.
+ *
+ * THE RULE (tests/sight_model.py restates it in numpy).  A target is {azimuth_deg, distance, height}; the setting is what
+ * atmrt_set_params / atmrt_set_atmosphere / the terrain say now: observer position and resolved altitude alt (Altitude::abs,
+ * params.rs:23-30), earth model, simulation_step, straight_rays.
+ *   Sample lattice (the Fast generator's): d_0 = 0, d_i = d_{i-1} + step (repeated addition, utils.rs:191-196); (lat_i, lon_i) =
+ *     coords_at_dist(d_i) from the observer along azimuth_deg; T_i = get_elev(lat_i, lon_i), 0 where the terrain has none; m = the
+ *     first index with d_m >= distance (m > 65535: invalid argument).
+ *   A ray at elevation angle e [deg, converted as atmrt_ray_paths converts]: H_0 = alt, H_i = the stepper's h after i steps of
+ *     `step`; c_i = H_i - T_i.  The ray is BLOCKED AT i for the first 1 <= i <= m - 1 with c_{i-1} * c_i < 0.0 (the strict test of
+ *     utils.rs:222) or with H_{i-1} < -1000 (utils.rs:167), whichever i is smaller.  Otherwise it ARRIVES:
+ *     prop = (distance - d_{m-1}) / (d_m - d_{m-1}), arrival = H_{m-1} + prop * (H_m - H_{m-1}).
+ *   Per target: ground = T_{m-1} + prop * (T_m - T_{m-1}), aim = ground + height.  Every operation of these formulas is an IEEE
+ *     operation rounded on its own (no FMA).
+ *   A FAN over [lo, hi] is 64 angles: delta = (hi - lo) / 63.0, e_k = lo + (double)k * delta (two rounded operations).  Ray k FAILS
+ *     iff it is blocked or arrival < aim; a NaN arrival fails.  k* = one above the highest failing ray: 0 if none fails, 64 if
+ *     ray 63 fails — an answer even where ducting makes rays cross.
+ *   ROUNDS, 1 <= rounds <= 4: if k* is 0 or 64 the solve stops there; otherwise the next fan is [e_{k*-1}, e_{k*}], those very
+ *     doubles.
+ * Equal targets get equal records; two calls return the same bytes (every NaN of a record is the quiet NaN 0x7ff8000000000000). */
+typedef struct atmrt_sight_target {
+  double azimuth_deg; /* finite */
+  double distance;    /* surface distance [m], finite, > 0 */
+  double height;      /* metres above the ground at the target, finite, >= 0 */
+} atmrt_sight_target_t;
+typedef enum atmrt_sight_status {
+  ATMRT_SIGHT_SEEN = 0,      /* the last round's ray k* - 1 arrived, merely low: the aimed point is visible at `angle` to within the last delta */
+  ATMRT_SIGHT_HIDDEN = 1,    /* ray k* - 1 was blocked */
+  ATMRT_SIGHT_ABOVE_FAN = 2, /* k* == 64: every angle of the fan is too low */
+  ATMRT_SIGHT_BELOW_FAN = 3  /* k* == 0: the lowest angle of the fan already passes above the aimed point */
+} atmrt_sight_status;
+typedef struct atmrt_sight {
+  int32_t status;        /* atmrt_sight_status */
+  int32_t rounds_done;   /* rounds actually run */
+  int32_t m;             /* as defined above */
+  int32_t block_index;   /* HIDDEN: the i of ray k* - 1's blocking pair; else -1 */
+  double angle;          /* e_{k*} of the last round [deg]; NaN for ABOVE_FAN */
+  double arrival;        /* of ray k*; NaN for ABOVE_FAN */
+  double ground;         /* as defined above */
+  double hidden;         /* arrival - aim: about 0 for SEEN; for HIDDEN the metres above the aimed point that terrain still covers; NaN for ABOVE_FAN */
+  double resolution;     /* the last round's delta [deg] */
+  double block_distance, block_lat, block_lon, block_elevation; /* HIDDEN: d_i, lat_i, lon_i, T_i of that pair — which ridge; else NaN */
+} atmrt_sight_t;
+/* One ray of atmrt_sight_fan_probe.  The minimum runs over the c_i the ray has (i <= m - 1, and i <= block_index for a blocked
+ * ray), smallest index first: a later c_i replaces it only when it is smaller. */
+typedef struct atmrt_sight_ray {
+  int32_t block_index;   /* -1: arrived */
+  int32_t min_index;
+  double arrival;        /* NaN for a blocked ray */
+  double min_clearance;
+} atmrt_sight_ray_t;
+/* The two host halves of the rule, ctx-free — the same functions the kernel's rule is written from.  fan_angles: out[k] = e_k.
+ * pick: fails[k] != 0 means ray k fails; *k_star as defined above.  NULL: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_sight_fan_angles(double lo, double hi, double out[64]);
+int atmrt_sight_pick(const uint8_t fails[64], int32_t* k_star);
+/* Solves n targets (host arrays in and out, 1 <= n <= 65536) over the first fan [fan_lo_deg, fan_hi_deg].  One wavefront per
+ * target, all rounds inside one kernel; targets are processed in batches so that the call's device scratch (an allocation of the
+ * context's own, grown on demand, freed with the context) stays under 256 MB — ATMRT_SIGHT_SCRATCH_BYTES, read at call time,
+ * lowers that limit (a test hook: the records do not depend on it).  ATMRT_ERR_INVALID_ARGUMENT: a NULL array, n out of range, a
+ * fan that is not finite, not increasing or wider than 180 degrees, rounds outside [1, 4], a target that breaks its rules or lies
+ * more than 65535 samples away.  ATMRT_ERR_STATE: before atmrt_set_params, and on a multi-device context. */
+int atmrt_sight_lines(atmrt_ctx* ctx, const atmrt_sight_target_t* targets, size_t n, double fan_lo_deg, double fan_hi_deg,
+                      int32_t rounds, atmrt_sight_t* out);
+/* A diagnostic in the spirit of atmrt_math_probe: the rays of any list of 1 <= n_angles <= 4096 elevation angles against one
+ * target, by the device functions the solve runs.  Arguments and states refused as above. */
+int atmrt_sight_fan_probe(atmrt_ctx* ctx, const atmrt_sight_target_t* target, size_t n_angles, const double* angles_deg,
+                          atmrt_sight_ray_t* rays);
+/* Where the time of the last atmrt_sight_lines call on ctx went, in milliseconds between events on the library's stream, summed
+ * over its batches: out = {profile pass (upload included), solve, download}. */
+int atmrt_last_sight_timings(atmrt_ctx* ctx, double out[3]);
+/* The number of batches that call took. */
+int atmrt_last_sight_batches(atmrt_ctx* ctx, int32_t* batches);
 
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the

@@ -308,4 +308,14 @@ inline LocatedLandmarks locate_landmarks(const Terrain& terrain, const std::vect
   return out;
 }
 
+// Sight lines (no reference counterpart; include/atmrt.h states the rule): for every target {azimuth_deg, distance, height} the
+// elevation angle at which the point `height` metres above the ground there appears from the observer set on `terrain`'s context, or
+// how much of it terrain hides and where that terrain is.  Needs parameters (a generator's configure or generate) and no frame.
+inline std::vector<atmrt_sight_t> sight_lines(const Terrain& terrain, const std::vector<atmrt_sight_target_t>& targets, double fan_lo_deg = -5.0,
+                                              double fan_hi_deg = 5.0, int32_t rounds = 3) {
+  std::vector<atmrt_sight_t> out(targets.size());
+  terrain.check(atmrt_sight_lines(terrain.ctx(), targets.data(), targets.size(), fan_lo_deg, fan_hi_deg, rounds, out.data()));
+  return out;
+}
+
 } // namespace atmrt_host
