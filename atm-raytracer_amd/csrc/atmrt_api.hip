@@ -1509,27 +1509,48 @@ bool earth_shape_is_flat(int32_t kind) { // EarthModel::to_shape, earth_model/mo
          kind == ATMRT_EARTH_SIMPLE_OBSERVER_AE;
 }
 
+// What the entry points that read the context's own last frame ask first; 0, or a status with the message set.  on_multi: the rest
+// of the sentence a multi-device parent answers with, naming the feature's *_planes_device entry point.
+int frame_state_check(atmrt_ctx* c, const char* what, const char* on_multi) {
+  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context %s", on_multi);
+  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "%s needs a frame: call atmrt_generate first", what);
+  return ATMRT_OK;
+}
+int u16_size_check(atmrt_ctx* c, uint32_t width, uint32_t height) {
+  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
+  return ATMRT_OK;
+}
+// *k: the device context that owns the memory `ptr` points at (its stream, its buffers, its copy of the observer altitude): c
+// itself, or the sub-context of a multi-device c on the pointer's device.  `name` is the pointer's name in the messages.
+int planes_context(atmrt_ctx* c, const void* ptr, const char* name, atmrt_ctx** k) {
+  *k = c;
+  if (!c->multi) return ATMRT_OK;
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s is not a device allocation", name);
+  }
+  for (int i = 0; i < multi_size(c); i++)
+    if (multi_child(c, i)->device == attr.device) return *k = multi_child(c, i), ATMRT_OK;
+  return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s is in the memory of device %d, which is not a device of this context", name, attr.device);
+}
+
 // output_image's annotations (:419-431) over the planes `az`, `el` ([h][w], memory of c's device) of a frame c has generated with
 // the position and atmosphere still set (its observer altitude is in d_alt, its atmosphere table in d_atm).
 int draw_overlay_on(atmrt_ctx* c, atmrt_ctx* report, const atmrt_params_t& p, const atmrt_overlay_t& o, const double* az, const double* el,
                     int w, int h, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
-#define OVERLAY_TRY(expr)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (expr);                                                                                    \
-    if (e_ != hipSuccess) return report->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
   if (flat_horizon_deg) *flat_horizon_deg = NAN;
   if (n_drawn) *n_drawn = 0;
   if (w < 2 || h < 2) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "the overlay needs an image of at least 2 x 2 pixels, not %d x %d", w, h);
   if (const char* msg = overlay_check(o)) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  OVERLAY_TRY(hipSetDevice(c->device));
+  HIP_TRY(report, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   std::vector<atmrt_drawn_tick_t> ticks;
   if (o.n_ticks || o.n_vertical_ticks) { // row 0 and column 0: W + H doubles to the host
     std::vector<double> az0(w), el0(h);
-    OVERLAY_TRY(hipMemcpyAsync(az0.data(), az, (size_t)w * 8, hipMemcpyDeviceToHost, s));
-    OVERLAY_TRY(hipMemcpy2DAsync(el0.data(), 8, el, (size_t)w * 8, 8, (size_t)h, hipMemcpyDeviceToHost, s));
-    OVERLAY_TRY(hipStreamSynchronize(s));
+    HIP_TRY(report, hipMemcpyAsync(az0.data(), az, (size_t)w * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(report, hipMemcpy2DAsync(el0.data(), 8, el, (size_t)w * 8, 8, (size_t)h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(report, hipStreamSynchronize(s));
     if (const char* msg = resolve_ticks(p, o, az0.data(), w, el0.data(), h, &ticks)) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
   }
   if (n_drawn) *n_drawn = ticks.size();
@@ -1539,14 +1560,14 @@ int draw_overlay_on(atmrt_ctx* c, atmrt_ctx* report, const atmrt_params_t& p, co
   const bool flat = o.show_flat_horizon && earth_shape_is_flat(p.earth.kind) && !p.straight_rays; // :420-422
   const bool eye = o.show_eye_level != 0;
   int n_cu = 0;
-  OVERLAY_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+  HIP_TRY(report, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
   const int bands = overlay_bands(w, h, n_cu);
   struct DevTick {
     uint32_t pos, size;
     int32_t vertical, _pad;
   };
   const size_t tick_bytes = Carve::pad(ticks.size() * sizeof(DevTick)), sample_bytes = Carve::pad(4 * sizeof(double));
-  OVERLAY_TRY(c->d_overlay.reserve(tick_bytes + sample_bytes + overlay_workspace_bytes(w, bands)));
+  HIP_TRY(report, c->d_overlay.reserve(tick_bytes + sample_bytes + overlay_workspace_bytes(w, bands)));
   char* base = c->d_overlay.as<char>();
   double target = NAN;
   if (flat) { // n at the observer's altitude through the library's own refr_n (k_atm_sample); acos and the degrees on the host
@@ -1555,16 +1576,16 @@ int draw_overlay_on(atmrt_ctx* c, atmrt_ctx* report, const atmrt_params_t& p, co
     double* d = reinterpret_cast<double*>(base + tick_bytes);
     launch_atm_sample(f, 1, c->d_alt.as<double>(), d, d + 1, d + 2, d + 3, s);
     double n_at_observer = 0.0;
-    OVERLAY_TRY(hipMemcpyAsync(&n_at_observer, d + 2, 8, hipMemcpyDeviceToHost, s));
-    OVERLAY_TRY(hipStreamSynchronize(s));
+    HIP_TRY(report, hipMemcpyAsync(&n_at_observer, d + 2, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(report, hipStreamSynchronize(s));
     target = std::acos(1.0 / n_at_observer) * (180.0 / M_PI); // f64::to_degrees
     if (flat_horizon_deg) *flat_horizon_deg = target;
   }
   if (!ticks.empty()) {
     std::vector<DevTick> dt(ticks.size());
     for (size_t i = 0; i < ticks.size(); i++) dt[i] = DevTick{ticks[i].pos, ticks[i].size, ticks[i].vertical, 0};
-    OVERLAY_TRY(hipMemcpyAsync(base, dt.data(), dt.size() * sizeof(DevTick), hipMemcpyHostToDevice, s));
-    OVERLAY_TRY(hipStreamSynchronize(s)); // dt goes out of scope
+    HIP_TRY(report, hipMemcpyAsync(base, dt.data(), dt.size() * sizeof(DevTick), hipMemcpyHostToDevice, s));
+    HIP_TRY(report, hipStreamSynchronize(s)); // dt goes out of scope
     launch_overlay_ticks(base, (int)dt.size(), w, h, rgb, s);
   }
   if (flat || eye) { // a NaN target is never close to anything: its line is all None
@@ -1574,10 +1595,9 @@ int draw_overlay_on(atmrt_ctx* c, atmrt_ctx* report, const atmrt_params_t& p, co
     if (flat) launch_overlay_lines(y_of_x, w, h, rgb, flat_color, s);
     if (eye) launch_overlay_lines(y_of_x + w, w, h, rgb, eye_color, s);
   }
-  OVERLAY_TRY(hipStreamSynchronize(s));
-  OVERLAY_TRY(hipGetLastError());
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
   return ATMRT_OK;
-#undef OVERLAY_TRY
 }
 
 } // namespace
@@ -1601,8 +1621,7 @@ extern "C" int atmrt_overlay_resolve_ticks(const atmrt_params_t* params, const a
 extern "C" int atmrt_draw_overlay_device(atmrt_ctx* c, const atmrt_overlay_t* overlay, uint8_t* rgb_device, atmrt_drawn_tick_t* drawn,
                                          size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
   if (!c || !overlay || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device");
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay needs a frame: call atmrt_generate first");
+  if (int rc = frame_state_check(c, "atmrt_draw_overlay", "draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device")) return rc;
   return draw_overlay_on(c, c, c->last_params, *overlay, c->last_dense.azimuth, c->last_dense.elevation_angle, c->last_wl, c->last_h,
                          rgb_device, drawn, capacity, n_drawn, flat_horizon_deg);
 }
@@ -1610,8 +1629,7 @@ extern "C" int atmrt_draw_overlay_device(atmrt_ctx* c, const atmrt_overlay_t* ov
 extern "C" int atmrt_draw_overlay(atmrt_ctx* c, const atmrt_overlay_t* overlay, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity,
                                   size_t* n_drawn, double* flat_horizon_deg) {
   if (!c || !overlay || !rgb) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device");
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay needs a frame: call atmrt_generate first");
+  if (int rc = frame_state_check(c, "atmrt_draw_overlay", "draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device")) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, c->d_io.reserve(3 * c->last_npx + 256));
   HIP_TRY(c, hipMemcpy(c->d_io.ptr, rgb, 3 * c->last_npx, hipMemcpyHostToDevice));
@@ -1625,20 +1643,10 @@ extern "C" int atmrt_draw_overlay_planes_device(atmrt_ctx* c, const atmrt_overla
                                                 const double* elevation_angle, uint32_t width, uint32_t height, uint8_t* rgb_device,
                                                 atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
   if (!c || !overlay || !azimuth || !elevation_angle || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
+  if (int rc = u16_size_check(c, width, height)) return rc;
   if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_set_params has not been called");
-  atmrt_ctx* k = c;
-  if (c->multi) { // the device context that owns the memory: its stream, its workspace, its copy of the observer altitude
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, rgb_device) != hipSuccess) {
-      (void)hipGetLastError();
-      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "rgb_device is not a device allocation");
-    }
-    k = nullptr;
-    for (int i = 0; i < multi_size(c) && !k; i++)
-      if (multi_child(c, i)->device == attr.device) k = multi_child(c, i);
-    if (!k) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "rgb_device is in the memory of device %d, which is not a device of this context", attr.device);
-  }
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, rgb_device, "rgb_device", &k)) return rc;
   if (!k->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay_planes_device needs a frame: call atmrt_generate_image_device first");
   return draw_overlay_on(k, c, c->params, *overlay, azimuth, elevation_angle, (int)width, (int)height, rgb_device, drawn, capacity, n_drawn,
                          flat_horizon_deg);
@@ -1657,20 +1665,14 @@ extern "C" int atmrt_geo_grid_cell(const atmrt_geo_grid_t* g, double lat, double
 
 namespace {
 
-// The trace points a mode reads: entry p of the planes, or the lists (hit_offset set).
-struct VisSource {
-  size_t n_pixels;
-  const uint32_t* hit_count;
-  const uint64_t* hit_offset;
-  const double *lat, *lon, *dist;
-};
-
-// ATMRT_VIS_ALL reads the packed lists where the last frame has them; a frame without lists holds one point per pixel at most, in
-// its planes, and ALL is FIRST.
-VisSource vis_source_of_last_frame(const atmrt_ctx* c, int32_t mode) {
-  if (mode == ATMRT_VIS_ALL && c->last_packed)
-    return VisSource{c->last_npx, c->last_dense.hit_count, c->last_offset, c->last_hits.lat, c->last_hits.lon, c->last_hits.distance};
-  return VisSource{c->last_npx, c->last_dense.hit_count, nullptr, c->last_dense.lat, c->last_dense.lon, c->last_dense.distance};
+// The trace points of c's last frame that a mode reads.  ATMRT_VIS_ALL reads the packed lists where the frame has them; a frame
+// without lists holds one point per pixel at most, in its planes, and ALL is FIRST.
+TracePoints last_frame_points(const atmrt_ctx* c, int32_t mode) {
+  const uint32_t width = (uint32_t)c->last_wl;
+  const PackedHits& l = c->last_hits;
+  const DensePlanes& d = c->last_dense;
+  if (mode == ATMRT_VIS_ALL && c->last_packed) return TracePoints{c->last_npx, width, d.hit_count, c->last_offset, l.lat, l.lon, l.distance, l.elevation};
+  return TracePoints{c->last_npx, width, d.hit_count, nullptr, d.lat, d.lon, d.distance, d.elevation};
 }
 
 bool vis_aggregate() { // read at every call, like ATMRT_ESCAPE
@@ -1680,39 +1682,32 @@ bool vis_aggregate() { // read at every call, like ATMRT_ESCAPE
 
 // k: the context whose device holds the memory; report: the context the caller handed in (its parent on a multi-device context).
 // grid == nullptr: only the bounds.
-int vis_run(atmrt_ctx* k, atmrt_ctx* report, const VisSource& src, const atmrt_geo_grid_t* grid, uint32_t* count, double* min_distance,
+int vis_run(atmrt_ctx* k, atmrt_ctx* report, const TracePoints& src, const atmrt_geo_grid_t* grid, uint32_t* count, double* min_distance,
             atmrt_visibility_stats_t* stats, double* bounds) {
-#define VIS_TRY(expr)                                                                                        \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return report->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-  VIS_TRY(hipSetDevice(k->device));
+  HIP_TRY(report, hipSetDevice(k->device));
   hipStream_t s = k->stream;
-  VIS_TRY(k->d_vis.reserve(vis_block_bytes()));
+  HIP_TRY(report, k->d_vis.reserve(vis_block_bytes()));
   launch_vis_reset(k->d_vis.ptr, s);
-  if (grid) launch_vis_map(src.n_pixels, *grid, src.hit_count, src.hit_offset, src.lat, src.lon, src.dist, vis_aggregate(), count, min_distance, k->d_vis.ptr, s);
-  else launch_vis_bounds(src.n_pixels, src.hit_count, src.hit_offset, src.lat, src.lon, src.dist, k->d_vis.ptr, s);
+  if (grid) launch_vis_map(src, *grid, vis_aggregate(), count, min_distance, k->d_vis.ptr, s);
+  else launch_vis_bounds(src, k->d_vis.ptr, s);
   uint64_t block[16] = {};
-  VIS_TRY(hipMemcpyAsync(block, k->d_vis.ptr, vis_block_bytes(), hipMemcpyDeviceToHost, s));
-  VIS_TRY(hipStreamSynchronize(s));
-  VIS_TRY(hipGetLastError());
+  HIP_TRY(report, hipMemcpyAsync(block, k->d_vis.ptr, vis_block_bytes(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
   vis_block_decode(block, stats, bounds);
   return ATMRT_OK;
-#undef VIS_TRY
 }
 
+int vis_mode_check(atmrt_ctx* c, int32_t mode) {
+  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
+  return ATMRT_OK;
+}
 // the checks every map entry point shares; 0 or a status with the message set
 int vis_check(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, const void* count) {
   if (!grid) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "grid is NULL");
   if (!count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count is NULL");
-  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
+  if (int rc = vis_mode_check(c, mode)) return rc;
   if (const char* msg = geo_grid_check(*grid)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  return ATMRT_OK;
-}
-int vis_check_state(atmrt_ctx* c, const char* what) {
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context has no frame of its own: %s works on the gathered planes through atmrt_visibility_map_planes_device", what);
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "%s needs a frame: call atmrt_generate first", what);
   return ATMRT_OK;
 }
 
@@ -1720,24 +1715,24 @@ int vis_check_state(atmrt_ctx* c, const char* what) {
 
 extern "C" int atmrt_frame_bounds(atmrt_ctx* c, int32_t mode, double out[4]) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
-  if (int rc = vis_check_state(c, "atmrt_frame_bounds")) return rc;
-  return vis_run(c, c, vis_source_of_last_frame(c, mode), nullptr, nullptr, nullptr, nullptr, out);
+  if (int rc = vis_mode_check(c, mode)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_frame_bounds", "has no frame of its own: atmrt_frame_bounds works on the gathered planes through atmrt_visibility_map_planes_device")) return rc;
+  return vis_run(c, c, last_frame_points(c, mode), nullptr, nullptr, nullptr, nullptr, out);
 }
 
 extern "C" int atmrt_visibility_map_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count_device,
                                            double* min_distance_device, atmrt_visibility_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (int rc = vis_check(c, grid, mode, count_device)) return rc;
-  if (int rc = vis_check_state(c, "atmrt_visibility_map")) return rc;
-  return vis_run(c, c, vis_source_of_last_frame(c, mode), grid, count_device, min_distance_device, stats, nullptr);
+  if (int rc = frame_state_check(c, "atmrt_visibility_map", "has no frame of its own: atmrt_visibility_map works on the gathered planes through atmrt_visibility_map_planes_device")) return rc;
+  return vis_run(c, c, last_frame_points(c, mode), grid, count_device, min_distance_device, stats, nullptr);
 }
 
 extern "C" int atmrt_visibility_map(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count, double* min_distance,
                                     atmrt_visibility_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (int rc = vis_check(c, grid, mode, count)) return rc;
-  if (int rc = vis_check_state(c, "atmrt_visibility_map")) return rc;
+  if (int rc = frame_state_check(c, "atmrt_visibility_map", "has no frame of its own: atmrt_visibility_map works on the gathered planes through atmrt_visibility_map_planes_device")) return rc;
   HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
   const size_t n_cells = (size_t)grid->n_lat * grid->n_lon, count_bytes = Carve::pad(n_cells * sizeof(uint32_t));
   HIP_TRY(c, c->d_io.reserve(count_bytes + n_cells * sizeof(double)));
@@ -1755,20 +1750,10 @@ extern "C" int atmrt_visibility_map_planes_device(atmrt_ctx* c, const atmrt_geo_
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (int rc = vis_check(c, grid, ATMRT_VIS_FIRST, count_device)) return rc;
   if (!lat || !lon || !distance || !hit_count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a plane is NULL");
-  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
-  atmrt_ctx* k = c;
-  if (c->multi) { // the device context that owns the memory: its stream, its statistics block
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, count_device) != hipSuccess) {
-      (void)hipGetLastError();
-      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count_device is not a device allocation");
-    }
-    k = nullptr;
-    for (int i = 0; i < multi_size(c) && !k; i++)
-      if (multi_child(c, i)->device == attr.device) k = multi_child(c, i);
-    if (!k) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count_device is in the memory of device %d, which is not a device of this context", attr.device);
-  }
-  return vis_run(k, c, VisSource{(size_t)width * height, hit_count, nullptr, lat, lon, distance}, grid, count_device, min_distance_device, stats,
+  if (int rc = u16_size_check(c, width, height)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, count_device, "count_device", &k)) return rc;
+  return vis_run(k, c, TracePoints{(size_t)width * height, width, hit_count, nullptr, lat, lon, distance, nullptr}, grid, count_device, min_distance_device, stats,
                  nullptr);
 }
 
@@ -1877,58 +1862,50 @@ const char* landmark_args_check(const atmrt_landmark_t* lm, size_t n, double rad
 }
 
 // k: the context whose device holds the frame; report: the context the caller handed in (vis_run).
-int landmarks_run(atmrt_ctx* k, atmrt_ctx* report, const LmSource& src, const atmrt_landmark_t* lm, size_t n, double radius_deg,
+int landmarks_run(atmrt_ctx* k, atmrt_ctx* report, const TracePoints& src, const atmrt_landmark_t* lm, size_t n, double radius_deg,
                   atmrt_landmark_hit_t* hits, atmrt_landmark_stats_t* stats) {
-#define LM_TRY(expr)                                                                                         \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return report->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
   double bounds[4];
-  if (int rc = vis_run(k, report, VisSource{src.n_pixels, src.hit_count, src.hit_offset, src.lat, src.lon, src.dist}, nullptr, nullptr, nullptr,
-                       nullptr, bounds))
-    return rc;
+  if (int rc = vis_run(k, report, src, nullptr, nullptr, nullptr, nullptr, bounds)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   const LandmarkIndex host = landmark_index(lm, n, radius_deg, bounds);
   report->lm_timings[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  LM_TRY(hipSetDevice(k->device));
+  HIP_TRY(report, hipSetDevice(k->device));
   hipStream_t s = k->stream;
   LmIndex ix{host.grid, nullptr, nullptr, nullptr, radius_deg * radius_deg};
   LmState st{};
   atmrt_landmark_hit_t* d_hits = nullptr;
   uint32_t *d_start = nullptr, *d_items = nullptr;
   atmrt_landmark_t* d_lm = nullptr;
-  LM_TRY(reserve_carved(k->d_landmarks, [&](Carve& c) {
+  HIP_TRY(report, reserve_carved(k->d_landmarks, [&](Carve& c) {
     c(d_lm, n * sizeof(atmrt_landmark_t)), c(d_start, host.cell_start.size() * sizeof(uint32_t)), c(d_items, host.items.size() * sizeof(uint32_t));
     c(st.count, n * sizeof(uint32_t)), c(st.d2min, n * sizeof(unsigned long long)), c(st.key, n * sizeof(unsigned long long));
     c(st.ctr, LM_N * sizeof(unsigned long long)), c(d_hits, n * sizeof(atmrt_landmark_hit_t));
   }));
   ix.cell_start = d_start, ix.items = d_items, ix.lm = d_lm;
-  LM_TRY(hipEventRecord(k->ev[0], s));
-  LM_TRY(hipMemcpyAsync(d_lm, lm, n * sizeof(atmrt_landmark_t), hipMemcpyHostToDevice, s));
-  LM_TRY(hipMemcpyAsync(d_start, host.cell_start.data(), host.cell_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  if (!host.items.empty()) LM_TRY(hipMemcpyAsync(d_items, host.items.data(), host.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(report, hipEventRecord(k->ev[0], s));
+  HIP_TRY(report, hipMemcpyAsync(d_lm, lm, n * sizeof(atmrt_landmark_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(report, hipMemcpyAsync(d_start, host.cell_start.data(), host.cell_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  if (!host.items.empty()) HIP_TRY(report, hipMemcpyAsync(d_items, host.items.data(), host.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   launch_lm_reset(n, st, s);
-  LM_TRY(hipEventRecord(k->ev[1], s));
+  HIP_TRY(report, hipEventRecord(k->ev[1], s));
   launch_lm_pass(false, src, ix, st, s);
-  LM_TRY(hipEventRecord(k->ev[2], s));
+  HIP_TRY(report, hipEventRecord(k->ev[2], s));
   launch_lm_pass(true, src, ix, st, s);
-  LM_TRY(hipEventRecord(k->ev[3], s));
+  HIP_TRY(report, hipEventRecord(k->ev[3], s));
   launch_lm_finish(n, src, st, d_hits, s);
-  LM_TRY(hipEventRecord(k->ev[4], s));
+  HIP_TRY(report, hipEventRecord(k->ev[4], s));
   unsigned long long block[LM_N] = {};
-  LM_TRY(hipMemcpyAsync(hits, d_hits, n * sizeof(atmrt_landmark_hit_t), hipMemcpyDeviceToHost, s));
-  LM_TRY(hipMemcpyAsync(block, st.ctr, sizeof block, hipMemcpyDeviceToHost, s));
-  LM_TRY(hipStreamSynchronize(s));
-  LM_TRY(hipGetLastError());
+  HIP_TRY(report, hipMemcpyAsync(hits, d_hits, n * sizeof(atmrt_landmark_hit_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(report, hipMemcpyAsync(block, st.ctr, sizeof block, hipMemcpyDeviceToHost, s));
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
   for (int i = 0; i < 4; i++) {
     float ms = 0.0f;
-    LM_TRY(hipEventElapsedTime(&ms, k->ev[i], k->ev[i + 1]));
+    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[i], k->ev[i + 1]));
     report->lm_timings[1 + i] = ms;
   }
   if (stats) *stats = atmrt_landmark_stats_t{block[LM_POINTS], block[LM_SKIPPED], block[LM_TESTED], block[LM_WITHIN]};
   return ATMRT_OK;
-#undef LM_TRY
 }
 
 } // namespace
@@ -1938,15 +1915,9 @@ extern "C" int atmrt_locate_landmarks(atmrt_ctx* c, const atmrt_landmark_t* land
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (const char* msg = landmark_args_check(landmarks, n, radius_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
   if (!hits) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "hits is NULL");
-  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context has no frame of its own: atmrt_locate_landmarks works on the gathered planes through atmrt_locate_landmarks_planes_device");
-  if (int rc = vis_check_state(c, "atmrt_locate_landmarks")) return rc;
-  const uint32_t width = (uint32_t)c->last_wl;
-  if (mode == ATMRT_VIS_ALL && c->last_packed)
-    return landmarks_run(c, c, LmSource{c->last_npx, width, c->last_dense.hit_count, c->last_offset, c->last_hits.lat, c->last_hits.lon, c->last_hits.distance, c->last_hits.elevation},
-                         landmarks, n, radius_deg, hits, stats);
-  return landmarks_run(c, c, LmSource{c->last_npx, width, c->last_dense.hit_count, nullptr, c->last_dense.lat, c->last_dense.lon, c->last_dense.distance, c->last_dense.elevation},
-                       landmarks, n, radius_deg, hits, stats);
+  if (int rc = vis_mode_check(c, mode)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_locate_landmarks", "has no frame of its own: atmrt_locate_landmarks works on the gathered planes through atmrt_locate_landmarks_planes_device")) return rc;
+  return landmarks_run(c, c, last_frame_points(c, mode), landmarks, n, radius_deg, hits, stats);
 }
 
 extern "C" int atmrt_locate_landmarks_planes_device(atmrt_ctx* c, const atmrt_landmark_t* landmarks, size_t n, double radius_deg,
@@ -1957,20 +1928,10 @@ extern "C" int atmrt_locate_landmarks_planes_device(atmrt_ctx* c, const atmrt_la
   if (const char* msg = landmark_args_check(landmarks, n, radius_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
   if (!hits) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "hits is NULL");
   if (!lat || !lon || !distance || !elevation || !hit_count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a plane is NULL");
-  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
-  atmrt_ctx* k = c;
-  if (c->multi) { // the device context that owns the planes: its stream, its buffers
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, lat) != hipSuccess) {
-      (void)hipGetLastError();
-      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "lat is not a device allocation");
-    }
-    k = nullptr;
-    for (int i = 0; i < multi_size(c) && !k; i++)
-      if (multi_child(c, i)->device == attr.device) k = multi_child(c, i);
-    if (!k) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "lat is in the memory of device %d, which is not a device of this context", attr.device);
-  }
-  return landmarks_run(k, c, LmSource{(size_t)width * height, width, hit_count, nullptr, lat, lon, distance, elevation}, landmarks, n, radius_deg, hits,
+  if (int rc = u16_size_check(c, width, height)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, lat, "lat", &k)) return rc;
+  return landmarks_run(k, c, TracePoints{(size_t)width * height, width, hit_count, nullptr, lat, lon, distance, elevation}, landmarks, n, radius_deg, hits,
                        stats);
 }
 

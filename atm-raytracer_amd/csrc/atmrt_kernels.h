@@ -470,30 +470,31 @@ void launch_overlay_find_elev(const double* elev, int w, int h, int bands, doubl
 void launch_overlay_lines(const int32_t* y_of_x, int w, int h, uint8_t* rgb, const uint8_t color[3], hipStream_t stream);
 void launch_overlay_ticks(const void* ticks, int n, int w, int h, uint8_t* rgb, hipStream_t stream);
 
-// The visibility map (kernels in atmrt_vismap.h).  `block` is the call's device block of vis_block_bytes(): launch_vis_reset
-// initialises it, the scatter adds its statistics and the bounds kernel its keys, vis_block_decode reads a host copy of it.  The
-// points are entry p of the planes lat / lon / dist where hit_count[p] != 0 (hit_offset null), or entries [hit_offset[p],
-// + hit_count[p]) of the lists.  min_distance may be null.
-size_t vis_block_bytes();
-void vis_block_decode(const void* block_host, atmrt_visibility_stats_t* stats, double bounds[4]);
-void launch_vis_reset(void* block, hipStream_t stream);
-void launch_vis_map(size_t n_pixels, const atmrt_geo_grid_t& grid, const uint32_t* hit_count, const uint64_t* hit_offset,
-                    const double* lat, const double* lon, const double* dist, bool aggregate, uint32_t* count, double* min_distance,
-                    void* block, hipStream_t stream);
-void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_t* hit_offset, const double* lat, const double* lon,
-                       const double* dist, void* block, hipStream_t stream);
-
-// The landmark search (kernels in atmrt_landmarks.h).  LmSource: the trace points, as the visibility map reads them, with the
-// elevations the records quote and the width that turns a flat pixel index into (x, y).  LmIndex: the call's bucket index in
-// device memory — cell c of `grid` lists the landmarks items[cell_start[c] .. cell_start[c + 1]), indices into lm.  LmState: per
-// landmark the count, the smallest d2 (its bits) and the winner's key p << 32 | point index, and the statistics block (LM_N u64).
-struct LmSource {
+// Where a frame's trace points are, for the kernels that read a finished frame (atmrt_vismap.h, atmrt_landmarks.h): pixel p of
+// n_pixels holds entry p of the planes lat / lon / dist / elev where hit_count[p] != 0 (hit_offset null), or entries [hit_offset[p],
+// + hit_count[p]) of the lists.  `width` turns a flat pixel index into (x, y).  The visibility map reads neither `width` nor `elev`:
+// a caller without an elevation plane leaves it null.
+struct TracePoints {
   size_t n_pixels;
   uint32_t width;
   const uint32_t* hit_count;
   const uint64_t* hit_offset; // null: the planes
   const double *lat, *lon, *dist, *elev;
 };
+
+// The visibility map (kernels in atmrt_vismap.h).  `block` is the call's device block of vis_block_bytes(): launch_vis_reset
+// initialises it, the scatter adds its statistics and the bounds kernel its keys, vis_block_decode reads a host copy of it.
+// min_distance may be null.
+size_t vis_block_bytes();
+void vis_block_decode(const void* block_host, atmrt_visibility_stats_t* stats, double bounds[4]);
+void launch_vis_reset(void* block, hipStream_t stream);
+void launch_vis_map(const TracePoints& src, const atmrt_geo_grid_t& grid, bool aggregate, uint32_t* count, double* min_distance, void* block,
+                    hipStream_t stream);
+void launch_vis_bounds(const TracePoints& src, void* block, hipStream_t stream);
+
+// The landmark search (kernels in atmrt_landmarks.h).  LmIndex: the call's bucket index in device memory — cell c of `grid` lists
+// the landmarks items[cell_start[c] .. cell_start[c + 1]), indices into lm.  LmState: per landmark the count, the smallest d2 (its
+// bits) and the winner's key p << 32 | point index, and the statistics block (LM_N u64).
 struct LmIndex {
   atmrt_geo_grid_t grid;
   const uint32_t* cell_start; // [n_cells + 1]
@@ -509,8 +510,8 @@ struct LmState {
 };
 // the call's kernels in order: reset, pass A (pass_b false), pass B, pass C; hits is device memory for n records
 void launch_lm_reset(size_t n, const LmState& state, hipStream_t stream);
-void launch_lm_pass(bool pass_b, const LmSource& src, const LmIndex& index, const LmState& state, hipStream_t stream);
-void launch_lm_finish(size_t n, const LmSource& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream);
+void launch_lm_pass(bool pass_b, const TracePoints& src, const LmIndex& index, const LmState& state, hipStream_t stream);
+void launch_lm_finish(size_t n, const TracePoints& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream);
 
 void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream);

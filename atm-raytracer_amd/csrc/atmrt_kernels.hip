@@ -1368,18 +1368,16 @@ void vis_block_decode(const void* block_host, atmrt_visibility_stats_t* stats, d
 void launch_vis_reset(void* block, hipStream_t stream) {
   hipLaunchKernelGGL(k_vis_reset, dim3(1), dim3(64), 0, stream, static_cast<unsigned long long*>(block));
 }
-void launch_vis_map(size_t n_pixels, const atmrt_geo_grid_t& grid, const uint32_t* hit_count, const uint64_t* hit_offset,
-                    const double* lat, const double* lon, const double* dist, bool aggregate, uint32_t* count, double* min_distance,
-                    void* block, hipStream_t stream) {
+void launch_vis_map(const TracePoints& src, const atmrt_geo_grid_t& grid, bool aggregate, uint32_t* count, double* min_distance, void* block,
+                    hipStream_t stream) {
   const size_t n_cells = (size_t)grid.n_lat * grid.n_lon;
   unsigned long long* mind = reinterpret_cast<unsigned long long*>(min_distance);
   unsigned long long* ctr = static_cast<unsigned long long*>(block);
   hipLaunchKernelGGL(k_vis_clear, dim3(cdiv(n_cells, 256)), dim3(256), 0, stream, n_cells, count, mind);
-  if (!n_pixels) return;
-  const dim3 grd(cdiv(n_pixels, 256)), blk(256);
-#define VIS_LAUNCH(PACKED, AGG) \
-  hipLaunchKernelGGL((k_vis_scatter<PACKED, AGG>), grd, blk, 0, stream, n_pixels, grid, hit_count, hit_offset, lat, lon, dist, count, mind, ctr)
-  if (hit_offset) {
+  if (!src.n_pixels) return;
+  const dim3 grd(cdiv(src.n_pixels, 256)), blk(256);
+#define VIS_LAUNCH(PACKED, AGG) hipLaunchKernelGGL((k_vis_scatter<PACKED, AGG>), grd, blk, 0, stream, src, grid, count, mind, ctr)
+  if (src.hit_offset) {
     if (aggregate) VIS_LAUNCH(true, true);
     else VIS_LAUNCH(true, false);
   } else {
@@ -1388,14 +1386,12 @@ void launch_vis_map(size_t n_pixels, const atmrt_geo_grid_t& grid, const uint32_
   }
 #undef VIS_LAUNCH
 }
-void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_t* hit_offset, const double* lat, const double* lon,
-                       const double* dist, void* block, hipStream_t stream) {
-  if (!n_pixels) return;
+void launch_vis_bounds(const TracePoints& src, void* block, hipStream_t stream) {
+  if (!src.n_pixels) return;
+  const dim3 grd(cdiv(src.n_pixels, 256)), blk(256);
   unsigned long long* ctr = static_cast<unsigned long long*>(block);
-  if (hit_offset)
-    hipLaunchKernelGGL((k_vis_bounds<true>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, hit_count, hit_offset, lat, lon, dist, ctr);
-  else
-    hipLaunchKernelGGL((k_vis_bounds<false>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, hit_count, hit_offset, lat, lon, dist, ctr);
+  if (src.hit_offset) hipLaunchKernelGGL((k_vis_bounds<true>), grd, blk, 0, stream, src, ctr);
+  else hipLaunchKernelGGL((k_vis_bounds<false>), grd, blk, 0, stream, src, ctr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1404,7 +1400,7 @@ void launch_vis_bounds(size_t n_pixels, const uint32_t* hit_count, const uint64_
 void launch_lm_reset(size_t n, const LmState& state, hipStream_t stream) {
   hipLaunchKernelGGL(k_lm_reset, dim3(cdiv(n > (size_t)LM_N ? n : (size_t)LM_N, 256)), dim3(256), 0, stream, n, state);
 }
-void launch_lm_pass(bool pass_b, const LmSource& src, const LmIndex& index, const LmState& state, hipStream_t stream) {
+void launch_lm_pass(bool pass_b, const TracePoints& src, const LmIndex& index, const LmState& state, hipStream_t stream) {
   if (!src.n_pixels) return;
   const dim3 grd(cdiv(src.n_pixels, 256)), blk(256);
 #define LM_LAUNCH(PACKED, PASS_B) hipLaunchKernelGGL((k_lm_pass<PACKED, PASS_B>), grd, blk, 0, stream, src, index, state)
@@ -1417,7 +1413,7 @@ void launch_lm_pass(bool pass_b, const LmSource& src, const LmIndex& index, cons
   }
 #undef LM_LAUNCH
 }
-void launch_lm_finish(size_t n, const LmSource& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream) {
+void launch_lm_finish(size_t n, const TracePoints& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream) {
   hipLaunchKernelGGL(k_lm_finish, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, src, state, hits);
 }
 

@@ -3,8 +3,8 @@
 //
 // The host lays a bucket index over the landmarks (atmrt_api.hip, LandmarkIndex: an atmrt_geo_grid_t whose cells list, as CSR,
 // the landmarks whose padded boxes overlap them), so a trace point looks up ONE cell with geo_grid_cell and evaluates the exact
-// rule landmark_d2 (atmrt_core.h) on that cell's list only.  The traversal is k_vis_scatter's: one pixel per lane, row-major, a
-// trip loop over the wavefront's largest point count.
+// rule landmark_d2 (atmrt_core.h) on that cell's list only.  The traversal is vis_span and vis_point (atmrt_vismap.h), as in
+// k_vis_scatter: one pixel per lane, row-major, a trip loop over the wavefront's largest point count.
 //   pass A  within pairs: u32 add on the landmark's count, u64 min on the bit pattern of d2 (a sum of squares, never negative:
 //           it orders like its bits)
 //   pass B  the same traversal; a pair whose d2 bits equal the landmark's minimum: u64 min on the key p << 32 | point index
@@ -32,13 +32,12 @@ __global__ __launch_bounds__(256) void k_lm_reset(size_t n, LmState st) {
 }
 
 template <bool PACKED, bool PASS_B>
-__global__ __launch_bounds__(256) void k_lm_pass(LmSource s, LmIndex ix, LmState st) {
+__global__ __launch_bounds__(256) void k_lm_pass(TracePoints s, LmIndex ix, LmState st) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  const bool in = p < s.n_pixels;
-  uint32_t cnt = in ? s.hit_count[p] : 0u;
-  if (!PACKED && cnt > 1u) cnt = 1u;
-  const size_t k0 = PACKED ? (in ? (size_t)s.hit_offset[p] : 0) : p;
+  const VisSpan span = vis_span<PACKED>(s, p);
+  const uint32_t cnt = span.cnt;
+  const size_t k0 = span.k0;
   unsigned long long n_points = 0, n_skipped = 0; // wave-uniform
   unsigned long long n_tested = 0, n_within = 0;  // this lane's; summed over the wavefront once, below
   for (uint32_t q = 0; __any(q < cnt); q++) {
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void k_lm_pass(LmSource s, LmIndex ix, LmState
   }
 }
 
-__global__ __launch_bounds__(256) void k_lm_finish(size_t n, LmSource s, LmState st, atmrt_landmark_hit_t* __restrict__ hits) {
+__global__ __launch_bounds__(256) void k_lm_finish(size_t n, TracePoints s, LmState st, atmrt_landmark_hit_t* __restrict__ hits) {
   const size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= n) return;
   atmrt_landmark_hit_t h{0u, 0xffffffffu, 0xffffffffu, 0u, __builtin_inf(), __builtin_nan(""), __builtin_nan("")};

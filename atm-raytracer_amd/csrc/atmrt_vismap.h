@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "atmrt_core.h"
+#include "atmrt_kernels.h"
 
 namespace atmrt {
 
@@ -51,9 +52,24 @@ __global__ __launch_bounds__(256) void k_vis_clear(size_t n_cells, uint32_t* __r
   if (mind) mind[i] = VIS_INF_BITS;
 }
 
+// The traversal every consumer of a frame's trace points (TracePoints, atmrt_kernels.h) shares: thread p is pixel p, row-major as
+// in k_draw_image, and holds `cnt` points, entries k0 .. k0 + cnt - 1 of s.lat / lon / dist.  PACKED: the pixel's entries of the
+// lists; else its one entry of the planes, present when hit_count[p] != 0.  A thread past the last pixel gets no point (and entry
+// 0) rather than leaving: the callers' ballots, shuffles and __any need all 64 lanes.
+struct VisSpan {
+  uint32_t cnt;
+  size_t k0;
+};
+template <bool PACKED>
+__device__ inline VisSpan vis_span(const TracePoints& s, size_t p) {
+  const bool in = p < s.n_pixels;
+  uint32_t cnt = in ? s.hit_count[p] : 0u;
+  if (!PACKED && cnt > 1u) cnt = 1u;
+  return VisSpan{cnt, PACKED ? (in ? (size_t)s.hit_offset[p] : 0) : p};
+}
+
 // One trace point of a lane: is there one in this trip, and is it one the map looks up (none of lat, lon, distance NaN, distance
-// not negative)?  PACKED: the points of pixel p are entries [hit_offset[p], + hit_count[p]) of the lists; else the one point of
-// the planes' entry p, present when hit_count[p] != 0.
+// not negative)?
 struct VisPoint {
   double lat, lon, dist;
   bool active, valid;
@@ -77,17 +93,13 @@ __device__ inline VisPoint vis_point(bool active, size_t k, const double* __rest
 // only the smallest distance needs the log-step combine: after step d a lane holds the minimum over itself and the next 2d - 1
 // lanes of its run.  A wavefront whose runs are all one lane long (a fine grid) skips the combine.
 template <bool PACKED, bool AGG>
-__global__ __launch_bounds__(256) void k_vis_scatter(size_t n_pixels, atmrt_geo_grid_t g, const uint32_t* __restrict__ hit_count,
-                                                     const uint64_t* __restrict__ hit_offset, const double* __restrict__ lat,
-                                                     const double* __restrict__ lon, const double* __restrict__ dist,
-                                                     uint32_t* __restrict__ count, unsigned long long* __restrict__ mind,
-                                                     unsigned long long* __restrict__ ctr) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void k_vis_scatter(TracePoints s, atmrt_geo_grid_t g, uint32_t* __restrict__ count,
+                                                     unsigned long long* __restrict__ mind, unsigned long long* __restrict__ ctr) {
   const int lane = threadIdx.x & 63;
-  const bool in = p < n_pixels;
-  uint32_t cnt = in ? hit_count[p] : 0u;
-  if (!PACKED && cnt > 1u) cnt = 1u;
-  const size_t k0 = PACKED ? (in ? (size_t)hit_offset[p] : 0) : p;
+  const VisSpan span = vis_span<PACKED>(s, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+  const uint32_t cnt = span.cnt;
+  const size_t k0 = span.k0;
+  const double *__restrict__ lat = s.lat, *__restrict__ lon = s.lon, *__restrict__ dist = s.dist;
   unsigned long long n_points = 0, n_binned = 0, n_skipped = 0, n_updates = 0; // wave-uniform
   for (uint32_t q = 0; __any(q < cnt); q++) {
     const VisPoint v = vis_point(q < cnt, k0 + q, lat, lon, dist);
@@ -134,16 +146,12 @@ __global__ __launch_bounds__(256) void k_vis_scatter(size_t n_pixels, atmrt_geo_
 // The frame's bounds over the points the scatter would look up: each lane keeps the extremes of its pixel's points as keys, the
 // wavefront combines them by butterfly, and one lane issues the four atomics (a wavefront without such a point issues none).
 template <bool PACKED>
-__global__ __launch_bounds__(256) void k_vis_bounds(size_t n_pixels, const uint32_t* __restrict__ hit_count,
-                                                    const uint64_t* __restrict__ hit_offset, const double* __restrict__ lat,
-                                                    const double* __restrict__ lon, const double* __restrict__ dist,
-                                                    unsigned long long* __restrict__ ctr) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void k_vis_bounds(TracePoints s, unsigned long long* __restrict__ ctr) {
   const int lane = threadIdx.x & 63;
-  const bool in = p < n_pixels;
-  uint32_t cnt = in ? hit_count[p] : 0u;
-  if (!PACKED && cnt > 1u) cnt = 1u;
-  const size_t k0 = PACKED ? (in ? (size_t)hit_offset[p] : 0) : p;
+  const VisSpan span = vis_span<PACKED>(s, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+  const uint32_t cnt = span.cnt;
+  const size_t k0 = span.k0;
+  const double *__restrict__ lat = s.lat, *__restrict__ lon = s.lon, *__restrict__ dist = s.dist;
   unsigned long long lat_min = ~0ull, lat_max = 0ull, lon_min = ~0ull, lon_max = 0ull;
   for (uint32_t q = 0; q < cnt; q++) {
     const VisPoint v = vis_point(true, k0 + q, lat, lon, dist);
