@@ -221,6 +221,9 @@ static __device__ __forceinline__ Earth earth_for(const Frame& f) {
 constexpr int STEP_CANDIDATES = 12; // trace points of one step kept in registers (terrain + up to 4 per object); a step with more
                                     // is counted exactly and written through the big-step route below (HBM, fill pass)
 
+struct StepGeom { // the two samples of the step: what an object point is interpolated from (utils.rs:261-272)
+  double lat0, lon0, re0, d0, pl0, lat1, lon1, re1, d1, pl1;
+};
 struct StepHits {
   int n;       // trace points pushed in this step; only the first STEP_CANDIDATES of them are kept below
   bool finish;
@@ -248,6 +251,17 @@ static __device__ __forceinline__ void step_push(StepHits& sh, double prop, int 
   sh.n++;
 }
 
+// the start of a step: nothing pushed yet but the terrain crossing between its two samples (ray - terrain: diff1, diff2), which
+// ends the ray over opaque terrain (utils.rs:222-240)
+static __device__ __forceinline__ void step_begin(StepHits& sh, bool crossing, double diff1, double diff2, bool terrain_opaque) {
+  sh.n = 0;
+  sh.finish = false;
+  if (crossing) {
+    step_push(sh, diff1 / (diff1 - diff2), -1, nullptr);
+    if (terrain_opaque) sh.finish = true;
+  }
+}
+
 // collisions of one object with the segment, utils.rs:251-278
 static __device__ __forceinline__ bool object_out_of_band(const ObjectDev& o, double re0, double re1) {
   return (re0 < o.vlo && re1 < o.vlo) || (re0 > o.vhi && re1 > o.vhi); // false for NaN: the geometry then decides
@@ -271,14 +285,25 @@ static __device__ __forceinline__ void step_object(StepHits& sh, const Frame& f,
   step_object_impl(sh, f.objects, f.textures, idx, pos1, pos2);
 }
 
+// an object point, complete (utils.rs:261-272), into entry k: interpolated between the step's two samples at the collision's prop
+static __device__ __forceinline__ void object_point_put(const PackedHits& packed, uint64_t k, const Collision& c, const StepGeom& g) {
+  packed.lat[k] = lerp_ts(g.lat0, g.lat1, c.prop);
+  packed.lon[k] = lerp_ts(g.lon0, g.lon1, c.prop);
+  packed.distance[k] = lerp_ts(g.d0, g.d1, c.prop);
+  packed.elevation[k] = lerp_ts(g.re0, g.re1, c.prop); // object hits report the RAY elevation (utils.rs:268)
+  packed.path_length[k] = lerp_ts(g.pl0, g.pl1, c.prop);
+  packed.normal[3 * k] = c.normal.x;
+  packed.normal[3 * k + 1] = c.normal.y;
+  packed.normal[3 * k + 2] = c.normal.z;
+  packed.color_tag[k] = ATMRT_COLOR_RGBA;
+  for (int q = 0; q < 4; q++) packed.rgba[4 * k + q] = c.color[q];
+}
+
 // ---- big steps: more trace points in one step than StepHits keeps ------------------------------------------------------------
 // Fill pass only (the counting pass counts them exactly and raises CTR_BIG_STEPS; such a pixel always exceeds its slots, so it is
 // traced again by the fill pass).  The step's points are produced a second time, written straight to their pixel's range of the
 // output list in production order with their `prop` beside them (Workspace::step_prop), and stable-sorted there by prop —
 // the same order as the reference's `step_result.sort_by(prop)` over its push order (utils.rs:279).
-struct StepGeom { // the two samples of the step: what an object point is interpolated from (utils.rs:261-272)
-  double lat0, lon0, re0, d0, pl0, lat1, lon1, re1, d1, pl1;
-};
 static __device__ __noinline__ void big_step_put(const PackedHits& packed, double* __restrict__ props, uint64_t k, double prop,
                                                  const Collision* c, const StepGeom& g) {
   props[k] = prop;
@@ -286,16 +311,7 @@ static __device__ __noinline__ void big_step_put(const PackedHits& packed, doubl
     packed.color_tag[k] = ATMRT_COLOR_TERRAIN; // completed by the *_finalize_list kernels
     return;
   }
-  packed.lat[k] = lerp_ts(g.lat0, g.lat1, prop);
-  packed.lon[k] = lerp_ts(g.lon0, g.lon1, prop);
-  packed.distance[k] = lerp_ts(g.d0, g.d1, prop);
-  packed.elevation[k] = lerp_ts(g.re0, g.re1, prop);
-  packed.path_length[k] = lerp_ts(g.pl0, g.pl1, prop);
-  packed.normal[3 * k] = c->normal.x;
-  packed.normal[3 * k + 1] = c->normal.y;
-  packed.normal[3 * k + 2] = c->normal.z;
-  packed.color_tag[k] = ATMRT_COLOR_RGBA;
-  for (int q = 0; q < 4; q++) packed.rgba[4 * k + q] = c->color[q];
+  object_point_put(packed, k, *c, g);
 }
 static __device__ __forceinline__ void big_step_object(const PackedHits& packed, double* __restrict__ props, uint64_t& k,
                                                        const Frame& f, int idx, Vec3 pos1, Vec3 pos2, const StepGeom& g) {
@@ -352,30 +368,14 @@ static __device__ __noinline__ void big_step_sort(const PackedHits& h, double* _
 // emit the sorted trace points of one step (fill pass).  Terrain points are finished later by the
 // *_finalize_list kernels (they need find_normal); object points are complete here (utils.rs:261-272).
 static __device__ __forceinline__ void step_emit(const StepHits& sh, const PackedHits& packed, uint32_t* list_step,
-                                                 uint32_t* list_pixel, uint64_t& k, uint32_t pixel, int step_index,
-                                                 double lat0, double lon0, double re0, double d0, double pl0, double lat1,
-                                                 double lon1, double re1, double d1, double pl1) {
+                                                 uint32_t* list_pixel, uint64_t& k, uint32_t pixel, int step_index, const StepGeom& g) {
   for (int j = 0; j < sh.n; j++, k++) {
     list_step[k] = (uint32_t)step_index;
     list_pixel[k] = pixel;
-    if (sh.kind[j] < 0) {
-      packed.color_tag[k] = ATMRT_COLOR_TERRAIN;
-      continue;
-    }
-    double prop = sh.col[j].prop;
-    packed.lat[k] = lerp_ts(lat0, lat1, prop);
-    packed.lon[k] = lerp_ts(lon0, lon1, prop);
-    packed.distance[k] = lerp_ts(d0, d1, prop);
-    packed.elevation[k] = lerp_ts(re0, re1, prop); // object hits report the RAY elevation (utils.rs:268)
-    packed.path_length[k] = lerp_ts(pl0, pl1, prop);
-    packed.normal[3 * k] = sh.col[j].normal.x;
-    packed.normal[3 * k + 1] = sh.col[j].normal.y;
-    packed.normal[3 * k + 2] = sh.col[j].normal.z;
-    packed.color_tag[k] = ATMRT_COLOR_RGBA;
-    for (int q = 0; q < 4; q++) packed.rgba[4 * k + q] = sh.col[j].color[q];
+    if (sh.kind[j] < 0) packed.color_tag[k] = ATMRT_COLOR_TERRAIN;
+    else object_point_put(packed, k, sh.col[j], g);
   }
 }
-
 
 // Rectilinear record: ray elevation and path length at the two samples that bracket a crossing (planar arrays)
 struct RectRec {
@@ -415,18 +415,72 @@ static __device__ __forceinline__ void packed_copy(const PackedHits& dst, size_t
   }, dst, src);
 }
 
-// where the out-of-line object step of the lean march (object_step_impl, atmrt_march_impl.h) writes: the general tracer's arenas of
-// the counting pass.  A copy lives in HBM beside a copy of the Frame (Workspace::step_ctx): an out-of-line device function cannot
-// address a kernel's by-value arguments.
-struct ObjectStepSinks {
-  PackedHits slot_packed;  // [plane * RECT_SLOTS]
-  RectRec slots;
-  uint32_t* slot_step;
-  uint32_t* slot_pixel;
+// Where the trace points of a step go, every array the two routes below write.  Counting pass: packed / rec / step / pixel are the
+// slot arena, pixel-major (slot_index), and ovf / ovf_packed the overflow arena.  Fill pass: they are the pixel-ordered list, and
+// there is no arena.  The out-of-line object step of the lean march (object_step_impl, atmrt_march_impl.h) writes to the general
+// tracer's arenas of the counting pass: a copy lives in HBM beside a copy of the Frame (Workspace::step_ctx): an out-of-line device
+// function cannot address a kernel's by-value arguments.
+struct StepSinks {
+  PackedHits packed;  // counting pass: [plane * RECT_SLOTS]
+  RectRec rec;        // Rectilinear (REC below): the record of every point
+  uint32_t* step;
+  uint32_t* pixel;
   OverflowArena ovf;
   PackedHits ovf_packed;
   unsigned long long* counters;
 };
-static_assert(sizeof(ObjectStepSinks) <= OBJECT_STEP_SINKS_MAX_BYTES, "Workspace::step_ctx reserves this much behind the Frame");
+static_assert(sizeof(StepSinks) <= STEP_SINKS_MAX_BYTES, "Workspace::step_ctx reserves this much behind the Frame");
+
+// THE counting route of a step's sorted trace points (k_fast_trace<false>, k_rect_trace<false>, object_step_impl): trace points
+// count ... of pixel p.  While they fit the pixel's slots they go there; beyond the slots the step's points go to the overflow
+// arena, if there is one and the step fits StepHits.  REC: with the Rectilinear record of the step beside every point.
+template <bool REC>
+static __device__ __forceinline__ void step_commit_count(const StepHits& hits, const StepSinks& sk, uint32_t p, unsigned count, int step_index,
+                                                         size_t plane, const StepGeom& g) {
+  if (hits.n > STEP_CANDIDATES) atomicAdd(&sk.counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
+  if (hits.n && count + (unsigned)hits.n <= (unsigned)RECT_SLOTS) {
+    uint64_t k = slot_index<SlotLayout::PixelMajor>(p, count, plane);
+    const uint64_t k0 = k;
+    step_emit(hits, sk.packed, sk.step, sk.pixel, k, p, step_index, g);
+    if (REC)
+      for (uint64_t q = k0; q < k; q++) rec_store(sk.rec, q, g.re0, g.pl0, g.re1, g.pl1); // terrain points: what k_rect_finalize_list needs
+  } else if (hits.n && hits.n <= STEP_CANDIDATES && sk.ovf.cap) { // beyond the slots: the step's points into the overflow arena
+    const unsigned long long base = atomicAdd(&sk.counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
+    if (base + (unsigned long long)hits.n <= sk.ovf.cap) {
+      uint64_t kk = base;
+      step_emit(hits, sk.ovf_packed, sk.ovf.step, sk.ovf.pixel, kk, p, step_index, g);
+      for (uint64_t q = base; q < kk; q++) {
+        sk.ovf.ordinal[q] = count + (unsigned)(q - base);
+        if (REC) rec_store(sk.ovf, q, g.re0, g.pl0, g.re1, g.pl1);
+      }
+    }
+  }
+}
+
+// THE fill route (k_fast_trace<true>, k_rect_trace<true>): the step's points to entries k ... of the pixel-ordered list.  A big step
+// is produced a second time, straight into the list, and sorted there; for_each_object(visit) enumerates the step's objects,
+// ascending, as it did for `hits`, and (crossing, diff1, diff2) are what step_begin was given.
+template <bool REC, class Objects>
+static __device__ __forceinline__ void step_commit_fill(const StepHits& hits, const StepSinks& sk, double* __restrict__ step_prop, uint64_t& k,
+                                                        uint32_t p, int step_index, const StepGeom& g, bool crossing, double diff1,
+                                                        double diff2, const Frame& f, const Vec3& pos1, const Vec3& pos2,
+                                                        Objects&& for_each_object) {
+  const uint64_t k0 = k;
+  if (hits.n > STEP_CANDIDATES) {
+    const PackedHits packed = sk.packed; // the out-of-line functions take it by address: of a copy, so that the sinks stay in registers
+    if (crossing) big_step_put(packed, step_prop, k++, diff1 / (diff1 - diff2), nullptr, g);
+    for_each_object([&](int j) { big_step_object(packed, step_prop, k, f, j, pos1, pos2, g); });
+    big_step_sort(packed, step_prop, k0, hits.n);
+    for (uint64_t q = k0; q < k; q++) {
+      sk.step[q] = (uint32_t)step_index;
+      sk.pixel[q] = p;
+      if (REC) rec_store(sk.rec, q, g.re0, g.pl0, g.re1, g.pl1);
+    }
+  } else if (hits.n) {
+    step_emit(hits, sk.packed, sk.step, sk.pixel, k, p, step_index, g);
+    if (REC)
+      for (uint64_t q = k0; q < k; q++) rec_store(sk.rec, q, g.re0, g.pl0, g.re1, g.pl1); // terrain points: what k_rect_finalize_list needs
+  }
+}
 
 } // namespace atmrt

@@ -192,7 +192,8 @@ constexpr int RECT_SLOTS = 4;
 // without objects keep it slot-major, [RECT_SLOTS][plane]: their counting passes (k_fast_intersect, the lean march in MODE 1) run
 // one pixel per lane, so a wavefront's stores to one slot coalesce.  Scenes with objects keep it pixel-major, [plane][RECT_SLOTS]:
 // the general tracers (k_fast_trace, k_rect_trace, the lean march's object step) emit the points of one step into consecutive
-// entries (step_emit), and the counting passes around them (k_fast_intersect with slot_tag, the lean march in MODE 3) follow suit.
+// entries (step_commit_count, atmrt_device.h: their one route into slots and overflow arena), and the counting passes around them
+// (k_fast_intersect with slot_tag, the lean march in MODE 3) follow suit.
 enum class SlotLayout { SlotMajor, PixelMajor };
 template <SlotLayout LAYOUT>
 ATMRT_HD size_t slot_index(size_t p, size_t j, size_t plane) {
@@ -212,7 +213,7 @@ struct OverflowArena {
   uint32_t* color_tag; // scenes with objects: the PackedHits arena's tags (the lean march writes TERRAIN), else null
   uint32_t cap;
 };
-constexpr size_t OBJECT_STEP_SINKS_MAX_BYTES = 1024; // ObjectStepSinks (atmrt_device.h) fits: what Workspace::step_ctx reserves behind the Frame
+constexpr size_t STEP_SINKS_MAX_BYTES = 1024; // StepSinks (atmrt_device.h) fits: what Workspace::step_ctx reserves behind the Frame
 static inline size_t overflow_arena_bytes(size_t cap) { return cap * (3 * sizeof(uint32_t) + 4 * sizeof(double)); }
 static inline OverflowArena carve_overflow(char* base, size_t cap) {
   OverflowArena a{};
@@ -316,7 +317,7 @@ struct Workspace {
   PackedHits overflow_packed; // scenes with objects: the arena's complete points
   size_t overflow_cap;    // its capacity in records (set before the layout runs: prepare_workspace)
   uint32_t* object_rays;  // Rectilinear, scenes with objects: pixels the lean march left to the general tracer
-  char* step_ctx;         // Rectilinear, scenes with objects: Frame + ObjectStepSinks in HBM for the lean march's out-of-line object step
+  char* step_ctx;         // Rectilinear, scenes with objects: Frame + StepSinks in HBM for the lean march's out-of-line object step
   char* slice_state;      // time-sliced march (march_slice_layout): ray state between two slices + the FIFO of groups, or null
   // --- carved by workspace_layout in an opaque frame (the march's first hits, [4][h][wl]), else sized by the frame's trace points
   double* rect_rec;       // Rectilinear: [4][n] ray elevation / path length at the two bracketing samples
@@ -379,7 +380,7 @@ static inline void workspace_layout(const Frame& f, Carve& k, Workspace& ws) {
   }
   if (rect && objects) {
     k(ws.object_rays, npx * sizeof(uint32_t));
-    k(ws.step_ctx, Carve::pad(sizeof(Frame)) + OBJECT_STEP_SINKS_MAX_BYTES); // launch_rect_trace_count carves the two out of it
+    k(ws.step_ctx, Carve::pad(sizeof(Frame)) + STEP_SINKS_MAX_BYTES); // launch_rect_trace_count carves the two out of it
   }
   SliceLayout slices;
   if (march_slice_layout(f, slices)) k(ws.slice_state, slices.bytes);   // a small Rectilinear launch: the time-sliced march

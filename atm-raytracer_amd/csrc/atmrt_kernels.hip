@@ -534,6 +534,19 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
   if (!__any(mine)) return;
   double te0 = kprof[x], re0 = n > 0 ? pelev_t[y] : 0.0;
   uint32_t c0 = kccount[x];
+  const StepSinks sinks{packed, RectRec{}, list_step, list_pixel, OverflowArena{}, PackedHits{}, counters}; // Fast: no record, no arena
+  // a step without close objects whose samples the terrain separates: the crossing, its tag only (utils.rs:222-240)
+  auto terrain_hit = [&](int step_index) {
+    if (FILL || count < (unsigned)RECT_SLOTS) {
+      const uint64_t kw = FILL ? k : slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
+      list_step[kw] = (uint32_t)step_index;
+      list_pixel[kw] = (uint32_t)p;
+      packed.color_tag[kw] = ATMRT_COLOR_TERRAIN;
+      k++;
+    }
+    count++;
+    if (terrain_opaque) active = false;
+  };
   constexpr int TCH = 8; // samples fetched ahead: every step's scalar loads would otherwise be a dependent round trip
   int i = 1;
   while (i < nmax) {
@@ -553,17 +566,7 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
           active = active && i + q < n;
           stp += active ? 1u : 0u;
           const double diff1 = re0 - te0, diff2 = re[q] - te[q];
-          if (active && diff1 * diff2 < 0.0) {
-            if (FILL || count < (unsigned)RECT_SLOTS) {
-              const uint64_t kw = FILL ? k : slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
-              list_step[kw] = (uint32_t)(i + q - 1);
-              list_pixel[kw] = (uint32_t)p;
-              packed.color_tag[kw] = ATMRT_COLOR_TERRAIN;
-              k++;
-            }
-            count++;
-            if (terrain_opaque) active = false;
-          }
+          if (active && diff1 * diff2 < 0.0) terrain_hit(i + q - 1);
           te0 = te[q];
           re0 = re[q];
         }
@@ -582,28 +585,13 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
     const double diff1 = re0 - te0, diff2 = re1 - te1;
     const bool hit = active && diff1 * diff2 < 0.0; // utils.rs:222
     if ((c0 | c1) == 0) { // wave-uniform: no close objects at either sample — terrain only (utils.rs:222-240)
-      if (hit) {
-        if (FILL || count < (unsigned)RECT_SLOTS) {
-          const uint64_t kw = FILL ? k : slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
-          list_step[kw] = (uint32_t)(i - 1);
-          list_pixel[kw] = (uint32_t)p;
-          packed.color_tag[kw] = ATMRT_COLOR_TERRAIN;
-          k++;
-        }
-        count++;
-        if (terrain_opaque) active = false;
-      }
+      if (hit) terrain_hit(i - 1);
     } else { // the same for every lane: the union of the two ascending close lists (utils.rs:241-280)
       const ConstU32 la = kclist + kcoffset[s0];
       const ConstU32 lb = kclist + kcoffset[s1];
       if (active) {
         StepHits sh;
-        sh.n = 0;
-        sh.finish = false;
-        if (hit) {
-          step_push(sh, diff1 / (diff1 - diff2), -1, nullptr);
-          if (terrain_opaque) sh.finish = true;
-        }
+        step_begin(sh, hit, diff1, diff2, terrain_opaque);
         const double lat0 = kplat[s0], lon0 = kplon[s0], lat1 = kplat[s1], lon1 = kplon[s1];
         bool have_pos = false;
         Vec3 pos1 = v3(0.0, 0.0, 0.0), pos2 = pos1;
@@ -631,23 +619,10 @@ __global__ __launch_bounds__(256, ATMRT_FAST_TRACE_WAVES) void k_fast_trace(Fram
         };
         for_each_object([&](int idx) { step_object(sh, f, idx, pos1, pos2); });
         const double d0 = i == 1 ? 0.0 : f.xs[i - 1], pl0 = i == 1 ? 0.0 : plen_t[(size_t)(i - 1) * hh + y];
-        if (!FILL) {
-          k = slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * hh);
-          if (sh.n > STEP_CANDIDATES) atomicAdd(&counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
-        }
-        if (FILL && sh.n > STEP_CANDIDATES) { // big step: produce the points again, straight into the list, and sort them there
+        if (sh.n) {
           const StepGeom g{lat0, lon0, re0, d0, pl0, lat1, lon1, re1, f.xs[i], plen_t[(size_t)i * hh + y]};
-          const uint64_t k0 = k;
-          if (hit) big_step_put(packed, step_prop, k++, diff1 / (diff1 - diff2), nullptr, g);
-          for_each_object([&](int idx) { big_step_object(packed, step_prop, k, f, idx, pos1, pos2, g); });
-          big_step_sort(packed, step_prop, k0, sh.n);
-          for (uint64_t q = k0; q < k; q++) {
-            list_step[q] = (uint32_t)(i - 1);
-            list_pixel[q] = (uint32_t)p;
-          }
-        } else if (sh.n && (FILL || count + (unsigned)sh.n <= (unsigned)RECT_SLOTS)) {
-          step_emit(sh, packed, list_step, list_pixel, k, (uint32_t)p, i - 1, lat0, lon0, re0, d0, pl0, lat1, lon1, re1, f.xs[i],
-                    plen_t[(size_t)i * hh + y]);
+          if (FILL) step_commit_fill<false>(sh, sinks, step_prop, k, (uint32_t)p, i - 1, g, hit, diff1, diff2, f, pos1, pos2, for_each_object);
+          else step_commit_count<false>(sh, sinks, (uint32_t)p, count, i - 1, (size_t)f.wl * hh, g);
         }
         count += (unsigned)sh.n;
         if (sh.finish) active = false;

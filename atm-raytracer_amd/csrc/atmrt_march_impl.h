@@ -145,7 +145,7 @@ static __device__ __forceinline__ void escape_count(unsigned long long* counters
 // (utils.rs:211-285): both samples' geodesic points and terrain heights, the terrain crossing, the proximity filter of the two
 // samples over the wavefront's candidate objects (TerrainData::from_lat_lon, utils.rs:74-80), the collisions (frustum.rs:18-101,
 // billboard.rs), the stable sort by `prop`, the emission into the tracer's slot arena / overflow arena — the general tracer's own
-// building blocks (step_push, step_object_impl, step_emit), so the trace points are the tracer's to the bit.  The function is
+// building blocks (step_begin, step_object_impl, step_commit_count), so the trace points are the tracer's to the bit.  The function is
 // called under divergent control flow a few times per flagged ray; it reads the frame and the sinks through pointers to copies in
 // HBM (a kernel argument cannot be addressed) and is built, like every unit that calls device functions, without interprocedural
 // register allocation (Makefile CALL_EXTRA).  Only a wavefront whose candidate list overflows (more than WAVE_CAND objects) or an
@@ -160,7 +160,7 @@ struct ObjectStepIO {      // one lane's step, in scratch at the call site
   int32_t finish;          // out: the ray ends with this step (utils.rs:237-239, 274-285)
 };
 template <int CALC>
-static __device__ __attribute__((noinline)) void object_step_impl(const Frame* __restrict__ fg, const ObjectStepSinks* __restrict__ sk,
+static __device__ __attribute__((noinline)) void object_step_impl(const Frame* __restrict__ fg, const StepSinks* __restrict__ sk,
                                                                   ObjectStepIO* io, const double* w_lo, const double* w_hi,
                                                                   const int* w_obj, int n_e) {
   Earth e = fg->earth;
@@ -173,12 +173,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
   const double te0 = terrain_elev_or_zero(fg->tv, lat0, lon0), te1 = terrain_elev_or_zero(fg->tv, lat1, lon1);
   const double diff1 = re0 - te0, diff2 = sh - te1;
   StepHits hits;
-  hits.n = 0;
-  hits.finish = false;
-  if (diff1 * diff2 < 0.0) { // utils.rs:222
-    step_push(hits, diff1 / (diff1 - diff2), -1, nullptr);
-    if (fg->p.terrain_alpha == 1.0) hits.finish = true;
-  }
+  step_begin(hits, diff1 * diff2 < 0.0, diff1, diff2, fg->p.terrain_alpha == 1.0); // utils.rs:222
   // the objects this step tests, ascending: those close to either sample (utils.rs:241-250) whose height band the segment enters
   const Vec3 pos1 = as_cartesian(e, lat0, lon0, re0), pos2 = as_cartesian(e, lat1, lon1, sh);
   const LatLonTrig t0 = latlon_trig(e, lat0, lon0), t1 = latlon_trig(e, lat1, lon1);
@@ -192,27 +187,10 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
     step_object_impl(hits, fg->objects, fg->textures, j, pos1, pos2);
   }
   // emission: the counting pass of the general tracer (k_rect_trace<false>)
-  const unsigned count = io->count;
-  const uint32_t p = io->pixel;
-  if (hits.n > STEP_CANDIDATES) atomicAdd(&sk->counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
-  if (hits.n && count + (unsigned)hits.n <= (unsigned)RECT_SLOTS) {
-    uint64_t k = slot_index<SlotLayout::PixelMajor>(p, count, (size_t)fg->wl * fg->h);
-    const uint64_t k0 = k;
-    step_emit(hits, sk->slot_packed, sk->slot_step, sk->slot_pixel, k, p, io->step_index, lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length);
-    for (uint64_t q = k0; q < k; q++) rec_store(sk->slots, q, re0, pl0, sh, path_length); // terrain points: what k_rect_finalize_list needs
-  } else if (hits.n && hits.n <= STEP_CANDIDATES && sk->ovf.cap) { // beyond the slots: the step's points into the overflow arena
-    const unsigned long long base = atomicAdd(&sk->counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
-    if (base + (unsigned long long)hits.n <= sk->ovf.cap) {
-      uint64_t kk = base;
-      step_emit(hits, sk->ovf_packed, sk->ovf.step, sk->ovf.pixel, kk, p, io->step_index, lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length);
-      for (uint64_t q = base; q < kk; q++) {
-        sk->ovf.ordinal[q] = count + (unsigned)(q - base);
-        rec_store(sk->ovf, q, re0, pl0, sh, path_length);
-      }
-    }
-  }
+  step_commit_count<true>(hits, *sk, io->pixel, io->count, io->step_index, (size_t)fg->wl * fg->h,
+                          StepGeom{lat0, lon0, re0, d0, pl0, lat1, lon1, sh, sx, path_length});
   atomicAdd(&sk->counters[CTR_OBJECT_STEPS], 1ull); // statistics (atmrt_last_stats().object_steps)
-  io->count = count + (unsigned)hits.n;
+  io->count += (unsigned)hits.n;
   io->finish = hits.finish ? 1 : 0;
   io->diff1 = diff2;
 }
@@ -247,7 +225,7 @@ struct MarchSinks {
   uint32_t n_list;
   // MODE 3: copies of the frame and of the tracer's arenas in HBM, for the out-of-line object step (object_step_impl)
   const Frame* frame_dev;
-  const ObjectStepSinks* step_sinks_dev;
+  const StepSinks* step_sinks_dev;
 };
 
 // Pixel p of the frame -> its ray: direction and elevation angle, geodesic calculator, stepper at the observer
@@ -936,6 +914,7 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
     rect_ray_setup(f, e, p, alt, direction, elevation, c, s);
     unsigned count = 0;
     uint64_t k = FILL ? hit_offset[p] : 0;
+    const StepSinks sinks{packed, rec, list_step, list_pixel, ovf, ovf_packed, counters};
     if (!(0.0 > max_dist || alt < -1000.0)) {
       double lat0, lon0;
       coords_at_step(f, e, c, 0, 0.0, lat0, lon0);
@@ -983,9 +962,6 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
             if (chi[q] >= sx) x_wake = clo[q] < x_wake ? clo[q] : x_wake;
         }
         steps++;
-        StepHits hits;
-        hits.n = 0;
-        hits.finish = false;
         double diff1 = have0 ? re0 - te0 : 1.0, diff2 = have1 ? sh_ - te1 : 1.0;
         const bool crossing = diff1 * diff2 < 0.0;
         // the objects this step tests, ascending: union of the close lists of its two samples (utils.rs:241-250)
@@ -1013,10 +989,8 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
           diff1 = re0 - te0;
           diff2 = sh_ - te1;
         }
-        if (crossing) {
-          step_push(hits, diff1 / (diff1 - diff2), -1, nullptr);
-          if (terrain_opaque) hits.finish = true;
-        }
+        StepHits hits;
+        step_begin(hits, crossing, diff1, diff2, terrain_opaque);
         Vec3 pos1 = v3(0.0, 0.0, 0.0), pos2 = pos1;
         LatLonTrig t0{}, t1{};
         if (any_object) {
@@ -1037,39 +1011,9 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
           }
         };
         if (any_object) for_each_object([&](int j) { step_object(hits, f, j, pos1, pos2); });
-        if (!FILL) {
-          k = slot_index<SlotLayout::PixelMajor>(p, count, (size_t)f.wl * f.h);
-          if (hits.n > STEP_CANDIDATES) atomicAdd(&counters[CTR_BIG_STEPS], 1ull); // the fill pass will need Workspace::step_prop
-        }
-        if (FILL && hits.n > STEP_CANDIDATES) { // big step: produce the points again, straight into the list, and sort them there
-          const StepGeom g{lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx, path_length};
-          const uint64_t k0 = k;
-          if (crossing) big_step_put(packed, step_prop, k++, diff1 / (diff1 - diff2), nullptr, g);
-          for_each_object([&](int j) { big_step_object(packed, step_prop, k, f, j, pos1, pos2, g); });
-          big_step_sort(packed, step_prop, k0, hits.n);
-          for (uint64_t q = k0; q < k; q++) {
-            list_step[q] = (uint32_t)(i - 1);
-            list_pixel[q] = (uint32_t)p;
-            rec_store(rec, q, re0, pl0, sh_, path_length);
-          }
-        } else if (hits.n && (FILL || count + (unsigned)hits.n <= (unsigned)RECT_SLOTS)) {
-          uint64_t k0 = k;
-          step_emit(hits, packed, list_step, list_pixel, k, (uint32_t)p, i - 1, lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx,
-                    path_length);
-          for (uint64_t q = k0; q < k; q++) rec_store(rec, q, re0, pl0, sh_, path_length); // terrain points: what k_rect_finalize_list needs
-        }
-        else if (!FILL && hits.n && hits.n <= STEP_CANDIDATES && ovf.cap) { // beyond the slots: the step's points into the overflow arena
-          const unsigned long long base = atomicAdd(&counters[CTR_OVERFLOW_RECORDS], (unsigned long long)hits.n);
-          if (base + (unsigned long long)hits.n <= ovf.cap) {
-            uint64_t kk = base;
-            step_emit(hits, ovf_packed, ovf.step, ovf.pixel, kk, (uint32_t)p, i - 1, lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx,
-                      path_length);
-            for (uint64_t q = base; q < kk; q++) {
-              ovf.ordinal[q] = count + (unsigned)(q - base);
-              rec_store(ovf, q, re0, pl0, sh_, path_length);
-            }
-          }
-        }
+        const StepGeom g{lat0, lon0, re0, d0, pl0, lat1, lon1, sh_, sx, path_length};
+        if (FILL) step_commit_fill<true>(hits, sinks, step_prop, k, (uint32_t)p, i - 1, g, crossing, diff1, diff2, f, pos1, pos2, for_each_object);
+        else step_commit_count<true>(hits, sinks, (uint32_t)p, count, i - 1, plane, g);
         count += (unsigned)hits.n;
         if (hits.finish) break;
         lat0 = lat1; lon0 = lon1; te0 = te1; re0 = sh_; d0 = sx; pl0 = path_length;
@@ -1191,19 +1135,19 @@ void launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes&
   size_t n = (size_t)f.wl * f.h;
   RectRec slots = carve_rec(ws.slot_rec, n * RECT_SLOTS);
   // the frame and the tracer's arenas where the out-of-line object step can address them (object_step_impl): copies in HBM
-  ObjectStepSinks sinks{};
-  sinks.slot_packed = ws.slot_packed;
-  sinks.slots = slots;
-  sinks.slot_step = ws.slot_step;
-  sinks.slot_pixel = ws.slot_pixel;
+  StepSinks sinks{};
+  sinks.packed = ws.slot_packed;
+  sinks.rec = slots;
+  sinks.step = ws.slot_step;
+  sinks.pixel = ws.slot_pixel;
   sinks.ovf = trace_overflow_arena(ws);
   sinks.ovf_packed = ws.overflow_packed;
   sinks.counters = (unsigned long long*)ws.counters;
   Frame* frame_dev;
-  ObjectStepSinks* sinks_dev;
+  StepSinks* sinks_dev;
   Carve ctx(ws.step_ctx); // the layout run_core reserves
   ctx(frame_dev, sizeof(Frame));
-  ctx(sinks_dev, OBJECT_STEP_SINKS_MAX_BYTES);
+  ctx(sinks_dev, STEP_SINKS_MAX_BYTES);
   (void)hipMemcpyAsync(frame_dev, &f, sizeof f, hipMemcpyHostToDevice, stream);
   (void)hipMemcpyAsync(sinks_dev, &sinks, sizeof sinks, hipMemcpyHostToDevice, stream);
   (void)hipStreamSynchronize(stream); // both sources are on this stack frame

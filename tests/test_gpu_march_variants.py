@@ -6,7 +6,10 @@ opaque terrain take by default and ATMRT_MARCH_VARIANT=sliced forces for translu
 size and kind of the launch (atmrt_kernels.h march_slice_layout, atmrt_march_impl.h ATMRT_LAUNCH_MARCH).  Every test frame below
 4 Mpixel runs the second or third, so this test forces each variant in a child process (ATMRT_MARCH_VARIANT is read once per process) and requires
 the same bits from all for opaque, translucent and object scenes; the opaque scene comes in a second size whose pixel count is not
-a multiple of a workgroup, and with a step that gives rays of 18 slices."""
+a multiple of a workgroup, and with a step that gives rays of 18 slices.  The last scene, `nested`, is the one of
+test_gpu_parity.py::test_more_trace_points_in_one_step_than_the_step_list at its Rectilinear size: steps of up to 41 trace points, so
+that the plain variant takes the general tracer's own counting pass (k_rect_trace<false>) through a big step and through steps of
+five or more points that go to the overflow arena; its result carries the frame's big_steps."""
 import hashlib
 import json
 import os
@@ -22,12 +25,15 @@ import hashlib, json, sys
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 import numpy as np
 from atm_raytracer_amd import generators, synth
-from util import run_gpu, FIELDS_PIXEL, FIELDS_HIT, bits, frame_stats
+from util import run_gpu, FIELDS_PIXEL, FIELDS_HIT, bits, frame_stats, nested_cylinders
 ctx = generators.Context(0)
 out = {{}}
 for name, kw, objects, size in (("opaque", dict(), False, (160, 96)), ("translucent", dict(terrain_alpha=0.5), False, (160, 96)),
-                                ("objects", dict(terrain_alpha=0.5), True, (160, 96)), ("opaque-ragged", dict(step=26.0), False, (150, 61))):
-    cfg, tiles = synth.scene("S2", size[0], size[1], generator="Rectilinear", max_distance=60_000.0, tilt=-1.0, **kw)
+                                ("objects", dict(terrain_alpha=0.5), True, (160, 96)), ("opaque-ragged", dict(step=26.0), False, (150, 61)),
+                                ("nested", dict(terrain_alpha=0.5, max_distance=20_000.0, tilt=3.0, fov=8.0), False, (40, 24))):
+    cfg, tiles = synth.scene("S2", size[0], size[1], generator="Rectilinear", **{{**dict(max_distance=60_000.0, tilt=-1.0), **kw}})
+    if name == "nested":
+        nested_cylinders(cfg, 20)
     if objects:
         synth.add_objects(cfg, n_cyl=40, n_bill=10, dist=(300.0, 20_000.0), spread_deg=30.0, radius=(30.0, 120.0), height=(150.0, 600.0),
                           bill_w=(150.0, 500.0), bill_h=(150.0, 500.0))
@@ -36,6 +42,8 @@ for name, kw, objects, size in (("opaque", dict(), False, (160, 96)), ("transluc
     for k in FIELDS_PIXEL + FIELDS_HIT:
         h.update(np.ascontiguousarray(bits(r[k])).tobytes())
     out[name] = [h.hexdigest(), int(r["n_hits"]), int(r["ray_steps"]), int(frame_stats(ctx)["retraced_pixels"])]
+    if name == "nested":
+        out[name].append(int(frame_stats(ctx)["big_steps"]))
 print("RESULT " + json.dumps(out))
 """
 
@@ -59,6 +67,7 @@ def test_all_march_variants_produce_the_same_frames():
     assert plain == small == sliced == default
     assert plain["opaque"][1] > 1000 and plain["translucent"][1] > plain["opaque"][1] and plain["objects"][1] > 0
     assert plain["opaque-ragged"][1] > 500
+    assert plain["nested"][-1] > 0, "the nested scene must have big steps"
     # Trace points beyond a pixel's four slots travel through the overflow arena; with an arena of 4 records (or none) they come
     # from a second pass over those pixels instead — the route of rounds 1-2, still the fall-back.  Same bits.
     assert plain["translucent"][3] > 4 and plain["objects"][3] > 4, "the scenes must have pixels beyond the slots"

@@ -23,6 +23,21 @@ def frame_stats(ctx):
     return {k: getattr(t, k) for k, _ in _abi.FrameStats._fields_}
 
 
+def nested_cylinders(cfg, n, lat=46.53, lon=8.5, r0=4.0, dr=3.0, alpha=0.5):
+    """n concentric translucent cylinders on one spot: a ray through them collects up to 2 n points inside ONE 100 m step."""
+    from atm_raytracer_amd import _abi
+    objs = []
+    for i in range(n):
+        o = _abi.Object()
+        o.kind, o.r1, o.r2, o.height = _abi.OBJ_FRUSTUM, r0 + dr * i, r0 + dr * i, 900.0
+        o.position.latitude, o.position.longitude = lat, lon
+        o.position.altitude_kind, o.position.altitude = _abi.ALT_RELATIVE, 0.0
+        o.color[0], o.color[1], o.color[2], o.color[3] = 0.1 + 0.04 * i, 0.9 - 0.04 * i, 0.5, alpha
+        objs.append(o)
+    cfg.objects = objs
+    return cfg
+
+
 def run_oracle(oracle, cfg, tiles, n_threads=0, rows=None):
     t = oracle.terrain_new(tiles)
     try:
