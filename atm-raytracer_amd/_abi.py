@@ -230,7 +230,7 @@ ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_siz
 class Timings(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("profile_ms", C.c_double), ("paths_ms", C.c_double), ("intersect_ms", C.c_double),
                 ("march_ms", C.c_double), ("finalize_ms", C.c_double), ("pack_ms", C.c_double), ("ray_steps", C.c_uint64),
-                ("n_hits", C.c_uint64)]
+                ("n_hits", C.c_uint64), ("ceiling_ms", C.c_double)]
 
 
 class FrameStats(C.Structure):

@@ -680,6 +680,52 @@ static bool step_trig_enabled() {
   return !(e && !strcmp(e, "off"));
 }
 
+// ATMRT_CEILING=off: no terrain ceiling table (Frame::ceil), the march runs on the mosaic's top alone; =rebuild: the table is built
+// again in every frame, as for an observer that moves from frame to frame (A/B runs, tests/test_gpu_ceiling.py).  Read at every frame.
+static int ceiling_mode() {
+  const char* e = getenv("ATMRT_CEILING");
+  return !e ? 1 : !strcmp(e, "off") ? 0 : !strcmp(e, "rebuild") ? 2 : 1;
+}
+
+// Frame::ceil for `f` (complete but for the three ceiling fields): the cached table, or a new one built on the frame's stream
+static int prepare_ceiling(atmrt_ctx* c, Frame& f) {
+  c->ceil_built = false;
+  f.ceil = nullptr;
+  f.ceil_layout = CeilLayout{};
+  f.ceil_floor = INFINITY;
+  const int mode = ceiling_mode();
+  const atmrt_params_t& p = f.p;
+  if (!mode || p.generator != ATMRT_GEN_RECTILINEAR || c->earth.calc != 2 || f.march_steps < 1 || f.wl < 1 || f.h < 1) return ATMRT_OK;
+  const atmrt_ctx::CeilLayoutKey lk{p.frame.direction, p.frame.fov, p.frame.tilt, (int32_t)p.width, (int32_t)p.height, f.c0, f.wl};
+  if (!c->ceil_layout_valid || memcmp(&lk, &c->ceil_layout_key, sizeof lk) != 0) {
+    c->ceil_layout = ceiling_layout(p, f.ph, f.c0, f.wl, f.h);
+    c->ceil_layout_key = lk;
+    c->ceil_layout_valid = true;
+  }
+  f.ceil_layout = c->ceil_layout;
+  const atmrt_ctx::CeilKey key{c->terrain_uploaded, p.position.latitude, p.position.longitude, p.simulation_step, p.frame.max_distance,
+                               c->earth, c->ceil_layout, f.march_steps, f.xs_sin ? 1 : 0};
+  const size_t entries = ((size_t)f.march_steps + 1) * (size_t)(f.ceil_layout.n_bins + 1);
+  if (mode == 2 || !c->ceil_valid || memcmp(&key, &c->ceil_key, sizeof key) != 0) {
+    c->ceil_valid = false;
+    HIP_TRY(c, c->d_ceil.reserve(entries * sizeof(CeilEntry)));
+    HIP_TRY(c, hipEventRecord(c->ev[10], c->stream));
+    launch_ceiling(f, c->d_ceil.as<CeilEntry>(), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[11], c->stream));
+    c->ceil_key = key;
+    c->ceil_valid = true;
+    c->ceil_built = true;
+  }
+  f.ceil = c->d_ceil.as<CeilEntry>();
+  // the certificate's part of the escape floor (Frame::esc_floor is the same rule over the mosaic's top)
+  if (escape_enabled()) {
+    if (p.straight_rays) f.ceil_floor = -INFINITY;
+    else if (c->earth.spherical) f.ceil_floor = c->ceil_from + p.simulation_step;
+  }
+  return ATMRT_OK;
+}
+
 extern "C" int atmrt_escape_certificate(const atmrt_atmosphere_t* atmosphere, double wavelength, int32_t spherical, double radius,
                                         int32_t straight, double simulation_step, double top, double out[3]) {
   if (!atmosphere || !out) return ATMRT_ERR_INVALID_ARGUMENT;
@@ -797,6 +843,8 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
     c->esc_bound = worst;
     c->esc_valid = true;
   }
+  // the same certificate from the lowest value an entry of the terrain ceiling table can have (1 m) minus a step
+  if (atm_fresh) c->ceil_from = escape_certified_from(c->atm.table(), c->earth.shape_radius, 1.0 - p.simulation_step, nullptr);
   f.esc_floor = INFINITY;
   f.esc_ang_max = INFINITY;
   if (escape_enabled() && p.generator == ATMRT_GEN_RECTILINEAR) {
@@ -823,6 +871,8 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   f.atm_cubic = atm_has_cubic(c->atm.table()) ? 1 : 0;
   f.di0 = f.ei0 = 0;
   f.dir_step = f.elev_step = 0.0;
+  rc = prepare_ceiling(c, f);
+  if (rc) return rc;
   *out = f;
   return ATMRT_OK;
 }
@@ -1086,6 +1136,10 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
     t.pack_ms = v;
     t.ray_steps = counters[CTR_RAY_STEPS];
     t.n_hits = counters[CTR_HITS];
+    if (c->ceil_built) {
+      HIP_TRY(c, hipEventElapsedTime(&v, ev[10], ev[11]));
+      t.ceiling_ms = v;
+    }
     c->timings = t;
   }
   if (counters[CTR_SLICE_UNFINISHED])

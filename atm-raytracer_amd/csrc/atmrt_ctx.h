@@ -107,7 +107,7 @@ struct atmrt_ctx {
   int device = 0;
   hipStream_t stream = nullptr, stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-  hipEvent_t ev[10] = {};
+  hipEvent_t ev[12] = {};                      // [10], [11]: around the build of the terrain ceiling table (timings.ceiling_ms)
   hipEvent_t ev_seg[atmrt::FAST_SEGMENTS] = {}; // a path segment is integrated (stream2) -> its intersect scan may start
   hipEvent_t ev_scan[2 * atmrt::FAST_SEGMENTS] = {}; // begin / end of every scan segment (after its wait), for intersect_ms
   int scan_segments = 0;                       // segments of the last pipelined frame (0: ev[4]..ev[5] time the scan)
@@ -148,6 +148,24 @@ struct atmrt_ctx {
   double trig_radius = 0.0;
   int32_t trig_fast_div = 0;
   bool trig_valid = false;
+  // The terrain ceiling table in d_ceil (Frame::ceil, atmrt_ceiling.h) and what it was built from (prepare_ceiling): the mosaic,
+  // the observer's place (not its altitude), the earth model, the distance table and the bins.  ceil_from: the certificate's
+  // lowest altitude for the lowest value a table entry can have (1 m), kept beside esc_from under the same atmosphere key.
+  struct CeilKey {
+    uint64_t terrain;
+    double lat, lon, step, max_distance;
+    atmrt::Earth earth;
+    atmrt::CeilLayout layout;
+    int32_t march_steps, trig;
+  } ceil_key{};
+  struct CeilLayoutKey { // what the bins follow from: the frame's directions and its column shard
+    double direction, fov, tilt;
+    int32_t width, height, c0, wl;
+  } ceil_layout_key{};
+  atmrt::CeilLayout ceil_layout{};
+  bool ceil_valid = false, ceil_layout_valid = false;
+  bool ceil_built = false; // this frame built the table: ev[10] .. ev[11] hold its time
+  double ceil_from = 0.0;
 
   // last generated frame (for atmrt_draw_image)
   bool last_valid = false, last_packed = false;
@@ -174,6 +192,7 @@ struct atmrt_ctx {
   // ... it survives the frame
   atmrt::DevBuf d_xs, d_atm;               // the distance table and the compiled atmosphere: uploaded when their inputs change
   atmrt::DevBuf d_xs_trig;                 // Spherical calculator: sin, then cos, of xs[0 .. march_steps] / calc_radius (k_step_trig): rebuilt when xs, the radius or EARTH_FAST_DIV change
+  atmrt::DevBuf d_ceil;                    // Spherical calculator, Rectilinear: the terrain ceiling table, (march_steps + 1) x (bins + 1) entries: rebuilt when ceil_key changes
   atmrt::DevBuf d_alt;                     // the observer's altitude (k_resolve): atmrt_draw_overlay* samples the atmosphere there
   atmrt::DevBuf d_objects, d_textures;     // the scene: textures are uploaded when the objects change
   atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last_dense, last_hits, last_offset): draw, overlay, hits

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "atmrt_core.h"
+#include "atmrt_ceiling.h"
 #include "atmrt_objects.h"
 
 namespace atmrt {
@@ -46,6 +47,14 @@ struct Frame {
   // dividing and reducing again (coords_at_step).  Null for the other calculators and under ATMRT_STEP_TRIG=off.
   const double* xs_sin;
   const double* xs_cos;
+  // The terrain ceiling table (atmrt_ceiling.h): rows 0 .. march_steps of ceil_layout.n_bins + 1 entries.  A sample
+  // of the lean march above its cell skips its lookup; a ray above max(its suffix, ceil_floor) that is ascending leaves.
+  // ceil_floor is the certificate's part of that floor: the lowest certified altitude + one step (refracted rays on a sphere),
+  // -inf (straight rays) or +inf (no escape).  Null for the other calculators and generators and under ATMRT_CEILING=off: the march
+  // then runs on skip_above and esc_floor alone.
+  const CeilEntry* ceil;
+  CeilLayout ceil_layout;
+  double ceil_floor;
 };
 
 // column azimuth / row elevation in degrees, as handed to gen_terrain_cache / gen_path_cache
@@ -527,6 +536,8 @@ void launch_ray_paths(const Frame& f, double h0, size_t n_angles, const double* 
 void launch_atm_sample(const Frame& f, size_t n, const double* alt, double* t, double* p, double* nidx, double* dn,
                        hipStream_t stream);
 void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, double* c, hipStream_t stream);
+// fills f.ceil (rows 0 .. f.march_steps) for f.ceil_layout: the cells, then every bin's suffix maxima
+void launch_ceiling(const Frame& f, CeilEntry* table, hipStream_t stream);
 void launch_math_probe(int op, size_t n, const double* a, const double* b, double* out0, double* out1, hipStream_t stream);
 void launch_coords_at_dist(const Frame& f, double lat0, double lon0, double dir, size_t n, const double* dist,
                            double* lat, double* lon, hipStream_t stream);

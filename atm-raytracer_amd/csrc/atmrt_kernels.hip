@@ -1454,6 +1454,56 @@ void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, dou
   if (n) hipLaunchKernelGGL(k_step_trig, dim3(cdiv(n, 256)), dim3(256), 0, stream, e, n, xs, s, c);
 }
 
+// Frame::ceil, the terrain ceiling table (atmrt_ceiling.h).  One thread per step i and bin j: the geodesic points of the bin's two
+// edge directions at xs[i], by the code a ray of the march runs (dircalc_new on the direction in degrees, coords_at_step), and the
+// cover of the arc between them.  Neighbouring threads are neighbouring bins of one step: their boxes share posts.  The thread of
+// bin 0 also writes the row's entry n_bins, the one of the rays outside the bins: the mosaic's top.
+__global__ __launch_bounds__(256) void k_ceiling_cells(Frame f, CeilEntry* __restrict__ table) {
+  const CeilLayout L = f.ceil_layout;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t rows = (size_t)f.march_steps + 1;
+  if (t >= rows * (size_t)L.n_bins) return;
+  const int i = (int)(t / (size_t)L.n_bins), j = (int)(t % (size_t)L.n_bins);
+  Earth e = f.earth;
+  e.calc = 2;
+  double d_lo, d_hi, lat0, lon0, lat1, lon1;
+  ceiling_bin_edges(L, j, d_lo, d_hi);
+  const double dist = f.xs[i];
+  DirCalc c;
+  dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(d_lo), c);
+  coords_at_step(f, e, c, i, dist, lat0, lon0);
+  dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(d_hi), c);
+  coords_at_step(f, e, c, i, dist, lat1, lon1);
+  CeilEntry* row = table + (size_t)i * (size_t)(L.n_bins + 1);
+  row[j].cell = ceiling_cell(f.tv, L, e.calc_radius, lat0, lon0, lat1, lon1, dist);
+  if (j == 0) row[L.n_bins] = CeilEntry{(float)f.tv.skip_above, (float)f.tv.skip_above};
+}
+// suffix[i][j] = max of cell[i'][j] over i' >= i: one wavefront per bin, every lane a run of consecutive steps — the maximum of its
+// run, a suffix scan of the 64 maxima across the wavefront, then the run again from its end downwards
+__global__ __launch_bounds__(64) void k_ceiling_suffix(CeilEntry* __restrict__ table, int rows, int stride) {
+  CeilEntry* col = table + blockIdx.x;
+  const int lane = threadIdx.x, run = (rows + 63) / 64;
+  const int i0 = lane * run, i1 = i0 + run < rows ? i0 + run : rows;
+  float m = 0.f;
+  for (int i = i0; i < i1; i++) m = fmaxf(m, col[(size_t)i * stride].cell);
+  for (int off = 1; off < 64; off <<= 1) { // inclusive: the maximum of the lanes lane ... 63
+    const float o = __shfl_down(m, off, 64);
+    if (lane + off < 64) m = fmaxf(m, o);
+  }
+  float above = __shfl_down(m, 1, 64); // of the runs behind this lane's
+  if (lane == 63) above = 0.f;
+  for (int i = i1 - 1; i >= i0; i--) {
+    above = fmaxf(above, col[(size_t)i * stride].cell);
+    col[(size_t)i * stride].suffix = above;
+  }
+}
+void launch_ceiling(const Frame& f, CeilEntry* table, hipStream_t stream) {
+  const size_t rows = (size_t)f.march_steps + 1, n = rows * (size_t)f.ceil_layout.n_bins;
+  if (!n) return;
+  hipLaunchKernelGGL(k_ceiling_cells, dim3(cdiv(n, 256)), dim3(256), 0, stream, f, table);
+  hipLaunchKernelGGL(k_ceiling_suffix, dim3((unsigned)f.ceil_layout.n_bins), dim3(64), 0, stream, table, (int)rows, f.ceil_layout.n_bins + 1);
+}
+
 // detmath.h element-wise (atmrt_math_probe): the GPU's instruction sequences against the host's on arbitrary operands
 __global__ void k_math_probe(int op, size_t n, const double* __restrict__ a, const double* __restrict__ b,
                              double* __restrict__ out0, double* __restrict__ out1) {

@@ -375,14 +375,20 @@ static __device__ __forceinline__ void crossing_store(const Frame& f, const Marc
 // small-launch variant of k_rect_march (the priority ladder; object steps out of line, as in the slices).
 template <int MODE, int CALC, bool CUBIC, bool SLICED, bool DRAIN>
 static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Earth& e, const DirCalc& c, MarchRay& r, MarchCount& n, int i0, int slice,
-                                                       const MarchSinks& sinks, unsigned long long* counters, size_t p, WaveList& wl) {
+                                                       const MarchSinks& sinks, unsigned long long* counters, size_t p, WaveList& wl, int bin) {
   const bool sph = e.spherical != 0;
   const double radius = e.shape_radius;
   const bool straight = f.p.straight_rays != 0;
   const double step = f.p.simulation_step, max_dist = f.p.frame.max_distance;
   const double skip_above = f.tv.skip_above;
   const bool opaque = f.p.terrain_alpha == 1.0; // (MODE 0 is launched over opaque terrain only, MODE 1 over translucent only)
-  const double esc_floor = MODE == 3 ? escape_floor_objects(f.esc_floor, wl.vhi, wl.n) : f.esc_floor;
+  // The terrain ceiling table (Frame::ceil), entry [i][bin] for the sample of step i: `cell` bounds the terrain under THIS sample
+  // (never above skip_above), `suffix` under this and every later sample of the ray.  With the table the escape floor is the
+  // suffix, the certificate's own lowest altitude (Frame::ceil_floor) and, MODE 3, the objects' bands; without it, Frame::esc_floor.
+  const CeilEntry* const ceil = f.ceil;
+  const unsigned ceil_stride = (unsigned)f.ceil_layout.n_bins + 1u;
+  const double floor_base = f.ceil ? f.ceil_floor : f.esc_floor;
+  const double esc_floor = MODE == 3 ? escape_floor_objects(floor_base, wl.vhi, wl.n) : floor_base;
   const int i_end = i0 + slice;
   double sx = r.s.x, lat, lon;
   for (int i = i0 + 1;; i++) {
@@ -391,6 +397,15 @@ static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Ear
       if (band == 1) __builtin_amdgcn_s_setprio(2);
       else if (band == 2) __builtin_amdgcn_s_setprio(1);
       else if (band == 3) __builtin_amdgcn_s_setprio(0);
+    }
+    // this step's entry of the table, asked for ahead of the RK4 stages that hide its latency (one 8-byte load per lane; the rays
+    // of a wavefront are in step, so the row is wave-uniform, and their bins are a handful of neighbours: one or two cache lines)
+    double skip_i = skip_above, floor_i = esc_floor;
+    if (ceil) {
+      const int iu = SLICED ? __builtin_amdgcn_readfirstlane(i) : i;
+      const CeilEntry ce = ceil[(size_t)(iu < f.march_steps ? iu : f.march_steps) * ceil_stride + (unsigned)bin];
+      skip_i = (double)ce.cell;
+      floor_i = (double)ce.suffix > esc_floor ? (double)ce.suffix : esc_floor;
     }
     bool tame;
     RayState nx = stepper_next<CUBIC>(r.s, *f.atm, sph, radius, straight, step, tame);
@@ -428,7 +443,7 @@ static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Ear
     // the lookup are skipped and any positive number stands for the difference.  Wavefronts are 64 columns of one row: sky
     // rows leave the terrain's height range together.  NaN heights take the full path.
     double diff1 = 1.0;
-    if (!(r.sh > skip_above)) {
+    if (!(r.sh > skip_i)) {
       // sx = xs[i]: r.s.x starts at 0 (or at xs[i0], slice_save) and only ever advances by x + step (stepper_next_with), the
       // additions of the table.  The rays of a wavefront march in step, so i is the same in every lane; a later slice reads its i0
       // from the group's state (a vector register: every ray still marching was saved with the same step), hence the readfirstlane
@@ -446,7 +461,7 @@ static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Ear
       r.count++;
       if (opaque) return MARCH_ENDED; // utils.rs:237-239, 283-285
     }
-    if (escapes(f, r.s, straight, r.sh, r.re0, esc_floor)) { // nothing left to find: credit the rest of the march and leave
+    if (escapes(f, r.s, straight, r.sh, r.re0, floor_i)) { // nothing left to find: credit the rest of the march and leave
       n.esc_credit = f.march_steps - i;
       if (n.esc_credit >= 0) n.steps += (unsigned)n.esc_credit;
       return MARCH_ENDED;
@@ -510,11 +525,12 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
     DirCalc c;
     MarchRay r;
     rect_ray_setup(f, e, p, alt, direction, elevation, c, r.s);
+    const int bin = f.ceil ? ceiling_bin(f.ceil_layout, direction) : 0;
     r.k = MODE == 2 ? sinks.hit_offset[p] : 0;
     WaveList wl = lists.wave(threadIdx.x >> 6);
     bool object_ray = MODE == 3 && !wave_list_build<CALC>(f, e, c, wl); // MODE 3: this ray is left to the general tracer
     if (!object_ray && march_begin(f, e, c, alt, r, n))
-      object_ray = march_steps<MODE, CALC, CUBIC, false, DRAIN>(f, e, c, r, n, 0, 0, sinks, counters, p, wl) == MARCH_GIVEN_UP;
+      object_ray = march_steps<MODE, CALC, CUBIC, false, DRAIN>(f, e, c, r, n, 0, 0, sinks, counters, p, wl, bin) == MARCH_GIVEN_UP;
     if (MODE == 3 && object_ray) { // nothing of this ray counts: k_rect_trace starts it again
       out.hit_count[p] = OBJECT_RAY;
       sinks.hit_step[p] = 1;
@@ -643,11 +659,12 @@ __global__ __launch_bounds__(256, ATMRT_SLICE_WAVES) void k_rect_march_first(Fra
     DirCalc c;
     MarchRay r;
     rect_ray_setup(f, e, p, alt, direction, elevation, c, r.s);
+    const int bin = f.ceil ? ceiling_bin(f.ceil_layout, direction) : 0;
     store_ray_angles(out, p, direction, elevation);
     WaveList wl = lists.wave(threadIdx.x >> 6);
     const bool object_ray = MODE == 3 && !wave_list_build<CALC>(f, e, c, wl); // MODE 3: the wavefront's rays go to the tracer
     if (!object_ray && march_begin(f, e, c, alt, r, n))
-      alive = march_steps<MODE, CALC, CUBIC, true, false>(f, e, c, r, n, 0, slice, sinks, counters, p, wl) == MARCH_ON;
+      alive = march_steps<MODE, CALC, CUBIC, true, false>(f, e, c, r, n, 0, slice, sinks, counters, p, wl, bin) == MARCH_ON;
     if (MODE == 3 && st.glist && __any(alive)) { // the group marches on: its list and wake distance for the slices to come
       const GroupList gl = group_list(st.glist, (uint32_t)(p >> 6));
       const int lane = threadIdx.x & 63;
@@ -768,7 +785,15 @@ __global__ __launch_bounds__(64, ATMRT_SLICE_WAVES) void k_rect_march_cont(Frame
     const DirCalc c = st.calc[p];
     r.first = -1;
     r.count = MODE == 1 || MODE == 3 ? st.count[p] : 0u;
-    alive = march_steps<MODE, CALC, CUBIC, true, false>(f, e, c, r, n, i0, slice, sinks, counters, p, wl) == MARCH_ON;
+    // The ray's bin of the ceiling table is a function of its direction alone: a slice derives it again from the pixel (the
+    // pinhole arithmetic of rect_ray_setup, once per 128 steps) rather than carry it in the state.
+    int bin = 0;
+    if (f.ceil) {
+      double direction, elevation;
+      rect_ray_params(f.p, f.ph, f.c0 + (int)(p % (size_t)f.wl), (int)(p / (size_t)f.wl), direction, elevation);
+      bin = ceiling_bin(f.ceil_layout, direction);
+    }
+    alive = march_steps<MODE, CALC, CUBIC, true, false>(f, e, c, r, n, i0, slice, sinks, counters, p, wl, bin) == MARCH_ON;
     if (alive) {
       slice_save<MODE>(st, p, r, i0 + slice);
     } else {

@@ -1324,6 +1324,7 @@ int atmrt::multi_last_timings(atmrt_ctx* parent, atmrt_timings_t* out) {
     t.march_ms = std::max(t.march_ms, a.march_ms);
     t.finalize_ms = std::max(t.finalize_ms, a.finalize_ms);
     t.pack_ms = std::max(t.pack_ms, a.pack_ms);
+    t.ceiling_ms = std::max(t.ceiling_ms, a.ceiling_ms);
     t.ray_steps += a.ray_steps;
     t.n_hits += a.n_hits;
   }

@@ -268,7 +268,14 @@ typedef struct atmrt_timings {
   double pack_ms;      /* scan + packing / multi-hit fill, when requested */
   uint64_t ray_steps;
   uint64_t n_hits;
+  double ceiling_ms;   /* Rectilinear, Spherical calculator: the terrain ceiling table, when this call had to build it (else 0); it is
+                          built ahead of the frame's first launch and is not part of total_ms */
 } atmrt_timings_t;
+/* Environment switches read at every frame (A/B runs; results are the same bits either way):
+ *   ATMRT_ESCAPE=off        no ray leaves the Rectilinear march early
+ *   ATMRT_STEP_TRIG=off     no per-step sin / cos table of the Spherical geodesic
+ *   ATMRT_CEILING=off       no terrain ceiling table: the march tests every sample against the mosaic's highest post
+ *   ATMRT_CEILING=rebuild   the terrain ceiling table is built again in every frame (it is cached otherwise) */
 int atmrt_last_timings(atmrt_ctx* ctx, atmrt_timings_t* out);
 
 /* How often the last frame left the fast routes of the device path (results are the same either way; tests use this to
