@@ -481,9 +481,6 @@ extern "C" int atmrt_set_params(atmrt_ctx* c, const atmrt_params_t* p) {
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "column shard [%u, %u) outside width %u", p->col_begin, p->col_end, p->width);
   if (p->generator < 0 || p->generator > 2) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown generator %d", p->generator);
   if (!(p->wavelength > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "wavelength must be positive");
-  if (p->simulation_step != c->params.simulation_step || p->frame.max_distance != c->params.frame.max_distance ||
-      !c->have_params)
-    c->xs_dirty = true;
   // distances handed to SphericalCalc are sums of steps and interpolation points inside a step: 0 or >= ~1e-17 step
   if (e.calc_radius >= 1.0e-30 && e.calc_radius <= 1.0e30 && p->simulation_step >= 1.0e-10 && p->frame.max_distance <= 1.0e30)
     e.flat_dirs |= EARTH_FAST_DIV;
@@ -533,7 +530,7 @@ extern "C" int atmrt_objects_set(atmrt_ctx* c, const atmrt_object_t* objects, si
   }
   c->objects.swap(objs);
   c->textures.swap(pool);
-  c->objects_dirty = true;
+  c->objects_serial++;
   if (c->multi) return multi_forward(c, [objects, n](atmrt_ctx* k) { return atmrt_objects_set(k, objects, n); });
   return ATMRT_OK;
 }
@@ -689,39 +686,33 @@ static int ceiling_mode() {
 
 // Frame::ceil for `f` (complete but for the three ceiling fields): the cached table, or a new one built on the frame's stream
 static int prepare_ceiling(atmrt_ctx* c, Frame& f) {
-  c->ceil_built = false;
+  c->ceil_built = false; // for the frames that return before the table's refresh
   f.ceil = nullptr;
   f.ceil_layout = CeilLayout{};
   f.ceil_floor = INFINITY;
   const int mode = ceiling_mode();
   const atmrt_params_t& p = f.p;
   if (!mode || p.generator != ATMRT_GEN_RECTILINEAR || c->earth.calc != 2 || f.march_steps < 1 || f.wl < 1 || f.h < 1) return ATMRT_OK;
-  const atmrt_ctx::CeilLayoutKey lk{p.frame.direction, p.frame.fov, p.frame.tilt, (int32_t)p.width, (int32_t)p.height, f.c0, f.wl};
-  if (!c->ceil_layout_valid || memcmp(&lk, &c->ceil_layout_key, sizeof lk) != 0) {
-    c->ceil_layout = ceiling_layout(p, f.ph, f.c0, f.wl, f.h);
-    c->ceil_layout_key = lk;
-    c->ceil_layout_valid = true;
-  }
-  f.ceil_layout = c->ceil_layout;
-  const atmrt_ctx::CeilKey key{c->terrain_uploaded, p.position.latitude, p.position.longitude, p.simulation_step, p.frame.max_distance,
-                               c->earth, c->ceil_layout, f.march_steps, f.xs_sin ? 1 : 0};
-  const size_t entries = ((size_t)f.march_steps + 1) * (size_t)(f.ceil_layout.n_bins + 1);
-  if (mode == 2 || !c->ceil_valid || memcmp(&key, &c->ceil_key, sizeof key) != 0) {
-    c->ceil_valid = false;
-    HIP_TRY(c, c->d_ceil.reserve(entries * sizeof(CeilEntry)));
-    HIP_TRY(c, hipEventRecord(c->ev[10], c->stream));
+  (void)c->bins.refresh({bits(p.frame.direction), bits(p.frame.fov), bits(p.frame.tilt), (int32_t)p.width, (int32_t)p.height, f.c0, f.wl}, [&](CeilLayout& l) {
+    l = ceiling_layout(p, f.ph, f.c0, f.wl, f.h);
+    return 0;
+  });
+  f.ceil_layout = c->bins.value();
+  const CeilKey key{c->terrain_uploaded, c->steps.serial(), bits(p.position.latitude), bits(p.position.longitude), key_of(c->earth), key_of(f.ceil_layout), f.xs_sin ? 1 : 0};
+  const int rc = c->ceiling.refresh(key, [&](Nothing&) {
+    HIP_TRY(c, c->d_ceil.reserve(((size_t)f.march_steps + 1) * (size_t)(f.ceil_layout.n_bins + 1) * sizeof(CeilEntry)));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_CEIL_BEGIN], c->stream));
     launch_ceiling(f, c->d_ceil.as<CeilEntry>(), c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev[11], c->stream));
-    c->ceil_key = key;
-    c->ceil_valid = true;
-    c->ceil_built = true;
-  }
+    HIP_TRY(c, hipEventRecord(c->ev[EV_CEIL_END], c->stream));
+    return 0;
+  }, mode == 2, &c->ceil_built);
+  if (rc) return rc;
   f.ceil = c->d_ceil.as<CeilEntry>();
   // the certificate's part of the escape floor (Frame::esc_floor is the same rule over the mosaic's top)
   if (escape_enabled()) {
     if (p.straight_rays) f.ceil_floor = -INFINITY;
-    else if (c->earth.spherical) f.ceil_floor = c->ceil_from + p.simulation_step;
+    else if (c->earth.spherical) f.ceil_floor = c->atm.value().ceil_from + p.simulation_step;
   }
   return ATMRT_OK;
 }
@@ -741,110 +732,111 @@ extern "C" int atmrt_escape_certificate(const atmrt_atmosphere_t* atmosphere, do
 // ---------------------------------------------------------------------------------------------
 // frame set-up
 // ---------------------------------------------------------------------------------------------
+// The products a frame is set up from (atmrt_ctx.h), one function each; prepare_frame refreshes sources before their dependents.
+// The distance table by repeated addition, exactly like `distance += step` (utils.rs:191-196) and the stepper's x;
+// n_t = #{k: xs[k] < max}; the path cache gets one element more than the first k whose PREVIOUS x exceeds max (utils.rs:160-170)
+static int refresh_steps(atmrt_ctx* c, const atmrt_params_t& p) {
+  return c->steps.refresh({bits(p.simulation_step), bits(p.frame.max_distance)}, [&](Steps& t) {
+    t.xs.clear();
+    t.n_t = 0;
+    for (double d = 0.0;; d += p.simulation_step) {
+      t.xs.push_back(d);
+      if (d < p.frame.max_distance) t.n_t++;
+      const size_t k = t.xs.size() - 1; // index of d
+      if (k >= 1 && t.xs[k - 1] > p.frame.max_distance) break;
+      if (t.xs.size() > 5000000) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "distance table too long");
+    }
+    t.march_steps = 0;
+    for (size_t k = 1; k < t.xs.size(); k++) // the march's own rule: step k is taken while x_k <= max_distance (rectilinear.rs:178)
+      if (t.xs[k] <= p.frame.max_distance) t.march_steps = (int)k;
+      else break;
+    t.n_path_cap = (int)t.xs.size();
+    HIP_TRY(c, c->d_xs.reserve(t.xs.size() * sizeof(double)));
+    HIP_TRY(c, hipMemcpy(c->d_xs.ptr, t.xs.data(), t.xs.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+  });
+}
+
+// The Spherical calculator's sin / cos of xs[k] / calc_radius, by the device code the samples would run (k_step_trig): like xs they
+// depend on nothing of the ray or the observer and survive the frame.  The kernels of this frame follow on the same stream.
+static int refresh_trig(atmrt_ctx* c) {
+  const size_t n = (size_t)c->steps.value().march_steps + 1;
+  return c->trig.refresh({c->steps.serial(), bits(c->earth.calc_radius), c->earth.flat_dirs & EARTH_FAST_DIV}, [&](Nothing&) {
+    HIP_TRY(c, c->d_xs_trig.reserve(2 * n * sizeof(double)));
+    launch_step_trig(c->earth, n, c->d_xs.as<double>(), c->d_xs_trig.as<double>(), c->d_xs_trig.as<double>() + n, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+  });
+}
+
+// The compiled table and its certificates: hosts set the same atmosphere before every frame (the Python mirror does), and the
+// certificate's bisections are a quarter of a millisecond of host time — a twentieth of a Fast frame.
+static int refresh_atm(atmrt_ctx* c, const atmrt_params_t& p) {
+  return c->atm.refresh({c->atm_def_serial, bits(p.wavelength), bits(p.simulation_step), bits(c->earth.shape_radius), c->earth.spherical}, [&](Atm& a) {
+    if (atm_compile(c->atm_def.pod, p.wavelength, a.table)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "invalid atmosphere");
+    AtmTable& t = a.table.table();
+    atm_certify(t, c->earth.spherical != 0, c->earth.shape_radius, p.simulation_step);
+    if (getenv("ATMRT_NO_TIGHT")) // experiments: the voting path of dm_div3 on every segment (same bits, tests/test_gpu_march_variants.py)
+      for (int k = 0; k < t.n; k++) {
+        t.seg(k).flags &= ~ATM_SEG_TIGHT;
+        t.seg(k).tight_lo = INFINITY, t.seg(k).tight_hi = -INFINITY;
+      }
+    // the escape certificate from the lowest value an entry of the terrain ceiling table can have (1 m) minus a step
+    a.ceil_from = escape_certified_from(t, c->earth.shape_radius, 1.0 - p.simulation_step, nullptr);
+    HIP_TRY(c, c->d_atm.reserve(a.table.bytes()));
+    HIP_TRY(c, hipMemcpy(c->d_atm.ptr, &t, a.table.bytes(), hipMemcpyHostToDevice));
+    return 0;
+  });
+}
+
+// the escape certificate of the compiled table for the mosaic's top
+static int refresh_escape(atmrt_ctx* c, const atmrt_params_t& p) {
+  return c->escape.refresh({c->atm.serial(), bits(c->tv.skip_above)}, [&](Escape& e) {
+    (void)escape_floor(c->atm.value().table.table(), true, c->earth.shape_radius, false, c->tv.skip_above, p.simulation_step, &e.from, &e.bound);
+    return 0;
+  });
+}
+
+// The scene: k_resolve rewrites the object table every frame (Altitude::abs depends on the terrain), the textures change with atmrt_objects_set
+static int upload_objects(atmrt_ctx* c) {
+  if (c->objects.empty()) return ATMRT_OK;
+  HIP_TRY(c, c->d_objects.reserve(c->objects.size() * sizeof(ObjectDev)));
+  HIP_TRY(c, hipMemcpy(c->d_objects.ptr, c->objects.data(), c->objects.size() * sizeof(ObjectDev), hipMemcpyHostToDevice));
+  return c->textures_dev.refresh(c->objects_serial, [&](Nothing&) {
+    if (c->textures.empty()) return 0;
+    HIP_TRY(c, c->d_textures.reserve(c->textures.size()));
+    HIP_TRY(c, hipMemcpy(c->d_textures.ptr, c->textures.data(), c->textures.size(), hipMemcpyHostToDevice));
+    return 0;
+  });
+}
+
 static int prepare_frame(atmrt_ctx* c, Frame* out) {
   if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_set_params has not been called");
   HIP_TRY(c, hipSetDevice(c->device));
   int rc = upload_terrain(c);
   if (rc) return rc;
   const atmrt_params_t& p = c->params;
-  // The compiled table and its certificate depend on the definition, the wavelength, the ODE's shape and the step: hosts set the
-  // same atmosphere before every frame (the Python mirror does), and the certificate's bisections are a quarter of a millisecond
-  // of host time — a twentieth of a Fast frame.  Recompiled, re-certified and uploaded again only when one of them changed.
-  const atmrt_ctx::AtmKey key{c->atm_def_serial, p.wavelength, p.simulation_step, c->earth.shape_radius, c->earth.spherical, 0};
-  const bool atm_fresh = !c->atm_key_valid || memcmp(&key, &c->atm_key, sizeof key) != 0;
-  if (atm_fresh) {
-    if (atm_compile(c->atm_def.pod, p.wavelength, c->atm)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "invalid atmosphere");
-    atm_certify(c->atm.table(), c->earth.spherical != 0, c->earth.shape_radius, p.simulation_step);
-    if (getenv("ATMRT_NO_TIGHT")) // experiments: the voting path of dm_div3 on every segment (same bits, tests/test_gpu_march_variants.py)
-      for (int k = 0; k < c->atm.table().n; k++) {
-        c->atm.table().seg(k).flags &= ~ATM_SEG_TIGHT;
-        c->atm.table().seg(k).tight_lo = INFINITY, c->atm.table().seg(k).tight_hi = -INFINITY;
-      }
-  }
-  pinhole_init(p, c->pinhole);
-  if (c->xs_dirty) {
-    // distance table by repeated addition, exactly like `distance += step` (utils.rs:191-196) and the
-    // stepper's x; n_t = #{k: xs[k] < max}; the path cache gets one element more than the first k
-    // whose PREVIOUS x exceeds max (utils.rs:160-170)
-    c->xs.clear();
-    double d = 0.0;
-    int n_t = 0;
-    for (;;) {
-      c->xs.push_back(d);
-      if (d < p.frame.max_distance) n_t++;
-      size_t k = c->xs.size() - 1; // index of d
-      if (k >= 1 && c->xs[k - 1] > p.frame.max_distance) break;
-      d += p.simulation_step;
-      if (c->xs.size() > 5000000) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "distance table too long");
-    }
-    c->n_t = n_t;
-    c->march_steps = 0;
-    for (size_t k = 1; k < c->xs.size(); k++) // the march's own rule: step k is taken while x_k <= max_distance (rectilinear.rs:178)
-      if (c->xs[k] <= p.frame.max_distance) c->march_steps = (int)k;
-      else break;
-    c->n_path_cap = (int)c->xs.size();
-    HIP_TRY(c, c->d_xs.reserve(c->xs.size() * sizeof(double)));
-    HIP_TRY(c, hipMemcpy(c->d_xs.ptr, c->xs.data(), c->xs.size() * sizeof(double), hipMemcpyHostToDevice));
-    c->xs_dirty = false;
-    c->trig_valid = false;
-  }
-  // The Spherical calculator's sin / cos of xs[k] / calc_radius, by the device code the samples would run (k_step_trig): like xs they
-  // depend on nothing of the ray or the observer and survive the frame.  The kernels of this frame follow on the same stream.
-  const bool trig = c->earth.calc == 2 && step_trig_enabled();
-  const size_t n_trig = (size_t)c->march_steps + 1;
-  if (trig && !(c->trig_valid && c->trig_radius == c->earth.calc_radius && c->trig_fast_div == (c->earth.flat_dirs & EARTH_FAST_DIV))) {
-    HIP_TRY(c, c->d_xs_trig.reserve(2 * n_trig * sizeof(double)));
-    launch_step_trig(c->earth, n_trig, c->d_xs.as<double>(), c->d_xs_trig.as<double>(), c->d_xs_trig.as<double>() + n_trig, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    c->trig_radius = c->earth.calc_radius;
-    c->trig_fast_div = c->earth.flat_dirs & EARTH_FAST_DIV;
-    c->trig_valid = true;
-  }
+  const bool trig = c->earth.calc == 2 && step_trig_enabled(); // off: a table of an earlier frame stays as it is
+  if ((rc = refresh_steps(c, p)) || (trig && (rc = refresh_trig(c))) || (rc = refresh_atm(c, p)) || (rc = refresh_escape(c, p)) || (rc = upload_objects(c))) return rc;
+  const Steps& steps = c->steps.value();
   Frame f{};
   f.p = p;
   f.earth = c->earth;
   f.inv_shape_radius = c->earth.spherical && c->earth.shape_radius != 0.0 ? 1.0 / c->earth.shape_radius : 0.0;
-  if (atm_fresh) {
-    HIP_TRY(c, c->d_atm.reserve(c->atm.bytes()));
-    HIP_TRY(c, hipMemcpy(c->d_atm.ptr, &c->atm.table(), c->atm.bytes(), hipMemcpyHostToDevice));
-    c->atm_key = key;
-    c->atm_key_valid = true;
-  }
   f.atm = c->d_atm.as<AtmTable>();
-  f.ph = c->pinhole;
+  pinhole_init(p, f.ph);
   f.tv = c->tv;
   HIP_TRY(c, c->d_alt.reserve(sizeof(double)));
   f.alt = c->d_alt.as<double>();
   f.xs = c->d_xs.as<double>();
   f.xs_sin = trig ? c->d_xs_trig.as<double>() : nullptr;
-  f.xs_cos = trig ? c->d_xs_trig.as<double>() + n_trig : nullptr;
-  // the device table is rewritten by k_resolve every frame (Altitude::abs depends on the terrain), so upload it each time
-  if (!c->objects.empty()) {
-    HIP_TRY(c, c->d_objects.reserve(c->objects.size() * sizeof(ObjectDev)));
-    HIP_TRY(c, hipMemcpy(c->d_objects.ptr, c->objects.data(), c->objects.size() * sizeof(ObjectDev), hipMemcpyHostToDevice));
-    if (c->objects_dirty && !c->textures.empty()) {
-      HIP_TRY(c, c->d_textures.reserve(c->textures.size()));
-      HIP_TRY(c, hipMemcpy(c->d_textures.ptr, c->textures.data(), c->textures.size(), hipMemcpyHostToDevice));
-    }
-    c->objects_dirty = false;
-  }
+  f.xs_cos = trig ? c->d_xs_trig.as<double>() + steps.march_steps + 1 : nullptr;
   f.objects = c->objects.empty() ? nullptr : c->d_objects.as<ObjectDev>();
   f.textures = c->d_textures.as<uint8_t>();
   f.n_objects = (int32_t)c->objects.size();
-  f.n_t = c->n_t;
-  f.n_path_cap = c->n_path_cap;
-  f.march_steps = c->march_steps;
-  // the escape certificate: cached with the table (atm_key) for the mosaic's top
-  if (atm_fresh || !c->esc_valid || c->esc_lo != c->tv.skip_above) {
-    double from = 0.0, worst = 0.0;
-    (void)escape_floor(c->atm.table(), true, c->earth.shape_radius, false, c->tv.skip_above, p.simulation_step, &from, &worst);
-    c->esc_lo = c->tv.skip_above;
-    c->esc_from = from;
-    c->esc_bound = worst;
-    c->esc_valid = true;
-  }
-  // the same certificate from the lowest value an entry of the terrain ceiling table can have (1 m) minus a step
-  if (atm_fresh) c->ceil_from = escape_certified_from(c->atm.table(), c->earth.shape_radius, 1.0 - p.simulation_step, nullptr);
+  f.n_t = steps.n_t;
+  f.n_path_cap = steps.n_path_cap;
+  f.march_steps = steps.march_steps;
   f.esc_floor = INFINITY;
   f.esc_ang_max = INFINITY;
   if (escape_enabled() && p.generator == ATMRT_GEN_RECTILINEAR) {
@@ -854,7 +846,7 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
       // and the reference stops the ray at -1000 m): with 0.05 rad of margin for the rounding of the angle
       if (c->earth.spherical) f.esc_ang_max = 1.5207963267948966 - p.frame.max_distance * f.inv_shape_radius;
     } else if (c->earth.spherical) {
-      f.esc_floor = std::max(c->tv.skip_above, c->esc_from + p.simulation_step);
+      f.esc_floor = std::max(c->tv.skip_above, c->escape.value().from + p.simulation_step);
     }
   }
   {
@@ -868,7 +860,7 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   f.h = p.height;
   f.opaque = (p.terrain_alpha == 1.0 && c->objects.empty()) ? 1 : 0;
   f.lattice = 0;
-  f.atm_cubic = atm_has_cubic(c->atm.table()) ? 1 : 0;
+  f.atm_cubic = atm_has_cubic(c->atm.value().table.table()) ? 1 : 0;
   f.di0 = f.ei0 = 0;
   f.dir_step = f.elev_step = 0.0;
   rc = prepare_ceiling(c, f);
@@ -911,7 +903,6 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
                     PackedHits* packed_out, uint64_t* n_hits_out) {
   hipStream_t s = c->stream;
   launch_resolve(f, ws, c->d_objects.as<ObjectDev>(), s);
-  // phase events: [0..1] profile, [2..3] paths (stream2), [4..5] intersect / march, [5..6] finalize, [7..8] pack
   hipEvent_t* ev = c->ev;
   const bool fast = f.p.generator == ATMRT_GEN_FAST;
   const bool general = f.n_objects > 0; // scenes with objects: full get_single_pixel, count -> scan -> fill
@@ -922,31 +913,31 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     HIP_TRY(c, read_counters(ws, s, cnt));
     HIP_TRY(c, reserve_into(c->d_clist, ws.clist, cnt[CTR_CLOSE_TOTAL] + 1));
     launch_close_fill(f, ws, s);
-    HIP_TRY(c, hipEventRecord(ev[4], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
     launch_trace_count(f, ws, dense, s);
-    HIP_TRY(c, hipEventRecord(ev[5], s));
-    HIP_TRY(c, hipEventRecord(ev[6], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_MARCH_END], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   } else if (general) {
     // Rectilinear with scene objects: the lean march first (it leaves the rays that can meet an object to the general tracer and
     // lists them), then the tracer over that list
-    HIP_TRY(c, hipEventRecord(ev[4], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
     launch_trace_count(f, ws, dense, s);
     uint64_t cnt[N_COUNTERS];
     HIP_TRY(c, read_counters(ws, s, cnt));
     launch_rect_trace_objects(f, ws, dense, cnt[CTR_OBJECT_RAYS], s);
-    HIP_TRY(c, hipEventRecord(ev[5], s));
-    HIP_TRY(c, hipEventRecord(ev[6], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_MARCH_END], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   } else if (fast) {
-    c->scan_segments = launch_fast_pipeline(f, ws, dense, s, c->stream2, c->ev_fork, c->ev_seg, c->ev_scan, ev); // records ev[0..4]
-    HIP_TRY(c, hipEventRecord(ev[5], s));
+    c->scan_segments = launch_fast_pipeline(f, ws, dense, s, c->stream2, c->ev_fork, c->ev_seg, c->ev_scan, ev); // records EV_PROFILE_BEGIN .. EV_MARCH_BEGIN
+    HIP_TRY(c, hipEventRecord(ev[EV_MARCH_END], s));
     if (f.opaque) launch_fast_finalize(f, ws, dense, s);
-    HIP_TRY(c, hipEventRecord(ev[6], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   } else {
-    HIP_TRY(c, hipEventRecord(ev[4], s));
-    launch_rect_march(f, ws, dense, s, ev[5]);
-    HIP_TRY(c, hipEventRecord(ev[6], s));
+    HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
+    launch_rect_march(f, ws, dense, s, ev[EV_MARCH_END]);
+    HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   }
-  HIP_TRY(c, hipEventRecord(ev[7], s));
+  HIP_TRY(c, hipEventRecord(ev[EV_PACK_BEGIN], s));
   PackedHits packed{};
   if (want_packed || !f.opaque) {
     uint64_t counters[N_COUNTERS];
@@ -971,7 +962,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     else launch_list_fill(f, ws, n_hits, dense, packed, s);
     if (n_hits_out) *n_hits_out = n_hits;
   }
-  HIP_TRY(c, hipEventRecord(ev[8], s));
+  HIP_TRY(c, hipEventRecord(ev[EV_PACK_END], s));
   if (packed_out) *packed_out = packed;
   return ATMRT_OK;
 }
@@ -1113,11 +1104,11 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
     float v = 0.f;
     t.total_ms = ms;
     if (f.p.generator != ATMRT_GEN_RECTILINEAR) {
-      HIP_TRY(c, hipEventElapsedTime(&v, ev[0], ev[1]));
+      HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_PROFILE_BEGIN], ev[EV_PROFILE_END]));
       t.profile_ms = v;
-      HIP_TRY(c, hipEventElapsedTime(&v, ev[2], ev[3]));
+      HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_PATHS_BEGIN], ev[EV_PATHS_END]));
       t.paths_ms = v;
-      HIP_TRY(c, hipEventElapsedTime(&v, ev[4], ev[5]));
+      HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_MARCH_BEGIN], ev[EV_MARCH_END]));
       t.intersect_ms = v;
       if (c->scan_segments) { // pipelined frame: the scan's own time, without the waits for the path segments
         t.intersect_ms = 0.0;
@@ -1127,17 +1118,17 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
         }
       }
     } else {
-      HIP_TRY(c, hipEventElapsedTime(&v, ev[4], ev[5]));
+      HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_MARCH_BEGIN], ev[EV_MARCH_END]));
       t.march_ms = v;
     }
-    HIP_TRY(c, hipEventElapsedTime(&v, ev[5], ev[6]));
+    HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_FINALIZE_BEGIN], ev[EV_FINALIZE_END]));
     t.finalize_ms = v;
-    HIP_TRY(c, hipEventElapsedTime(&v, ev[7], ev[8]));
+    HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_PACK_BEGIN], ev[EV_PACK_END]));
     t.pack_ms = v;
     t.ray_steps = counters[CTR_RAY_STEPS];
     t.n_hits = counters[CTR_HITS];
     if (c->ceil_built) {
-      HIP_TRY(c, hipEventElapsedTime(&v, ev[10], ev[11]));
+      HIP_TRY(c, hipEventElapsedTime(&v, ev[EV_CEIL_BEGIN], ev[EV_CEIL_END]));
       t.ceiling_ms = v;
     }
     c->timings = t;
@@ -1936,18 +1927,18 @@ int landmarks_run(atmrt_ctx* k, atmrt_ctx* report, const TracePoints& src, const
     c(st.ctr, LM_N * sizeof(unsigned long long)), c(d_hits, n * sizeof(atmrt_landmark_hit_t));
   }));
   ix.cell_start = d_start, ix.items = d_items, ix.lm = d_lm;
-  HIP_TRY(report, hipEventRecord(k->ev[0], s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_BEGIN], s));
   HIP_TRY(report, hipMemcpyAsync(d_lm, lm, n * sizeof(atmrt_landmark_t), hipMemcpyHostToDevice, s));
   HIP_TRY(report, hipMemcpyAsync(d_start, host.cell_start.data(), host.cell_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   if (!host.items.empty()) HIP_TRY(report, hipMemcpyAsync(d_items, host.items.data(), host.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   launch_lm_reset(n, st, s);
-  HIP_TRY(report, hipEventRecord(k->ev[1], s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_UPLOADED], s));
   launch_lm_pass(false, src, ix, st, s);
-  HIP_TRY(report, hipEventRecord(k->ev[2], s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_FIRST_PASS], s));
   launch_lm_pass(true, src, ix, st, s);
-  HIP_TRY(report, hipEventRecord(k->ev[3], s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_SECOND_PASS], s));
   launch_lm_finish(n, src, st, d_hits, s);
-  HIP_TRY(report, hipEventRecord(k->ev[4], s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_END], s));
   unsigned long long block[LM_N] = {};
   HIP_TRY(report, hipMemcpyAsync(hits, d_hits, n * sizeof(atmrt_landmark_hit_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(report, hipMemcpyAsync(block, st.ctr, sizeof block, hipMemcpyDeviceToHost, s));
@@ -1955,7 +1946,7 @@ int landmarks_run(atmrt_ctx* k, atmrt_ctx* report, const TracePoints& src, const
   HIP_TRY(report, hipGetLastError());
   for (int i = 0; i < 4; i++) {
     float ms = 0.0f;
-    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[i], k->ev[i + 1]));
+    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[EV_LM_BEGIN + i], k->ev[EV_LM_BEGIN + i + 1]));
     report->lm_timings[1 + i] = ms;
   }
   if (stats) *stats = atmrt_landmark_stats_t{block[LM_POINTS], block[LM_SKIPPED], block[LM_TESTED], block[LM_WITHIN]};
@@ -2146,20 +2137,20 @@ extern "C" int atmrt_sight_lines(atmrt_ctx* c, const atmrt_sight_target_t* targe
     Carve carve(c->d_sight.ptr);
     sight_carve(carve, n_dtab, nb, entries, nb, d_targets, d_meta, b, d_dtab, d_out, d_none, 0);
     b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_BEGIN], s));
     HIP_TRY(c, hipMemcpyAsync(d_targets, targets + t0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d_meta, plan.meta.data() + t0, nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
     launch_sight_profile(f, b, m_max, s);
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_PROFILED], s));
     launch_sight_solve(f, b, fan_lo_deg, fan_hi_deg, rounds, d_out, s);
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_SOLVED], s));
     HIP_TRY(c, hipMemcpyAsync(out + t0, d_out, nb * sizeof(atmrt_sight_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_END], s));
     HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes (and reads the host arrays again)
     HIP_TRY(c, hipGetLastError());
     for (int i = 0; i < 3; i++) {
       float ms = 0.0f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
+      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_SIGHT_BEGIN + i], c->ev[EV_SIGHT_BEGIN + i + 1]));
       ms_sum[i] += ms;
     }
   }

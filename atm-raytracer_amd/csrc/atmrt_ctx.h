@@ -9,9 +9,11 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
+#include "atmrt_cached.h"
 #include "atmrt_kernels.h"
 
 namespace atmrt {
@@ -98,6 +100,32 @@ struct AtmDef {
   AtmDef& operator=(const AtmDef&) = delete;
 };
 
+// ---- what a context builds from a frame's inputs and keeps across frames: one rule, atmrt_cached.h (the table: DESIGN.md §3) ----
+// A key is the tuple of a product's inputs in the order of its comment: doubles as their bits(), a source product as its serial().
+using StepsKey = std::tuple<uint64_t, uint64_t>;                                    // simulation_step, max_distance
+using TrigKey = std::tuple<uint64_t, uint64_t, int32_t>;                            // steps, calc_radius, EARTH_FAST_DIV
+using AtmKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, int32_t>;         // atm_def_serial, wavelength, step, shape_radius, spherical
+using EscapeKey = std::tuple<uint64_t, uint64_t>;                                   // atm, the mosaic's top
+using BinsKey = std::tuple<uint64_t, uint64_t, uint64_t, int32_t, int32_t, int32_t, int32_t>; // direction, fov, tilt, width, height, column shard
+using EarthKey = std::tuple<int32_t, int32_t, int32_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t>;
+using LayoutKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, int32_t>;
+using CeilKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, EarthKey, LayoutKey, int32_t>; // terrain_uploaded, steps, latitude, longitude (no altitude), earth, bins, trig table in use
+inline EarthKey key_of(const Earth& e) {
+  return {e.calc, e.flat_dirs, e.cart, e.spherical, bits(e.calc_radius), bits(e.cart_radius), bits(e.a), bits(e.b), bits(e.shape_radius)};
+}
+inline LayoutKey key_of(const CeilLayout& l) { return {bits(l.dir0), bits(l.rel_lo), bits(l.w), bits(l.inv_w), l.n_bins}; }
+struct Steps {
+  std::vector<double> xs;
+  int n_t = 0, n_path_cap = 0, march_steps = 0; // march_steps = #{k >= 1 : xs[k] <= max_distance}: the steps of a ray that marches to the end
+};
+struct Atm {
+  AtmTableBuf table;
+  double ceil_from = 0.0; // the escape certificate's lowest altitude for the lowest value a ceiling entry can have (1 m) minus a step
+};
+struct Escape { // the certificate from the mosaic's top minus a step up: the lowest altitude from which it holds, the largest bound above that
+  double from = 0.0, bound = 0.0;
+};
+
 struct MultiGroup; // atmrt_multi.hip: the devices of a multi-device context and their worker threads
 struct Comm;       // atmrt_multi.hip: this context's place among the ranks that share one frame
 
@@ -107,10 +135,10 @@ struct atmrt_ctx {
   int device = 0;
   hipStream_t stream = nullptr, stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-  hipEvent_t ev[12] = {};                      // [10], [11]: around the build of the terrain ceiling table (timings.ceiling_ms)
+  hipEvent_t ev[atmrt::EV_COUNT] = {};         // the phases of a frame (PhaseEvent, atmrt_kernels.h)
   hipEvent_t ev_seg[atmrt::FAST_SEGMENTS] = {}; // a path segment is integrated (stream2) -> its intersect scan may start
   hipEvent_t ev_scan[2 * atmrt::FAST_SEGMENTS] = {}; // begin / end of every scan segment (after its wait), for intersect_ms
-  int scan_segments = 0;                       // segments of the last pipelined frame (0: ev[4]..ev[5] time the scan)
+  int scan_segments = 0;                       // segments of the last pipelined frame (0: EV_MARCH_BEGIN .. EV_MARCH_END time the scan)
   atmrt_timings_t timings{};
   atmrt_frame_stats_t stats{};
   bool inject_failure = false; // atmrt_debug_fail_next_frame
@@ -126,46 +154,11 @@ struct atmrt_ctx {
   atmrt::AtmDef atm_def;
   std::vector<uint8_t> atm_def_bytes; // the definition as it was last set, byte for byte (atmrt_set_atmosphere)
   uint64_t atm_def_serial = 0;        // counts its changes
-  atmrt::AtmTableBuf atm;
-  struct AtmKey {                     // what the compiled table in `atm` / d_atm was built from (prepare_frame)
-    uint64_t def_serial;
-    double wavelength, step, radius;
-    int32_t spherical;
-    int32_t _pad = 0;
-  } atm_key{};
-  bool atm_key_valid = false;
-  // the escape certificate of the table under atm_key (prepare_frame, escape_floor): the lowest altitude from which it holds,
-  // computed for the altitudes from esc_lo up (the mosaic's top minus a step)
-  double esc_lo = 0.0, esc_from = 0.0, esc_bound = 0.0;
-  bool esc_valid = false;
   atmrt::Earth earth{};
-  atmrt::Pinhole pinhole{};
-  std::vector<double> xs;
-  int n_t = 0, n_path_cap = 0;
-  int march_steps = 0; // #{k >= 1 : xs[k] <= max_distance}: the steps of a ray that marches to the end
-  bool xs_dirty = true;
-  // what the table in d_xs_trig (Frame::xs_sin / xs_cos) was built from besides xs itself (a new xs clears trig_valid)
-  double trig_radius = 0.0;
-  int32_t trig_fast_div = 0;
-  bool trig_valid = false;
-  // The terrain ceiling table in d_ceil (Frame::ceil, atmrt_ceiling.h) and what it was built from (prepare_ceiling): the mosaic,
-  // the observer's place (not its altitude), the earth model, the distance table and the bins.  ceil_from: the certificate's
-  // lowest altitude for the lowest value a table entry can have (1 m), kept beside esc_from under the same atmosphere key.
-  struct CeilKey {
-    uint64_t terrain;
-    double lat, lon, step, max_distance;
-    atmrt::Earth earth;
-    atmrt::CeilLayout layout;
-    int32_t march_steps, trig;
-  } ceil_key{};
-  struct CeilLayoutKey { // what the bins follow from: the frame's directions and its column shard
-    double direction, fov, tilt;
-    int32_t width, height, c0, wl;
-  } ceil_layout_key{};
-  atmrt::CeilLayout ceil_layout{};
-  bool ceil_valid = false, ceil_layout_valid = false;
-  bool ceil_built = false; // this frame built the table: ev[10] .. ev[11] hold its time
-  double ceil_from = 0.0;
+  atmrt::Cached<atmrt::AtmKey, atmrt::Atm> atm;          // the compiled, certified table (prepare_frame)
+  atmrt::Cached<atmrt::EscapeKey, atmrt::Escape> escape; // its certificate above the mosaic's top (Frame::esc_floor)
+  atmrt::Cached<atmrt::BinsKey, atmrt::CeilLayout> bins; // the ceiling table's bins (prepare_ceiling)
+  bool ceil_built = false; // this frame built the ceiling table: EV_CEIL_BEGIN .. EV_CEIL_END hold its time
 
   // last generated frame (for atmrt_draw_image)
   bool last_valid = false, last_packed = false;
@@ -181,7 +174,7 @@ struct atmrt_ctx {
 
   std::vector<atmrt::ObjectDev> objects; // host image of the device table (altitude kind in _pad until k_resolve)
   std::vector<uint8_t> textures;         // RGBA8 pool
-  bool objects_dirty = true;
+  uint64_t objects_serial = 0;           // counts atmrt_objects_set
 
   // several devices / ranks (atmrt_multi.hip); both null for a plain one-device context
   atmrt::MultiGroup* multi = nullptr; // this is the PARENT of a multi-device context: every entry point forwards to its children
@@ -190,11 +183,15 @@ struct atmrt_ctx {
   // Device memory.  The scratch of a frame is ONE allocation, d_workspace, carved by workspace_layout (atmrt_kernels.h) and re-carved
   // by every prepare_workspace.  A buffer of its own needs a reason:
   // ... it survives the frame
-  atmrt::DevBuf d_xs, d_atm;               // the distance table and the compiled atmosphere: uploaded when their inputs change
-  atmrt::DevBuf d_xs_trig;                 // Spherical calculator: sin, then cos, of xs[0 .. march_steps] / calc_radius (k_step_trig): rebuilt when xs, the radius or EARTH_FAST_DIV change
-  atmrt::DevBuf d_ceil;                    // Spherical calculator, Rectilinear: the terrain ceiling table, (march_steps + 1) x (bins + 1) entries: rebuilt when ceil_key changes
+  atmrt::DevBuf d_xs, d_atm;               // the distance table (`steps`) and the compiled atmosphere (`atm`)
+  atmrt::Cached<atmrt::StepsKey, atmrt::Steps> steps;
+  atmrt::DevBuf d_xs_trig;                 // Spherical calculator: sin, then cos, of xs[0 .. march_steps] / calc_radius (k_step_trig)
+  atmrt::Cached<atmrt::TrigKey> trig;
+  atmrt::DevBuf d_ceil;                    // Spherical calculator, Rectilinear: the terrain ceiling table (atmrt_ceiling.h), (march_steps + 1) x (bins + 1) entries
+  atmrt::Cached<atmrt::CeilKey> ceiling;
   atmrt::DevBuf d_alt;                     // the observer's altitude (k_resolve): atmrt_draw_overlay* samples the atmosphere there
-  atmrt::DevBuf d_objects, d_textures;     // the scene: textures are uploaded when the objects change
+  atmrt::DevBuf d_objects, d_textures;     // the scene: the object table is uploaded every frame, the textures when objects_serial changes
+  atmrt::Cached<uint64_t> textures_dev;
   atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last_dense, last_hits, last_offset): draw, overlay, hits
   atmrt::DevBuf d_io, d_overlay;           // staging of the entry points that run between frames
   atmrt::DevBuf d_vis;                     // atmrt_visibility_map* / atmrt_frame_bounds: the call's statistics block (72 B), read while the last frame's buffers are live

@@ -442,14 +442,29 @@ void launch_close_fill(const Frame& f, Workspace& ws, hipStream_t stream);
 void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* tmp, uint64_t* out, unsigned long long* total, hipStream_t stream);
 void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_fast_paths(const Frame& f, Workspace& ws, hipStream_t stream, int i_begin, int i_end); // atmrt_paths.hip
+// The phase events of a context (atmrt_ctx::ev; `timing` below): an interval of atmrt_timings_t lies between two of them.  Between
+// frames atmrt_sight_lines and atmrt_locate_landmarks* time their own consecutive intervals with the same events, under names of their own.
+enum PhaseEvent {
+  EV_PROFILE_BEGIN, EV_PROFILE_END, // Fast: the terrain profile
+  EV_PATHS_BEGIN, EV_PATHS_END,     // Fast: the ray paths (second stream)
+  EV_MARCH_BEGIN, EV_MARCH_END,     // the intersect scan (Fast) or the march (Rectilinear)
+  EV_FINALIZE_END,                  // finalize begins where the scan or march ends
+  EV_PACK_BEGIN, EV_PACK_END,
+  EV_CEIL_BEGIN, EV_CEIL_END,       // the build of the terrain ceiling table (timings.ceiling_ms)
+  EV_COUNT,
+  EV_FINALIZE_BEGIN = EV_MARCH_END,
+  EV_SIGHT_BEGIN = 0, EV_SIGHT_PROFILED, EV_SIGHT_SOLVED, EV_SIGHT_END,
+  EV_LM_BEGIN = 0, EV_LM_UPLOADED, EV_LM_FIRST_PASS, EV_LM_SECOND_PASS, EV_LM_END,
+};
+static_assert(EV_SIGHT_END < EV_COUNT && EV_LM_END < EV_COUNT, "the borrowed events exist");
 #ifndef ATMRT_FAST_SEGMENTS
 #define ATMRT_FAST_SEGMENTS 4
 #endif
 constexpr int FAST_SEGMENTS = ATMRT_FAST_SEGMENTS;
 int launch_fast_pipeline(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipStream_t stream2,
-                         hipEvent_t ev_fork, hipEvent_t* ev_seg, hipEvent_t* ev_scan, hipEvent_t* timing); // returns the number of segments
+                         hipEvent_t ev_fork, hipEvent_t* ev_seg, hipEvent_t* ev_scan, hipEvent_t* timing); // returns the number of segments; records EV_PROFILE_BEGIN .. EV_MARCH_BEGIN
 void launch_fast_caches(const Frame& f, Workspace& ws, hipStream_t stream, hipStream_t stream2, hipEvent_t ev,
-                        hipEvent_t ev_join, hipEvent_t* timing /* [0..1] phase A, [2..3] phase B */);
+                        hipEvent_t ev_join, hipEvent_t* timing /* EV_PROFILE_*: phase A, EV_PATHS_*: phase B */);
 void launch_fast_intersect(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_fast_finalize(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_rect_march(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched);

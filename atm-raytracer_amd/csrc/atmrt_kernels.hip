@@ -1578,11 +1578,11 @@ void launch_fast_caches(const Frame& f, Workspace& ws, hipStream_t stream, hipSt
   // phase B (few long sequential rays) runs beside phase A (many short samples) on a second stream
   (void)hipEventRecord(ev, stream);
   (void)hipStreamWaitEvent(stream2, ev, 0);
-  (void)hipEventRecord(timing[2], stream2);
+  (void)hipEventRecord(timing[EV_PATHS_BEGIN], stream2);
   launch_fast_paths(f, ws, stream2, 1, f.n_path_cap);
-  (void)hipEventRecord(timing[3], stream2);
+  (void)hipEventRecord(timing[EV_PATHS_END], stream2);
   (void)hipEventRecord(ev_join, stream2);
-  (void)hipEventRecord(timing[0], stream);
+  (void)hipEventRecord(timing[EV_PROFILE_BEGIN], stream);
   hipLaunchKernelGGL(k_fast_columns, dim3(cdiv(f.wl, 256)), dim3(256), 0, stream, f, ws.colcalc);
   if (f.n_objects) {
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_terrain_profile<CALC, true>),
@@ -1593,7 +1593,7 @@ void launch_fast_caches(const Frame& f, Workspace& ws, hipStream_t stream, hipSt
                                                           dim3(cdiv(f.n_t, PROFILE_SAMPLES_PER_BLOCK), cdiv(f.wl, 64)),
                                                           dim3(256), 0, stream, f, ws.colcalc, ws.prof, ws.plat, ws.plon));
   }
-  (void)hipEventRecord(timing[1], stream);
+  (void)hipEventRecord(timing[EV_PROFILE_END], stream);
   (void)hipStreamWaitEvent(stream, ev_join, 0);
 }
 
@@ -1617,7 +1617,7 @@ void launch_fast_intersect(const Frame& f, Workspace& ws, const DensePlanes& out
 // Phases A, B and C of a Fast frame without scene objects.  The ray paths are one long dependent chain per row (3.5 ms at the
 // headline size on a tenth of the chip) and the intersect scan only ever needs the samples integrated so far: the paths are
 // integrated in FAST_SEGMENTS pieces on the second stream and the scan of piece k (main stream, after the terrain profile)
-// waits for piece k alone, so it overlaps the integration of piece k + 1.  timing[4] is recorded before the first scan.
+// waits for piece k alone, so it overlaps the integration of piece k + 1.  timing[EV_MARCH_BEGIN] is recorded before the first scan.
 int launch_fast_pipeline(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipStream_t stream2,
                          hipEvent_t ev_fork, hipEvent_t* ev_seg, hipEvent_t* ev_scan, hipEvent_t* timing) {
   const int cap = f.n_path_cap;
@@ -1626,20 +1626,20 @@ int launch_fast_pipeline(const Frame& f, Workspace& ws, const DensePlanes& out, 
   per = (per + 3) / 4 * 4; // whole chunks of the scan
   (void)hipEventRecord(ev_fork, stream);
   (void)hipStreamWaitEvent(stream2, ev_fork, 0);
-  (void)hipEventRecord(timing[2], stream2);
+  (void)hipEventRecord(timing[EV_PATHS_BEGIN], stream2);
   for (int k = 0; k < nseg; k++) {
     const int b0 = 1 + k * per, b1 = k == nseg - 1 ? cap : (b0 + per < cap ? b0 + per : cap);
     launch_fast_paths(f, ws, stream2, b0, b1);
     (void)hipEventRecord(ev_seg[k], stream2);
   }
-  (void)hipEventRecord(timing[3], stream2);
-  (void)hipEventRecord(timing[0], stream);
+  (void)hipEventRecord(timing[EV_PATHS_END], stream2);
+  (void)hipEventRecord(timing[EV_PROFILE_BEGIN], stream);
   hipLaunchKernelGGL(k_fast_columns, dim3(cdiv(f.wl, 256)), dim3(256), 0, stream, f, ws.colcalc);
   ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_terrain_profile<CALC, false>),
                                                         dim3(cdiv(f.n_t, PROFILE_SAMPLES_PER_BLOCK), cdiv(f.wl, 64)), dim3(256), 0,
                                                         stream, f, ws.colcalc, ws.prof, ws.plat, ws.plon));
-  (void)hipEventRecord(timing[1], stream);
-  (void)hipEventRecord(timing[4], stream);
+  (void)hipEventRecord(timing[EV_PROFILE_END], stream);
+  (void)hipEventRecord(timing[EV_MARCH_BEGIN], stream);
   for (int k = 0; k < nseg; k++) {
     const int b0 = 1 + k * per, b1 = k == nseg - 1 ? cap : (b0 + per < cap ? b0 + per : cap);
     (void)hipStreamWaitEvent(stream, ev_seg[k], 0);
