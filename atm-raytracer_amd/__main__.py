@@ -4,6 +4,8 @@
                                     [--visibility-map OUT.npz [--map-cell ARCSEC] [--map-all]]
                                     [--landmarks FILE.csv [--landmark-radius ARCSEC] [--landmarks-all] [--landmarks-out OUT.csv]]
                                     [--sight-lines FILE.csv [--sight-out OUT.csv] [--sight-fan LO HI] [--sight-rounds N]]
+                                    [--viewshed OUT.npz [--viewshed-az LO HI N] [--viewshed-reach M] [--viewshed-height M]
+                                     [--viewshed-fan LO HI K]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -29,6 +31,12 @@ many metres of it the terrain hides and where that terrain is.  The table — na
 above_fan, below_fan), angle_deg, hidden_m, ground_m, resolution_deg, the blocking point's block_distance_m, block_lat, block_lon,
 block_elevation_m, and the Fast generator's pixel x, y that (azimuth, angle) falls in for the configured frame, empty outside it —
 goes to --sight-out or to stdout.
+`--viewshed` (no reference counterpart) answers the same question for a whole area: for N azimuths from LO to HI (--viewshed-az; the
+frame's field of view at one azimuth per pixel column unless said otherwise) and every sample of the lattice as far as
+--viewshed-reach (max_distance), whether a point --viewshed-height metres above the ground (0) is seen over a fan of K rays between
+LO and HI degrees (--viewshed-fan, -5 5 64), and how many metres of it are hidden.  OUT.npz holds the planes k_star, status (0 seen,
+1 hidden, 2 above_fan, 3 below_fan), hidden, block_index, ground, lat and lon as [N][m] arrays, the lattice d, the azimuths, the
+fan's angles and the height.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -136,6 +144,30 @@ def solve_sight_lines(ctx, cfg, path, fan, rounds, out_path):
     return targets, sights
 
 
+def viewshed_defaults(cfg, az, reach):
+    """(az_lo, az_step, n_az, reach) of gen --viewshed: what --viewshed-az LO HI N and --viewshed-reach say, else one azimuth per pixel
+    column of the frame (the Fast generator's column directions) as far as max_distance."""
+    p = cfg.params
+    if az is None:
+        lo, step, n = p.frame.direction - float(p.width // 2) / p.width * p.frame.fov, p.frame.fov / p.width, int(p.width)
+    else:
+        lo, hi, n = float(az[0]), float(az[1]), int(az[2])
+        if n < 1 or float(az[2]) != n:
+            raise config.ConfigError("--viewshed-az LO HI N: N must be a positive whole number")
+        step = (hi - lo) / (n - 1) if n > 1 else 0.0
+    return lo, step, n, p.frame.max_distance if reach is None else float(reach)
+
+
+def write_viewshed(ctx, cfg, path, az, reach, height, fan):
+    """The viewshed of the context's parameters, atmosphere and terrain to an .npz; returns the Viewshed."""
+    lo, step, n, reach = viewshed_defaults(cfg, az, reach)
+    if float(fan[2]) != int(fan[2]):
+        raise config.ConfigError("--viewshed-fan LO HI K: K must be a whole number")
+    v = generators.viewshed(ctx, lo, step, n, reach, height, (float(fan[0]), float(fan[1])), int(fan[2]))
+    generators.write_viewshed_npz(path, v)
+    return v
+
+
 def draw_landmarks(img, names, hits):
     """A short vertical marker above every found landmark's pixel and its name, drawn on the host like the tick labels."""
     from PIL import ImageDraw, ImageFont
@@ -180,6 +212,9 @@ def cmd_gen(a):
     if a.sight_lines:  # needs no frame: the context's parameters, atmosphere and terrain
         stamp("Solving sight lines...")
         solve_sight_lines(ctx, cfg, a.sight_lines, tuple(a.sight_fan), a.sight_rounds, a.sight_out)
+    if a.viewshed:  # likewise
+        stamp("Scanning the viewshed...")
+        write_viewshed(ctx, cfg, a.viewshed, a.viewshed_az, a.viewshed_reach, a.viewshed_height, a.viewshed_fan)
     img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
     draw_labels(img, ticks)
     if located:
@@ -272,6 +307,11 @@ def main(argv=None):
     g.add_argument("--sight-out", default=None, metavar="OUT.csv")
     g.add_argument("--sight-fan", type=float, nargs=2, default=(-5.0, 5.0), metavar=("LO", "HI"))
     g.add_argument("--sight-rounds", type=int, default=3, metavar="N")
+    g.add_argument("--viewshed", default=None, metavar="OUT.npz")
+    g.add_argument("--viewshed-az", type=float, nargs=3, default=None, metavar=("LO", "HI", "N"))
+    g.add_argument("--viewshed-reach", type=float, default=None, metavar="M")
+    g.add_argument("--viewshed-height", type=float, default=0.0, metavar="M")
+    g.add_argument("--viewshed-fan", type=float, nargs=3, default=(-5.0, 5.0, 64), metavar=("LO", "HI", "K"))
     g.set_defaults(fn=cmd_gen)
     p = sub.add_parser("output-atm")
     p.add_argument("config")

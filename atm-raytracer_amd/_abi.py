@@ -192,6 +192,12 @@ class SightRay(C.Structure):
     _fields_ = [("block_index", C.c_int32), ("min_index", C.c_int32), ("arrival", C.c_double), ("min_clearance", C.c_double)]
 
 
+class ViewshedSpec(C.Structure):
+    """atmrt_viewshed_spec_t: the azimuths, the reach [m], the height above the ground [m], the fan [deg] and its rays."""
+    _fields_ = [(k, C.c_double) for k in ("az_lo_deg", "az_step_deg", "reach", "height", "fan_lo_deg", "fan_hi_deg")] + \
+        [("n_az", C.c_int32), ("fan_rays", C.c_int32)]
+
+
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""
     import numpy as np

@@ -23,6 +23,7 @@
 #include "atmrt_multi.h"
 #include "atmrt_render.h"
 #include "atmrt_sight.h"
+#include "atmrt_viewshed.h"
 #include "atmrt_tiff.h"
 
 using namespace atmrt;
@@ -150,6 +151,7 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 24: return sizeof(atmrt_sight_target_t);
     case 25: return sizeof(atmrt_sight_t);
     case 26: return sizeof(atmrt_sight_ray_t);
+    case 28: return sizeof(atmrt_viewshed_spec_t);
     default: return 0;
   }
 }
@@ -2199,6 +2201,199 @@ extern "C" int atmrt_last_sight_timings(atmrt_ctx* c, double out[3]) {
 extern "C" int atmrt_last_sight_batches(atmrt_ctx* c, int32_t* batches) {
   if (!c || !batches) return ATMRT_ERR_INVALID_ARGUMENT;
   *batches = c->sight_batches;
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// viewshed (include/atmrt.h; kernels in atmrt_viewshed.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int atmrt_viewshed_fan_angles(double lo, double hi, int32_t fan_rays, double* out) {
+  if (!out || !viewshed_fan_rays_ok(fan_rays) || !std::isfinite(lo) || !std::isfinite(hi)) return ATMRT_ERR_INVALID_ARGUMENT;
+  const double delta = viewshed_fan_delta(lo, hi, fan_rays);
+  for (int k = 0; k < fan_rays; k++) out[k] = sight_fan_angle(lo, delta, k);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_viewshed_shape(int32_t fan_rays, int32_t* az_per_load, int32_t* step_tile, int32_t* rays_per_lane) {
+  if (az_per_load) *az_per_load = VIEWSHED_AZ;
+  if (step_tile) *step_tile = VIEWSHED_TILE;
+  if (rays_per_lane) *rays_per_lane = viewshed_fan_rays_ok(fan_rays) ? viewshed_rays_per_lane(fan_rays) : 0;
+  return ATMRT_OK;
+}
+
+namespace {
+
+// everything a batch of nb azimuths carves from d_sight: the sight lines' layout (dtab first: it stays where the call put it), then
+// the planes of the host route (`staged`: null pointers where the caller asked for none)
+void viewshed_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, const ViewshedPlanes& asked, bool stage, atmrt_sight_target_t*& targets,
+                    SightMeta*& meta, SightBatch& b, double*& dtab, ViewshedPlanes& staged) {
+  double* none = nullptr;
+  uint8_t* out = nullptr;
+  sight_carve(k, n_dtab, nb, nb * (m + 1), 0, targets, meta, b, dtab, out, none, 0);
+  staged = ViewshedPlanes{};
+  if (!stage) return;
+  const size_t cells = nb * m;
+  k(staged.k_star, cells * 2), k(staged.status, cells), k(staged.hidden, cells * 8);
+  if (asked.block_index) k(staged.block_index, cells * 4);
+  if (asked.ground) k(staged.ground, cells * 8);
+  if (asked.lat) k(staged.lat, cells * 8);
+  if (asked.lon) k(staged.lon, cells * 8);
+}
+
+int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* spec, const ViewshedPlanes& dst, bool device_planes) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!spec || !dst.k_star || !dst.status || !dst.hidden) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec, k_star, status or hidden is NULL", what);
+  const atmrt_viewshed_spec_t v = *spec;
+  if (!(std::isfinite(v.az_lo_deg) && std::isfinite(v.az_step_deg))) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: az_lo_deg and az_step_deg must be finite", what);
+  if (v.n_az < 1 || (size_t)v.n_az > VIEWSHED_N_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_az must lie in [1, 65536]", what);
+  if (!viewshed_fan_rays_ok(v.fan_rays)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: fan_rays must be a multiple of 64 in [64, 4096]", what);
+  if (!(std::isfinite(v.fan_lo_deg) && std::isfinite(v.fan_hi_deg) && v.fan_lo_deg < v.fan_hi_deg && v.fan_hi_deg - v.fan_lo_deg <= 180.0))
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the fan must be finite, increasing and at most 180 degrees wide", what);
+  if (int rc = sight_check_state(c, what)) return rc;
+  // the lattice, and one target per azimuth, through the sight lines' own plan: every target's m is the call's
+  std::vector<atmrt_sight_target_t> targets((size_t)v.n_az);
+  for (int32_t j = 0; j < v.n_az; j++) targets[j] = atmrt_sight_target_t{v.az_lo_deg + (double)j * v.az_step_deg, v.reach, v.height};
+  if (!std::isfinite(targets.back().azimuth_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the last azimuth is not finite", what);
+  const size_t cell = device_planes ? 0 : viewshed_cell_bytes(dst);
+  SightPlan plan;
+  {
+    const atmrt_sight_target_t first = targets[0]; // reach and height are the same for every azimuth: checked once, with the lattice
+    if (const char* msg = sight_plan(c, &first, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  }
+  const int m = plan.meta[0].m;
+  const int K = v.fan_rays;
+  const size_t table_bytes = ((size_t)m + 1) * (size_t)K * sizeof(double);
+  if (table_bytes > SIGHT_SCRATCH_BYTES)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the path table of (m + 1) * K * 8 = %zu bytes exceeds the scratch limit of %zu", what, table_bytes, SIGHT_SCRATCH_BYTES);
+  // azimuths of a batch: what one adds is its profile (sight_target_bytes) and, on the host route, its cells of the staged planes;
+  // then as many fewer as it takes for the whole layout — distance table, altitude and every array's padding included — to stay
+  // under the limit (a batch holds at least one azimuth)
+  const size_t per_az = sight_target_bytes(m) + cell * (size_t)m, limit = sight_scratch_limit();
+  const auto layout_bytes = [&](size_t nb) {
+    Carve k(nullptr);
+    atmrt_sight_target_t* t = nullptr;
+    SightMeta* me = nullptr;
+    SightBatch sb{};
+    double* dt = nullptr;
+    ViewshedPlanes st{};
+    viewshed_carve(k, (size_t)m + 1, nb, (size_t)m, dst, !device_planes, t, me, sb, dt, st);
+    return k.bytes;
+  };
+  size_t nb_max = std::min((size_t)v.n_az, std::max<size_t>(1, limit / per_az));
+  while (nb_max > 1 && layout_bytes(nb_max) > limit) nb_max--;
+  Frame f;
+  if (int rc = prepare_frame(c, &f)) return rc;
+  hipStream_t s = c->stream;
+  const atmrt_position_t& pos = c->params.position;
+  const ViewshedKey key{c->atm.serial(), c->terrain_uploaded, pos.altitude_kind, bits(pos.latitude), bits(pos.longitude), bits(pos.altitude),
+                        bits(v.fan_lo_deg), bits(v.fan_hi_deg), bits(c->params.simulation_step), K, m, c->params.straight_rays ? 1 : 0, key_of(c->earth)};
+  bool rebuilt = false;
+  double ms_sum[4] = {};
+  HIP_TRY(c, hipEventRecord(c->ev[EV_VS_BEGIN], s));
+  int rc = c->viewshed_paths.refresh(key, [&](Nothing&) -> int {
+    HIP_TRY(c, c->d_viewshed_paths.reserve(table_bytes));
+    launch_viewshed_paths(f, v.fan_lo_deg, v.fan_hi_deg, K, m, c->d_viewshed_paths.as<double>(), s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_PATHS], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return ATMRT_OK;
+  }, false, &rebuilt);
+  if (rc) return rc;
+  if (rebuilt) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_VS_BEGIN], c->ev[EV_VS_PATHS]));
+    ms_sum[0] = ms;
+  }
+  const size_t n_dtab = (size_t)m + 1;
+  atmrt_sight_target_t* d_targets = nullptr;
+  SightMeta* d_meta = nullptr;
+  SightBatch b{};
+  double* d_dtab = nullptr;
+  ViewshedPlanes staged{};
+  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { viewshed_carve(k, n_dtab, nb_max, (size_t)m, dst, !device_planes, d_targets, d_meta, b, d_dtab, staged); }));
+  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
+  std::vector<SightMeta> meta(nb_max);
+  for (size_t t = 0; t < nb_max; t++) meta[t] = SightMeta{t * ((size_t)m + 1), m, 0};
+  size_t n_batches = 0;
+  for (size_t j0 = 0; j0 < (size_t)v.n_az; j0 += nb_max, n_batches++) {
+    const size_t nb = std::min(nb_max, (size_t)v.n_az - j0), cells = nb * (size_t)m, at = j0 * (size_t)m;
+    Carve carve(c->d_sight.ptr);
+    viewshed_carve(carve, n_dtab, nb, (size_t)m, dst, !device_planes, d_targets, d_meta, b, d_dtab, staged);
+    b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
+    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_BATCH], s));
+    HIP_TRY(c, hipMemcpyAsync(d_targets, targets.data() + j0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_meta, meta.data(), nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
+    launch_sight_profile(f, b, m, s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_PROFILED], s));
+    ViewshedScan scan{};
+    scan.n = (int32_t)nb, scan.m = m, scan.K = K, scan.height = v.height;
+    scan.H = c->d_viewshed_paths.as<double>();
+    scan.T = b.T, scan.lat = b.lat, scan.lon = b.lon;
+    if (device_planes) {
+      scan.out = ViewshedPlanes{dst.k_star + at, dst.status + at, dst.hidden + at, dst.block_index ? dst.block_index + at : nullptr,
+                                dst.ground ? dst.ground + at : nullptr, dst.lat ? dst.lat + at : nullptr, dst.lon ? dst.lon + at : nullptr};
+    } else {
+      scan.out = staged;
+    }
+    launch_viewshed_scan(scan, s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_SCANNED], s));
+    if (!device_planes) {
+      HIP_TRY(c, hipMemcpyAsync(dst.k_star + at, staged.k_star, cells * 2, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(dst.status + at, staged.status, cells, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(dst.hidden + at, staged.hidden, cells * 8, hipMemcpyDeviceToHost, s));
+      if (dst.block_index) HIP_TRY(c, hipMemcpyAsync(dst.block_index + at, staged.block_index, cells * 4, hipMemcpyDeviceToHost, s));
+      if (dst.ground) HIP_TRY(c, hipMemcpyAsync(dst.ground + at, staged.ground, cells * 8, hipMemcpyDeviceToHost, s));
+      if (dst.lat) HIP_TRY(c, hipMemcpyAsync(dst.lat + at, staged.lat, cells * 8, hipMemcpyDeviceToHost, s));
+      if (dst.lon) HIP_TRY(c, hipMemcpyAsync(dst.lon + at, staged.lon, cells * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_END], s));
+    HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes
+    HIP_TRY(c, hipGetLastError());
+    for (int i = 0; i < 3; i++) {
+      float ms = 0.0f;
+      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_VS_BATCH + i], c->ev[EV_VS_BATCH + i + 1]));
+      ms_sum[1 + i] += ms;
+    }
+  }
+  memcpy(c->viewshed_timings, ms_sum, sizeof ms_sum);
+  c->viewshed_batches = (int32_t)n_batches;
+  c->viewshed_rebuilt = rebuilt ? 1 : 0;
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_viewshed_steps(atmrt_ctx* c, double reach, int32_t* m) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!m) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_viewshed_steps: m is NULL");
+  if (int rc = sight_check_state(c, "atmrt_viewshed_steps")) return rc;
+  const atmrt_sight_target_t t{0.0, reach, 0.0};
+  SightPlan plan;
+  if (const char* msg = sight_plan(c, &t, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_viewshed_steps: %s", msg);
+  *m = plan.meta[0].m;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_viewshed(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, uint16_t* k_star, uint8_t* status, double* hidden,
+                              int32_t* block_index, double* ground, double* lat, double* lon) {
+  return viewshed_run(c, "atmrt_viewshed", spec, ViewshedPlanes{k_star, status, hidden, block_index, ground, lat, lon}, false);
+}
+
+extern "C" int atmrt_viewshed_device(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, uint16_t* k_star, uint8_t* status, double* hidden,
+                                     int32_t* block_index, double* ground, double* lat, double* lon) {
+  return viewshed_run(c, "atmrt_viewshed_device", spec, ViewshedPlanes{k_star, status, hidden, block_index, ground, lat, lon}, true);
+}
+
+extern "C" int atmrt_last_viewshed_timings(atmrt_ctx* c, double out[4]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memcpy(out, c->viewshed_timings, sizeof c->viewshed_timings);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_viewshed_work(atmrt_ctx* c, int32_t* batches, int32_t* table_rebuilt) {
+  if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
+  *batches = c->viewshed_batches;
+  *table_rebuilt = c->viewshed_rebuilt;
   return ATMRT_OK;
 }
 

@@ -110,6 +110,9 @@ using BinsKey = std::tuple<uint64_t, uint64_t, uint64_t, int32_t, int32_t, int32
 using EarthKey = std::tuple<int32_t, int32_t, int32_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t>;
 using LayoutKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, int32_t>;
 using CeilKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, EarthKey, LayoutKey, int32_t>; // terrain_uploaded, steps, latitude, longitude (no altitude), earth, bins, trig table in use
+// atm, terrain_uploaded, altitude_kind, latitude, longitude, altitude (what the observer's altitude is resolved from), fan lo, hi,
+// simulation_step, K, m, straight_rays, earth
+using ViewshedKey = std::tuple<uint64_t, uint64_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, int32_t, int32_t, int32_t, EarthKey>;
 inline EarthKey key_of(const Earth& e) {
   return {e.calc, e.flat_dirs, e.cart, e.spherical, bits(e.calc_radius), bits(e.cart_radius), bits(e.a), bits(e.b), bits(e.shape_radius)};
 }
@@ -200,6 +203,10 @@ struct atmrt_ctx {
   atmrt::DevBuf d_sight;                   // atmrt_sight_lines / atmrt_sight_fan_probe: the call's distance table and one batch of targets, profiles and records
   double sight_timings[3] = {};            // atmrt_last_sight_timings
   int32_t sight_batches = 0;               // atmrt_last_sight_batches
+  atmrt::DevBuf d_viewshed_paths;          // atmrt_viewshed*: the path table H[i][k] of the last fan, kept across calls
+  atmrt::Cached<atmrt::ViewshedKey> viewshed_paths;
+  double viewshed_timings[4] = {};         // atmrt_last_viewshed_timings
+  int32_t viewshed_batches = 0, viewshed_rebuilt = 0; // atmrt_last_viewshed_work
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
   atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
   atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend

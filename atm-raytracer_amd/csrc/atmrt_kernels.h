@@ -454,9 +454,10 @@ enum PhaseEvent {
   EV_COUNT,
   EV_FINALIZE_BEGIN = EV_MARCH_END,
   EV_SIGHT_BEGIN = 0, EV_SIGHT_PROFILED, EV_SIGHT_SOLVED, EV_SIGHT_END,
+  EV_VS_BEGIN = 0, EV_VS_PATHS, EV_VS_BATCH, EV_VS_PROFILED, EV_VS_SCANNED, EV_VS_END,
   EV_LM_BEGIN = 0, EV_LM_UPLOADED, EV_LM_FIRST_PASS, EV_LM_SECOND_PASS, EV_LM_END,
 };
-static_assert(EV_SIGHT_END < EV_COUNT && EV_LM_END < EV_COUNT, "the borrowed events exist");
+static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_LM_END < EV_COUNT, "the borrowed events exist");
 #ifndef ATMRT_FAST_SEGMENTS
 #define ATMRT_FAST_SEGMENTS 4
 #endif

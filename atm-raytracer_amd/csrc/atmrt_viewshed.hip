@@ -1,0 +1,5 @@
+// atmrt_viewshed.hip — the viewshed kernels (atmrt_viewshed.h) on gfx950.  A translation unit of its own beside the frame pipeline,
+// like the sight lines: the path table is one dependent chain per lane, the scan streams that table against the azimuths' profiles.
+// Built with the flags of the calling units (Makefile, CALL_EXTRA).
+#define ATMRT_VIEWSHED_KERNELS
+#include "atmrt_viewshed.h"

@@ -771,6 +771,86 @@ def ctx_params(ctx):
     return p
 
 
+# ---- viewshed: the first round of the sight-line rule at every cell of a polar lattice (include/atmrt.h) ---------------------
+VIEWSHED_PLANES = (("k_star", np.uint16), ("status", np.uint8), ("hidden", np.float64), ("block_index", np.int32), ("ground", np.float64),
+                   ("lat", np.float64), ("lon", np.float64))
+
+
+class Viewshed:
+    """The planes of one viewshed call as numpy arrays [n_az][m] (cell (j, i) at [j, i - 1]; an optional plane that was not asked
+    for is None), with d [m + 1] (the lattice), azimuths [n_az], angles [K] (the fan) and height."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def planes(self):
+        return {k: getattr(self, k) for k, _ in VIEWSHED_PLANES if getattr(self, k) is not None}
+
+
+def viewshed_fan_angles(lo, hi, fan_rays=64, lib=None):
+    """atmrt_viewshed_fan_angles (host code, no device): the fan_rays angles of the fan over [lo, hi]."""
+    lib = lib or _lib.load()
+    out = np.empty(max(int(fan_rays), 1), dtype=np.float64)
+    rc = lib.atmrt_viewshed_fan_angles(lo, hi, int(fan_rays), out.ctypes.data)
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_viewshed_fan_angles refused its arguments")
+    return out
+
+
+def viewshed_kernel_shape(fan_rays=64, lib=None):
+    """atmrt_debug_viewshed_shape: {'az_per_load', 'step_tile', 'rays_per_lane'} of the scan kernel at fan_rays."""
+    lib = lib or _lib.load()
+    a, t, r = C.c_int32(), C.c_int32(), C.c_int32()
+    lib.atmrt_debug_viewshed_shape(int(fan_rays), C.byref(a), C.byref(t), C.byref(r))
+    return dict(az_per_load=a.value, step_tile=t.value, rays_per_lane=r.value)
+
+
+def viewshed_lattice(step, reach):
+    """d_0 = 0, d_i = d_{i-1} + step as far as the first d_m >= reach (the sight lines' lattice) -> d [m + 1]."""
+    d, x = [0.0], 0.0
+    while not x >= reach:
+        x = x + step
+        d.append(x)
+        if len(d) - 1 > 65535:
+            raise ValueError("the reach lies more than 65535 samples away")
+    return np.array(d, dtype=np.float64)
+
+
+def viewshed_azimuths(az_lo_deg, az_step_deg, n_az):
+    """az_j = az_lo + (double)j * az_step."""
+    return np.float64(az_lo_deg) + np.arange(int(n_az), dtype=np.float64) * np.float64(az_step_deg)
+
+
+def viewshed(ctx, az_lo_deg, az_step_deg, n_az, reach, height=0.0, fan=(-5.0, 5.0), fan_rays=64, optional=("block_index", "ground", "lat", "lon")):
+    """atmrt_viewshed against the parameters, atmosphere and terrain now set on `ctx`: for the n_az azimuths az_lo + j az_step and
+    every lattice sample as far as `reach`, whether a point `height` metres above the ground is seen over the fan of fan_rays rays,
+    and how many metres are hidden.  No frame is needed.  `optional` names the optional planes to fill.  Returns a Viewshed."""
+    spec = _abi.ViewshedSpec(float(az_lo_deg), float(az_step_deg), float(reach), float(height), float(fan[0]), float(fan[1]), int(n_az), int(fan_rays))
+    m = C.c_int32()
+    ctx.check(ctx.lib.atmrt_viewshed_steps(ctx.handle, float(reach), C.byref(m)))
+    m = m.value
+    d = viewshed_lattice(ctx_params(ctx).simulation_step, float(reach))
+    if d.size != m + 1:
+        raise AtmrtError(_abi.ERR_STATE, f"the library's lattice has {m} steps, this module's {d.size - 1}: the parameters on the context are not the ones recorded")
+    arrays = {k: np.empty((max(int(n_az), 1), m), dtype=t) if k in ("k_star", "status", "hidden") or k in optional else None for k, t in VIEWSHED_PLANES}
+    ctx.check(ctx.lib.atmrt_viewshed(ctx.handle, C.byref(spec), *[None if arrays[k] is None else arrays[k].ctypes.data for k, _ in VIEWSHED_PLANES]))
+    return Viewshed(d=d, azimuths=viewshed_azimuths(az_lo_deg, az_step_deg, n_az), angles=viewshed_fan_angles(fan[0], fan[1], fan_rays, ctx.lib),
+                    height=float(height), **arrays)
+
+
+def viewshed_work(ctx):
+    """atmrt_last_viewshed_timings / atmrt_last_viewshed_work of the last viewshed on `ctx`."""
+    out, n, rebuilt = (C.c_double * 4)(), C.c_int32(), C.c_int32()
+    ctx.check(ctx.lib.atmrt_last_viewshed_timings(ctx.handle, out))
+    ctx.check(ctx.lib.atmrt_last_viewshed_work(ctx.handle, C.byref(n), C.byref(rebuilt)))
+    return dict(zip(("paths_ms", "profiles_ms", "scan_ms", "download_ms"), out), batches=n.value, table_rebuilt=bool(rebuilt.value))
+
+
+def write_viewshed_npz(path, v):
+    """OUT.npz of gen --viewshed: the planes, d, the azimuths, the fan's angles and the height."""
+    np.savez_compressed(path, d=v.d, azimuths=v.azimuths, angles=v.angles, height=np.float64(v.height), **v.planes())
+
+
 # ---- the sight-line tables of the command line (gen --sight-lines FILE.csv) --------------------------------------------------
 SIGHT_COLUMNS = ("name", "azimuth_deg", "distance_m", "status", "angle_deg", "hidden_m", "ground_m", "resolution_deg", "block_distance_m",
                  "block_lat", "block_lon", "block_elevation_m", "x", "y")

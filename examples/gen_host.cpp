@@ -72,6 +72,13 @@ int main(int argc, char** argv) {
       for (const atmrt_sight_t& s : sights)
         printf("sight status %d rounds %d m %d angle %.17g hidden %.17g ground %.17g resolution %.17g block %d %.17g %.17g\n", s.status, s.rounds_done,
                s.m, s.angle, s.hidden, s.ground, s.resolution, s.block_index, s.block_distance, s.block_elevation);
+      // and the same question for the ground along three azimuths as far as 23.7 km: the viewshed, one line per cell of the last sample
+      const Viewshed v = viewshed(terrain, atmrt_viewshed_spec_t{88.0, 2.0, 23700.0, 0.0, -6.0, 6.0, 3, 128});
+      for (int32_t j = 0; j < v.n_az; j++) {
+        const size_t o = (size_t)j * v.m + (v.m - 1);
+        printf("viewshed azimuth %d m %d k_star %d status %d hidden %.17g ground %.17g block %d lat %.17g lon %.17g\n", j, v.m, v.k_star[o], v.status[o],
+               v.hidden[o], v.ground[o], v.block_index[o], v.lat[o], v.lon[o]);
+      }
     }
     if (auto e = terrain.get_elev(46.5, 8.5)) printf("elevation under the observer: %.3f m\n", *e);
   } catch (const Error& e) {

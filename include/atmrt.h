@@ -594,6 +594,69 @@ int atmrt_last_sight_timings(atmrt_ctx* ctx, double out[3]);
 /* The number of batches that call took. */
 int atmrt_last_sight_batches(atmrt_ctx* ctx, int32_t* batches);
 
+/* ---- viewshed: for every cell of a polar lattice around the observer, whether a point `height` metres above the ground there is
+ * seen, and how many metres are hidden (no reference counterpart).  Like the sight lines it needs the context's parameters,
+ * atmosphere and terrain only; it neither needs nor disturbs a generated frame.
+ *
+ * THE RULE (tests/viewshed_model.py restates it in numpy): the viewshed is, by definition, the FIRST ROUND of the sight-line rule
+ * evaluated at every lattice cell.  A call gives az_lo_deg, az_step_deg and 1 <= n_az <= 65536; reach [m], which gives m = the
+ * first index with d_m >= reach, 1 <= m <= 65535; height [m] >= 0, the same for every cell; and a fan [fan_lo_deg, fan_hi_deg] of
+ * K rays, K a multiple of 64 in [64, 4096].
+ *   Azimuths: az_j = az_lo + (double)j * az_step (two rounded operations).
+ *   Fan: delta = (hi - lo) / (double)(K - 1), e_k = lo + (double)k * delta; at K = 64 the very doubles of atmrt_sight_fan_angles.
+ *   Lattice and profiles: d_i, (lat_{j,i}, lon_{j,i}) and T_{j,i} for 0 <= i <= m are exactly the sight lines' sample lattice for
+ *     azimuth az_j (the same device functions produce them).
+ *   Ray heights: H_{k,0} = alt, H_{k,i} = the stepper's h after i steps of simulation_step at angle e_k.  A ray is integrated for
+ *     all m steps, whatever it meets.  The atmosphere is horizontally uniform: one table serves every azimuth.
+ *   Blocking: c = H_{k,i} - T_{j,i}; ray k is blocked against azimuth j at the first i' >= 1 with c_{i'-1} * c_{i'} < 0.0 or
+ *     H_{k,i'-1} < -1000.
+ *   Cell (j, i), 1 <= i <= m, plays the target {az_j, d_i, height}, whose m is i and whose prop is 1.0; the expressions keep the
+ *     sight rule's shape so that the bits agree: arrival_k = H_{k,i-1} + 1.0 * (H_{k,i} - H_{k,i-1}), ground = T_{j,i-1} + 1.0 *
+ *     (T_{j,i} - T_{j,i-1}), aim = ground + height.  Ray k FAILS iff it is blocked at some i' <= i - 1 or !(arrival_k >= aim).
+ *     k* = one above the highest failing ray: 0 if none fails, K if ray K - 1 fails — an answer even where ducting makes rays cross.
+ *   status: ATMRT_SIGHT_ABOVE_FAN when k* = K, BELOW_FAN when k* = 0, HIDDEN when ray k* - 1 is blocked at some i' <= i - 1, SEEN
+ *     otherwise.  hidden = arrival_{k*} - aim, NaN for ABOVE_FAN (every NaN is the quiet NaN the sight lines write).  block_index =
+ *     the i' of ray k* - 1 when HIDDEN, -1 otherwise.
+ * The outputs are planes indexed [j * m + (i - 1)].  Equal calls return equal bytes: the scan uses no atomics and does not depend
+ * on the order in which wavefronts arrive. */
+typedef struct atmrt_viewshed_spec {
+  double az_lo_deg, az_step_deg; /* finite */
+  double reach;                  /* [m], finite, > 0 */
+  double height;                 /* metres above the ground at every cell, finite, >= 0 */
+  double fan_lo_deg, fan_hi_deg; /* finite, increasing, at most 180 degrees apart */
+  int32_t n_az;                  /* 1 .. 65536 */
+  int32_t fan_rays;              /* K */
+} atmrt_viewshed_spec_t;
+/* The fan's host half, ctx-free — the same function the kernels run: out[k] = e_k for k < fan_rays.  NULL, a fan_rays that is
+ * not a multiple of 64 in [64, 4096] or a bound that is not finite: ATMRT_ERR_INVALID_ARGUMENT. */
+int atmrt_viewshed_fan_angles(double lo, double hi, int32_t fan_rays, double* out);
+/* A diagnostic in the spirit of atmrt_debug_step_trig, NOT part of the stable surface: the shape of THIS BUILD's scan kernel, so
+ * that tests can straddle it.  *az_per_load = the azimuths that share one load of a ray height, *step_tile = the steps between two
+ * meetings of a block's wavefronts, *rays_per_lane = the rays a lane owns at fan_rays (0 for a fan_rays the call would refuse).  The
+ * values may change with any build; no result of atmrt_viewshed depends on them.  Any pointer may be NULL. */
+int atmrt_debug_viewshed_shape(int32_t fan_rays, int32_t* az_per_load, int32_t* step_tile, int32_t* rays_per_lane);
+/* m for `reach` under the parameters now set on ctx: what sizes the planes.  Refuses what atmrt_viewshed refuses of reach and state. */
+int atmrt_viewshed_steps(atmrt_ctx* ctx, double reach, int32_t* m);
+/* The raster into host arrays of n_az * m entries each; block_index, ground, lat and lon are optional (NULL skips one).
+ * Three passes: the path table H[i][k] (kept in the context with the key it was built from: atmosphere,
+ * observer, terrain, fan, K, m, step, straight_rays, earth — a second call that changes only height or the azimuths does not
+ * rebuild it), the azimuths' profiles, and the scan.  Azimuths are processed in batches so that the call's device scratch stays
+ * under the sight lines' limit (ATMRT_SIGHT_SCRATCH_BYTES lowers it here too; the planes do not depend on it).
+ * ATMRT_ERR_INVALID_ARGUMENT: a NULL spec or required plane, a number that is not finite, n_az, m or fan_rays out of range, a fan
+ * that is not increasing or wider than 180 degrees, a negative height, a reach that is not positive, a path table of
+ * (m + 1) * K * 8 bytes above the (unlowered) scratch limit of 200 MiB.  ATMRT_ERR_STATE: before atmrt_set_params, and on a
+ * multi-device context. */
+int atmrt_viewshed(atmrt_ctx* ctx, const atmrt_viewshed_spec_t* spec, uint16_t* k_star, uint8_t* status, double* hidden,
+                   int32_t* block_index, double* ground, double* lat, double* lon);
+/* The same with the planes written into caller-provided memory of the context's device: no download. */
+int atmrt_viewshed_device(atmrt_ctx* ctx, const atmrt_viewshed_spec_t* spec, uint16_t* k_star, uint8_t* status, double* hidden,
+                          int32_t* block_index, double* ground, double* lat, double* lon);
+/* Where the time of the last viewshed call on ctx went, in milliseconds between events on the library's stream, the last three
+ * summed over its batches: out = {path table (0 when it was not rebuilt), profiles (upload included), scan, download}. */
+int atmrt_last_viewshed_timings(atmrt_ctx* ctx, double out[4]);
+/* The batches that call took, and whether it rebuilt the path table (1) or found it (0). */
+int atmrt_last_viewshed_work(atmrt_ctx* ctx, int32_t* batches, int32_t* table_rebuilt);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —

@@ -318,4 +318,25 @@ inline std::vector<atmrt_sight_t> sight_lines(const Terrain& terrain, const std:
   return out;
 }
 
+// Viewshed (no reference counterpart; include/atmrt.h states the rule): the first round of the sight-line rule at every cell of the
+// polar lattice spec describes, from the observer set on `terrain`'s context.  Planes are [n_az][m], cell (j, i) at j * m + (i - 1).
+struct Viewshed {
+  int32_t n_az = 0, m = 0;
+  std::vector<uint16_t> k_star;
+  std::vector<uint8_t> status;
+  std::vector<double> hidden, ground, lat, lon;
+  std::vector<int32_t> block_index;
+};
+inline Viewshed viewshed(const Terrain& terrain, const atmrt_viewshed_spec_t& spec) {
+  Viewshed out;
+  terrain.check(atmrt_viewshed_steps(terrain.ctx(), spec.reach, &out.m));
+  out.n_az = spec.n_az;
+  const size_t cells = (size_t)(spec.n_az > 0 ? spec.n_az : 0) * (size_t)out.m;
+  out.k_star.resize(cells), out.status.resize(cells), out.hidden.resize(cells), out.block_index.resize(cells);
+  out.ground.resize(cells), out.lat.resize(cells), out.lon.resize(cells);
+  terrain.check(atmrt_viewshed(terrain.ctx(), &spec, out.k_star.data(), out.status.data(), out.hidden.data(), out.block_index.data(),
+                               out.ground.data(), out.lat.data(), out.lon.data()));
+  return out;
+}
+
 } // namespace atmrt_host
