@@ -6,6 +6,8 @@
                                     [--sight-lines FILE.csv [--sight-out OUT.csv] [--sight-fan LO HI] [--sight-rounds N]]
                                     [--viewshed OUT.npz [--viewshed-az LO HI N] [--viewshed-reach M] [--viewshed-height M]
                                      [--viewshed-fan LO HI K]]
+                                    [--horizon OUT.csv [--horizon-az LO HI N] [--horizon-reach M] [--horizon-fan LO HI K]
+                                     [--horizon-rounds N]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -37,6 +39,11 @@ frame's field of view at one azimuth per pixel column unless said otherwise) and
 LO and HI degrees (--viewshed-fan, -5 5 64), and how many metres of it are hidden.  OUT.npz holds the planes k_star, status (0 seen,
 1 hidden, 2 above_fan, 3 below_fan), hidden, block_index, ground, lat and lon as [N][m] arrays, the lattice d, the azimuths, the
 fan's angles and the height.
+`--horizon` (no reference counterpart) asks where the skyline is: for N azimuths from LO to HI (--horizon-az; one per pixel column of
+the frame unless said otherwise) and the terrain within --horizon-reach (max_distance), the refracted elevation angle at which
+terrain ends and sky begins, bracketed between the highest blocked ray and the ray above it — first fan --horizon-fan (-5 5 64),
+narrowed --horizon-rounds times (3) — and the ridge that forms it.  OUT.csv has one row per azimuth: azimuth_deg, status (found,
+above_fan, below_fan), angle_clear_deg, angle_blocked_deg, resolution_deg, ridge_distance_m, ridge_lat, ridge_lon, ridge_elevation_m.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -144,16 +151,16 @@ def solve_sight_lines(ctx, cfg, path, fan, rounds, out_path):
     return targets, sights
 
 
-def viewshed_defaults(cfg, az, reach):
-    """(az_lo, az_step, n_az, reach) of gen --viewshed: what --viewshed-az LO HI N and --viewshed-reach say, else one azimuth per pixel
-    column of the frame (the Fast generator's column directions) as far as max_distance."""
+def viewshed_defaults(cfg, az, reach, flag="--viewshed-az"):
+    """(az_lo, az_step, n_az, reach) of gen --viewshed (and gen --horizon): what --viewshed-az LO HI N and --viewshed-reach say, else one
+    azimuth per pixel column of the frame (the Fast generator's column directions) as far as max_distance."""
     p = cfg.params
     if az is None:
         lo, step, n = p.frame.direction - float(p.width // 2) / p.width * p.frame.fov, p.frame.fov / p.width, int(p.width)
     else:
         lo, hi, n = float(az[0]), float(az[1]), int(az[2])
         if n < 1 or float(az[2]) != n:
-            raise config.ConfigError("--viewshed-az LO HI N: N must be a positive whole number")
+            raise config.ConfigError(f"{flag} LO HI N: N must be a positive whole number")
         step = (hi - lo) / (n - 1) if n > 1 else 0.0
     return lo, step, n, p.frame.max_distance if reach is None else float(reach)
 
@@ -166,6 +173,16 @@ def write_viewshed(ctx, cfg, path, az, reach, height, fan):
     v = generators.viewshed(ctx, lo, step, n, reach, height, (float(fan[0]), float(fan[1])), int(fan[2]))
     generators.write_viewshed_npz(path, v)
     return v
+
+
+def write_horizon(ctx, cfg, path, az, reach, fan, rounds):
+    """The horizon of the context's parameters, atmosphere and terrain to a .csv; returns the Horizon."""
+    lo, step, n, reach = viewshed_defaults(cfg, az, reach, "--horizon-az")
+    if float(fan[2]) != int(fan[2]):
+        raise config.ConfigError("--horizon-fan LO HI K: K must be a whole number")
+    h = generators.horizon(ctx, lo, step, n, reach, (float(fan[0]), float(fan[1])), int(fan[2]), rounds)
+    generators.write_horizon_csv(path, h)
+    return h
 
 
 def draw_landmarks(img, names, hits):
@@ -215,6 +232,9 @@ def cmd_gen(a):
     if a.viewshed:  # likewise
         stamp("Scanning the viewshed...")
         write_viewshed(ctx, cfg, a.viewshed, a.viewshed_az, a.viewshed_reach, a.viewshed_height, a.viewshed_fan)
+    if a.horizon:  # likewise
+        stamp("Solving the horizon...")
+        write_horizon(ctx, cfg, a.horizon, a.horizon_az, a.horizon_reach, a.horizon_fan, a.horizon_rounds)
     img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
     draw_labels(img, ticks)
     if located:
@@ -312,6 +332,11 @@ def main(argv=None):
     g.add_argument("--viewshed-reach", type=float, default=None, metavar="M")
     g.add_argument("--viewshed-height", type=float, default=0.0, metavar="M")
     g.add_argument("--viewshed-fan", type=float, nargs=3, default=(-5.0, 5.0, 64), metavar=("LO", "HI", "K"))
+    g.add_argument("--horizon", default=None, metavar="OUT.csv")
+    g.add_argument("--horizon-az", type=float, nargs=3, default=None, metavar=("LO", "HI", "N"))
+    g.add_argument("--horizon-reach", type=float, default=None, metavar="M")
+    g.add_argument("--horizon-fan", type=float, nargs=3, default=(-5.0, 5.0, 64), metavar=("LO", "HI", "K"))
+    g.add_argument("--horizon-rounds", type=int, default=3, metavar="N")
     g.set_defaults(fn=cmd_gen)
     p = sub.add_parser("output-atm")
     p.add_argument("config")

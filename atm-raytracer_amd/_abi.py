@@ -198,6 +198,22 @@ class ViewshedSpec(C.Structure):
         [("n_az", C.c_int32), ("fan_rays", C.c_int32)]
 
 
+# atmrt_horizon_status: the last two have the values of the sight statuses of the same meaning
+HORIZON_FOUND, HORIZON_ABOVE_FAN, HORIZON_BELOW_FAN = 0, SIGHT_ABOVE_FAN, SIGHT_BELOW_FAN
+HORIZON_STATUS = {HORIZON_FOUND: "found", HORIZON_ABOVE_FAN: "above_fan", HORIZON_BELOW_FAN: "below_fan"}
+
+
+class HorizonSpec(C.Structure):
+    """atmrt_horizon_spec_t: the azimuths, the reach [m], the first fan [deg] and its rays, and the rounds."""
+    _fields_ = [(k, C.c_double) for k in ("az_lo_deg", "az_step_deg", "reach", "fan_lo_deg", "fan_hi_deg")] + \
+        [("n_az", C.c_int32), ("fan_rays", C.c_int32), ("rounds", C.c_int32)]
+
+
+class Horizon(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rounds_done", C.c_int32), ("k_star", C.c_int32), ("block_index", C.c_int32)] + \
+        [(k, C.c_double) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon", "block_elevation")]
+
+
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""
     import numpy as np

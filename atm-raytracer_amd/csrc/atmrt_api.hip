@@ -24,6 +24,7 @@
 #include "atmrt_render.h"
 #include "atmrt_sight.h"
 #include "atmrt_viewshed.h"
+#include "atmrt_horizon.h"
 #include "atmrt_tiff.h"
 
 using namespace atmrt;
@@ -152,6 +153,8 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 25: return sizeof(atmrt_sight_t);
     case 26: return sizeof(atmrt_sight_ray_t);
     case 28: return sizeof(atmrt_viewshed_spec_t);
+    case 30: return sizeof(atmrt_horizon_spec_t);
+    case 31: return sizeof(atmrt_horizon_t);
     default: return 0;
   }
 }
@@ -2240,31 +2243,65 @@ void viewshed_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, const Viewshed
   if (asked.lon) k(staged.lon, cells * 8);
 }
 
-int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* spec, const ViewshedPlanes& dst, bool device_planes) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!spec || !dst.k_star || !dst.status || !dst.hidden) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec, k_star, status or hidden is NULL", what);
-  const atmrt_viewshed_spec_t v = *spec;
-  if (!(std::isfinite(v.az_lo_deg) && std::isfinite(v.az_step_deg))) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: az_lo_deg and az_step_deg must be finite", what);
-  if (v.n_az < 1 || (size_t)v.n_az > VIEWSHED_N_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_az must lie in [1, 65536]", what);
-  if (!viewshed_fan_rays_ok(v.fan_rays)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: fan_rays must be a multiple of 64 in [64, 4096]", what);
-  if (!(std::isfinite(v.fan_lo_deg) && std::isfinite(v.fan_hi_deg) && v.fan_lo_deg < v.fan_hi_deg && v.fan_hi_deg - v.fan_lo_deg <= 180.0))
+// What the viewshed and the horizon refuse alike, and what both begin with: the lattice, and one target per azimuth, through the
+// sight lines' own plan (every target's m is the call's, plan.meta[0].m).
+int polar_call_plan(atmrt_ctx* c, const char* what, double az_lo_deg, double az_step_deg, int32_t n_az, double reach, double height, double fan_lo_deg,
+                    double fan_hi_deg, int32_t fan_rays, std::vector<atmrt_sight_target_t>& targets, SightPlan& plan) {
+  if (!(std::isfinite(az_lo_deg) && std::isfinite(az_step_deg))) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: az_lo_deg and az_step_deg must be finite", what);
+  if (n_az < 1 || (size_t)n_az > VIEWSHED_N_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_az must lie in [1, 65536]", what);
+  if (!viewshed_fan_rays_ok(fan_rays)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: fan_rays must be a multiple of 64 in [64, 4096]", what);
+  if (!(std::isfinite(fan_lo_deg) && std::isfinite(fan_hi_deg) && fan_lo_deg < fan_hi_deg && fan_hi_deg - fan_lo_deg <= 180.0))
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the fan must be finite, increasing and at most 180 degrees wide", what);
   if (int rc = sight_check_state(c, what)) return rc;
-  // the lattice, and one target per azimuth, through the sight lines' own plan: every target's m is the call's
-  std::vector<atmrt_sight_target_t> targets((size_t)v.n_az);
-  for (int32_t j = 0; j < v.n_az; j++) targets[j] = atmrt_sight_target_t{v.az_lo_deg + (double)j * v.az_step_deg, v.reach, v.height};
+  targets.resize((size_t)n_az);
+  for (int32_t j = 0; j < n_az; j++) targets[j] = atmrt_sight_target_t{az_lo_deg + (double)j * az_step_deg, reach, height};
   if (!std::isfinite(targets.back().azimuth_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the last azimuth is not finite", what);
-  const size_t cell = device_planes ? 0 : viewshed_cell_bytes(dst);
-  SightPlan plan;
   {
     const atmrt_sight_target_t first = targets[0]; // reach and height are the same for every azimuth: checked once, with the lattice
     if (const char* msg = sight_plan(c, &first, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
   }
-  const int m = plan.meta[0].m;
-  const int K = v.fan_rays;
-  const size_t table_bytes = ((size_t)m + 1) * (size_t)K * sizeof(double);
+  const size_t table_bytes = ((size_t)plan.meta[0].m + 1) * (size_t)fan_rays * sizeof(double);
   if (table_bytes > SIGHT_SCRATCH_BYTES)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the path table of (m + 1) * K * 8 = %zu bytes exceeds the scratch limit of %zu", what, table_bytes, SIGHT_SCRATCH_BYTES);
+  return ATMRT_OK;
+}
+
+// The path table H[i][k] of the fan, the one product of both calls under the one key: built where the key differs from the last
+// build's.  *ms: what the build took between EV_VS_BEGIN and EV_VS_PATHS, 0 when the table was found.
+int viewshed_paths_refresh(atmrt_ctx* c, const Frame& f, double fan_lo_deg, double fan_hi_deg, int K, int m, bool* rebuilt, double* ms_paths) {
+  hipStream_t s = c->stream;
+  const atmrt_position_t& pos = c->params.position;
+  const ViewshedKey key{c->atm.serial(), c->terrain_uploaded, pos.altitude_kind, bits(pos.latitude), bits(pos.longitude), bits(pos.altitude),
+                        bits(fan_lo_deg), bits(fan_hi_deg), bits(c->params.simulation_step), K, m, c->params.straight_rays ? 1 : 0, key_of(c->earth)};
+  *ms_paths = 0.0;
+  HIP_TRY(c, hipEventRecord(c->ev[EV_VS_BEGIN], s));
+  int rc = c->viewshed_paths.refresh(key, [&](Nothing&) -> int {
+    HIP_TRY(c, c->d_viewshed_paths.reserve(((size_t)m + 1) * (size_t)K * sizeof(double)));
+    launch_viewshed_paths(f, fan_lo_deg, fan_hi_deg, K, m, c->d_viewshed_paths.as<double>(), s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_PATHS], s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return ATMRT_OK;
+  }, false, rebuilt);
+  if (rc) return rc;
+  if (*rebuilt) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_VS_BEGIN], c->ev[EV_VS_PATHS]));
+    *ms_paths = ms;
+  }
+  return ATMRT_OK;
+}
+
+int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* spec, const ViewshedPlanes& dst, bool device_planes) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!spec || !dst.k_star || !dst.status || !dst.hidden) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec, k_star, status or hidden is NULL", what);
+  const atmrt_viewshed_spec_t v = *spec;
+  std::vector<atmrt_sight_target_t> targets;
+  SightPlan plan;
+  if (int rc = polar_call_plan(c, what, v.az_lo_deg, v.az_step_deg, v.n_az, v.reach, v.height, v.fan_lo_deg, v.fan_hi_deg, v.fan_rays, targets, plan)) return rc;
+  const size_t cell = device_planes ? 0 : viewshed_cell_bytes(dst);
+  const int m = plan.meta[0].m;
+  const int K = v.fan_rays;
   // azimuths of a batch: what one adds is its profile (sight_target_bytes) and, on the host route, its cells of the staged planes;
   // then as many fewer as it takes for the whole layout — distance table, altitude and every array's padding included — to stay
   // under the limit (a batch holds at least one azimuth)
@@ -2284,26 +2321,9 @@ int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* sp
   Frame f;
   if (int rc = prepare_frame(c, &f)) return rc;
   hipStream_t s = c->stream;
-  const atmrt_position_t& pos = c->params.position;
-  const ViewshedKey key{c->atm.serial(), c->terrain_uploaded, pos.altitude_kind, bits(pos.latitude), bits(pos.longitude), bits(pos.altitude),
-                        bits(v.fan_lo_deg), bits(v.fan_hi_deg), bits(c->params.simulation_step), K, m, c->params.straight_rays ? 1 : 0, key_of(c->earth)};
   bool rebuilt = false;
   double ms_sum[4] = {};
-  HIP_TRY(c, hipEventRecord(c->ev[EV_VS_BEGIN], s));
-  int rc = c->viewshed_paths.refresh(key, [&](Nothing&) -> int {
-    HIP_TRY(c, c->d_viewshed_paths.reserve(table_bytes));
-    launch_viewshed_paths(f, v.fan_lo_deg, v.fan_hi_deg, K, m, c->d_viewshed_paths.as<double>(), s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_PATHS], s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    return ATMRT_OK;
-  }, false, &rebuilt);
-  if (rc) return rc;
-  if (rebuilt) {
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_VS_BEGIN], c->ev[EV_VS_PATHS]));
-    ms_sum[0] = ms;
-  }
+  if (int rc = viewshed_paths_refresh(c, f, v.fan_lo_deg, v.fan_hi_deg, K, m, &rebuilt, &ms_sum[0])) return rc;
   const size_t n_dtab = (size_t)m + 1;
   atmrt_sight_target_t* d_targets = nullptr;
   SightMeta* d_meta = nullptr;
@@ -2394,6 +2414,122 @@ extern "C" int atmrt_last_viewshed_work(atmrt_ctx* c, int32_t* batches, int32_t*
   if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
   *batches = c->viewshed_batches;
   *table_rebuilt = c->viewshed_rebuilt;
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// horizon (include/atmrt.h; kernels in atmrt_horizon.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int atmrt_debug_horizon_shape(int32_t fan_rays, int32_t* az_per_load, int32_t* step_tile, int32_t* rays_per_lane) {
+  if (az_per_load) *az_per_load = HORIZON_AZ;
+  if (step_tile) *step_tile = HORIZON_TILE;
+  if (rays_per_lane) *rays_per_lane = viewshed_fan_rays_ok(fan_rays) ? horizon_rays_per_lane(fan_rays) : 0;
+  return ATMRT_OK;
+}
+
+namespace {
+
+// everything a batch of nb azimuths carves from d_sight: the sight lines' layout (dtab first: it stays where the call put it), with
+// the records of the host route where the sight lines have theirs (`stage`)
+void horizon_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, bool stage, atmrt_sight_target_t*& targets, SightMeta*& meta, SightBatch& b,
+                   double*& dtab, atmrt_horizon_t*& staged) {
+  double* none = nullptr;
+  sight_carve(k, n_dtab, nb, nb * (m + 1), stage ? nb : 0, targets, meta, b, dtab, staged, none, 0);
+  if (!stage) staged = nullptr;
+}
+
+int horizon_run(atmrt_ctx* c, const char* what, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* dst, bool device_out) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!spec || !dst) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or out is NULL", what);
+  const atmrt_horizon_spec_t v = *spec;
+  if (v.rounds < 1 || v.rounds > 4) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: rounds must lie in [1, 4]", what);
+  std::vector<atmrt_sight_target_t> targets;
+  SightPlan plan;
+  if (int rc = polar_call_plan(c, what, v.az_lo_deg, v.az_step_deg, v.n_az, v.reach, 0.0, v.fan_lo_deg, v.fan_hi_deg, v.fan_rays, targets, plan)) return rc;
+  const int m = plan.meta[0].m;
+  const int K = v.fan_rays;
+  // azimuths of a batch, as the viewshed counts them: what one adds is its profile (sight_target_bytes) and, on the host route, its
+  // record; then as many fewer as it takes for the whole layout to stay under the limit (a batch holds at least one azimuth)
+  const size_t per_az = sight_target_bytes(m) + (device_out ? 0 : sizeof(atmrt_horizon_t)), limit = sight_scratch_limit();
+  const size_t n_dtab = (size_t)m + 1;
+  atmrt_sight_target_t* d_targets = nullptr;
+  SightMeta* d_meta = nullptr;
+  SightBatch b{};
+  double* d_dtab = nullptr;
+  atmrt_horizon_t* staged = nullptr;
+  const auto layout_bytes = [&](size_t nb) {
+    Carve k(nullptr);
+    horizon_carve(k, n_dtab, nb, (size_t)m, !device_out, d_targets, d_meta, b, d_dtab, staged);
+    return k.bytes;
+  };
+  size_t nb_max = std::min((size_t)v.n_az, std::max<size_t>(1, limit / per_az));
+  while (nb_max > 1 && layout_bytes(nb_max) > limit) nb_max--;
+  Frame f;
+  if (int rc = prepare_frame(c, &f)) return rc;
+  hipStream_t s = c->stream;
+  bool rebuilt = false;
+  double ms_sum[5] = {};
+  if (int rc = viewshed_paths_refresh(c, f, v.fan_lo_deg, v.fan_hi_deg, K, m, &rebuilt, &ms_sum[0])) return rc;
+  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { horizon_carve(k, n_dtab, nb_max, (size_t)m, !device_out, d_targets, d_meta, b, d_dtab, staged); }));
+  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
+  std::vector<SightMeta> meta(nb_max);
+  for (size_t t = 0; t < nb_max; t++) meta[t] = SightMeta{t * ((size_t)m + 1), m, 0};
+  size_t n_batches = 0;
+  for (size_t j0 = 0; j0 < (size_t)v.n_az; j0 += nb_max, n_batches++) {
+    const size_t nb = std::min(nb_max, (size_t)v.n_az - j0);
+    Carve carve(c->d_sight.ptr);
+    horizon_carve(carve, n_dtab, nb, (size_t)m, !device_out, d_targets, d_meta, b, d_dtab, staged);
+    b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
+    atmrt_horizon_t* const d_out = device_out ? dst + j0 : staged;
+    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_BATCH], s));
+    HIP_TRY(c, hipMemcpyAsync(d_targets, targets.data() + j0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_meta, meta.data(), nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
+    launch_sight_profile(f, b, m, s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_PROFILED], s));
+    HorizonScan scan{};
+    scan.n = (int32_t)nb, scan.m = m, scan.K = K, scan.lo = v.fan_lo_deg, scan.hi = v.fan_hi_deg;
+    scan.H = c->d_viewshed_paths.as<double>();
+    scan.T = b.T, scan.out = d_out;
+    launch_horizon_scan(scan, s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_SCANNED], s));
+    launch_horizon_refine(f, b, v.rounds, d_out, s);
+    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_REFINED], s));
+    if (!device_out) HIP_TRY(c, hipMemcpyAsync(dst + j0, staged, nb * sizeof(atmrt_horizon_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_END], s));
+    HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes
+    HIP_TRY(c, hipGetLastError());
+    for (int i = 0; i < 4; i++) {
+      float ms = 0.0f;
+      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_HZ_BATCH + i], c->ev[EV_HZ_BATCH + i + 1]));
+      ms_sum[1 + i] += ms;
+    }
+  }
+  memcpy(c->horizon_timings, ms_sum, sizeof ms_sum);
+  c->horizon_batches = (int32_t)n_batches;
+  c->horizon_rebuilt = rebuilt ? 1 : 0;
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_horizon(atmrt_ctx* c, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* out) {
+  return horizon_run(c, "atmrt_horizon", spec, out, false);
+}
+
+extern "C" int atmrt_horizon_device(atmrt_ctx* c, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* out) {
+  return horizon_run(c, "atmrt_horizon_device", spec, out, true);
+}
+
+extern "C" int atmrt_last_horizon_timings(atmrt_ctx* c, double out[5]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memcpy(out, c->horizon_timings, sizeof c->horizon_timings);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_horizon_work(atmrt_ctx* c, int32_t* batches, int32_t* table_rebuilt) {
+  if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
+  *batches = c->horizon_batches;
+  *table_rebuilt = c->horizon_rebuilt;
   return ATMRT_OK;
 }
 

@@ -455,9 +455,10 @@ enum PhaseEvent {
   EV_FINALIZE_BEGIN = EV_MARCH_END,
   EV_SIGHT_BEGIN = 0, EV_SIGHT_PROFILED, EV_SIGHT_SOLVED, EV_SIGHT_END,
   EV_VS_BEGIN = 0, EV_VS_PATHS, EV_VS_BATCH, EV_VS_PROFILED, EV_VS_SCANNED, EV_VS_END,
+  EV_HZ_BATCH = EV_VS_BATCH, EV_HZ_PROFILED, EV_HZ_SCANNED, EV_HZ_REFINED, EV_HZ_END, // after EV_VS_BEGIN and EV_VS_PATHS: the table is the viewshed's
   EV_LM_BEGIN = 0, EV_LM_UPLOADED, EV_LM_FIRST_PASS, EV_LM_SECOND_PASS, EV_LM_END,
 };
-static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_LM_END < EV_COUNT, "the borrowed events exist");
+static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_HZ_END < EV_COUNT && EV_LM_END < EV_COUNT, "the borrowed events exist");
 #ifndef ATMRT_FAST_SEGMENTS
 #define ATMRT_FAST_SEGMENTS 4
 #endif

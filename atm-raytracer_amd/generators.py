@@ -851,6 +851,63 @@ def write_viewshed_npz(path, v):
     np.savez_compressed(path, d=v.d, azimuths=v.azimuths, angles=v.angles, height=np.float64(v.height), **v.planes())
 
 
+# ---- horizon: per azimuth the bracket of elevation angles between terrain and sky, and the ridge that forms it (include/atmrt.h) ----
+HORIZON_DTYPE = np.dtype([("status", np.int32), ("rounds_done", np.int32), ("k_star", np.int32), ("block_index", np.int32)] +
+                         [(k, np.float64) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon",
+                                                    "block_elevation")])
+HORIZON_COLUMNS = ("azimuth_deg", "status", "angle_clear_deg", "angle_blocked_deg", "resolution_deg", "ridge_distance_m", "ridge_lat", "ridge_lon",
+                   "ridge_elevation_m")
+
+
+class Horizon:
+    """The records of one horizon call (HORIZON_DTYPE [n_az]) with azimuths [n_az] and angles [K] (the first fan)."""
+
+    def __init__(self, records, azimuths, angles):
+        self.records, self.azimuths, self.angles = records, azimuths, angles
+
+
+def horizon_kernel_shape(fan_rays=64, lib=None):
+    """atmrt_debug_horizon_shape: {'az_per_load', 'step_tile', 'rays_per_lane'} of the round-one scan at fan_rays."""
+    lib = lib or _lib.load()
+    a, t, r = C.c_int32(), C.c_int32(), C.c_int32()
+    lib.atmrt_debug_horizon_shape(int(fan_rays), C.byref(a), C.byref(t), C.byref(r))
+    return dict(az_per_load=a.value, step_tile=t.value, rays_per_lane=r.value)
+
+
+def horizon(ctx, az_lo_deg, az_step_deg, n_az, reach, fan=(-5.0, 5.0), fan_rays=64, rounds=3):
+    """atmrt_horizon against the parameters, atmosphere and terrain now set on `ctx`: for the n_az azimuths az_lo + j az_step, the
+    bracket [angle_blocked, angle_clear] between the highest ray that terrain within `reach` stops and the ray above it — the
+    refracted skyline to within `resolution` — and the ridge that stops it.  The first fan has fan_rays rays; every later round
+    narrows the bracket 63-fold.  No frame is needed.  Returns a Horizon."""
+    spec = _abi.HorizonSpec(float(az_lo_deg), float(az_step_deg), float(reach), float(fan[0]), float(fan[1]), int(n_az), int(fan_rays), int(rounds))
+    records = np.empty(max(int(n_az), 1), dtype=HORIZON_DTYPE)
+    ctx.check(ctx.lib.atmrt_horizon(ctx.handle, C.byref(spec), records.ctypes.data))
+    return Horizon(records, viewshed_azimuths(az_lo_deg, az_step_deg, n_az), viewshed_fan_angles(fan[0], fan[1], fan_rays, ctx.lib))
+
+
+def horizon_work(ctx):
+    """atmrt_last_horizon_timings / atmrt_last_horizon_work of the last horizon on `ctx`."""
+    out, n, rebuilt = (C.c_double * 5)(), C.c_int32(), C.c_int32()
+    ctx.check(ctx.lib.atmrt_last_horizon_timings(ctx.handle, out))
+    ctx.check(ctx.lib.atmrt_last_horizon_work(ctx.handle, C.byref(n), C.byref(rebuilt)))
+    return dict(zip(("paths_ms", "profiles_ms", "scan_ms", "refine_ms", "download_ms"), out), batches=n.value, table_rebuilt=bool(rebuilt.value))
+
+
+def write_horizon_csv(path, h):
+    """OUT.csv of gen --horizon: one row per azimuth (HORIZON_COLUMNS); numbers as repr() writes them, NaN as an empty field."""
+    import csv
+
+    def num(v):
+        return "" if np.isnan(v) else repr(float(v))
+
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(HORIZON_COLUMNS)
+        for az, r in zip(h.azimuths, h.records):
+            w.writerow([repr(float(az)), _abi.HORIZON_STATUS[int(r["status"])], num(r["angle_clear"]), num(r["angle_blocked"]), num(r["resolution"]),
+                        num(r["block_distance"]), num(r["block_lat"]), num(r["block_lon"]), num(r["block_elevation"])])
+
+
 # ---- the sight-line tables of the command line (gen --sight-lines FILE.csv) --------------------------------------------------
 SIGHT_COLUMNS = ("name", "azimuth_deg", "distance_m", "status", "angle_deg", "hidden_m", "ground_m", "resolution_deg", "block_distance_m",
                  "block_lat", "block_lon", "block_elevation_m", "x", "y")

@@ -79,6 +79,12 @@ int main(int argc, char** argv) {
         printf("viewshed azimuth %d m %d k_star %d status %d hidden %.17g ground %.17g block %d lat %.17g lon %.17g\n", j, v.m, v.k_star[o], v.status[o],
                v.hidden[o], v.ground[o], v.block_index[o], v.lat[o], v.lon[o]);
       }
+      // and where the skyline is along the same three azimuths, over the same fan (the same path table), narrowed twice
+      const std::vector<atmrt_horizon_t> hz = horizon(terrain, atmrt_horizon_spec_t{88.0, 2.0, 23700.0, -6.0, 6.0, 3, 128, 3});
+      for (size_t j = 0; j < hz.size(); j++)
+        printf("horizon azimuth %zu status %d rounds %d k_star %d block %d clear %.17g blocked %.17g resolution %.17g distance %.17g lat %.17g lon %.17g "
+               "elevation %.17g\n", j, hz[j].status, hz[j].rounds_done, hz[j].k_star, hz[j].block_index, hz[j].angle_clear, hz[j].angle_blocked,
+               hz[j].resolution, hz[j].block_distance, hz[j].block_lat, hz[j].block_lon, hz[j].block_elevation);
     }
     if (auto e = terrain.get_elev(46.5, 8.5)) printf("elevation under the observer: %.3f m\n", *e);
   } catch (const Error& e) {

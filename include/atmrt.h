@@ -657,6 +657,72 @@ int atmrt_last_viewshed_timings(atmrt_ctx* ctx, double out[4]);
 /* The batches that call took, and whether it rebuilt the path table (1) or found it (0). */
 int atmrt_last_viewshed_work(atmrt_ctx* ctx, int32_t* batches, int32_t* table_rebuilt);
 
+/* ---- horizon: for every azimuth of a fan, the elevation angle at which terrain ends and sky begins, with refraction, and which
+ * ridge forms it (no reference counterpart).  Like the viewshed it needs the context's parameters, atmosphere and terrain only; it
+ * neither needs nor disturbs a generated frame.
+ *
+ * THE RULE (tests/horizon_model.py restates it in numpy).  A call gives az_lo_deg, az_step_deg and 1 <= n_az <= 65536; reach [m],
+ * which gives m = the first index with d_m >= reach, 1 <= m <= 65535; a first fan [fan_lo_deg, fan_hi_deg] of K rays, K a multiple
+ * of 64 in [64, 4096]; and 1 <= rounds <= 4.
+ *   Shared with the viewshed, bit for bit (the same device functions produce them, and the same path table of the context holds the
+ *     heights under the same key): the azimuths az_j, the first fan's angles e_k, the lattice d_i, the profiles (lat, lon, T)_{j,i}
+ *     for 0 <= i <= m, and the ray heights H_{k,i}.
+ *   Blocking: c = H_{k,i} - T_{j,i}; a ray is BLOCKED at the first 1 <= i' <= m with c_{i'-1} * c_{i'} < 0.0 or H_{k,i'-1} < -1000.
+ *     i' = m is included (the sight lines' ray stops testing at m - 1).  A ray FAILS iff it is blocked or H_{k,m} is NaN.
+ *   Round one, over the K rays of the table: k* = one above the highest failing ray: 0 if none fails, K if ray K - 1 fails — the
+ *     highest failing ray, not the first clear one: an answer even where ducting makes rays cross.  k* = K: ATMRT_HORIZON_ABOVE_FAN;
+ *     k* = 0: ATMRT_HORIZON_BELOW_FAN; either stops the solve.  Otherwise ATMRT_HORIZON_FOUND with the bracket [e_{k*-1}, e_{k*}].
+ *   Rounds 2 to `rounds`: the fan is the sight lines' 64 angles over the bracket [lo, hi], delta = (hi - lo) / 63.0, e_k = lo +
+ *     (double)k * delta (atmrt_sight_fan_angles); every ray is integrated by the serial stepper and k* is picked in the same way.
+ *     0 < k* < 64: the bracket becomes [e_{k*-1}, e_{k*}].  k* = 0 or 64 (possible only through the last-bit difference between
+ *     e_63 and hi): the round is discarded, the bracket stays, the failing ray of record is that round's ray 0 — the same angle as
+ *     before, hence the same ray — and the solve stops.
+ * Every NaN of a record is the quiet NaN the sight lines write.  Equal calls return equal bytes: the solve uses no atomics and does
+ * not depend on the order in which wavefronts arrive. */
+typedef enum atmrt_horizon_status {
+  ATMRT_HORIZON_FOUND = 0,
+  ATMRT_HORIZON_ABOVE_FAN = 2, /* every ray of the first fan fails: the skyline lies above it (ATMRT_SIGHT_ABOVE_FAN's value) */
+  ATMRT_HORIZON_BELOW_FAN = 3  /* no ray of the first fan fails: the skyline lies below it (ATMRT_SIGHT_BELOW_FAN's value) */
+} atmrt_horizon_status;
+typedef struct atmrt_horizon_spec {
+  double az_lo_deg, az_step_deg; /* finite */
+  double reach;                  /* [m], finite, > 0 */
+  double fan_lo_deg, fan_hi_deg; /* the first fan: finite, increasing, at most 180 degrees apart */
+  int32_t n_az;                  /* 1 .. 65536 */
+  int32_t fan_rays;              /* K */
+  int32_t rounds;                /* 1 .. 4 */
+} atmrt_horizon_spec_t; /* 56 bytes: four of padding at the end */
+typedef struct atmrt_horizon {
+  int32_t status;        /* atmrt_horizon_status */
+  int32_t rounds_done;   /* rounds run, a discarded one included */
+  int32_t k_star;        /* round one's k* */
+  int32_t block_index;   /* the i' of the failing ray of record; -1 where it failed by NaN or where there is none */
+  double angle_clear;    /* upper end of the last bracket [deg]; e_0 for BELOW_FAN; NaN for ABOVE_FAN */
+  double angle_blocked;  /* lower end of the last bracket: the failing ray of record; e_{K-1} for ABOVE_FAN; NaN for BELOW_FAN */
+  double resolution;     /* the delta of the round that produced the bracket [deg] */
+  double block_distance, block_lat, block_lon, block_elevation; /* d, lat, lon, T at block_index — which ridge; NaN where it is -1 */
+} atmrt_horizon_t;
+/* A diagnostic like atmrt_debug_viewshed_shape, NOT part of the stable surface: the shape of THIS BUILD's round-one scan, so that
+ * tests can straddle it.  *az_per_load = the azimuths that share one load of a ray height, *step_tile = the steps between two
+ * looks at whether the wavefront may leave the step loop, *rays_per_lane = the rays a lane owns at fan_rays (0 for a fan_rays the
+ * call would refuse).  No result of atmrt_horizon depends on them.  Any pointer may be NULL. */
+int atmrt_debug_horizon_shape(int32_t fan_rays, int32_t* az_per_load, int32_t* step_tile, int32_t* rays_per_lane);
+/* n_az records into a host array.  The path table H[i][k] is the viewshed's own product under the viewshed's key: a horizon call
+ * after a viewshed call of the same fan, K, reach and setting does not rebuild it, nor the reverse.  Then per batch of azimuths
+ * (batched as the viewshed batches them; ATMRT_SIGHT_SCRATCH_BYTES lowers the limit here too, and the records do not depend on
+ * it): the profiles, the scan of the table (round one), and one wavefront per azimuth for the later rounds and the ridge.
+ * ATMRT_ERR_INVALID_ARGUMENT: a NULL spec or array, a number that is not finite, n_az, m, fan_rays or rounds out of range, a fan
+ * that is not increasing or wider than 180 degrees, a reach that is not positive, a path table of (m + 1) * K * 8 bytes above the
+ * (unlowered) scratch limit of 200 MiB.  ATMRT_ERR_STATE: before atmrt_set_params, and on a multi-device context. */
+int atmrt_horizon(atmrt_ctx* ctx, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* out);
+/* The same with the records written into caller-provided memory of the context's device: no download. */
+int atmrt_horizon_device(atmrt_ctx* ctx, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* out);
+/* Where the time of the last horizon call on ctx went, in milliseconds between events on the library's stream, the last four
+ * summed over its batches: out = {path table (0 when it was not rebuilt), profiles (upload included), scan, refine, download}. */
+int atmrt_last_horizon_timings(atmrt_ctx* ctx, double out[5]);
+/* The batches that call took, and whether it rebuilt the path table (1) or found it (0). */
+int atmrt_last_horizon_work(atmrt_ctx* ctx, int32_t* batches, int32_t* table_rebuilt);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —

@@ -339,4 +339,13 @@ inline Viewshed viewshed(const Terrain& terrain, const atmrt_viewshed_spec_t& sp
   return out;
 }
 
+// Horizon (no reference counterpart; include/atmrt.h states the rule): for every azimuth of spec the bracket of elevation angles
+// between the highest ray that terrain within spec.reach stops and the ray above it, and the ridge that stops it, from the observer
+// set on `terrain`'s context.  One record per azimuth.
+inline std::vector<atmrt_horizon_t> horizon(const Terrain& terrain, const atmrt_horizon_spec_t& spec) {
+  std::vector<atmrt_horizon_t> out((size_t)(spec.n_az > 0 ? spec.n_az : 0));
+  terrain.check(atmrt_horizon(terrain.ctx(), &spec, out.data()));
+  return out;
+}
+
 } // namespace atmrt_host
