@@ -1084,6 +1084,7 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   // the buffers of the previous frame are about to be reused (or reallocated): until this frame has succeeded there is nothing
   // atmrt_draw_image / atmrt_last_hits_device may touch
   c->last_valid = false;
+  c->last_ceil_rows = 0;
   c->stats = atmrt_frame_stats_t{};
   HIP_TRY(c, hipEventRecord(c->ev_t0, s));
   c->scan_segments = 0;
@@ -1166,6 +1167,9 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   c->last_hits = packed;
   c->last_offset = ws.hit_offset;
   c->last_nhits = c->last_packed ? counters[CTR_HITS] : 0;
+  c->last_ceil_rows = f.ceil ? f.march_steps + 1 : 0;
+  c->last_ceil_layout = f.ceil_layout;
+  c->last_ceil_serial = c->ceiling.serial();
   return ATMRT_OK;
 }
 
@@ -2658,6 +2662,28 @@ extern "C" int atmrt_debug_step_trig(atmrt_ctx* c, size_t cap, double* xs, doubl
   HIP_TRY(c, hipMemcpyAsync(cos_out, f.xs_cos, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_ceiling_table(atmrt_ctx* c, size_t cap, float* cell, float* suffix, int32_t* rows, int32_t* n_bins, double layout[3]) {
+  if (!c || !rows || !n_bins || !layout || (cap && (!cell || !suffix))) return ATMRT_ERR_INVALID_ARGUMENT;
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_ceiling_table(k_, cap, cell, suffix, rows, n_bins, layout));
+  *rows = *n_bins = 0;
+  layout[0] = layout[1] = layout[2] = 0.0;
+  if (!c->last_valid || !c->last_ceil_rows) return ATMRT_OK;
+  if (c->ceiling.serial() != c->last_ceil_serial)
+    return c->fail(ATMRT_ERR_STATE, "the ceiling table of the last frame is gone: a later call built another one in its place");
+  const CeilLayout& L = c->last_ceil_layout;
+  *rows = c->last_ceil_rows;
+  *n_bins = L.n_bins;
+  layout[0] = L.dir0, layout[1] = L.rel_lo, layout[2] = L.w;
+  const size_t total = (size_t)*rows * (size_t)(L.n_bins + 1), n = total < cap ? total : cap;
+  if (!n) return ATMRT_OK;
+  std::vector<CeilEntry> host(n);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(host.data(), c->d_ceil.as<CeilEntry>(), n * sizeof(CeilEntry), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < n; k++) cell[k] = host[k].cell, suffix[k] = host[k].suffix;
   return ATMRT_OK;
 }
 

@@ -174,6 +174,11 @@ struct atmrt_ctx {
   const uint64_t* last_offset = nullptr;
   uint64_t last_nhits = 0;
   uint64_t last_ray_steps = 0, last_escaped_steps = 0, last_escaped_rays = 0; // atmrt_last_march_work
+  // atmrt_debug_ceiling_table: the ceiling table that frame marched with — its rows (0: none), its bins and the build of
+  // `ceiling` (its serial) that filled d_ceil then; a later build overwrites the buffer
+  int32_t last_ceil_rows = 0;
+  atmrt::CeilLayout last_ceil_layout{};
+  uint64_t last_ceil_serial = 0;
 
   std::vector<atmrt::ObjectDev> objects; // host image of the device table (altitude kind in _pad until k_resolve)
   std::vector<uint8_t> textures;         // RGBA8 pool

@@ -112,6 +112,20 @@ class Context:
             arr = (C.c_int32 * len(cols))(*[int(v) for v in cols])
             self.check(self.lib.atmrt_debug_set_tiling(self.handle, arr, len(cols)))
 
+    def debug_ceiling_table(self):
+        """Diagnostic (atmrt_debug_ceiling_table): the terrain ceiling table the last generated frame marched with, as
+        {'rows', 'n_bins', 'layout': (dir0, rel_lo, w), 'cell', 'suffix'}, the planes float32 [rows][n_bins + 1]; rows == 0 and
+        empty planes when that frame had no table."""
+        rows, bins, lay = C.c_int32(), C.c_int32(), (C.c_double * 3)()
+        self.check(self.lib.atmrt_debug_ceiling_table(self.handle, 0, None, None, C.byref(rows), C.byref(bins), lay))
+        n = rows.value * (bins.value + 1) if rows.value else 0
+        cell, suffix = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+        if n:
+            self.check(self.lib.atmrt_debug_ceiling_table(self.handle, n, cell.ctypes.data, suffix.ctypes.data, C.byref(rows), C.byref(bins), lay))
+            assert rows.value * (bins.value + 1) == n
+        shape = (rows.value, bins.value + 1) if n else (0, 0)
+        return dict(rows=rows.value, n_bins=bins.value, layout=tuple(lay), cell=cell.reshape(shape), suffix=suffix.reshape(shape))
+
     def fail_next_collective(self, index=0, nth=1):
         """Test hook (atmrt_debug_fail_next_collective)."""
         self.check(self.lib.atmrt_debug_fail_next_collective(self.handle, index, nth))

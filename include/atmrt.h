@@ -890,6 +890,16 @@ int atmrt_math_probe(atmrt_ctx* ctx, int32_t op, size_t n, const double* a, cons
  * and the first min(cap, *n) of xs[k], sin(xs[k] / radius), cos(xs[k] / radius).  tests/test_gpu_step_trig.py compares them with
  * atmrt_math_probe's division and SINCOS: an entry must be the bit pattern a lane computes for that distance. */
 int atmrt_debug_step_trig(atmrt_ctx* ctx, size_t cap, double* xs, double* sin_out, double* cos_out, size_t* n);
+/* A diagnostic like atmrt_debug_step_trig, NOT part of the stable surface: the terrain ceiling table that
+ * the context's LAST GENERATED FRAME marched with, as the device holds it.  *rows = its rows (the march's steps + 1) and *n_bins
+ * its bins; layout = {dir0, rel_lo, w} of the bins in radians; cell and suffix receive the first min(cap, *rows x (*n_bins + 1))
+ * floats of the two planes, row i at i x (*n_bins + 1), the last column being the one of the rays outside the bins.  *rows = 0
+ * (and nothing written) when that frame had no table: ATMRT_CEILING=off, another generator than Rectilinear, another calculator
+ * than the Spherical one, or no frame yet.  A multi-device context answers for its first device, whose table holds the bins of
+ * that device's pixel-column tile.  ATMRT_ERR_STATE when a call after that frame (another set of parameters put through a
+ * harness or a tool such as atmrt_viewshed) has built another table in its place.  tests/test_gpu_ceiling_table.py compares the
+ * table with the one tests/csrc/ceiling_host.cpp builds on the host: every byte must be equal. */
+int atmrt_debug_ceiling_table(atmrt_ctx* ctx, size_t cap, float* cell, float* suffix, int32_t* rows, int32_t* n_bins, double layout[3]);
 
 #ifdef __cplusplus
 }

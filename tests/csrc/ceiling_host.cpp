@@ -4,9 +4,11 @@
 // point must lie at least the table's 1 m margin below the cell and the suffix of the ray's bin.
 //   ceiling_host CASE OUT
 // CASE (binary, little endian): 12 doubles {lat, lon, direction, fov, tilt, step, max_distance, radius, width, height, samples per
-// cell, seed}, int32 n_tiles, then per tile int32 {lat0, lon0, n_lat, n_lon} and n_lat x n_lon int16 posts (south to north, west to east).
+// cell (-4: no attack, the table alone), seed}, int32 n_tiles, then per tile int32 {lat0, lon0, n_lat, n_lon} (at most 3601 posts per
+// side) and n_lat x n_lon int16 posts (south to north, west to east).
 // OUT (binary): int32 {rows, n_bins}, doubles {dir0, rel_lo, w}, rows doubles xs, rows x (n_bins + 1) floats cell, the same of suffix,
-// int64 n_samples and per sample doubles {lat, lon, cell, suffix} — for the caller, who puts the same points through another lookup.
+// int64 n_samples and per sample doubles {lat, lon, cell, suffix} — for the caller, who puts the same points through another lookup —
+// then per sample int32 {step, bin, k}: the entry the sample read and its number within the cell (0 - 3: the edges, from 4: interior).
 // stdout: "rows R bins B samples S unbounded U uncovered C bad X"; exit status 1 when bad or uncovered is not 0.
 #include "../../atm-raytracer_amd/csrc/atmrt_ceiling.h"
 #include <cstdio>
@@ -39,7 +41,7 @@ int main(int argc, char** argv) {
   std::vector<TileDesc> descs;
   int lat_min = 1 << 30, lat_max = -(1 << 30), lon_min = 1 << 30, lon_max = -(1 << 30);
   for (Tile& t : tiles) {
-    if (!get(in, &t, 1) || t.n_lat < 2 || t.n_lon < 2 || t.n_lat > 301 || t.n_lon > 301) return 2;
+    if (!get(in, &t, 1) || t.n_lat < 2 || t.n_lon < 2 || t.n_lat > 3601 || t.n_lon > 3601) return 2;
     TileDesc td;
     td.offset = (int64_t)mosaic.size();
     td.n_lat = t.n_lat, td.n_lon = t.n_lon;
@@ -112,6 +114,7 @@ int main(int argc, char** argv) {
   // the attack: per step and bin the two edges (as the layout states them, and a rounding step to either side) and seeded interior
   // directions; each ray looks its own bin up, as the march does, wherever the rounding of ceiling_bin puts it
   std::vector<double> samples;
+  std::vector<int32_t> where;
   std::vector<int> seen((size_t)rows * stride, 0);
   long bad = 0, n_samples = 0;
   const double pi = CEIL_PI;
@@ -140,6 +143,7 @@ int main(int argc, char** argv) {
           if (bad++ < 5) printf("step %d bin %d direction %a: terrain %.17g at (%.17g, %.17g), cell %g suffix %g\n", i, bin, direction, elev, lat, lon, ce, su);
         }
         samples.push_back(lat), samples.push_back(lon), samples.push_back((double)ce), samples.push_back((double)su);
+        where.push_back(i), where.push_back(bin), where.push_back(k);
       }
     }
   }
@@ -161,6 +165,7 @@ int main(int argc, char** argv) {
   fwrite(suffix.data(), sizeof(float), suffix.size(), out);
   fwrite(&ns, sizeof ns, 1, out);
   fwrite(samples.data(), sizeof(double), samples.size(), out);
+  fwrite(where.data(), sizeof(int32_t), where.size(), out);
   fclose(out);
   printf("rows %d bins %d samples %ld unbounded %ld uncovered %ld bad %ld\n", rows, L.n_bins, n_samples, unbounded, uncovered, bad);
   return bad || uncovered ? 1 : 0;

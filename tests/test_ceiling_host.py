@@ -35,10 +35,10 @@ def _rough(seed, n_lat, n_lon):
     return np.random.default_rng(seed).integers(-50, 3000, size=(n_lat, n_lon)).astype(np.int16)
 
 
-def _run(exe, tmp_path, tiles, lat, lon, direction, step, max_distance, tilt=0.0, per_cell=3, seed=1):
+def _run(exe, tmp_path, tiles, lat, lon, direction, step, max_distance, tilt=0.0, per_cell=3, seed=1, fov=FOV):
     case, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
     with open(case, "wb") as f:
-        f.write(struct.pack("<12d", lat, lon, direction, FOV, tilt, step, max_distance, RADIUS, W, H, per_cell, seed))
+        f.write(struct.pack("<12d", lat, lon, direction, fov, tilt, step, max_distance, RADIUS, W, H, per_cell, seed))
         f.write(struct.pack("<i", len(tiles)))
         for (la, lo), posts in tiles.items():
             f.write(struct.pack("<4i", la, lo, posts.shape[0], posts.shape[1]))
@@ -55,9 +55,11 @@ def _run(exe, tmp_path, tiles, lat, lon, direction, step, max_distance, tilt=0.0
         suffix = np.frombuffer(f.read(4 * rows * (bins + 1)), dtype="<f4").reshape(rows, bins + 1)
         (n,) = struct.unpack("<q", f.read(8))
         samples = np.frombuffer(f.read(32 * n), dtype="<f8").reshape(n, 4)
+        where = np.frombuffer(f.read(12 * n), dtype="<i4").reshape(n, 3)  # step, bin, number within the cell
+        assert len(where) == n and not f.read(1)
     assert stat["rows"] == rows and stat["bins"] == bins and stat["samples"] == n and stat["bad"] == 0 and stat["uncovered"] == 0
     assert n >= rows * bins * (per_cell + 2)
-    return dict(stat=stat, xs=xs, cell=cell, suffix=suffix, samples=samples, layout=(dir0, rel_lo, w))
+    return dict(stat=stat, xs=xs, cell=cell, suffix=suffix, samples=samples, where=where, layout=(dir0, rel_lo, w))
 
 
 def _oracle_agrees(oracle, tiles, samples):
