@@ -6,6 +6,7 @@
                                     [--sight-lines FILE.csv [--sight-out OUT.csv] [--sight-fan LO HI] [--sight-rounds N]]
                                     [--viewshed OUT.npz [--viewshed-az LO HI N] [--viewshed-reach M] [--viewshed-height M]
                                      [--viewshed-fan LO HI K]]
+                                    [--viewshed-map OUT.npz [--map-cell ARCSEC] [--viewshed-observers FILE.csv]]
                                     [--horizon OUT.csv [--horizon-az LO HI N] [--horizon-reach M] [--horizon-fan LO HI K]
                                      [--horizon-rounds N]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
@@ -39,6 +40,12 @@ frame's field of view at one azimuth per pixel column unless said otherwise) and
 LO and HI degrees (--viewshed-fan, -5 5 64), and how many metres of it are hidden.  OUT.npz holds the planes k_star, status (0 seen,
 1 hidden, 2 above_fan, 3 below_fan), hidden, block_index, ground, lat and lon as [N][m] arrays, the lattice d, the azimuths, the
 fan's angles and the height.
+`--viewshed-map` (no reference counterpart) bins that viewshed (the same --viewshed-az, -reach, -height and -fan) over a latitude /
+longitude grid on the device, --map-cell arcseconds a cell (3), laid around the observer as far as the lattice reaches: OUT.npz holds
+n_samples, n_seen and min_hidden as [n_lat][n_lon] arrays, rows south to north, the grid's lat0, lon0, cell_lat, cell_lon, n_lat, n_lon
+and the call's stats_n_samples, stats_n_binned, stats_n_outside, stats_n_skipped, stats_n_seen.  With --viewshed-observers FILE.csv
+(columns lat, lon, altitude — of the configured altitude kind) it is the cumulative form over a grid that holds every observer's
+reach: observers_seeing (from how many observers a cell is seen) and min_hidden (the smallest over them), and the grid.
 `--horizon` (no reference counterpart) asks where the skyline is: for N azimuths from LO to HI (--horizon-az; one per pixel column of
 the frame unless said otherwise) and the terrain within --horizon-reach (max_distance), the refracted elevation angle at which
 terrain ends and sky begins, bracketed between the highest blocked ray and the ray above it — first fan --horizon-fan (-5 5 64),
@@ -175,6 +182,48 @@ def write_viewshed(ctx, cfg, path, az, reach, height, fan):
     return v
 
 
+def read_observers_csv(path):
+    """FILE.csv of --viewshed-observers: a header naming lat, lon and altitude, one observer per row -> [{lat, lon, altitude}]."""
+    import csv
+    with open(path, newline="") as f:
+        rows = list(csv.DictReader(f))
+    try:
+        return [dict(lat=float(r["lat"]), lon=float(r["lon"]), altitude=float(r["altitude"])) for r in rows]
+    except (KeyError, TypeError, ValueError) as exc:
+        raise config.ConfigError(f"{path}: every row needs the numbers lat, lon and altitude ({exc})")
+
+
+def write_viewshed_map(ctx, cfg, gen, path, cell_arcsec, az, reach, height, fan, observers_path=None):
+    """The viewshed map of the context's parameters, atmosphere and terrain to an .npz over the grid viewshed_map_grid lays around the
+    observer (as far as the lattice's last sample); with observers_path the cumulative form over a grid that holds every observer's
+    reach.  Returns what it wrote: a ViewshedMap, or (observers_seeing, min_hidden) as numpy arrays."""
+    if not (cell_arcsec > 0 and np.isfinite(cell_arcsec)):
+        raise config.ConfigError("--map-cell must be a positive number of arcseconds")
+    lo, step, n, reach = viewshed_defaults(cfg, az, reach)
+    if float(fan[2]) != int(fan[2]):
+        raise config.ConfigError("--viewshed-fan LO HI K: K must be a whole number")
+    fan, K, cell = (float(fan[0]), float(fan[1])), int(fan[2]), cell_arcsec / 3600.0
+    far = float(generators.viewshed_lattice(cfg.params.simulation_step, reach)[-1])
+    with open(path, "wb") as f:  # a file object: numpy appends no extension to the name the user gave
+        if observers_path is None:
+            pos = cfg.params.position
+            grid = generators.viewshed_map_grid(pos.latitude, pos.longitude, far, cell)
+            v = generators.viewshed_map(ctx, grid, lo, step, n, reach, height, fan, K)
+            generators.write_viewshed_map_npz(f, grid, dict(n_samples=v.n_samples, n_seen=v.n_seen, min_hidden=v.min_hidden), v.stats)
+            return v
+        observers = read_observers_csv(observers_path)
+        if not observers:
+            raise config.ConfigError(f"{observers_path} holds no observer")
+        grids = [generators.viewshed_map_grid(o["lat"], o["lon"], far, cell) for o in observers]
+        bounds = (min(g.lat0 for g in grids), max(g.lat0 + g.n_lat * g.cell_lat for g in grids) - 0.5 * cell,
+                  min(g.lon0 for g in grids), max(g.lon0 + g.n_lon * g.cell_lon for g in grids) - 0.5 * cell)
+        grid = generators.snap_grid(bounds, cell)
+        seeing, minh = generators.cumulative_viewshed(gen, observers, grid, lo, step, n, reach, height, fan, K)
+        seeing, minh = seeing.cpu().numpy().view(np.uint32), minh.cpu().numpy()
+        generators.write_viewshed_map_npz(f, grid, dict(observers_seeing=seeing, min_hidden=minh))
+        return seeing, minh
+
+
 def write_horizon(ctx, cfg, path, az, reach, fan, rounds):
     """The horizon of the context's parameters, atmosphere and terrain to a .csv; returns the Horizon."""
     lo, step, n, reach = viewshed_defaults(cfg, az, reach, "--horizon-az")
@@ -235,6 +284,9 @@ def cmd_gen(a):
     if a.horizon:  # likewise
         stamp("Solving the horizon...")
         write_horizon(ctx, cfg, a.horizon, a.horizon_az, a.horizon_reach, a.horizon_fan, a.horizon_rounds)
+    if a.viewshed_map:  # likewise
+        stamp("Binning the viewshed map...")
+        write_viewshed_map(ctx, cfg, gen, a.viewshed_map, a.map_cell, a.viewshed_az, a.viewshed_reach, a.viewshed_height, a.viewshed_fan, a.viewshed_observers)
     img = Image.fromarray(rgb_dev.cpu().numpy(), "RGB")
     draw_labels(img, ticks)
     if located:
@@ -332,6 +384,8 @@ def main(argv=None):
     g.add_argument("--viewshed-reach", type=float, default=None, metavar="M")
     g.add_argument("--viewshed-height", type=float, default=0.0, metavar="M")
     g.add_argument("--viewshed-fan", type=float, nargs=3, default=(-5.0, 5.0, 64), metavar=("LO", "HI", "K"))
+    g.add_argument("--viewshed-map", default=None, metavar="OUT.npz")
+    g.add_argument("--viewshed-observers", default=None, metavar="FILE.csv")
     g.add_argument("--horizon", default=None, metavar="OUT.csv")
     g.add_argument("--horizon-az", type=float, nargs=3, default=None, metavar=("LO", "HI", "N"))
     g.add_argument("--horizon-reach", type=float, default=None, metavar="M")

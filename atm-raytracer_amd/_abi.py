@@ -198,6 +198,11 @@ class ViewshedSpec(C.Structure):
         [("n_az", C.c_int32), ("fan_rays", C.c_int32)]
 
 
+class ViewshedMapStats(C.Structure):
+    """atmrt_viewshed_map_stats_t: n_samples = n_binned + n_outside + n_skipped, of one call."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_samples", "n_binned", "n_outside", "n_skipped", "n_seen")]
+
+
 # atmrt_horizon_status: the last two have the values of the sight statuses of the same meaning
 HORIZON_FOUND, HORIZON_ABOVE_FAN, HORIZON_BELOW_FAN = 0, SIGHT_ABOVE_FAN, SIGHT_BELOW_FAN
 HORIZON_STATUS = {HORIZON_FOUND: "found", HORIZON_ABOVE_FAN: "above_fan", HORIZON_BELOW_FAN: "below_fan"}

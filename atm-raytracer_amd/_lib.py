@@ -127,6 +127,9 @@ def load():
         "atmrt_viewshed_steps": (C.c_int, [vp, dbl, C.POINTER(i32)]),
         "atmrt_last_viewshed_timings": (C.c_int, [vp, pd]),
         "atmrt_last_viewshed_work": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "atmrt_viewshed_map_planes_device": (C.c_int, [vp, C.POINTER(_abi.GeoGrid), sz, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(_abi.ViewshedMapStats)]),
+        "atmrt_viewshed_map_device": (C.c_int, [vp, C.POINTER(_abi.ViewshedSpec), C.POINTER(_abi.GeoGrid), i32, vp, vp, vp, C.POINTER(_abi.ViewshedMapStats)]),
+        "atmrt_viewshed_map": (C.c_int, [vp, C.POINTER(_abi.ViewshedSpec), C.POINTER(_abi.GeoGrid), i32, vp, vp, vp, C.POINTER(_abi.ViewshedMapStats)]),
         "atmrt_debug_horizon_shape": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "atmrt_horizon": (C.c_int, [vp, C.POINTER(_abi.HorizonSpec), vp]),
         "atmrt_horizon_device": (C.c_int, [vp, C.POINTER(_abi.HorizonSpec), vp]),
@@ -177,6 +180,7 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_locate_landmarks_planes_device", "atmrt_last_landmark_timings", "atmrt_landmark_index_probe", "atmrt_sight_fan_angles", "atmrt_sight_pick",
             "atmrt_sight_lines", "atmrt_sight_fan_probe", "atmrt_last_sight_timings", "atmrt_last_sight_batches", "atmrt_viewshed_fan_angles",
             "atmrt_debug_viewshed_shape", "atmrt_viewshed_steps", "atmrt_viewshed", "atmrt_viewshed_device", "atmrt_last_viewshed_timings", "atmrt_last_viewshed_work",
+            "atmrt_viewshed_map_planes_device", "atmrt_viewshed_map_device", "atmrt_viewshed_map",
             "atmrt_debug_horizon_shape", "atmrt_horizon", "atmrt_horizon_device", "atmrt_last_horizon_timings", "atmrt_last_horizon_work", "atmrt_ray_paths", "atmrt_atmosphere_sample",
             "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_debug_step_trig", "atmrt_debug_ceiling_table", "atmrt_result_encode_bincode",
             "atmrt_result_decode_bincode", "atmrt_comm_unique_id", "atmrt_ctx_comm_init_rank", "atmrt_ctx_comm_init_external", "atmrt_ctx_comm_init_external_device",

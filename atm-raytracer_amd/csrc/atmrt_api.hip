@@ -24,6 +24,7 @@
 #include "atmrt_render.h"
 #include "atmrt_sight.h"
 #include "atmrt_viewshed.h"
+#include "atmrt_viewshed_map.h"
 #include "atmrt_horizon.h"
 #include "atmrt_tiff.h"
 
@@ -155,6 +156,8 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 28: return sizeof(atmrt_viewshed_spec_t);
     case 30: return sizeof(atmrt_horizon_spec_t);
     case 31: return sizeof(atmrt_horizon_t);
+    // 32 stays 0
+    case 33: return sizeof(atmrt_viewshed_map_stats_t);
     default: return 0;
   }
 }
@@ -2231,7 +2234,8 @@ extern "C" int atmrt_debug_viewshed_shape(int32_t fan_rays, int32_t* az_per_load
 namespace {
 
 // everything a batch of nb azimuths carves from d_sight: the sight lines' layout (dtab first: it stays where the call put it), then
-// the planes of the host route (`staged`: null pointers where the caller asked for none)
+// the planes of the host route and of the map (`staged`: null pointers where the caller asked for none; of `asked` only which
+// pointers are null matters)
 void viewshed_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, const ViewshedPlanes& asked, bool stage, atmrt_sight_target_t*& targets,
                     SightMeta*& meta, SightBatch& b, double*& dtab, ViewshedPlanes& staged) {
   double* none = nullptr;
@@ -2240,7 +2244,8 @@ void viewshed_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, const Viewshed
   staged = ViewshedPlanes{};
   if (!stage) return;
   const size_t cells = nb * m;
-  k(staged.k_star, cells * 2), k(staged.status, cells), k(staged.hidden, cells * 8);
+  if (asked.k_star) k(staged.k_star, cells * 2);
+  k(staged.status, cells), k(staged.hidden, cells * 8);
   if (asked.block_index) k(staged.block_index, cells * 4);
   if (asked.ground) k(staged.ground, cells * 8);
   if (asked.lat) k(staged.lat, cells * 8);
@@ -2296,9 +2301,40 @@ int viewshed_paths_refresh(atmrt_ctx* c, const Frame& f, double fan_lo_deg, doub
   return ATMRT_OK;
 }
 
-int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* spec, const ViewshedPlanes& dst, bool device_planes) {
+// The map a fused call scatters its batches into (atmrt_viewshed_map*): device planes on c's device.
+struct ViewshedMapSink {
+  atmrt_geo_grid_t grid;
+  VsMapPlanes planes;
+  bool accumulate;
+  atmrt_viewshed_map_stats_t* stats; // may be null
+};
+
+// The checks the three map entry points share; 0 or a status with the message set.
+int viewshed_map_check(atmrt_ctx* c, const char* what, const atmrt_geo_grid_t* grid, const void* n_samples, const void* n_seen) {
+  if (!grid || !n_samples || !n_seen) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: grid, n_samples or n_seen is NULL", what);
+  if (const char* msg = geo_grid_check(*grid)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  return ATMRT_OK;
+}
+
+// The call's statistics block, read back once every scatter of the call has run.
+int viewshed_map_stats(atmrt_ctx* c, atmrt_viewshed_map_stats_t* stats) {
+  uint64_t block[VSMAP_N] = {};
+  HIP_TRY(c, hipMemcpyAsync(block, c->d_vsmap.ptr, sizeof block, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  if (stats) *stats = atmrt_viewshed_map_stats_t{block[VSMAP_SAMPLES], block[VSMAP_BINNED], block[VSMAP_OUTSIDE], block[VSMAP_SKIPPED], block[VSMAP_SEEN]};
+  return ATMRT_OK;
+}
+
+// map == nullptr: the viewshed into dst (host arrays, or device_planes).  map != nullptr: dst is empty; every batch's status, hidden,
+// lat and lon are staged in d_sight like the host route's planes and scattered into the map where the host route downloads.
+int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* spec, const ViewshedPlanes& dst_in, bool device_planes,
+                 const ViewshedMapSink* map = nullptr) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!spec || !dst.k_star || !dst.status || !dst.hidden) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec, k_star, status or hidden is NULL", what);
+  static double mark; // a plane the map asks of the scan: only that the pointer is not null matters
+  const ViewshedPlanes dst = map ? ViewshedPlanes{nullptr, reinterpret_cast<uint8_t*>(&mark), &mark, nullptr, nullptr, &mark, &mark} : dst_in;
+  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
+  if (!map && (!dst.k_star || !dst.status || !dst.hidden)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec, k_star, status or hidden is NULL", what);
   const atmrt_viewshed_spec_t v = *spec;
   std::vector<atmrt_sight_target_t> targets;
   SightPlan plan;
@@ -2338,6 +2374,11 @@ int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* sp
   HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
   std::vector<SightMeta> meta(nb_max);
   for (size_t t = 0; t < nb_max; t++) meta[t] = SightMeta{t * ((size_t)m + 1), m, 0};
+  if (map) {
+    HIP_TRY(c, c->d_vsmap.reserve(VSMAP_N * sizeof(uint64_t)));
+    launch_vsmap_reset(c->d_vsmap.ptr, s);
+    if (!map->accumulate) launch_vsmap_clear(map->grid, map->planes, s);
+  }
   size_t n_batches = 0;
   for (size_t j0 = 0; j0 < (size_t)v.n_az; j0 += nb_max, n_batches++) {
     const size_t nb = std::min(nb_max, (size_t)v.n_az - j0), cells = nb * (size_t)m, at = j0 * (size_t)m;
@@ -2361,7 +2402,9 @@ int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* sp
     }
     launch_viewshed_scan(scan, s);
     HIP_TRY(c, hipEventRecord(c->ev[EV_VS_SCANNED], s));
-    if (!device_planes) {
+    if (map) {
+      launch_vsmap_scatter(VsMapSamples{cells, staged.status, staged.hidden, staged.lat, staged.lon}, map->grid, map->planes, c->d_vsmap.ptr, s);
+    } else if (!device_planes) {
       HIP_TRY(c, hipMemcpyAsync(dst.k_star + at, staged.k_star, cells * 2, hipMemcpyDeviceToHost, s));
       HIP_TRY(c, hipMemcpyAsync(dst.status + at, staged.status, cells, hipMemcpyDeviceToHost, s));
       HIP_TRY(c, hipMemcpyAsync(dst.hidden + at, staged.hidden, cells * 8, hipMemcpyDeviceToHost, s));
@@ -2382,6 +2425,7 @@ int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* sp
   memcpy(c->viewshed_timings, ms_sum, sizeof ms_sum);
   c->viewshed_batches = (int32_t)n_batches;
   c->viewshed_rebuilt = rebuilt ? 1 : 0;
+  if (map) return viewshed_map_stats(c, map->stats);
   return ATMRT_OK;
 }
 
@@ -2418,6 +2462,63 @@ extern "C" int atmrt_last_viewshed_work(atmrt_ctx* c, int32_t* batches, int32_t*
   if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
   *batches = c->viewshed_batches;
   *table_rebuilt = c->viewshed_rebuilt;
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// viewshed map (include/atmrt.h; kernels in atmrt_viewshed_map.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int atmrt_viewshed_map_planes_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, size_t n, const uint8_t* status, const double* hidden,
+                                                const double* lat, const double* lon, int32_t accumulate, uint32_t* n_samples, uint32_t* n_seen,
+                                                double* min_hidden, atmrt_viewshed_map_stats_t* stats) {
+  const char* what = "atmrt_viewshed_map_planes_device";
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = viewshed_map_check(c, what, grid, n_samples, n_seen)) return rc;
+  if (n > VSMAP_SAMPLES_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n exceeds (2^31 - 1) * 256 samples", what);
+  if (n && (!status || !hidden || !lat || !lon)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: status, hidden, lat or lon is NULL", what);
+  if (int rc = sight_check_state(c, what)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const VsMapPlanes map{n_samples, n_seen, min_hidden};
+  HIP_TRY(c, c->d_vsmap.reserve(VSMAP_N * sizeof(uint64_t)));
+  launch_vsmap_reset(c->d_vsmap.ptr, s);
+  if (!accumulate) launch_vsmap_clear(*grid, map, s);
+  launch_vsmap_scatter(VsMapSamples{n, status, hidden, lat, lon}, *grid, map, c->d_vsmap.ptr, s);
+  return viewshed_map_stats(c, stats);
+}
+
+extern "C" int atmrt_viewshed_map_device(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, const atmrt_geo_grid_t* grid, int32_t accumulate,
+                                         uint32_t* n_samples, uint32_t* n_seen, double* min_hidden, atmrt_viewshed_map_stats_t* stats) {
+  const char* what = "atmrt_viewshed_map_device";
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
+  if (int rc = viewshed_map_check(c, what, grid, n_samples, n_seen)) return rc;
+  const ViewshedMapSink sink{*grid, VsMapPlanes{n_samples, n_seen, min_hidden}, accumulate != 0, stats};
+  return viewshed_run(c, what, spec, ViewshedPlanes{}, false, &sink);
+}
+
+extern "C" int atmrt_viewshed_map(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, const atmrt_geo_grid_t* grid, int32_t accumulate,
+                                  uint32_t* n_samples, uint32_t* n_seen, double* min_hidden, atmrt_viewshed_map_stats_t* stats) {
+  const char* what = "atmrt_viewshed_map";
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
+  if (int rc = viewshed_map_check(c, what, grid, n_samples, n_seen)) return rc;
+  if (int rc = sight_check_state(c, what)) return rc; // before the staging buffer is touched
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n_cells = (size_t)grid->n_lat * grid->n_lon, count_bytes = Carve::pad(n_cells * sizeof(uint32_t));
+  HIP_TRY(c, c->d_io.reserve(2 * count_bytes + n_cells * sizeof(double)));
+  uint32_t *d_samples = c->d_io.as<uint32_t>(), *d_seen = reinterpret_cast<uint32_t*>(c->d_io.as<char>() + count_bytes);
+  double* d_min = min_hidden ? reinterpret_cast<double*>(c->d_io.as<char>() + 2 * count_bytes) : nullptr;
+  if (accumulate) {
+    HIP_TRY(c, hipMemcpy(d_samples, n_samples, n_cells * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_seen, n_seen, n_cells * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (min_hidden) HIP_TRY(c, hipMemcpy(d_min, min_hidden, n_cells * sizeof(double), hipMemcpyHostToDevice));
+  }
+  const ViewshedMapSink sink{*grid, VsMapPlanes{d_samples, d_seen, d_min}, accumulate != 0, stats};
+  if (int rc = viewshed_run(c, what, spec, ViewshedPlanes{}, false, &sink)) return rc;
+  HIP_TRY(c, hipMemcpy(n_samples, d_samples, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(n_seen, d_seen, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (min_hidden) HIP_TRY(c, hipMemcpy(min_hidden, d_min, n_cells * sizeof(double), hipMemcpyDeviceToHost));
   return ATMRT_OK;
 }
 

@@ -212,6 +212,7 @@ struct atmrt_ctx {
   atmrt::Cached<atmrt::ViewshedKey> viewshed_paths;
   double viewshed_timings[4] = {};         // atmrt_last_viewshed_timings
   int32_t viewshed_batches = 0, viewshed_rebuilt = 0; // atmrt_last_viewshed_work
+  atmrt::DevBuf d_vsmap;                   // atmrt_viewshed_map*: the call's statistics block (40 B)
   double horizon_timings[5] = {};          // atmrt_last_horizon_timings
   int32_t horizon_batches = 0, horizon_rebuilt = 0;   // atmrt_last_horizon_work
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)

@@ -31,7 +31,7 @@ ATMRT_HD int viewshed_rays_per_lane(int K) { return K <= 256 ? 1 : K <= 1024 ? 2
 ATMRT_HD int viewshed_waves(int K) { return (K / 64 + viewshed_rays_per_lane(K) - 1) / viewshed_rays_per_lane(K); }
 
 // ---- launch interface -----------------------------------------------------------------------------------------------------------------
-struct ViewshedPlanes { // [n_az][m], entry j * m + (i - 1); the last four may be null
+struct ViewshedPlanes { // [n_az][m], entry j * m + (i - 1); the last four may be null, and k_star where the viewshed map asks
   uint16_t* k_star;
   uint8_t* status;
   double* hidden;
@@ -47,7 +47,7 @@ struct ViewshedScan {
   ViewshedPlanes out;
 };
 static inline size_t viewshed_cell_bytes(const ViewshedPlanes& p) { // of the planes asked for
-  return 2 + 1 + 8 + (p.block_index ? 4 : 0) + (p.ground ? 8 : 0) + (p.lat ? 8 : 0) + (p.lon ? 8 : 0);
+  return (p.k_star ? 2 : 0) + 1 + 8 + (p.block_index ? 4 : 0) + (p.ground ? 8 : 0) + (p.lat ? 8 : 0) + (p.lon ? 8 : 0);
 }
 void launch_viewshed_paths(const Frame& f, double lo, double hi, int K, int m, double* H, hipStream_t stream);
 void launch_viewshed_scan(const ViewshedScan& s, hipStream_t stream);
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256 * R) void k_viewshed_scan(ViewshedScan s) {
         if (hidden != hidden) hidden = qnan();
       }
       const size_t o = (size_t)j * m + (i - 1);
-      s.out.k_star[o] = (uint16_t)ks;
+      if (s.out.k_star) s.out.k_star[o] = (uint16_t)ks;
       s.out.status[o] = (uint8_t)(ks == K ? ATMRT_SIGHT_ABOVE_FAN : ks == 0 ? ATMRT_SIGHT_BELOW_FAN : block >= 0 ? ATMRT_SIGHT_HIDDEN : ATMRT_SIGHT_SEEN);
       s.out.hidden[o] = hidden;
       if (s.out.block_index) s.out.block_index[o] = block;

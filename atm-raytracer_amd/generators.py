@@ -865,6 +865,130 @@ def write_viewshed_npz(path, v):
     np.savez_compressed(path, d=v.d, azimuths=v.azimuths, angles=v.angles, height=np.float64(v.height), **v.planes())
 
 
+# ---- viewshed map: the polar viewshed binned over a latitude / longitude grid on the device (include/atmrt.h) -----------------
+VIEWSHED_MAP_PLANES = (("n_samples", np.uint32), ("n_seen", np.uint32), ("min_hidden", np.float64))
+VIEWSHED_MAP_RADIUS = 6_371_000.0  # the sphere viewshed_map_grid lays its bounds on
+
+
+class ViewshedMap:
+    """One viewshed map: n_samples, n_seen (uint32) and min_hidden (float64, +inf where no sample takes part), each [n_lat][n_lon] —
+    numpy arrays on the host route, the caller's torch tensors on the device route (the counts as int32, the bits of the u32) —
+    with the grid and stats (the atmrt_viewshed_map_stats_t of the call, a dict)."""
+
+    def __init__(self, grid, n_samples, n_seen, min_hidden, stats):
+        self.grid, self.n_samples, self.n_seen, self.min_hidden, self.stats = grid, n_samples, n_seen, min_hidden, stats
+
+
+def _vsmap_stats(st):
+    return {k: getattr(st, k) for k, _ in _abi.ViewshedMapStats._fields_}
+
+
+def viewshed_map_tensors(grid, device):
+    """The three planes of a map on `grid` as torch tensors on `device` (uninitialised: a call without accumulate overwrites them)."""
+    import torch
+    shape = (grid.n_lat, grid.n_lon)
+    return dict(n_samples=torch.empty(shape, dtype=torch.int32, device=device), n_seen=torch.empty(shape, dtype=torch.int32, device=device),
+                min_hidden=torch.empty(shape, dtype=torch.float64, device=device))
+
+
+def _vsmap_into(grid, into):
+    for k, _ in VIEWSHED_MAP_PLANES:
+        t = into[k]
+        if tuple(t.shape) != (grid.n_lat, grid.n_lon) or not t.is_contiguous() or t.element_size() != (8 if k == "min_hidden" else 4):
+            raise ValueError(f"into[{k!r}] must be a contiguous [n_lat][n_lon] tensor of {'float64' if k == 'min_hidden' else 'int32'}")
+    return [into[k].data_ptr() for k, _ in VIEWSHED_MAP_PLANES]
+
+
+def viewshed_map(ctx, grid, az_lo_deg, az_step_deg, n_az, reach, height=0.0, fan=(-5.0, 5.0), fan_rays=64, accumulate=False, into=None):
+    """atmrt_viewshed_map against the parameters, atmosphere and terrain now set on `ctx`: the viewshed of the call's lattice (see
+    viewshed) binned over `grid` on the device, without its planes ever leaving it.  accumulate adds to a map that is already there:
+    `into`, a dict of torch device tensors n_samples, n_seen (int32) and min_hidden (float64) as viewshed_map_tensors makes them —
+    the device route, nothing is downloaded — or, on the host route, the arrays of a ViewshedMap passed as `into`.  Returns a ViewshedMap."""
+    spec = _abi.ViewshedSpec(float(az_lo_deg), float(az_step_deg), float(reach), float(height), float(fan[0]), float(fan[1]), int(n_az), int(fan_rays))
+    st = _abi.ViewshedMapStats()
+    if isinstance(into, dict):
+        ctx.check(ctx.lib.atmrt_viewshed_map_device(ctx.handle, C.byref(spec), C.byref(grid), int(bool(accumulate)), *_vsmap_into(grid, into), C.byref(st)))
+        return ViewshedMap(grid, into["n_samples"], into["n_seen"], into["min_hidden"], _vsmap_stats(st))
+    if into is not None:
+        arrays = {k: np.ascontiguousarray(getattr(into, k), dtype=t) for k, t in VIEWSHED_MAP_PLANES}
+    elif accumulate:
+        raise ValueError("accumulate needs the map to add to: pass it as `into`")
+    else:
+        arrays = {k: np.empty((grid.n_lat, grid.n_lon), dtype=t) for k, t in VIEWSHED_MAP_PLANES}
+    ctx.check(ctx.lib.atmrt_viewshed_map(ctx.handle, C.byref(spec), C.byref(grid), int(bool(accumulate)), *[arrays[k].ctypes.data for k, _ in VIEWSHED_MAP_PLANES],
+                                         C.byref(st)))
+    return ViewshedMap(grid, stats=_vsmap_stats(st), **arrays)
+
+
+def viewshed_map_planes(ctx, grid, status, hidden, lat, lon, accumulate=False, into=None):
+    """atmrt_viewshed_map_planes_device: any samples — torch device tensors status (uint8), hidden, lat, lon (float64) of one size,
+    e.g. the planes of atmrt_viewshed_device — binned over `grid` into torch device tensors (`into`, else new ones).  Returns a ViewshedMap."""
+    n = status.numel()
+    if not (hidden.numel() == lat.numel() == lon.numel() == n) or status.element_size() != 1 or any(t.element_size() != 8 for t in (hidden, lat, lon)):
+        raise ValueError("status (uint8), hidden, lat and lon (float64) must hold the same number of samples")
+    if not all(t.is_contiguous() for t in (status, hidden, lat, lon)):
+        raise ValueError("the sample planes must be contiguous")
+    if into is None:
+        if accumulate:
+            raise ValueError("accumulate needs the map to add to: pass it as `into`")
+        into = viewshed_map_tensors(grid, status.device)
+    st = _abi.ViewshedMapStats()
+    ctx.check(ctx.lib.atmrt_viewshed_map_planes_device(ctx.handle, C.byref(grid), n, status.data_ptr(), hidden.data_ptr(), lat.data_ptr(), lon.data_ptr(),
+                                                       int(bool(accumulate)), *_vsmap_into(grid, into), C.byref(st)))
+    return ViewshedMap(grid, into["n_samples"], into["n_seen"], into["min_hidden"], _vsmap_stats(st))
+
+
+def viewshed_map_grid(lat, lon, reach, cell_deg):
+    """The grid of cell_deg cells, snapped by snap_grid's rule, that holds every point within `reach` metres of (lat, lon) on the
+    sphere of 6,371 km — the cap's extreme latitudes lat +- reach / R, its extreme longitudes lon +- asin(sin(reach / R) / cos(lat)),
+    every longitude once the cap holds a pole — with one cell of margin on every side.  There is no antimeridian handling (GeoGrid):
+    the longitudes are plain numbers around `lon`.  On other earth models, and for the lattice's last sample where it lies beyond
+    `reach`, samples may leave the grid: the map counts them n_outside."""
+    delta = float(reach) / VIEWSHED_MAP_RADIUS
+    ddeg = np.degrees(delta)
+    lat_lo, lat_hi = max(lat - ddeg, -90.0), min(lat + ddeg, 90.0)
+    if delta >= np.pi / 2 or abs(lat) + ddeg >= 90.0:
+        half = 180.0
+    else:
+        half = float(np.degrees(np.arcsin(min(1.0, np.sin(delta) / np.cos(np.radians(lat))))))
+    return snap_grid((lat_lo - cell_deg, lat_hi + cell_deg, lon - half - cell_deg, lon + half + cell_deg), cell_deg)
+
+
+def cumulative_viewshed(gen, observers, grid, az_lo_deg, az_step_deg, n_az, reach, height=0.0, fan=(-5.0, 5.0), fan_rays=64):
+    """From how many observers each cell of `grid` is seen: for every observer {lat, lon, altitude} (altitude of the kind the
+    generator's parameters give) the position is set on gen's context, one fresh map is made on device tensors, and (n_seen > 0) is
+    added into observers_seeing with torch — the plumbing; the map is the kernels'.  Returns (observers_seeing int32 — the bits of
+    the u32 counts — and the cell-wise minimum min_hidden over the observers, float64), torch tensors [n_lat][n_lon] on the device.
+    The generator's own position is set on the context again afterwards."""
+    import torch
+    ctx = gen.ctx
+    dev = torch.device("cuda", ctx.device)
+    fresh = viewshed_map_tensors(grid, dev)
+    seeing = torch.zeros((grid.n_lat, grid.n_lon), dtype=torch.int32, device=dev)
+    min_hidden = torch.full((grid.n_lat, grid.n_lon), float("inf"), dtype=torch.float64, device=dev)
+    pos = gen.params.pod.position
+    before = (pos.latitude, pos.longitude, pos.altitude)
+    try:
+        for o in observers:
+            pos.latitude, pos.longitude, pos.altitude = float(o["lat"]), float(o["lon"]), float(o["altitude"])
+            gen._configure()
+            viewshed_map(ctx, grid, az_lo_deg, az_step_deg, n_az, reach, height, fan, fan_rays, into=fresh)
+            seeing += (fresh["n_seen"] != 0).to(torch.int32)
+            min_hidden = torch.minimum(min_hidden, fresh["min_hidden"])
+    finally:
+        pos.latitude, pos.longitude, pos.altitude = before
+        gen._configure()
+    return seeing, min_hidden
+
+
+def write_viewshed_map_npz(path, grid, planes, stats=None):
+    """OUT.npz of gen --viewshed-map: the planes by name (n_samples, n_seen, min_hidden; observers_seeing, min_hidden in the cumulative
+    form), the grid's six numbers and, for a single map, the call's stats as stats_<name>."""
+    extra = {} if stats is None else {"stats_" + k: np.uint64(v) for k, v in stats.items()}
+    np.savez_compressed(path, lat0=np.float64(grid.lat0), lon0=np.float64(grid.lon0), cell_lat=np.float64(grid.cell_lat), cell_lon=np.float64(grid.cell_lon),
+                        n_lat=np.uint32(grid.n_lat), n_lon=np.uint32(grid.n_lon), **planes, **extra)
+
+
 # ---- horizon: per azimuth the bracket of elevation angles between terrain and sky, and the ridge that forms it (include/atmrt.h) ----
 HORIZON_DTYPE = np.dtype([("status", np.int32), ("rounds_done", np.int32), ("k_star", np.int32), ("block_index", np.int32)] +
                          [(k, np.float64) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon",

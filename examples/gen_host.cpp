@@ -79,6 +79,14 @@ int main(int argc, char** argv) {
         printf("viewshed azimuth %d m %d k_star %d status %d hidden %.17g ground %.17g block %d lat %.17g lon %.17g\n", j, v.m, v.k_star[o], v.status[o],
                v.hidden[o], v.ground[o], v.block_index[o], v.lat[o], v.lon[o]);
       }
+      // the same viewshed as a raster over a map: four quarter-degree cells east of the observer, binned on the device
+      const atmrt_geo_grid_t grid{46.25, 8.5, 0.25, 0.25, 2, 2};
+      const ViewshedMap vmap = viewshed_map(terrain, atmrt_viewshed_spec_t{88.0, 2.0, 23700.0, 0.0, -6.0, 6.0, 3, 128}, grid);
+      for (uint32_t cell = 0; cell < grid.n_lat * grid.n_lon; cell++)
+        printf("viewshed_map cell %u n_samples %u n_seen %u min_hidden %.17g\n", cell, vmap.n_samples[cell], vmap.n_seen[cell], vmap.min_hidden[cell]);
+      printf("viewshed_map stats n_samples %llu n_binned %llu n_outside %llu n_skipped %llu n_seen %llu\n", (unsigned long long)vmap.stats.n_samples,
+             (unsigned long long)vmap.stats.n_binned, (unsigned long long)vmap.stats.n_outside, (unsigned long long)vmap.stats.n_skipped,
+             (unsigned long long)vmap.stats.n_seen);
       // and where the skyline is along the same three azimuths, over the same fan (the same path table), narrowed twice
       const std::vector<atmrt_horizon_t> hz = horizon(terrain, atmrt_horizon_spec_t{88.0, 2.0, 23700.0, -6.0, 6.0, 3, 128, 3});
       for (size_t j = 0; j < hz.size(); j++)

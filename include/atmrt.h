@@ -657,6 +657,50 @@ int atmrt_last_viewshed_timings(atmrt_ctx* ctx, double out[4]);
 /* The batches that call took, and whether it rebuilt the path table (1) or found it (0). */
 int atmrt_last_viewshed_work(atmrt_ctx* ctx, int32_t* batches, int32_t* table_rebuilt);
 
+/* ---- viewshed map: the polar viewshed binned over a latitude / longitude grid on the device (no reference counterpart) — which
+ * ground is seen from here, as a raster that lies over a map; accumulated over observers, from how many of them.
+ *
+ * THE RULE (tests/viewshed_map_model.py restates it in numpy).  A SAMPLE is one lattice cell (j, i) of a viewshed with its status,
+ * hidden, lat and lon entries as atmrt_viewshed defines them; a grid is an atmrt_geo_grid_t under its own rules.
+ *   The cell of a sample is atmrt_geo_grid_cell(grid, lat, lon): the kernel runs the same function.
+ *   Every sample falls into exactly one class.  SKIPPED: lat or lon is NaN, or status > 3.  OUTSIDE: the grid function returns -1.
+ *     BINNED: every other sample.  So n_samples = n_binned + n_outside + n_skipped.
+ *   Planes, each [n_lat][n_lon], rows south to north:
+ *     n_samples (u32): the binned samples of the cell.
+ *     n_seen (u32): those of them whose status is ATMRT_SIGHT_SEEN or ATMRT_SIGHT_BELOW_FAN.
+ *     min_hidden (f64, may be NULL): the smallest hidden among the cell's binned samples of status SEEN or HIDDEN whose hidden is
+ *       not NaN and does not have its sign bit set (-0.0 does not take part); +inf where no sample takes part.  By the viewshed
+ *       rule ray k* does not fail, so hidden = arrival - aim >= +0.0 for those statuses: the condition only matters for
+ *       atmrt_viewshed_map_planes_device.  The minimum is a u64 minimum on the bit pattern, as the visibility map takes the
+ *       minimum of distances.
+ *   accumulate == 0: the three planes are overwritten.  accumulate != 0: they must already hold a map on the same grid; counts are
+ *     added and the minimum is taken against what is there, so the map of observers A then B accumulated is the cell-wise sum and
+ *     minimum of their separate maps.
+ *   Integer atomics only (u32 add, u64 min): equal calls give equal bytes, however the call was batched.
+ * stats (may be NULL) are of this call only, also under accumulate. */
+typedef struct atmrt_viewshed_map_stats {
+  uint64_t n_samples, n_binned, n_outside, n_skipped, n_seen;
+} atmrt_viewshed_map_stats_t;
+/* Any n samples (0 <= n <= (2^31 - 1) * 256) in memory of the context's device: what consumes the planes of atmrt_viewshed_device.
+ * The three map planes are device memory too.  Refusals as below. */
+int atmrt_viewshed_map_planes_device(atmrt_ctx* ctx, const atmrt_geo_grid_t* grid, size_t n, const uint8_t* status, const double* hidden,
+                                     const double* lat, const double* lon, int32_t accumulate, uint32_t* n_samples, uint32_t* n_seen,
+                                     double* min_hidden, atmrt_viewshed_map_stats_t* stats);
+/* The fused call: the viewshed's three passes per batch of azimuths exactly as atmrt_viewshed batches them — the path table is
+ * the same product of the context under the same key — with the scan writing only status, hidden, lat and lon (25 bytes per
+ * cell, counted by the batch size) into the call's scratch, and every batch scattered into the map in place of a download.
+ * atmrt_last_viewshed_work and atmrt_last_viewshed_timings report this call like a viewshed call; the last timing entry is the
+ * scatter.  The map planes are memory of the context's device.
+ * ATMRT_ERR_INVALID_ARGUMENT: everything atmrt_viewshed refuses in a spec, a grid atmrt_geo_grid_cell refuses, a NULL spec, grid,
+ * n_samples or n_seen (and, for the planes route, a NULL sample plane or an n above its limit).  ATMRT_ERR_STATE: before
+ * atmrt_set_params, and on a multi-device context (all three entry points).  A failed call leaves the context usable; with
+ * accumulate == 0 it leaves no promise about the planes. */
+int atmrt_viewshed_map_device(atmrt_ctx* ctx, const atmrt_viewshed_spec_t* spec, const atmrt_geo_grid_t* grid, int32_t accumulate,
+                              uint32_t* n_samples, uint32_t* n_seen, double* min_hidden, atmrt_viewshed_map_stats_t* stats);
+/* The same into host arrays, staged through the context's device (under accumulate the arrays are uploaded first). */
+int atmrt_viewshed_map(atmrt_ctx* ctx, const atmrt_viewshed_spec_t* spec, const atmrt_geo_grid_t* grid, int32_t accumulate,
+                       uint32_t* n_samples, uint32_t* n_seen, double* min_hidden, atmrt_viewshed_map_stats_t* stats);
+
 /* ---- horizon: for every azimuth of a fan, the elevation angle at which terrain ends and sky begins, with refraction, and which
  * ridge forms it (no reference counterpart).  Like the viewshed it needs the context's parameters, atmosphere and terrain only; it
  * neither needs nor disturbs a generated frame.

@@ -339,6 +339,23 @@ inline Viewshed viewshed(const Terrain& terrain, const atmrt_viewshed_spec_t& sp
   return out;
 }
 
+// Viewshed map (no reference counterpart; include/atmrt.h states the rule): that viewshed binned over `grid` on the device, its planes
+// never downloaded.  n_samples, n_seen and min_hidden are [n_lat][n_lon], rows south to north; min_hidden is +inf where no sample
+// takes part.  `into`: a map on the same grid to add to (counts are added, the minimum is taken against what is there).
+struct ViewshedMap {
+  std::vector<uint32_t> n_samples, n_seen;
+  std::vector<double> min_hidden;
+  atmrt_viewshed_map_stats_t stats{};
+};
+inline ViewshedMap viewshed_map(const Terrain& terrain, const atmrt_viewshed_spec_t& spec, const atmrt_geo_grid_t& grid, const ViewshedMap* into = nullptr) {
+  ViewshedMap out;
+  if (into) out = *into;
+  const size_t n = (size_t)grid.n_lat * grid.n_lon;
+  out.n_samples.resize(n), out.n_seen.resize(n), out.min_hidden.resize(n);
+  terrain.check(atmrt_viewshed_map(terrain.ctx(), &spec, &grid, into ? 1 : 0, out.n_samples.data(), out.n_seen.data(), out.min_hidden.data(), &out.stats));
+  return out;
+}
+
 // Horizon (no reference counterpart; include/atmrt.h states the rule): for every azimuth of spec the bracket of elevation angles
 // between the highest ray that terrain within spec.reach stops and the ray above it, and the ridge that stops it, from the observer
 // set on `terrain`'s context.  One record per azimuth.
