@@ -2804,3 +2804,24 @@ extern "C" int atmrt_math_probe(atmrt_ctx* c, int32_t op, size_t n, const double
   HIP_TRY(c, hipGetLastError());
   return ATMRT_OK;
 }
+
+extern "C" int atmrt_math_probe3(atmrt_ctx* c, int32_t op, size_t n, const double* a, const double* b0, const double* b1, const double* b2,
+                                 double* out0, double* out1, double* out2, int32_t* took) {
+  if (!c || (n && (!a || !b0 || !b1 || !b2 || !out0 || !out1 || !out2 || !took)) || op < 0 || op > ATMRT_PROBE3_EXP3_TIGHT || n > ((size_t)1 << 40))
+    return ATMRT_ERR_INVALID_ARGUMENT;
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_math_probe3(k_, op, n, a, b0, b1, b2, out0, out1, out2, took));
+  if (!n) return ATMRT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->d_io.reserve(8 * n * 8)); // a, b0, b1, b2, out0, out1, out2: n doubles each; took: n int32
+  double* d = c->d_io.as<double>();
+  const double* in[4] = {a, b0, b1, b2};
+  for (int k = 0; k < 4; k++) HIP_TRY(c, hipMemcpyAsync(d + k * n, in[k], n * 8, hipMemcpyHostToDevice, c->stream));
+  int32_t* d_took = reinterpret_cast<int32_t*>(d + 7 * n);
+  launch_math_probe3(op, n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, d_took, c->stream);
+  double* out[3] = {out0, out1, out2};
+  for (int k = 0; k < 3; k++) HIP_TRY(c, hipMemcpyAsync(out[k], d + (4 + k) * n, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(took, d_took, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}

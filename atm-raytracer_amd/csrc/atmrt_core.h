@@ -421,16 +421,31 @@ inline bool atm_interval_certified(const AtmTable& t, int k, double lo, double h
   return t.k_refr * ptmax * 2.0 <= 256.0;
 }
 
+// AtmSeg::exp_thr, the threshold dm_exp3_main_shared votes on (1/2 - margin, or -1: the shared form never runs): the exponents of
+// the three points of one right-hand side are e = expo1 log(x) with log arguments within 2^-21 of one another on a tight segment
+// (+ the rounding of log itself: 4 ulp of a value below 12), or e = expo1 (h - hb) with h 1 cm apart on an isothermal one; the
+// margin is their distance in units of ln2 / 128 with 1 % and 1e-6 to spare.  One formula for atm_certify and for the diagnostics
+// that run pow3_tight / exp3_tight on operands of their own (atmrt_math_probe, atmrt_math_probe3).
+ATMRT_HD double atm_exp_thr(double expo1, bool isothermal) {
+  const double ae = dm_fabs(expo1);
+  const double de = !isothermal ? ae * (4.76837158203125e-07 + 1.0e-14) : ae * 0.01 * (1.0 + 1.0e-9);
+  const double margin = 1.01 * de * DM_INVLN2N + 1.0e-6;
+  const double thr = margin < 0.5 ? 0.5 - margin : -1.0; // (NaN: -1)
+  return thr >= 0.0 ? thr : -1.0;
+}
+
 // The extra bounds of a TIGHT segment over its certified interval [lo, hi] (Linear segments only; atm_interval_certified holds):
 //   (1) |lapse| eps / Tmin <= 2^-21: the arguments x = fma(gtb, h - hb, 1) of log at h, h -+ eps differ by |gtb| eps = |lapse| eps / tb,
 //       relative to x = T / tb that is |lapse| eps / T; with the rounding of each x (2^-53 absolute, x >= 1e-5) they and the
-//       temperatures T = tb x are within 2^-21 (1 + 2^-35) of one another, half of what dm_div3's seeds tolerate (2^-20);
+//       temperatures T = tb x are within 2^-21 (1 + 2^-35) of one another: the distance at which dm_div3_seeded and the shared-row
+//       pow are tested (tests/test_gpu_detmath.py; the division also at 2^-20, the threshold of dm_div3's vote);
 //   (2) the same for the compressibilities: |dZ| / Z <= 2 |dZ| with |dZ| <= d_pt ptmax amax + ptmax |lapse| eps (|a1| + 2 tm a2)
 //       + 2 d_pt ptmax^2 d, where d_pt = (g0 M / R + |lapse|) eps / Tmin bounds the relative change of p / T over eps
 //       (p is a power or an exponential of h with logarithmic derivative g0 M / (R T));
 //   (3) |1 - Z| <= ptmax amax + ptmax^2 d <= 2^-10.5 and n - 1 = k_refr (p/T) / Z <= k_refr ptmax / (1 - 2^-10.5) <= 2^-10.5: the
-//       squares are the seed errors of 2 - Z for 1/Z and of 1 - (n - 1) for 1/n, 2^-21 — half of what the seeded divisions are
-//       tested for (2^-20).  (Standard air at sea level: |1 - Z| = 4.1e-4, n - 1 = 2.8e-4; 2^-10.5 = 6.9e-4.)
+//       squares are the seed errors of 2 - Z for 1/Z and of 1 - (n - 1) for 1/n, 2^-21; the seeded divisions are tested with
+//       |1 - Z| and n - 1 up to 2^-10.5 exactly (dm_div_seeded also at 2^-10: a seed error of 2^-20).  (Standard air at sea level:
+//       |1 - Z| = 4.1e-4, n - 1 = 2.8e-4; 2^-10.5 = 6.9e-4.)
 // Every left side is evaluated with a margin of 1 % for the rounding of the bound itself.
 inline bool atm_interval_tight(const AtmTable& t, int k, double lo, double hi) {
   const double a0 = 1.58123e-6, a1 = -2.9331e-8, a2 = 1.1043e-10, d = 1.83e-11, eps = 0.01, gmr = 9.80665 * 0.0289644 / 8.31432;
@@ -476,13 +491,7 @@ inline void atm_certify(AtmTable& t, bool spherical, double radius, double step)
     t.seg(k).safe_hi = t.seg(k).tight_hi = -dm_inf();
     t.seg(k).flags = !t.seg(k).cubic && t.seg(k).lapse == 0.0 ? ATM_SEG_ISOTHERMAL : 0;
     t.seg(k).k_refr = t.k_refr;
-    // the exponents of the three points of one right-hand side: e = expo1 log(x), log arguments within 2^-21 of one another on
-    // a tight segment (+ the rounding of log itself: 4 ulp of a value below 12), or e = expo1 (h - hb) with h 1 cm apart
-    const double ae = dm_fabs(t.seg(k).expo1);
-    const double de = t.seg(k).lapse != 0.0 ? ae * (4.76837158203125e-07 + 1.0e-14) : ae * 0.01 * (1.0 + 1.0e-9);
-    const double margin = 1.01 * de * DM_INVLN2N + 1.0e-6;
-    t.seg(k).exp_thr = margin < 0.5 ? 0.5 - margin : -1.0; // (NaN: -1)
-    if (!(t.seg(k).exp_thr >= 0.0)) t.seg(k).exp_thr = -1.0;
+    t.seg(k).exp_thr = atm_exp_thr(t.seg(k).expo1, !(t.seg(k).lapse != 0.0));
   }
   t.alt_lo = dm_inf();
   t.alt_hi = -dm_inf();
@@ -687,31 +696,42 @@ ATMRT_HD void pow3_in_range(double x0, double x1, double x2, double y, double& r
   r1 = dm_exp_main(e1);
   r2 = dm_exp_main(e2);
 }
-// the same on a TIGHT segment: the shared-row forms of detmath.h where no lane sits on a table edge (wave votes), else the plain ones
-ATMRT_HD void pow3_tight(double x0, double x1, double x2, double y, double thr, double& r0, double& r1, double& r2) {
+// the same on a TIGHT segment: the shared-row forms of detmath.h where no lane sits on a table edge (wave votes), else the plain ones.
+// REPORT (atmrt_math_probe3 only; the steppers instantiate the default and pass nothing): *took receives which forms the wavefront
+// took, bit 0 the shared log, bit 1 the shared exp (0 on the host, which has neither).
+template <bool REPORT = false>
+ATMRT_HD void pow3_tight(double x0, double x1, double x2, double y, double thr, double& r0, double& r1, double& r2, int* took = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double l0, l1, l2;
-  if (!dm_log3_core_pow_shared(x0, x1, x2, &l0, &l1, &l2)) {
+  const int shared_log = dm_log3_core_pow_shared(x0, x1, x2, &l0, &l1, &l2);
+  if (!shared_log) {
     l0 = dm_log_core_pow(x0);
     l1 = dm_log_core_pow(x1);
     l2 = dm_log_core_pow(x2);
   }
   const double e0 = y * l0, e1 = y * l1, e2 = y * l2;
-  if (!dm_exp3_main_shared(e0, e1, e2, thr, &r0, &r1, &r2)) {
+  const int shared_exp = dm_exp3_main_shared(e0, e1, e2, thr, &r0, &r1, &r2);
+  if (!shared_exp) {
     r0 = dm_exp_main(e0);
     r1 = dm_exp_main(e1);
     r2 = dm_exp_main(e2);
   }
+  if (REPORT) *took = shared_log | (shared_exp << 1);
 #else
   (void)thr;
+  if (REPORT) *took = 0;
   pow3_in_range(x0, x1, x2, y, r0, r1, r2);
 #endif
 }
-ATMRT_HD void exp3_tight(double e0, double e1, double e2, double thr, double& r0, double& r1, double& r2) {
+template <bool REPORT = false>
+ATMRT_HD void exp3_tight(double e0, double e1, double e2, double thr, double& r0, double& r1, double& r2, int* took = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (dm_exp3_main_shared(e0, e1, e2, thr, &r0, &r1, &r2)) return;
+  const int shared_exp = dm_exp3_main_shared(e0, e1, e2, thr, &r0, &r1, &r2);
+  if (REPORT) *took = shared_exp; // 1: the shared exp
+  if (shared_exp) return;
 #else
   (void)thr;
+  if (REPORT) *took = 0;
 #endif
   r0 = dm_exp_main(e0);
   r1 = dm_exp_main(e1);

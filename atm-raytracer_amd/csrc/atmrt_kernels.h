@@ -556,6 +556,8 @@ void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, dou
 // fills f.ceil (rows 0 .. f.march_steps) for f.ceil_layout: the cells, then every bin's suffix maxima
 void launch_ceiling(const Frame& f, CeilEntry* table, hipStream_t stream);
 void launch_math_probe(int op, size_t n, const double* a, const double* b, double* out0, double* out1, hipStream_t stream);
+void launch_math_probe3(int op, size_t n, const double* a, const double* b0, const double* b1, const double* b2, double* out0, double* out1,
+                        double* out2, int32_t* took, hipStream_t stream);
 void launch_coords_at_dist(const Frame& f, double lat0, double lon0, double dir, size_t n, const double* dist,
                            double* lat, double* lon, hipStream_t stream);
 

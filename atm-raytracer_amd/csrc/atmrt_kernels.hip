@@ -1547,10 +1547,9 @@ __global__ void k_math_probe(int op, size_t n, const double* __restrict__ a, con
       break;
     }
     case ATMRT_PROBE_DIV_SEED_N: r0 = dm_div_seeded(x, 1.0 + y, 1.0 - y); break;
-    case ATMRT_PROBE_POW3_SHARED: { // as refr_n_layer3 calls it on a tight segment (the threshold as atm_certify computes it)
-      const double margin = 1.01 * (dm_fabs(y) * (4.76837158203125e-07 + 1.0e-14)) * DM_INVLN2N + 1.0e-6;
+    case ATMRT_PROBE_POW3_SHARED: { // as refr_n_layer3 calls it on a tight segment (the threshold atm_certify stores)
       double p1, p2;
-      pow3_tight(x, x * 0.99999976158142090, x * 1.00000023841857910, y, margin < 0.5 ? 0.5 - margin : -1.0, r0, p1, p2);
+      pow3_tight(x, x * 0.99999976158142090, x * 1.00000023841857910, y, atm_exp_thr(y, false), r0, p1, p2);
       r1 = p1 + p2;
       break;
     }
@@ -1561,6 +1560,39 @@ __global__ void k_math_probe(int op, size_t n, const double* __restrict__ a, con
 }
 void launch_math_probe(int op, size_t n, const double* a, const double* b, double* out0, double* out1, hipStream_t stream) {
   if (n) hipLaunchKernelGGL(k_math_probe, dim3(cdiv(n, 256)), dim3(256), 0, stream, op, n, a, b, out0, out1);
+}
+// the three-point forms with every operand the caller's (atmrt_math_probe3): the three results apart, and which form the lane's
+// wavefront took.  Same launch shape as k_math_probe: elements 64 w .. 64 w + 63 are one wavefront.
+__global__ void k_math_probe3(int op, size_t n, const double* __restrict__ a, const double* __restrict__ b0, const double* __restrict__ b1,
+                              const double* __restrict__ b2, double* __restrict__ out0, double* __restrict__ out1, double* __restrict__ out2,
+                              int32_t* __restrict__ took) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = a[i], y0 = b0[i], y1 = b1[i], y2 = b2[i];
+  double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+  int tk = 0;
+  switch (op) {
+    case ATMRT_PROBE3_DIV3: tk = dm_div3(x, y0, x, y1, x, y2, &r0, &r1, &r2); break;
+    case ATMRT_PROBE3_DIV3_SEEDED:
+      dm_div3_seeded(x, y0, x, y1, x, y2, 0, 0.0, &r0, &r1, &r2);
+      tk = 1;
+      break;
+    case ATMRT_PROBE3_DIV3_SEED_Z:
+      dm_div3_seeded(x, y0, x, y1, x, y2, 1, 2.0 - y0, &r0, &r1, &r2);
+      tk = 1;
+      break;
+    case ATMRT_PROBE3_POW3_TIGHT: pow3_tight<true>(y0, y1, y2, x, atm_exp_thr(x, false), r0, r1, r2, &tk); break;
+    case ATMRT_PROBE3_EXP3_TIGHT: exp3_tight<true>(x * y0, x * y1, x * y2, atm_exp_thr(x, true), r0, r1, r2, &tk); break; // expo1 * d_i, as refr_n_layer3
+    default: break;
+  }
+  out0[i] = r0;
+  out1[i] = r1;
+  out2[i] = r2;
+  took[i] = tk;
+}
+void launch_math_probe3(int op, size_t n, const double* a, const double* b0, const double* b1, const double* b2, double* out0, double* out1,
+                        double* out2, int32_t* took, hipStream_t stream) {
+  if (n) hipLaunchKernelGGL(k_math_probe3, dim3(cdiv(n, 256)), dim3(256), 0, stream, op, n, a, b0, b1, b2, out0, out1, out2, took);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -144,12 +144,17 @@ DM_FN double dm_div_seeded(double a, double b, double r0) { (void)r0; return a /
  * seed error |1 - b_i r_0| <= 2^-20 two Newton steps leave 2^-80 before rounding, the same class of reciprocal dm_div's own two
  * steps from v_rcp_f64 produce, and the quotient correction is dm_div's.  That saves the two quarter-rate v_rcp_f64 (the guard costs
  * what the two instructions save).  The guard is a wave vote; lanes that fail it (or hold NaN) send the whole wavefront through
- * dm_div.  Same operand range as dm_div.  tests/test_gpu_detmath.py checks the sequence against IEEE division like dm_div.
- * dm_div3_seeded: the same for call sites that HOLD the bound |1 - b_i / b_0| <= 2^-21 as a certificate (atm_certify's `tight`
- * segments) — no vote — and, optionally, a seed r0 for b_0's own reciprocal (have_seed: |1 - b_0 r0| <= 2^-20, likewise
- * certified) in place of its v_rcp_f64. */
+ * dm_div.  Returns the vote (1: seeded; the host's 0 means nothing) for the diagnostics; the steppers ignore it.  Same operand
+ * range as dm_div.
+ * dm_div3_seeded: the same for call sites that HOLD the bound |1 - b_i / b_0| <= 2^-21 (1 + 2^-35) as a certificate (atm_certify's
+ * `tight` segments) — no vote — and, optionally, a seed r0 for b_0's own reciprocal (have_seed: |1 - b_0 r0| <= 2^-21, likewise
+ * certified) in place of its v_rcp_f64.
+ * Tested against IEEE division with outer divisors built at exact distances (tests/test_gpu_detmath.py through atmrt_math_probe3,
+ * the call sites' operands and the exponent range +-480): dm_div3 at every distance up to 2^-20 (1 - 2^-10), where every wavefront
+ * must vote yes, at 2^-20 and at 2^-20 (1 + 2^-10), where none may, and with one such lane among 63 inside; dm_div3_seeded at
+ * 2^-22, 0.99 2^-21, 2^-21, 2^-21 (1 + 2^-35) and 2^-20, with and without the seed 2 - b_0 for |1 - b_0| <= 2^-10.5. */
 #if defined(__HIP_DEVICE_COMPILE__)
-DM_FN void dm_div3(double a0, double b0, double a1, double b1, double a2, double b2, double* q0, double* q1, double* q2) {
+DM_FN int dm_div3(double a0, double b0, double a1, double b1, double a2, double b2, double* q0, double* q1, double* q2) {
   double r = __builtin_amdgcn_rcp(b0);
   double e = __builtin_fma(-b0, r, 1.0);
   r = __builtin_fma(r, e, r);
@@ -173,10 +178,11 @@ DM_FN void dm_div3(double a0, double b0, double a1, double b1, double a2, double
     q = a2 * r2;
     e2 = DM_FNMA_VVV(b2, q, a2);
     *q2 = __builtin_fma(e2, r2, q);
-  } else {
-    *q1 = dm_div(a1, b1);
-    *q2 = dm_div(a2, b2);
+    return 1;
   }
+  *q1 = dm_div(a1, b1);
+  *q2 = dm_div(a2, b2);
+  return 0;
 }
 DM_FN void dm_div3_seeded(double a0, double b0, double a1, double b1, double a2, double b2, int have_seed, double r0, double* q0, double* q1,
                           double* q2) {
@@ -209,10 +215,11 @@ DM_FN void dm_div3_seeded(double a0, double b0, double a1, double b1, double a2,
   *q2 = __builtin_fma(e2, r2, q);
 }
 #else
-DM_FN void dm_div3(double a0, double b0, double a1, double b1, double a2, double b2, double* q0, double* q1, double* q2) {
+DM_FN int dm_div3(double a0, double b0, double a1, double b1, double a2, double b2, double* q0, double* q1, double* q2) {
   *q0 = a0 / b0;
   *q1 = a1 / b1;
   *q2 = a2 / b2;
+  return 0;
 }
 DM_FN void dm_div3_seeded(double a0, double b0, double a1, double b1, double a2, double b2, int have_seed, double r0, double* q0, double* q1,
                           double* q2) {
@@ -602,7 +609,11 @@ DM_FN double dm_log_core_pow(double x) {
  *   exp: |e_i - e_0| 128 / ln2 <= margin (the segment's bound, `thr` = 1/2 - margin), so rint(e_i 128 / ln2) = rint(e_0 128 / ln2)
  *        unless the centre's own product lies within margin of a half-integer.
  * One lane at an edge sends its wavefront through the plain calls (the caller's other branch); the values are those of the plain
- * calls bit for bit either way — same operations on the same operands.  GPU only; tests/test_gpu_detmath.py (POW3_SHARED). */
+ * calls bit for bit either way — same operations on the same operands.  GPU only.  tests/test_gpu_detmath.py runs both through
+ * atmrt_math_probe3 with arguments up to 2^-21 (1 + 2^-35) apart (exact distances), centres on the last high words that pass the
+ * log vote (1, 2, 0x1ffd, 0x1ffe) with the neighbour at the full distance towards the interval's edge, centres next to 0.5, 1 and 2, and exponent
+ * products a hair on either side of thr, and checks the values AND the path each wavefront took against the host's prediction;
+ * at 2^-20 about 0.01 % of the outer results are no longer dm_pow's (recorded there). */
 #if defined(__HIP_DEVICE_COMPILE__)
 DM_FN int dm_log3_core_pow_shared(double x0, double x1, double x2, double* l0, double* l1, double* l2) {
   const uint64_t i0 = dm_bits(x0), i1 = dm_bits(x1), i2 = dm_bits(x2);

@@ -929,6 +929,24 @@ typedef enum atmrt_math_probe_op {
                                    out1 = dm_pow(a (1 - 2^-22), b) + dm_pow(a (1 + 2^-22), b) */
 } atmrt_math_probe_op;
 int atmrt_math_probe(atmrt_ctx* ctx, int32_t op, size_t n, const double* a, const double* b, double* out0, double* out1);
+/* The three-point forms of one ODE right-hand side with EVERY operand the caller's, so that a test can place the outer points at
+ * the exact distance from the centre a certificate admits (atm_certify's TIGHT segments: 2^-21 (1 + 2^-35) relative) instead of the
+ * fixed 1 -+ 2^-22 of the ops above.  out0 / out1 / out2 receive the three results apart; took[i] says which form the wavefront of
+ * element i ran (the kernel is launched in blocks of 256: elements 64 w .. 64 w + 63 form one wavefront, and every branch is a
+ * wave vote).  All pointers are required; a diagnostic like atmrt_math_probe, a multi-device context answers on its first device.
+ * tests/test_gpu_detmath.py predicts took from the host and compares the results bit for bit with the plain operations. */
+typedef enum atmrt_math_probe3_op {
+  ATMRT_PROBE3_DIV3 = 0,        /* dm_div3(a, b0, a, b1, a, b2); took = 1: the outer reciprocals seeded from b0's (every lane's seed
+                                   residual <= 2^-20), 0: dm_div for both */
+  ATMRT_PROBE3_DIV3_SEEDED = 1, /* dm_div3_seeded(..., have_seed = 0): no vote, took = 1 */
+  ATMRT_PROBE3_DIV3_SEED_Z = 2, /* dm_div3_seeded(..., 1, 2 - b0): b0 = Z close to 1 with 2 - Z seeding its reciprocal; took = 1 */
+  ATMRT_PROBE3_POW3_TIGHT = 3,  /* pow3_tight(b0, b1, b2, y = a, thr): dm_pow(b_i, a) of a tight Linear segment with expo1 = a and the
+                                   exp_thr atm_certify stores for it; took bit 0: the shared log row, bit 1: the shared exp entry */
+  ATMRT_PROBE3_EXP3_TIGHT = 4   /* exp3_tight(a b0, a b1, a b2, thr): dm_exp_main(a * b_i) of a tight isothermal segment with expo1 = a
+                                   and its exp_thr; took = 1: the shared exp entry */
+} atmrt_math_probe3_op;
+int atmrt_math_probe3(atmrt_ctx* ctx, int32_t op, size_t n, const double* a, const double* b0, const double* b1, const double* b2,
+                      double* out0, double* out1, double* out2, int32_t* took);
 /* The table the marching kernels read the Spherical geodesic's sin / cos from, for the parameters now set: *n = its entries
  * (max over k of the stepper distances xs[k] <= max_distance, plus one; 0: no table — another calculator, or ATMRT_STEP_TRIG=off),
  * and the first min(cap, *n) of xs[k], sin(xs[k] / radius), cos(xs[k] / radius).  tests/test_gpu_step_trig.py compares them with

@@ -84,6 +84,10 @@ int ch_certify(const atmrt_atmosphere_t* def, double wavelength, int spherical, 
   }
   return 0;
 }
+// AtmSeg::exp_thr as atm_certify stores it for a segment with this expo1 (tests/test_gpu_detmath.py predicts dm_exp3_main_shared's vote from it)
+void ch_exp_thr(const double* expo1, int isothermal, double* thr, size_t n) {
+  for (size_t i = 0; i < n; i++) thr[i] = atm_exp_thr(expo1[i], isothermal != 0);
+}
 int ch_ray_path(const atmrt_atmosphere_t* def, const atmrt_earth_model_t* m, double wavelength, double h0, double ang_deg, int straight,
                 double step, size_t n_steps, double* x, double* h) {
   AtmTableBuf buf;

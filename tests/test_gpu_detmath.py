@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import cbuild
+import tight_populations as tp
 from util import bits
 
 pytestmark = pytest.mark.gpu
@@ -207,6 +208,175 @@ def test_shared_row_pow_of_tight_segments_is_the_plain_pow(gpu_ctx, host):
     same(g0, h0, "shared-row pow, centre")
     same(g12, h12, "shared-row pow, outer points")
     same(g0, gpu(gpu_ctx, "POW", x, y), "shared-row pow against the plain device pow")
+
+
+# ---- the three-point forms AT the bounds a TIGHT segment certifies (atmrt_math_probe3: every operand the test's own) ----------------
+PROBE3 = dict(DIV3=0, DIV3_SEEDED=1, DIV3_SEED_Z=2, POW3_TIGHT=3, EXP3_TIGHT=4)
+N3 = 1 << 20  # per population: a few seconds per test
+
+
+def probe3(ctx, op, a, b0, b1, b2):
+    arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in (a, b0, b1, b2)]
+    assert arrs[0].size % tp.WAVE == 0 and all(x.size == arrs[0].size for x in arrs)
+    outs = [np.empty_like(arrs[0]) for _ in range(3)]
+    took = np.full(arrs[0].size, -1, dtype=np.int32)
+    ctx.check(ctx.lib.atmrt_math_probe3(ctx.handle, PROBE3[op], arrs[0].size, *[x.ctypes.data for x in arrs + outs], took.ctypes.data))
+    return outs[0], outs[1], outs[2], took
+
+
+def wave_counts(what, took, bit=1):
+    """(#wavefronts with the bit set, #without); the flag must be uniform over each wavefront."""
+    w = (took.reshape(-1, tp.WAVE) & bit) != 0
+    assert np.all(w == w[:, :1]), f"{what}: the path flag differs inside a wavefront"
+    on = int(w[:, 0].sum())
+    print(f"{what}: {on} wavefronts took the shared / seeded form, {w.shape[0] - on} the fall-back")
+    return on, w.shape[0] - on
+
+
+def wave_all(ok):
+    return np.repeat(ok.reshape(-1, tp.WAVE).all(axis=1), tp.WAVE)
+
+
+def differing(g, w):
+    return float(np.mean((bits(g) != bits(w)) & ~(np.isnan(g) & np.isnan(w))))
+
+
+@pytest.fixture(scope="module")
+def thr_of():
+    """AtmSeg::exp_thr for an array of expo1, from the host build of atm_certify's own formula (atm_exp_thr)."""
+    core = C.CDLL(cbuild.core_host())
+    core.ch_exp_thr.restype = None
+
+    def f(expo1, isothermal=False):
+        expo1 = np.ascontiguousarray(expo1, dtype=np.float64)
+        thr = np.empty_like(expo1)
+        core.ch_exp_thr(C.c_void_p(expo1.ctypes.data), C.c_int(int(isothermal)), C.c_void_p(thr.ctypes.data), C.c_size_t(expo1.size))
+        return thr
+    return f
+
+
+def largest_expo_with_a_threshold(thr_of, isothermal):
+    lo, hi = 0.0, 1.0e6  # thr_of(lo) > 0 > thr_of(hi)
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if thr_of(np.array([mid]), isothermal)[0] >= 0.0 else (lo, mid)
+    return lo
+
+
+def host_votes(host, a, b0, thr, isothermal):
+    a, b0, thr = (np.ascontiguousarray(x, dtype=np.float64) for x in (a, b0, thr))
+    log_ok, exp_ok = np.empty(a.size, dtype=np.int32), np.empty(a.size, dtype=np.int32)
+    host.t_vote3.restype = None
+    host.t_vote3(*[C.c_void_p(x.ctypes.data) for x in (a, b0, thr)], C.c_int(int(isothermal)), C.c_void_p(log_ok.ctypes.data),
+                 C.c_void_p(exp_ok.ctypes.data), C.c_size_t(a.size))
+    return log_ok != 0, exp_ok != 0
+
+
+def test_vote_free_seeded_divisions_at_the_certified_distance_and_at_the_claimed_tolerance(gpu_ctx, host):
+    """dm_div3_seeded runs without a vote wherever atm_interval_tight admits the three divisors: within 2^-21 (1 + 2^-35) of one
+    another.  Here the outer divisors stand at 2^-22, 0.99 2^-21, 2^-21 and exactly that bound (each on its own side, built in integer
+    arithmetic: tests/tight_populations.py), then at 2^-20, the seed error detmath.h names as the tolerance of two Newton steps —
+    for the call sites' operands (p / T; K pt / Z with |1 - Z| up to 2^-10.5, with and without the 2 - Z seed) and over the
+    exponent range.  Every quotient must be numpy's a / b."""
+    rng = np.random.default_rng(51)
+    for site, (a, b0) in tp.division_sites(rng, N3).items():
+        for label, nums in (("<= 2^-21 (1 + 2^-35)", tp.ADMITTED), ("2^-21 (1 + 2^-35)", (tp.BOUND,)), ("2^-20", (tp.D20,))):
+            b1, b2, _, _ = tp.triple(rng, b0, nums)
+            for op in (("DIV3_SEEDED", "DIV3_SEED_Z") if site == "K pt / Z" else ("DIV3_SEEDED",)):
+                q0, q1, q2, took = probe3(gpu_ctx, op, a, b0, b1, b2)
+                with np.errstate(all="ignore"):
+                    for q, b, which in ((q0, b0, "centre"), (q1, b1, "first outer"), (q2, b2, "second outer")):
+                        same(q, a / b, f"{op} {site}, divisors at {label}, {which}")
+                assert np.all(took == 1)
+
+
+def test_voting_div3_up_to_its_threshold_and_across_it(gpu_ctx, host):
+    """dm_div3 lets a wavefront through while every lane's seed residual is at most 2^-20: the non-tight segments run it between the
+    certified 2^-21 and that threshold.  Divisors up to the certified distance and at 2^-20 (1 - 2^-10): every wavefront must take
+    the seeded form; at 2^-20 (1 + 2^-10), and with ONE such lane among 63 inside: none may; at 2^-20 itself the refined reciprocal
+    decides, so only the quotients are asserted.  They must be numpy's a / b on whichever branch ran."""
+    rng = np.random.default_rng(52)
+    for site, (a, b0) in tp.division_sites(rng, N3 // 2).items():
+        one_out = np.zeros(a.size, dtype=bool)
+        one_out[np.arange(0, a.size, tp.WAVE) + rng.integers(0, tp.WAVE, a.size // tp.WAVE)] = True
+        for label, nums, expect in (("<= 2^-20 (1 - 2^-10)", tp.ADMITTED + (tp.D20_IN,), 1), ("2^-20 (1 - 2^-10)", (tp.D20_IN,), 1),
+                                    ("2^-20", (tp.D20,), None), ("2^-20 (1 + 2^-10)", (tp.D20_OUT,), 0), ("63 lanes inside, one outside", None, 0)):
+            b1, b2, _, _ = tp.triple(rng, b0, tp.ADMITTED + (tp.D20_IN,) if nums is None else nums)
+            if nums is None:
+                first = rng.uniform(size=a.size) < 0.5
+                far = tp.neighbour(b0, rng.uniform(size=a.size) < 0.5, tp.D20_OUT)
+                b1, b2 = np.where(one_out & first, far, b1), np.where(one_out & ~first, far, b2)
+            q0, q1, q2, took = probe3(gpu_ctx, "DIV3", a, b0, b1, b2)
+            with np.errstate(all="ignore"):
+                for q, b, which in ((q0, b0, "centre"), (q1, b1, "first outer"), (q2, b2, "second outer")):
+                    same(q, a / b, f"dm_div3 {site}, divisors at {label}, {which}")
+            on, off = wave_counts(f"dm_div3 {site}, divisors at {label}", took)
+            if expect is not None:
+                assert (on, off)[expect] == 0, f"dm_div3 {site}, divisors at {label}: {on} wavefronts seeded, {off} not"
+
+
+def test_pow3_tight_at_the_certified_distance_on_table_and_binade_edges(gpu_ctx, host, thr_of):
+    """pow3_tight as refr_n_layer3 calls it, the three bases up to 2^-21 (1 + 2^-35) apart: the barometric population, and — in
+    wavefronts of their own and one per ordinary wavefront — centres on the LAST high words that pass the shared log's vote
+    ((hi + 0x1000) & 0x1fff in {1, 2, 0x1ffd, 0x1ffe}) with the neighbour at the full distance on the side of the next table
+    interval, centres that fail it, centres next to 0.5, 1.0 and 2.0, and exponent products a hair inside and outside of the
+    shared exp's threshold, for physical exponents and the largest ones that still have a threshold.  All three results must be
+    the host's dm_pow, and the path every wavefront took must be the one the host predicts from the centre operands."""
+    rng = np.random.default_rng(53)
+    ymax = largest_expo_with_a_threshold(thr_of, False)
+    assert thr_of(np.array([ymax]))[0] >= 0.0 and thr_of(np.array([ymax * 1.001]))[0] == -1.0
+    y, x0, x1, x2, _, _, special = tp.pow_population(rng, N3, [ymax, -ymax, ymax * (1.0 - 1e-6), -ymax * 1.001], thr_of)
+    r0, r1, r2, took = probe3(gpu_ctx, "POW3_TIGHT", y, x0, x1, x2)
+    h0, h1, h2 = cpu(host, "pow3x", y, x0, x1, x2, outs=3)
+    same(r0, h0, "pow3_tight, centre")
+    same(r1, h1, "pow3_tight, first outer point")
+    same(r2, h2, "pow3_tight, second outer point")
+    same(r0, gpu(gpu_ctx, "POW", x0, y), "pow3_tight against the plain device pow")
+    log_ok, exp_ok = host_votes(host, y, x0, thr_of(y), False)
+    want = wave_all(log_ok).astype(np.int32) | (wave_all(exp_ok).astype(np.int32) << 1)
+    bad = np.flatnonzero(took != want)
+    assert bad.size == 0, f"{bad.size} lanes took another path than predicted, e.g. {bad[:3]}: took {took[bad[:3]]} predicted {want[bad[:3]]}"
+    own = special.reshape(-1, tp.WAVE).all(axis=1).repeat(tp.WAVE)
+    for what, sel in (("edge wavefronts", own), ("ordinary wavefronts with one edge lane", ~own)):
+        for form, bit in (("log", 1), ("exp", 2)):
+            on, off = wave_counts(f"pow3_tight {what}, shared {form}", took[sel], bit)
+            assert on > 0 and off > 0, "the population must straddle the vote"
+    # what the certificate buys: beyond the bound the shared forms are NOT the plain calls (recorded, not asserted)
+    for label, num in (("2^-21 (1 + 2^-30)", tp.BEYOND), ("2^-20", tp.D20)):
+        y, x0, x1, x2, _, _, _ = tp.pow_population(rng, N3 // 4, [ymax], thr_of, nums=(num,))
+        r0, r1, r2, took = probe3(gpu_ctx, "POW3_TIGHT", y, x0, x1, x2)
+        h0, h1, h2 = cpu(host, "pow3x", y, x0, x1, x2, outs=3)
+        same(r0, h0, "pow3_tight, centre")
+        print(f"pow3_tight with bases {label} apart: {100 * differing(r1, h1):.4f} % / {100 * differing(r2, h2):.4f} % of the outer results differ from dm_pow")
+
+
+def test_exp3_tight_of_isothermal_segments_on_both_sides_of_its_threshold(gpu_ctx, host, thr_of):
+    """exp3_tight as refr_n_layer3 calls it on a tight isothermal segment: e_i = expo1 (h_i - hb), h_i = h, h - 1 cm, h + 1 cm with the
+    stepper's roundings, expo1 = -g M / (R T) for 150 .. 330 K and the largest |expo1| that still has a threshold; centres a hair
+    inside and outside of the threshold, in wavefronts of their own and one per ordinary wavefront.  Results: the host's
+    dm_exp_main of the same products; paths: as the host predicts."""
+    rng = np.random.default_rng(54)
+    amax = largest_expo_with_a_threshold(thr_of, True)
+    a, d0, d1, d2, special = tp.exp_population(rng, N3, [-amax, -amax * (1.0 - 1e-6), -amax * 1.001, -0.01], lambda v: thr_of(v, True))
+    r0, r1, r2, took = probe3(gpu_ctx, "EXP3_TIGHT", a, d0, d1, d2)
+    h0, h1, h2 = cpu(host, "exp3x", a, d0, d1, d2, outs=3)
+    same(r0, h0, "exp3_tight, centre")
+    same(r1, h1, "exp3_tight, h - eps")
+    same(r2, h2, "exp3_tight, h + eps")
+    _, exp_ok = host_votes(host, a, d0, thr_of(a, True), True)
+    want = wave_all(exp_ok).astype(np.int32)
+    bad = np.flatnonzero(took != want)
+    assert bad.size == 0, f"{bad.size} lanes took another path than predicted, e.g. {bad[:3]}: took {took[bad[:3]]} predicted {want[bad[:3]]}"
+    own = special.reshape(-1, tp.WAVE).all(axis=1).repeat(tp.WAVE)
+    for what, sel in (("threshold wavefronts", own), ("ordinary wavefronts with one threshold lane", ~own)):
+        on, off = wave_counts(f"exp3_tight {what}", took[sel])
+        assert on > 0 and off > 0, "the population must straddle the vote"
+    for eps in (0.0101, 0.011, 0.02):  # beyond what exp_thr allows for (recorded, not asserted)
+        a, d0, d1, d2, _ = tp.exp_population(rng, N3 // 4, [-amax], lambda v: thr_of(v, True), eps=eps)
+        r0, r1, r2, took = probe3(gpu_ctx, "EXP3_TIGHT", a, d0, d1, d2)
+        h0, h1, h2 = cpu(host, "exp3x", a, d0, d1, d2, outs=3)
+        same(r0, h0, "exp3_tight, centre")
+        print(f"exp3_tight with h -+ {eps} m: {100 * differing(r1, h1):.4f} % / {100 * differing(r2, h2):.4f} % of the outer results differ from dm_exp_main")
 
 
 def test_dm_sqrt_inrange_is_ieee_sqrt_in_range(gpu_ctx, host):
