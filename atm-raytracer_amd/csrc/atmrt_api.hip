@@ -698,6 +698,7 @@ static int prepare_ceiling(atmrt_ctx* c, Frame& f) {
   f.ceil = nullptr;
   f.ceil_layout = CeilLayout{};
   f.ceil_floor = INFINITY;
+  f.ceil_order = f.ceil_order_steps = nullptr;
   const int mode = ceiling_mode();
   const atmrt_params_t& p = f.p;
   if (!mode || p.generator != ATMRT_GEN_RECTILINEAR || c->earth.calc != 2 || f.march_steps < 1 || f.wl < 1 || f.h < 1) return ATMRT_OK;
@@ -712,11 +713,31 @@ static int prepare_ceiling(atmrt_ctx* c, Frame& f) {
     HIP_TRY(c, hipEventRecord(c->ev[EV_CEIL_BEGIN], c->stream));
     launch_ceiling(f, c->d_ceil.as<CeilEntry>(), c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev[EV_CEIL_END], c->stream));
     return 0;
   }, mode == 2, &c->ceil_built);
   if (rc) return rc;
   f.ceil = c->d_ceil.as<CeilEntry>();
+  // The work queue of the whole-frame march, beside the table: built whenever the table is, and when what the table does not depend
+  // on changes the rays (the image's rows and the observer's altitude; the bins' key holds the rest of the camera).  Its time is the
+  // table's (EV_CEIL_BEGIN .. EV_CEIL_END, ceiling_ms).
+  bool order_built = false;
+  if (!c->comm && march_queue_wanted(f)) {
+    const OrderKey okey{c->ceiling.serial(), c->bins.serial(), f.h, p.position.altitude_kind, bits(p.position.altitude)};
+    MarchOrder o{};
+    const int orc = c->ceil_order.refresh(okey, [&](Nothing&) {
+      HIP_TRY(c, reserve_carved(c->d_ceil_order, [&](Carve& k) { march_order_layout(f, k, o); }));
+      if (!c->ceil_built) HIP_TRY(c, hipEventRecord(c->ev[EV_CEIL_BEGIN], c->stream));
+      launch_march_order(f, o, c->stream);
+      HIP_TRY(c, hipGetLastError());
+      return 0;
+    }, mode == 2, &order_built);
+    if (orc) return orc;
+    Carve carved(c->d_ceil_order.ptr); // the order's key holds what the layout depends on: the same carving as the build's
+    march_order_layout(f, carved, o);
+    f.ceil_order = o.order, f.ceil_order_steps = o.order_steps;
+  }
+  if (c->ceil_built || order_built) HIP_TRY(c, hipEventRecord(c->ev[EV_CEIL_END], c->stream));
+  c->ceil_built = c->ceil_built || order_built;
   // the certificate's part of the escape floor (Frame::esc_floor is the same rule over the mosaic's top)
   if (escape_enabled()) {
     if (p.straight_rays) f.ceil_floor = -INFINITY;
@@ -1173,6 +1194,8 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   c->last_ceil_rows = f.ceil ? f.march_steps + 1 : 0;
   c->last_ceil_layout = f.ceil_layout;
   c->last_ceil_serial = c->ceiling.serial();
+  c->last_order_groups = f.ceil_order ? (uint32_t)(((size_t)f.wl * f.h + 63) / 64) : 0;
+  c->last_order_serial = c->ceil_order.serial();
   return ATMRT_OK;
 }
 
@@ -2785,6 +2808,22 @@ extern "C" int atmrt_debug_ceiling_table(atmrt_ctx* c, size_t cap, float* cell, 
   HIP_TRY(c, hipMemcpyAsync(host.data(), c->d_ceil.as<CeilEntry>(), n * sizeof(CeilEntry), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (size_t k = 0; k < n; k++) cell[k] = host[k].cell, suffix[k] = host[k].suffix;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_march_order(atmrt_ctx* c, size_t cap, uint32_t* order, uint32_t* n_groups) {
+  if (!c || !n_groups || (cap && !order)) return ATMRT_ERR_INVALID_ARGUMENT;
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_march_order(k_, cap, order, n_groups));
+  *n_groups = 0;
+  if (!c->last_valid || !c->last_order_groups) return ATMRT_OK;
+  if (c->ceil_order.serial() != c->last_order_serial)
+    return c->fail(ATMRT_ERR_STATE, "the march order of the last frame is gone: a later call built another one in its place");
+  *n_groups = c->last_order_groups;
+  const size_t n = *n_groups < cap ? *n_groups : cap;
+  if (!n) return ATMRT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(order, c->d_ceil_order.as<uint32_t>(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return ATMRT_OK;
 }
 

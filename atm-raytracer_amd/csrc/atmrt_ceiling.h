@@ -137,4 +137,15 @@ ATMRT_HD float ceiling_cell(const TerrainView& tv, const CeilLayout& L, double r
   return c == CEIL_UNBOUNDED || c > global ? global : c;
 }
 
+// An ESTIMATE of the steps a ray of bin `bin` marches, for the order of the whole-frame work queue (Frame::ceil_order): a key
+// that decides scheduling, never a result.  The ray's height is the closed form alt + x slope + x^2 / (2 R_eff) over the distance
+// table (slope = tan of its elevation angle, R_eff the usual 7/6 earth radius, inv_2r = 1 / (2 R_eff)); the estimate is the first
+// step at which it is ascending and above its bin's suffix (it would escape) or below its cell (it would meet terrain soon), else
+// march_steps.  This is the test of one step, `ce` the bin's entry of the step's row and x its distance (k_march_length_estimate
+// spreads the steps of a ray over lanes).
+ATMRT_HD bool ceiling_estimate_ends(const CeilEntry& ce, double x, double alt, double slope, double inv_2r) {
+  const double h = alt + x * slope + x * x * inv_2r;
+  return (slope + 2.0 * x * inv_2r > 0.0 && h > (double)ce.suffix) || h < (double)ce.cell;
+}
+
 } // namespace atmrt

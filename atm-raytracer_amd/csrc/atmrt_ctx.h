@@ -113,6 +113,7 @@ using CeilKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, EarthKey, Lay
 // atm, terrain_uploaded, altitude_kind, latitude, longitude, altitude (what the observer's altitude is resolved from), fan lo, hi,
 // simulation_step, K, m, straight_rays, earth
 using ViewshedKey = std::tuple<uint64_t, uint64_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, int32_t, int32_t, int32_t, EarthKey>;
+using OrderKey = std::tuple<uint64_t, uint64_t, int32_t, int32_t, uint64_t>;        // ceiling, bins, image rows, altitude_kind, altitude
 inline EarthKey key_of(const Earth& e) {
   return {e.calc, e.flat_dirs, e.cart, e.spherical, bits(e.calc_radius), bits(e.cart_radius), bits(e.a), bits(e.b), bits(e.shape_radius)};
 }
@@ -179,6 +180,9 @@ struct atmrt_ctx {
   int32_t last_ceil_rows = 0;
   atmrt::CeilLayout last_ceil_layout{};
   uint64_t last_ceil_serial = 0;
+  // atmrt_debug_march_order: the work queue that frame marched with — its groups (0: none) and the build of `ceil_order` that filled it
+  uint32_t last_order_groups = 0;
+  uint64_t last_order_serial = 0;
 
   std::vector<atmrt::ObjectDev> objects; // host image of the device table (altitude kind in _pad until k_resolve)
   std::vector<uint8_t> textures;         // RGBA8 pool
@@ -197,6 +201,8 @@ struct atmrt_ctx {
   atmrt::Cached<atmrt::TrigKey> trig;
   atmrt::DevBuf d_ceil;                    // Spherical calculator, Rectilinear: the terrain ceiling table (atmrt_ceiling.h), (march_steps + 1) x (bins + 1) entries
   atmrt::Cached<atmrt::CeilKey> ceiling;
+  atmrt::DevBuf d_ceil_order;              // beside it: the work queue of the whole-frame march (Frame::ceil_order) and its sort's scratch (march_order_layout)
+  atmrt::Cached<atmrt::OrderKey> ceil_order;
   atmrt::DevBuf d_alt;                     // the observer's altitude (k_resolve): atmrt_draw_overlay* samples the atmosphere there
   atmrt::DevBuf d_objects, d_textures;     // the scene: the object table is uploaded every frame, the textures when objects_serial changes
   atmrt::Cached<uint64_t> textures_dev;

@@ -7,6 +7,7 @@
 
 #include "atmrt_core.h"
 #include "atmrt_ceiling.h"
+#include "atmrt_march_queue.h"
 #include "atmrt_objects.h"
 
 namespace atmrt {
@@ -55,6 +56,11 @@ struct Frame {
   const CeilEntry* ceil;
   CeilLayout ceil_layout;
   double ceil_floor;
+  // The work queue of the whole-frame opaque march (k_rect_march_queue): the frame's groups of 64 consecutive pixels, longest
+  // estimated march first (k_march_length_estimate over the table above) — a permutation of 0 .. ceil(wl h / 64) - 1 that decides
+  // scheduling only.  Null: no table, or a frame that does not take the queue (march_queue_wanted); the march is the plain grid.
+  const uint32_t* ceil_order;
+  const uint32_t* ceil_order_steps; // beside it: the estimated steps of every entry of ceil_order (descending): sizes the chunks claimed from its tail
 };
 
 // column azimuth / row elevation in degrees, as handed to gen_terrain_cache / gen_path_cache
@@ -242,13 +248,15 @@ static inline OverflowArena carve_overflow(char* base, size_t cap) {
 // The time-sliced march of small Rectilinear launches (atmrt_march_impl.h, k_rect_march_first / _cont): which launches take it and
 // what they need.  A launch of at most MARCH_SMALL_MAX_BLOCKS 256-thread blocks is "small" (a few resident sets: column shards of a
 // frame, test frames); ATMRT_MARCH_VARIANT=plain|small|sliced forces one variant for every launch (test hook: the random sweeps run
-// small frames over the kernel the full-size frames use, and the other way round; same results every way).
+// small frames over the kernel the full-size frames use, and the other way round; same results every way).  =queue forces the
+// whole-frame work queue (k_rect_march_queue) on the frames that can take it at any size — opaque terrain, no objects, the whole
+// image, a ceiling table — and leaves every other launch to the choice by size.
 constexpr unsigned MARCH_SMALL_MAX_BLOCKS = 16384u;
 constexpr int MARCH_SLICE_STEPS = 128;
 static inline int march_variant_override() {
   static const int v = [] {
     const char* e = getenv("ATMRT_MARCH_VARIANT");
-    return !e ? 0 : !strcmp(e, "plain") ? 1 : !strcmp(e, "small") ? 2 : !strcmp(e, "sliced") ? 3 : 0;
+    return !e ? 0 : !strcmp(e, "plain") ? 1 : !strcmp(e, "small") ? 2 : !strcmp(e, "sliced") ? 3 : !strcmp(e, "queue") ? 4 : 0;
   }();
   return v;
 }
@@ -278,7 +286,8 @@ static inline bool march_slice_layout(const Frame& f, SliceLayout& L) {
   // not stop at the terrain are of near-uniform length, which is what the slices were there to even out; the launcher picks between
   // the plain and the small-launch variant by the size of the grid (ATMRT_LAUNCH_MARCH).
   if (!f.opaque && ov != 3) return false;
-  if (ov ? ov != 3 : (n + 255) / 256 > MARCH_SMALL_MAX_BLOCKS) return false;
+  if (ov && ov != 4 ? ov != 3 : (n + 255) / 256 > MARCH_SMALL_MAX_BLOCKS) return false;
+  if (ov == 4 && f.ceil_order) return false; // the queue is forced and this frame has one
   L.n_groups = (uint32_t)((n + 63) / 64);
   L.n_pad = (size_t)L.n_groups * 64;
   L.slices_after = ((size_t)f.n_t + 2 + MARCH_SLICE_STEPS - 1) / MARCH_SLICE_STEPS;
@@ -288,6 +297,41 @@ static inline bool march_slice_layout(const Frame& f, SliceLayout& L) {
   // scenes with objects: every group's candidate list (what a wavefront of k_rect_march<3> keeps in LDS) travels with its state
   if (f.n_objects) L.bytes += 256 + (size_t)L.n_groups * SLICE_GROUP_LIST_BYTES;
   return true;
+}
+
+// The whole-frame work queue (k_rect_march_queue) is for the launches the plain grid runs today: opaque terrain without objects, the
+// whole image in one launch (the column tiles of a multi-GPU frame stay on the sliced march), a ceiling table to estimate from, and a
+// grid above MARCH_SMALL_MAX_BLOCKS unless ATMRT_MARCH_VARIANT=queue forces it.  `f` needs its ceiling fields but ceil_order.
+static inline bool march_queue_wanted(const Frame& f) {
+  const int ov = march_variant_override();
+  if (f.p.generator != ATMRT_GEN_RECTILINEAR || !f.opaque || !f.ceil || f.lattice || f.c0 != 0 || f.wl != (int32_t)f.p.width) return false;
+  return ov == 4 || (ov == 0 && ((size_t)f.wl * f.h + 255) / 256 > MARCH_SMALL_MAX_BLOCKS);
+}
+// Wavefronts per SIMD that claim from the head of the queue.  Measured on the headline frame (ATMRT_MARCH_QUEUE_LONG=1|2|3
+// is the A/B switch): with 1 the heads are served too slowly for the 2,200 items of 250 steps and more (8.28 ms per frame against
+// the grid's 8.75), with 2 the launch ends with its longest item (6.61 ms).
+constexpr int MARCH_QUEUE_LONG = 2;
+static inline int march_queue_long() {
+  static const int v = [] {
+    const char* e = getenv("ATMRT_MARCH_QUEUE_LONG");
+    const int l = e ? atoi(e) : MARCH_QUEUE_LONG;
+    return l < 1 ? 1 : l > 3 ? 3 : l;
+  }();
+  return v;
+}
+// the queue's scratch beside the ceiling table: the order, and what the counting sort needs to build it
+struct MarchOrder {
+  uint32_t* order;     // [n_groups] groups by estimated length, descending
+  uint32_t* order_steps; // [n_groups] the estimate of every entry of `order`
+  uint32_t* estimate;  // [n_groups] estimated steps of each group (the longest of its sampled rays), 0 .. march_steps
+  uint32_t* bin_count; // [march_steps + 1] groups per estimate, then the cursor of each estimate's run in `order`
+};
+static inline void march_order_layout(const Frame& f, Carve& k, MarchOrder& o) {
+  const size_t n_groups = ((size_t)f.wl * f.h + 63) / 64;
+  k(o.order, n_groups * sizeof(uint32_t));
+  k(o.order_steps, n_groups * sizeof(uint32_t));
+  k(o.estimate, n_groups * sizeof(uint32_t));
+  k(o.bin_count, ((size_t)f.march_steps + 1) * sizeof(uint32_t));
 }
 
 // Scratch of one frame.  Three owners (atmrt_ctx.h): the context's one workspace allocation, carved by workspace_layout below (array
@@ -328,6 +372,7 @@ struct Workspace {
   uint32_t* object_rays;  // Rectilinear, scenes with objects: pixels the lean march left to the general tracer
   char* step_ctx;         // Rectilinear, scenes with objects: Frame + StepSinks in HBM for the lean march's out-of-line object step
   char* slice_state;      // time-sliced march (march_slice_layout): ray state between two slices + the FIFO of groups, or null
+  unsigned long long* march_claim; // whole-frame work queue (Frame::ceil_order): the claim word, zeroed before the launch, or null
   // --- carved by workspace_layout in an opaque frame (the march's first hits, [4][h][wl]), else sized by the frame's trace points
   double* rect_rec;       // Rectilinear: [4][n] ray elevation / path length at the two bracketing samples
   // --- buffers of their own
@@ -393,6 +438,7 @@ static inline void workspace_layout(const Frame& f, Carve& k, Workspace& ws) {
   }
   SliceLayout slices;
   if (march_slice_layout(f, slices)) k(ws.slice_state, slices.bytes);   // a small Rectilinear launch: the time-sliced march
+  if (f.ceil_order) k(ws.march_claim, sizeof(unsigned long long));      // the whole-frame work queue
 }
 
 // InterpolatingRectilinear scratch
@@ -555,6 +601,8 @@ void launch_atm_sample(const Frame& f, size_t n, const double* alt, double* t, d
 void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, double* c, hipStream_t stream);
 // fills f.ceil (rows 0 .. f.march_steps) for f.ceil_layout: the cells, then every bin's suffix maxima
 void launch_ceiling(const Frame& f, CeilEntry* table, hipStream_t stream);
+// Frame::ceil_order from the table (f.ceil set): estimate, histogram, scan, scatter
+void launch_march_order(const Frame& f, const MarchOrder& o, hipStream_t stream);
 void launch_math_probe(int op, size_t n, const double* a, const double* b, double* out0, double* out1, hipStream_t stream);
 void launch_math_probe3(int op, size_t n, const double* a, const double* b0, const double* b1, const double* b2, double* out0, double* out1,
                         double* out2, int32_t* took, hipStream_t stream);

@@ -1504,6 +1504,87 @@ void launch_ceiling(const Frame& f, CeilEntry* table, hipStream_t stream) {
   hipLaunchKernelGGL(k_ceiling_suffix, dim3((unsigned)f.ceil_layout.n_bins), dim3(64), 0, stream, table, (int)rows, f.ceil_layout.n_bins + 1);
 }
 
+// Frame::ceil_order, the work queue of the whole-frame opaque march: the groups of 64 consecutive pixels by estimated length,
+// longest first.  One wavefront per group estimates the march of four rays across the group from the ceiling table (a wavefront
+// marches as long as its longest ray, and its 64 pixels span a dozen bins), 16 lanes to a ray and a step to a lane
+// (ceiling_estimate_ends; a thread that walks a ray alone waits for one table entry per step: 2.7 ms for the headline's 131,072
+// groups against 0.1 ms), and counts the longest into its estimate's bin; one workgroup turns the counts into the start of every
+// estimate's run, highest estimate first; a scatter appends every group to its run.  The order inside a run is whatever the
+// atomics make it: it decides scheduling only.
+__global__ __launch_bounds__(256) void k_march_length_estimate(Frame f, uint32_t n_groups, uint32_t* __restrict__ estimate,
+                                                               uint32_t* __restrict__ bin_count) {
+  const uint32_t g = (uint32_t)(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6); // wave-uniform
+  if (g >= n_groups) return;
+  const int lane = threadIdx.x & 63, ray = lane >> 4, sub = lane & 15;
+  const size_t plane = (size_t)f.wl * f.h;
+  const double r_eff = f.earth.shape_radius * (7.0 / 6.0), inv_2r = f.earth.spherical && r_eff > 0.0 ? 0.5 / r_eff : 0.0;
+  const double alt = observer_altitude(f);
+  size_t p = (size_t)g * 64 + (size_t)(ray * 21); // pixels 0, 21, 42, 63 of the group
+  p = p < plane ? p : plane - 1;
+  double direction, elevation;
+  rect_ray_params(f.p, f.ph, f.c0 + (int)(p % (size_t)f.wl), (int)(p / (size_t)f.wl), direction, elevation);
+  const double slope = tan(elevation);
+  const size_t stride = (size_t)f.ceil_layout.n_bins + 1, bin = (size_t)ceiling_bin(f.ceil_layout, direction);
+  int est = f.march_steps;
+  bool done = false; // of this lane's ray: the same in its 16 lanes
+  for (int base = 1; base <= f.march_steps; base += 16) {
+    const int i = base + sub;
+    const bool ends = !done && i <= f.march_steps && ceiling_estimate_ends(f.ceil[(size_t)i * stride + bin], f.xs[i], alt, slope, inv_2r);
+    const unsigned first = (unsigned)(__ballot(ends) >> (16 * ray)) & 0xffffu; // the steps base ... base + 15 of this ray that end it
+    if (!done && first) est = base + __builtin_ctz(first), done = true;
+    if (__all(done)) break;
+  }
+  for (int off = 16; off < 64; off <<= 1) { // the longest of the four
+    const int o = __shfl_xor(est, off, 64);
+    est = o > est ? o : est;
+  }
+  if (lane == 0) {
+    estimate[g] = (uint32_t)est; // 1 .. march_steps
+    atomicAdd(&bin_count[est], 1u);
+  }
+}
+// bin_count[b] -> the number of groups with an estimate above b: where the run of estimate b starts.  One workgroup; every thread
+// sums a stretch of consecutive bins, the stretches are scanned through LDS, then every thread walks its stretch again.
+__global__ __launch_bounds__(1024) void k_march_order_scan(uint32_t* __restrict__ bin_count, uint32_t n_bins) {
+  __shared__ uint32_t part[1024];
+  const uint32_t t = threadIdx.x, run = (n_bins + 1023u) / 1024u;
+  // stretch t, counted from the HIGHEST bin down: positions r = t run ... of the reversed bins, bin = n_bins - 1 - r
+  const uint32_t r0 = t * run < n_bins ? t * run : n_bins, r1 = r0 + run < n_bins ? r0 + run : n_bins;
+  uint32_t sum = 0;
+  for (uint32_t r = r0; r < r1; r++) sum += bin_count[n_bins - 1u - r];
+  part[t] = sum;
+  __syncthreads();
+  for (uint32_t off = 1; off < 1024u; off <<= 1) { // inclusive scan of the stretch sums
+    const uint32_t v = t >= off ? part[t - off] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t start = part[t] - sum;
+  for (uint32_t r = r0; r < r1; r++) {
+    const uint32_t c = bin_count[n_bins - 1u - r];
+    bin_count[n_bins - 1u - r] = start;
+    start += c;
+  }
+}
+__global__ __launch_bounds__(256) void k_march_order_scatter(uint32_t n_groups, const uint32_t* __restrict__ estimate,
+                                                             uint32_t* __restrict__ cursor, uint32_t* __restrict__ order,
+                                                             uint32_t* __restrict__ order_steps) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_groups) return;
+  const uint32_t est = estimate[g], at = atomicAdd(&cursor[est], 1u);
+  if (at < n_groups) order[at] = g, order_steps[at] = est; // (the runs tile 0 .. n_groups - 1: the counts of the same estimates made them)
+}
+void launch_march_order(const Frame& f, const MarchOrder& o, hipStream_t stream) {
+  const uint32_t n_groups = (uint32_t)(((size_t)f.wl * f.h + 63) / 64), n_bins = (uint32_t)f.march_steps + 1u;
+  if (!n_groups || !f.ceil) return;
+  (void)hipMemsetAsync(o.bin_count, 0, (size_t)n_bins * sizeof(uint32_t), stream);
+  hipLaunchKernelGGL(k_march_length_estimate, dim3(cdiv((size_t)n_groups * 64, 256)), dim3(256), 0, stream, f, n_groups, o.estimate, o.bin_count);
+  hipLaunchKernelGGL(k_march_order_scan, dim3(1), dim3(1024), 0, stream, o.bin_count, n_bins);
+  hipLaunchKernelGGL(k_march_order_scatter, dim3(cdiv(n_groups, 256)), dim3(256), 0, stream, n_groups, (const uint32_t*)o.estimate,
+                     o.bin_count, o.order, o.order_steps);
+}
+
 // detmath.h element-wise (atmrt_math_probe): the GPU's instruction sequences against the host's on arbitrary operands
 __global__ void k_math_probe(int op, size_t n, const double* __restrict__ a, const double* __restrict__ b,
                              double* __restrict__ out0, double* __restrict__ out1) {

@@ -80,7 +80,7 @@ constexpr unsigned drain_max_blocks() {
   do {                                                                                                                                 \
     const unsigned blocks_ = cdiv((size_t)(N), 256);                                                                                   \
     const int override_ = march_variant_override();                                                                                    \
-    if (override_ ? override_ != 1 : blocks_ <= drain_max_blocks<MODE>()) {                                                            \
+    if (override_ && override_ != 4 ? override_ != 1 : blocks_ <= drain_max_blocks<MODE>()) { /* 4 = queue: the grid goes by its size */ \
       ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march<MODE, CALC, CUBIC, true>),                                    \
                                                             dim3(cdiv((size_t)(N), ATMRT_MARCH_BLOCK_SMALL)), dim3(ATMRT_MARCH_BLOCK_SMALL), 0, STREAM, \
                                                             __VA_ARGS__));                                                             \
@@ -197,8 +197,10 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
 
 #ifdef ATMRT_TIMELINE
 // Experiment hook (tools/measure_march_timeline.py; never defined in the product build): start / end time and steps of every
-// wavefront of the last k_rect_march launch, read back through atmrt_debug_timeline.
-static __device__ unsigned long long g_timeline[3 * 65536 + 4 * 32768];
+// wavefront (k_rect_march_queue: of every 64-pixel group) of the last k_rect_march launch, read back through atmrt_debug_timeline.
+// TIMELINE_WAVES covers the whole headline frame (4096 x 2048 / 64 = 131072 groups) twice over.
+constexpr size_t TIMELINE_WAVES = 262144;
+static __device__ unsigned long long g_timeline[3 * TIMELINE_WAVES];
 static __device__ unsigned long long g_slices[4 * 262144 + 8]; // [0] = count; then {group | i0 << 32, start, end, wave | hw_id << 32}
 static __device__ __forceinline__ int timeline_wave_max(int v) {
   for (int o = 32; o; o >>= 1) {
@@ -331,6 +333,22 @@ struct MarchCount {
   unsigned long long steps = 0, lookups = 0;
   int esc_credit = -1; // >= 0: the ray escaped and was credited this many steps (escapes)
 };
+#ifdef ATMRT_TIMELINE
+// the steps the wavefront's loop ran: the most any of its lanes integrated (credited escape steps are not run)
+static __device__ __forceinline__ int timeline_wave_steps(const MarchCount& n) {
+  return timeline_wave_max((int)n.steps - (n.esc_credit > 0 ? n.esc_credit : 0));
+}
+// entry w of g_timeline: start, end, and steps | wavefront of its workgroup << 20 | HW_ID[15:0] (wave, simd, pipe, cu, sh, se) << 24 |
+// XCC_ID << 40 | wave-steps << 44
+static __device__ __forceinline__ void timeline_record(size_t w, unsigned long long t0, unsigned long long steps, int wave_steps) {
+  if ((threadIdx.x & 63) != 0 || w >= TIMELINE_WAVES) return;
+  g_timeline[3 * w] = t0;
+  g_timeline[3 * w + 1] = wall_clock64();
+  g_timeline[3 * w + 2] = (steps & 0xfffffull) | ((unsigned long long)((threadIdx.x >> 6) & 15u) << 20) | ((unsigned long long)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xffffu) << 24) |
+                          ((unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xfu) << 40) |
+                          ((unsigned long long)(wave_steps & 0xfffff) << 44);
+}
+#endif
 enum MarchEnd {
   MARCH_ENDED,   // the ray has finished
   MARCH_ON,      // the slice has ended, the ray marches on
@@ -541,20 +559,94 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
     }
   }
   if (MODE != 2) {
+#ifdef ATMRT_TIMELINE
+    const int tl_wave_steps = timeline_wave_steps(n);
+#endif
     const unsigned long long steps = count_wave_steps<true>(counters, n.steps, n.lookups, n.esc_credit);
     (void)steps;
 #ifdef ATMRT_TIMELINE
-    if (MODE == 0 && (threadIdx.x & 63) == 0) {
-      const size_t w = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-      if (w < 65536) {
-        g_timeline[3 * w] = tl_t0;
-        g_timeline[3 * w + 1] = wall_clock64();
-        // steps | HW_ID[15:0] (wave, simd, pipe, cu, sh, se) << 24 | XCC_ID << 40
-        g_timeline[3 * w + 2] = steps | ((unsigned long long)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xffffu) << 24) |
-                                ((unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xfu) << 40);
-      }
-    }
+    if (MODE == 0) timeline_record(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, tl_t0, steps, tl_wave_steps);
 #endif
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The whole-frame work queue (opaque terrain, MODE 0).  After the escape shortcut and the ceiling table two thirds
+// of the headline's wave-steps sit in a few thousand wavefronts around the skyline (250 - 1,700 steps each, against tens for the
+// rest), and an ordinary grid deals a SIMD about five of them at random: the sum of five such draws, maximised over 1,024 SIMDs,
+// is twice its mean, and the launch ends ragged.  Here the unit of work is an ITEM — a group of 64 consecutive pixels, marched
+// whole, by exactly the per-ray code of k_rect_march — and the items come from a queue sorted by estimated length, longest first
+// (Frame::ceil_order, k_march_length_estimate).  One persistent workgroup of 16 wavefronts per CU (1024 threads at <= 128 VGPRs: a
+// CU holds no second one, so there are 4 wavefronts on every SIMD by construction), and on every SIMD `n_long` of them are LONG:
+// they take one item at a time from the head of the queue and run at a raised priority, so a SIMD works on n_long long items at a
+// time, each at the speed of its dependency chain, while the SHORT wavefronts fill the issue slots they leave with chunks of items
+// from the tail, each chunk sized by the estimate of the item it starts at (queue_chunk_for: a chunk is one wavefront's serial work,
+// and chunks of 16 items that reach into the skyline band cost the frame 26 ms instead of 8).  Which wavefronts are long is elected per SIMD through LDS from the SIMD each wavefront finds itself on, not
+// assumed from its index.  The claim arithmetic is atmrt_march_queue.h; `claim` is zeroed on the stream before every launch.
+// ---------------------------------------------------------------------------------------------
+template <int CALC, bool CUBIC>
+__global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes out, MarchSinks sinks, unsigned long long* __restrict__ counters,
+                                                           const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_steps,
+                                                           unsigned long long* __restrict__ claim, uint32_t n_groups, int n_long) {
+  __shared__ int simd_rank[4];
+  if (threadIdx.x < 4) simd_rank[threadIdx.x] = 0;
+  stage_dm_tables(); // (ends in a workgroup barrier: the ranks are zero from here on)
+  const int lane = threadIdx.x & 63;
+  int rank = 0;
+  if (lane == 0) rank = atomicAdd(&simd_rank[(__builtin_amdgcn_s_getreg((15 << 11) | 4) >> 4) & 3], 1); // HW_ID[5:4]: SIMD_ID
+  const bool is_long = __builtin_amdgcn_readfirstlane(rank) < n_long;
+  if (is_long) __builtin_amdgcn_s_setprio(1);
+  const size_t plane = (size_t)f.wl * f.h;
+  const Earth e = earth_for<CALC>(f);
+  const double alt = *f.alt;
+  __shared__ WaveListLds<0, 1> lists;
+  for (;;) {
+    // a short wavefront sizes its chunk by the estimate of the item at the tail as it is now (a look, not a claim: the tail may have
+    // moved on by the time of the claim, towards longer items — by a few claims' worth)
+    unsigned long long seen = 0;
+    uint32_t chunk = 1;
+    if (lane == 0) {
+      if (!is_long) {
+        const unsigned long long now = __hip_atomic_load(claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long tail = now >> 32;
+        chunk = tail < (unsigned long long)n_groups ? queue_chunk_for(order_steps[n_groups - 1u - (uint32_t)tail]) : 1u;
+      }
+      seen = atomicAdd(claim, queue_claim_increment(is_long, chunk));
+    }
+    chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk);
+    seen = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(seen >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(seen & 0xffffffffull));
+    uint32_t first;
+    const uint32_t count = queue_claim_items(seen, is_long, chunk, n_groups, first);
+    if (!count) break;
+    for (uint32_t k = 0; k < count; k++) {
+#ifdef ATMRT_TIMELINE
+      const unsigned long long tl_t0 = wall_clock64();
+#endif
+      const uint32_t group = order[is_long ? first : first - k];
+      const size_t p = (size_t)group * 64 + lane;
+      MarchCount n;
+      if (p < plane) { // (also keeps a group number that is none out of every array)
+        double direction, elevation;
+        DirCalc c;
+        MarchRay r;
+        rect_ray_setup(f, e, p, alt, direction, elevation, c, r.s);
+        const int bin = f.ceil ? ceiling_bin(f.ceil_layout, direction) : 0;
+        r.k = 0;
+        WaveList wl = lists.wave(0);
+        if (march_begin(f, e, c, alt, r, n)) march_steps<0, CALC, CUBIC, false, false>(f, e, c, r, n, 0, 0, sinks, counters, p, wl, bin);
+        store_ray_angles(out, p, direction, elevation);
+        march_finish<0>(out, sinks, counters, p, r);
+      }
+#ifdef ATMRT_TIMELINE
+      const int tl_wave_steps = timeline_wave_steps(n);
+#endif
+      const unsigned long long steps = count_wave_steps<true>(counters, n.steps, n.lookups, n.esc_credit);
+      (void)steps;
+#ifdef ATMRT_TIMELINE
+      timeline_record(group, tl_t0, steps, tl_wave_steps);
+#endif
+    }
   }
 }
 
@@ -1104,6 +1196,22 @@ static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DenseP
   return true;
 }
 
+// The whole-frame work queue (k_rect_march_queue) for the frames that have an order (Frame::ceil_order, march_queue_wanted): one
+// workgroup per CU.  false: the frame has none and the caller launches the grid.
+template <bool CUBIC>
+static bool launch_rect_march_queue(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
+  if (!f.ceil_order || !f.ceil_order_steps || !ws.march_claim) return false;
+  int device = 0, cus = 0;
+  if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1)
+    return false;
+  const uint32_t n_groups = (uint32_t)(((size_t)f.wl * f.h + 63) / 64);
+  (void)hipMemsetAsync(ws.march_claim, 0, sizeof(unsigned long long), stream);
+  ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_queue<CALC, CUBIC>), dim3((unsigned)cus), dim3(1024), 0, stream, f, out, sinks,
+                                                        (unsigned long long*)ws.counters, f.ceil_order, f.ceil_order_steps, ws.march_claim, n_groups,
+                                                        march_queue_long()));
+  return true;
+}
+
 template <bool CUBIC>
 void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched) {
   size_t n = (size_t)f.wl * f.h;
@@ -1112,7 +1220,8 @@ void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, 
   if (f.opaque) {
     sinks.hit_step = ws.hit_step;
     sinks.rec = rec;
-    if (!launch_rect_march_sliced<0, CUBIC>(f, ws, out, sinks, stream)) ATMRT_LAUNCH_MARCH(0, n, stream, f, out, sinks, (unsigned long long*)ws.counters);
+    if (!launch_rect_march_sliced<0, CUBIC>(f, ws, out, sinks, stream) && !launch_rect_march_queue<CUBIC>(f, ws, out, sinks, stream))
+      ATMRT_LAUNCH_MARCH(0, n, stream, f, out, sinks, (unsigned long long*)ws.counters);
     (void)hipEventRecord(ev_marched, stream);
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_finalize<CALC>), dim3(cdiv(n, 256)), dim3(256), 0, stream,
                                                           f, ws.hit_step, rec, out));

@@ -126,6 +126,17 @@ class Context:
         shape = (rows.value, bins.value + 1) if n else (0, 0)
         return dict(rows=rows.value, n_bins=bins.value, layout=tuple(lay), cell=cell.reshape(shape), suffix=suffix.reshape(shape))
 
+    def debug_march_order(self):
+        """Diagnostic (atmrt_debug_march_order): the work queue the last generated frame's whole-frame march took its 64-pixel
+        groups from, uint32 [n_groups], longest estimated march first; empty when that frame marched without one."""
+        n = C.c_uint32()
+        self.check(self.lib.atmrt_debug_march_order(self.handle, 0, None, C.byref(n)))
+        order = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.check(self.lib.atmrt_debug_march_order(self.handle, n.value, order.ctypes.data, C.byref(n)))
+            assert n.value == order.size
+        return order
+
     def fail_next_collective(self, index=0, nth=1):
         """Test hook (atmrt_debug_fail_next_collective)."""
         self.check(self.lib.atmrt_debug_fail_next_collective(self.handle, index, nth))

@@ -962,6 +962,13 @@ int atmrt_debug_step_trig(atmrt_ctx* ctx, size_t cap, double* xs, double* sin_ou
  * harness or a tool such as atmrt_viewshed) has built another table in its place.  tests/test_gpu_ceiling_table.py compares the
  * table with the one tests/csrc/ceiling_host.cpp builds on the host: every byte must be equal. */
 int atmrt_debug_ceiling_table(atmrt_ctx* ctx, size_t cap, float* cell, float* suffix, int32_t* rows, int32_t* n_bins, double layout[3]);
+/* A diagnostic of the same kind: the work queue the LAST GENERATED FRAME's whole-frame opaque march took its 64-pixel groups from
+ * (DESIGN.md §7.9), longest estimated march first.  *n_groups = its entries, ceil(pixels / 64) (0, and nothing written: that frame
+ * marched without a queue — a small frame unless ATMRT_MARCH_VARIANT=queue, translucent terrain, objects, a column tile, no ceiling
+ * table); order receives the first min(cap, *n_groups) of them.  The order decides scheduling only, and entries of equal estimate
+ * may change places from build to build; what must hold is that it is a permutation of 0 .. *n_groups - 1
+ * (tests/test_gpu_march_queue.py).  ATMRT_ERR_STATE when a later call has built another order in its place. */
+int atmrt_debug_march_order(atmrt_ctx* ctx, size_t cap, uint32_t* order, uint32_t* n_groups);
 
 #ifdef __cplusplus
 }
