@@ -309,13 +309,34 @@ static inline bool march_queue_wanted(const Frame& f) {
 }
 // Wavefronts per SIMD that claim from the head of the queue.  Measured on the headline frame (ATMRT_MARCH_QUEUE_LONG=1|2|3
 // is the A/B switch): with 1 the heads are served too slowly for the 2,200 items of 250 steps and more (8.28 ms per frame against
-// the grid's 8.75), with 2 the launch ends with its longest item (6.61 ms).
+// the grid's 8.75), with 2 the launch ends with its longest item (6.61 ms).  With priorities by item and chunks that shrink as the
+// queue empties (below) 3 measured 0.12 ms below 2 on the headline frame in every run, which is less than three
+// spreads (0.18 ms) and was measured on no other shape: 2 stays.
 constexpr int MARCH_QUEUE_LONG = 2;
 static inline int march_queue_long() {
   static const int v = [] {
     const char* e = getenv("ATMRT_MARCH_QUEUE_LONG");
     const int l = e ? atoi(e) : MARCH_QUEUE_LONG;
     return l < 1 ? 1 : l > 3 ? 3 : l;
+  }();
+  return v;
+}
+// What a long wavefront's priority goes by (ATMRT_MARCH_QUEUE_PRIO=role|item is the A/B switch, read once per
+// process).  item: the estimate of the item it owns against the head's (queue_item_priority: 3, 2 or 1).  role: every long wavefront
+// at 1, as before.
+static inline bool march_queue_item_prio() {
+  static const bool v = [] {
+    const char* e = getenv("ATMRT_MARCH_QUEUE_PRIO");
+    return !(e && !strcmp(e, "role"));
+  }();
+  return v;
+}
+// Chunks that shrink as the queue empties (queue_chunk_cap; ATMRT_MARCH_QUEUE_CHUNKS=steps|guided is the A/B switch): false — a
+// chunk goes by the steps rule alone, as before.
+static inline bool march_queue_guided() {
+  static const bool v = [] {
+    const char* e = getenv("ATMRT_MARCH_QUEUE_CHUNKS");
+    return !(e && !strcmp(e, "steps"));
   }();
   return v;
 }

@@ -201,6 +201,7 @@ static __device__ __attribute__((noinline)) void object_step_impl(const Frame* _
 // TIMELINE_WAVES covers the whole headline frame (4096 x 2048 / 64 = 131072 groups) twice over.
 constexpr size_t TIMELINE_WAVES = 262144;
 static __device__ unsigned long long g_timeline[3 * TIMELINE_WAVES];
+static __device__ uint32_t g_timeline_estimate[TIMELINE_WAVES]; // k_rect_march_queue: the group's estimate | 1 << 31: marched by a long wavefront
 static __device__ unsigned long long g_slices[4 * 262144 + 8]; // [0] = count; then {group | i0 << 32, start, end, wave | hw_id << 32}
 static __device__ __forceinline__ int timeline_wave_max(int v) {
   for (int o = 32; o; o >>= 1) {
@@ -579,15 +580,22 @@ __global__ __launch_bounds__(DRAIN ? ATMRT_MARCH_BLOCK_SMALL : 256, DRAIN ? ATMR
 // (Frame::ceil_order, k_march_length_estimate).  One persistent workgroup of 16 wavefronts per CU (1024 threads at <= 128 VGPRs: a
 // CU holds no second one, so there are 4 wavefronts on every SIMD by construction), and on every SIMD `n_long` of them are LONG:
 // they take one item at a time from the head of the queue and run at a raised priority, so a SIMD works on n_long long items at a
-// time, each at the speed of its dependency chain, while the SHORT wavefronts fill the issue slots they leave with chunks of items
-// from the tail, each chunk sized by the estimate of the item it starts at (queue_chunk_for: a chunk is one wavefront's serial work,
-// and chunks of 16 items that reach into the skyline band cost the frame 26 ms instead of 8).  Which wavefronts are long is elected per SIMD through LDS from the SIMD each wavefront finds itself on, not
-// assumed from its index.  The claim arithmetic is atmrt_march_queue.h; `claim` is zeroed on the stream before every launch.
+// time, each at the speed of its dependency chain, while the SHORT wavefronts (priority 0) fill the issue slots they leave with
+// chunks of items from the tail.  A long wavefront sets its priority after every claim by the item it now owns (item_prio; DESIGN.md
+// §7.10): 3 where the item's estimate is at least half of the head's (order_steps[0], the longest of the frame), 2 from an eighth,
+// 1 below (queue_item_priority) — the long items of a SIMD are served in the order of their length, not by turns.  A chunk is sized
+// by the estimate of the item it starts at (queue_chunk_for: a chunk is one wavefront's serial work, and chunks of 16 items that
+// reach into the skyline band cost the frame 26 ms instead of 8) and capped by a wavefront's even share of what is left
+// (`claimers`: the wavefronts of the launch; queue_chunk_cap), so that chunks shrink to single items as the queue empties and the launch drains in one
+// item, not in one chunk.  Which wavefronts are long is elected per SIMD through LDS from the SIMD each wavefront finds itself on,
+// not assumed from its index.  No wavefront ever waits for another: claims are single fetch-and-adds.  The claim arithmetic is
+// atmrt_march_queue.h; `claim` is zeroed on the stream before every launch.
 // ---------------------------------------------------------------------------------------------
 template <int CALC, bool CUBIC>
 __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes out, MarchSinks sinks, unsigned long long* __restrict__ counters,
                                                            const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_steps,
-                                                           unsigned long long* __restrict__ claim, uint32_t n_groups, int n_long) {
+                                                           unsigned long long* __restrict__ claim, uint32_t n_groups, int n_long, bool item_prio,
+                                                           uint32_t claimers) {
   __shared__ int simd_rank[4];
   if (threadIdx.x < 4) simd_rank[threadIdx.x] = 0;
   stage_dm_tables(); // (ends in a workgroup barrier: the ranks are zero from here on)
@@ -599,17 +607,20 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
   const size_t plane = (size_t)f.wl * f.h;
   const Earth e = earth_for<CALC>(f);
   const double alt = *f.alt;
+  const uint32_t head_steps = n_groups ? order_steps[0] : 0u; // the longest estimate of the frame: what a long item's estimate is set against
   __shared__ WaveListLds<0, 1> lists;
   for (;;) {
-    // a short wavefront sizes its chunk by the estimate of the item at the tail as it is now (a look, not a claim: the tail may have
-    // moved on by the time of the claim, towards longer items — by a few claims' worth)
+    // a short wavefront sizes its chunk by the estimate of the item at the tail as it is now and by the items left (a look, not a
+    // claim: the tail may have moved on by the time of the claim, towards longer items — by a few claims' worth)
     unsigned long long seen = 0;
     uint32_t chunk = 1;
     if (lane == 0) {
       if (!is_long) {
         const unsigned long long now = __hip_atomic_load(claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long tail = now >> 32;
-        chunk = tail < (unsigned long long)n_groups ? queue_chunk_for(order_steps[n_groups - 1u - (uint32_t)tail]) : 1u;
+        chunk = tail < (unsigned long long)n_groups
+                    ? queue_chunk_for(order_steps[n_groups - 1u - (uint32_t)tail], queue_items_left(now, n_groups), claimers)
+                    : 1u;
       }
       seen = atomicAdd(claim, queue_claim_increment(is_long, chunk));
     }
@@ -619,6 +630,12 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
     uint32_t first;
     const uint32_t count = queue_claim_items(seen, is_long, chunk, n_groups, first);
     if (!count) break;
+    if (is_long && item_prio) { // the priority of the item this wavefront now owns (s_setprio takes an immediate)
+      const int prio = queue_item_priority(order_steps[first], head_steps);
+      if (prio == 3) __builtin_amdgcn_s_setprio(3);
+      else if (prio == 2) __builtin_amdgcn_s_setprio(2);
+      else __builtin_amdgcn_s_setprio(1);
+    }
     for (uint32_t k = 0; k < count; k++) {
 #ifdef ATMRT_TIMELINE
       const unsigned long long tl_t0 = wall_clock64();
@@ -645,6 +662,7 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
       (void)steps;
 #ifdef ATMRT_TIMELINE
       timeline_record(group, tl_t0, steps, tl_wave_steps);
+      if (lane == 0 && group < TIMELINE_WAVES) g_timeline_estimate[group] = order_steps[is_long ? first : first - k] | (is_long ? 1u << 31 : 0u);
 #endif
     }
   }
@@ -1208,7 +1226,8 @@ static bool launch_rect_march_queue(const Frame& f, Workspace& ws, const DensePl
   (void)hipMemsetAsync(ws.march_claim, 0, sizeof(unsigned long long), stream);
   ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_queue<CALC, CUBIC>), dim3((unsigned)cus), dim3(1024), 0, stream, f, out, sinks,
                                                         (unsigned long long*)ws.counters, f.ceil_order, f.ceil_order_steps, ws.march_claim, n_groups,
-                                                        march_queue_long()));
+                                                        march_queue_long(), march_queue_item_prio(),
+                                                        march_queue_guided() ? (uint32_t)cus * 16u : 0u)); // the launch's wavefronts
   return true;
 }
 

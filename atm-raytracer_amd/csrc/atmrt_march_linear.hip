@@ -43,6 +43,9 @@ void launch_rect_finalize_list(const Frame& f, Workspace& ws, uint64_t n_hits, c
 extern "C" int atmrt_debug_timeline(unsigned long long* dst, size_t n_words) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(atmrt::g_timeline), n_words * sizeof(unsigned long long));
 }
+extern "C" int atmrt_debug_timeline_estimates(uint32_t* dst, size_t n) {
+  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(atmrt::g_timeline_estimate), n * sizeof(uint32_t));
+}
 extern "C" int atmrt_debug_slices(unsigned long long* dst, size_t n_words) {
   int rc = (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(atmrt::g_slices), n_words * sizeof(unsigned long long));
   unsigned long long zero = 0;

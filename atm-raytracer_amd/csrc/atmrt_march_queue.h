@@ -28,6 +28,32 @@ ATMRT_QUEUE_HD uint32_t queue_chunk_for(uint32_t estimated_steps) {
   const uint32_t c = MARCH_QUEUE_CHUNK_STEPS / (estimated_steps ? estimated_steps : 1u);
   return c < 1u ? 1u : c > MARCH_QUEUE_CHUNK ? MARCH_QUEUE_CHUNK : c;
 }
+// Towards the end of the queue a chunk is also the length of the drain: the wavefronts that still own several items while every
+// other claimer finds nothing.  So a chunk shrinks with what is left: besides the steps rule, at most left / (k x claimers) items,
+// `left` = n - h - t of the word the claimer looked at (the look it sizes its chunk by anyway) and `claimers` the wavefronts of
+// the launch — a k-th of an even share — and 1 once left <= k x claimers, so that the drain is one item long.  claimers 0: no cap.
+// k = 1 by measurement (with 4,096 wavefronts k = 1/2 and k = 2 cost the headline frame 0.1 ms, k = 4 0.3 ms).
+constexpr uint32_t MARCH_QUEUE_GUIDE_K = 1;
+ATMRT_QUEUE_HD uint32_t queue_chunk_cap(uint32_t left, uint32_t claimers) {
+  if (!claimers) return MARCH_QUEUE_CHUNK;
+  const unsigned long long c = (unsigned long long)left / ((unsigned long long)MARCH_QUEUE_GUIDE_K * claimers);
+  return c < 1u ? 1u : c > MARCH_QUEUE_CHUNK ? MARCH_QUEUE_CHUNK : (uint32_t)c;
+}
+ATMRT_QUEUE_HD uint32_t queue_chunk_for(uint32_t estimated_steps, uint32_t left, uint32_t claimers) {
+  const uint32_t c = queue_chunk_for(estimated_steps), cap = queue_chunk_cap(left, claimers);
+  return c < cap ? c : cap;
+}
+// the items left in the queue at the word `seen` (0 once it has run empty)
+ATMRT_QUEUE_HD uint32_t queue_items_left(unsigned long long seen, uint32_t n) {
+  const unsigned long long h = seen & 0xffffffffull, t = seen >> 32;
+  return h + t >= (unsigned long long)n ? 0u : (uint32_t)((unsigned long long)n - h - t);
+}
+
+// The priority of a long claimer, by the estimate of the item it now owns against the head's (the longest estimate of the frame):
+// 3 from half of it on, 2 from an eighth, 1 below.  (Short claimers run at 0.)
+ATMRT_QUEUE_HD int queue_item_priority(uint32_t estimated_steps, uint32_t head_steps) {
+  return estimated_steps >= (head_steps + 1u) / 2u ? 3 : estimated_steps >= (head_steps + 7u) / 8u ? 2 : 1;
+}
 
 // what a claimer adds to the word
 ATMRT_QUEUE_HD unsigned long long queue_claim_increment(bool is_long, uint32_t chunk) {

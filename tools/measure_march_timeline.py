@@ -59,6 +59,20 @@ se = (hw >> 13) & 7
 cu_key = (xcc * 8 + se) * 16 + cu
 simd_key = cu_key * 4 + simd
 wl = c1 - c0
+# the queue's view of every group: its position in the order, and (a library with atmrt_debug_timeline_estimates) the estimate it
+# was sorted by and whether a long wavefront marched it
+position = estimate = by_long = None
+if WHOLE:
+    order = ctx.debug_march_order()
+    if order.size == n_waves:
+        position = np.empty(n_waves, dtype=np.int64)
+        position[order] = np.arange(n_waves)
+        if hasattr(lib, "atmrt_debug_timeline_estimates"):
+            est = np.zeros(n_waves, dtype=np.uint32)
+            lib.atmrt_debug_timeline_estimates.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+            assert lib.atmrt_debug_timeline_estimates(est.ctypes.data, est.size) == 0
+            estimate = (est & np.uint32(0x7fffffff)).astype(np.int64)
+            by_long = (est >> np.uint32(31)).astype(np.int64)
 
 
 def whole_frame(out):
@@ -79,12 +93,28 @@ def whole_frame(out):
     k = int(np.argmax(dur))
     p(f"longest single entry: {dur[k]:.3f} ms = {dur[k] / span:.3f} of the span ({loop[k]} wave-steps, group {k}, row {k * 64 // wl}, "
       f"start {st[k]:.3f} ms); per wave-step {1e3 * dur[k] / max(loop[k], 1):.2f} us")
-    p("most wave-steps: (group, row, start, end, wave-steps, us per wave-step)")
-    for w in np.argsort(-loop)[:6]:
-        p(f"  {w:6d} row {w * 64 // wl:5d} {st[w]:7.3f} {en[w]:7.3f} {loop[w]:6d} {1e3 * dur[w] / max(loop[w], 1):6.2f}")
-    p("last to end: (group, row, start, end, wave-steps, SIMD key)")
+    def queue_columns(w):  # position in the order, estimate, L = marched by a long wavefront
+        if position is None:
+            return ""
+        return f" pos {position[w]:6d}" + ("" if estimate is None else f" est {estimate[w]:5d} {'L' if by_long[w] else 's'}")
+    p(f"span minus the mean end of a SIMD: {span - last.mean():.3f} ms; the launch ends with group {int(np.argmax(en))}, "
+      f"started at {st[int(np.argmax(en))]:.3f} ms")
+    if estimate is not None:
+        p(f"estimate of the head {estimate[position == 0][0]}; entries marched by long wavefronts {int(by_long.sum())}")
+        head = int(estimate[position == 0][0])
+        eighth = (head + 7) // 8
+        p(f"entries that outrun their estimate: by an eighth of the head's ({eighth}) {int((loop > estimate + eighth).sum())}, by a quarter "
+          f"{int((loop > estimate + 2 * eighth).sum())}; to twice the estimate and past a quarter of the head's "
+          f"{int(((loop >= 2 * estimate) & (loop >= 2 * eighth)).sum())}")
+        p("largest wave-steps minus estimate: (group, row, start, end, wave-steps, us per wave-step, position in the order, estimate, long / short)")
+        for w in np.argsort(-(loop - estimate))[:12]:
+            p(f"  {w:6d} row {w * 64 // wl:5d} {st[w]:7.3f} {en[w]:7.3f} {loop[w]:6d} {1e3 * dur[w] / max(loop[w], 1):6.2f}{queue_columns(w)}")
+    p("most wave-steps: (group, row, start, end, wave-steps, us per wave-step[, position in the order, estimate, long / short])")
+    for w in np.argsort(-loop)[:10]:
+        p(f"  {w:6d} row {w * 64 // wl:5d} {st[w]:7.3f} {en[w]:7.3f} {loop[w]:6d} {1e3 * dur[w] / max(loop[w], 1):6.2f}{queue_columns(w)}")
+    p("last to end: (group, row, start, end, wave-steps, SIMD key[, position in the order, estimate, long / short])")
     for w in np.argsort(-en)[:10]:
-        p(f"  {w:6d} row {w * 64 // wl:5d} {st[w]:7.3f} {en[w]:7.3f} {loop[w]:6d} {simd_key[w]:6d}")
+        p(f"  {w:6d} row {w * 64 // wl:5d} {st[w]:7.3f} {en[w]:7.3f} {loop[w]:6d} {simd_key[w]:6d}{queue_columns(w)}")
     heavy = loop >= 250
     p(f"entries of >= 250 wave-steps: {int(heavy.sum())}, carrying {int(loop[heavy].sum())} wave-steps; per SIMD mean "
       f"{np.bincount(inv, weights=heavy).mean():.2f} max {int(np.bincount(inv, weights=heavy).max())}")
@@ -118,7 +148,8 @@ def whole_frame(out):
     p("per SIMD: key (((xcc * 8 + se) * 16 + cu) * 4 + simd), entries, wave-steps, end of its last wavefront in ms")
     for q in np.argsort(-last):
         p(f"{keys[q]:6d} {count[q]:6d} {work[q]:8d} {last[q]:8.3f}")
-    return {"event_ms": ms, "span_ms": span, "longest_ms": float(dur[k]), "longest_frac": float(dur[k] / span),
+    return {"event_ms": ms, "span_ms": span, "simd_end_mean_ms": float(last.mean()), "span_minus_simd_end_ms": float(span - last.mean()),
+            "last_group": int(np.argmax(en)), "last_group_start_ms": float(st[int(np.argmax(en))]), "longest_ms": float(dur[k]), "longest_frac": float(dur[k] / span),
             "wave_steps": int(loop.sum()), "simd_work_mean": float(work.mean()), "simd_work_max": int(work.max())}
 
 

@@ -122,7 +122,7 @@ def main():
         if "SQ_THREAD_CYCLES_VALU" in v and v.get("SQ_ACTIVE_INST_VALU"):
             v["lane_utilisation"] = v["SQ_THREAD_CYCLES_VALU"] / (64.0 * v["SQ_ACTIVE_INST_VALU"])
         for frag, n in steps.items():
-            if frag in k and "SQ_INSTS_VALU" in v and "lane_utilisation" in v and ("march<0" in k or "intersect<8, 0" in k):
+            if frag in k and "SQ_INSTS_VALU" in v and "lane_utilisation" in v and ("march<0" in k or "march_queue<" in k or "intersect<8, 0" in k):
                 per_frame = sq_launches.get(k, 0) / frames[frag] if frames.get(frag) else 1.0  # a kernel launched in segments
                 v["launches_per_frame"] = per_frame
                 v["valu_lane_instructions_per_ray_step"] = v["SQ_INSTS_VALU"] * per_frame * 64.0 * v["lane_utilisation"] / n
