@@ -141,6 +141,7 @@ def load():
         "atmrt_math_probe": (C.c_int, [vp, i32, sz, vp, vp, vp, vp]),
         "atmrt_math_probe3": (C.c_int, [vp, i32, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "atmrt_debug_step_trig": (C.c_int, [vp, sz, vp, vp, vp, C.POINTER(sz)]),
+        "atmrt_debug_normal_trig": (C.c_int, [vp, sz, vp, C.POINTER(sz)]),
         "atmrt_debug_ceiling_table": (C.c_int, [vp, sz, vp, vp, C.POINTER(i32), C.POINTER(i32), pd]),
         "atmrt_debug_march_order": (C.c_int, [vp, sz, vp, C.POINTER(C.c_uint32)]),
         "atmrt_result_encode_bincode": (C.c_int, [C.POINTER(_abi.Result), i32, vp, sz, C.POINTER(sz)]),
@@ -184,7 +185,7 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_debug_viewshed_shape", "atmrt_viewshed_steps", "atmrt_viewshed", "atmrt_viewshed_device", "atmrt_last_viewshed_timings", "atmrt_last_viewshed_work",
             "atmrt_viewshed_map_planes_device", "atmrt_viewshed_map_device", "atmrt_viewshed_map",
             "atmrt_debug_horizon_shape", "atmrt_horizon", "atmrt_horizon_device", "atmrt_last_horizon_timings", "atmrt_last_horizon_work", "atmrt_ray_paths", "atmrt_atmosphere_sample",
-            "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_result_encode_bincode",
+            "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_result_encode_bincode",
             "atmrt_result_decode_bincode", "atmrt_comm_unique_id", "atmrt_ctx_comm_init_rank", "atmrt_ctx_comm_init_external", "atmrt_ctx_comm_init_external_device",
             "atmrt_ctx_create_multi", "atmrt_ctx_device_count", "atmrt_generate_image_device", "atmrt_image_hits_device",
             "atmrt_draw_image_gathered_device", "atmrt_last_comm_timings", "atmrt_comm_available", "atmrt_ctx_tile_columns",

@@ -684,6 +684,12 @@ static bool step_trig_enabled() {
   const char* e = getenv("ATMRT_STEP_TRIG");
   return !(e && !strcmp(e, "off"));
 }
+// ATMRT_NORMAL_TRIG=off: no record of the epilogue's frame constants (Frame::normal_trig), every trace point computes them (A/B runs,
+// tests/test_gpu_normal_trig.py).  Read at every frame.
+static bool normal_trig_enabled() {
+  const char* e = getenv("ATMRT_NORMAL_TRIG");
+  return !(e && !strcmp(e, "off"));
+}
 
 // ATMRT_CEILING=off: no terrain ceiling table (Frame::ceil), the march runs on the mosaic's top alone; =rebuild: the table is built
 // again in every frame, as for an observer that moves from frame to frame (A/B runs, tests/test_gpu_ceiling.py).  Read at every frame.
@@ -798,6 +804,18 @@ static int refresh_trig(atmrt_ctx* c) {
   });
 }
 
+// The Spherical calculator's constants of the trace-point epilogue, by the device code a lane would run (k_normal_trig): the earth
+// model is the same from call to call, the observer's position changes when the observer moves.  The kernels of this frame follow on
+// the same stream.
+static int refresh_normal_trig(atmrt_ctx* c, const atmrt_params_t& p) {
+  return c->normal_trig.refresh({bits(c->earth.calc_radius), c->earth.flat_dirs & EARTH_FAST_DIV, bits(p.position.latitude), bits(p.position.longitude)}, [&](Nothing&) {
+    HIP_TRY(c, c->d_normal_trig.reserve(sizeof(NormalTrig)));
+    launch_normal_trig(c->earth, p.position.latitude, p.position.longitude, c->d_normal_trig.as<NormalTrig>(), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+  });
+}
+
 // The compiled table and its certificates: hosts set the same atmosphere before every frame (the Python mirror does), and the
 // certificate's bisections are a quarter of a millisecond of host time — a twentieth of a Fast frame.
 static int refresh_atm(atmrt_ctx* c, const atmrt_params_t& p) {
@@ -846,7 +864,8 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   if (rc) return rc;
   const atmrt_params_t& p = c->params;
   const bool trig = c->earth.calc == 2 && step_trig_enabled(); // off: a table of an earlier frame stays as it is
-  if ((rc = refresh_steps(c, p)) || (trig && (rc = refresh_trig(c))) || (rc = refresh_atm(c, p)) || (rc = refresh_escape(c, p)) || (rc = upload_objects(c))) return rc;
+  const bool ntrig = c->earth.calc == 2 && normal_trig_enabled(); // off: a record of an earlier frame stays as it is
+  if ((rc = refresh_steps(c, p)) || (trig && (rc = refresh_trig(c))) || (ntrig && (rc = refresh_normal_trig(c, p))) || (rc = refresh_atm(c, p)) || (rc = refresh_escape(c, p)) || (rc = upload_objects(c))) return rc;
   const Steps& steps = c->steps.value();
   Frame f{};
   f.p = p;
@@ -860,6 +879,7 @@ static int prepare_frame(atmrt_ctx* c, Frame* out) {
   f.xs = c->d_xs.as<double>();
   f.xs_sin = trig ? c->d_xs_trig.as<double>() : nullptr;
   f.xs_cos = trig ? c->d_xs_trig.as<double>() + steps.march_steps + 1 : nullptr;
+  f.normal_trig = ntrig ? c->d_normal_trig.as<NormalTrig>() : nullptr;
   f.objects = c->objects.empty() ? nullptr : c->d_objects.as<ObjectDev>();
   f.textures = c->d_textures.as<uint8_t>();
   f.n_objects = (int32_t)c->objects.size();
@@ -2784,6 +2804,22 @@ extern "C" int atmrt_debug_step_trig(atmrt_ctx* c, size_t cap, double* xs, doubl
   HIP_TRY(c, hipMemcpyAsync(xs, f.xs, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(sin_out, f.xs_sin, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(cos_out, f.xs_cos, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_normal_trig(atmrt_ctx* c, size_t cap, double* out, size_t* n_out) {
+  if (!c || !n_out || (cap && !out)) return ATMRT_ERR_INVALID_ARGUMENT;
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_normal_trig(k_, cap, out, n_out));
+  Frame f;
+  int rc = harness_frame(c, &f);
+  if (rc) return rc;
+  static_assert(sizeof(NormalTrig) == 17 * sizeof(double), "the record is 17 doubles, in the order include/atmrt.h documents");
+  *n_out = f.normal_trig ? sizeof(NormalTrig) / sizeof(double) : 0;
+  const size_t n = *n_out < cap ? *n_out : cap;
+  if (!n) return ATMRT_OK;
+  HIP_TRY(c, hipMemcpyAsync(out, f.normal_trig, n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
   return ATMRT_OK;

@@ -995,6 +995,14 @@ struct DirCalc {
   double p[10];
 };
 
+// SphericalCalc::new from spherical_directions(lat, lon) and the sine and cosine of the azimuth on, directional_calc.rs:62-68: what
+// dircalc_new runs, and what a caller runs that already holds the start point's three vectors or the azimuth's sine and cosine
+// (find_normal, rect_hit).  The products stay as written: dirn * 1.0 + dire * 0.0 is not dirn where a component is -0.0.
+ATMRT_HD void spherical_calc_from(const Vec3& dirn, const Vec3& dire, const Vec3& up, double sindir, double cosdir, DirCalc& c) {
+  c.pos = up;
+  c.dir = dirn * cosdir + dire * sindir;
+}
+
 // EarthModel::coords_at_dist_calc, mod.rs:114-145 and the ::new of each calculator
 ATMRT_HD void dircalc_new(const Earth& e, double lat, double lon, double dir, DirCalc& c) {
   for (int i = 0; i < 10; i++) c.p[i] = 0.0;
@@ -1004,8 +1012,7 @@ ATMRT_HD void dircalc_new(const Earth& e, double lat, double lon, double dir, Di
     spherical_directions(lat, lon, dirn, dire, pos);
     double sindir, cosdir;
     dm_sincos(dm_to_radians(dir), &sindir, &cosdir);
-    c.pos = pos;
-    c.dir = dirn * cosdir + dire * sindir;
+    spherical_calc_from(dirn, dire, pos, sindir, cosdir, c);
   } else if (e.calc == 0) { // AzEqCalc, mod.rs:116-125
     Vec3 vn, ve, vu;
     c.pos = as_cartesian(e, lat, lon, 0.0);
@@ -1174,10 +1181,30 @@ ATMRT_HD double terrain_elev_or_zero(const TerrainView& tv, double lat, double l
   return terrain_get_elev(tv, lat, lon, e) ? e : 0.0; // .unwrap_or(0.0), utils.rs:28-31,84
 }
 
+// What find_normal and the trace-point epilogue compute again in every lane although it is the same for every pixel of every frame:
+// the Spherical calculator's frame constants (earth.calc == 2).  k_normal_trig fills the record with the device functions named here,
+// so an entry is the bit pattern a lane computes; the kernels read it through Frame::normal_trig.
+struct NormalTrig {
+  double sin_p, cos_p;       // spherical_sincos(e, +NORMAL_DIFF): the angle of find_normal's step to the north / east neighbour
+  double sin_m, cos_m;       // spherical_sincos(e, -NORMAL_DIFF): to the south / west one (computed, not negated)
+  double sin_az0, cos_az0;   // dm_sincos(dm_to_radians(0.0)): the azimuth of find_normal's first calculator
+  double sin_az90, cos_az90; // dm_sincos(dm_to_radians(90.0)): of its second (the cosine is 6.1e-17, not 0)
+  Vec3 obs_n, obs_e, obs_up; // spherical_directions(observer's latitude, longitude): the start of every ray of the frame
+};
+constexpr double NORMAL_DIFF = 15.0; // find_normal's DIFF, utils.rs:16
+
+ATMRT_HD void normal_trig_fill(const Earth& e, double obs_lat, double obs_lon, NormalTrig& t) {
+  spherical_sincos(e, NORMAL_DIFF, t.sin_p, t.cos_p);
+  spherical_sincos(e, -NORMAL_DIFF, t.sin_m, t.cos_m);
+  dm_sincos(dm_to_radians(0.0), &t.sin_az0, &t.cos_az0);
+  dm_sincos(dm_to_radians(90.0), &t.sin_az90, &t.cos_az90);
+  spherical_directions(obs_lat, obs_lon, t.obs_n, t.obs_e, t.obs_up);
+}
+
 // find_normal, utils.rs:15-40.  The two calculators (azimuth 0 and 90) are handled by one rolled
 // loop so the geodesic code is instantiated once, not four times (register pressure on the GPU).
 ATMRT_HD Vec3 find_normal(const Earth& e, const TerrainView& tv, double lat, double lon) {
-  const double DIFF = 15.0;
+  const double DIFF = NORMAL_DIFF;
   double diff_ns = 0.0, diff_ew = 0.0;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
@@ -1199,6 +1226,41 @@ ATMRT_HD Vec3 find_normal(const Earth& e, const TerrainView& tv, double lat, dou
   Vec3 normal = cross(vec_ew, vec_ns);
   double len = dm_sqrt(normal.x * normal.x + normal.y * normal.y + normal.z * normal.z);
   return normal / len;
+}
+// The same for the Spherical calculator (e.calc == 2) with the record of the frame's constants: the start point's three vectors
+// are computed once instead of three times (each dircalc_new and world_directions ran spherical_directions(lat, lon)), and the
+// sines and cosines of the two azimuths and of +-DIFF / radius are the record's.  Pure functions of arguments that repeat, evaluated
+// once: the same bits (-ffp-contract=off, no fast math).  Nothing is simplified: dirn * 1.0 + dire * 0.0 stays as written.
+ATMRT_HD Vec3 find_normal_sc(const Earth& e, const TerrainView& tv, double lat, double lon, const NormalTrig& nt) {
+  const double DIFF = NORMAL_DIFF;
+  double diff_ns = 0.0, diff_ew = 0.0;
+  Vec3 dirn, dire, up;
+  spherical_directions(lat, lon, dirn, dire, up);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int k = 0; k < 2; k++) {
+    DirCalc c;
+    spherical_calc_from(dirn, dire, up, k == 0 ? nt.sin_az0 : nt.sin_az90, k == 0 ? nt.cos_az0 : nt.cos_az90, c);
+    double plat, plon, mlat, mlon;
+    coords_at_dist_sc(e, c, nt.sin_p, nt.cos_p, plat, plon); // p_north / p_east
+    coords_at_dist_sc(e, c, nt.sin_m, nt.cos_m, mlat, mlon); // p_south / p_west
+    double d = terrain_elev_or_zero(tv, plat, plon) - terrain_elev_or_zero(tv, mlat, mlon);
+    if (k == 0) diff_ns = d;
+    else diff_ew = d;
+  }
+  Vec3 dn, de, du;
+  if (e.flat_dirs & EARTH_FLAT_DIRS) world_directions(e, lat, lon, dn, de, du);
+  else dn = dirn, de = dire, du = up; // world_directions is spherical_directions(lat, lon) there
+  Vec3 vec_ns = dn * (2.0 * DIFF) + du * diff_ns;
+  Vec3 vec_ew = de * (2.0 * DIFF) + du * diff_ew;
+  Vec3 normal = cross(vec_ew, vec_ns);
+  double len = dm_sqrt(normal.x * normal.x + normal.y * normal.y + normal.z * normal.z);
+  return normal / len;
+}
+// find_normal with the record where there is one and it applies (null, or another calculator: the code as the reference has it)
+ATMRT_HD Vec3 find_normal(const Earth& e, const TerrainView& tv, double lat, double lon, const NormalTrig* nt) {
+  return e.calc == 2 && nt ? find_normal_sc(e, tv, lat, lon, *nt) : find_normal(e, tv, lat, lon);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -104,6 +104,7 @@ struct AtmDef {
 // A key is the tuple of a product's inputs in the order of its comment: doubles as their bits(), a source product as its serial().
 using StepsKey = std::tuple<uint64_t, uint64_t>;                                    // simulation_step, max_distance
 using TrigKey = std::tuple<uint64_t, uint64_t, int32_t>;                            // steps, calc_radius, EARTH_FAST_DIV
+using NormalTrigKey = std::tuple<uint64_t, int32_t, uint64_t, uint64_t>;                // calc_radius, EARTH_FAST_DIV, observer's latitude, longitude
 using AtmKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, int32_t>;         // atm_def_serial, wavelength, step, shape_radius, spherical
 using EscapeKey = std::tuple<uint64_t, uint64_t>;                                   // atm, the mosaic's top
 using BinsKey = std::tuple<uint64_t, uint64_t, uint64_t, int32_t, int32_t, int32_t, int32_t>; // direction, fov, tilt, width, height, column shard
@@ -199,6 +200,8 @@ struct atmrt_ctx {
   atmrt::Cached<atmrt::StepsKey, atmrt::Steps> steps;
   atmrt::DevBuf d_xs_trig;                 // Spherical calculator: sin, then cos, of xs[0 .. march_steps] / calc_radius (k_step_trig)
   atmrt::Cached<atmrt::TrigKey> trig;
+  atmrt::DevBuf d_normal_trig;             // Spherical calculator: the record of the trace-point epilogue's frame constants (NormalTrig, k_normal_trig)
+  atmrt::Cached<atmrt::NormalTrigKey> normal_trig;
   atmrt::DevBuf d_ceil;                    // Spherical calculator, Rectilinear: the terrain ceiling table (atmrt_ceiling.h), (march_steps + 1) x (bins + 1) entries
   atmrt::Cached<atmrt::CeilKey> ceiling;
   atmrt::DevBuf d_ceil_order;              // beside it: the work queue of the whole-frame march (Frame::ceil_order) and its sort's scratch (march_order_layout)

@@ -25,6 +25,19 @@ static __device__ __forceinline__ void coords_at_step(const Frame& f, const Eart
   else coords_at_dist(e, c, dist, lat, lon);
 }
 
+// The frame's record of the epilogue's constants (Frame::normal_trig) copied into `t`, read through the constant address space: the
+// loads are scalar and the values live in SGPRs.  False (wave-uniform): no record, every lane computes what it would hold.
+static __device__ __forceinline__ bool normal_trig_of(const Frame& f, const Earth& e, NormalTrig& t) {
+  typedef const __attribute__((address_space(4))) double* ConstF64;
+  if (e.calc != 2 || !f.normal_trig) return false;
+  static_assert(sizeof(NormalTrig) == 17 * sizeof(double), "seventeen doubles, in the order of the struct");
+  const ConstF64 p = (ConstF64)(uintptr_t)f.normal_trig;
+  t.sin_p = p[0], t.cos_p = p[1], t.sin_m = p[2], t.cos_m = p[3];
+  t.sin_az0 = p[4], t.cos_az0 = p[5], t.sin_az90 = p[6], t.cos_az90 = p[7];
+  t.obs_n = v3(p[8], p[9], p[10]), t.obs_e = v3(p[11], p[12], p[13]), t.obs_up = v3(p[14], p[15], p[16]);
+  return true;
+}
+
 // TracePoint (generators/mod.rs:21-30) of a terrain hit
 struct TracePointDev {
   double lat, lon, distance, elevation, path_length;
@@ -39,9 +52,12 @@ static __device__ TracePointDev terrain_trace_point(const Frame& f, const Earth&
   double diff2 = re1 - te1;
   double prop = diff1 / (diff1 - diff2);
   Vec3 n0 = v3(0.0, 0.0, 0.0), n1 = n0;
+  NormalTrig nt;
+  const bool tabled = normal_trig_of(f, e, nt);
 #pragma unroll 1
   for (int k = 0; k < 2; k++) { // one instantiation of find_normal for both bracketing samples
-    Vec3 n = find_normal(e, f.tv, k == 0 ? lat0 : lat1, k == 0 ? lon0 : lon1);
+    const double lat = k == 0 ? lat0 : lat1, lon = k == 0 ? lon0 : lon1;
+    Vec3 n = tabled ? find_normal_sc(e, f.tv, lat, lon, nt) : find_normal(e, f.tv, lat, lon);
     if (k == 0) n0 = n;
     else n1 = n;
   }

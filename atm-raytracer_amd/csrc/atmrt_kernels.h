@@ -61,6 +61,11 @@ struct Frame {
   // scheduling only.  Null: no table, or a frame that does not take the queue (march_queue_wanted); the march is the plain grid.
   const uint32_t* ceil_order;
   const uint32_t* ceil_order_steps; // beside it: the estimated steps of every entry of ceil_order (descending): sizes the chunks claimed from its tail
+  // Spherical calculator: the record of what the trace-point epilogue would compute again in every lane (NormalTrig, atmrt_core.h;
+  // k_normal_trig): sin / cos of find_normal's two azimuths and of +-15 m / calc_radius, and the three vectors of the observer's
+  // position.  Null for the other calculators and under ATMRT_NORMAL_TRIG=off: every lane then computes them, as the reference does.
+  // The struct's last field: every other one keeps its place in the kernels' arguments.
+  const NormalTrig* normal_trig;
 };
 
 // column azimuth / row elevation in degrees, as handed to gen_terrain_cache / gen_path_cache
@@ -620,6 +625,7 @@ void launch_ray_paths(const Frame& f, double h0, size_t n_angles, const double* 
 void launch_atm_sample(const Frame& f, size_t n, const double* alt, double* t, double* p, double* nidx, double* dn,
                        hipStream_t stream);
 void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, double* c, hipStream_t stream);
+void launch_normal_trig(const Earth& e, double obs_lat, double obs_lon, NormalTrig* out, hipStream_t stream);
 // fills f.ceil (rows 0 .. f.march_steps) for f.ceil_layout: the cells, then every bin's suffix maxima
 void launch_ceiling(const Frame& f, CeilEntry* table, hipStream_t stream);
 // Frame::ceil_order from the table (f.ceil set): estimate, histogram, scan, scatter

@@ -264,8 +264,8 @@ static __device__ __forceinline__ TracePointDev fast_hit(const Frame& f, const E
                                          const double* plen, int x, int y, int s) {
   double lat0, lon0, lat1, lon1;
   double d0 = f.xs[s], d1 = f.xs[s + 1];
-  coords_at_dist(e, c, d0, lat0, lon0);
-  coords_at_dist(e, c, d1, lat1, lon1);
+  coords_at_step(f, e, c, s, d0, lat0, lon0); // the stepper's distances: s + 1 < n_t <= march_steps + 1
+  coords_at_step(f, e, c, s + 1, d1, lat1, lon1);
   double te0 = prof[(size_t)s * f.wl + x], te1 = prof[(size_t)(s + 1) * f.wl + x];
   size_t base = (size_t)y * f.n_path_cap;
   double re0 = pelev[base + s], re1 = pelev[base + s + 1];
@@ -1452,6 +1452,17 @@ __global__ void k_step_trig(Earth e, size_t n, const double* __restrict__ xs, do
 }
 void launch_step_trig(const Earth& e, size_t n, const double* xs, double* s, double* c, hipStream_t stream) {
   if (n) hipLaunchKernelGGL(k_step_trig, dim3(cdiv(n, 256)), dim3(256), 0, stream, e, n, xs, s, c);
+}
+
+// Frame::normal_trig: the device code of find_normal and of the observer's calculator on their frame constants, once instead of once
+// per trace point.  One wavefront; its first lane writes.
+__global__ __launch_bounds__(64) void k_normal_trig(Earth e, double obs_lat, double obs_lon, NormalTrig* __restrict__ out) {
+  NormalTrig t;
+  normal_trig_fill(e, obs_lat, obs_lon, t);
+  if (threadIdx.x == 0) *out = t;
+}
+void launch_normal_trig(const Earth& e, double obs_lat, double obs_lon, NormalTrig* out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_normal_trig, dim3(1), dim3(64), 0, stream, e, obs_lat, obs_lon, out);
 }
 
 // Frame::ceil, the terrain ceiling table (atmrt_ceiling.h).  One thread per step i and bin j: the geodesic points of the bin's two

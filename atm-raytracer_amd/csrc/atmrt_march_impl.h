@@ -950,7 +950,15 @@ static __device__ __forceinline__ TracePointDev rect_hit(const Frame& f, int x, 
   double direction, elevation;
   rect_ray_params(f.p, f.ph, f.c0 + x, y, direction, elevation);
   DirCalc c;
-  dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
+  NormalTrig nt;
+  if (normal_trig_of(f, e, nt)) { // the observer's three vectors are the frame's: only the ray's azimuth is the lane's
+    double sindir, cosdir;
+    dm_sincos(dm_to_radians(dm_to_degrees(direction)), &sindir, &cosdir);
+    for (int i = 0; i < 10; i++) c.p[i] = 0.0;
+    spherical_calc_from(nt.obs_n, nt.obs_e, nt.obs_up, sindir, cosdir, c);
+  } else {
+    dircalc_new(e, f.p.position.latitude, f.p.position.longitude, dm_to_degrees(direction), c);
+  }
   double d0 = f.xs[s], d1 = f.xs[s + 1]; // the stepper's x: 0 + step + ... (same additions as xs)
   double lat0, lon0, lat1, lon1;
   coords_at_step(f, e, c, s, d0, lat0, lon0);

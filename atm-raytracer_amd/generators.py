@@ -137,6 +137,18 @@ class Context:
             assert n.value == order.size
         return order
 
+    def debug_normal_trig(self):
+        """Diagnostic (atmrt_debug_normal_trig): the record of the trace-point epilogue's frame constants for the parameters now
+        set, float64 [17]: sin, cos of +15 m / radius, of -15 m / radius, of 0 and of 90 degrees, then the observer's north, east
+        and up vectors; empty when there is none (another calculator than the Spherical one, ATMRT_NORMAL_TRIG=off)."""
+        n = C.c_size_t()
+        self.check(self.lib.atmrt_debug_normal_trig(self.handle, 0, None, C.byref(n)))
+        out = np.zeros(n.value)
+        if n.value:
+            self.check(self.lib.atmrt_debug_normal_trig(self.handle, n.value, out.ctypes.data, C.byref(n)))
+            assert n.value == out.size
+        return out
+
     def fail_next_collective(self, index=0, nth=1):
         """Test hook (atmrt_debug_fail_next_collective)."""
         self.check(self.lib.atmrt_debug_fail_next_collective(self.handle, index, nth))

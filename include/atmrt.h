@@ -274,6 +274,7 @@ typedef struct atmrt_timings {
 /* Environment switches read at every frame (A/B runs; results are the same bits either way):
  *   ATMRT_ESCAPE=off        no ray leaves the Rectilinear march early
  *   ATMRT_STEP_TRIG=off     no per-step sin / cos table of the Spherical geodesic
+ *   ATMRT_NORMAL_TRIG=off   no record of the trace-point epilogue's frame constants: every trace point computes them
  *   ATMRT_CEILING=off       no terrain ceiling table: the march tests every sample against the mosaic's highest post
  *   ATMRT_CEILING=rebuild   the terrain ceiling table is built again in every frame (it is cached otherwise) */
 int atmrt_last_timings(atmrt_ctx* ctx, atmrt_timings_t* out);
@@ -952,6 +953,12 @@ int atmrt_math_probe3(atmrt_ctx* ctx, int32_t op, size_t n, const double* a, con
  * and the first min(cap, *n) of xs[k], sin(xs[k] / radius), cos(xs[k] / radius).  tests/test_gpu_step_trig.py compares them with
  * atmrt_math_probe's division and SINCOS: an entry must be the bit pattern a lane computes for that distance. */
 int atmrt_debug_step_trig(atmrt_ctx* ctx, size_t cap, double* xs, double* sin_out, double* cos_out, size_t* n);
+/* A diagnostic like atmrt_debug_step_trig, NOT part of the stable surface: the record the trace-point epilogue of the Spherical
+ * calculator reads its frame constants from, for the parameters now set.  *n = its doubles (17; 0: no
+ * record — another calculator, or ATMRT_NORMAL_TRIG=off), and the first min(cap, *n) of them: sin, cos of +15 m / radius; sin, cos
+ * of -15 m / radius; sin, cos of 0 degrees; sin, cos of 90 degrees; then the north, east and up vectors (x, y, z each) of the
+ * observer's latitude and longitude.  tests/test_gpu_normal_trig.py compares them with atmrt_math_probe's division and SINCOS. */
+int atmrt_debug_normal_trig(atmrt_ctx* ctx, size_t cap, double* out, size_t* n);
 /* A diagnostic like atmrt_debug_step_trig, NOT part of the stable surface: the terrain ceiling table that
  * the context's LAST GENERATED FRAME marched with, as the device holds it.  *rows = its rows (the march's steps + 1) and *n_bins
  * its bins; layout = {dir0, rel_lo, w} of the bins in radians; cell and suffix receive the first min(cap, *rows x (*n_bins + 1))
