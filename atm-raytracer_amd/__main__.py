@@ -9,6 +9,7 @@
                                     [--viewshed-map OUT.npz [--map-cell ARCSEC] [--viewshed-observers FILE.csv]]
                                     [--horizon OUT.csv [--horizon-az LO HI N] [--horizon-reach M] [--horizon-fan LO HI K]
                                      [--horizon-rounds N]]
+                                    [--shadows [--shadow-reach M] [--shadow-lift M] [--shadow-light AZ EL]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -51,6 +52,11 @@ the frame unless said otherwise) and the terrain within --horizon-reach (max_dis
 terrain ends and sky begins, bracketed between the highest blocked ray and the ray above it — first fan --horizon-fan (-5 5 64),
 narrowed --horizon-rounds times (3) — and the ridge that forms it.  OUT.csv has one row per azimuth: azimuth_deg, status (found,
 above_fan, below_fan), angle_clear_deg, angle_blocked_deg, resolution_deg, ridge_distance_m, ridge_lat, ridge_lon, ridge_elevation_m.
+`--shadows` (no reference counterpart) casts shadows into the image: from the first trace point of every pixel a ray is marched toward
+the light through the same atmosphere, --shadow-reach metres far (max_distance, at most 65535 steps) from --shadow-lift metres above
+the point (0), and a point whose ray meets terrain is drawn at the Shading method's ambient light.  The light is the Shading
+configuration's (azimuth = frame direction + 180 - light_dir, elevation = 90 - light_zenith_angle) unless --shadow-light AZ EL names
+the azimuth toward it and its elevation in degrees; both are taken as the same at every point of the frame.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -249,6 +255,24 @@ def draw_landmarks(img, names, hits):
             draw.text((x + 3, y - 16), name, fill=(255, 255, 255), font=font, anchor="ls")
 
 
+def shadow_spec_of(cfg, reach, lift, light):
+    """The atmrt_shadow_spec_t of gen --shadows: --shadow-light AZ EL or the Shading configuration's light, --shadow-reach or
+    max_distance capped at 65535 steps, --shadow-lift."""
+    if light is not None:
+        az, el = float(light[0]), float(light[1])
+    elif cfg.coloring["kind"] == 1:
+        az, el = generators.light_from_coloring(cfg.params, cfg.coloring["light_zenith_angle"], cfg.coloring["light_dir"])
+    else:
+        raise config.ConfigError("--shadows needs a light: the Shading colouring method's, or --shadow-light AZ EL")
+    if not -90.0 < el < 90.0:
+        raise config.ConfigError(f"--shadows: the light's elevation {el!r} must lie strictly between -90 and 90 degrees")
+    step = cfg.params.simulation_step
+    reach = min(float(reach) if reach is not None else cfg.params.frame.max_distance, 65535 * step)
+    if not reach > 0.0 or lift < 0.0:
+        raise config.ConfigError("--shadow-reach must be positive and --shadow-lift not negative")
+    return generators.shadow_spec(az, el, reach, lift)
+
+
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
@@ -266,7 +290,16 @@ def cmd_gen(a):
     from PIL import Image
     w, h = res["width"], res["height"]
     rgb_dev = torch.empty((h, w, 3), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
-    ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
+    if a.shadows:  # the second march, then the image through the status plane: both stay on the device
+        stamp("Casting shadows...")
+        spec = shadow_spec_of(cfg, a.shadow_reach, a.shadow_lift, a.shadow_light)
+        status_dev = torch.empty((h, w), dtype=torch.uint8, device=rgb_dev.device)
+        st = _abi.ShadowStats()
+        ctx.check(ctx.lib.atmrt_shadow_mask_device(ctx.handle, C.byref(spec), status_dev.data_ptr(), None, C.byref(st)))
+        print(f"Light at azimuth {spec.azimuth_deg!r}, elevation {spec.elevation_deg!r}: {st.lit} points lit, {st.shadowed} in shadow")
+        ctx.check(ctx.lib.atmrt_draw_image_shadowed_device(ctx.handle, C.byref(col), status_dev.data_ptr(), rgb_dev.data_ptr()))
+    else:
+        ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
     ticks, _ = generators.draw_overlay_device(ctx, generators.into_overlay(cfg.output), rgb_dev.data_ptr(), w, h)
     if a.visibility_map:  # on the device, while the frame is still in HBM
         stamp("Binning the visibility map...")
@@ -386,6 +419,10 @@ def main(argv=None):
     g.add_argument("--viewshed-fan", type=float, nargs=3, default=(-5.0, 5.0, 64), metavar=("LO", "HI", "K"))
     g.add_argument("--viewshed-map", default=None, metavar="OUT.npz")
     g.add_argument("--viewshed-observers", default=None, metavar="FILE.csv")
+    g.add_argument("--shadows", action="store_true")
+    g.add_argument("--shadow-reach", type=float, default=None, metavar="M")
+    g.add_argument("--shadow-lift", type=float, default=0.0, metavar="M")
+    g.add_argument("--shadow-light", type=float, nargs=2, default=None, metavar=("AZ", "EL"))
     g.add_argument("--horizon", default=None, metavar="OUT.csv")
     g.add_argument("--horizon-az", type=float, nargs=3, default=None, metavar=("LO", "HI", "N"))
     g.add_argument("--horizon-reach", type=float, default=None, metavar="M")

@@ -214,6 +214,20 @@ class HorizonSpec(C.Structure):
         [("n_az", C.c_int32), ("fan_rays", C.c_int32), ("rounds", C.c_int32)]
 
 
+# atmrt_shadow_status
+SHADOW_NONE, SHADOW_LIT, SHADOW_SHADOWED = 0, 1, 2
+
+
+class ShadowSpec(C.Structure):
+    """atmrt_shadow_spec_t: the direction toward the light and the shadow ray's launch elevation [deg], the reach and the lift [m]."""
+    _fields_ = [(k, C.c_double) for k in ("azimuth_deg", "elevation_deg", "reach", "lift")]
+
+
+class ShadowStats(C.Structure):
+    """atmrt_shadow_stats_t: none + lit + shadowed = the pixels; the stepper steps taken and the rays that escaped, of one call."""
+    _fields_ = [(k, C.c_uint64) for k in ("none", "lit", "shadowed", "integrated_steps", "escaped_rays")]
+
+
 class Horizon(C.Structure):
     _fields_ = [("status", C.c_int32), ("rounds_done", C.c_int32), ("k_star", C.c_int32), ("block_index", C.c_int32)] + \
         [(k, C.c_double) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon", "block_elevation")]

@@ -26,6 +26,7 @@
 #include "atmrt_viewshed.h"
 #include "atmrt_viewshed_map.h"
 #include "atmrt_horizon.h"
+#include "atmrt_shadow.h"
 #include "atmrt_tiff.h"
 
 using namespace atmrt;
@@ -158,6 +159,9 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 31: return sizeof(atmrt_horizon_t);
     // 32 stays 0
     case 33: return sizeof(atmrt_viewshed_map_stats_t);
+    // 34 stays 0
+    case 35: return sizeof(atmrt_shadow_spec_t);
+    case 36: return sizeof(atmrt_shadow_stats_t);
     default: return 0;
   }
 }
@@ -2678,6 +2682,191 @@ extern "C" int atmrt_last_horizon_work(atmrt_ctx* c, int32_t* batches, int32_t* 
   if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
   *batches = c->horizon_batches;
   *table_rebuilt = c->horizon_rebuilt;
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// cast shadows: which of a frame's first trace points the light reaches (kernels: atmrt_shadow.h; the rule: include/atmrt.h)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// ATMRT_SHADOW_ESCAPE=off: every ray marches to m or to its block (A/B runs, tests/test_gpu_shadows.py).  Read at every call.
+bool shadow_escape_enabled() {
+  const char* e = getenv("ATMRT_SHADOW_ESCAPE");
+  return !(e && !strcmp(e, "off"));
+}
+
+// m: the first index with d_m >= reach, d by repeated addition (utils.rs:191-196); 0 or a message
+const char* shadow_steps_of(const atmrt_ctx* c, double reach, int32_t* m) {
+  const double step = c->params.simulation_step;
+  if (!(step > 0.0)) return "simulation_step must be positive";
+  if (!(std::isfinite(reach) && reach > 0.0)) return "reach must be finite and positive";
+  int32_t i = 0;
+  for (double d = 0.0; d < reach;) {
+    d += step;
+    if (++i > SHADOW_M_MAX) return "reach lies more than 65535 samples away";
+  }
+  *m = i;
+  return nullptr;
+}
+
+const char* shadow_spec_check(const atmrt_shadow_spec_t& s) {
+  if (!std::isfinite(s.azimuth_deg)) return "azimuth_deg is not finite";
+  if (!(std::isfinite(s.elevation_deg) && s.elevation_deg > -90.0 && s.elevation_deg < 90.0)) return "elevation_deg must lie strictly between -90 and 90";
+  if (!(std::isfinite(s.reach) && s.reach > 0.0)) return "reach must be finite and positive";
+  if (!(std::isfinite(s.lift) && s.lift >= 0.0)) return "lift must be finite and not negative";
+  return nullptr;
+}
+
+// what every shadow entry point asks of its arguments and of the context's parameters; 0 or a status with the message set
+int shadow_check(atmrt_ctx* c, const char* what, const atmrt_shadow_spec_t* spec, const void* status, int32_t* m) {
+  if (!spec || !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or status is NULL", what);
+  if (const char* msg = shadow_spec_check(*spec)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
+  if (const char* msg = shadow_steps_of(c, spec->reach, m)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  return ATMRT_OK;
+}
+
+// The floor of the escape shortcut for THIS call, from the context's cached certificate and the mosaic's top (Frame::esc_floor is a
+// Rectilinear frame's only; the shadowed frame may be a Fast one).  The certificate is stated "to max_distance", but nothing in its
+// argument depends on a distance: above `from`, r'' > 0 whatever r' is, so a ray with dr/dphi > 0 there ascends for as long as it
+// is integrated — the bound holds for any reach.  What does depend on the distance is the straight spherical ray's convexity
+// (esc_ang_max): it is evaluated for this call's reach, one step past it (d_m < reach + step).  No certificate (flat earth,
+// refracted; an atmosphere the sweep refuses): +inf, every ray marches to m.
+double shadow_escape_floor(const atmrt_ctx* k, Frame& f, double reach) {
+  f.esc_floor = INFINITY; // the frame's own floor is not this call's
+  f.esc_ang_max = INFINITY;
+  if (!shadow_escape_enabled()) return INFINITY;
+  const double step = f.p.simulation_step;
+  if (f.p.straight_rays) {
+    if (k->earth.spherical) f.esc_ang_max = 1.5207963267948966 - (reach + step) * f.inv_shape_radius;
+    return k->tv.skip_above;
+  }
+  if (!k->earth.spherical) return INFINITY;
+  return std::max(k->tv.skip_above, k->escape.value().from + step);
+}
+
+// k: the context whose device holds the memory and whose setting is used; report: the context the caller handed in.  host_status /
+// host_block: where the planes are downloaded to inside the call's timed window (null: none).
+int shadow_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_spec_t& spec, int32_t m, const TracePoints& src, uint8_t* status_dev,
+               uint16_t* block_dev, atmrt_shadow_stats_t* stats, uint8_t* host_status, uint16_t* host_block) {
+  Frame f;
+  if (int rc = prepare_frame(k, &f)) {
+    if (k != report) report->error = k->error;
+    return rc;
+  }
+  hipStream_t s = k->stream;
+  ShadowJob job{};
+  job.src = src;
+  job.azimuth_deg = spec.azimuth_deg, job.elevation_deg = spec.elevation_deg, job.lift = spec.lift;
+  job.m = m;
+  job.esc_floor = shadow_escape_floor(k, f, spec.reach);
+  job.escape = job.esc_floor < INFINITY ? 1 : 0;
+  job.status = status_dev, job.block = block_dev;
+  HIP_TRY(report, reserve_carved(k->d_shadow, [&](Carve& cv) { cv(job.list, src.n_pixels * sizeof(uint32_t)), cv(job.ctr, SH_N * sizeof(unsigned long long)); }));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_BEGIN], s));
+  launch_shadow_mask(f, job, s, k->ev[EV_SH_COMPACTED]);
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_MARCHED], s));
+  unsigned long long ctr[SH_N] = {};
+  HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+  if (host_status) HIP_TRY(report, hipMemcpyAsync(host_status, status_dev, src.n_pixels, hipMemcpyDeviceToHost, s));
+  if (host_block) HIP_TRY(report, hipMemcpyAsync(host_block, block_dev, src.n_pixels * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_END], s));
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
+  for (int i = 0; i < 3; i++) {
+    float ms = 0.0f;
+    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[EV_SH_BEGIN + i], k->ev[EV_SH_BEGIN + i + 1]));
+    report->shadow_timings[i] = ms;
+  }
+  if (stats) {
+    stats->lit = ctr[SH_LIT], stats->shadowed = ctr[SH_SHADOWED];
+    stats->none = src.n_pixels - ctr[SH_LIST];
+    stats->integrated_steps = ctr[SH_STEPS], stats->escaped_rays = ctr[SH_ESCAPED];
+  }
+  return ATMRT_OK;
+}
+
+const char* const SHADOW_ON_MULTI = "has no frame of its own: cast shadows work on the gathered planes through atmrt_shadow_mask_planes_device";
+
+} // namespace
+
+extern "C" int atmrt_shadow_steps(atmrt_ctx* c, double reach, int32_t* m) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!m) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: m is NULL");
+  if (!(std::isfinite(reach) && reach > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: reach must be finite and positive");
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_shadow_steps: atmrt_set_params has not been called");
+  if (const char* msg = shadow_steps_of(c, reach, m)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: %s", msg);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_shadow_mask_device(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, uint8_t* status_device, uint16_t* block_device,
+                                        atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  int32_t m = 0;
+  if (int rc = shadow_check(c, "atmrt_shadow_mask", spec, status_device, &m)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_shadow_mask", SHADOW_ON_MULTI)) return rc;
+  return shadow_run(c, c, *spec, m, last_frame_points(c, ATMRT_VIS_ALL), status_device, block_device, stats, nullptr, nullptr);
+}
+
+extern "C" int atmrt_shadow_mask(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, uint8_t* status, uint16_t* block, atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  int32_t m = 0;
+  if (int rc = shadow_check(c, "atmrt_shadow_mask", spec, status, &m)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_shadow_mask", SHADOW_ON_MULTI)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n = c->last_npx, block_bytes = Carve::pad(n * sizeof(uint16_t));
+  HIP_TRY(c, c->d_io.reserve(block_bytes + n));
+  uint16_t* d_block = block ? c->d_io.as<uint16_t>() : nullptr;
+  uint8_t* d_status = c->d_io.as<uint8_t>() + block_bytes;
+  return shadow_run(c, c, *spec, m, last_frame_points(c, ATMRT_VIS_ALL), d_status, d_block, stats, status, block);
+}
+
+extern "C" int atmrt_shadow_mask_planes_device(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
+                                               const double* lat, const double* lon, const double* elev, uint8_t* status_device,
+                                               uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!hit_count || !lat || !lon || !elev) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_mask_planes_device: a plane is NULL");
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_mask_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  int32_t m = 0;
+  if (int rc = shadow_check(c, "atmrt_shadow_mask_planes_device", spec, status_device, &m)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, status_device, "status_device", &k)) return rc;
+  HIP_TRY(c, hipSetDevice(k->device));
+  return shadow_run(k, c, *spec, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, status_device, block_device, stats, nullptr,
+                    nullptr);
+}
+
+extern "C" int atmrt_draw_image_shadowed_device(atmrt_ctx* c, const atmrt_coloring_t* coloring, const uint8_t* status_device, uint8_t* rgb_device) {
+  if (!c || !coloring || !status_device || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = frame_state_check(c, "atmrt_draw_image_shadowed", "draws its shadowed image from the gathered planes: not part of this entry point")) return rc;
+  if (coloring->kind != ATMRT_COLORING_SIMPLE && coloring->kind != ATMRT_COLORING_SHADING)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown coloring kind %d", coloring->kind);
+  if (coloring->has_fog && !(coloring->fog_distance > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "fog_distance must be positive");
+  HIP_TRY(c, hipSetDevice(c->device));
+  launch_draw_image_shadowed(c->last_npx, *coloring, c->last_alpha, c->last_packed, c->last_dense.hit_count, c->last_offset, c->last_hits,
+                             c->last_dense, status_device, rgb_device, c->stream);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_draw_image_shadowed(atmrt_ctx* c, const atmrt_coloring_t* coloring, const uint8_t* status, uint8_t* rgb) {
+  if (!c || !coloring || !status || !rgb) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = frame_state_check(c, "atmrt_draw_image_shadowed", "draws its shadowed image from the gathered planes: not part of this entry point")) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n = c->last_npx, rgb_bytes = Carve::pad(3 * n);
+  HIP_TRY(c, c->d_io.reserve(rgb_bytes + n));
+  uint8_t* d_status = c->d_io.as<uint8_t>() + rgb_bytes;
+  HIP_TRY(c, hipMemcpy(d_status, status, n, hipMemcpyHostToDevice));
+  if (int rc = atmrt_draw_image_shadowed_device(c, coloring, d_status, c->d_io.as<uint8_t>())) return rc;
+  HIP_TRY(c, hipMemcpy(rgb, c->d_io.ptr, 3 * n, hipMemcpyDeviceToHost));
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_shadow_timings(atmrt_ctx* c, double out[3]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memcpy(out, c->shadow_timings, sizeof c->shadow_timings);
   return ATMRT_OK;
 }
 

@@ -224,6 +224,8 @@ struct atmrt_ctx {
   atmrt::DevBuf d_vsmap;                   // atmrt_viewshed_map*: the call's statistics block (40 B)
   double horizon_timings[5] = {};          // atmrt_last_horizon_timings
   int32_t horizon_batches = 0, horizon_rebuilt = 0;   // atmrt_last_horizon_work
+  atmrt::DevBuf d_shadow;                  // atmrt_shadow_mask*: the call's list of hit pixels and its counters
+  double shadow_timings[3] = {};           // atmrt_last_shadow_timings
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
   atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
   atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend

@@ -114,6 +114,15 @@ static __device__ __forceinline__ unsigned long long wave_sum(unsigned long long
   return v;
 }
 
+// The escape test, after a step's sign test (Frame::esc_floor; the certificate is atmrt_api.hip's escape_floor).  The last sample
+// is above the mosaic's top and the bands of the wavefront's objects, and the ray is ascending: refracted, dr/dphi > 0, which the
+// certificate keeps positive to max_distance; straight, the sample above the one before (h(x) is convex while the ray's angle
+// stays below esc_ang_max).  From here on every sample is above the floor: no sign change, no object step, no lookup.
+static __device__ __forceinline__ bool escapes(const Frame& f, const Stepper& s, bool straight, double sh, double re0, double floor) {
+  if (!(sh > floor)) return false;
+  return straight ? sh > re0 && s.ang < f.esc_ang_max : s.b > 0.0;
+}
+
 // Objects that can EVER be close to a sample of this ray (exact superset of Object::is_close over the whole ray).
 // Spherical model: every sample, lifted to the object's elevation, lies in the great-circle plane span(pos, dir) of the
 // ray's ground track, so |P - P_obj| >= distance of P_obj to that plane.  Azimuthal-equidistant model: the ground track

@@ -515,7 +515,7 @@ void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* tmp, uint64_t* out,
 void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_fast_paths(const Frame& f, Workspace& ws, hipStream_t stream, int i_begin, int i_end); // atmrt_paths.hip
 // The phase events of a context (atmrt_ctx::ev; `timing` below): an interval of atmrt_timings_t lies between two of them.  Between
-// frames atmrt_sight_lines and atmrt_locate_landmarks* time their own consecutive intervals with the same events, under names of their own.
+// frames atmrt_sight_lines, atmrt_locate_landmarks* and atmrt_shadow_mask* time their own consecutive intervals with the same events, under names of their own.
 enum PhaseEvent {
   EV_PROFILE_BEGIN, EV_PROFILE_END, // Fast: the terrain profile
   EV_PATHS_BEGIN, EV_PATHS_END,     // Fast: the ray paths (second stream)
@@ -529,8 +529,9 @@ enum PhaseEvent {
   EV_VS_BEGIN = 0, EV_VS_PATHS, EV_VS_BATCH, EV_VS_PROFILED, EV_VS_SCANNED, EV_VS_END,
   EV_HZ_BATCH = EV_VS_BATCH, EV_HZ_PROFILED, EV_HZ_SCANNED, EV_HZ_REFINED, EV_HZ_END, // after EV_VS_BEGIN and EV_VS_PATHS: the table is the viewshed's
   EV_LM_BEGIN = 0, EV_LM_UPLOADED, EV_LM_FIRST_PASS, EV_LM_SECOND_PASS, EV_LM_END,
+  EV_SH_BEGIN = 0, EV_SH_COMPACTED, EV_SH_MARCHED, EV_SH_END,
 };
-static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_HZ_END < EV_COUNT && EV_LM_END < EV_COUNT, "the borrowed events exist");
+static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_HZ_END < EV_COUNT && EV_LM_END < EV_COUNT && EV_SH_END < EV_COUNT, "the borrowed events exist");
 #ifndef ATMRT_FAST_SEGMENTS
 #define ATMRT_FAST_SEGMENTS 4
 #endif
@@ -558,6 +559,10 @@ void launch_rect_finalize_list(const Frame& f, Workspace& ws, uint64_t n_hits, c
 void launch_draw_image(size_t n_pixels, const atmrt_coloring_t& col, double terrain_alpha, bool packed_valid,
                        const uint32_t* hit_count, const uint64_t* hit_offset, const PackedHits& hits, const DensePlanes& dense,
                        uint8_t* rgb, hipStream_t stream);
+// the same with the cast-shadow status plane (include/atmrt.h, "cast shadows"): the first trace point of a SHADOWED pixel takes light_dot = 0
+void launch_draw_image_shadowed(size_t n_pixels, const atmrt_coloring_t& col, double terrain_alpha, bool packed_valid,
+                                const uint32_t* hit_count, const uint64_t* hit_offset, const PackedHits& hits, const DensePlanes& dense,
+                                const uint8_t* status, uint8_t* rgb, hipStream_t stream);
 
 // The annotations of renderer::output_image (kernels in atmrt_overlay.h).  find_elev for every column of the [h][w] plane `elev` and
 // the targets t0, t1 in one pass over `bands` row bands (overlay_bands; workspace of overlay_workspace_bytes): *y_of_x points at

@@ -1233,11 +1233,14 @@ void launch_interp_finish(const Frame& f, Workspace& ws, const InterpBuffers& ib
 // pixel's trace points with the colouring method and optional fog; 3 B per pixel leave the kernel instead of 88.
 // PACKED: trace points from the packed lists; otherwise from the dense first-hit planes (opaque frames).
 // ---------------------------------------------------------------------------------------------
-template <bool PACKED>
-__global__ __launch_bounds__(256) void k_draw_image(size_t n_pixels, atmrt_coloring_t col, double terrain_alpha,
-                                                    const uint32_t* __restrict__ hit_count,
-                                                    const uint64_t* __restrict__ hit_offset, PackedHits hits, DensePlanes dense,
-                                                    uint8_t* __restrict__ rgb) {
+// SHADOWED (include/atmrt.h, "cast shadows"): under Shading the first trace point of a pixel whose status is ATMRT_SHADOW_SHADOWED
+// takes light_dot = 0.0 — a zero normal gives exactly that (0 >= 0.0 keeps it, whatever the zero's sign) — so its brightness is
+// ambient_light.  One body for both kernels; the plain kernel's instantiations carry nothing of the status plane.
+template <bool PACKED, bool SHADOWED>
+static __device__ __forceinline__ void draw_pixel(size_t n_pixels, const atmrt_coloring_t& col, double terrain_alpha,
+                                                  const uint32_t* __restrict__ hit_count, const uint64_t* __restrict__ hit_offset,
+                                                  const PackedHits& hits, const DensePlanes& dense, const uint8_t* __restrict__ status,
+                                                  uint8_t* __restrict__ rgb) {
   size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_pixels) return;
   Rgb8 result{{0, 0, 0}};
@@ -1259,6 +1262,7 @@ __global__ __launch_bounds__(256) void k_draw_image(size_t n_pixels, atmrt_color
       tag = ATMRT_COLOR_TERRAIN;
       alpha = terrain_alpha;
     }
+    if (SHADOWED && q == 0 && status[p] == ATMRT_SHADOW_SHADOWED) nx = ny = nz = 0.0;
     Rgb8 c1 = col.kind == ATMRT_COLORING_SIMPLE ? simple_color(col, distance, elevation)
                                                  : shading_color(col, nx, ny, nz, elevation, tag, r, g, b);
     Rgb8 c2 = col.has_fog ? apply_fog(col.fog_distance, path_length, c1) : c1;
@@ -1270,6 +1274,20 @@ __global__ __launch_bounds__(256) void k_draw_image(size_t n_pixels, atmrt_color
   rgb[3 * p + 1] = result.c[1];
   rgb[3 * p + 2] = result.c[2];
 }
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_draw_image(size_t n_pixels, atmrt_coloring_t col, double terrain_alpha,
+                                                    const uint32_t* __restrict__ hit_count,
+                                                    const uint64_t* __restrict__ hit_offset, PackedHits hits, DensePlanes dense,
+                                                    uint8_t* __restrict__ rgb) {
+  draw_pixel<PACKED, false>(n_pixels, col, terrain_alpha, hit_count, hit_offset, hits, dense, nullptr, rgb);
+}
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_draw_image_shadowed(size_t n_pixels, atmrt_coloring_t col, double terrain_alpha,
+                                                             const uint32_t* __restrict__ hit_count,
+                                                             const uint64_t* __restrict__ hit_offset, PackedHits hits, DensePlanes dense,
+                                                             const uint8_t* __restrict__ status, uint8_t* __restrict__ rgb) {
+  draw_pixel<PACKED, true>(n_pixels, col, terrain_alpha, hit_count, hit_offset, hits, dense, status, rgb);
+}
 
 void launch_draw_image(size_t n_pixels, const atmrt_coloring_t& col, double terrain_alpha, bool packed_valid,
                        const uint32_t* hit_count, const uint64_t* hit_offset, const PackedHits& hits, const DensePlanes& dense,
@@ -1280,6 +1298,16 @@ void launch_draw_image(size_t n_pixels, const atmrt_coloring_t& col, double terr
   else
     hipLaunchKernelGGL((k_draw_image<false>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, col, terrain_alpha,
                        hit_count, hit_offset, hits, dense, rgb);
+}
+void launch_draw_image_shadowed(size_t n_pixels, const atmrt_coloring_t& col, double terrain_alpha, bool packed_valid,
+                                const uint32_t* hit_count, const uint64_t* hit_offset, const PackedHits& hits, const DensePlanes& dense,
+                                const uint8_t* status, uint8_t* rgb, hipStream_t stream) {
+  if (packed_valid)
+    hipLaunchKernelGGL((k_draw_image_shadowed<true>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, col, terrain_alpha,
+                       hit_count, hit_offset, hits, dense, status, rgb);
+  else
+    hipLaunchKernelGGL((k_draw_image_shadowed<false>), dim3(cdiv(n_pixels, 256)), dim3(256), 0, stream, n_pixels, col, terrain_alpha,
+                       hit_count, hit_offset, hits, dense, status, rgb);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -111,14 +111,7 @@ static __device__ __forceinline__ void overflow_append(const OverflowArena& ovf,
   }
 }
 
-// The escape test, after a step's sign test (Frame::esc_floor; the certificate is atmrt_api.hip's escape_floor).  The last sample
-// is above the mosaic's top and the bands of the wavefront's objects, and the ray is ascending: refracted, dr/dphi > 0, which the
-// certificate keeps positive to max_distance; straight, the sample above the one before (h(x) is convex while the ray's angle
-// stays below esc_ang_max).  From here on every sample is above the floor: no sign change, no object step, no lookup.
-static __device__ __forceinline__ bool escapes(const Frame& f, const Stepper& s, bool straight, double sh, double re0, double floor) {
-  if (!(sh > floor)) return false;
-  return straight ? sh > re0 && s.ang < f.esc_ang_max : s.b > 0.0;
-}
+// The escape test itself, escapes(), is atmrt_device.h's: the shadow march (atmrt_shadow.h) runs it too.
 // MODE 3: the floor also clears the height band [vlo, vhi] of every object in the wavefront's candidate list (a ray can only meet
 // an object of that list); + 1 m against the rounding of the samples
 static __device__ __forceinline__ double escape_floor_objects(double floor, const double* w_vhi, int n_e) {

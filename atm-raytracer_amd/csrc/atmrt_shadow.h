@@ -1,0 +1,130 @@
+// atmrt_shadow.h — cast shadows (include/atmrt.h, "cast shadows": the rule is stated there): which of a finished frame's first
+// trace points the light reaches.  The launch interface for atmrt_api.hip; the kernels themselves are compiled by atmrt_shadow.hip
+// only (ATMRT_SHADOW_KERNELS).
+//
+//   k_shadow_compact  one thread per pixel: the pixels with a trace point appended to a list, a wavefront's entries contiguous and
+//                     in lane order (wave_compact_append), so that the march's wavefronts are full — the sky half of a frame costs
+//                     no lanes; a pixel without one gets ATMRT_SHADOW_NONE (and block 0) here
+//   k_shadow_march    one list entry per lane: dircalc_new at the point, the stepper from H_0, then per step coords_at_dist,
+//                     terrain_elev_or_zero and the rule's test.  A lane that is decided idles (it is not in the stepper's votes any
+//                     more, as in sight_trace); the wavefront leaves when all its lanes are decided.  Writes status and block of
+//                     its pixel; the counts of the call with one atomic per wavefront and counter.
+//
+// The launch covers the pixels, not the list (its length stays on the device: no host round trip between the two kernels); a
+// wavefront beyond the list's end leaves at once.
+#pragma once
+
+#include "atmrt_kernels.h"
+
+namespace atmrt {
+
+constexpr int SHADOW_M_MAX = 65535;
+enum ShadowCtr : int { SH_LIST = 0, SH_LIT, SH_SHADOWED, SH_STEPS, SH_ESCAPED, SH_N };
+
+struct ShadowJob {
+  TracePoints src;      // dist and width are not read
+  double azimuth_deg, elevation_deg, lift;
+  int32_t m;
+  int32_t escape;       // the shortcut is on
+  double esc_floor;     // +inf: no certificate
+  uint32_t* list;       // [n_pixels]
+  unsigned long long* ctr; // [SH_N], zeroed by the launch
+  uint8_t* status;      // [n_pixels]
+  uint16_t* block;      // [n_pixels] or null
+};
+// f: the frame of the context's setting (prepare_frame), with esc_ang_max for this call's reach
+void launch_shadow_mask(const Frame& f, const ShadowJob& job, hipStream_t stream, hipEvent_t ev_compacted);
+
+} // namespace atmrt
+
+#if defined(ATMRT_SHADOW_KERNELS)
+#include "atmrt_device.h"
+
+namespace atmrt {
+
+__global__ __launch_bounds__(256) void k_shadow_compact(ShadowJob j) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = p < j.src.n_pixels;
+  const bool hit = in && j.src.hit_count[p] != 0;
+  wave_compact_append(hit, (uint32_t)p, j.list, &j.ctr[SH_LIST]); // every lane of the wavefront
+  if (in && !hit) {
+    j.status[p] = ATMRT_SHADOW_NONE;
+    if (j.block) j.block[p] = 0;
+  }
+}
+
+constexpr int SHADOW_WAVES = 4; // wavefronts per block
+
+template <int CALC, bool CUBIC>
+__global__ __launch_bounds__(64 * SHADOW_WAVES) void k_shadow_march(Frame f, ShadowJob j) {
+  const int lane = threadIdx.x & 63;
+  const size_t first = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SHADOW_WAVES + (threadIdx.x >> 6))) * 64;
+  const size_t n = (size_t)j.ctr[SH_LIST];
+  if (first >= n) return; // the whole wavefront
+  const bool live = first + lane < n;
+  const uint32_t p = j.list[live ? first + lane : n - 1];
+  const size_t k0 = j.src.hit_offset ? (size_t)j.src.hit_offset[p] : (size_t)p;
+  const Earth e = earth_for<CALC>(f);
+  const bool sph = e.spherical != 0, straight = f.p.straight_rays != 0;
+  const double radius = e.shape_radius, step = f.p.simulation_step, skip_above = f.tv.skip_above;
+  DirCalc c;
+  dircalc_new(e, j.src.lat[k0], j.src.lon[k0], j.azimuth_deg, c);
+  const double h0 = j.src.elev[k0] + j.lift;
+  Stepper s;
+  stepper_init(s, sph, radius, h0, dm_to_radians(j.elevation_deg));
+  double h_prev = h0, d = 0.0;
+  bool decided = !live;
+  int block = 0, steps = 0, escaped = 0;
+  for (int i = 1; i <= j.m; i++) {
+    d = d + step; // d_i: the additions of the stepper's x, wave-uniform
+    if (!decided) {
+      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
+      steps = i;
+      // A sample above every post of the mosaic is above the terrain, whatever its geodesic point (skip_above, as in the frame's
+      // march): H_i < T_i is false without the lookup.  A NaN height takes the full path and compares false there.
+      bool under = false;
+      if (!(st.h > skip_above)) {
+        double lat, lon;
+        coords_at_dist(e, c, d, lat, lon);
+        under = st.h < terrain_elev_or_zero(f.tv, lat, lon);
+      }
+      if (h_prev < -1000.0 || under) { // utils.rs:167
+        block = i;
+        decided = true;
+      } else if (j.escape && escapes(f, s, straight, st.h, h_prev, j.esc_floor)) { // LIT for good
+        escaped = i < j.m ? 1 : 0;
+        decided = true;
+      }
+      h_prev = st.h;
+    }
+    if (__all(decided)) break;
+  }
+  if (live) {
+    j.status[p] = block ? ATMRT_SHADOW_SHADOWED : ATMRT_SHADOW_LIT;
+    if (j.block) j.block[p] = (uint16_t)block;
+  }
+  const unsigned long long n_lit = wave_sum(live && !block ? 1ull : 0ull), n_sh = wave_sum(live && block ? 1ull : 0ull);
+  const unsigned long long n_steps = wave_sum((unsigned long long)steps), n_esc = wave_sum((unsigned long long)escaped);
+  if (lane == 0) {
+    if (n_lit) atomicAdd(&j.ctr[SH_LIT], n_lit);
+    if (n_sh) atomicAdd(&j.ctr[SH_SHADOWED], n_sh);
+    if (n_steps) atomicAdd(&j.ctr[SH_STEPS], n_steps);
+    if (n_esc) atomicAdd(&j.ctr[SH_ESCAPED], n_esc);
+  }
+}
+
+void launch_shadow_mask(const Frame& f, const ShadowJob& job, hipStream_t stream, hipEvent_t ev_compacted) {
+  const size_t n = job.src.n_pixels;
+  (void)hipMemsetAsync(job.ctr, 0, SH_N * sizeof(unsigned long long), stream);
+  hipLaunchKernelGGL(k_shadow_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, job);
+  if (ev_compacted) (void)hipEventRecord(ev_compacted, stream);
+  const dim3 grid(cdiv(n, 64 * SHADOW_WAVES)), blk(64 * SHADOW_WAVES);
+  if (f.atm_cubic) {
+    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_march<CALC, true>), grid, blk, 0, stream, f, job));
+  } else {
+    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_march<CALC, false>), grid, blk, 0, stream, f, job));
+  }
+}
+
+} // namespace atmrt
+#endif

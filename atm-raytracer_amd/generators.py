@@ -393,11 +393,71 @@ def into_coloring(lib, params_pod, conf):
     return col
 
 
-def draw_image(ctx, coloring, width, height):
-    """Composite the frame of the last generate() on `ctx` into an RGB8 image [height][width][3]."""
+def draw_image(ctx, coloring, width, height, shadows=None):
+    """Composite the frame of the last generate() on `ctx` into an RGB8 image [height][width][3].  shadows: the status plane of
+    shadow_mask() for that frame — under Shading the first trace point of a SHADOWED pixel is drawn at ambient_light."""
     rgb = np.zeros((height, width, 3), dtype=np.uint8)
-    ctx.check(ctx.lib.atmrt_draw_image(ctx.handle, C.byref(coloring), rgb.ctypes.data))
+    if shadows is None:
+        ctx.check(ctx.lib.atmrt_draw_image(ctx.handle, C.byref(coloring), rgb.ctypes.data))
+        return rgb
+    status = np.ascontiguousarray(shadows, dtype=np.uint8)
+    if status.size != width * height:
+        raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, f"the shadow status plane has {status.size} entries, the image {width * height} pixels")
+    ctx.check(ctx.lib.atmrt_draw_image_shadowed(ctx.handle, C.byref(coloring), status.ctypes.data, rgb.ctypes.data))
     return rgb
+
+
+# ---- cast shadows: which of the frame's first trace points the light reaches (include/atmrt.h) ------------------------------
+class ShadowMask:
+    """One shadow call: status [height][width] u8 (_abi.SHADOW_*), block [height][width] u16 (None if not asked for), stats (dict)."""
+
+    def __init__(self, status, block, stats):
+        self.status, self.block, self.stats = status, block, stats
+
+
+def shadow_spec(azimuth_deg, elevation_deg, reach, lift=0.0):
+    return _abi.ShadowSpec(float(azimuth_deg), float(elevation_deg), float(reach), float(lift))
+
+
+def light_from_coloring(params_pod, light_zenith_angle, light_dir):
+    """(azimuth_deg, elevation_deg) of the Shading configuration's light for a shadow spec.  ConfColoring::into_coloring
+    (params.rs:250-258) builds the light's horizontal part as -front cos(d) + right sin(d), d = light_dir: front points along
+    frame.direction and right 90 degrees clockwise of it, so the direction toward the light is frame.direction + 180 - light_dir;
+    light_zenith_angle counts from the vertical, so the elevation is 90 - light_zenith_angle."""
+    return params_pod.frame.direction + 180.0 - float(light_dir), 90.0 - float(light_zenith_angle)
+
+
+def shadow_steps(ctx, reach):
+    """atmrt_shadow_steps: m for `reach` under the parameters now set on `ctx`."""
+    m = C.c_int32()
+    ctx.check(ctx.lib.atmrt_shadow_steps(ctx.handle, float(reach), C.byref(m)))
+    return m.value
+
+
+def _shadow_stats(st):
+    return {k: int(getattr(st, k)) for k, _ in _abi.ShadowStats._fields_}
+
+
+def shadow_mask(ctx, spec, width=None, height=None, block=True):
+    """atmrt_shadow_mask over the frame of the last generate() on `ctx`, in the setting now on the context.  spec: an
+    _abi.ShadowSpec, or (azimuth_deg, elevation_deg, reach[, lift]).  Returns a ShadowMask."""
+    if not isinstance(spec, _abi.ShadowSpec):
+        spec = shadow_spec(*spec)
+    if width is None or height is None:
+        p = ctx_params(ctx)
+        width, height = int(p.width), int(p.height)
+    status = np.zeros((height, width), dtype=np.uint8)
+    blk = np.zeros((height, width), dtype=np.uint16) if block else None
+    st = _abi.ShadowStats()
+    ctx.check(ctx.lib.atmrt_shadow_mask(ctx.handle, C.byref(spec), status.ctypes.data, None if blk is None else blk.ctypes.data, C.byref(st)))
+    return ShadowMask(status, blk, _shadow_stats(st))
+
+
+def shadow_timings(ctx):
+    """atmrt_last_shadow_timings of the last shadow call on `ctx`."""
+    out = (C.c_double * 3)()
+    ctx.check(ctx.lib.atmrt_last_shadow_timings(ctx.handle, out))
+    return dict(zip(("compact_ms", "march_ms", "download_ms"), out))
 
 
 # ---- the annotations of renderer::output_image (src/renderer/mod.rs:28-365, 416-431) on the device -----------------------

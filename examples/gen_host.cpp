@@ -67,6 +67,31 @@ int main(int argc, char** argv) {
              h.x, h.y, h.distance);
       if (h.n_within == 0 || h.d2 != 0.0) return 4;
     }
+    if (devices.empty()) { // which of the frame's points does a low western light reach?  (needs the frame: before the calls that follow)
+      const uint32_t w = params.width, h = params.height;
+      const ShadowMask sh = shadow_mask(terrain, atmrt_shadow_spec_t{260.0, 2.0, 20000.0, 0.0}, w, h);
+      for (uint32_t y = 0; y < h; y++) {
+        printf("shadow row %u ", y);
+        for (uint32_t x = 0; x < w; x++) printf("%d:%u%s", sh.status[(size_t)y * w + x], sh.block[(size_t)y * w + x], x + 1 < w ? "," : "\n");
+      }
+      printf("shadow stats none %llu lit %llu shadowed %llu integrated_steps %llu escaped_rays %llu\n", (unsigned long long)sh.stats.none,
+             (unsigned long long)sh.stats.lit, (unsigned long long)sh.stats.shadowed, (unsigned long long)sh.stats.integrated_steps,
+             (unsigned long long)sh.stats.escaped_rays);
+      // and the image with those shadows under the Shading method lit from the same direction: frame.direction + 180 - light_dir = 260
+      const atmrt_params_t pod = params.pod(params.generator);
+      atmrt_coloring_t coloring;
+      if (atmrt_coloring_from_conf(&pod, ATMRT_COLORING_SHADING, 300.0, 0.3, 88.0, -80.0, ATMRT_PALETTE_IMPROVED, 0, 1.0, &coloring)) return 5;
+      const std::vector<uint8_t> lit_image = draw_image_shadowed(terrain, coloring, ShadowMask{std::vector<uint8_t>(sh.status.size(), ATMRT_SHADOW_LIT), {}, {}}, w, h);
+      const std::vector<uint8_t> image = draw_image_shadowed(terrain, coloring, sh, w, h);
+      size_t darker = 0, other = 0;
+      for (size_t p = 0; p < (size_t)w * h; p++) {
+        const bool differs = memcmp(&image[3 * p], &lit_image[3 * p], 3) != 0;
+        if (differs && sh.status[p] == ATMRT_SHADOW_SHADOWED) darker++;
+        else if (differs) other++;
+      }
+      printf("shadow image darker %zu other %zu\n", darker, other);
+      if (other) return 6;
+    }
     if (devices.empty()) { // at which angle does the ground 23.7 km to the east appear, and the top of an 1800 m mast on it?  (no frame needed)
       const std::vector<atmrt_sight_t> sights = sight_lines(terrain, {{90.0, 23700.0, 0.0}, {90.0, 23700.0, 1800.0}}, -6.0, 6.0, 3);
       for (const atmrt_sight_t& s : sights)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Render a panorama PNG on the GPU: generator (C ABI) -> renderer::draw_image on the device -> PNG via Pillow.
-Usage: python examples/render_png.py OUT.png [--scene S3] [--width 1024] [--height 512] [--generator Fast] [--objects N]"""
+Usage: python examples/render_png.py OUT.png [--scene S3] [--width 1024] [--height 512] [--generator Fast] [--objects N]
+       [--shadows [--sun-elevation DEG] [--shadow-reach M]]"""
 import argparse
 import os
 import sys
@@ -20,10 +21,13 @@ def main():
     ap.add_argument("--terrain-alpha", type=float, default=1.0)
     ap.add_argument("--coloring", default="Shading", choices=["Shading", "Simple"])
     ap.add_argument("--fog", type=float, default=None)
+    ap.add_argument("--shadows", action="store_true", help="cast shadows from the Shading light (include/atmrt.h, cast shadows)")
+    ap.add_argument("--sun-elevation", type=float, default=35.0, help="degrees above the horizon: light_zenith_angle = 90 - this")
+    ap.add_argument("--shadow-reach", type=float, default=50_000.0)
     a = ap.parse_args()
     from PIL import Image
     cfg, tiles = synth.scene(a.scene, a.width, a.height, generator=a.generator, step=100.0, terrain_alpha=a.terrain_alpha)
-    view = {"coloring": {a.coloring: {"water_level": 300.0} if a.coloring == "Simple" else {"water_level": 300.0, "light_dir": 40.0, "light_zenith_angle": 55.0}}}
+    view = {"coloring": {a.coloring: {"water_level": 300.0} if a.coloring == "Simple" else {"water_level": 300.0, "light_dir": 40.0, "light_zenith_angle": 90.0 - a.sun_elevation}}}
     if a.fog:
         view["fog_distance"] = a.fog
     cfg.coloring = config._coloring(view)
@@ -34,7 +38,16 @@ def main():
     terrain = generators.Terrain.from_tiles(tiles, ctx)
     gen = generators.make_generator(generators.Params(cfg), terrain)
     res = gen.generate()
-    rgb = generators.draw_image(ctx, generators.into_coloring(ctx.lib, cfg.params, cfg.coloring), a.width, a.height)
+    shadows = None
+    if a.shadows:
+        if a.coloring != "Shading":
+            ap.error("--shadows darkens the Shading method's image: use --coloring Shading")
+        az, el = generators.light_from_coloring(cfg.params, cfg.coloring["light_zenith_angle"], cfg.coloring["light_dir"])
+        mask = generators.shadow_mask(ctx, (az, el, a.shadow_reach, 0.0), a.width, a.height, block=False)
+        shadows = mask.status
+        print(f"light at azimuth {az:g}, elevation {el:g}: {mask.stats['lit']} points lit, {mask.stats['shadowed']} in shadow, "
+              f"{generators.shadow_timings(ctx)['march_ms']:.2f} ms of shadow march")
+    rgb = generators.draw_image(ctx, generators.into_coloring(ctx.lib, cfg.params, cfg.coloring), a.width, a.height, shadows=shadows)
     Image.fromarray(rgb, "RGB").save(a.out)
     print(f"{a.out}: {a.width}x{a.height}, {res['n_hits']} trace points, {res['ray_steps']} ray-steps, {res['device_ms']:.2f} ms on device")
 

@@ -768,6 +768,71 @@ int atmrt_last_horizon_timings(atmrt_ctx* ctx, double out[5]);
 /* The batches that call took, and whether it rebuilt the path table (1) or found it (0). */
 int atmrt_last_horizon_work(atmrt_ctx* ctx, int32_t* batches, int32_t* table_rebuilt);
 
+/* ---- cast shadows: which of a frame's first trace points the light reaches (no reference counterpart: Shading, coloring/shading.rs:
+ * 108-112, darkens a slope by the angle between its normal and light_dir and knows nothing of the terrain between the point and
+ * the light).  A second march, from every hit pixel toward the light, through the refracting stepper.
+ *
+ * THE RULE (tests/shadow_model.py restates it in numpy).  A spec is {azimuth_deg: the direction TOWARD the light, elevation_deg:
+ * the launch elevation angle of the shadow ray, reach [m] > 0, lift [m] >= 0}; elevation_deg is finite and strictly between -90
+ * and 90.  SIMPLIFICATION: azimuth_deg and elevation_deg are taken as the same in the local frame of every surface point.  The
+ * true local direction of a light at infinity turns with the point's position by distance / R: up to 1.8 degrees over a frame of
+ * 200 km.  A direction per point is a later change.  The setting is what the context holds NOW: earth model, simulation_step
+ * (`step`), straight_rays, atmosphere, terrain.
+ *   For pixel p of the last frame with hit_count[p] >= 1 take its FIRST trace point (lat_p, lon_p, elev_p): entry p of the planes,
+ *   or entry hit_offset[p] of the lists — whatever the point is, terrain or object: objects receive shadows, they cast none.
+ *   Lattice: d_0 = 0, d_i = d_{i-1} + step by repeated addition; m = the first index with d_m >= reach (m > 65535: invalid);
+ *     (lat_i, lon_i) = coords_at_dist(d_i) from (lat_p, lon_p) along azimuth_deg, through a DirectionalCalc made at the point
+ *     exactly as the reference makes one at the observer; T_i = get_elev(lat_i, lon_i), 0 where the terrain has none.
+ *   Ray: H_0 = elev_p + lift (one rounded addition); H_i = the stepper's h after i steps of `step` from H_0 at elevation_deg, as
+ *     atmrt_ray_paths returns it; with straight_rays the straight stepper.
+ *   SHADOWED at i for the first 1 <= i <= m with H_i < T_i or H_{i-1} < -1000.0 (utils.rs:167), whichever i is smaller; otherwise
+ *     LIT.  The point's own sample (i = 0) is deliberately not tested: a trace point is interpolated between two samples and may
+ *     lie a hair under the bilinear surface.  A NaN compares false: it never shadows.
+ *   Outputs per pixel: status u8 (atmrt_shadow_status), and optionally block u16 = that i for SHADOWED, else 0.
+ * Equal calls return equal bytes.  The escape shortcut (ATMRT_SHADOW_ESCAPE=off, read at every call, disables it) only ends rays
+ * that are LIT for good: the planes do not depend on it, atmrt_shadow_stats_t's last two counts do. */
+typedef struct atmrt_shadow_spec {
+  double azimuth_deg;   /* toward the light, finite */
+  double elevation_deg; /* finite, in (-90, 90) */
+  double reach;         /* [m], finite, > 0 */
+  double lift;          /* [m], finite, >= 0 */
+} atmrt_shadow_spec_t;
+typedef enum atmrt_shadow_status {
+  ATMRT_SHADOW_NONE = 0, /* the pixel has no trace point */
+  ATMRT_SHADOW_LIT = 1,
+  ATMRT_SHADOW_SHADOWED = 2
+} atmrt_shadow_status;
+/* none + lit + shadowed = the pixels; integrated_steps: the stepper steps taken (a SHADOWED ray its block index, a LIT ray m, or
+ * the index at which it passed the escape test); escaped_rays: the LIT rays that passed it before m. */
+typedef struct atmrt_shadow_stats {
+  uint64_t none, lit, shadowed, integrated_steps, escaped_rays;
+} atmrt_shadow_stats_t;
+/* m for `reach` under the parameters now set on ctx.  ATMRT_ERR_INVALID_ARGUMENT: NULL, a reach that is not finite and positive,
+ * m > 65535.  ATMRT_ERR_STATE: before atmrt_set_params. */
+int atmrt_shadow_steps(atmrt_ctx* ctx, double reach, int32_t* m);
+/* The status plane (and block, unless NULL) of the last frame of a single-device context, [height][width] as the frame's planes,
+ * into memory of the context's device.  stats may be NULL.  The frame stays as it is.  ATMRT_ERR_INVALID_ARGUMENT: NULL, a
+ * number that is not finite, elevation_deg outside (-90, 90), reach <= 0, lift < 0, m > 65535.  ATMRT_ERR_STATE: before
+ * atmrt_set_params, without a frame, on a multi-device context. */
+int atmrt_shadow_mask_device(atmrt_ctx* ctx, const atmrt_shadow_spec_t* spec, uint8_t* status_device, uint16_t* block_device,
+                             atmrt_shadow_stats_t* stats);
+/* The same into host arrays. */
+int atmrt_shadow_mask(atmrt_ctx* ctx, const atmrt_shadow_spec_t* spec, uint8_t* status, uint16_t* block, atmrt_shadow_stats_t* stats);
+/* The same over any planes of n_pixels entries in device memory (the first trace point of pixel p is entry p): what a gathered
+ * multi-device frame uses, as atmrt_visibility_map_planes_device does; the setting is still the context's. */
+int atmrt_shadow_mask_planes_device(atmrt_ctx* ctx, const atmrt_shadow_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
+                                    const double* lat, const double* lon, const double* elev, uint8_t* status_device,
+                                    uint16_t* block_device, atmrt_shadow_stats_t* stats);
+/* renderer::draw_image exactly as atmrt_draw_image does it, with one exception: under ATMRT_COLORING_SHADING the first trace point
+ * of a pixel whose status is ATMRT_SHADOW_SHADOWED takes light_dot = 0.0, so its brightness is exactly ambient_light; later
+ * points of a translucent pixel are shaded as before.  Under ATMRT_COLORING_SIMPLE the status plane has no effect.  `status`:
+ * [height][width] of the last frame, host memory (_device: memory of the context's device, like rgb_device). */
+int atmrt_draw_image_shadowed(atmrt_ctx* ctx, const atmrt_coloring_t* coloring, const uint8_t* status, uint8_t* rgb);
+int atmrt_draw_image_shadowed_device(atmrt_ctx* ctx, const atmrt_coloring_t* coloring, const uint8_t* status_device, uint8_t* rgb_device);
+/* Where the time of the last shadow call on ctx went, in milliseconds between events on the library's stream:
+ * out = {compaction (clear and upload included), march, download (statistics, and the planes of atmrt_shadow_mask)}. */
+int atmrt_last_shadow_timings(atmrt_ctx* ctx, double out[3]);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —

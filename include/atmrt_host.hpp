@@ -365,4 +365,27 @@ inline std::vector<atmrt_horizon_t> horizon(const Terrain& terrain, const atmrt_
   return out;
 }
 
+// Cast shadows (no reference counterpart; include/atmrt.h states the rule): for the first trace point of every pixel of the frame
+// last generated on `terrain`'s context, whether a ray toward the light (spec: azimuth toward it, launch elevation, reach, lift)
+// clears the terrain.  status (atmrt_shadow_status) and block are [height][width].
+struct ShadowMask {
+  std::vector<uint8_t> status;
+  std::vector<uint16_t> block;
+  atmrt_shadow_stats_t stats{};
+};
+inline ShadowMask shadow_mask(const Terrain& terrain, const atmrt_shadow_spec_t& spec, uint32_t width, uint32_t height) {
+  ShadowMask out;
+  out.status.resize((size_t)width * height), out.block.resize((size_t)width * height);
+  terrain.check(atmrt_shadow_mask(terrain.ctx(), &spec, out.status.data(), out.block.data(), &out.stats));
+  return out;
+}
+// renderer::draw_image of that frame, RGB8 [height][width][3], the first trace point of a SHADOWED pixel at the Shading method's ambient light
+inline std::vector<uint8_t> draw_image_shadowed(const Terrain& terrain, const atmrt_coloring_t& coloring, const ShadowMask& mask, uint32_t width,
+                                                uint32_t height) {
+  if (mask.status.size() != (size_t)width * height) throw Error(ATMRT_ERR_INVALID_ARGUMENT, "the shadow mask is not the image's size");
+  std::vector<uint8_t> rgb(3 * (size_t)width * height);
+  terrain.check(atmrt_draw_image_shadowed(terrain.ctx(), &coloring, mask.status.data(), rgb.data()));
+  return rgb;
+}
+
 } // namespace atmrt_host
