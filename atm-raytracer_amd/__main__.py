@@ -9,7 +9,8 @@
                                     [--viewshed-map OUT.npz [--map-cell ARCSEC] [--viewshed-observers FILE.csv]]
                                     [--horizon OUT.csv [--horizon-az LO HI N] [--horizon-reach M] [--horizon-fan LO HI K]
                                      [--horizon-rounds N]]
-                                    [--shadows [--shadow-reach M] [--shadow-lift M] [--shadow-light AZ EL]]
+                                    [--shadows [--shadow-reach M] [--shadow-lift M] [--shadow-light AZ EL] [--shadow-per-point]]
+                                    [--shadow-lights FILE.csv [--shadow-lights-out OUT.npz] [--shadow-reach M] [--shadow-lift M]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -56,7 +57,15 @@ above_fan, below_fan), angle_clear_deg, angle_blocked_deg, resolution_deg, ridge
 the light through the same atmosphere, --shadow-reach metres far (max_distance, at most 65535 steps) from --shadow-lift metres above
 the point (0), and a point whose ray meets terrain is drawn at the Shading method's ambient light.  The light is the Shading
 configuration's (azimuth = frame direction + 180 - light_dir, elevation = 90 - light_zenith_angle) unless --shadow-light AZ EL names
-the azimuth toward it and its elevation in degrees; both are taken as the same at every point of the frame.
+the azimuth toward it and its elevation in degrees; both are taken as the same at every point of the frame.  With
+--shadow-per-point the light is a direction in the world instead — the Shading configuration's own light_dir vector, so that slopes
+and shadows share one light, or --shadow-light AZ EL as seen from the observer — and every point marches in its own local direction
+toward it (include/atmrt.h, "shadow lights").
+`--shadow-lights FILE.csv` (no reference counterpart) asks the same for up to 64 lights in one call, a day's sun path for instance:
+rows of azimuth_deg,elevation_deg as seen from the observer, each turned into a world-frame vector there; --shadow-reach and
+--shadow-lift as above.  OUT.npz (--shadow-lights-out, shadow_lights.npz) holds lit_mask [height][width] u64 (bit l: light l reaches
+the pixel's first trace point), lit_count (its popcount, taken on the host), dirs [n][3], azimuth_deg, elevation_deg and the call's
+stats_none, stats_lit, stats_shadowed, stats_integrated_steps, stats_escaped_rays.
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -273,6 +282,65 @@ def shadow_spec_of(cfg, reach, lift, light):
     return generators.shadow_spec(az, el, reach, lift)
 
 
+def shadow_reach_of(cfg, reach, lift):
+    step = cfg.params.simulation_step
+    reach = min(float(reach) if reach is not None else cfg.params.frame.max_distance, 65535 * step)
+    if not reach > 0.0 or lift < 0.0:
+        raise config.ConfigError("--shadow-reach must be positive and --shadow-lift not negative")
+    return reach
+
+
+def shadow_world_light(cfg, col, light):
+    """The one light of gen --shadows --shadow-per-point as a world-frame vector [1][3]: --shadow-light AZ EL as seen from the
+    observer, or the Shading configuration's own light_dir."""
+    if light is not None:
+        if not -90.0 <= float(light[1]) <= 90.0:
+            raise config.ConfigError(f"--shadows: the light's elevation {light[1]!r} must lie between -90 and 90 degrees")
+        return generators.lights_from_angles(cfg.params, [(float(light[0]), float(light[1]))])
+    if cfg.coloring["kind"] != 1:
+        raise config.ConfigError("--shadows needs a light: the Shading colouring method's, or --shadow-light AZ EL")
+    return np.array([list(col.light_dir)], dtype=np.float64)
+
+
+def read_lights_csv(path):
+    """Rows of azimuth_deg,elevation_deg; blank lines, lines that start with # and one header line are skipped."""
+    rows = []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            text = line.strip()
+            if not text or text.startswith("#"):
+                continue
+            cells = [c.strip() for c in text.split(",")]
+            try:
+                az, el = float(cells[0]), float(cells[1])
+            except (ValueError, IndexError):
+                if not rows and any(c.isalpha() for c in text):
+                    continue  # the header
+                raise config.ConfigError(f"{path}:{n}: expected azimuth_deg,elevation_deg, found {text!r}")
+            rows.append((az, el))
+    if not 1 <= len(rows) <= 64:
+        raise config.ConfigError(f"{path}: {len(rows)} lights; a call takes 1 to 64")
+    return rows
+
+
+def write_shadow_lights(ctx, cfg, path, out, reach, lift, w, h):
+    """gen --shadow-lights: the lit mask of the lights of `path` over the frame on the device, its popcount and the call's counts
+    to an .npz; returns what was written."""
+    import torch
+    rows = read_lights_csv(path)
+    spec, dirs = generators.shadow_lights_spec(generators.lights_from_angles(cfg.params, rows, ctx.lib), shadow_reach_of(cfg, reach, lift), lift)
+    mask_dev = torch.empty((h, w), dtype=torch.int64, device=torch.device("cuda", ctx.device))
+    st = _abi.ShadowStats()
+    ctx.check(ctx.lib.atmrt_shadow_lights_device(ctx.handle, C.byref(spec), mask_dev.data_ptr(), None, None, C.byref(st)))
+    mask = mask_dev.cpu().numpy().view(np.uint64)
+    count = np.unpackbits(mask.view(np.uint8).reshape(h, w, 8), axis=2).sum(axis=2).astype(np.uint8)
+    data = dict(lit_mask=mask, lit_count=count, dirs=dirs, azimuth_deg=np.array([r[0] for r in rows]), elevation_deg=np.array([r[1] for r in rows]))
+    data.update({"stats_" + k: np.uint64(v) for k, v in generators._shadow_stats(st).items()})
+    np.savez_compressed(out, **data)
+    print(f"{len(rows)} lights: {st.lit} point-light pairs lit, {st.shadowed} in shadow, {st.none} pixels without a trace point")
+    return data
+
+
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
@@ -292,16 +360,25 @@ def cmd_gen(a):
     rgb_dev = torch.empty((h, w, 3), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
     if a.shadows:  # the second march, then the image through the status plane: both stay on the device
         stamp("Casting shadows...")
-        spec = shadow_spec_of(cfg, a.shadow_reach, a.shadow_lift, a.shadow_light)
         status_dev = torch.empty((h, w), dtype=torch.uint8, device=rgb_dev.device)
         st = _abi.ShadowStats()
-        ctx.check(ctx.lib.atmrt_shadow_mask_device(ctx.handle, C.byref(spec), status_dev.data_ptr(), None, C.byref(st)))
-        print(f"Light at azimuth {spec.azimuth_deg!r}, elevation {spec.elevation_deg!r}: {st.lit} points lit, {st.shadowed} in shadow")
+        if a.shadow_per_point:  # one light of the world: every point marches in its own local direction
+            light = shadow_world_light(cfg, col, a.shadow_light)
+            lights, keep = generators.shadow_lights_spec(light, shadow_reach_of(cfg, a.shadow_reach, a.shadow_lift), a.shadow_lift)
+            ctx.check(ctx.lib.atmrt_shadow_lights_device(ctx.handle, C.byref(lights), None, status_dev.data_ptr(), None, C.byref(st)))
+            print(f"Light along {[float(v) for v in keep[0]]!r} of the world: {st.lit} points lit, {st.shadowed} in shadow")
+        else:
+            spec = shadow_spec_of(cfg, a.shadow_reach, a.shadow_lift, a.shadow_light)
+            ctx.check(ctx.lib.atmrt_shadow_mask_device(ctx.handle, C.byref(spec), status_dev.data_ptr(), None, C.byref(st)))
+            print(f"Light at azimuth {spec.azimuth_deg!r}, elevation {spec.elevation_deg!r}: {st.lit} points lit, {st.shadowed} in shadow")
         ctx.check(ctx.lib.atmrt_draw_image_shadowed_device(ctx.handle, C.byref(col), status_dev.data_ptr(), rgb_dev.data_ptr()))
     else:
         ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
     ticks, _ = generators.draw_overlay_device(ctx, generators.into_overlay(cfg.output), rgb_dev.data_ptr(), w, h)
-    if a.visibility_map:  # on the device, while the frame is still in HBM
+    if a.shadow_lights:  # on the device, while the frame is still in HBM
+        stamp("Casting the shadows of the light list...")
+        write_shadow_lights(ctx, cfg, a.shadow_lights, a.shadow_lights_out, a.shadow_reach, a.shadow_lift, w, h)
+    if a.visibility_map:  # likewise
         stamp("Binning the visibility map...")
         write_visibility_map(ctx, a.visibility_map, a.map_cell, "all" if a.map_all else "first")
     located = None
@@ -423,6 +500,9 @@ def main(argv=None):
     g.add_argument("--shadow-reach", type=float, default=None, metavar="M")
     g.add_argument("--shadow-lift", type=float, default=0.0, metavar="M")
     g.add_argument("--shadow-light", type=float, nargs=2, default=None, metavar=("AZ", "EL"))
+    g.add_argument("--shadow-per-point", action="store_true")
+    g.add_argument("--shadow-lights", default=None, metavar="FILE.csv")
+    g.add_argument("--shadow-lights-out", default="shadow_lights.npz", metavar="OUT.npz")
     g.add_argument("--horizon", default=None, metavar="OUT.csv")
     g.add_argument("--horizon-az", type=float, nargs=3, default=None, metavar=("LO", "HI", "N"))
     g.add_argument("--horizon-reach", type=float, default=None, metavar="M")

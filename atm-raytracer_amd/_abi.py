@@ -228,6 +228,11 @@ class ShadowStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("none", "lit", "shadowed", "integrated_steps", "escaped_rays")]
 
 
+class ShadowLightsSpec(C.Structure):
+    """atmrt_shadow_lights_spec_t: the lights (world-frame vectors [n_lights][3], host memory), the reach and the lift [m]."""
+    _fields_ = [("dir", C.POINTER(C.c_double)), ("n_lights", C.c_uint32), ("_pad", C.c_uint32), ("reach", C.c_double), ("lift", C.c_double)]
+
+
 class Horizon(C.Structure):
     _fields_ = [("status", C.c_int32), ("rounds_done", C.c_int32), ("k_star", C.c_int32), ("block_index", C.c_int32)] + \
         [(k, C.c_double) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon", "block_elevation")]

@@ -142,6 +142,11 @@ def load():
         "atmrt_draw_image_shadowed": (C.c_int, [vp, C.POINTER(_abi.Coloring), vp, vp]),
         "atmrt_draw_image_shadowed_device": (C.c_int, [vp, C.POINTER(_abi.Coloring), vp, vp]),
         "atmrt_last_shadow_timings": (C.c_int, [vp, pd]),
+        "atmrt_shadow_light_direction": (C.c_int, [C.POINTER(_abi.EarthModel), dbl, dbl, dbl, dbl, pd]),
+        "atmrt_shadow_local_direction": (C.c_int, [C.POINTER(_abi.EarthModel), pd, dbl, dbl, pd, pd]),
+        "atmrt_shadow_lights_device": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), vp, vp, vp, C.POINTER(_abi.ShadowStats)]),
+        "atmrt_shadow_lights": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), vp, vp, vp, C.POINTER(_abi.ShadowStats)]),
+        "atmrt_shadow_lights_planes_device": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(_abi.ShadowStats)]),
         "atmrt_ray_paths": (C.c_int, [vp, dbl, sz, vp, i32, dbl, sz, vp, vp]),
         "atmrt_atmosphere_sample": (C.c_int, [vp, sz, vp, vp, vp, vp, vp]),
         "atmrt_coords_at_dist": (C.c_int, [vp, dbl, dbl, dbl, sz, vp, vp, vp]),
@@ -193,7 +198,8 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_viewshed_map_planes_device", "atmrt_viewshed_map_device", "atmrt_viewshed_map",
             "atmrt_debug_horizon_shape", "atmrt_horizon", "atmrt_horizon_device", "atmrt_last_horizon_timings", "atmrt_last_horizon_work",
             "atmrt_shadow_steps", "atmrt_shadow_mask_device", "atmrt_shadow_mask", "atmrt_shadow_mask_planes_device", "atmrt_draw_image_shadowed",
-            "atmrt_draw_image_shadowed_device", "atmrt_last_shadow_timings", "atmrt_ray_paths", "atmrt_atmosphere_sample",
+            "atmrt_draw_image_shadowed_device", "atmrt_last_shadow_timings", "atmrt_shadow_light_direction", "atmrt_shadow_local_direction",
+            "atmrt_shadow_lights_device", "atmrt_shadow_lights", "atmrt_shadow_lights_planes_device", "atmrt_ray_paths", "atmrt_atmosphere_sample",
             "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_result_encode_bincode",
             "atmrt_result_decode_bincode", "atmrt_comm_unique_id", "atmrt_ctx_comm_init_rank", "atmrt_ctx_comm_init_external", "atmrt_ctx_comm_init_external_device",
             "atmrt_ctx_create_multi", "atmrt_ctx_device_count", "atmrt_generate_image_device", "atmrt_image_hits_device",

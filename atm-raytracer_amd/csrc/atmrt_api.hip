@@ -162,6 +162,8 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     // 34 stays 0
     case 35: return sizeof(atmrt_shadow_spec_t);
     case 36: return sizeof(atmrt_shadow_stats_t);
+    // 37 stays 0
+    case 38: return sizeof(atmrt_shadow_lights_spec_t);
     default: return 0;
   }
 }
@@ -2835,6 +2837,155 @@ extern "C" int atmrt_shadow_mask_planes_device(atmrt_ctx* c, const atmrt_shadow_
   HIP_TRY(c, hipSetDevice(k->device));
   return shadow_run(k, c, *spec, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, status_device, block_device, stats, nullptr,
                     nullptr);
+}
+
+// ---- shadow lights: a direction per point and a list of lights per call (include/atmrt.h, "shadow lights") -------------------
+extern "C" int atmrt_shadow_light_direction(const atmrt_earth_model_t* earth, double lat, double lon, double azimuth_deg, double elevation_deg,
+                                            double dir[3]) {
+  if (!earth || !dir) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!(std::isfinite(lat) && std::isfinite(lon) && std::isfinite(azimuth_deg) && std::isfinite(elevation_deg))) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!(elevation_deg >= -90.0 && elevation_deg <= 90.0)) return ATMRT_ERR_INVALID_ARGUMENT;
+  Earth e;
+  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
+  Vec3 n, ea, u;
+  world_directions(e, lat, lon, n, ea, u);
+  double sin_az, cos_az, sin_el, cos_el;
+  dm_sincos(dm_to_radians(azimuth_deg), &sin_az, &cos_az);
+  dm_sincos(dm_to_radians(elevation_deg), &sin_el, &cos_el);
+  const Vec3 v = n * (cos_el * cos_az) + ea * (cos_el * sin_az) + u * sin_el;
+  dir[0] = v.x, dir[1] = v.y, dir[2] = v.z;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_shadow_local_direction(const atmrt_earth_model_t* earth, const double dir[3], double lat, double lon, double* azimuth_deg,
+                                            double* elevation_deg) {
+  if (!earth || !dir || !azimuth_deg || !elevation_deg) return ATMRT_ERR_INVALID_ARGUMENT;
+  Earth e;
+  Vec3 light;
+  if (earth_resolve(*earth, e) || !shadow_light_normalise(dir, light)) return ATMRT_ERR_INVALID_ARGUMENT;
+  Vec3 n, ea, u;
+  world_directions(e, lat, lon, n, ea, u);
+  shadow_local_direction(n, ea, u, light, *azimuth_deg, *elevation_deg);
+  return ATMRT_OK;
+}
+
+namespace {
+
+// what every shadow-lights entry point asks of its arguments and of the context's parameters; lights: [n_lights][3], normalised
+int shadow_lights_check(atmrt_ctx* c, const char* what, const atmrt_shadow_lights_spec_t* spec, const void* lit_mask, const void* status,
+                        int32_t* m, std::vector<double>& lights) {
+  if (!spec || !spec->dir) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or its dir is NULL", what);
+  if (!lit_mask && !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: neither lit_mask nor status is given", what);
+  if (spec->n_lights < 1 || spec->n_lights > SHADOW_LIGHTS_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_lights must lie in [1, 64], not %u", what, spec->n_lights);
+  lights.resize(3 * (size_t)spec->n_lights);
+  for (uint32_t l = 0; l < spec->n_lights; l++) {
+    Vec3 v;
+    if (!shadow_light_normalise(spec->dir + 3 * l, v))
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: light %u is not a finite vector of a finite, positive squared length", what, l);
+    lights[3 * l] = v.x, lights[3 * l + 1] = v.y, lights[3 * l + 2] = v.z;
+  }
+  if (!(std::isfinite(spec->reach) && spec->reach > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: reach must be finite and positive", what);
+  if (!(std::isfinite(spec->lift) && spec->lift >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: lift must be finite and not negative", what);
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
+  if (const char* msg = shadow_steps_of(c, spec->reach, m)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  return ATMRT_OK;
+}
+
+const char* const SHADOW_LIGHTS_ON_MULTI = "has no frame of its own: shadow lights work on the gathered planes through atmrt_shadow_lights_planes_device";
+
+// shadow_run for a list of lights.  host_*: where the planes are downloaded to inside the call's timed window (null: none).
+int shadow_lights_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_lights_spec_t& spec, const std::vector<double>& lights, int32_t m,
+                      const TracePoints& src, uint64_t* mask_dev, uint8_t* status_dev, uint16_t* block_dev, atmrt_shadow_stats_t* stats,
+                      uint64_t* host_mask, uint8_t* host_status, uint16_t* host_block) {
+  Frame f;
+  if (int rc = prepare_frame(k, &f)) {
+    if (k != report) report->error = k->error;
+    return rc;
+  }
+  hipStream_t s = k->stream;
+  ShadowLightsJob job{};
+  job.src = src;
+  job.n_lights = spec.n_lights, job.lift = spec.lift, job.m = m;
+  job.esc_floor = shadow_escape_floor(k, f, spec.reach);
+  job.escape = job.esc_floor < INFINITY ? 1 : 0;
+  job.lit_mask = reinterpret_cast<unsigned long long*>(mask_dev), job.status = status_dev, job.block = block_dev;
+  double* d_dirs = nullptr;
+  HIP_TRY(report, reserve_carved(k->d_shadow, [&](Carve& cv) {
+            cv(job.list, src.n_pixels * sizeof(uint32_t)), cv(job.ctr, SH_N * sizeof(unsigned long long)), cv(d_dirs, 3 * SHADOW_LIGHTS_MAX * sizeof(double));
+          }));
+  job.dirs = d_dirs;
+  const size_t planes = src.n_pixels * spec.n_lights;
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_BEGIN], s));
+  HIP_TRY(report, hipMemcpyAsync(d_dirs, lights.data(), lights.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_shadow_lights(f, job, s, k->ev[EV_SH_COMPACTED]);
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_MARCHED], s));
+  unsigned long long ctr[SH_N] = {};
+  HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+  if (host_mask) HIP_TRY(report, hipMemcpyAsync(host_mask, mask_dev, src.n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  if (host_status) HIP_TRY(report, hipMemcpyAsync(host_status, status_dev, planes, hipMemcpyDeviceToHost, s));
+  if (host_block) HIP_TRY(report, hipMemcpyAsync(host_block, block_dev, planes * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_END], s));
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
+  for (int i = 0; i < 3; i++) {
+    float ms = 0.0f;
+    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[EV_SH_BEGIN + i], k->ev[EV_SH_BEGIN + i + 1]));
+    report->shadow_timings[i] = ms;
+  }
+  if (stats) {
+    stats->lit = ctr[SH_LIT], stats->shadowed = ctr[SH_SHADOWED];
+    stats->none = src.n_pixels - ctr[SH_LIST];
+    stats->integrated_steps = ctr[SH_STEPS], stats->escaped_rays = ctr[SH_ESCAPED];
+  }
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_shadow_lights_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask_device, uint8_t* status_device,
+                                          uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  int32_t m = 0;
+  std::vector<double> lights;
+  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights", spec, lit_mask_device, status_device, &m, lights)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_shadow_lights", SHADOW_LIGHTS_ON_MULTI)) return rc;
+  return shadow_lights_run(c, c, *spec, lights, m, last_frame_points(c, ATMRT_VIS_ALL), lit_mask_device, status_device, block_device, stats, nullptr,
+                           nullptr, nullptr);
+}
+
+extern "C" int atmrt_shadow_lights(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask, uint8_t* status, uint16_t* block,
+                                   atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  int32_t m = 0;
+  std::vector<double> lights;
+  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights", spec, lit_mask, status, &m, lights)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_shadow_lights", SHADOW_LIGHTS_ON_MULTI)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  // the staging buffer: the mask (8 n), then the block planes (2 n L), then the status planes (n L); what is not asked for takes no room
+  const size_t n = c->last_npx, planes = n * spec->n_lights;
+  const size_t mask_bytes = lit_mask ? n * sizeof(uint64_t) : 0, block_bytes = block ? planes * sizeof(uint16_t) : 0;
+  HIP_TRY(c, c->d_io.reserve(mask_bytes + block_bytes + (status ? planes : 0)));
+  uint64_t* d_mask = lit_mask ? c->d_io.as<uint64_t>() : nullptr;
+  uint16_t* d_block = block ? reinterpret_cast<uint16_t*>(c->d_io.as<uint8_t>() + mask_bytes) : nullptr;
+  uint8_t* d_status = status ? c->d_io.as<uint8_t>() + mask_bytes + block_bytes : nullptr;
+  return shadow_lights_run(c, c, *spec, lights, m, last_frame_points(c, ATMRT_VIS_ALL), d_mask, d_status, d_block, stats, lit_mask, status, block);
+}
+
+extern "C" int atmrt_shadow_lights_planes_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
+                                                 const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
+                                                 uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!hit_count || !lat || !lon || !elev) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_lights_planes_device: a plane is NULL");
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_lights_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  int32_t m = 0;
+  std::vector<double> lights;
+  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights_planes_device", spec, lit_mask_device, status_device, &m, lights)) return rc;
+  atmrt_ctx* k = nullptr;
+  const bool by_mask = lit_mask_device != nullptr;
+  if (int rc = planes_context(c, by_mask ? (const void*)lit_mask_device : (const void*)status_device, by_mask ? "lit_mask_device" : "status_device", &k)) return rc;
+  HIP_TRY(c, hipSetDevice(k->device));
+  return shadow_lights_run(k, c, *spec, lights, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, lit_mask_device, status_device,
+                           block_device, stats, nullptr, nullptr, nullptr);
 }
 
 extern "C" int atmrt_draw_image_shadowed_device(atmrt_ctx* c, const atmrt_coloring_t* coloring, const uint8_t* status_device, uint8_t* rgb_device) {

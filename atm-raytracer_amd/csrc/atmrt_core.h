@@ -963,6 +963,27 @@ ATMRT_HD void world_directions(const Earth& e, double lat, double lon, Vec3& n, 
   }
 }
 
+// include/atmrt.h, "shadow lights": the local direction of the normalised world-frame light L at a point whose world_directions
+// are (n, ea, up).  One function for the kernel (k_shadow_lights) and the host (atmrt_shadow_local_direction).
+ATMRT_HD void shadow_local_direction(const Vec3& n, const Vec3& ea, const Vec3& up, const Vec3& L, double& azimuth_deg, double& elevation_deg) {
+  const double a = dot(L, n), b = dot(L, ea), c = dot(L, up);
+  const double cc = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c); // a NaN passes through
+  azimuth_deg = dm_to_degrees(dm_atan2(b, a));
+  elevation_deg = dm_to_degrees(dm_asin(cc));
+}
+
+// A light as the caller gives it -> the normalised L of the rule; false: a component or the squared length is not finite, or the
+// length is 0.  Host only in effect (the library normalises once per call).
+ATMRT_HD bool shadow_light_normalise(const double dir[3], Vec3& L) {
+  const double x = dir[0], y = dir[1], z = dir[2];
+  if (dm_isnan(x) || dm_isinf(x) || dm_isnan(y) || dm_isinf(y) || dm_isnan(z) || dm_isinf(z)) return false;
+  const double n2 = x * x + y * y + z * z;
+  if (dm_isnan(n2) || dm_isinf(n2) || !(n2 > 0.0)) return false;
+  const double s = dm_sqrt(n2);
+  L = v3(x / s, y / s, z / s);
+  return true;
+}
+
 // EarthModel::as_cartesian, mod.rs:59-93 (+ spherical_to_cartesian :148-153)
 ATMRT_HD Vec3 as_cartesian(const Earth& e, double lat, double lon, double elev) {
   if (e.cart == 1) {

@@ -453,6 +453,68 @@ def shadow_mask(ctx, spec, width=None, height=None, block=True):
     return ShadowMask(status, blk, _shadow_stats(st))
 
 
+# ---- shadow lights: a direction per point and a list of lights per call (include/atmrt.h, "shadow lights") ------------------
+class ShadowLights:
+    """One shadow-lights call: lit_mask [height][width] u64 (bit l: light l reaches the pixel's first trace point), status
+    [n_lights][height][width] u8 and block [n_lights][height][width] u16 (None if not asked for), stats (dict), dirs [n_lights][3]."""
+
+    def __init__(self, lit_mask, status, block, stats, dirs):
+        self.lit_mask, self.status, self.block, self.stats, self.dirs = lit_mask, status, block, stats, dirs
+
+
+def shadow_light_direction(earth, lat, lon, azimuth_deg, elevation_deg, lib=None):
+    """atmrt_shadow_light_direction (host code, no device): the world-frame vector of a light seen from (lat, lon) under
+    (azimuth_deg, elevation_deg).  earth: an _abi.EarthModel (params.earth)."""
+    lib = lib or _lib.load()
+    out = (C.c_double * 3)()
+    rc = lib.atmrt_shadow_light_direction(C.byref(earth), float(lat), float(lon), float(azimuth_deg), float(elevation_deg), out)
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_shadow_light_direction refused its arguments")
+    return np.array(out[:], dtype=np.float64)
+
+
+def shadow_local_direction(earth, direction, lat, lon, lib=None):
+    """atmrt_shadow_local_direction (host code, no device): (azimuth_deg, elevation_deg) of the world-frame light `direction` in
+    the local frame of (lat, lon) — the function the kernel runs."""
+    lib = lib or _lib.load()
+    d = (C.c_double * 3)(*[float(v) for v in direction])
+    az, el = C.c_double(), C.c_double()
+    rc = lib.atmrt_shadow_local_direction(C.byref(earth), d, float(lat), float(lon), C.byref(az), C.byref(el))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_shadow_local_direction refused its arguments")
+    return az.value, el.value
+
+
+def lights_from_angles(params_pod, rows, lib=None):
+    """rows of (azimuth_deg, elevation_deg) as seen from the observer of `params_pod` -> dirs [n][3], world frame."""
+    pos = params_pod.position
+    return np.array([shadow_light_direction(params_pod.earth, pos.latitude, pos.longitude, az, el, lib) for az, el in rows],
+                    dtype=np.float64).reshape(-1, 3)
+
+
+def shadow_lights_spec(dirs, reach, lift=0.0):
+    """-> (_abi.ShadowLightsSpec, dirs [n][3] f64 contiguous): the array must outlive the spec, which borrows it."""
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    spec = _abi.ShadowLightsSpec(dirs.ctypes.data_as(C.POINTER(C.c_double)), dirs.shape[0], 0, float(reach), float(lift))
+    return spec, dirs
+
+
+def shadow_lights(ctx, dirs, reach, lift=0.0, status=False, block=False, width=None, height=None, mask=True):
+    """atmrt_shadow_lights over the frame of the last generate() on `ctx`, in the setting now on the context.  dirs: [n_lights][3]
+    world-frame vectors toward the lights (lights_from_angles, or a coloring's light_dir).  Returns a ShadowLights."""
+    spec, dirs = shadow_lights_spec(dirs, reach, lift)
+    if width is None or height is None:
+        p = ctx_params(ctx)
+        width, height = int(p.width), int(p.height)
+    n = dirs.shape[0]
+    lit = np.zeros((height, width), dtype=np.uint64) if mask else None
+    sta = np.zeros((n, height, width), dtype=np.uint8) if status else None
+    blk = np.zeros((n, height, width), dtype=np.uint16) if block else None
+    st = _abi.ShadowStats()
+    ctx.check(ctx.lib.atmrt_shadow_lights(ctx.handle, C.byref(spec), *[None if a is None else a.ctypes.data for a in (lit, sta, blk)], C.byref(st)))
+    return ShadowLights(lit, sta, blk, _shadow_stats(st), dirs)
+
+
 def shadow_timings(ctx):
     """atmrt_last_shadow_timings of the last shadow call on `ctx`."""
     out = (C.c_double * 3)()

@@ -91,6 +91,23 @@ int main(int argc, char** argv) {
       }
       printf("shadow image darker %zu other %zu\n", darker, other);
       if (other) return 6;
+      // the same light and one at 30 degrees in the south-east as world-frame vectors: every point marches in its own local direction
+      const atmrt_position_t& at = pod.position;
+      const std::vector<std::array<double, 3>> lights = {shadow_light_direction(pod.earth, at.latitude, at.longitude, 260.0, 2.0),
+                                                         shadow_light_direction(pod.earth, at.latitude, at.longitude, 135.0, 30.0)};
+      const std::pair<double, double> seen = shadow_local_direction(pod.earth, lights[0], at.latitude, at.longitude);
+      if (std::fabs(seen.first + 100.0) > 1e-9 || std::fabs(seen.second - 2.0) > 1e-9) return 7; // atan2 returns -100 for 260
+      const ShadowLights sl = shadow_lights(terrain, lights, 20000.0, 0.0, w, h, true, true);
+      for (uint32_t y = 0; y < h; y++) {
+        printf("lights row %u ", y);
+        for (uint32_t x = 0; x < w; x++) {
+          const size_t p = (size_t)y * w + x, q = (size_t)w * h + p;
+          printf("%llu:%d:%u:%d:%u%s", (unsigned long long)sl.lit_mask[p], sl.status[p], sl.block[p], sl.status[q], sl.block[q], x + 1 < w ? "," : "\n");
+        }
+      }
+      printf("lights stats none %llu lit %llu shadowed %llu integrated_steps %llu escaped_rays %llu\n", (unsigned long long)sl.stats.none,
+             (unsigned long long)sl.stats.lit, (unsigned long long)sl.stats.shadowed, (unsigned long long)sl.stats.integrated_steps,
+             (unsigned long long)sl.stats.escaped_rays);
     }
     if (devices.empty()) { // at which angle does the ground 23.7 km to the east appear, and the top of an 1800 m mast on it?  (no frame needed)
       const std::vector<atmrt_sight_t> sights = sight_lines(terrain, {{90.0, 23700.0, 0.0}, {90.0, 23700.0, 1800.0}}, -6.0, 6.0, 3);

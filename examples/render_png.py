@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Render a panorama PNG on the GPU: generator (C ABI) -> renderer::draw_image on the device -> PNG via Pillow.
 Usage: python examples/render_png.py OUT.png [--scene S3] [--width 1024] [--height 512] [--generator Fast] [--objects N]
-       [--shadows [--sun-elevation DEG] [--shadow-reach M]]"""
+       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]]"""
 import argparse
 import os
 import sys
@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--shadows", action="store_true", help="cast shadows from the Shading light (include/atmrt.h, cast shadows)")
     ap.add_argument("--sun-elevation", type=float, default=35.0, help="degrees above the horizon: light_zenith_angle = 90 - this")
     ap.add_argument("--shadow-reach", type=float, default=50_000.0)
+    ap.add_argument("--shadow-per-point", action="store_true",
+                    help="the light is the Shading method's own world-frame vector: every point marches in its own local direction (shadow lights)")
     a = ap.parse_args()
     from PIL import Image
     cfg, tiles = synth.scene(a.scene, a.width, a.height, generator=a.generator, step=100.0, terrain_alpha=a.terrain_alpha)
@@ -43,7 +45,12 @@ def main():
         if a.coloring != "Shading":
             ap.error("--shadows darkens the Shading method's image: use --coloring Shading")
         az, el = generators.light_from_coloring(cfg.params, cfg.coloring["light_zenith_angle"], cfg.coloring["light_dir"])
-        mask = generators.shadow_mask(ctx, (az, el, a.shadow_reach, 0.0), a.width, a.height, block=False)
+        if a.shadow_per_point:  # slopes and shadows share one light: the coloring's light_dir vector
+            light = list(generators.into_coloring(ctx.lib, cfg.params, cfg.coloring).light_dir)
+            mask = generators.shadow_lights(ctx, [light], a.shadow_reach, status=True, width=a.width, height=a.height, mask=False)
+            mask.status = mask.status[0]
+        else:
+            mask = generators.shadow_mask(ctx, (az, el, a.shadow_reach, 0.0), a.width, a.height, block=False)
         shadows = mask.status
         print(f"light at azimuth {az:g}, elevation {el:g}: {mask.stats['lit']} points lit, {mask.stats['shadowed']} in shadow, "
               f"{generators.shadow_timings(ctx)['march_ms']:.2f} ms of shadow march")

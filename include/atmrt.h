@@ -776,7 +776,7 @@ int atmrt_last_horizon_work(atmrt_ctx* ctx, int32_t* batches, int32_t* table_reb
  * the launch elevation angle of the shadow ray, reach [m] > 0, lift [m] >= 0}; elevation_deg is finite and strictly between -90
  * and 90.  SIMPLIFICATION: azimuth_deg and elevation_deg are taken as the same in the local frame of every surface point.  The
  * true local direction of a light at infinity turns with the point's position by distance / R: up to 1.8 degrees over a frame of
- * 200 km.  A direction per point is a later change.  The setting is what the context holds NOW: earth model, simulation_step
+ * 200 km.  The entry points of "shadow lights" below take the direction per point.  The setting is what the context holds NOW: earth model, simulation_step
  * (`step`), straight_rays, atmosphere, terrain.
  *   For pixel p of the last frame with hit_count[p] >= 1 take its FIRST trace point (lat_p, lon_p, elev_p): entry p of the planes,
  *   or entry hit_offset[p] of the lists — whatever the point is, terrain or object: objects receive shadows, they cast none.
@@ -832,6 +832,66 @@ int atmrt_draw_image_shadowed_device(atmrt_ctx* ctx, const atmrt_coloring_t* col
 /* Where the time of the last shadow call on ctx went, in milliseconds between events on the library's stream:
  * out = {compaction (clear and upload included), march, download (statistics, and the planes of atmrt_shadow_mask)}. */
 int atmrt_last_shadow_timings(atmrt_ctx* ctx, double out[3]);
+
+/* ---- shadow lights: a direction per point and a list of lights per call (no reference counterpart) ----------------------------
+ * The cast shadows above without their simplification, and for up to 64 lights in one call: a light is a WORLD-FRAME vector, every
+ * surface point marches toward each light in that light's own local direction at the point, and the answer is a 64-bit mask per
+ * pixel: which lights reach the point.  The atmrt_shadow_mask* calls and their rule stay as they are.
+ *
+ * THE RULE (tests/shadow_lights_model.py restates it in numpy).
+ *   World frame: the frame of EarthModel::world_directions, in which atmrt_coloring_t.light_dir lives: a Shading configuration's
+ *     light_dir can be passed as a light unchanged.
+ *   A light: three doubles (x, y, z), a vector TOWARD the light, all finite; n2 = x*x + y*y + z*z (summed left to right, every
+ *     operation rounded on its own) finite and > 0.  The library normalises once on the host: s = sqrt(n2), L = (x/s, y/s, z/s).
+ *   Local direction at a point (lat, lon): (n, e, u) = world_directions(earth, lat, lon); a = dot(L, n), b = dot(L, e),
+ *     c = dot(L, u) with dot(p, q) = p.x*q.x + p.y*q.y + p.z*q.z, every operation rounded on its own; c' = c > 1 ? 1 : (c < -1 ? -1 : c)
+ *     (a NaN passes through); azimuth_deg = to_degrees(atan2(b, a)), elevation_deg = to_degrees(asin(c')), in the library's
+ *     deterministic functions.  atmrt_shadow_local_direction below IS the function the kernel runs.
+ *   Per (pixel p with hit_count[p] >= 1, light l), decided without a march, in this order: elevation_deg >= 90: LIT, block 0 (a
+ *     height field has nothing straight above a point); otherwise elevation_deg <= -90: SHADOWED, block 1; otherwise elevation_deg
+ *     not strictly inside (-90, 90), that is NaN: LIT, block 0.  Such a pair counts 0 integrated steps.
+ *   Otherwise the rule of "cast shadows" verbatim with THIS point's azimuth_deg and elevation_deg in place of the spec's: the
+ *     lattice d_i and m from reach, the DirectionalCalc at the point, H_0 = elev_p + lift, the stepper, SHADOWED at the first
+ *     1 <= i <= m with H_i < T_i or H_{i-1} < -1000.0, otherwise LIT; the escape shortcut and ATMRT_SHADOW_ESCAPE=off as there
+ *     (nothing in the certificate depends on the launch elevation), and the planes do not depend on it.
+ *   Outputs for 1 <= n_lights <= 64: lit_mask u64 [n_pixels], bit l set iff light l is LIT at p, 0 for a pixel without a trace
+ *     point; optionally status u8 [n_lights][n_pixels] (atmrt_shadow_status) and block u16 [n_lights][n_pixels].  At least one of
+ *     lit_mask and status is required.
+ *   atmrt_shadow_stats_t: none = the pixels without a trace point, counted once; lit + shadowed = hit pixels * n_lights;
+ *     integrated_steps and escaped_rays summed over all pairs.
+ * Equal calls return equal bytes: a lane owns its pixel's mask and writes it once, the counts are integer sums. */
+typedef struct atmrt_shadow_lights_spec {
+  const double* dir; /* [n_lights][3], host memory: vectors toward the lights, world frame, any positive length */
+  uint32_t n_lights; /* 1 .. 64 */
+  uint32_t _pad;
+  double reach;      /* [m], finite, > 0 */
+  double lift;       /* [m], finite, >= 0 */
+} atmrt_shadow_lights_spec_t;
+/* Host code, no context and no device.  A light given as the angles under which it is seen from (lat, lon): with (n, e, u) =
+ * world_directions there, ce = cos(el), se = sin(el), ca = cos(az), sa = sin(az) of the angles in radians (deg * (pi / 180)),
+ * dir[k] = (n[k] * (ce * ca) + e[k] * (ce * sa)) + u[k] * se, every operation rounded on its own.  ATMRT_ERR_INVALID_ARGUMENT: NULL,
+ * an unknown earth model, an argument that is not finite, |elevation_deg| > 90. */
+int atmrt_shadow_light_direction(const atmrt_earth_model_t* earth, double lat, double lon, double azimuth_deg, double elevation_deg,
+                                 double dir[3]);
+/* Host code, no context and no device: the light normalised, then the rule's local direction at (lat, lon) — the function the
+ * kernel runs.  ATMRT_ERR_INVALID_ARGUMENT: NULL, an unknown earth model, a light the rule refuses. */
+int atmrt_shadow_local_direction(const atmrt_earth_model_t* earth, const double dir[3], double lat, double lon, double* azimuth_deg,
+                                 double* elevation_deg);
+/* The planes of the last frame of a single-device context into memory of the context's device; lit_mask_device, status_device and
+ * block_device may each be NULL, but not both of the first two; stats may be NULL.  The frame stays as it is.
+ * ATMRT_ERR_INVALID_ARGUMENT: a NULL spec or dir, n_lights of 0 or above 64, a light the rule refuses, reach or lift as
+ * atmrt_shadow_mask refuses them, m > 65535, neither lit_mask nor status given.  ATMRT_ERR_STATE: as atmrt_shadow_mask. */
+int atmrt_shadow_lights_device(atmrt_ctx* ctx, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask_device, uint8_t* status_device,
+                               uint16_t* block_device, atmrt_shadow_stats_t* stats);
+/* The same into host arrays, staged through a device buffer of n_pixels * (8 + 3 * n_lights) bytes at most (less where a plane is
+ * not asked for). */
+int atmrt_shadow_lights(atmrt_ctx* ctx, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask, uint8_t* status, uint16_t* block,
+                        atmrt_shadow_stats_t* stats);
+/* The same over any planes of n_pixels entries in device memory, as atmrt_shadow_mask_planes_device: what a gathered multi-device
+ * frame uses.  atmrt_last_shadow_timings reports all three calls. */
+int atmrt_shadow_lights_planes_device(atmrt_ctx* ctx, const atmrt_shadow_lights_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
+                                      const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
+                                      uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats);
 
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the

@@ -25,6 +25,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "atmrt.h"
@@ -386,6 +387,39 @@ inline std::vector<uint8_t> draw_image_shadowed(const Terrain& terrain, const at
   std::vector<uint8_t> rgb(3 * (size_t)width * height);
   terrain.check(atmrt_draw_image_shadowed(terrain.ctx(), &coloring, mask.status.data(), rgb.data()));
   return rgb;
+}
+
+// Shadow lights (include/atmrt.h, "shadow lights"): the same march toward each of up to 64 lights given as world-frame vectors, every
+// point in the light's own local direction.  lit_mask [height][width]: bit l set where light l reaches the first trace point;
+// status and block [n_lights][height][width] when asked for.
+struct ShadowLights {
+  std::vector<uint64_t> lit_mask;
+  std::vector<uint8_t> status;
+  std::vector<uint16_t> block;
+  atmrt_shadow_stats_t stats{};
+};
+// a light seen from (lat, lon) under (azimuth_deg, elevation_deg) -> its world-frame vector (host code, no device)
+inline std::array<double, 3> shadow_light_direction(const atmrt_earth_model_t& earth, double lat, double lon, double azimuth_deg, double elevation_deg) {
+  std::array<double, 3> dir{};
+  if (int rc = atmrt_shadow_light_direction(&earth, lat, lon, azimuth_deg, elevation_deg, dir.data())) throw Error(rc, "atmrt_shadow_light_direction refused its arguments");
+  return dir;
+}
+// (azimuth_deg, elevation_deg) of a world-frame light in the local frame of (lat, lon): the function the kernel runs (host code, no device)
+inline std::pair<double, double> shadow_local_direction(const atmrt_earth_model_t& earth, const std::array<double, 3>& dir, double lat, double lon) {
+  std::pair<double, double> out{};
+  if (int rc = atmrt_shadow_local_direction(&earth, dir.data(), lat, lon, &out.first, &out.second)) throw Error(rc, "atmrt_shadow_local_direction refused its arguments");
+  return out;
+}
+inline ShadowLights shadow_lights(const Terrain& terrain, const std::vector<std::array<double, 3>>& dirs, double reach, double lift, uint32_t width,
+                                  uint32_t height, bool status = false, bool block = false) {
+  ShadowLights out;
+  const size_t n = (size_t)width * height;
+  out.lit_mask.resize(n);
+  if (status) out.status.resize(n * dirs.size());
+  if (block) out.block.resize(n * dirs.size());
+  const atmrt_shadow_lights_spec_t spec{dirs.empty() ? nullptr : dirs[0].data(), (uint32_t)dirs.size(), 0, reach, lift};
+  terrain.check(atmrt_shadow_lights(terrain.ctx(), &spec, out.lit_mask.data(), status ? out.status.data() : nullptr, block ? out.block.data() : nullptr, &out.stats));
+  return out;
 }
 
 } // namespace atmrt_host
