@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -21,11 +22,8 @@
 #include "atmrt_hostmem.h"
 #include "atmrt_kernels.h"
 #include "atmrt_multi.h"
+#include "atmrt_polar_plan.h"
 #include "atmrt_render.h"
-#include "atmrt_sight.h"
-#include "atmrt_viewshed.h"
-#include "atmrt_viewshed_map.h"
-#include "atmrt_horizon.h"
 #include "atmrt_shadow.h"
 #include "atmrt_tiff.h"
 
@@ -863,7 +861,7 @@ static int upload_objects(atmrt_ctx* c) {
   });
 }
 
-static int prepare_frame(atmrt_ctx* c, Frame* out) {
+int atmrt::prepare_frame(atmrt_ctx* c, Frame* out) {
   if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_set_params has not been called");
   HIP_TRY(c, hipSetDevice(c->device));
   int rc = upload_terrain(c);
@@ -2073,621 +2071,6 @@ extern "C" int atmrt_landmark_index_probe(const atmrt_landmark_t* landmarks, siz
 }
 
 // ---------------------------------------------------------------------------------------------
-// sight lines (include/atmrt.h; kernels in atmrt_sight.h)
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_sight_fan_angles(double lo, double hi, double out[64]) {
-  if (!out) return ATMRT_ERR_INVALID_ARGUMENT;
-  const double delta = sight_fan_delta(lo, hi);
-  for (int k = 0; k < SIGHT_FAN; k++) out[k] = sight_fan_angle(lo, delta, k);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_sight_pick(const uint8_t fails[64], int32_t* k_star) {
-  if (!fails || !k_star) return ATMRT_ERR_INVALID_ARGUMENT;
-  unsigned long long mask = 0;
-  for (int k = 0; k < SIGHT_FAN; k++)
-    if (fails[k]) mask |= 1ull << k;
-  *k_star = sight_pick(mask);
-  return ATMRT_OK;
-}
-
-namespace {
-
-// The call's sample lattice on the host: d_i by repeated addition as far as the farthest target, and every target's m.
-struct SightPlan {
-  std::vector<double> dtab;
-  std::vector<SightMeta> meta; // off counts from the start of the target's batch
-  std::vector<size_t> batch_begin; // first target of every batch, and n at the end
-  size_t entries_max = 0;          // profile entries of the largest batch
-};
-
-const char* sight_target_check(const atmrt_sight_target_t& t) {
-  if (!std::isfinite(t.azimuth_deg)) return "a target's azimuth_deg is not finite";
-  if (!(std::isfinite(t.distance) && t.distance > 0.0)) return "a target's distance must be finite and positive";
-  if (!(std::isfinite(t.height) && t.height >= 0.0)) return "a target's height must be finite and not negative";
-  return nullptr;
-}
-
-// everything a batch carves from d_sight; dtab first, so that it stays where the call put it
-template <class Out>
-void sight_carve(Carve& k, size_t n_dtab, size_t nb, size_t n_prof, size_t n_out, atmrt_sight_target_t*& targets, SightMeta*& meta,
-                 SightBatch& b, double*& dtab, Out*& out, double*& angles, size_t n_angles) {
-  k(dtab, n_dtab * sizeof(double)), k(b.alt, sizeof(double));
-  k(targets, nb * sizeof(atmrt_sight_target_t)), k(meta, nb * sizeof(SightMeta)), k(b.calc, nb * sizeof(DirCalc));
-  k(b.T, n_prof * sizeof(double)), k(b.lat, n_prof * sizeof(double)), k(b.lon, n_prof * sizeof(double));
-  k(out, n_out * sizeof(Out)), k(angles, n_angles * sizeof(double));
-}
-
-const char* sight_plan(const atmrt_ctx* c, const atmrt_sight_target_t* targets, size_t n, size_t limit, SightPlan& plan) {
-  const double step = c->params.simulation_step;
-  if (!(step > 0.0)) return "simulation_step must be positive";
-  double far = 0.0;
-  for (size_t t = 0; t < n; t++) {
-    if (const char* msg = sight_target_check(targets[t])) return msg;
-    far = std::max(far, targets[t].distance);
-  }
-  plan.dtab.assign(1, 0.0);
-  for (double d = 0.0; d < far;) { // utils.rs:191-196
-    d += step;
-    plan.dtab.push_back(d);
-    if (plan.dtab.size() > (size_t)SIGHT_M_MAX + 1) return "a target lies more than 65535 samples away";
-  }
-  plan.meta.resize(n);
-  plan.batch_begin.assign(1, 0);
-  size_t bytes = 0, entries = 0;
-  for (size_t t = 0; t < n; t++) { // m: the first index with d_m >= distance (the table ascends: step > 0)
-    const int m = (int)(std::lower_bound(plan.dtab.begin(), plan.dtab.end(), targets[t].distance) - plan.dtab.begin());
-    const size_t add = sight_target_bytes(m);
-    if (bytes && bytes + add > limit) { // a batch holds at least one target
-      plan.batch_begin.push_back(t);
-      bytes = entries = 0;
-    }
-    plan.meta[t] = SightMeta{entries, m, 0};
-    bytes += add, entries += (size_t)m + 1;
-    plan.entries_max = std::max(plan.entries_max, entries);
-  }
-  plan.batch_begin.push_back(n);
-  return nullptr;
-}
-
-size_t sight_scratch_limit() { // read at call time: tests lower it to force several batches
-  const char* e = getenv("ATMRT_SIGHT_SCRATCH_BYTES");
-  const long long v = e ? atoll(e) : 0;
-  return v > 0 && (size_t)v < SIGHT_SCRATCH_BYTES ? (size_t)v : SIGHT_SCRATCH_BYTES;
-}
-
-int sight_check_state(atmrt_ctx* c, const char* what) {
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "%s solves on one device: a multi-device context has none of its own", what);
-  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
-  return ATMRT_OK;
-}
-
-} // namespace
-
-extern "C" int atmrt_sight_lines(atmrt_ctx* c, const atmrt_sight_target_t* targets, size_t n, double fan_lo_deg, double fan_hi_deg,
-                                 int32_t rounds, atmrt_sight_t* out) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!targets || !out) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "targets or out is NULL");
-  if (n == 0 || n > SIGHT_N_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "the number of targets must lie in [1, 65536]");
-  if (!(std::isfinite(fan_lo_deg) && std::isfinite(fan_hi_deg) && fan_lo_deg < fan_hi_deg && fan_hi_deg - fan_lo_deg <= 180.0))
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "the fan must be finite, increasing and at most 180 degrees wide");
-  if (rounds < 1 || rounds > 4) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "rounds must lie in [1, 4]");
-  if (int rc = sight_check_state(c, "atmrt_sight_lines")) return rc;
-  SightPlan plan;
-  if (const char* msg = sight_plan(c, targets, n, sight_scratch_limit(), plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  Frame f;
-  if (int rc = prepare_frame(c, &f)) return rc;
-  hipStream_t s = c->stream;
-  const size_t n_dtab = plan.dtab.size(), n_batches = plan.batch_begin.size() - 1;
-  size_t nb_max = 0;
-  for (size_t k = 0; k < n_batches; k++) nb_max = std::max(nb_max, plan.batch_begin[k + 1] - plan.batch_begin[k]);
-  // reserved once for the largest batch (every array at its largest), carved again by every batch: dtab keeps its place
-  atmrt_sight_target_t* d_targets = nullptr;
-  SightMeta* d_meta = nullptr;
-  SightBatch b{};
-  double *d_dtab = nullptr, *d_none = nullptr;
-  atmrt_sight_t* d_out = nullptr;
-  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { sight_carve(k, n_dtab, nb_max, plan.entries_max, nb_max, d_targets, d_meta, b, d_dtab, d_out, d_none, 0); }));
-  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
-  double ms_sum[3] = {};
-  for (size_t k = 0; k < n_batches; k++) {
-    const size_t t0 = plan.batch_begin[k], nb = plan.batch_begin[k + 1] - t0;
-    const size_t entries = (size_t)plan.meta[t0 + nb - 1].off + plan.meta[t0 + nb - 1].m + 1;
-    int m_max = 0;
-    for (size_t t = t0; t < t0 + nb; t++) m_max = std::max(m_max, plan.meta[t].m);
-    Carve carve(c->d_sight.ptr);
-    sight_carve(carve, n_dtab, nb, entries, nb, d_targets, d_meta, b, d_dtab, d_out, d_none, 0);
-    b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
-    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_BEGIN], s));
-    HIP_TRY(c, hipMemcpyAsync(d_targets, targets + t0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_meta, plan.meta.data() + t0, nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
-    launch_sight_profile(f, b, m_max, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_PROFILED], s));
-    launch_sight_solve(f, b, fan_lo_deg, fan_hi_deg, rounds, d_out, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_SOLVED], s));
-    HIP_TRY(c, hipMemcpyAsync(out + t0, d_out, nb * sizeof(atmrt_sight_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipEventRecord(c->ev[EV_SIGHT_END], s));
-    HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes (and reads the host arrays again)
-    HIP_TRY(c, hipGetLastError());
-    for (int i = 0; i < 3; i++) {
-      float ms = 0.0f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_SIGHT_BEGIN + i], c->ev[EV_SIGHT_BEGIN + i + 1]));
-      ms_sum[i] += ms;
-    }
-  }
-  memcpy(c->sight_timings, ms_sum, sizeof ms_sum);
-  c->sight_batches = (int32_t)n_batches;
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_sight_fan_probe(atmrt_ctx* c, const atmrt_sight_target_t* target, size_t n_angles, const double* angles_deg,
-                                     atmrt_sight_ray_t* rays) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!target || !angles_deg || !rays) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "target, angles_deg or rays is NULL");
-  if (n_angles == 0 || n_angles > SIGHT_PROBE_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "the number of angles must lie in [1, 4096]");
-  if (int rc = sight_check_state(c, "atmrt_sight_fan_probe")) return rc;
-  SightPlan plan;
-  if (const char* msg = sight_plan(c, target, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  Frame f;
-  if (int rc = prepare_frame(c, &f)) return rc;
-  hipStream_t s = c->stream;
-  const size_t n_dtab = plan.dtab.size(), entries = (size_t)plan.meta[0].m + 1;
-  atmrt_sight_target_t* d_targets = nullptr;
-  SightMeta* d_meta = nullptr;
-  SightBatch b{};
-  double *d_dtab = nullptr, *d_angles = nullptr;
-  atmrt_sight_ray_t* d_rays = nullptr;
-  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { sight_carve(k, n_dtab, 1, entries, n_angles, d_targets, d_meta, b, d_dtab, d_rays, d_angles, n_angles); }));
-  b.n = 1, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
-  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d_targets, target, sizeof *target, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d_meta, plan.meta.data(), sizeof(SightMeta), hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d_angles, angles_deg, n_angles * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_sight_profile(f, b, plan.meta[0].m, s);
-  launch_sight_probe(f, b, n_angles, d_angles, d_rays, s);
-  HIP_TRY(c, hipMemcpyAsync(rays, d_rays, n_angles * sizeof(atmrt_sight_ray_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_last_sight_timings(atmrt_ctx* c, double out[3]) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  memcpy(out, c->sight_timings, sizeof c->sight_timings);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_last_sight_batches(atmrt_ctx* c, int32_t* batches) {
-  if (!c || !batches) return ATMRT_ERR_INVALID_ARGUMENT;
-  *batches = c->sight_batches;
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// viewshed (include/atmrt.h; kernels in atmrt_viewshed.h)
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_viewshed_fan_angles(double lo, double hi, int32_t fan_rays, double* out) {
-  if (!out || !viewshed_fan_rays_ok(fan_rays) || !std::isfinite(lo) || !std::isfinite(hi)) return ATMRT_ERR_INVALID_ARGUMENT;
-  const double delta = viewshed_fan_delta(lo, hi, fan_rays);
-  for (int k = 0; k < fan_rays; k++) out[k] = sight_fan_angle(lo, delta, k);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_debug_viewshed_shape(int32_t fan_rays, int32_t* az_per_load, int32_t* step_tile, int32_t* rays_per_lane) {
-  if (az_per_load) *az_per_load = VIEWSHED_AZ;
-  if (step_tile) *step_tile = VIEWSHED_TILE;
-  if (rays_per_lane) *rays_per_lane = viewshed_fan_rays_ok(fan_rays) ? viewshed_rays_per_lane(fan_rays) : 0;
-  return ATMRT_OK;
-}
-
-namespace {
-
-// everything a batch of nb azimuths carves from d_sight: the sight lines' layout (dtab first: it stays where the call put it), then
-// the planes of the host route and of the map (`staged`: null pointers where the caller asked for none; of `asked` only which
-// pointers are null matters)
-void viewshed_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, const ViewshedPlanes& asked, bool stage, atmrt_sight_target_t*& targets,
-                    SightMeta*& meta, SightBatch& b, double*& dtab, ViewshedPlanes& staged) {
-  double* none = nullptr;
-  uint8_t* out = nullptr;
-  sight_carve(k, n_dtab, nb, nb * (m + 1), 0, targets, meta, b, dtab, out, none, 0);
-  staged = ViewshedPlanes{};
-  if (!stage) return;
-  const size_t cells = nb * m;
-  if (asked.k_star) k(staged.k_star, cells * 2);
-  k(staged.status, cells), k(staged.hidden, cells * 8);
-  if (asked.block_index) k(staged.block_index, cells * 4);
-  if (asked.ground) k(staged.ground, cells * 8);
-  if (asked.lat) k(staged.lat, cells * 8);
-  if (asked.lon) k(staged.lon, cells * 8);
-}
-
-// What the viewshed and the horizon refuse alike, and what both begin with: the lattice, and one target per azimuth, through the
-// sight lines' own plan (every target's m is the call's, plan.meta[0].m).
-int polar_call_plan(atmrt_ctx* c, const char* what, double az_lo_deg, double az_step_deg, int32_t n_az, double reach, double height, double fan_lo_deg,
-                    double fan_hi_deg, int32_t fan_rays, std::vector<atmrt_sight_target_t>& targets, SightPlan& plan) {
-  if (!(std::isfinite(az_lo_deg) && std::isfinite(az_step_deg))) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: az_lo_deg and az_step_deg must be finite", what);
-  if (n_az < 1 || (size_t)n_az > VIEWSHED_N_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_az must lie in [1, 65536]", what);
-  if (!viewshed_fan_rays_ok(fan_rays)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: fan_rays must be a multiple of 64 in [64, 4096]", what);
-  if (!(std::isfinite(fan_lo_deg) && std::isfinite(fan_hi_deg) && fan_lo_deg < fan_hi_deg && fan_hi_deg - fan_lo_deg <= 180.0))
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the fan must be finite, increasing and at most 180 degrees wide", what);
-  if (int rc = sight_check_state(c, what)) return rc;
-  targets.resize((size_t)n_az);
-  for (int32_t j = 0; j < n_az; j++) targets[j] = atmrt_sight_target_t{az_lo_deg + (double)j * az_step_deg, reach, height};
-  if (!std::isfinite(targets.back().azimuth_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the last azimuth is not finite", what);
-  {
-    const atmrt_sight_target_t first = targets[0]; // reach and height are the same for every azimuth: checked once, with the lattice
-    if (const char* msg = sight_plan(c, &first, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
-  }
-  const size_t table_bytes = ((size_t)plan.meta[0].m + 1) * (size_t)fan_rays * sizeof(double);
-  if (table_bytes > SIGHT_SCRATCH_BYTES)
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the path table of (m + 1) * K * 8 = %zu bytes exceeds the scratch limit of %zu", what, table_bytes, SIGHT_SCRATCH_BYTES);
-  return ATMRT_OK;
-}
-
-// The path table H[i][k] of the fan, the one product of both calls under the one key: built where the key differs from the last
-// build's.  *ms: what the build took between EV_VS_BEGIN and EV_VS_PATHS, 0 when the table was found.
-int viewshed_paths_refresh(atmrt_ctx* c, const Frame& f, double fan_lo_deg, double fan_hi_deg, int K, int m, bool* rebuilt, double* ms_paths) {
-  hipStream_t s = c->stream;
-  const atmrt_position_t& pos = c->params.position;
-  const ViewshedKey key{c->atm.serial(), c->terrain_uploaded, pos.altitude_kind, bits(pos.latitude), bits(pos.longitude), bits(pos.altitude),
-                        bits(fan_lo_deg), bits(fan_hi_deg), bits(c->params.simulation_step), K, m, c->params.straight_rays ? 1 : 0, key_of(c->earth)};
-  *ms_paths = 0.0;
-  HIP_TRY(c, hipEventRecord(c->ev[EV_VS_BEGIN], s));
-  int rc = c->viewshed_paths.refresh(key, [&](Nothing&) -> int {
-    HIP_TRY(c, c->d_viewshed_paths.reserve(((size_t)m + 1) * (size_t)K * sizeof(double)));
-    launch_viewshed_paths(f, fan_lo_deg, fan_hi_deg, K, m, c->d_viewshed_paths.as<double>(), s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_PATHS], s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    return ATMRT_OK;
-  }, false, rebuilt);
-  if (rc) return rc;
-  if (*rebuilt) {
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_VS_BEGIN], c->ev[EV_VS_PATHS]));
-    *ms_paths = ms;
-  }
-  return ATMRT_OK;
-}
-
-// The map a fused call scatters its batches into (atmrt_viewshed_map*): device planes on c's device.
-struct ViewshedMapSink {
-  atmrt_geo_grid_t grid;
-  VsMapPlanes planes;
-  bool accumulate;
-  atmrt_viewshed_map_stats_t* stats; // may be null
-};
-
-// The checks the three map entry points share; 0 or a status with the message set.
-int viewshed_map_check(atmrt_ctx* c, const char* what, const atmrt_geo_grid_t* grid, const void* n_samples, const void* n_seen) {
-  if (!grid || !n_samples || !n_seen) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: grid, n_samples or n_seen is NULL", what);
-  if (const char* msg = geo_grid_check(*grid)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
-  return ATMRT_OK;
-}
-
-// The call's statistics block, read back once every scatter of the call has run.
-int viewshed_map_stats(atmrt_ctx* c, atmrt_viewshed_map_stats_t* stats) {
-  uint64_t block[VSMAP_N] = {};
-  HIP_TRY(c, hipMemcpyAsync(block, c->d_vsmap.ptr, sizeof block, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  if (stats) *stats = atmrt_viewshed_map_stats_t{block[VSMAP_SAMPLES], block[VSMAP_BINNED], block[VSMAP_OUTSIDE], block[VSMAP_SKIPPED], block[VSMAP_SEEN]};
-  return ATMRT_OK;
-}
-
-// map == nullptr: the viewshed into dst (host arrays, or device_planes).  map != nullptr: dst is empty; every batch's status, hidden,
-// lat and lon are staged in d_sight like the host route's planes and scattered into the map where the host route downloads.
-int viewshed_run(atmrt_ctx* c, const char* what, const atmrt_viewshed_spec_t* spec, const ViewshedPlanes& dst_in, bool device_planes,
-                 const ViewshedMapSink* map = nullptr) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  static double mark; // a plane the map asks of the scan: only that the pointer is not null matters
-  const ViewshedPlanes dst = map ? ViewshedPlanes{nullptr, reinterpret_cast<uint8_t*>(&mark), &mark, nullptr, nullptr, &mark, &mark} : dst_in;
-  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
-  if (!map && (!dst.k_star || !dst.status || !dst.hidden)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec, k_star, status or hidden is NULL", what);
-  const atmrt_viewshed_spec_t v = *spec;
-  std::vector<atmrt_sight_target_t> targets;
-  SightPlan plan;
-  if (int rc = polar_call_plan(c, what, v.az_lo_deg, v.az_step_deg, v.n_az, v.reach, v.height, v.fan_lo_deg, v.fan_hi_deg, v.fan_rays, targets, plan)) return rc;
-  const size_t cell = device_planes ? 0 : viewshed_cell_bytes(dst);
-  const int m = plan.meta[0].m;
-  const int K = v.fan_rays;
-  // azimuths of a batch: what one adds is its profile (sight_target_bytes) and, on the host route, its cells of the staged planes;
-  // then as many fewer as it takes for the whole layout — distance table, altitude and every array's padding included — to stay
-  // under the limit (a batch holds at least one azimuth)
-  const size_t per_az = sight_target_bytes(m) + cell * (size_t)m, limit = sight_scratch_limit();
-  const auto layout_bytes = [&](size_t nb) {
-    Carve k(nullptr);
-    atmrt_sight_target_t* t = nullptr;
-    SightMeta* me = nullptr;
-    SightBatch sb{};
-    double* dt = nullptr;
-    ViewshedPlanes st{};
-    viewshed_carve(k, (size_t)m + 1, nb, (size_t)m, dst, !device_planes, t, me, sb, dt, st);
-    return k.bytes;
-  };
-  size_t nb_max = std::min((size_t)v.n_az, std::max<size_t>(1, limit / per_az));
-  while (nb_max > 1 && layout_bytes(nb_max) > limit) nb_max--;
-  Frame f;
-  if (int rc = prepare_frame(c, &f)) return rc;
-  hipStream_t s = c->stream;
-  bool rebuilt = false;
-  double ms_sum[4] = {};
-  if (int rc = viewshed_paths_refresh(c, f, v.fan_lo_deg, v.fan_hi_deg, K, m, &rebuilt, &ms_sum[0])) return rc;
-  const size_t n_dtab = (size_t)m + 1;
-  atmrt_sight_target_t* d_targets = nullptr;
-  SightMeta* d_meta = nullptr;
-  SightBatch b{};
-  double* d_dtab = nullptr;
-  ViewshedPlanes staged{};
-  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { viewshed_carve(k, n_dtab, nb_max, (size_t)m, dst, !device_planes, d_targets, d_meta, b, d_dtab, staged); }));
-  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
-  std::vector<SightMeta> meta(nb_max);
-  for (size_t t = 0; t < nb_max; t++) meta[t] = SightMeta{t * ((size_t)m + 1), m, 0};
-  if (map) {
-    HIP_TRY(c, c->d_vsmap.reserve(VSMAP_N * sizeof(uint64_t)));
-    launch_vsmap_reset(c->d_vsmap.ptr, s);
-    if (!map->accumulate) launch_vsmap_clear(map->grid, map->planes, s);
-  }
-  size_t n_batches = 0;
-  for (size_t j0 = 0; j0 < (size_t)v.n_az; j0 += nb_max, n_batches++) {
-    const size_t nb = std::min(nb_max, (size_t)v.n_az - j0), cells = nb * (size_t)m, at = j0 * (size_t)m;
-    Carve carve(c->d_sight.ptr);
-    viewshed_carve(carve, n_dtab, nb, (size_t)m, dst, !device_planes, d_targets, d_meta, b, d_dtab, staged);
-    b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
-    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_BATCH], s));
-    HIP_TRY(c, hipMemcpyAsync(d_targets, targets.data() + j0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_meta, meta.data(), nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
-    launch_sight_profile(f, b, m, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_PROFILED], s));
-    ViewshedScan scan{};
-    scan.n = (int32_t)nb, scan.m = m, scan.K = K, scan.height = v.height;
-    scan.H = c->d_viewshed_paths.as<double>();
-    scan.T = b.T, scan.lat = b.lat, scan.lon = b.lon;
-    if (device_planes) {
-      scan.out = ViewshedPlanes{dst.k_star + at, dst.status + at, dst.hidden + at, dst.block_index ? dst.block_index + at : nullptr,
-                                dst.ground ? dst.ground + at : nullptr, dst.lat ? dst.lat + at : nullptr, dst.lon ? dst.lon + at : nullptr};
-    } else {
-      scan.out = staged;
-    }
-    launch_viewshed_scan(scan, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_SCANNED], s));
-    if (map) {
-      launch_vsmap_scatter(VsMapSamples{cells, staged.status, staged.hidden, staged.lat, staged.lon}, map->grid, map->planes, c->d_vsmap.ptr, s);
-    } else if (!device_planes) {
-      HIP_TRY(c, hipMemcpyAsync(dst.k_star + at, staged.k_star, cells * 2, hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipMemcpyAsync(dst.status + at, staged.status, cells, hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipMemcpyAsync(dst.hidden + at, staged.hidden, cells * 8, hipMemcpyDeviceToHost, s));
-      if (dst.block_index) HIP_TRY(c, hipMemcpyAsync(dst.block_index + at, staged.block_index, cells * 4, hipMemcpyDeviceToHost, s));
-      if (dst.ground) HIP_TRY(c, hipMemcpyAsync(dst.ground + at, staged.ground, cells * 8, hipMemcpyDeviceToHost, s));
-      if (dst.lat) HIP_TRY(c, hipMemcpyAsync(dst.lat + at, staged.lat, cells * 8, hipMemcpyDeviceToHost, s));
-      if (dst.lon) HIP_TRY(c, hipMemcpyAsync(dst.lon + at, staged.lon, cells * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[EV_VS_END], s));
-    HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes
-    HIP_TRY(c, hipGetLastError());
-    for (int i = 0; i < 3; i++) {
-      float ms = 0.0f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_VS_BATCH + i], c->ev[EV_VS_BATCH + i + 1]));
-      ms_sum[1 + i] += ms;
-    }
-  }
-  memcpy(c->viewshed_timings, ms_sum, sizeof ms_sum);
-  c->viewshed_batches = (int32_t)n_batches;
-  c->viewshed_rebuilt = rebuilt ? 1 : 0;
-  if (map) return viewshed_map_stats(c, map->stats);
-  return ATMRT_OK;
-}
-
-} // namespace
-
-extern "C" int atmrt_viewshed_steps(atmrt_ctx* c, double reach, int32_t* m) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!m) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_viewshed_steps: m is NULL");
-  if (int rc = sight_check_state(c, "atmrt_viewshed_steps")) return rc;
-  const atmrt_sight_target_t t{0.0, reach, 0.0};
-  SightPlan plan;
-  if (const char* msg = sight_plan(c, &t, 1, SIGHT_SCRATCH_BYTES, plan)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_viewshed_steps: %s", msg);
-  *m = plan.meta[0].m;
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_viewshed(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, uint16_t* k_star, uint8_t* status, double* hidden,
-                              int32_t* block_index, double* ground, double* lat, double* lon) {
-  return viewshed_run(c, "atmrt_viewshed", spec, ViewshedPlanes{k_star, status, hidden, block_index, ground, lat, lon}, false);
-}
-
-extern "C" int atmrt_viewshed_device(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, uint16_t* k_star, uint8_t* status, double* hidden,
-                                     int32_t* block_index, double* ground, double* lat, double* lon) {
-  return viewshed_run(c, "atmrt_viewshed_device", spec, ViewshedPlanes{k_star, status, hidden, block_index, ground, lat, lon}, true);
-}
-
-extern "C" int atmrt_last_viewshed_timings(atmrt_ctx* c, double out[4]) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  memcpy(out, c->viewshed_timings, sizeof c->viewshed_timings);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_last_viewshed_work(atmrt_ctx* c, int32_t* batches, int32_t* table_rebuilt) {
-  if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
-  *batches = c->viewshed_batches;
-  *table_rebuilt = c->viewshed_rebuilt;
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// viewshed map (include/atmrt.h; kernels in atmrt_viewshed_map.h)
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_viewshed_map_planes_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, size_t n, const uint8_t* status, const double* hidden,
-                                                const double* lat, const double* lon, int32_t accumulate, uint32_t* n_samples, uint32_t* n_seen,
-                                                double* min_hidden, atmrt_viewshed_map_stats_t* stats) {
-  const char* what = "atmrt_viewshed_map_planes_device";
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = viewshed_map_check(c, what, grid, n_samples, n_seen)) return rc;
-  if (n > VSMAP_SAMPLES_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n exceeds (2^31 - 1) * 256 samples", what);
-  if (n && (!status || !hidden || !lat || !lon)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: status, hidden, lat or lon is NULL", what);
-  if (int rc = sight_check_state(c, what)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const VsMapPlanes map{n_samples, n_seen, min_hidden};
-  HIP_TRY(c, c->d_vsmap.reserve(VSMAP_N * sizeof(uint64_t)));
-  launch_vsmap_reset(c->d_vsmap.ptr, s);
-  if (!accumulate) launch_vsmap_clear(*grid, map, s);
-  launch_vsmap_scatter(VsMapSamples{n, status, hidden, lat, lon}, *grid, map, c->d_vsmap.ptr, s);
-  return viewshed_map_stats(c, stats);
-}
-
-extern "C" int atmrt_viewshed_map_device(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, const atmrt_geo_grid_t* grid, int32_t accumulate,
-                                         uint32_t* n_samples, uint32_t* n_seen, double* min_hidden, atmrt_viewshed_map_stats_t* stats) {
-  const char* what = "atmrt_viewshed_map_device";
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
-  if (int rc = viewshed_map_check(c, what, grid, n_samples, n_seen)) return rc;
-  const ViewshedMapSink sink{*grid, VsMapPlanes{n_samples, n_seen, min_hidden}, accumulate != 0, stats};
-  return viewshed_run(c, what, spec, ViewshedPlanes{}, false, &sink);
-}
-
-extern "C" int atmrt_viewshed_map(atmrt_ctx* c, const atmrt_viewshed_spec_t* spec, const atmrt_geo_grid_t* grid, int32_t accumulate,
-                                  uint32_t* n_samples, uint32_t* n_seen, double* min_hidden, atmrt_viewshed_map_stats_t* stats) {
-  const char* what = "atmrt_viewshed_map";
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
-  if (int rc = viewshed_map_check(c, what, grid, n_samples, n_seen)) return rc;
-  if (int rc = sight_check_state(c, what)) return rc; // before the staging buffer is touched
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n_cells = (size_t)grid->n_lat * grid->n_lon, count_bytes = Carve::pad(n_cells * sizeof(uint32_t));
-  HIP_TRY(c, c->d_io.reserve(2 * count_bytes + n_cells * sizeof(double)));
-  uint32_t *d_samples = c->d_io.as<uint32_t>(), *d_seen = reinterpret_cast<uint32_t*>(c->d_io.as<char>() + count_bytes);
-  double* d_min = min_hidden ? reinterpret_cast<double*>(c->d_io.as<char>() + 2 * count_bytes) : nullptr;
-  if (accumulate) {
-    HIP_TRY(c, hipMemcpy(d_samples, n_samples, n_cells * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d_seen, n_seen, n_cells * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (min_hidden) HIP_TRY(c, hipMemcpy(d_min, min_hidden, n_cells * sizeof(double), hipMemcpyHostToDevice));
-  }
-  const ViewshedMapSink sink{*grid, VsMapPlanes{d_samples, d_seen, d_min}, accumulate != 0, stats};
-  if (int rc = viewshed_run(c, what, spec, ViewshedPlanes{}, false, &sink)) return rc;
-  HIP_TRY(c, hipMemcpy(n_samples, d_samples, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(n_seen, d_seen, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (min_hidden) HIP_TRY(c, hipMemcpy(min_hidden, d_min, n_cells * sizeof(double), hipMemcpyDeviceToHost));
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// horizon (include/atmrt.h; kernels in atmrt_horizon.h)
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_debug_horizon_shape(int32_t fan_rays, int32_t* az_per_load, int32_t* step_tile, int32_t* rays_per_lane) {
-  if (az_per_load) *az_per_load = HORIZON_AZ;
-  if (step_tile) *step_tile = HORIZON_TILE;
-  if (rays_per_lane) *rays_per_lane = viewshed_fan_rays_ok(fan_rays) ? horizon_rays_per_lane(fan_rays) : 0;
-  return ATMRT_OK;
-}
-
-namespace {
-
-// everything a batch of nb azimuths carves from d_sight: the sight lines' layout (dtab first: it stays where the call put it), with
-// the records of the host route where the sight lines have theirs (`stage`)
-void horizon_carve(Carve& k, size_t n_dtab, size_t nb, size_t m, bool stage, atmrt_sight_target_t*& targets, SightMeta*& meta, SightBatch& b,
-                   double*& dtab, atmrt_horizon_t*& staged) {
-  double* none = nullptr;
-  sight_carve(k, n_dtab, nb, nb * (m + 1), stage ? nb : 0, targets, meta, b, dtab, staged, none, 0);
-  if (!stage) staged = nullptr;
-}
-
-int horizon_run(atmrt_ctx* c, const char* what, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* dst, bool device_out) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!spec || !dst) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or out is NULL", what);
-  const atmrt_horizon_spec_t v = *spec;
-  if (v.rounds < 1 || v.rounds > 4) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: rounds must lie in [1, 4]", what);
-  std::vector<atmrt_sight_target_t> targets;
-  SightPlan plan;
-  if (int rc = polar_call_plan(c, what, v.az_lo_deg, v.az_step_deg, v.n_az, v.reach, 0.0, v.fan_lo_deg, v.fan_hi_deg, v.fan_rays, targets, plan)) return rc;
-  const int m = plan.meta[0].m;
-  const int K = v.fan_rays;
-  // azimuths of a batch, as the viewshed counts them: what one adds is its profile (sight_target_bytes) and, on the host route, its
-  // record; then as many fewer as it takes for the whole layout to stay under the limit (a batch holds at least one azimuth)
-  const size_t per_az = sight_target_bytes(m) + (device_out ? 0 : sizeof(atmrt_horizon_t)), limit = sight_scratch_limit();
-  const size_t n_dtab = (size_t)m + 1;
-  atmrt_sight_target_t* d_targets = nullptr;
-  SightMeta* d_meta = nullptr;
-  SightBatch b{};
-  double* d_dtab = nullptr;
-  atmrt_horizon_t* staged = nullptr;
-  const auto layout_bytes = [&](size_t nb) {
-    Carve k(nullptr);
-    horizon_carve(k, n_dtab, nb, (size_t)m, !device_out, d_targets, d_meta, b, d_dtab, staged);
-    return k.bytes;
-  };
-  size_t nb_max = std::min((size_t)v.n_az, std::max<size_t>(1, limit / per_az));
-  while (nb_max > 1 && layout_bytes(nb_max) > limit) nb_max--;
-  Frame f;
-  if (int rc = prepare_frame(c, &f)) return rc;
-  hipStream_t s = c->stream;
-  bool rebuilt = false;
-  double ms_sum[5] = {};
-  if (int rc = viewshed_paths_refresh(c, f, v.fan_lo_deg, v.fan_hi_deg, K, m, &rebuilt, &ms_sum[0])) return rc;
-  HIP_TRY(c, reserve_carved(c->d_sight, [&](Carve& k) { horizon_carve(k, n_dtab, nb_max, (size_t)m, !device_out, d_targets, d_meta, b, d_dtab, staged); }));
-  HIP_TRY(c, hipMemcpyAsync(d_dtab, plan.dtab.data(), n_dtab * sizeof(double), hipMemcpyHostToDevice, s));
-  std::vector<SightMeta> meta(nb_max);
-  for (size_t t = 0; t < nb_max; t++) meta[t] = SightMeta{t * ((size_t)m + 1), m, 0};
-  size_t n_batches = 0;
-  for (size_t j0 = 0; j0 < (size_t)v.n_az; j0 += nb_max, n_batches++) {
-    const size_t nb = std::min(nb_max, (size_t)v.n_az - j0);
-    Carve carve(c->d_sight.ptr);
-    horizon_carve(carve, n_dtab, nb, (size_t)m, !device_out, d_targets, d_meta, b, d_dtab, staged);
-    b.n = (int32_t)nb, b.targets = d_targets, b.meta = d_meta, b.dtab = d_dtab;
-    atmrt_horizon_t* const d_out = device_out ? dst + j0 : staged;
-    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_BATCH], s));
-    HIP_TRY(c, hipMemcpyAsync(d_targets, targets.data() + j0, nb * sizeof(atmrt_sight_target_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_meta, meta.data(), nb * sizeof(SightMeta), hipMemcpyHostToDevice, s));
-    launch_sight_profile(f, b, m, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_PROFILED], s));
-    HorizonScan scan{};
-    scan.n = (int32_t)nb, scan.m = m, scan.K = K, scan.lo = v.fan_lo_deg, scan.hi = v.fan_hi_deg;
-    scan.H = c->d_viewshed_paths.as<double>();
-    scan.T = b.T, scan.out = d_out;
-    launch_horizon_scan(scan, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_SCANNED], s));
-    launch_horizon_refine(f, b, v.rounds, d_out, s);
-    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_REFINED], s));
-    if (!device_out) HIP_TRY(c, hipMemcpyAsync(dst + j0, staged, nb * sizeof(atmrt_horizon_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipEventRecord(c->ev[EV_HZ_END], s));
-    HIP_TRY(c, hipStreamSynchronize(s)); // the next batch carves the same bytes
-    HIP_TRY(c, hipGetLastError());
-    for (int i = 0; i < 4; i++) {
-      float ms = 0.0f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[EV_HZ_BATCH + i], c->ev[EV_HZ_BATCH + i + 1]));
-      ms_sum[1 + i] += ms;
-    }
-  }
-  memcpy(c->horizon_timings, ms_sum, sizeof ms_sum);
-  c->horizon_batches = (int32_t)n_batches;
-  c->horizon_rebuilt = rebuilt ? 1 : 0;
-  return ATMRT_OK;
-}
-
-} // namespace
-
-extern "C" int atmrt_horizon(atmrt_ctx* c, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* out) {
-  return horizon_run(c, "atmrt_horizon", spec, out, false);
-}
-
-extern "C" int atmrt_horizon_device(atmrt_ctx* c, const atmrt_horizon_spec_t* spec, atmrt_horizon_t* out) {
-  return horizon_run(c, "atmrt_horizon_device", spec, out, true);
-}
-
-extern "C" int atmrt_last_horizon_timings(atmrt_ctx* c, double out[5]) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  memcpy(out, c->horizon_timings, sizeof c->horizon_timings);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_last_horizon_work(atmrt_ctx* c, int32_t* batches, int32_t* table_rebuilt) {
-  if (!c || !batches || !table_rebuilt) return ATMRT_ERR_INVALID_ARGUMENT;
-  *batches = c->horizon_batches;
-  *table_rebuilt = c->horizon_rebuilt;
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
 // cast shadows: which of a frame's first trace points the light reaches (kernels: atmrt_shadow.h; the rule: include/atmrt.h)
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -2698,34 +2081,32 @@ bool shadow_escape_enabled() {
   return !(e && !strcmp(e, "off"));
 }
 
-// m: the first index with d_m >= reach, d by repeated addition (utils.rs:191-196); 0 or a message
-const char* shadow_steps_of(const atmrt_ctx* c, double reach, int32_t* m) {
-  const double step = c->params.simulation_step;
-  if (!(step > 0.0)) return "simulation_step must be positive";
-  if (!(std::isfinite(reach) && reach > 0.0)) return "reach must be finite and positive";
-  int32_t i = 0;
-  for (double d = 0.0; d < reach;) {
-    d += step;
-    if (++i > SHADOW_M_MAX) return "reach lies more than 65535 samples away";
-  }
-  *m = i;
-  return nullptr;
+// what every shadow entry point asks of reach and lift and of the context's parameters; *m: the samples to reach, the first index
+// with d_m >= reach (atmrt_polar_plan.h).  0 or a status with the message set
+int shadow_reach_check(atmrt_ctx* c, const char* what, double reach, double lift, int32_t* m) {
+  if (!(std::isfinite(reach) && reach > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: reach must be finite and positive", what);
+  if (!(std::isfinite(lift) && lift >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: lift must be finite and not negative", what);
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
+  if (!(c->params.simulation_step > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: simulation_step must be positive", what);
+  const int32_t steps = lattice_steps(c->params.simulation_step, reach, SHADOW_M_MAX);
+  if (steps < 0) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: reach lies more than 65535 samples away", what);
+  *m = steps;
+  return ATMRT_OK;
 }
 
-const char* shadow_spec_check(const atmrt_shadow_spec_t& s) {
-  if (!std::isfinite(s.azimuth_deg)) return "azimuth_deg is not finite";
-  if (!(std::isfinite(s.elevation_deg) && s.elevation_deg > -90.0 && s.elevation_deg < 90.0)) return "elevation_deg must lie strictly between -90 and 90";
-  if (!(std::isfinite(s.reach) && s.reach > 0.0)) return "reach must be finite and positive";
-  if (!(std::isfinite(s.lift) && s.lift >= 0.0)) return "lift must be finite and not negative";
-  return nullptr;
-}
-
-// what every shadow entry point asks of its arguments and of the context's parameters; 0 or a status with the message set
+// what the entry points of one light ask beyond that
 int shadow_check(atmrt_ctx* c, const char* what, const atmrt_shadow_spec_t* spec, const void* status, int32_t* m) {
   if (!spec || !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or status is NULL", what);
-  if (const char* msg = shadow_spec_check(*spec)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
-  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
-  if (const char* msg = shadow_steps_of(c, spec->reach, m)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  if (!std::isfinite(spec->azimuth_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: azimuth_deg is not finite", what);
+  if (!(std::isfinite(spec->elevation_deg) && spec->elevation_deg > -90.0 && spec->elevation_deg < 90.0))
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: elevation_deg must lie strictly between -90 and 90", what);
+  return shadow_reach_check(c, what, spec->reach, spec->lift, m);
+}
+
+// what the two entry points on the caller's planes ask of them
+int shadow_planes_check(atmrt_ctx* c, const char* what, size_t n_pixels, const uint32_t* hit_count, const double* lat, const double* lon, const double* elev) {
+  if (!hit_count || !lat || !lon || !elev) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: a plane is NULL", what);
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must lie in [1, 2^32 - 1]", what);
   return ATMRT_OK;
 }
 
@@ -2748,31 +2129,36 @@ double shadow_escape_floor(const atmrt_ctx* k, Frame& f, double reach) {
   return std::max(k->tv.skip_above, k->escape.value().from + step);
 }
 
-// k: the context whose device holds the memory and whose setting is used; report: the context the caller handed in.  host_status /
-// host_block: where the planes are downloaded to inside the call's timed window (null: none).
-int shadow_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_spec_t& spec, int32_t m, const TracePoints& src, uint8_t* status_dev,
-               uint16_t* block_dev, atmrt_shadow_stats_t* stats, uint8_t* host_status, uint16_t* host_block) {
+struct ShadowDownload { // a plane the host asked for (host null: not this one), downloaded inside the call's timed window
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+
+// One shadow call around its kernels, for a ShadowJob or a ShadowLightsJob with its source, its m and its planes filled in.
+// k: the context whose device holds the memory and whose setting is used; report: the context the caller handed in.
+// carve_more: what the call carves from d_shadow beside the list and the counters; launch: its uploads and its kernels.
+template <class Job>
+int shadow_call(atmrt_ctx* k, atmrt_ctx* report, double reach, Job& job, const std::function<void(Carve&)>& carve_more,
+                const std::function<int(const Frame&, hipStream_t)>& launch, std::initializer_list<ShadowDownload> downloads, atmrt_shadow_stats_t* stats) {
   Frame f;
   if (int rc = prepare_frame(k, &f)) {
     if (k != report) report->error = k->error;
     return rc;
   }
   hipStream_t s = k->stream;
-  ShadowJob job{};
-  job.src = src;
-  job.azimuth_deg = spec.azimuth_deg, job.elevation_deg = spec.elevation_deg, job.lift = spec.lift;
-  job.m = m;
-  job.esc_floor = shadow_escape_floor(k, f, spec.reach);
+  job.esc_floor = shadow_escape_floor(k, f, reach);
   job.escape = job.esc_floor < INFINITY ? 1 : 0;
-  job.status = status_dev, job.block = block_dev;
-  HIP_TRY(report, reserve_carved(k->d_shadow, [&](Carve& cv) { cv(job.list, src.n_pixels * sizeof(uint32_t)), cv(job.ctr, SH_N * sizeof(unsigned long long)); }));
+  HIP_TRY(report, reserve_carved(k->d_shadow, [&](Carve& cv) {
+            cv(job.list, job.src.n_pixels * sizeof(uint32_t)), cv(job.ctr, SH_N * sizeof(unsigned long long)), carve_more(cv);
+          }));
   HIP_TRY(report, hipEventRecord(k->ev[EV_SH_BEGIN], s));
-  launch_shadow_mask(f, job, s, k->ev[EV_SH_COMPACTED]);
+  if (int rc = launch(f, s)) return rc;
   HIP_TRY(report, hipEventRecord(k->ev[EV_SH_MARCHED], s));
   unsigned long long ctr[SH_N] = {};
   HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
-  if (host_status) HIP_TRY(report, hipMemcpyAsync(host_status, status_dev, src.n_pixels, hipMemcpyDeviceToHost, s));
-  if (host_block) HIP_TRY(report, hipMemcpyAsync(host_block, block_dev, src.n_pixels * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+  for (const ShadowDownload& d : downloads)
+    if (d.host) HIP_TRY(report, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(report, hipEventRecord(k->ev[EV_SH_END], s));
   HIP_TRY(report, hipStreamSynchronize(s));
   HIP_TRY(report, hipGetLastError());
@@ -2783,10 +2169,26 @@ int shadow_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_spec_t& spec,
   }
   if (stats) {
     stats->lit = ctr[SH_LIT], stats->shadowed = ctr[SH_SHADOWED];
-    stats->none = src.n_pixels - ctr[SH_LIST];
+    stats->none = job.src.n_pixels - ctr[SH_LIST];
     stats->integrated_steps = ctr[SH_STEPS], stats->escaped_rays = ctr[SH_ESCAPED];
   }
   return ATMRT_OK;
+}
+
+// host_status / host_block: where the planes are downloaded to (null: none).
+int shadow_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_spec_t& spec, int32_t m, const TracePoints& src, uint8_t* status_dev,
+               uint16_t* block_dev, atmrt_shadow_stats_t* stats, uint8_t* host_status, uint16_t* host_block) {
+  ShadowJob job{};
+  job.src = src;
+  job.azimuth_deg = spec.azimuth_deg, job.elevation_deg = spec.elevation_deg, job.lift = spec.lift;
+  job.m = m;
+  job.status = status_dev, job.block = block_dev;
+  return shadow_call(k, report, spec.reach, job, [](Carve&) {},
+                     [&](const Frame& f, hipStream_t s) -> int {
+                       launch_shadow_mask(f, job, s, k->ev[EV_SH_COMPACTED]);
+                       return ATMRT_OK;
+                     },
+                     {{host_status, status_dev, src.n_pixels}, {host_block, block_dev, src.n_pixels * sizeof(uint16_t)}}, stats);
 }
 
 const char* const SHADOW_ON_MULTI = "has no frame of its own: cast shadows work on the gathered planes through atmrt_shadow_mask_planes_device";
@@ -2796,10 +2198,7 @@ const char* const SHADOW_ON_MULTI = "has no frame of its own: cast shadows work 
 extern "C" int atmrt_shadow_steps(atmrt_ctx* c, double reach, int32_t* m) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!m) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: m is NULL");
-  if (!(std::isfinite(reach) && reach > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: reach must be finite and positive");
-  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_shadow_steps: atmrt_set_params has not been called");
-  if (const char* msg = shadow_steps_of(c, reach, m)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: %s", msg);
-  return ATMRT_OK;
+  return shadow_reach_check(c, "atmrt_shadow_steps", reach, 0.0, m);
 }
 
 extern "C" int atmrt_shadow_mask_device(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, uint8_t* status_device, uint16_t* block_device,
@@ -2828,8 +2227,7 @@ extern "C" int atmrt_shadow_mask_planes_device(atmrt_ctx* c, const atmrt_shadow_
                                                const double* lat, const double* lon, const double* elev, uint8_t* status_device,
                                                uint16_t* block_device, atmrt_shadow_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!hit_count || !lat || !lon || !elev) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_mask_planes_device: a plane is NULL");
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_mask_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  if (int rc = shadow_planes_check(c, "atmrt_shadow_mask_planes_device", n_pixels, hit_count, lat, lon, elev)) return rc;
   int32_t m = 0;
   if (int rc = shadow_check(c, "atmrt_shadow_mask_planes_device", spec, status_device, &m)) return rc;
   atmrt_ctx* k = nullptr;
@@ -2884,60 +2282,30 @@ int shadow_lights_check(atmrt_ctx* c, const char* what, const atmrt_shadow_light
       return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: light %u is not a finite vector of a finite, positive squared length", what, l);
     lights[3 * l] = v.x, lights[3 * l + 1] = v.y, lights[3 * l + 2] = v.z;
   }
-  if (!(std::isfinite(spec->reach) && spec->reach > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: reach must be finite and positive", what);
-  if (!(std::isfinite(spec->lift) && spec->lift >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: lift must be finite and not negative", what);
-  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
-  if (const char* msg = shadow_steps_of(c, spec->reach, m)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
-  return ATMRT_OK;
+  return shadow_reach_check(c, what, spec->reach, spec->lift, m);
 }
 
 const char* const SHADOW_LIGHTS_ON_MULTI = "has no frame of its own: shadow lights work on the gathered planes through atmrt_shadow_lights_planes_device";
 
-// shadow_run for a list of lights.  host_*: where the planes are downloaded to inside the call's timed window (null: none).
+// shadow_run for a list of lights.  host_*: where the planes are downloaded to (null: none).
 int shadow_lights_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_lights_spec_t& spec, const std::vector<double>& lights, int32_t m,
                       const TracePoints& src, uint64_t* mask_dev, uint8_t* status_dev, uint16_t* block_dev, atmrt_shadow_stats_t* stats,
                       uint64_t* host_mask, uint8_t* host_status, uint16_t* host_block) {
-  Frame f;
-  if (int rc = prepare_frame(k, &f)) {
-    if (k != report) report->error = k->error;
-    return rc;
-  }
-  hipStream_t s = k->stream;
   ShadowLightsJob job{};
   job.src = src;
   job.n_lights = spec.n_lights, job.lift = spec.lift, job.m = m;
-  job.esc_floor = shadow_escape_floor(k, f, spec.reach);
-  job.escape = job.esc_floor < INFINITY ? 1 : 0;
   job.lit_mask = reinterpret_cast<unsigned long long*>(mask_dev), job.status = status_dev, job.block = block_dev;
   double* d_dirs = nullptr;
-  HIP_TRY(report, reserve_carved(k->d_shadow, [&](Carve& cv) {
-            cv(job.list, src.n_pixels * sizeof(uint32_t)), cv(job.ctr, SH_N * sizeof(unsigned long long)), cv(d_dirs, 3 * SHADOW_LIGHTS_MAX * sizeof(double));
-          }));
-  job.dirs = d_dirs;
   const size_t planes = src.n_pixels * spec.n_lights;
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_BEGIN], s));
-  HIP_TRY(report, hipMemcpyAsync(d_dirs, lights.data(), lights.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_shadow_lights(f, job, s, k->ev[EV_SH_COMPACTED]);
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_MARCHED], s));
-  unsigned long long ctr[SH_N] = {};
-  HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
-  if (host_mask) HIP_TRY(report, hipMemcpyAsync(host_mask, mask_dev, src.n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (host_status) HIP_TRY(report, hipMemcpyAsync(host_status, status_dev, planes, hipMemcpyDeviceToHost, s));
-  if (host_block) HIP_TRY(report, hipMemcpyAsync(host_block, block_dev, planes * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_END], s));
-  HIP_TRY(report, hipStreamSynchronize(s));
-  HIP_TRY(report, hipGetLastError());
-  for (int i = 0; i < 3; i++) {
-    float ms = 0.0f;
-    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[EV_SH_BEGIN + i], k->ev[EV_SH_BEGIN + i + 1]));
-    report->shadow_timings[i] = ms;
-  }
-  if (stats) {
-    stats->lit = ctr[SH_LIT], stats->shadowed = ctr[SH_SHADOWED];
-    stats->none = src.n_pixels - ctr[SH_LIST];
-    stats->integrated_steps = ctr[SH_STEPS], stats->escaped_rays = ctr[SH_ESCAPED];
-  }
-  return ATMRT_OK;
+  return shadow_call(k, report, spec.reach, job, [&](Carve& cv) { cv(d_dirs, 3 * SHADOW_LIGHTS_MAX * sizeof(double)); },
+                     [&](const Frame& f, hipStream_t s) -> int {
+                       job.dirs = d_dirs;
+                       HIP_TRY(report, hipMemcpyAsync(d_dirs, lights.data(), lights.size() * sizeof(double), hipMemcpyHostToDevice, s));
+                       launch_shadow_lights(f, job, s, k->ev[EV_SH_COMPACTED]);
+                       return ATMRT_OK;
+                     },
+                     {{host_mask, mask_dev, src.n_pixels * sizeof(uint64_t)}, {host_status, status_dev, planes}, {host_block, block_dev, planes * sizeof(uint16_t)}},
+                     stats);
 }
 
 } // namespace
@@ -2975,8 +2343,7 @@ extern "C" int atmrt_shadow_lights_planes_device(atmrt_ctx* c, const atmrt_shado
                                                  const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
                                                  uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!hit_count || !lat || !lon || !elev) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_lights_planes_device: a plane is NULL");
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_lights_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  if (int rc = shadow_planes_check(c, "atmrt_shadow_lights_planes_device", n_pixels, hit_count, lat, lon, elev)) return rc;
   int32_t m = 0;
   std::vector<double> lights;
   if (int rc = shadow_lights_check(c, "atmrt_shadow_lights_planes_device", spec, lit_mask_device, status_device, &m, lights)) return rc;

@@ -1,6 +1,7 @@
 // atmrt_ctx.h — internal: the context behind the C ABI (include/atmrt.h), shared by the translation units that implement it:
-// atmrt_api.hip (one device: terrain store, frame set-up, launch sequences) and atmrt_multi.hip (several devices: column tiles,
-// the RCCL all-gather, image assembly).
+// atmrt_api.hip (one device: terrain store, frame set-up, launch sequences), atmrt_polar.hip (the calls along azimuths from the
+// observer: sight lines, viewshed, viewshed map, horizon) and atmrt_multi.hip (several devices: column tiles, the RCCL all-gather,
+// image assembly).
 #pragma once
 
 #include <cstdarg>
@@ -254,3 +255,7 @@ struct atmrt_ctx {
     if (e_ != hipSuccess) return (ctx)->fail(ATMRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
+namespace atmrt {
+// implemented in atmrt_api.hip, used by atmrt_polar.hip: the context's cached frame inputs refreshed and handed out as a Frame
+int prepare_frame(atmrt_ctx* c, Frame* out);
+} // namespace atmrt

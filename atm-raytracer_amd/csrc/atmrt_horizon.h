@@ -1,6 +1,6 @@
 // atmrt_horizon.h — the horizon profile (include/atmrt.h, "horizon": the rule is stated there): per azimuth the bracket of elevation
 // angles between the highest ray that terrain stops and the ray above it, and the ridge that stops it.  The launch interface for
-// atmrt_api.hip; the kernels themselves are compiled by atmrt_horizon.hip only (ATMRT_HORIZON_KERNELS).
+// atmrt_polar.hip; the kernels themselves are compiled by atmrt_horizon.hip only (ATMRT_HORIZON_KERNELS).
 //
 //   (path table)      the viewshed's k_viewshed_paths and its Cached product: H[i][k], step-major
 //   (profiles)        k_sight_calc / k_sight_profile through launch_sight_profile: every azimuth is a target whose m is the call's

@@ -1,5 +1,5 @@
 // atmrt_sight.h — sight lines (include/atmrt.h, "sight lines": the rule is stated there): at which elevation angle a target appears
-// and what terrain hides it.  The two host halves of the rule and the launch interface for atmrt_api.hip; the kernels themselves are
+// and what terrain hides it.  The two host halves of the rule and the launch interface for atmrt_polar.hip; the kernels themselves are
 // compiled by atmrt_sight.hip only (ATMRT_SIGHT_KERNELS).
 //
 //   k_sight_calc     one thread per target: its DirectionalCalc, as k_fast_columns makes a column's (thread 0: the observer's altitude)
@@ -13,6 +13,7 @@
 #pragma once
 
 #include "atmrt_kernels.h"
+#include "atmrt_polar_plan.h" // SightMeta, sight_target_bytes
 
 namespace atmrt {
 
@@ -29,11 +30,6 @@ ATMRT_HD double sight_fan_angle(double lo, double delta, int k) { return lo + (d
 ATMRT_HD int sight_pick(unsigned long long fails) { return fails ? 64 - __builtin_clzll(fails) : 0; }
 
 // ---- launch interface -----------------------------------------------------------------------------------------------------------------
-struct SightMeta {
-  uint64_t off; // first entry of the target's profile in SightBatch::T / lat / lon
-  int32_t m;
-  int32_t _pad;
-};
 // One batch of targets in device memory.  dtab[i] = d_i for i <= the largest m of the call.
 struct SightBatch {
   int32_t n;
@@ -44,7 +40,6 @@ struct SightBatch {
   const double* dtab;
   double* alt;                         // [1] the observer's altitude after Altitude::abs
 };
-static inline size_t sight_target_bytes(int m) { return 3 * sizeof(double) * ((size_t)m + 1) + 1024; } // what a target adds to a batch
 void launch_sight_profile(const Frame& f, const SightBatch& b, int m_max, hipStream_t stream);
 void launch_sight_solve(const Frame& f, const SightBatch& b, double lo, double hi, int rounds, atmrt_sight_t* out, hipStream_t stream);
 void launch_sight_probe(const Frame& f, const SightBatch& b, size_t n_angles, const double* angles_deg, atmrt_sight_ray_t* rays,

@@ -1,5 +1,5 @@
 // atmrt_viewshed.h — the viewshed raster (include/atmrt.h, "viewshed": the rule is stated there): the first round of the sight-line
-// rule at every cell of a polar lattice.  The host half of the rule, the kernels' shape and the launch interface for atmrt_api.hip;
+// rule at every cell of a polar lattice.  The host half of the rule, the kernels' shape and the launch interface for atmrt_polar.hip;
 // the kernels themselves are compiled by atmrt_viewshed.hip only (ATMRT_VIEWSHED_KERNELS).
 //
 //   k_viewshed_paths  one lane per ray of the fan: the serial stepper exactly as sight_trace and k_ray_paths call it, all m steps
@@ -46,8 +46,11 @@ struct ViewshedScan {
   const double *T, *lat, *lon; // [n][m + 1]
   ViewshedPlanes out;
 };
-static inline size_t viewshed_cell_bytes(const ViewshedPlanes& p) { // of the planes asked for
-  return (p.k_star ? 2 : 0) + 1 + 8 + (p.block_index ? 4 : 0) + (p.ground ? 8 : 0) + (p.lat ? 8 : 0) + (p.lon ? 8 : 0);
+struct ViewshedAsked { // which planes a call wants beside status and hidden, which every call has
+  bool k_star, block_index, ground, lat, lon;
+};
+static inline size_t viewshed_cell_bytes(const ViewshedAsked& a) { // of the planes asked for
+  return (a.k_star ? 2 : 0) + 1 + 8 + (a.block_index ? 4 : 0) + (a.ground ? 8 : 0) + (a.lat ? 8 : 0) + (a.lon ? 8 : 0);
 }
 void launch_viewshed_paths(const Frame& f, double lo, double hi, int K, int m, double* H, hipStream_t stream);
 void launch_viewshed_scan(const ViewshedScan& s, hipStream_t stream);

@@ -1,6 +1,6 @@
 // atmrt_viewshed_map.h — the viewshed map (include/atmrt.h, "viewshed map": the rule is stated there): the samples of a viewshed —
 // lattice cell (j, i) with its status, hidden, lat and lon — scattered into a latitude / longitude grid.  The launch interface for
-// atmrt_api.hip; the kernels are compiled by atmrt_viewshed.hip only (ATMRT_VIEWSHED_KERNELS).
+// atmrt_polar.hip; the kernels are compiled by atmrt_viewshed.hip only (ATMRT_VIEWSHED_KERNELS).
 //
 //   k_vsmap_clear    n_samples = n_seen = 0, min_hidden = +inf.
 //   k_vsmap_scatter  one sample per lane, in the planes' own order [j * m + (i - 1)]: a wavefront is 64 consecutive steps of one

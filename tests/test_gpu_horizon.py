@@ -12,6 +12,7 @@ import pytest
 import yaml
 
 import horizon_model as hm
+import polar_plan_model as pm
 import sight_model as sm
 import viewshed_model as vm
 from atm_raytracer_amd import _abi, generators, synth
@@ -195,6 +196,14 @@ def test_brackets_equal_the_fan_probe(gpu_ctx):
         assert r["block_distance"] == r["block_index"] * STEP and abs((r["angle_clear"] - r["angle_blocked"]) - r["resolution"]) < 1e-12
 
 
+def timings_hold(work, found):
+    """every interval of the call's timing array is a finite time; after a call that found its path table the table's entry is exactly 0"""
+    ms = [v for k, v in work.items() if k.endswith("_ms")]
+    assert all(np.isfinite(v) and v >= 0.0 for v in ms), work
+    if found:
+        assert work["paths_ms"] == 0.0 and not work["table_rebuilt"], work
+
+
 def test_batches_and_determinism(gpu_ctx, monkeypatch):
     cfg, tiles = scene()
     configure(gpu_ctx, cfg, tiles)
@@ -203,7 +212,9 @@ def test_batches_and_determinism(gpu_ctx, monkeypatch):
     args = (0.0, 40.0, n_az, m * STEP, FAN, 128, 3)
     whole = generators.horizon(gpu_ctx, *args)
     assert generators.horizon_work(gpu_ctx)["batches"] == 1
+    timings_hold(generators.horizon_work(gpu_ctx), False)
     again = generators.horizon(gpu_ctx, *args)
+    timings_hold(generators.horizon_work(gpu_ctx), True)
     assert whole.records.tobytes() == again.records.tobytes()
     # what an azimuth adds to a batch: its profile, 3 x 8 x (m + 1) + 1024 bytes, and its record of 72
     per_az = 3 * 8 * (m + 1) + 1024 + 72
@@ -211,10 +222,13 @@ def test_batches_and_determinism(gpu_ctx, monkeypatch):
     split = generators.horizon(gpu_ctx, *args)
     work = generators.horizon_work(gpu_ctx)
     print(f"horizon batches: limit {4 * per_az} bytes: {work}")
-    assert 1 < work["batches"] < n_az and not work["table_rebuilt"]
+    want = pm.batches(pm.uniform(n_az, m, 4 * per_az, pm.HORIZON_STAGED))
+    assert 1 < want < n_az and work["batches"] == want
+    timings_hold(work, True)
     monkeypatch.setenv("ATMRT_SIGHT_SCRATCH_BYTES", "1")  # a batch holds at least one azimuth
     single = generators.horizon(gpu_ctx, *args)
     assert generators.horizon_work(gpu_ctx)["batches"] == n_az
+    timings_hold(generators.horizon_work(gpu_ctx), True)
     assert whole.records.tobytes() == split.records.tobytes() == single.records.tobytes()
     assert (whole.records["status"] == hm.FOUND).all()
 

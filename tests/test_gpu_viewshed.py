@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import yaml
 
+import polar_plan_model as pm
 import sight_model as sm
 import viewshed_model as vm
 from atm_raytracer_amd import _abi, generators, synth
@@ -172,6 +173,14 @@ def test_scan_equals_the_sight_lines(gpu_ctx):
     assert (total > 0).all(), "the scene must hold all four statuses"
 
 
+def timings_hold(work, found):
+    """every interval of the call's timing array is a finite time; after a call that found its path table the table's entry is exactly 0"""
+    ms = [v for k, v in work.items() if k.endswith("_ms")]
+    assert all(np.isfinite(v) and v >= 0.0 for v in ms), work
+    if found:
+        assert work["paths_ms"] == 0.0 and not work["table_rebuilt"], work
+
+
 def test_batches_and_determinism(gpu_ctx, monkeypatch):
     cfg, tiles = scene()
     configure(gpu_ctx, cfg, tiles)
@@ -180,7 +189,9 @@ def test_batches_and_determinism(gpu_ctx, monkeypatch):
     args = (0.0, 40.0, n_az, m * STEP, 10.0, FAN, 128)
     whole = generators.viewshed(gpu_ctx, *args)
     assert generators.viewshed_work(gpu_ctx)["batches"] == 1
+    timings_hold(generators.viewshed_work(gpu_ctx), False)
     again = generators.viewshed(gpu_ctx, *args)
+    timings_hold(generators.viewshed_work(gpu_ctx), True)
     for k, a in whole.planes().items():
         assert a.tobytes() == getattr(again, k).tobytes(), k
     # a limit that holds a few azimuths of this call, not all nine (one adds some 5 kB: its profile and its cells of the seven planes)
@@ -188,10 +199,13 @@ def test_batches_and_determinism(gpu_ctx, monkeypatch):
     split = generators.viewshed(gpu_ctx, *args)
     work = generators.viewshed_work(gpu_ctx)
     print(f"viewshed batches: limit 20000 bytes: {work}")
-    assert 1 < work["batches"] < n_az and not work["table_rebuilt"]
+    want = pm.batches(pm.uniform(n_az, m, 20000, pm.viewshed_staged(m)))
+    assert 1 < want < n_az and work["batches"] == want
+    timings_hold(work, True)
     monkeypatch.setenv("ATMRT_SIGHT_SCRATCH_BYTES", "1")  # a batch holds at least one azimuth
     single = generators.viewshed(gpu_ctx, *args)
-    assert generators.viewshed_work(gpu_ctx)["batches"] == n_az
+    assert generators.viewshed_work(gpu_ctx)["batches"] == n_az == pm.batches(pm.uniform(n_az, m, 1, pm.viewshed_staged(m)))
+    timings_hold(generators.viewshed_work(gpu_ctx), True)
     for k, a in whole.planes().items():
         assert a.tobytes() == getattr(split, k).tobytes() == getattr(single, k).tobytes(), k
 

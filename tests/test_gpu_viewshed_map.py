@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import yaml
 
+import polar_plan_model as pm
 import viewshed_map_model as mm
 import viewshed_model as vm
 from atm_raytracer_amd import _abi, generators, synth
@@ -141,6 +142,14 @@ def test_grids(gpu_ctx):
     assert st["n_outside"] > 0 and st["n_binned"] > 0 and st["n_skipped"] == 0
 
 
+def timings_hold(work, found):
+    """every interval of the call's timing array is a finite time; after a call that found its path table the table's entry is exactly 0"""
+    ms = [v for k, v in work.items() if k.endswith("_ms")]
+    assert all(np.isfinite(v) and v >= 0.0 for v in ms), work
+    if found:
+        assert work["paths_ms"] == 0.0 and not work["table_rebuilt"], work
+
+
 def test_batches(gpu_ctx, monkeypatch):
     """The scratch limit lowered until the fused call takes several batches: the same bytes as in one batch."""
     cfg, tiles = scene()
@@ -152,16 +161,20 @@ def test_batches(gpu_ctx, monkeypatch):
     _, want = expected(gpu_ctx, grid, call)
     whole = to_host(fused(gpu_ctx, grid, call))
     assert generators.viewshed_work(gpu_ctx)["batches"] == 1
+    timings_hold(generators.viewshed_work(gpu_ctx), True)  # the viewshed of `expected` built the table under the same key
     mm.assert_same(whole, want, "one batch")
     # one azimuth adds its profile (three doubles per sample and a kilobyte) and 25 bytes per cell, some 4.2 kB here: four to a batch
     monkeypatch.setenv("ATMRT_SIGHT_SCRATCH_BYTES", "20000")
     split = to_host(fused(gpu_ctx, grid, call))
     work = generators.viewshed_work(gpu_ctx)
     print(f"viewshed map batches: limit 20000 bytes: {work}")
-    assert 3 <= work["batches"] < n_az and not work["table_rebuilt"] and work["download_ms"] > 0.0  # the last entry: the scatter
+    batches = pm.batches(pm.uniform(n_az, m, 20000, pm.viewshed_map_staged(m)))
+    assert 3 <= batches < n_az and work["batches"] == batches and work["download_ms"] > 0.0  # the last entry: the scatter
+    timings_hold(work, True)
     monkeypatch.setenv("ATMRT_SIGHT_SCRATCH_BYTES", "1")  # a batch holds at least one azimuth
     single = to_host(fused(gpu_ctx, grid, call))
     assert generators.viewshed_work(gpu_ctx)["batches"] == n_az
+    timings_hold(generators.viewshed_work(gpu_ctx), True)
     host = to_host(generators.viewshed_map(gpu_ctx, grid, *call))
     assert generators.viewshed_work(gpu_ctx)["batches"] == n_az
     assert same_bytes(whole, split) and same_bytes(whole, single) and same_bytes(whole, host)
