@@ -731,7 +731,7 @@ static int prepare_ceiling(atmrt_ctx* c, Frame& f) {
   // on changes the rays (the image's rows and the observer's altitude; the bins' key holds the rest of the camera).  Its time is the
   // table's (EV_CEIL_BEGIN .. EV_CEIL_END, ceiling_ms).
   bool order_built = false;
-  if (!c->comm && march_queue_wanted(f)) {
+  if (frame_march_plan(f, c->comm != nullptr).route == MarchRoute::Queue) {
     const OrderKey okey{c->ceiling.serial(), c->bins.serial(), f.h, p.position.altitude_kind, bits(p.position.altitude)};
     MarchOrder o{};
     const int orc = c->ceil_order.refresh(okey, [&](Nothing&) {
@@ -929,6 +929,7 @@ int atmrt::prepare_frame(atmrt_ctx* c, Frame* out) {
 // in buffers of its own.  No pointer into the allocation is kept in the context across frames.
 static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
   *ws = Workspace{};
+  ws->march = frame_march_plan(f, c->comm != nullptr);
   if (f.p.generator == ATMRT_GEN_RECTILINEAR && !f.opaque) { // the counting passes' trace points beyond the slots
     static const long forced_cap = [] { // test hook: a tiny arena forces the second-pass route (tests/test_gpu_march_variants.py)
       const char* e = getenv("ATMRT_OVERFLOW_CAP");
@@ -974,7 +975,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     // Rectilinear with scene objects: the lean march first (it leaves the rays that can meet an object to the general tracer and
     // lists them), then the tracer over that list
     HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
-    launch_trace_count(f, ws, dense, s);
+    c->last_march_route = launch_rect_trace_count(f, ws, dense, s);
     uint64_t cnt[N_COUNTERS];
     HIP_TRY(c, read_counters(ws, s, cnt));
     launch_rect_trace_objects(f, ws, dense, cnt[CTR_OBJECT_RAYS], s);
@@ -987,7 +988,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   } else {
     HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
-    launch_rect_march(f, ws, dense, s, ev[EV_MARCH_END]);
+    c->last_march_route = launch_rect_march(f, ws, dense, s, ev[EV_MARCH_END]);
     HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   }
   HIP_TRY(c, hipEventRecord(ev[EV_PACK_BEGIN], s));
@@ -1133,6 +1134,7 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   // atmrt_draw_image / atmrt_last_hits_device may touch
   c->last_valid = false;
   c->last_ceil_rows = 0;
+  c->last_march_route = MarchRoute::None; // run_core sets it where it launches the Rectilinear march
   c->stats = atmrt_frame_stats_t{};
   HIP_TRY(c, hipEventRecord(c->ev_t0, s));
   c->scan_segments = 0;
@@ -1423,8 +1425,9 @@ extern "C" int atmrt_debug_march_plan(int32_t width, int32_t height, int32_t sam
   f.n_t = samples;
   f.n_objects = n_objects;
   f.opaque = n_objects == 0; // (the plan of a frame over opaque terrain: translucent terrain is not sliced, like scenes with objects)
-  SliceLayout L{};
-  const bool sliced = march_slice_layout(f, L);
+  const MarchPlan plan = frame_march_plan(f, false);
+  const bool sliced = plan.route == MarchRoute::Sliced;
+  const SliceLayout& L = plan.slices;
   out[0] = sliced ? 1 : 0;
   out[1] = sliced ? L.n_groups : 0;
   out[2] = sliced ? L.cap : 0;
@@ -2567,6 +2570,21 @@ extern "C" int atmrt_debug_march_order(atmrt_ctx* c, size_t cap, uint32_t* order
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpyAsync(order, c->d_ceil_order.as<uint32_t>(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_last_march_route(atmrt_ctx* c, int32_t index, int32_t* route) {
+  if (!c || !route) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (c->multi) {
+    if (index < 0 || index >= multi_size(c)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "device index %d outside the context's %d devices", index, multi_size(c));
+    atmrt_ctx* k = multi_child(c, index);
+    const int rc = atmrt_debug_last_march_route(k, -1, route);
+    if (rc) c->error = k->error;
+    return rc;
+  }
+  if (index != -1 && index != 0) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a context of one device has no tile %d", index);
+  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_debug_last_march_route needs a frame: call atmrt_generate first");
+  *route = (int32_t)c->last_march_route;
   return ATMRT_OK;
 }
 

@@ -185,6 +185,8 @@ struct atmrt_ctx {
   // atmrt_debug_march_order: the work queue that frame marched with — its groups (0: none) and the build of `ceil_order` that filled it
   uint32_t last_order_groups = 0;
   uint64_t last_order_serial = 0;
+  // atmrt_debug_last_march_route: the route that frame's first-pass march was launched by (None: not a Rectilinear frame)
+  atmrt::MarchRoute last_march_route = atmrt::MarchRoute::None;
 
   std::vector<atmrt::ObjectDev> objects; // host image of the device table (altitude kind in _pad until k_resolve)
   std::vector<uint8_t> textures;         // RGBA8 pool

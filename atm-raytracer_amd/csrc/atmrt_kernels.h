@@ -8,6 +8,7 @@
 #include "atmrt_core.h"
 #include "atmrt_ceiling.h"
 #include "atmrt_march_queue.h"
+#include "atmrt_march_plan.h"
 #include "atmrt_objects.h"
 
 namespace atmrt {
@@ -58,7 +59,7 @@ struct Frame {
   double ceil_floor;
   // The work queue of the whole-frame opaque march (k_rect_march_queue): the frame's groups of 64 consecutive pixels, longest
   // estimated march first (k_march_length_estimate over the table above) — a permutation of 0 .. ceil(wl h / 64) - 1 that decides
-  // scheduling only.  Null: no table, or a frame that does not take the queue (march_queue_wanted); the march is the plain grid.
+  // scheduling only.  Set exactly when the frame's route is MarchRoute::Queue (frame_march_plan), else null.
   const uint32_t* ceil_order;
   const uint32_t* ceil_order_steps; // beside it: the estimated steps of every entry of ceil_order (descending): sizes the chunks claimed from its tail
   // Spherical calculator: the record of what the trace-point epilogue would compute again in every lane (NormalTrig, atmrt_core.h;
@@ -250,14 +251,7 @@ static inline OverflowArena carve_overflow(char* base, size_t cap) {
   return a;
 }
 
-// The time-sliced march of small Rectilinear launches (atmrt_march_impl.h, k_rect_march_first / _cont): which launches take it and
-// what they need.  A launch of at most MARCH_SMALL_MAX_BLOCKS 256-thread blocks is "small" (a few resident sets: column shards of a
-// frame, test frames); ATMRT_MARCH_VARIANT=plain|small|sliced forces one variant for every launch (test hook: the random sweeps run
-// small frames over the kernel the full-size frames use, and the other way round; same results every way).  =queue forces the
-// whole-frame work queue (k_rect_march_queue) on the frames that can take it at any size — opaque terrain, no objects, the whole
-// image, a ceiling table — and leaves every other launch to the choice by size.
-constexpr unsigned MARCH_SMALL_MAX_BLOCKS = 16384u;
-constexpr int MARCH_SLICE_STEPS = 128;
+// ATMRT_MARCH_VARIANT (MarchOverride, atmrt_march_plan.h), read once per process.
 static inline int march_variant_override() {
   static const int v = [] {
     const char* e = getenv("ATMRT_MARCH_VARIANT");
@@ -265,52 +259,19 @@ static inline int march_variant_override() {
   }();
   return v;
 }
-constexpr int WAVE_CAND = 96; // entries of a wavefront's candidate list (scenes with objects); more: every ray of the wavefront is left to the tracer
-// a group's list between two slices: lo, hi, vlo, vhi (f64) and the object index (i32) of every entry, the number of entries and
-// the next wake distance
-constexpr size_t SLICE_GROUP_LIST_BYTES = (size_t)WAVE_CAND * (4 * sizeof(double) + sizeof(int32_t)) + 2 * sizeof(double);
-struct SliceLayout {
-  uint32_t n_groups;     // groups of 64 consecutive pixels
-  size_t n_pad;          // pixels rounded up to whole groups
-  size_t slices_after;   // an upper bound on the slices a ray can need after the first
-  size_t cap;            // FIFO entries: n_groups x slices_after
-  size_t bytes;          // of Workspace::slice_state
-};
-// false: this frame's march is not sliced (scene objects unless forced, rays one slice long, too big a launch, or forced otherwise)
-static inline bool march_slice_layout(const Frame& f, SliceLayout& L) {
-  const size_t n = (size_t)f.wl * f.h;
-  const int ov = march_variant_override();
-  if (f.p.generator != ATMRT_GEN_RECTILINEAR || n == 0 || f.n_t + 2 <= MARCH_SLICE_STEPS) return false;
-  // Scenes with objects CAN be sliced (round 4: a group's candidate list travels with its state, the object steps are done out of
-  // line inside the slices; bit-identical, tests/test_gpu_march_variants.py) but are not by default: config 5's tiles at 8 GPUs
-  // take 8 x 43.8 ms sliced against 8 x 42.3 ms through the small-launch variant of k_rect_march<3> (the slices that contain object
-  // steps run long and put their groups out of step) — ATMRT_MARCH_VARIANT=sliced forces it.
-  if (f.n_objects != 0 && ov != 3) return false;
-  // Translucent terrain likewise (round 4, after the march went to 5 wavefronts per SIMD; tiles of the headline at alpha 0.5, sum of the
-  // tile times): 2 tiles sliced 210 ms / plain 195 / small-launch 199, 4 tiles 211 / 203 / 208, 8 tiles 224 / 235 / 218 — rays that do
-  // not stop at the terrain are of near-uniform length, which is what the slices were there to even out; the launcher picks between
-  // the plain and the small-launch variant by the size of the grid (ATMRT_LAUNCH_MARCH).
-  if (!f.opaque && ov != 3) return false;
-  if (ov && ov != 4 ? ov != 3 : (n + 255) / 256 > MARCH_SMALL_MAX_BLOCKS) return false;
-  if (ov == 4 && f.ceil_order) return false; // the queue is forced and this frame has one
-  L.n_groups = (uint32_t)((n + 63) / 64);
-  L.n_pad = (size_t)L.n_groups * 64;
-  L.slices_after = ((size_t)f.n_t + 2 + MARCH_SLICE_STEPS - 1) / MARCH_SLICE_STEPS;
-  L.cap = (size_t)L.n_groups * L.slices_after;
-  if (L.cap > 0x7fffffffull) return false; // (a frame of > 2^31 slices is marched whole)
-  L.bytes = L.n_pad * (7 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(DirCalc)) + 64 + L.cap * sizeof(uint32_t);
-  // scenes with objects: every group's candidate list (what a wavefront of k_rect_march<3> keeps in LDS) travels with its state
-  if (f.n_objects) L.bytes += 256 + (size_t)L.n_groups * SLICE_GROUP_LIST_BYTES;
-  return true;
-}
-
-// The whole-frame work queue (k_rect_march_queue) is for the launches the plain grid runs today: opaque terrain without objects, the
-// whole image in one launch (the column tiles of a multi-GPU frame stay on the sliced march), a ceiling table to estimate from, and a
-// grid above MARCH_SMALL_MAX_BLOCKS unless ATMRT_MARCH_VARIANT=queue forces it.  `f` needs its ceiling fields but ceil_order.
-static inline bool march_queue_wanted(const Frame& f) {
-  const int ov = march_variant_override();
-  if (f.p.generator != ATMRT_GEN_RECTILINEAR || !f.opaque || !f.ceil || f.lattice || f.c0 != 0 || f.wl != (int32_t)f.p.width) return false;
-  return ov == 4 || (ov == 0 && ((size_t)f.wl * f.h + 255) / 256 > MARCH_SMALL_MAX_BLOCKS);
+// The plan of frame `f`'s first-pass march (march_plan), made where the frame is set up (prepare_ceiling: does it take the work
+// queue?) and where its scratch is (prepare_workspace: Workspace::march, which the launchers go by) — one function of the same
+// inputs, so that Frame::ceil_order is set exactly when the route is Queue.  `f` needs its ceiling fields but ceil_order;
+// shared_frame: the context is a rank of a frame that several devices share.
+static inline MarchPlan frame_march_plan(const Frame& f, bool shared_frame) {
+  if (f.p.generator != ATMRT_GEN_RECTILINEAR) return MarchPlan{};
+  MarchShape s{};
+  s.n = (size_t)f.wl * f.h;
+  s.n_t = f.n_t;
+  s.mode = f.n_objects ? 3 : f.opaque ? 0 : 1;
+  s.objects = f.n_objects != 0;
+  s.queue_ok = f.opaque && f.ceil && !f.lattice && f.c0 == 0 && f.wl == (int32_t)f.p.width && !shared_frame;
+  return march_plan(s, march_variant_override());
 }
 // Wavefronts per SIMD that claim from the head of the queue.  Measured on the headline frame (ATMRT_MARCH_QUEUE_LONG=1|2|3
 // is the A/B switch): with 1 the heads are served too slowly for the 2,200 items of 250 steps and more (8.28 ms per frame against
@@ -364,6 +325,7 @@ static inline void march_order_layout(const Frame& f, Carve& k, MarchOrder& o) {
 // shapes, conditions and sizes are stated there); buffers of their own that outlive the frame or a second preparation within it; and
 // buffers sized by a count the host reads back in mid-frame.  A field nobody set is null / zero.
 struct Workspace {
+  MarchPlan march;        // Rectilinear: the route of the frame's first-pass march (prepare_workspace), which the layout and the launchers go by
   // --- carved by workspace_layout
   int32_t* hit_step;      // first hit: index of the older sample of the pair, or -1
   uint64_t* scan_tmp;     // block sums for the scan
@@ -397,8 +359,8 @@ struct Workspace {
   size_t overflow_cap;    // its capacity in records (set before the layout runs: prepare_workspace)
   uint32_t* object_rays;  // Rectilinear, scenes with objects: pixels the lean march left to the general tracer
   char* step_ctx;         // Rectilinear, scenes with objects: Frame + StepSinks in HBM for the lean march's out-of-line object step
-  char* slice_state;      // time-sliced march (march_slice_layout): ray state between two slices + the FIFO of groups, or null
-  unsigned long long* march_claim; // whole-frame work queue (Frame::ceil_order): the claim word, zeroed before the launch, or null
+  char* slice_state;      // route Sliced (slice_state_layout): ray state between two slices + the FIFO of groups, or null
+  unsigned long long* march_claim; // route Queue: the claim word, zeroed before the launch, or null
   // --- carved by workspace_layout in an opaque frame (the march's first hits, [4][h][wl]), else sized by the frame's trace points
   double* rect_rec;       // Rectilinear: [4][n] ray elevation / path length at the two bracketing samples
   // --- buffers of their own
@@ -462,9 +424,8 @@ static inline void workspace_layout(const Frame& f, Carve& k, Workspace& ws) {
     k(ws.object_rays, npx * sizeof(uint32_t));
     k(ws.step_ctx, Carve::pad(sizeof(Frame)) + STEP_SINKS_MAX_BYTES); // launch_rect_trace_count carves the two out of it
   }
-  SliceLayout slices;
-  if (march_slice_layout(f, slices)) k(ws.slice_state, slices.bytes);   // a small Rectilinear launch: the time-sliced march
-  if (f.ceil_order) k(ws.march_claim, sizeof(unsigned long long));      // the whole-frame work queue
+  if (ws.march.route == MarchRoute::Sliced) k(ws.slice_state, ws.march.slices.bytes); // a small Rectilinear launch: the time-sliced march
+  if (ws.march.route == MarchRoute::Queue) k(ws.march_claim, sizeof(unsigned long long)); // the whole-frame work queue
 }
 
 // InterpolatingRectilinear scratch
@@ -512,7 +473,7 @@ void launch_close_count(const Frame& f, Workspace& ws, hipStream_t stream);
 void launch_close_fill(const Frame& f, Workspace& ws, hipStream_t stream);
 // exclusive scan of in[0, n) into out; the grand total into *total (and nothing else)
 void launch_scan_u32(const uint32_t* in, size_t n, uint64_t* tmp, uint64_t* out, unsigned long long* total, hipStream_t stream);
-void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
+void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream); // Fast (Rectilinear: launch_rect_trace_count)
 void launch_fast_paths(const Frame& f, Workspace& ws, hipStream_t stream, int i_begin, int i_end); // atmrt_paths.hip
 // The phase events of a context (atmrt_ctx::ev; `timing` below): an interval of atmrt_timings_t lies between two of them.  Between
 // frames atmrt_sight_lines, atmrt_locate_landmarks* and atmrt_shadow_mask* time their own consecutive intervals with the same events, under names of their own.
@@ -542,7 +503,7 @@ void launch_fast_caches(const Frame& f, Workspace& ws, hipStream_t stream, hipSt
                         hipEvent_t ev_join, hipEvent_t* timing /* EV_PROFILE_*: phase A, EV_PATHS_*: phase B */);
 void launch_fast_intersect(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
 void launch_fast_finalize(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
-void launch_rect_march(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched);
+MarchRoute launch_rect_march(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched); // the route it launched
 void launch_scan_counts(const Frame& f, Workspace& ws, const uint32_t* hit_count, hipStream_t stream);
 void launch_pack_first_hits(const Frame& f, Workspace& ws, const DensePlanes& dense, const PackedHits& packed,
                             hipStream_t stream);
@@ -617,7 +578,7 @@ void launch_lm_reset(size_t n, const LmState& state, hipStream_t stream);
 void launch_lm_pass(bool pass_b, const TracePoints& src, const LmIndex& index, const LmState& state, hipStream_t stream);
 void launch_lm_finish(size_t n, const TracePoints& src, const LmState& state, atmrt_landmark_hit_t* hits, hipStream_t stream);
 
-void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream);
+MarchRoute launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream); // the route it launched
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream);
 void launch_dense_from_packed(const Frame& f, Workspace& ws, const PackedHits& packed, const DensePlanes& dense, int fast_angles,
                               hipStream_t stream);

@@ -1842,10 +1842,6 @@ void launch_pack_first_hits(const Frame& f, Workspace& ws, const DensePlanes& de
 }
 
 void launch_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream) {
-  if (f.p.generator == ATMRT_GEN_RECTILINEAR) {
-    launch_rect_trace_count(f, ws, out, stream);
-    return;
-  }
   hipLaunchKernelGGL(k_paths_transpose, dim3(f.n_path_cap, cdiv(f.h, 256)), dim3(256), 0, stream, f, ws.pelev, ws.plen, ws.npath,
                      ws.pelev_t, ws.plen_t);
   // Counting pass in three parts: (1) mark the pixels that can have a step with an object (k_fast_flag_rows); (2) the plain

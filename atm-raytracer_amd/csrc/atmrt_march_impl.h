@@ -59,36 +59,13 @@ constexpr uint32_t OBJECT_RAY = 0xffffffffu; // hit_count of a ray left to k_rec
 // ends alone on a SIMD it cannot fill (a launch of uniform 2000-step rays takes 4.02 ms per workgroup-per-CU + 3.5 ms: one resident
 // set 19.5 ms, not 16.1).  A wavefront therefore starts at priority 3 and drops one level every DRAIN_PRIO_BAND steps: the
 // wavefronts of a SIMD are kept within a band of one another and the last set drains together (16.8 ms; a shard of the headline at
-// 8 GPUs 41.5 -> 39.0 ms).  In a launch of many resident sets the drain is 1 % and the priorities cost about as much (the headline
-// frame 269.4 -> 271.6 ms), so only launches of at most DRAIN_PRIO_MAX_BLOCKS workgroups (16 resident sets) use them: the kernel is
-// compiled in both variants (DRAIN) and the launcher picks one by the size of its grid (ATMRT_LAUNCH_MARCH).
-constexpr unsigned DRAIN_PRIO_MAX_BLOCKS = MARCH_SMALL_MAX_BLOCKS;
+// 8 GPUs 41.5 -> 39.0 ms).  In a launch of many resident sets the drain is 1 % and the priorities cost about as much, so only small
+// launches use them: the kernel is compiled in both variants (DRAIN) and the frame's plan picks one by the size and kind of the
+// grid (atmrt_march_plan.h: MarchRoute::GridDrain, march_drain_max_blocks; launch_march_grid below).
 constexpr int DRAIN_PRIO_BAND = 512;
-// Since the plain march runs 5 wavefronts per SIMD too (round 4) the small-launch variant only pays where the drain is a large part
-// of the launch: measured on the tiles of the headline (profiles/r04/march_occupancy_and_slices.json), translucent terrain (MODE 1)
-// plain / small at 16384 blocks 195 / 199 ms, at 8192 203 / 208, at 4096 235 / 218; scenes with objects (MODE 3, where the variant also
-// does the object steps out of line) 251 / 258, 295 / 267, 384 / 274.
-template <int MODE>
-constexpr unsigned drain_max_blocks() {
-  return MODE == 1 ? 6144u : MODE == 3 ? 12288u : DRAIN_PRIO_MAX_BLOCKS;
-}
 #ifndef ATMRT_MARCH_BLOCK_SMALL
 #define ATMRT_MARCH_BLOCK_SMALL 256 // workgroup size of the small-launch (DRAIN) variant
 #endif
-// launches k_rect_march<MODE, CALC, CUBIC, DRAIN> over N rays / list entries, DRAIN by the grid size
-#define ATMRT_LAUNCH_MARCH(MODE, N, STREAM, ...)                                                                                       \
-  do {                                                                                                                                 \
-    const unsigned blocks_ = cdiv((size_t)(N), 256);                                                                                   \
-    const int override_ = march_variant_override();                                                                                    \
-    if (override_ && override_ != 4 ? override_ != 1 : blocks_ <= drain_max_blocks<MODE>()) { /* 4 = queue: the grid goes by its size */ \
-      ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march<MODE, CALC, CUBIC, true>),                                    \
-                                                            dim3(cdiv((size_t)(N), ATMRT_MARCH_BLOCK_SMALL)), dim3(ATMRT_MARCH_BLOCK_SMALL), 0, STREAM, \
-                                                            __VA_ARGS__));                                                             \
-    } else {                                                                                                                           \
-      ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march<MODE, CALC, CUBIC, false>), dim3(blocks_), dim3(256), 0, STREAM, \
-                                                            __VA_ARGS__));                                                             \
-    }                                                                                                                                  \
-  } while (0)
 
 // The DRAIN variant also runs 5 wavefronts per SIMD (96 VGPRs, 136 B of scratch per lane) instead of 4 (127 VGPRs, none): a shard's
 // long wavefronts are 1.37 resident sets of 4096 but 1.09 sets of 5120, so far fewer of them are left to run on half-empty SIMDs at
@@ -404,7 +381,7 @@ static __device__ __forceinline__ MarchEnd march_steps(const Frame& f, const Ear
   const int i_end = i0 + slice;
   double sx = r.s.x, lat, lon;
   for (int i = i0 + 1;; i++) {
-    if (DRAIN && (i & (DRAIN_PRIO_BAND - 1)) == 0) { // see DRAIN_PRIO_MAX_BLOCKS
+    if (DRAIN && (i & (DRAIN_PRIO_BAND - 1)) == 0) { // see DRAIN_PRIO_BAND
       const int band = i / DRAIN_PRIO_BAND;
       if (band == 1) __builtin_amdgcn_s_setprio(2);
       else if (band == 2) __builtin_amdgcn_s_setprio(1);
@@ -680,34 +657,8 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
 // FIFO: ctl[0] = entries claimed by readers, ctl[1] = entries written, ctl[2] = groups finished.  Entries are never reused (capacity:
 // groups x slices a ray can need) and each has exactly one reader, the workgroup whose claim returned its index.  A reader whose
 // entry is still empty waits for it — the writer is a wavefront that is marching, never one that waits — and gives up when every
-// group has finished (its index is then beyond the last entry that will ever be written).
-struct SliceState {
-  double *x, *a, *b, *sh, *pl, *diff0, *ang; // [plane]
-  int32_t *step, *hint;                      // [plane]; step < 0: the ray has finished
-  uint32_t* count;                           // [plane] MODE 1: crossings so far
-  DirCalc* calc;                             // [plane] the ray's geodesic calculator
-  uint32_t* queue;                           // [cap], 0xffffffff = not written yet
-  unsigned long long* ctl;                   // [4]
-  uint32_t cap;
-  char* glist;                               // MODE 3: [n_groups] candidate lists of SLICE_GROUP_LIST_BYTES each, or null
-};
-// a group's candidate list in HBM (MODE 3): the arrays of one record
-struct GroupList {
-  double *lo, *hi, *vlo, *vhi;
-  int32_t* obj;
-  double* n_and_wake; // [0] number of entries (as a double), [1] x_wake
-};
-static __device__ __forceinline__ GroupList group_list(char* base, uint32_t group) {
-  char* q = base + (size_t)group * SLICE_GROUP_LIST_BYTES;
-  GroupList g;
-  g.n_and_wake = (double*)q;
-  g.lo = g.n_and_wake + 2;
-  g.hi = g.lo + WAVE_CAND;
-  g.vlo = g.hi + WAVE_CAND;
-  g.vhi = g.vlo + WAVE_CAND;
-  g.obj = (int32_t*)(g.vhi + WAVE_CAND);
-  return g;
-}
+// group has finished (its index is then beyond the last entry that will ever be written).  SliceState, its layout in HBM and a
+// group's candidate list (GroupList, group_list): atmrt_march_plan.h.
 constexpr uint32_t SLICE_EMPTY = 0xffffffffu, SLICE_EXIT = 0xfffffffeu;
 #ifndef ATMRT_SLICE_WAVES
 #define ATMRT_SLICE_WAVES 5 // per SIMD, like the plain march (round 4: 2 x 93.3 -> 90.0 ms, 4 x 47.8 -> 46.2, 8 x 24.24 -> 24.01; 6: slower)
@@ -1170,39 +1121,37 @@ __global__ __launch_bounds__(256, ATMRT_TRACE_WAVES) void k_rect_trace(Frame f, 
 // launchers
 // ---------------------------------------------------------------------------------------------
 
-// The sliced march of a terrain-only frame: slice 0 as an ordinary grid, one host round trip for the number of groups still
-// marching (it bounds the entries the later slices can write: the grid of the second kernel), then one wavefront per entry.
-// false: the frame is not sliced (march_slice_layout) and the caller launches k_rect_march.
+// k_rect_march<MODE, CALC, CUBIC, DRAIN> over n rays / list entries; returns the route that is
 template <int MODE, bool CUBIC>
-static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
-  SliceLayout L;
-  if (!ws.slice_state || !march_slice_layout(f, L)) return false;
+static MarchRoute launch_march_grid(bool drain, size_t n, const Frame& f, const DensePlanes& out, const MarchSinks& sinks, unsigned long long* counters,
+                                    hipStream_t stream) {
+  if (drain) {
+    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march<MODE, CALC, CUBIC, true>), dim3(cdiv(n, ATMRT_MARCH_BLOCK_SMALL)),
+                                                          dim3(ATMRT_MARCH_BLOCK_SMALL), 0, stream, f, out, sinks, counters));
+  } else {
+    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march<MODE, CALC, CUBIC, false>), dim3(cdiv(n, 256)), dim3(256), 0, stream, f, out,
+                                                          sinks, counters));
+  }
+  return drain ? MarchRoute::GridDrain : MarchRoute::Grid;
+}
+
+// The sliced march (route Sliced; ws.march.slices, ws.slice_state): slice 0 as an ordinary grid, one host round trip for the number
+// of groups still marching (it bounds the entries the later slices can write: the grid of the second kernel), then one wavefront
+// per entry.
+template <int MODE, bool CUBIC>
+static void launch_rect_march_sliced(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
+  const SliceLayout& L = ws.march.slices;
   const size_t n = (size_t)f.wl * f.h;
   const int slice = MARCH_SLICE_STEPS;
   SliceState st;
-  char* q = ws.slice_state;
-  st.calc = (DirCalc*)q; q += L.n_pad * sizeof(DirCalc);
-  st.x = (double*)q; q += L.n_pad * 8;
-  st.a = (double*)q; q += L.n_pad * 8;
-  st.b = (double*)q; q += L.n_pad * 8;
-  st.sh = (double*)q; q += L.n_pad * 8;
-  st.pl = (double*)q; q += L.n_pad * 8;
-  st.diff0 = (double*)q; q += L.n_pad * 8;
-  st.ang = (double*)q; q += L.n_pad * 8;
-  st.step = (int32_t*)q; q += L.n_pad * 4;
-  st.hint = (int32_t*)q; q += L.n_pad * 4;
-  st.count = (uint32_t*)q; q += L.n_pad * 4;
-  st.ctl = (unsigned long long*)q; q += 64;
-  st.queue = (uint32_t*)q;
-  st.cap = (uint32_t)L.cap;
-  st.glist = f.n_objects ? ws.slice_state + Carve::pad((size_t)((char*)(st.queue + L.cap) - ws.slice_state)) : nullptr;
+  slice_state_layout(ws.slice_state, L, f.n_objects != 0, st);
   (void)hipMemsetAsync(st.ctl, 0, 64, stream);
   ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_first<MODE, CALC, CUBIC>), dim3(cdiv(n, 256)), dim3(256), 0, stream, f,
                                                         out, sinks, (unsigned long long*)ws.counters, st, L.n_groups, slice));
   unsigned long long ctl_host[4] = {0, 0, 0, 0};
   if (hipMemcpyAsync(ctl_host, st.ctl, sizeof ctl_host, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
-    return true; // the error is sticky: the caller's next HIP call reports it
+    return; // the error is sticky: the caller's next HIP call reports it
   // a group writes at most one entry per slice it survives
   const size_t entries = std::min<size_t>(L.cap, (size_t)ctl_host[1] * L.slices_after);
   if (entries) {
@@ -1212,36 +1161,57 @@ static bool launch_rect_march_sliced(const Frame& f, Workspace& ws, const DenseP
   }
   hipLaunchKernelGGL(k_slice_check, dim3(1), dim3(1), 0, stream, (const unsigned long long*)st.ctl, L.n_groups,
                      (unsigned long long*)ws.counters);
-  return true;
 }
 
-// The whole-frame work queue (k_rect_march_queue) for the frames that have an order (Frame::ceil_order, march_queue_wanted): one
-// workgroup per CU.  false: the frame has none and the caller launches the grid.
+// The whole-frame work queue (route Queue; k_rect_march_queue over Frame::ceil_order): one workgroup per CU.  Without a claim word
+// or the device's CU count it launches the grid instead, and says so.
 template <bool CUBIC>
-static bool launch_rect_march_queue(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
-  if (!f.ceil_order || !f.ceil_order_steps || !ws.march_claim) return false;
+static MarchRoute launch_rect_march_queue(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
+  const size_t n = (size_t)f.wl * f.h;
   int device = 0, cus = 0;
-  if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1)
-    return false;
-  const uint32_t n_groups = (uint32_t)(((size_t)f.wl * f.h + 63) / 64);
+  if (!f.ceil_order || !f.ceil_order_steps || !ws.march_claim || hipGetDevice(&device) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1)
+    return launch_march_grid<0, CUBIC>(march_grid_drain(0, n, ws.march.override), n, f, out, sinks, (unsigned long long*)ws.counters, stream);
+  const uint32_t n_groups = (uint32_t)((n + 63) / 64);
   (void)hipMemsetAsync(ws.march_claim, 0, sizeof(unsigned long long), stream);
   ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_march_queue<CALC, CUBIC>), dim3((unsigned)cus), dim3(1024), 0, stream, f, out, sinks,
                                                         (unsigned long long*)ws.counters, f.ceil_order, f.ceil_order_steps, ws.march_claim, n_groups,
                                                         march_queue_long(), march_queue_item_prio(),
                                                         march_queue_guided() ? (uint32_t)cus * 16u : 0u)); // the launch's wavefronts
-  return true;
+  return MarchRoute::Queue;
+}
+
+// The first-pass march of the frame by the route its workspace was planned with (Workspace::march): MODE 0 opaque terrain, 1
+// translucent terrain, 3 scenes with objects.  Returns the route it launched.
+template <int MODE, bool CUBIC>
+static MarchRoute launch_march_planned(const Frame& f, Workspace& ws, const DensePlanes& out, const MarchSinks& sinks, hipStream_t stream) {
+  const size_t n = (size_t)f.wl * f.h;
+  switch (ws.march.route) {
+    case MarchRoute::Sliced:
+      launch_rect_march_sliced<MODE, CUBIC>(f, ws, out, sinks, stream);
+      return MarchRoute::Sliced;
+    case MarchRoute::Queue: // (planned for opaque terrain only: MarchShape::queue_ok)
+      if constexpr (MODE == 0) return launch_rect_march_queue<CUBIC>(f, ws, out, sinks, stream);
+      break;
+    case MarchRoute::Grid:
+    case MarchRoute::GridDrain:
+      return launch_march_grid<MODE, CUBIC>(ws.march.route == MarchRoute::GridDrain, n, f, out, sinks, (unsigned long long*)ws.counters, stream);
+    case MarchRoute::None:
+      break;
+  }
+  return MarchRoute::None; // no plan, no launch
 }
 
 template <bool CUBIC>
-void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched) {
+MarchRoute launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched) {
   size_t n = (size_t)f.wl * f.h;
   RectRec rec = carve_rec(ws.rect_rec, n);
   MarchSinks sinks{};
+  MarchRoute route;
   if (f.opaque) {
     sinks.hit_step = ws.hit_step;
     sinks.rec = rec;
-    if (!launch_rect_march_sliced<0, CUBIC>(f, ws, out, sinks, stream) && !launch_rect_march_queue<CUBIC>(f, ws, out, sinks, stream))
-      ATMRT_LAUNCH_MARCH(0, n, stream, f, out, sinks, (unsigned long long*)ws.counters);
+    route = launch_march_planned<0, CUBIC>(f, ws, out, sinks, stream);
     (void)hipEventRecord(ev_marched, stream);
     ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_rect_finalize<CALC>), dim3(cdiv(n, 256)), dim3(256), 0, stream,
                                                           f, ws.hit_step, rec, out));
@@ -1249,9 +1219,10 @@ void launch_rect_march_t(const Frame& f, Workspace& ws, const DensePlanes& out, 
     sinks.rec = carve_rec(ws.slot_rec, n * RECT_SLOTS);
     sinks.step = ws.slot_step;
     sinks.ovf = carve_overflow(ws.overflow_arena, ws.overflow_cap);
-    if (!launch_rect_march_sliced<1, CUBIC>(f, ws, out, sinks, stream)) ATMRT_LAUNCH_MARCH(1, n, stream, f, out, sinks, (unsigned long long*)ws.counters);
+    route = launch_march_planned<1, CUBIC>(f, ws, out, sinks, stream);
     (void)hipEventRecord(ev_marched, stream);
   }
+  return route;
 }
 
 // terrain_alpha < 1, no usable overflow arena (launch_list_fill): the pixels with more crossings than slots, listed in ws.overflow
@@ -1265,7 +1236,8 @@ void launch_rect_second_march_t(const Frame& f, Workspace& ws, uint64_t n_hits, 
   sinks.hit_offset = ws.hit_offset;
   sinks.pixel_list = ws.overflow;
   sinks.n_list = (uint32_t)ws.n_overflow;
-  ATMRT_LAUNCH_MARCH(2, ws.n_overflow, stream, f, dense, sinks, (unsigned long long*)ws.counters);
+  launch_march_grid<2, CUBIC>(march_grid_drain(2, (size_t)ws.n_overflow, ws.march.override), (size_t)ws.n_overflow, f, dense, sinks,
+                              (unsigned long long*)ws.counters, stream);
 }
 
 // the rays k_rect_march<3> left to the tracer, collected into a list (order irrelevant: every ray is independent); CTR_OBJECT_RAYS counts them
@@ -1285,7 +1257,7 @@ static inline OverflowArena trace_overflow_arena(const Workspace& ws) {
 // rays that can meet an object flagged and listed); phase 2 (launch_rect_trace_objects_t, after the host has read the list's
 // length) traces the listed rays with the general tracer.
 template <bool CUBIC>
-void launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream) {
+MarchRoute launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream) {
   size_t n = (size_t)f.wl * f.h;
   RectRec slots = carve_rec(ws.slot_rec, n * RECT_SLOTS);
   // the frame and the tracer's arenas where the out-of-line object step can address them (object_step_impl): copies in HBM
@@ -1305,7 +1277,7 @@ void launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes&
   (void)hipMemcpyAsync(frame_dev, &f, sizeof f, hipMemcpyHostToDevice, stream);
   (void)hipMemcpyAsync(sinks_dev, &sinks, sizeof sinks, hipMemcpyHostToDevice, stream);
   (void)hipStreamSynchronize(stream); // both sources are on this stack frame
-  // a small launch (a column tile): the time-sliced march, its groups carrying their candidate lists; else the whole grid at once
+  // the planned route: a grid, or (forced) the time-sliced march, its groups carrying their candidate lists
   MarchSinks msinks{};
   msinks.hit_step = ws.hit_step;
   msinks.rec = slots;
@@ -1314,9 +1286,10 @@ void launch_rect_trace_count_t(const Frame& f, Workspace& ws, const DensePlanes&
   msinks.slot_tag = ws.slot_packed.color_tag;
   msinks.frame_dev = frame_dev;
   msinks.step_sinks_dev = sinks_dev;
-  if (!launch_rect_march_sliced<3, CUBIC>(f, ws, out, msinks, stream)) ATMRT_LAUNCH_MARCH(3, n, stream, f, out, msinks, (unsigned long long*)ws.counters);
+  const MarchRoute route = launch_march_planned<3, CUBIC>(f, ws, out, msinks, stream);
   hipLaunchKernelGGL(k_collect_object_rays, dim3(cdiv(n, 256)), dim3(256), 0, stream, n, (const uint32_t*)out.hit_count, ws.object_rays,
                      (unsigned long long*)ws.counters);
+  return route;
 }
 template <bool CUBIC>
 void launch_rect_trace_objects_t(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream) {
@@ -1344,9 +1317,9 @@ void launch_rect_second_trace_t(const Frame& f, Workspace& ws, uint64_t n_hits, 
 // explicit instantiation of the launchers for one value of CUBIC, in two groups so that four translation units (march / trace x
 // linear / spline atmospheres) compile in parallel: the lean march (k_rect_march, all modes) and the general tracer (k_rect_trace)
 #define ATMRT_INSTANTIATE_MARCH(CUBIC)                                                                                        \
-  template void launch_rect_march_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, hipStream_t, hipEvent_t);            \
+  template MarchRoute launch_rect_march_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, hipStream_t, hipEvent_t);      \
   template void launch_rect_second_march_t<CUBIC>(const Frame&, Workspace&, uint64_t, const DensePlanes&, hipStream_t);       \
-  template void launch_rect_trace_count_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, hipStream_t);
+  template MarchRoute launch_rect_trace_count_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, hipStream_t);
 #define ATMRT_INSTANTIATE_TRACE(CUBIC)                                                                                        \
   template void launch_rect_trace_objects_t<CUBIC>(const Frame&, Workspace&, const DensePlanes&, uint64_t, hipStream_t);      \
   template void launch_rect_second_trace_t<CUBIC>(const Frame&, Workspace&, uint64_t, const DensePlanes&, const PackedHits&,  \

@@ -5,21 +5,19 @@ namespace atmrt {
 ATMRT_INSTANTIATE_MARCH(false)
 
 // the non-template entry points pick the variant by whether the compiled atmosphere has Spline (cubic) segments
-extern template void launch_rect_march_t<true>(const Frame&, Workspace&, const DensePlanes&, hipStream_t, hipEvent_t);
+extern template MarchRoute launch_rect_march_t<true>(const Frame&, Workspace&, const DensePlanes&, hipStream_t, hipEvent_t);
 extern template void launch_rect_second_march_t<true>(const Frame&, Workspace&, uint64_t, const DensePlanes&, hipStream_t);
-extern template void launch_rect_trace_count_t<true>(const Frame&, Workspace&, const DensePlanes&, hipStream_t);
+extern template MarchRoute launch_rect_trace_count_t<true>(const Frame&, Workspace&, const DensePlanes&, hipStream_t);
 extern template void launch_rect_trace_objects_t<true>(const Frame&, Workspace&, const DensePlanes&, uint64_t, hipStream_t);
 extern template void launch_rect_second_trace_t<true>(const Frame&, Workspace&, uint64_t, const DensePlanes&, const PackedHits&, hipStream_t);
 extern template void launch_rect_trace_objects_t<false>(const Frame&, Workspace&, const DensePlanes&, uint64_t, hipStream_t); // atmrt_trace_linear.hip
 extern template void launch_rect_second_trace_t<false>(const Frame&, Workspace&, uint64_t, const DensePlanes&, const PackedHits&, hipStream_t);
 
-void launch_rect_march(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched) {
-  if (f.atm_cubic) launch_rect_march_t<true>(f, ws, out, stream, ev_marched);
-  else launch_rect_march_t<false>(f, ws, out, stream, ev_marched);
+MarchRoute launch_rect_march(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream, hipEvent_t ev_marched) {
+  return f.atm_cubic ? launch_rect_march_t<true>(f, ws, out, stream, ev_marched) : launch_rect_march_t<false>(f, ws, out, stream, ev_marched);
 }
-void launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream) {
-  if (f.atm_cubic) launch_rect_trace_count_t<true>(f, ws, out, stream);
-  else launch_rect_trace_count_t<false>(f, ws, out, stream);
+MarchRoute launch_rect_trace_count(const Frame& f, Workspace& ws, const DensePlanes& out, hipStream_t stream) {
+  return f.atm_cubic ? launch_rect_trace_count_t<true>(f, ws, out, stream) : launch_rect_trace_count_t<false>(f, ws, out, stream);
 }
 void launch_rect_trace_objects(const Frame& f, Workspace& ws, const DensePlanes& out, uint64_t n_rays, hipStream_t stream) {
   if (f.atm_cubic) launch_rect_trace_objects_t<true>(f, ws, out, n_rays, stream);

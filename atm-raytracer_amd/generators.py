@@ -137,6 +137,12 @@ class Context:
             assert n.value == order.size
         return order
 
+    def debug_march_route(self, index=-1):
+        """Diagnostic (atmrt_debug_last_march_route): 1 plain grid, 2 small-launch grid, 3 time-sliced, 4 work queue; 0 not Rectilinear."""
+        route = C.c_int32()
+        self.check(self.lib.atmrt_debug_last_march_route(self.handle, index, C.byref(route)))
+        return route.value
+
     def debug_normal_trig(self):
         """Diagnostic (atmrt_debug_normal_trig): the record of the trace-point epilogue's frame constants for the parameters now
         set, float64 [17]: sin, cos of +15 m / radius, of -15 m / radius, of 0 and of 90 degrees, then the observer's north, east

@@ -1095,12 +1095,19 @@ int atmrt_debug_normal_trig(atmrt_ctx* ctx, size_t cap, double* out, size_t* n);
  * table with the one tests/csrc/ceiling_host.cpp builds on the host: every byte must be equal. */
 int atmrt_debug_ceiling_table(atmrt_ctx* ctx, size_t cap, float* cell, float* suffix, int32_t* rows, int32_t* n_bins, double layout[3]);
 /* A diagnostic of the same kind: the work queue the LAST GENERATED FRAME's whole-frame opaque march took its 64-pixel groups from
- * (DESIGN.md §7.9), longest estimated march first.  *n_groups = its entries, ceil(pixels / 64) (0, and nothing written: that frame
- * marched without a queue — a small frame unless ATMRT_MARCH_VARIANT=queue, translucent terrain, objects, a column tile, no ceiling
- * table); order receives the first min(cap, *n_groups) of them.  The order decides scheduling only, and entries of equal estimate
- * may change places from build to build; what must hold is that it is a permutation of 0 .. *n_groups - 1
- * (tests/test_gpu_march_queue.py).  ATMRT_ERR_STATE when a later call has built another order in its place. */
+ * (DESIGN.md §7.9), longest estimated march first.  *n_groups = its entries, ceil(pixels / 64) (0, and nothing written: the
+ * frame's plan — march_plan, csrc/atmrt_march_plan.h — did not route it to the queue: a small frame unless
+ * ATMRT_MARCH_VARIANT=queue, translucent terrain, objects, a column tile, no ceiling table); order receives the first
+ * min(cap, *n_groups) of them.  The order decides scheduling only, and entries of equal estimate may change places from build to
+ * build; what must hold is that it is a permutation of 0 .. *n_groups - 1 (tests/test_gpu_march_queue.py).  ATMRT_ERR_STATE when a
+ * later call has built another order in its place. */
 int atmrt_debug_march_order(atmrt_ctx* ctx, size_t cap, uint32_t* order, uint32_t* n_groups);
+/* The route the LAST GENERATED FRAME's first-pass Rectilinear march was launched by (MarchRoute, csrc/atmrt_march_plan.h): 0 none
+ * (another generator), 1 the plain grid, 2 the small-launch grid, 3 the time-sliced march, 4 the whole-frame work queue.  What was
+ * launched, not what was planned: a queue that had to fall back reports its grid.  All routes give the same bits, so this is how a
+ * test sees which one a frame took.  index: the device of a multi-device context, as in atmrt_ctx_tile_columns; a context of one
+ * device takes -1 or 0.  ATMRT_ERR_STATE without a valid last frame. */
+int atmrt_debug_last_march_route(atmrt_ctx* ctx, int32_t index, int32_t* route);
 
 #ifdef __cplusplus
 }

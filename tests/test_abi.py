@@ -75,7 +75,7 @@ def test_no_cpu_fallback(lib):
 
 
 def test_march_plan_of_frames_and_tiles(lib):
-    """Host logic of the time-sliced march (csrc/atmrt_kernels.h march_slice_layout): which launches take it and the sizes it reserves.
+    """Host logic of the time-sliced march (march_plan, csrc/atmrt_march_plan.h): which launches take it and the sizes it reserves.
     The FIFO must hold one entry per group and slice a ray can survive; the grid bound of its second kernel (alive groups x
     slices) relies on `slices_after` covering every step count the march can reach (samples + 1 steps, the first slice excluded)."""
     out = (C.c_uint64 * 6)()

@@ -7,8 +7,10 @@ process: child processes, as in test_gpu_march_variants.py) on scene S2 and requ
   * 200x37: 116 groups, the last one partial; 40x24: 15 groups, fewer than the wavefronts of ONE workgroup, so most claim nothing;
     64x1: a single group;
   * ATMRT_CEILING=rebuild (the order is built again in every frame) and two long wavefronts per SIMD instead of one: the same;
-  * ATMRT_CEILING=off: no table, no order — the forced queue falls back to the grid; translucent terrain and objects never take it.
-The order every queued frame marched with is read back (atmrt_debug_march_order) and must be a permutation of its groups."""
+  * ATMRT_CEILING=off: no table, no order — the forced queue leaves the frames to the choice by size (here the time-sliced march);
+    translucent terrain and objects never take it, nor does a column shard of the first frame (col_begin 64, col_end 160).
+The order every queued frame marched with is read back (atmrt_debug_march_order) and must be a permutation of its groups, and
+every frame says which route it was launched by (atmrt_debug_last_march_route; the plan: csrc/atmrt_march_plan.h)."""
 import functools
 import json
 import os
@@ -30,8 +32,12 @@ out = {{}}
 for name, kw, objects, size in (("opaque", dict(), False, (160, 96)), ("opaque-again", dict(), False, (160, 96)),
                                 ("ragged", dict(step=26.0), False, (150, 61)), ("partial", dict(), False, (200, 37)),
                                 ("tiny", dict(), False, (40, 24)), ("one", dict(), False, (64, 1)),
-                                ("translucent", dict(terrain_alpha=0.5), False, (160, 96)), ("objects", dict(), True, (160, 96))):
+                                ("translucent", dict(terrain_alpha=0.5), False, (160, 96)), ("objects", dict(), True, (160, 96)),
+                                ("shard", dict(), False, (160, 96))):
     cfg, tiles = synth.scene("S2", size[0], size[1], generator="Rectilinear", **{{**dict(max_distance=60_000.0, tilt=-1.0), **kw}})
+    if name == "shard":  # `opaque` as a column shard: never the whole image, so never the queue
+        cfg.params.col_begin, cfg.params.col_end = 64, 160
+        size = (96, 96)
     if objects:
         synth.add_objects(cfg, n_cyl=40, n_bill=10, dist=(300.0, 20_000.0), spread_deg=30.0, radius=(30.0, 120.0), height=(150.0, 600.0),
                           bill_w=(150.0, 500.0), bill_h=(150.0, 500.0))
@@ -46,7 +52,7 @@ for name, kw, objects, size in (("opaque", dict(), False, (160, 96)), ("opaque-a
     permutation = order.size == groups and bool((np.sort(order) == np.arange(groups, dtype=np.uint32)).all())
     out[name] = dict(frame=[h.hexdigest(), int(r["n_hits"]), int(r["ray_steps"]), int(frame_stats(ctx)["terrain_lookups"]),
                             int(integrated.value), int(escaped.value)],
-                     queued=int(order.size), permutation=permutation)
+                     queued=int(order.size), permutation=permutation, route=ctx.debug_march_route())
 print("RESULT " + json.dumps(out))
 """
 OPAQUE = ("opaque", "opaque-again", "ragged", "partial", "tiny", "one")
@@ -89,8 +95,12 @@ def test_the_queue_gives_the_bits_and_counters_of_the_plain_march():
     plain, queue = _run("plain"), _run("queue")
     for name in OPAQUE:  # the opaque frames took the queue, over an order that is a permutation of their groups
         assert queue[name]["queued"] == GROUPS[name] and queue[name]["permutation"], (name, queue[name])
-    for name in ("translucent", "objects"):  # these never do
-        assert queue[name]["queued"] == 0, name
+        assert queue[name]["route"] == 4, (name, queue[name])  # MarchRoute::Queue: launched, not only planned
+    for name in ("translucent", "objects"):  # these never do: the small-launch grid, by their size
+        assert queue[name]["queued"] == 0 and queue[name]["route"] == 2, (name, queue[name])
+    # a column shard is not the whole image: no order is built for it and it stays on the time-sliced march
+    assert queue["shard"]["queued"] == 0 and queue["shard"]["route"] == 3, queue["shard"]
+    assert queue["shard"]["frame"][:3] == plain["shard"]["frame"][:3] and plain["shard"]["route"] == 1
     assert _frames(queue) == _frames(plain)
     assert queue["opaque"]["frame"] == queue["opaque-again"]["frame"], "the second frame of a context starts from a fresh claim word"
 
@@ -110,6 +120,7 @@ def test_an_order_rebuilt_in_every_frame_and_two_long_wavefronts_per_simd_change
 def test_without_a_ceiling_table_the_forced_queue_falls_back_to_the_grid():
     off = _run("queue", ATMRT_CEILING="off")
     assert all(r["queued"] == 0 for r in off.values())
+    assert all(off[name]["route"] == 3 for name in OPAQUE), "small opaque launches without an order: the time-sliced march, not the queue"
     # without the table fewer samples skip their lookup and rays leave later: the work counters differ from the table's; the image,
     # its hits and the ray-steps (credited steps included) do not
     assert {k: f[:3] for k, f in _frames(off).items()} == {k: f[:3] for k, f in _frames(_run("plain")).items()}
