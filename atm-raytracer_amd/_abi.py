@@ -238,6 +238,39 @@ class Horizon(C.Structure):
         [(k, C.c_double) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon", "block_elevation")]
 
 
+class InterpLattice(C.Structure):
+    """atmrt_interp_lattice_t: the lattice atmrt_debug_interp_blend blends, host arrays (borrowed: build with interp_lattice())."""
+    _fields_ = [("ne", C.c_int32), ("nd", C.c_int32), ("n_hits", C.c_uint64),
+                ("hit_count", C.POINTER(C.c_uint32)), ("azimuth", C.POINTER(C.c_double)), ("elevation_angle", C.POINTER(C.c_double)),
+                ("px_steps", C.POINTER(C.c_uint32)),
+                ("lat", C.POINTER(C.c_double)), ("lon", C.POINTER(C.c_double)), ("distance", C.POINTER(C.c_double)),
+                ("elevation", C.POINTER(C.c_double)), ("path_length", C.POINTER(C.c_double)), ("normal", C.POINTER(C.c_double)),
+                ("color_tag", C.POINTER(C.c_uint32)), ("rgba", C.POINTER(C.c_double))]
+
+
+def interp_lattice(lat):
+    """An atmrt_interp_lattice_t over the arrays of the dict `lat` (hit_count, azimuth, elevation_angle, px_steps: [ne][nd]; lat, lon,
+    distance, elevation, path_length [n], normal [n][3], color_tag [n], rgba [n][4]) and the arrays it borrows (keep them alive)."""
+    import numpy as np
+    r = InterpLattice()
+    keep = {}
+
+    def ptr(key, dtype, ctype):
+        a = np.ascontiguousarray(lat[key], dtype=dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=dtype)
+        keep[key] = a
+        return a.ctypes.data_as(C.POINTER(ctype))
+
+    r.ne, r.nd = np.shape(lat["hit_count"])
+    r.n_hits = int(np.size(lat["distance"]))
+    for k in ("hit_count", "px_steps", "color_tag"):
+        setattr(r, k, ptr(k, np.uint32, C.c_uint32))
+    for k in ("azimuth", "elevation_angle", "lat", "lon", "distance", "elevation", "path_length", "normal", "rgba"):
+        setattr(r, k, ptr(k, np.float64, C.c_double))
+    return r, keep
+
+
 def numpy_to_result(res):
     """Inverse of result_to_numpy: an atmrt_result_t whose pointers borrow the numpy arrays (keep `res` alive)."""
     import numpy as np

@@ -162,6 +162,8 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 36: return sizeof(atmrt_shadow_stats_t);
     // 37 stays 0
     case 38: return sizeof(atmrt_shadow_lights_spec_t);
+    // 39 stays 0
+    case 40: return sizeof(atmrt_interp_lattice_t);
     default: return 0;
   }
 }
@@ -924,7 +926,7 @@ int atmrt::prepare_frame(atmrt_ctx* c, Frame* out) {
 
 // The scratch of frame `f`: the context's workspace allocation grown to workspace_layout(f) and carved by it, and the three arrays
 // that outlive it (atmrt_ctx.h).  The allocation moves when it grows, so the rule is: NOTHING OF THIS FRAME IS LIVE IN IT WHEN IT IS
-// RESERVED.  Every call comes before the frame's first launch, but for the second one of run_interpolating: it prepares the frame
+// RESERVED.  Every call comes before the frame's first launch, but for the one in interp_blend_tail: it prepares the frame
 // that the entry point prepared already, so it cannot grow the allocation, and what the blend still needs of the lattice pass lies
 // in buffers of its own.  No pointer into the allocation is kept in the context across frames.
 static int prepare_workspace(atmrt_ctx* c, const Frame& f, Workspace* ws) {
@@ -1021,6 +1023,61 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
   return ATMRT_OK;
 }
 
+// The last stage of InterpolatingRectilinearGenerator::generate, for the frame and for atmrt_debug_interp_blend alike: cache_coords
+// (:186-204) of every pixel of `f` over the ray table in ib.elev / ib.dir, the bounding rectangle of the lattice points the pixels
+// reference, the lattice itself — `lattice(ei0, di0, ne, nd, lr)` leaves the ne x nd points of that rectangle in HBM, names them in
+// `lr` (all but lr.ne / lr.nd) and points ib.referenced at ne x nd zeroed flags — and the 4-corner blend (:395-418) into `dense` and
+// c->d_packed: count -> scan -> arena -> scan -> fill -> finish.  ws is the workspace of `f`, its counters zeroed by the caller.
+template <class Lattice>
+static int interp_blend_tail(atmrt_ctx* c, const Frame& f, Workspace& ws, InterpBuffers& ib, double min_elev_step, double min_dir_step,
+                             const DensePlanes& dense, Lattice&& lattice, PackedHits* packed_out, uint64_t* n_hits_out) {
+  hipStream_t s = c->stream;
+  int32_t bounds[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
+  HIP_TRY(c, hipMemcpyAsync(ib.bounds, bounds, sizeof bounds, hipMemcpyHostToDevice, s));
+  launch_lattice_keys(f, ib, min_elev_step, min_dir_step, s);
+  HIP_TRY(c, hipMemcpyAsync(bounds, ib.bounds, sizeof bounds, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  const int64_t ne = (int64_t)bounds[1] + 1 - bounds[0] + 1, nd = (int64_t)bounds[3] + 1 - bounds[2] + 1;
+  if (ne <= 0 || nd <= 0 || ne > 60000 || nd > 2000000 || ne * nd > (int64_t)1 << 31)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "InterpolatingRectilinear lattice of %lld x %lld points is out of range",
+                   (long long)nd, (long long)ne);
+  LatticeResult lr{};
+  int rc = lattice(bounds[0], bounds[2], ne, nd, lr);
+  if (rc) return rc;
+  lr.nd = (int32_t)nd;
+  lr.ne = (int32_t)ne;
+  // blend: count -> scan -> fill
+  if ((rc = prepare_workspace(c, f, &ws))) return rc;
+  HIP_TRY(c, hipMemsetAsync(&ws.counters[CTR_RAY_STEPS], 0, sizeof(uint64_t), s)); // only referenced lattice pixels count
+  PackedHits none{};
+  Frame fb = f;
+  fb.di0 = bounds[2];
+  fb.ei0 = bounds[0];
+  launch_interp_blend(fb, ws, ib, lr, false, dense, none, s);
+  launch_scan_counts(f, ws, dense.hit_count, s);
+  uint64_t counters[N_COUNTERS];
+  HIP_TRY(c, read_counters(ws, s, counters));
+  BlendArena arena{};
+  if (counters[CTR_BIG_BLEND_PIXELS]) { // pixels whose four corners hold more points than the in-register member list: blended over an HBM arena
+    const size_t n = (size_t)counters[CTR_BIG_BLEND_POINTS];
+    HIP_TRY(c, reserve_carved(c->d_blend_arena, [&](Carve& k) {
+      k(arena.k, n * 8), k(arena.dist, n * 8), k(arena.group, n * 4), k(arena.corner, n), k(arena.tag, n);
+    }));
+    launch_interp_blend_big(fb, ws, ib, lr, false, dense, none, arena, s);
+    launch_scan_counts(f, ws, dense.hit_count, s); // again, now that every pixel has its count
+    HIP_TRY(c, read_counters(ws, s, counters));
+  }
+  uint64_t n_hits = counters[CTR_HITS];
+  PackedHits packed;
+  HIP_TRY(c, reserve_carved(c->d_packed, [&](Carve& k) { packed = carve_packed(k, n_hits); }));
+  launch_interp_blend(fb, ws, ib, lr, true, dense, packed, s);
+  if (arena.k) launch_interp_blend_big(fb, ws, ib, lr, true, dense, packed, arena, s);
+  launch_interp_finish(f, ws, ib, lr, dense, packed, s);
+  if (packed_out) *packed_out = packed;
+  if (n_hits_out) *n_hits_out = n_hits;
+  return ATMRT_OK;
+}
+
 // InterpolatingRectilinearGenerator::generate (interpolating_rectilinear.rs:110-162): ray table -> lattice steps ->
 // lattice frame through the Fast pipeline -> 4-corner blend (count -> scan -> fill).
 static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlanes& dense, PackedHits* packed_out,
@@ -1045,83 +1102,44 @@ static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const 
   min_dir_step *= 1.5;
   if (!(min_elev_step > 0.0) || !(min_dir_step > 0.0) || !std::isfinite(min_elev_step) || !std::isfinite(min_dir_step))
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "degenerate field of view for InterpolatingRectilinear");
-  int32_t bounds[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
-  HIP_TRY(c, hipMemcpyAsync(ib.bounds, bounds, sizeof bounds, hipMemcpyHostToDevice, s));
-  launch_lattice_keys(f, ib, min_elev_step, min_dir_step, s);
-  HIP_TRY(c, hipMemcpyAsync(bounds, ib.bounds, sizeof bounds, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  const int64_t ne = (int64_t)bounds[1] + 1 - bounds[0] + 1, nd = (int64_t)bounds[3] + 1 - bounds[2] + 1;
-  if (ne <= 0 || nd <= 0 || ne > 60000 || nd > 2000000 || ne * nd > (int64_t)1 << 31)
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "InterpolatingRectilinear lattice of %lld x %lld points is out of range",
-                   (long long)nd, (long long)ne);
   // the lattice frame (Cache::get_pixel :80-107 for every lattice point of the bounding rectangle)
-  Frame fl = f;
-  fl.p.generator = ATMRT_GEN_FAST;
-  fl.lattice = 1;
-  fl.di0 = bounds[2];
-  fl.ei0 = bounds[0];
-  fl.dir_step = min_dir_step;
-  fl.elev_step = min_elev_step;
-  fl.c0 = 0;
-  fl.wl = (int32_t)nd;
-  fl.h = (int32_t)ne;
-  const size_t nlat = (size_t)nd * ne;
-  // run_core leaves its trace points in d_packed / d_hit_offset, and so must this frame.  The two pairs of buffers trade places
-  // twice per frame — here, before the lattice workspace takes their addresses, and after the lattice pass — so that each pair serves the same role (lattice / image) in every frame
-  // and keeps its capacity: with one swap the roles alternated and the smaller buffer was reallocated in the second frame.
-  std::swap(c->d_packed, c->d_lat_packed);
-  std::swap(c->d_hit_offset, c->d_lat_offset);
-  Workspace wsl{};
-  int rc = prepare_workspace(c, fl, &wsl);
-  if (rc) return rc;
-  HIP_TRY(c, reserve_carved(c->d_px_steps, [&](Carve& k) { k(wsl.px_steps, nlat * sizeof(uint32_t)), k(ib.referenced, nlat); }));
-  HIP_TRY(c, hipMemsetAsync(ib.referenced, 0, nlat, s));
-  DensePlanes ldense;
-  HIP_TRY(c, reserve_carved(c->d_lat_dense, [&](Carve& k) { ldense = carve_dense(k, nlat); }));
-  PackedHits lpacked{};
-  uint64_t lhits = 0;
-  if ((rc = run_core(c, fl, wsl, ldense, true, &lpacked, &lhits))) return rc;
-  std::swap(c->d_packed, c->d_lat_packed);   // keep the lattice result; the image gets the other pair
-  std::swap(c->d_hit_offset, c->d_lat_offset);
-  LatticeResult lr{};
-  lr.hit_count = ldense.hit_count;
-  lr.hit_offset = c->d_lat_offset.as<uint64_t>();
-  lr.azimuth = ldense.azimuth;
-  lr.elevation_angle = ldense.elevation_angle;
-  lr.hits = lpacked;
-  lr.px_steps = wsl.px_steps;
-  lr.nd = (int32_t)nd;
-  lr.ne = (int32_t)ne;
-  // blend: count -> scan -> fill
-  if ((rc = prepare_workspace(c, f, &ws))) return rc;
-  HIP_TRY(c, hipMemsetAsync(&ws.counters[CTR_RAY_STEPS], 0, sizeof(uint64_t), s)); // only referenced lattice pixels count
-  PackedHits none{};
-  Frame fb = f;
-  fb.di0 = fl.di0;
-  fb.ei0 = fl.ei0;
-  launch_interp_blend(fb, ws, ib, lr, false, dense, none, s);
-  launch_scan_counts(f, ws, dense.hit_count, s);
-  uint64_t counters[N_COUNTERS];
-  HIP_TRY(c, read_counters(ws, s, counters));
-  BlendArena arena{};
-  if (counters[CTR_BIG_BLEND_PIXELS]) { // pixels whose four corners hold more points than the in-register member list: blended over an HBM arena
-    const size_t n = (size_t)counters[CTR_BIG_BLEND_POINTS];
-    HIP_TRY(c, reserve_carved(c->d_blend_arena, [&](Carve& k) {
-      k(arena.k, n * 8), k(arena.dist, n * 8), k(arena.group, n * 4), k(arena.corner, n), k(arena.tag, n);
-    }));
-    launch_interp_blend_big(fb, ws, ib, lr, false, dense, none, arena, s);
-    launch_scan_counts(f, ws, dense.hit_count, s); // again, now that every pixel has its count
-    HIP_TRY(c, read_counters(ws, s, counters));
-  }
-  uint64_t n_hits = counters[CTR_HITS];
-  PackedHits packed;
-  HIP_TRY(c, reserve_carved(c->d_packed, [&](Carve& k) { packed = carve_packed(k, n_hits); }));
-  launch_interp_blend(fb, ws, ib, lr, true, dense, packed, s);
-  if (arena.k) launch_interp_blend_big(fb, ws, ib, lr, true, dense, packed, arena, s);
-  launch_interp_finish(f, ws, ib, lr, dense, packed, s);
-  if (packed_out) *packed_out = packed;
-  if (n_hits_out) *n_hits_out = n_hits;
-  return ATMRT_OK;
+  return interp_blend_tail(c, f, ws, ib, min_elev_step, min_dir_step, dense, [&](int32_t ei0, int32_t di0, int64_t ne, int64_t nd, LatticeResult& lr) {
+    Frame fl = f;
+    fl.p.generator = ATMRT_GEN_FAST;
+    fl.lattice = 1;
+    fl.di0 = di0;
+    fl.ei0 = ei0;
+    fl.dir_step = min_dir_step;
+    fl.elev_step = min_elev_step;
+    fl.c0 = 0;
+    fl.wl = (int32_t)nd;
+    fl.h = (int32_t)ne;
+    const size_t nlat = (size_t)nd * ne;
+    // run_core leaves its trace points in d_packed / d_hit_offset, and so must this frame.  The two pairs of buffers trade places
+    // twice per frame — here, before the lattice workspace takes their addresses, and after the lattice pass — so that each pair serves the same role (lattice / image) in every frame
+    // and keeps its capacity: with one swap the roles alternated and the smaller buffer was reallocated in the second frame.
+    std::swap(c->d_packed, c->d_lat_packed);
+    std::swap(c->d_hit_offset, c->d_lat_offset);
+    Workspace wsl{};
+    int rc = prepare_workspace(c, fl, &wsl);
+    if (rc) return rc;
+    HIP_TRY(c, reserve_carved(c->d_px_steps, [&](Carve& k) { k(wsl.px_steps, nlat * sizeof(uint32_t)), k(ib.referenced, nlat); }));
+    HIP_TRY(c, hipMemsetAsync(ib.referenced, 0, nlat, s));
+    DensePlanes ldense;
+    HIP_TRY(c, reserve_carved(c->d_lat_dense, [&](Carve& k) { ldense = carve_dense(k, nlat); }));
+    PackedHits lpacked{};
+    uint64_t lhits = 0;
+    if ((rc = run_core(c, fl, wsl, ldense, true, &lpacked, &lhits))) return rc;
+    std::swap(c->d_packed, c->d_lat_packed);   // keep the lattice result; the image gets the other pair
+    std::swap(c->d_hit_offset, c->d_lat_offset);
+    lr.hit_count = ldense.hit_count;
+    lr.hit_offset = c->d_lat_offset.as<uint64_t>();
+    lr.azimuth = ldense.azimuth;
+    lr.elevation_angle = ldense.elevation_angle;
+    lr.hits = lpacked;
+    lr.px_steps = wsl.px_steps;
+    return (int)ATMRT_OK;
+  }, packed_out, n_hits_out);
 }
 
 // Runs the generator named in params.  `dense` must be device memory.  When `want_packed`, the
@@ -1327,23 +1345,10 @@ int atmrt::api_generate_tile(atmrt_ctx* c, const DensePlanes* dense_in, bool wan
   return rc;
 }
 
-extern "C" int atmrt_generate(atmrt_ctx* c, atmrt_result_t* out) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  memset(out, 0, sizeof *out);
-  if (c->multi) return multi_generate(c, out); // every device its pixel-column tile, straight into the one [H][W] block
-  Frame f;
-  int rc = prepare_frame(c, &f);
-  if (rc) return rc;
-  Workspace ws{};
-  if ((rc = prepare_workspace(c, f, &ws))) return rc;
-  size_t npx = (size_t)f.wl * f.h;
-  DensePlanes dense;
-  HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, npx); }));
-  PackedHits packed{};
-  uint64_t n_hits = 0, steps = 0;
-  double ms = 0;
-  if ((rc = run_generator(c, f, ws, dense, true, &packed, &n_hits, &steps, &ms))) return rc;
-
+// The frame (or the probe's image) that `dense`, ws.hit_offset and `packed` hold in HBM as a library-allocated atmrt_result_t.
+static int result_to_host(atmrt_ctx* c, const Frame& f, const Workspace& ws, const DensePlanes& dense, const PackedHits& packed,
+                          uint64_t n_hits, uint64_t steps, double ms, atmrt_result_t* out) {
+  const size_t npx = (size_t)f.wl * f.h;
   if (atmrt_internal_result_alloc(out, (uint32_t)f.wl, (uint32_t)f.h, n_hits))
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "out of host memory for %zu pixels / %llu hits", npx, (unsigned long long)n_hits);
   out->ray_steps = steps;
@@ -1361,6 +1366,25 @@ extern "C" int atmrt_generate(atmrt_ctx* c, atmrt_result_t* out) {
     return c->fail(ATMRT_ERR_HIP, "copying the result to the host: %s", hipGetErrorString(e));
   }
   return ATMRT_OK;
+}
+
+extern "C" int atmrt_generate(atmrt_ctx* c, atmrt_result_t* out) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof *out);
+  if (c->multi) return multi_generate(c, out); // every device its pixel-column tile, straight into the one [H][W] block
+  Frame f;
+  int rc = prepare_frame(c, &f);
+  if (rc) return rc;
+  Workspace ws{};
+  if ((rc = prepare_workspace(c, f, &ws))) return rc;
+  size_t npx = (size_t)f.wl * f.h;
+  DensePlanes dense;
+  HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, npx); }));
+  PackedHits packed{};
+  uint64_t n_hits = 0, steps = 0;
+  double ms = 0;
+  if ((rc = run_generator(c, f, ws, dense, true, &packed, &n_hits, &steps, &ms))) return rc;
+  return result_to_host(c, f, ws, dense, packed, n_hits, steps, ms, out);
 }
 
 extern "C" int atmrt_generate_device(atmrt_ctx* c, const atmrt_device_planes_t* planes, uint64_t* ray_steps,
@@ -2586,6 +2610,100 @@ extern "C" int atmrt_debug_last_march_route(atmrt_ctx* c, int32_t index, int32_t
   if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_debug_last_march_route needs a frame: call atmrt_generate first");
   *route = (int32_t)c->last_march_route;
   return ATMRT_OK;
+}
+
+extern "C" int atmrt_debug_interp_blend(atmrt_ctx* c, uint32_t width, uint32_t height, const double* elev, const double* dir,
+                                        double min_elev_step, double min_dir_step, double simulation_step,
+                                        const atmrt_interp_lattice_t* lat, atmrt_result_t* out) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof *out);
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_interp_blend(k_, width, height, elev, dir, min_elev_step, min_dir_step, simulation_step, lat, out));
+  if (!elev || !dir || !lat) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: a NULL ray table or lattice");
+  if (!lat->hit_count || !lat->azimuth || !lat->elevation_angle || !lat->px_steps ||
+      (lat->n_hits && (!lat->lat || !lat->lon || !lat->distance || !lat->elevation || !lat->path_length || !lat->normal || !lat->color_tag || !lat->rgba)))
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: a NULL lattice plane");
+  const size_t npx = (size_t)width * height;
+  if (!width || !height || width > 65535 || height > 65535 || npx > ((size_t)1 << 24)) // a frame's sides are u16
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: an image of %u x %u pixels", width, height);
+  for (double step : {min_elev_step, min_dir_step, simulation_step})
+    if (!(step > 0.0) || !std::isfinite(step))
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: a step of %g is not finite and positive", step);
+  if (lat->ne <= 0 || lat->nd <= 0 || (int64_t)lat->ne * lat->nd > (int64_t)1 << 31)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: a lattice of %d x %d points", lat->nd, lat->ne);
+  const size_t nlat = (size_t)lat->ne * lat->nd;
+  std::vector<uint64_t> offset(nlat); // what launch_scan_counts leaves of the lattice frame's hit_count
+  uint64_t total = 0;
+  for (size_t q = 0; q < nlat; q++) offset[q] = total, total += lat->hit_count[q];
+  if (total != lat->n_hits)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: hit_count sums to %llu, n_hits is %llu", (unsigned long long)total,
+                   (unsigned long long)lat->n_hits);
+  for (uint64_t k = 0; k < total; k++)
+    if (lat->color_tag[k] != ATMRT_COLOR_TERRAIN && lat->color_tag[k] != ATMRT_COLOR_RGBA)
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: trace point %llu has the unknown colour tag %u", (unsigned long long)k,
+                     lat->color_tag[k]);
+  HIP_TRY(c, hipSetDevice(c->device));
+  c->last_valid = false; // the buffers of the last frame are about to be rewritten
+  hipStream_t s = c->stream;
+  Frame f{}; // what the blend reads of a frame: the image, its shard (all of it) and the step; an opaque frame sizes the least scratch
+  f.p.generator = ATMRT_GEN_INTERPOLATING_RECTILINEAR;
+  f.p.width = (uint16_t)width;
+  f.p.height = (uint16_t)height;
+  f.p.simulation_step = simulation_step;
+  f.wl = (int32_t)width;
+  f.h = (int32_t)height;
+  f.opaque = 1;
+  Workspace ws{};
+  int rc = prepare_workspace(c, f, &ws);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(ws.counters, 0, N_COUNTERS * sizeof(uint64_t), s));
+  DensePlanes dense;
+  HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, npx); }));
+  InterpBuffers ib{};
+  HIP_TRY(c, reserve_carved(c->d_interp, [&](Carve& k) {
+    k(ib.dir, npx * 8), k(ib.elev, npx * 8);
+    k(ib.rem_e, npx * 8), k(ib.rem_d, npx * 8), k(ib.key_e, npx * 4), k(ib.key_d, npx * 4), k(ib.bounds, 16);
+  }));
+  HIP_TRY(c, hipMemcpyAsync(ib.elev, elev, npx * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(ib.dir, dir, npx * 8, hipMemcpyHostToDevice, s));
+  PackedHits packed{};
+  uint64_t n_hits = 0;
+  rc = interp_blend_tail(c, f, ws, ib, min_elev_step, min_dir_step, dense, [&](int32_t ei0, int32_t di0, int64_t ne, int64_t nd, LatticeResult& lr) {
+    if (ne != lat->ne || nd != lat->nd)
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: the rays reference %lld x %lld lattice points from (%d, %d), the lattice has %d x %d",
+                     (long long)nd, (long long)ne, di0, ei0, lat->nd, lat->ne);
+    // the caller's planes where the lattice pass of a frame leaves its own
+    uint32_t* px_steps;
+    HIP_TRY(c, reserve_carved(c->d_px_steps, [&](Carve& k) { k(px_steps, nlat * sizeof(uint32_t)), k(ib.referenced, nlat); }));
+    HIP_TRY(c, hipMemsetAsync(ib.referenced, 0, nlat, s));
+    DensePlanes ldense;
+    HIP_TRY(c, reserve_carved(c->d_lat_dense, [&](Carve& k) { ldense = carve_dense(k, nlat); }));
+    PackedHits lpacked{};
+    HIP_TRY(c, reserve_carved(c->d_lat_packed, [&](Carve& k) { lpacked = carve_packed(k, total); }));
+    uint64_t* loffset;
+    HIP_TRY(c, reserve_into(c->d_lat_offset, loffset, nlat));
+    auto h2d = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); };
+    HIP_TRY(c, h2d(px_steps, lat->px_steps, nlat * 4));
+    HIP_TRY(c, h2d(ldense.hit_count, lat->hit_count, nlat * 4));
+    HIP_TRY(c, h2d(ldense.azimuth, lat->azimuth, nlat * 8));
+    HIP_TRY(c, h2d(ldense.elevation_angle, lat->elevation_angle, nlat * 8));
+    HIP_TRY(c, h2d(loffset, offset.data(), nlat * 8));
+    hipError_t e = hipSuccess;
+    if (total) packed_fields([&](size_t b, auto* to, auto* from) { if (e == hipSuccess) e = h2d(to, from, total * b); }, lpacked, *lat);
+    HIP_TRY(c, e);
+    HIP_TRY(c, hipStreamSynchronize(s)); // `offset` and the caller's arrays are pageable memory
+    lr.hit_count = ldense.hit_count;
+    lr.hit_offset = loffset;
+    lr.azimuth = ldense.azimuth;
+    lr.elevation_angle = ldense.elevation_angle;
+    lr.hits = lpacked;
+    lr.px_steps = px_steps;
+    return (int)ATMRT_OK;
+  }, &packed, &n_hits);
+  if (rc) return rc;
+  uint64_t counters[N_COUNTERS];
+  HIP_TRY(c, read_counters(ws, s, counters));
+  HIP_TRY(c, hipGetLastError());
+  return result_to_host(c, f, ws, dense, packed, n_hits, counters[CTR_RAY_STEPS], 0.0, out);
 }
 
 extern "C" int atmrt_math_probe(atmrt_ctx* c, int32_t op, size_t n, const double* a, const double* b, double* out0, double* out1) {

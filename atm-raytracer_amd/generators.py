@@ -155,6 +155,22 @@ class Context:
             assert n.value == out.size
         return out
 
+    def debug_interp_blend(self, elev, dir, min_elev_step, min_dir_step, simulation_step, lattice):
+        """Diagnostic (atmrt_debug_interp_blend): the last stage of an InterpolatingRectilinear frame — lattice keys, the 4-corner
+        blend, the step count — on the caller's rays (elev, dir: float64 [h][w], radians) and lattice (the dict _abi.interp_lattice
+        takes), run by the code the frame runs.  Returns what generate() returns: a ResultPixels."""
+        elev, dir = np.ascontiguousarray(elev, dtype=np.float64), np.ascontiguousarray(dir, dtype=np.float64)
+        assert elev.ndim == 2 and elev.shape == dir.shape
+        lat, keep = _abi.interp_lattice(lattice)
+        res = _abi.Result()
+        self.check(self.lib.atmrt_debug_interp_blend(self.handle, elev.shape[1], elev.shape[0], elev.ctypes.data, dir.ctypes.data, min_elev_step,
+                                                     min_dir_step, simulation_step, C.byref(lat), C.byref(res)))
+        del keep
+        try:
+            return ResultPixels(_abi.result_to_numpy(res))
+        finally:
+            self.lib.atmrt_result_free(C.byref(res))
+
     def fail_next_collective(self, index=0, nth=1):
         """Test hook (atmrt_debug_fail_next_collective)."""
         self.check(self.lib.atmrt_debug_fail_next_collective(self.handle, index, nth))

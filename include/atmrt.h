@@ -1108,6 +1108,42 @@ int atmrt_debug_march_order(atmrt_ctx* ctx, size_t cap, uint32_t* order, uint32_
  * test sees which one a frame took.  index: the device of a multi-device context, as in atmrt_ctx_tile_columns; a context of one
  * device takes -1 or 0.  ATMRT_ERR_STATE without a valid last frame. */
 int atmrt_debug_last_march_route(atmrt_ctx* ctx, int32_t index, int32_t* route);
+/* A lattice for atmrt_debug_interp_blend, host memory: ne rows (elevation keys, ascending) of nd points (direction keys, ascending),
+ * each what Cache::get_pixel (interpolating_rectilinear.rs:80-107) would hold for it — its ResultPixel and the ray steps computing it
+ * took.  The trace points of point q are hits [o(q), o(q) + hit_count[q]), o the running sum of hit_count in lattice order, laid out
+ * like the hit arrays of atmrt_result_t; n_hits must be the sum of hit_count, every color_tag an atmrt_color_tag. */
+typedef struct atmrt_interp_lattice {
+  int32_t ne, nd;
+  uint64_t n_hits;
+  const uint32_t* hit_count;     /* [ne][nd] */
+  const double* azimuth;         /* [ne][nd] */
+  const double* elevation_angle; /* [ne][nd] */
+  const uint32_t* px_steps;      /* [ne][nd] */
+  const double* lat;             /* [n_hits] */
+  const double* lon;
+  const double* distance;
+  const double* elevation;
+  const double* path_length;
+  const double* normal;          /* [n_hits][3] */
+  const uint32_t* color_tag;     /* [n_hits] */
+  const double* rgba;            /* [n_hits][4] */
+} atmrt_interp_lattice_t;
+/* A diagnostic in the spirit of atmrt_debug_step_trig, NOT part of the stable surface: the last stage of an InterpolatingRectilinear
+ * frame — FovData::cache_coords (:186-204), collect_trace_points, match_sequence, interpolate_trace_points and the angle blend
+ * (:213-418), the ray-step count of the referenced lattice points — run on a ray table and a lattice of the caller's, by the host
+ * function and the kernels the frame itself runs (k_lattice_keys, k_interp_blend, k_interp_blend_big, k_lattice_steps).  elev and dir
+ * are the rays of a width x height image, radians, row-major; min_elev_step, min_dir_step and simulation_step are what the frame
+ * derives from its field of view and takes from its parameters.  The lattice must be exactly the rectangle the frame would trace:
+ * rows floor(min elev / min_elev_step) .. floor(max elev / min_elev_step) + 1 and the columns likewise; the frame's own limits on it
+ * (at most 60000 rows, 2000000 columns, 2^31 points) hold.  `out` is filled as atmrt_generate fills it (release it with
+ * atmrt_result_free; device_ms stays 0).  Needs neither parameters nor terrain; a frame generated before is gone afterwards, as
+ * after a failed frame.  ATMRT_ERR_INVALID_ARGUMENT: NULL, an empty image, a side above 65535 or more than 2^24 pixels, a step that is not finite and
+ * positive, a lattice that is not that rectangle, an n_hits that is not the sum of hit_count, an unknown colour tag.  A multi-device
+ * context answers with its first device.  tests/test_gpu_interp_blend.py compares the result with tests/interp_blend_model.py, a
+ * model written from the reference's text: every bit must be equal. */
+int atmrt_debug_interp_blend(atmrt_ctx* ctx, uint32_t width, uint32_t height, const double* elev, const double* dir,
+                             double min_elev_step, double min_dir_step, double simulation_step,
+                             const atmrt_interp_lattice_t* lattice, atmrt_result_t* out);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ def test_struct_sizes_match_the_header(lib):
                                 _abi.Position, _abi.Frame, _abi.FrameStats, _abi.Timings, _abi.Coloring, _abi.DeviceHits, _abi.CommTimings,
                                 _abi.TempFunction)):
         assert lib.atmrt_abi_sizeof(which) == C.sizeof(st), st.__name__
+    assert lib.atmrt_abi_sizeof(40) == C.sizeof(_abi.InterpLattice) == 112 and lib.atmrt_abi_sizeof(39) == 0 and lib.atmrt_abi_sizeof(41) == 0
 
 
 def test_defaults_match_the_reference(lib):

@@ -254,7 +254,9 @@ def test_scene_objects_flat_earth(gpu_ctx, oracle_det):
 @pytest.mark.parametrize("kw", [{}, {"terrain_alpha": 0.5, "tilt": -4.0}, {"earth_shape": "Wgs84"}, {"fov": 100.0, "tilt": -8.0}],
                          ids=["opaque", "translucent", "wgs84", "wide-fov"])
 def test_interpolating_rectilinear(gpu_ctx, oracle_det, kw):
-    """InterpolatingRectilinear (interpolating_rectilinear.rs): lattice of Fast-style pixels + the 15-case 4-corner blend."""
+    """InterpolatingRectilinear (interpolating_rectilinear.rs): lattice of Fast-style pixels + the 15-case 4-corner blend.  A frame
+    reaches the arms of that blend its scene happens to produce; tests/test_gpu_interp_blend.py is where every one of the 15 cases,
+    accepted and rejected, is actually exercised, against a model written from the reference's text."""
     cfg, tiles = synth.scene("S2", 72, 40, generator="InterpolatingRectilinear", max_distance=80_000.0, **kw)
     got = run_gpu(gpu_ctx, cfg, tiles)
     assert got["n_hits"] > 0
