@@ -1,10 +1,10 @@
 // atmrt_api.hip — implementation of the C ABI in include/atmrt.h: context, terrain store (own DTED
-// parser), frame set-up and the launch sequence of each generator.  There is no CPU compute path:
+// parser), frame set-up and the launch sequence of each generator.  The calls that read a finished frame are in
+// atmrt_consumers.hip, the harness and debug probes in atmrt_probes.hip.  There is no CPU compute path:
 // without a HIP device atmrt_ctx_create fails with ATMRT_ERR_NO_DEVICE.
 #include <dirent.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -22,9 +22,6 @@
 #include "atmrt_hostmem.h"
 #include "atmrt_kernels.h"
 #include "atmrt_multi.h"
-#include "atmrt_polar_plan.h"
-#include "atmrt_render.h"
-#include "atmrt_shadow.h"
 #include "atmrt_tiff.h"
 
 using namespace atmrt;
@@ -681,21 +678,12 @@ static double escape_floor(const AtmTable& t, bool spherical, double radius, boo
   return std::max(top, from + step); // the stages of a step reach no lower than its start; one step of margin below that
 }
 
-static bool escape_enabled() {
-  const char* e = getenv("ATMRT_ESCAPE");
-  return !(e && !strcmp(e, "off"));
-}
+static bool escape_enabled() { return !env_off("ATMRT_ESCAPE"); }
 // ATMRT_STEP_TRIG=off: no table of the geodesic's sin / cos (Frame::xs_sin), every sample computes them (A/B runs, tests/test_gpu_step_trig.py)
-static bool step_trig_enabled() {
-  const char* e = getenv("ATMRT_STEP_TRIG");
-  return !(e && !strcmp(e, "off"));
-}
+static bool step_trig_enabled() { return !env_off("ATMRT_STEP_TRIG"); }
 // ATMRT_NORMAL_TRIG=off: no record of the epilogue's frame constants (Frame::normal_trig), every trace point computes them (A/B runs,
 // tests/test_gpu_normal_trig.py).  Read at every frame.
-static bool normal_trig_enabled() {
-  const char* e = getenv("ATMRT_NORMAL_TRIG");
-  return !(e && !strcmp(e, "off"));
-}
+static bool normal_trig_enabled() { return !env_off("ATMRT_NORMAL_TRIG"); }
 
 // ATMRT_CEILING=off: no terrain ceiling table (Frame::ceil), the march runs on the mosaic's top alone; =rebuild: the table is built
 // again in every frame, as for an observer that moves from frame to frame (A/B runs, tests/test_gpu_ceiling.py).  Read at every frame.
@@ -977,7 +965,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     // Rectilinear with scene objects: the lean march first (it leaves the rays that can meet an object to the general tracer and
     // lists them), then the tracer over that list
     HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
-    c->last_march_route = launch_rect_trace_count(f, ws, dense, s);
+    c->last.march_route = launch_rect_trace_count(f, ws, dense, s);
     uint64_t cnt[N_COUNTERS];
     HIP_TRY(c, read_counters(ws, s, cnt));
     launch_rect_trace_objects(f, ws, dense, cnt[CTR_OBJECT_RAYS], s);
@@ -990,7 +978,7 @@ static int run_core(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlan
     HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   } else {
     HIP_TRY(c, hipEventRecord(ev[EV_MARCH_BEGIN], s));
-    c->last_march_route = launch_rect_march(f, ws, dense, s, ev[EV_MARCH_END]);
+    c->last.march_route = launch_rect_march(f, ws, dense, s, ev[EV_MARCH_END]);
     HIP_TRY(c, hipEventRecord(ev[EV_FINALIZE_END], s));
   }
   HIP_TRY(c, hipEventRecord(ev[EV_PACK_BEGIN], s));
@@ -1143,16 +1131,16 @@ static int run_interpolating(atmrt_ctx* c, const Frame& f, Workspace& ws, const 
 }
 
 // Runs the generator named in params.  `dense` must be device memory.  When `want_packed`, the
-// packed trace points are left in c->d_packed (n_hits of them).
-static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlanes& dense, bool want_packed,
-                         PackedHits* packed_out, uint64_t* n_hits_out, uint64_t* ray_steps_out, double* ms_out) {
+// packed trace points are left in c->d_packed (n_hits of them).  What the frame left where is c->last.
+static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const DensePlanes& dense, bool want_packed, uint64_t* n_hits_out,
+                         uint64_t* ray_steps_out, double* ms_out) {
   hipStream_t s = c->stream;
   hipEvent_t* ev = c->ev;
   // the buffers of the previous frame are about to be reused (or reallocated): until this frame has succeeded there is nothing
   // atmrt_draw_image / atmrt_last_hits_device may touch
-  c->last_valid = false;
-  c->last_ceil_rows = 0;
-  c->last_march_route = MarchRoute::None; // run_core sets it where it launches the Rectilinear march
+  c->last.valid = false;
+  c->last.ceil_rows = 0;
+  c->last.march_route = MarchRoute::None; // run_core sets it where it launches the Rectilinear march
   c->stats = atmrt_frame_stats_t{};
   HIP_TRY(c, hipEventRecord(c->ev_t0, s));
   c->scan_segments = 0;
@@ -1217,29 +1205,23 @@ static int run_generator(atmrt_ctx* c, const Frame& f, Workspace& ws, const Dens
   c->stats.terrain_lookups = counters[CTR_TERRAIN_LOOKUPS];
   c->stats.object_rays = counters[CTR_OBJECT_RAYS];
   c->stats.object_steps = counters[CTR_OBJECT_STEPS];
-  c->last_ray_steps = counters[CTR_RAY_STEPS];
-  c->last_escaped_steps = counters[CTR_ESCAPED_STEPS];
-  c->last_escaped_rays = counters[CTR_ESCAPED_RAYS];
   if (ms_out) *ms_out = ms;
   if (ray_steps_out) *ray_steps_out = counters[CTR_RAY_STEPS];
-  if (packed_out) *packed_out = packed;
-  c->last_valid = true;
-  c->last_packed = want_packed || !f.opaque || f.p.generator == ATMRT_GEN_INTERPOLATING_RECTILINEAR;
-  c->last_npx = (size_t)f.wl * f.h;
-  c->last_wl = f.wl;
-  c->last_h = f.h;
-  c->last_c0 = f.c0;
-  c->last_alpha = f.p.terrain_alpha;
-  c->last_params = f.p;
-  c->last_dense = dense;
-  c->last_hits = packed;
-  c->last_offset = ws.hit_offset;
-  c->last_nhits = c->last_packed ? counters[CTR_HITS] : 0;
-  c->last_ceil_rows = f.ceil ? f.march_steps + 1 : 0;
-  c->last_ceil_layout = f.ceil_layout;
-  c->last_ceil_serial = c->ceiling.serial();
-  c->last_order_groups = f.ceil_order ? (uint32_t)(((size_t)f.wl * f.h + 63) / 64) : 0;
-  c->last_order_serial = c->ceil_order.serial();
+  LastFrame& l = c->last; // the frame has succeeded: everything of the record but march_route, which run_core has set
+  l.valid = true;
+  l.packed = want_packed || !f.opaque || f.p.generator == ATMRT_GEN_INTERPOLATING_RECTILINEAR;
+  l.npx = (size_t)f.wl * f.h;
+  l.wl = f.wl, l.h = f.h, l.c0 = f.c0;
+  l.alpha = f.p.terrain_alpha;
+  l.params = f.p;
+  l.dense = dense, l.hits = packed, l.offset = ws.hit_offset;
+  l.nhits = l.packed ? counters[CTR_HITS] : 0;
+  l.ray_steps = counters[CTR_RAY_STEPS], l.escaped_steps = counters[CTR_ESCAPED_STEPS], l.escaped_rays = counters[CTR_ESCAPED_RAYS];
+  l.ceil_rows = f.ceil ? f.march_steps + 1 : 0;
+  l.ceil_layout = f.ceil_layout;
+  l.ceil_serial = c->ceiling.serial();
+  l.order_groups = f.ceil_order ? (uint32_t)(((size_t)f.wl * f.h + 63) / 64) : 0;
+  l.order_serial = c->ceil_order.serial();
   return ATMRT_OK;
 }
 
@@ -1325,7 +1307,8 @@ extern "C" void atmrt_result_free(atmrt_result_t* r) {
   memset(r, 0, sizeof *r);
 }
 
-// One frame of this context's tile, everything left in HBM (shared by atmrt_generate_device and the multi-device paths).
+// One frame of this context's tile, everything left in HBM: the one generate sequence, of atmrt_generate, atmrt_generate_device and
+// the multi-device paths alike.
 int atmrt::api_generate_tile(atmrt_ctx* c, const DensePlanes* dense_in, bool want_packed, uint64_t* n_hits, uint64_t* ray_steps,
                              double* device_ms) {
   Frame f;
@@ -1340,16 +1323,17 @@ int atmrt::api_generate_tile(atmrt_ctx* c, const DensePlanes* dense_in, bool wan
     HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, (size_t)f.wl * f.h); }));
   }
   uint64_t nh = 0;
-  rc = run_generator(c, f, ws, dense, want_packed, nullptr, &nh, ray_steps, device_ms);
+  rc = run_generator(c, f, ws, dense, want_packed, &nh, ray_steps, device_ms);
   if (n_hits) *n_hits = nh;
   return rc;
 }
 
-// The frame (or the probe's image) that `dense`, ws.hit_offset and `packed` hold in HBM as a library-allocated atmrt_result_t.
-static int result_to_host(atmrt_ctx* c, const Frame& f, const Workspace& ws, const DensePlanes& dense, const PackedHits& packed,
+// The frame (or the probe's image) of wl x h pixels that `dense`, `hit_offset` and `packed` hold in HBM as a library-allocated
+// atmrt_result_t.
+static int result_to_host(atmrt_ctx* c, int wl, int h, const DensePlanes& dense, const uint64_t* hit_offset, const PackedHits& packed,
                           uint64_t n_hits, uint64_t steps, double ms, atmrt_result_t* out) {
-  const size_t npx = (size_t)f.wl * f.h;
-  if (atmrt_internal_result_alloc(out, (uint32_t)f.wl, (uint32_t)f.h, n_hits))
+  const size_t npx = (size_t)wl * h;
+  if (atmrt_internal_result_alloc(out, (uint32_t)wl, (uint32_t)h, n_hits))
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "out of host memory for %zu pixels / %llu hits", npx, (unsigned long long)n_hits);
   out->ray_steps = steps;
   out->device_ms = ms;
@@ -1358,7 +1342,7 @@ static int result_to_host(atmrt_ctx* c, const Frame& f, const Workspace& ws, con
   hipError_t e = d2h(out->azimuth, dense.azimuth, npx * 8);
   if (e == hipSuccess) e = d2h(out->elevation_angle, dense.elevation_angle, npx * 8);
   if (e == hipSuccess) e = d2h(out->hit_count, dense.hit_count, npx * 4);
-  if (e == hipSuccess) e = d2h(out->hit_offset, ws.hit_offset, npx * 8);
+  if (e == hipSuccess) e = d2h(out->hit_offset, hit_offset, npx * 8);
   if (e == hipSuccess) e = copy_packed(*out, packed, n_hits, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
@@ -1372,19 +1356,11 @@ extern "C" int atmrt_generate(atmrt_ctx* c, atmrt_result_t* out) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof *out);
   if (c->multi) return multi_generate(c, out); // every device its pixel-column tile, straight into the one [H][W] block
-  Frame f;
-  int rc = prepare_frame(c, &f);
-  if (rc) return rc;
-  Workspace ws{};
-  if ((rc = prepare_workspace(c, f, &ws))) return rc;
-  size_t npx = (size_t)f.wl * f.h;
-  DensePlanes dense;
-  HIP_TRY(c, reserve_carved(c->d_dense, [&](Carve& k) { dense = carve_dense(k, npx); }));
-  PackedHits packed{};
   uint64_t n_hits = 0, steps = 0;
   double ms = 0;
-  if ((rc = run_generator(c, f, ws, dense, true, &packed, &n_hits, &steps, &ms))) return rc;
-  return result_to_host(c, f, ws, dense, packed, n_hits, steps, ms, out);
+  if (int rc = api_generate_tile(c, nullptr, true, &n_hits, &steps, &ms)) return rc;
+  const LastFrame& l = c->last;
+  return result_to_host(c, l.wl, l.h, l.dense, l.offset, l.hits, n_hits, steps, ms, out);
 }
 
 extern "C" int atmrt_generate_device(atmrt_ctx* c, const atmrt_device_planes_t* planes, uint64_t* ray_steps,
@@ -1393,23 +1369,17 @@ extern "C" int atmrt_generate_device(atmrt_ctx* c, const atmrt_device_planes_t* 
   if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context leaves its frame in HBM through atmrt_generate_image_device");
   DensePlanes dense;
   if (!planes_from_abi(*planes, &dense)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every plane pointer must be a device allocation");
-  Frame f;
-  int rc = prepare_frame(c, &f);
-  if (rc) return rc;
-  Workspace ws{};
-  if ((rc = prepare_workspace(c, f, &ws))) return rc;
-  uint64_t n_hits = 0;
-  return run_generator(c, f, ws, dense, false, nullptr, &n_hits, ray_steps, device_ms);
+  return api_generate_tile(c, &dense, false, nullptr, ray_steps, device_ms);
 }
 
 extern "C" int atmrt_last_hits_device(atmrt_ctx* c, const atmrt_device_hits_t* dst, uint64_t* n_hits) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context hands its lists over through atmrt_image_hits_device");
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_last_hits_device needs a frame: call atmrt_generate_device first");
-  if (!c->last_packed)
+  if (!c->last.valid) return c->fail(ATMRT_ERR_STATE, "atmrt_last_hits_device needs a frame: call atmrt_generate_device first");
+  if (!c->last.packed)
     return c->fail(ATMRT_ERR_STATE, "the last frame holds first-hit planes only (opaque scene through atmrt_generate_device): "
                                     "its trace points are the planes themselves");
-  const uint64_t n = c->last_nhits;
+  const uint64_t n = c->last.nhits;
   if (n_hits) *n_hits = n;
   if (!dst) return ATMRT_OK; // size query
   if (dst->capacity < n)
@@ -1420,8 +1390,8 @@ extern "C" int atmrt_last_hits_device(atmrt_ctx* c, const atmrt_device_hits_t* d
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "every array pointer must be a device allocation");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  if (c->last_npx) HIP_TRY(c, hipMemcpyAsync(dst->hit_offset, c->last_offset, c->last_npx * 8, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(c, copy_packed(to, c->last_hits, n, hipMemcpyDeviceToDevice, s));
+  if (c->last.npx) HIP_TRY(c, hipMemcpyAsync(dst->hit_offset, c->last.offset, c->last.npx * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(c, copy_packed(to, c->last.hits, n, hipMemcpyDeviceToDevice, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return ATMRT_OK;
 }
@@ -1440,27 +1410,6 @@ extern "C" int atmrt_debug_fail_next_frame(atmrt_ctx* c) {
   return ATMRT_OK;
 }
 
-extern "C" int atmrt_debug_march_plan(int32_t width, int32_t height, int32_t samples, int32_t n_objects, uint64_t out[6]) {
-  if (!out || width < 0 || height < 0 || samples < 0 || n_objects < 0) return ATMRT_ERR_INVALID_ARGUMENT;
-  Frame f{};
-  f.p.generator = ATMRT_GEN_RECTILINEAR;
-  f.wl = width;
-  f.h = height;
-  f.n_t = samples;
-  f.n_objects = n_objects;
-  f.opaque = n_objects == 0; // (the plan of a frame over opaque terrain: translucent terrain is not sliced, like scenes with objects)
-  const MarchPlan plan = frame_march_plan(f, false);
-  const bool sliced = plan.route == MarchRoute::Sliced;
-  const SliceLayout& L = plan.slices;
-  out[0] = sliced ? 1 : 0;
-  out[1] = sliced ? L.n_groups : 0;
-  out[2] = sliced ? L.cap : 0;
-  out[3] = sliced ? L.bytes : 0;
-  out[4] = sliced ? L.slices_after : 0;
-  out[5] = MARCH_SLICE_STEPS;
-  return ATMRT_OK;
-}
-
 extern "C" int atmrt_last_stats(atmrt_ctx* c, atmrt_frame_stats_t* out) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) return multi_last_stats(c, out);
@@ -1471,1144 +1420,8 @@ extern "C" int atmrt_last_stats(atmrt_ctx* c, atmrt_frame_stats_t* out) {
 extern "C" int atmrt_last_march_work(atmrt_ctx* c, uint64_t* integrated_steps, uint64_t* escaped_rays) {
   if (!c || !integrated_steps || !escaped_rays) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) return multi_last_march_work(c, integrated_steps, escaped_rays);
-  *integrated_steps = c->last_ray_steps - c->last_escaped_steps;
-  *escaped_rays = c->last_escaped_rays;
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// renderer compositing + colouring
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_coloring_from_conf(const atmrt_params_t* params, int32_t kind, double water_level, double ambient_light,
-                                        double light_zenith_angle, double light_dir, int32_t palette, int32_t has_fog,
-                                        double fog_distance, atmrt_coloring_t* out) {
-  if (!params || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (palette != ATMRT_PALETTE_LEGACY && palette != ATMRT_PALETTE_IMPROVED) return ATMRT_ERR_INVALID_ARGUMENT;
-  return coloring_from_conf(*params, kind, water_level, ambient_light, light_zenith_angle, light_dir, palette, has_fog,
-                            fog_distance, *out)
-             ? ATMRT_ERR_INVALID_ARGUMENT
-             : ATMRT_OK;
-}
-
-extern "C" int atmrt_draw_image_device(atmrt_ctx* c, const atmrt_coloring_t* coloring, uint8_t* rgb_device) {
-  if (!c || !coloring || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context draws through atmrt_draw_image (host image) or atmrt_draw_image_gathered_device");
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_image needs a frame: call atmrt_generate first");
-  if (coloring->kind != ATMRT_COLORING_SIMPLE && coloring->kind != ATMRT_COLORING_SHADING)
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown coloring kind %d", coloring->kind);
-  if (coloring->has_fog && !(coloring->fog_distance > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "fog_distance must be positive");
-  HIP_TRY(c, hipSetDevice(c->device));
-  launch_draw_image(c->last_npx, *coloring, c->last_alpha, c->last_packed, c->last_dense.hit_count, c->last_offset, c->last_hits,
-                    c->last_dense, rgb_device, c->stream);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_draw_image(atmrt_ctx* c, const atmrt_coloring_t* coloring, uint8_t* rgb) {
-  if (!c || !coloring || !rgb) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (c->multi) return multi_draw_image(c, coloring, rgb);
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_image needs a frame: call atmrt_generate first");
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  HIP_TRY(c, c->d_io.reserve(3 * c->last_npx + 256));
-  int rc = atmrt_draw_image_device(c, coloring, c->d_io.as<uint8_t>());
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpy(rgb, c->d_io.ptr, 3 * c->last_npx, hipMemcpyDeviceToHost));
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// the annotations of renderer::output_image: ticks resolved on the host (W + H values), lines searched and drawn on the device
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-double diff_azimuth(double az1, double az2) { // renderer/mod.rs:28-37
-  const double diff = az1 - az2;
-  if (diff < -180.0) return diff + 360.0;
-  if (diff > 180.0) return diff - 360.0;
-  return diff;
-}
-
-// Iterator::min_by keeps the first of equal minima: strict `<` in ascending index.  (A NaN makes the reference panic in
-// partial_cmp().unwrap(); here it never wins.)
-bool azimuth_to_x(double azimuth, const double* row, int w, uint32_t* x) { // :39-59
-  int candidate = 0;
-  double best = std::fabs(diff_azimuth(azimuth, row[0]));
-  for (int i = 1; i < w; i++) {
-    const double d = std::fabs(diff_azimuth(azimuth, row[i]));
-    if (d < best || best != best) best = d, candidate = i;
-  }
-  const int neighbour = candidate == 0 ? 1 : candidate - 1;
-  const double diff_per_pixel = std::fabs(diff_azimuth(row[candidate], row[neighbour]));
-  *x = (uint32_t)candidate;
-  return std::fabs(diff_azimuth(row[candidate], azimuth)) < diff_per_pixel * 1.5;
-}
-
-bool elevation_to_y(double elevation, const double* col, int h, uint32_t* y) { // :61-80
-  int candidate = 0;
-  double best = std::fabs(elevation - col[0]);
-  for (int i = 1; i < h; i++) {
-    const double d = std::fabs(elevation - col[i]);
-    if (d < best || best != best) best = d, candidate = i;
-  }
-  const int neighbour = candidate == 0 ? 1 : candidate - 1;
-  const double diff_per_pixel = std::fabs(col[candidate] - col[neighbour]);
-  *y = (uint32_t)candidate;
-  return std::fabs(col[candidate] - elevation) < diff_per_pixel * 1.5;
-}
-
-int num_decimals(double x) { // :208-216; f64::round is half away from zero, like round()
-  double mul = 1.0;
-  for (int i = 0; i < 10; i++, mul *= 10.0) { // 10^i is exact below 10^23
-    const double mul_x = x * mul;
-    if (std::fabs(std::round(mul_x) - mul_x) < 0.001) return i;
-  }
-  return 10;
-}
-
-int round_decimals(const atmrt_tick_t* ticks, uint32_t n) { // :218-225; TickLike::angle is the step of a Multiple (params.rs:347-352)
-  int decimals = 0;
-  for (uint32_t i = 0; i < n; i++)
-    if (ticks[i].labelled) decimals = std::max(decimals, num_decimals(ticks[i].kind == ATMRT_TICK_SINGLE ? ticks[i].angle : ticks[i].step));
-  return decimals;
-}
-
-constexpr int OVERLAY_MAX_TICKS_PER_DEF = 1 << 20;
-
-const char* overlay_check(const atmrt_overlay_t& o) {
-  if ((o.n_ticks && !o.ticks) || (o.n_vertical_ticks && !o.vertical_ticks)) return "a tick list is NULL";
-  for (int v = 0; v < 2; v++) {
-    const atmrt_tick_t* t = v ? o.vertical_ticks : o.ticks;
-    for (uint32_t i = 0, n = v ? o.n_vertical_ticks : o.n_ticks; i < n; i++) {
-      if (t[i].kind != ATMRT_TICK_SINGLE && t[i].kind != ATMRT_TICK_MULTIPLE) return "unknown tick kind";
-      if (t[i].kind == ATMRT_TICK_MULTIPLE && !(t[i].step > 0.0 && t[i].step < INFINITY)) return "the step of a Multiple tick must be positive and finite";
-    }
-  }
-  return nullptr;
-}
-
-// gen_ticks (:227-268) over row 0 of the azimuth plane (w values) and column 0 of the elevation plane (h values); `out` sorted by
-// (vertical, pos).  The label is glibc's %.*f: correctly rounded from the binary value and signed like Rust's {:.N}.
-const char* resolve_ticks(const atmrt_params_t& p, const atmrt_overlay_t& o, const double* az, int w, const double* el, int h,
-                          std::vector<atmrt_drawn_tick_t>* out) {
-  out->clear();
-  for (int v = 0; v < 2; v++) {
-    const atmrt_tick_t* ticks = v ? o.vertical_ticks : o.ticks;
-    const uint32_t n = v ? o.n_vertical_ticks : o.n_ticks;
-    const int decimals = round_decimals(ticks, n);
-    std::map<uint32_t, atmrt_drawn_tick_t> at; // HashMap<u32, DrawTick>: the larger size stays, the earlier one when equal (:237-246)
-    auto put = [&](uint32_t pos, const atmrt_tick_t& t, double angle) {
-      atmrt_drawn_tick_t d{};
-      d.pos = pos, d.size = t.size, d.labelled = t.labelled ? 1 : 0, d.vertical = v;
-      snprintf(d.label, sizeof d.label, "%.*f", decimals, angle);
-      auto it = at.find(pos);
-      if (it == at.end()) at.emplace(pos, d);
-      else if (it->second.size < d.size) it->second = d;
-    };
-    for (uint32_t i = 0; i < n; i++) {
-      const atmrt_tick_t& t = ticks[i];
-      uint32_t pos;
-      if (t.kind == ATMRT_TICK_SINGLE) { // :89-106, :149-166
-        if (v ? elevation_to_y(t.angle, el, h, &pos) : azimuth_to_x(t.angle, az, w, &pos)) put(pos, t, t.angle);
-        continue;
-      }
-      int count = 0;
-      if (!v) { // :107-138: the UNWRAPPED current_az goes to azimuth_to_x, the wrapped one into the label
-        const double min_az = p.frame.direction - p.frame.fov / 2.0, max_az = p.frame.direction + p.frame.fov / 2.0;
-        for (double current_az = std::ceil((min_az - t.bias) / t.step) * t.step + t.bias; current_az < max_az; current_az += t.step) {
-          if (++count > OVERLAY_MAX_TICKS_PER_DEF) return "a Multiple tick yields more than 2^20 ticks";
-          const double azimuth = current_az < 0.0 ? current_az + 360.0 : current_az >= 360.0 ? current_az - 360.0 : current_az;
-          if (azimuth_to_x(current_az, az, w, &pos)) put(pos, t, azimuth);
-        }
-      } else { // :167-199: the folded elevation goes to elevation_to_y and into the label
-        const double aspect = (double)p.height / (double)p.width;
-        const double min_elev = p.frame.tilt - p.frame.fov * aspect / 2.0, max_elev = p.frame.tilt + p.frame.fov * aspect / 2.0;
-        for (double current_elev = std::ceil((min_elev - t.bias) / t.step) * t.step + t.bias; current_elev < max_elev; current_elev += t.step) {
-          if (++count > OVERLAY_MAX_TICKS_PER_DEF) return "a Multiple tick yields more than 2^20 ticks";
-          const double elevation = current_elev < -90.0 ? -180.0 - current_elev : current_elev > 90.0 ? 180.0 - current_elev : current_elev;
-          if (elevation_to_y(elevation, el, h, &pos)) put(pos, t, elevation);
-        }
-      }
-    }
-    for (const auto& kv : at) out->push_back(kv.second);
-  }
-  return nullptr;
-}
-
-bool earth_shape_is_flat(int32_t kind) { // EarthModel::to_shape, earth_model/mod.rs:95-112
-  return kind == ATMRT_EARTH_AZIMUTHAL_EQUIDISTANT || kind == ATMRT_EARTH_FLAT_DISTORTED || kind == ATMRT_EARTH_OBSERVER_AE ||
-         kind == ATMRT_EARTH_SIMPLE_OBSERVER_AE;
-}
-
-// What the entry points that read the context's own last frame ask first; 0, or a status with the message set.  on_multi: the rest
-// of the sentence a multi-device parent answers with, naming the feature's *_planes_device entry point.
-int frame_state_check(atmrt_ctx* c, const char* what, const char* on_multi) {
-  if (c->multi) return c->fail(ATMRT_ERR_STATE, "a multi-device context %s", on_multi);
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "%s needs a frame: call atmrt_generate first", what);
-  return ATMRT_OK;
-}
-int u16_size_check(atmrt_ctx* c, uint32_t width, uint32_t height) {
-  if (width > 65535 || height > 65535) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "width and height are u16 (params.rs:398-402)");
-  return ATMRT_OK;
-}
-// *k: the device context that owns the memory `ptr` points at (its stream, its buffers, its copy of the observer altitude): c
-// itself, or the sub-context of a multi-device c on the pointer's device.  `name` is the pointer's name in the messages.
-int planes_context(atmrt_ctx* c, const void* ptr, const char* name, atmrt_ctx** k) {
-  *k = c;
-  if (!c->multi) return ATMRT_OK;
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s is not a device allocation", name);
-  }
-  for (int i = 0; i < multi_size(c); i++)
-    if (multi_child(c, i)->device == attr.device) return *k = multi_child(c, i), ATMRT_OK;
-  return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s is in the memory of device %d, which is not a device of this context", name, attr.device);
-}
-
-// output_image's annotations (:419-431) over the planes `az`, `el` ([h][w], memory of c's device) of a frame c has generated with
-// the position and atmosphere still set (its observer altitude is in d_alt, its atmosphere table in d_atm).
-int draw_overlay_on(atmrt_ctx* c, atmrt_ctx* report, const atmrt_params_t& p, const atmrt_overlay_t& o, const double* az, const double* el,
-                    int w, int h, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
-  if (flat_horizon_deg) *flat_horizon_deg = NAN;
-  if (n_drawn) *n_drawn = 0;
-  if (w < 2 || h < 2) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "the overlay needs an image of at least 2 x 2 pixels, not %d x %d", w, h);
-  if (const char* msg = overlay_check(o)) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  HIP_TRY(report, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  std::vector<atmrt_drawn_tick_t> ticks;
-  if (o.n_ticks || o.n_vertical_ticks) { // row 0 and column 0: W + H doubles to the host
-    std::vector<double> az0(w), el0(h);
-    HIP_TRY(report, hipMemcpyAsync(az0.data(), az, (size_t)w * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(report, hipMemcpy2DAsync(el0.data(), 8, el, (size_t)w * 8, 8, (size_t)h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(report, hipStreamSynchronize(s));
-    if (const char* msg = resolve_ticks(p, o, az0.data(), w, el0.data(), h, &ticks)) return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  }
-  if (n_drawn) *n_drawn = ticks.size();
-  if (drawn && capacity < ticks.size())
-    return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "capacity %zu is less than the %zu ticks of the frame", capacity, ticks.size());
-  if (drawn) std::copy(ticks.begin(), ticks.end(), drawn);
-  const bool flat = o.show_flat_horizon && earth_shape_is_flat(p.earth.kind) && !p.straight_rays; // :420-422
-  const bool eye = o.show_eye_level != 0;
-  int n_cu = 0;
-  HIP_TRY(report, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-  const int bands = overlay_bands(w, h, n_cu);
-  struct DevTick {
-    uint32_t pos, size;
-    int32_t vertical, _pad;
-  };
-  const size_t tick_bytes = Carve::pad(ticks.size() * sizeof(DevTick)), sample_bytes = Carve::pad(4 * sizeof(double));
-  HIP_TRY(report, c->d_overlay.reserve(tick_bytes + sample_bytes + overlay_workspace_bytes(w, bands)));
-  char* base = c->d_overlay.as<char>();
-  double target = NAN;
-  if (flat) { // n at the observer's altitude through the library's own refr_n (k_atm_sample); acos and the degrees on the host
-    Frame f{};
-    f.atm = c->d_atm.as<AtmTable>();
-    double* d = reinterpret_cast<double*>(base + tick_bytes);
-    launch_atm_sample(f, 1, c->d_alt.as<double>(), d, d + 1, d + 2, d + 3, s);
-    double n_at_observer = 0.0;
-    HIP_TRY(report, hipMemcpyAsync(&n_at_observer, d + 2, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(report, hipStreamSynchronize(s));
-    target = std::acos(1.0 / n_at_observer) * (180.0 / M_PI); // f64::to_degrees
-    if (flat_horizon_deg) *flat_horizon_deg = target;
-  }
-  if (!ticks.empty()) {
-    std::vector<DevTick> dt(ticks.size());
-    for (size_t i = 0; i < ticks.size(); i++) dt[i] = DevTick{ticks[i].pos, ticks[i].size, ticks[i].vertical, 0};
-    HIP_TRY(report, hipMemcpyAsync(base, dt.data(), dt.size() * sizeof(DevTick), hipMemcpyHostToDevice, s));
-    HIP_TRY(report, hipStreamSynchronize(s)); // dt goes out of scope
-    launch_overlay_ticks(base, (int)dt.size(), w, h, rgb, s);
-  }
-  if (flat || eye) { // a NaN target is never close to anything: its line is all None
-    int32_t* y_of_x = nullptr;
-    launch_overlay_find_elev(el, w, h, bands, target, eye ? 0.0 : NAN, base + tick_bytes + sample_bytes, &y_of_x, s);
-    const uint8_t flat_color[3] = {0, 128, 255}, eye_color[3] = {255, 128, 255};
-    if (flat) launch_overlay_lines(y_of_x, w, h, rgb, flat_color, s);
-    if (eye) launch_overlay_lines(y_of_x + w, w, h, rgb, eye_color, s);
-  }
-  HIP_TRY(report, hipStreamSynchronize(s));
-  HIP_TRY(report, hipGetLastError());
-  return ATMRT_OK;
-}
-
-} // namespace
-
-extern "C" int atmrt_overlay_resolve_ticks(const atmrt_params_t* params, const atmrt_overlay_t* overlay, const double* azimuth_row0,
-                                           const double* elevation_col0, atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn) {
-  if (!params || !overlay || !azimuth_row0 || !elevation_col0 || !n_drawn) return ATMRT_ERR_INVALID_ARGUMENT;
-  *n_drawn = 0;
-  const bool whole = params->col_begin == 0 && params->col_end == 0;
-  const int w = whole ? params->width : (int)params->col_end - (int)params->col_begin, h = params->height;
-  if (w < 2 || h < 2 || overlay_check(*overlay)) return ATMRT_ERR_INVALID_ARGUMENT;
-  std::vector<atmrt_drawn_tick_t> ticks;
-  if (resolve_ticks(*params, *overlay, azimuth_row0, w, elevation_col0, h, &ticks)) return ATMRT_ERR_INVALID_ARGUMENT;
-  *n_drawn = ticks.size();
-  if (!drawn) return ATMRT_OK;
-  if (capacity < ticks.size()) return ATMRT_ERR_INVALID_ARGUMENT;
-  std::copy(ticks.begin(), ticks.end(), drawn);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_draw_overlay_device(atmrt_ctx* c, const atmrt_overlay_t* overlay, uint8_t* rgb_device, atmrt_drawn_tick_t* drawn,
-                                         size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
-  if (!c || !overlay || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = frame_state_check(c, "atmrt_draw_overlay", "draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device")) return rc;
-  return draw_overlay_on(c, c, c->last_params, *overlay, c->last_dense.azimuth, c->last_dense.elevation_angle, c->last_wl, c->last_h,
-                         rgb_device, drawn, capacity, n_drawn, flat_horizon_deg);
-}
-
-extern "C" int atmrt_draw_overlay(atmrt_ctx* c, const atmrt_overlay_t* overlay, uint8_t* rgb, atmrt_drawn_tick_t* drawn, size_t capacity,
-                                  size_t* n_drawn, double* flat_horizon_deg) {
-  if (!c || !overlay || !rgb) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = frame_state_check(c, "atmrt_draw_overlay", "draws its overlay on the gathered planes: atmrt_draw_overlay_planes_device")) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_io.reserve(3 * c->last_npx + 256));
-  HIP_TRY(c, hipMemcpy(c->d_io.ptr, rgb, 3 * c->last_npx, hipMemcpyHostToDevice));
-  int rc = atmrt_draw_overlay_device(c, overlay, c->d_io.as<uint8_t>(), drawn, capacity, n_drawn, flat_horizon_deg);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpy(rgb, c->d_io.ptr, 3 * c->last_npx, hipMemcpyDeviceToHost));
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_draw_overlay_planes_device(atmrt_ctx* c, const atmrt_overlay_t* overlay, const double* azimuth,
-                                                const double* elevation_angle, uint32_t width, uint32_t height, uint8_t* rgb_device,
-                                                atmrt_drawn_tick_t* drawn, size_t capacity, size_t* n_drawn, double* flat_horizon_deg) {
-  if (!c || !overlay || !azimuth || !elevation_angle || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = u16_size_check(c, width, height)) return rc;
-  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "atmrt_set_params has not been called");
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, rgb_device, "rgb_device", &k)) return rc;
-  if (!k->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_overlay_planes_device needs a frame: call atmrt_generate_image_device first");
-  return draw_overlay_on(k, c, c->params, *overlay, azimuth, elevation_angle, (int)width, (int)height, rgb_device, drawn, capacity, n_drawn,
-                         flat_horizon_deg);
-}
-
-// ---------------------------------------------------------------------------------------------
-// the visibility map: the frame's trace points binned over a latitude / longitude grid (kernels: atmrt_vismap.h)
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_geo_grid_cell(const atmrt_geo_grid_t* g, double lat, double lon, int64_t* cell) {
-  if (!g || !cell) return ATMRT_ERR_INVALID_ARGUMENT;
-  *cell = -1;
-  if (geo_grid_check(*g)) return ATMRT_ERR_INVALID_ARGUMENT;
-  *cell = geo_grid_cell(*g, lat, lon);
-  return ATMRT_OK;
-}
-
-namespace {
-
-// The trace points of c's last frame that a mode reads.  ATMRT_VIS_ALL reads the packed lists where the frame has them; a frame
-// without lists holds one point per pixel at most, in its planes, and ALL is FIRST.
-TracePoints last_frame_points(const atmrt_ctx* c, int32_t mode) {
-  const uint32_t width = (uint32_t)c->last_wl;
-  const PackedHits& l = c->last_hits;
-  const DensePlanes& d = c->last_dense;
-  if (mode == ATMRT_VIS_ALL && c->last_packed) return TracePoints{c->last_npx, width, d.hit_count, c->last_offset, l.lat, l.lon, l.distance, l.elevation};
-  return TracePoints{c->last_npx, width, d.hit_count, nullptr, d.lat, d.lon, d.distance, d.elevation};
-}
-
-bool vis_aggregate() { // read at every call, like ATMRT_ESCAPE
-  const char* e = getenv("ATMRT_VIS_AGGREGATE");
-  return !(e && !strcmp(e, "off"));
-}
-
-// k: the context whose device holds the memory; report: the context the caller handed in (its parent on a multi-device context).
-// grid == nullptr: only the bounds.
-int vis_run(atmrt_ctx* k, atmrt_ctx* report, const TracePoints& src, const atmrt_geo_grid_t* grid, uint32_t* count, double* min_distance,
-            atmrt_visibility_stats_t* stats, double* bounds) {
-  HIP_TRY(report, hipSetDevice(k->device));
-  hipStream_t s = k->stream;
-  HIP_TRY(report, k->d_vis.reserve(vis_block_bytes()));
-  launch_vis_reset(k->d_vis.ptr, s);
-  if (grid) launch_vis_map(src, *grid, vis_aggregate(), count, min_distance, k->d_vis.ptr, s);
-  else launch_vis_bounds(src, k->d_vis.ptr, s);
-  uint64_t block[16] = {};
-  HIP_TRY(report, hipMemcpyAsync(block, k->d_vis.ptr, vis_block_bytes(), hipMemcpyDeviceToHost, s));
-  HIP_TRY(report, hipStreamSynchronize(s));
-  HIP_TRY(report, hipGetLastError());
-  vis_block_decode(block, stats, bounds);
-  return ATMRT_OK;
-}
-
-int vis_mode_check(atmrt_ctx* c, int32_t mode) {
-  if (mode != ATMRT_VIS_FIRST && mode != ATMRT_VIS_ALL) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown visibility mode %d", mode);
-  return ATMRT_OK;
-}
-// the checks every map entry point shares; 0 or a status with the message set
-int vis_check(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, const void* count) {
-  if (!grid) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "grid is NULL");
-  if (!count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "count is NULL");
-  if (int rc = vis_mode_check(c, mode)) return rc;
-  if (const char* msg = geo_grid_check(*grid)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  return ATMRT_OK;
-}
-
-} // namespace
-
-extern "C" int atmrt_frame_bounds(atmrt_ctx* c, int32_t mode, double out[4]) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = vis_mode_check(c, mode)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_frame_bounds", "has no frame of its own: atmrt_frame_bounds works on the gathered planes through atmrt_visibility_map_planes_device")) return rc;
-  return vis_run(c, c, last_frame_points(c, mode), nullptr, nullptr, nullptr, nullptr, out);
-}
-
-extern "C" int atmrt_visibility_map_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count_device,
-                                           double* min_distance_device, atmrt_visibility_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = vis_check(c, grid, mode, count_device)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_visibility_map", "has no frame of its own: atmrt_visibility_map works on the gathered planes through atmrt_visibility_map_planes_device")) return rc;
-  return vis_run(c, c, last_frame_points(c, mode), grid, count_device, min_distance_device, stats, nullptr);
-}
-
-extern "C" int atmrt_visibility_map(atmrt_ctx* c, const atmrt_geo_grid_t* grid, int32_t mode, uint32_t* count, double* min_distance,
-                                    atmrt_visibility_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = vis_check(c, grid, mode, count)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_visibility_map", "has no frame of its own: atmrt_visibility_map works on the gathered planes through atmrt_visibility_map_planes_device")) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n_cells = (size_t)grid->n_lat * grid->n_lon, count_bytes = Carve::pad(n_cells * sizeof(uint32_t));
-  HIP_TRY(c, c->d_io.reserve(count_bytes + n_cells * sizeof(double)));
-  uint32_t* d_count = c->d_io.as<uint32_t>();
-  double* d_min = min_distance ? reinterpret_cast<double*>(c->d_io.as<char>() + count_bytes) : nullptr;
-  if (int rc = atmrt_visibility_map_device(c, grid, mode, d_count, d_min, stats)) return rc;
-  HIP_TRY(c, hipMemcpy(count, d_count, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (min_distance) HIP_TRY(c, hipMemcpy(min_distance, d_min, n_cells * sizeof(double), hipMemcpyDeviceToHost));
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_visibility_map_planes_device(atmrt_ctx* c, const atmrt_geo_grid_t* grid, const double* lat, const double* lon,
-                                                  const double* distance, const uint32_t* hit_count, uint32_t width, uint32_t height,
-                                                  uint32_t* count_device, double* min_distance_device, atmrt_visibility_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = vis_check(c, grid, ATMRT_VIS_FIRST, count_device)) return rc;
-  if (!lat || !lon || !distance || !hit_count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a plane is NULL");
-  if (int rc = u16_size_check(c, width, height)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, count_device, "count_device", &k)) return rc;
-  return vis_run(k, c, TracePoints{(size_t)width * height, width, hit_count, nullptr, lat, lon, distance, nullptr}, grid, count_device, min_distance_device, stats,
-                 nullptr);
-}
-
-// ---------------------------------------------------------------------------------------------
-// landmarks: the nearest trace point of each latitude / longitude (kernels: atmrt_landmarks.h)
-// ---------------------------------------------------------------------------------------------
-extern "C" int atmrt_landmark_d2(const atmrt_landmark_t* l, double lat, double lon, double* d2) {
-  if (!l || !d2) return ATMRT_ERR_INVALID_ARGUMENT;
-  *d2 = landmark_d2(*l, lat, lon);
-  return ATMRT_OK;
-}
-
-namespace {
-
-constexpr size_t LM_MAX = (size_t)1 << 20;        // landmarks per call
-constexpr uint64_t LM_MAX_ITEMS = 1ull << 24;     // entries of the index: coarser cells above that
-constexpr double LM_WORLD = 1e300;                // the index looks no further than this many degrees (a frame's coordinates are degrees)
-
-// The bucket index of one call: cell c of `grid` lists the landmarks items[cell_start[c] .. cell_start[c + 1]), in ascending order.
-// It is a FILTER for the exact rule landmark_d2(l, lat, lon) <= r2 and may only ever add candidates:
-//  * a landmark's box is +-r in lat and +-r / lon_scale in lon, PADDED by far more than rounding can move a pair (d2 <= r2 bounds
-//    |lat - l.lat| by r (1 + a few 2^-53); the padding is r 1e-6, plus 1e-12 of the magnitudes involved for the rounding of the box's
-//    own corners, plus 1e-150 for a radius whose square underflows, where d2 <= 0 admits differences up to 1.6e-162);
-//  * the cells a box covers are found with the floor rule of geo_grid_cell itself, applied to the box's corners: the rule is
-//    monotone in lat and in lon, so every point inside the box falls into a cell between those of the corners.
-// Landmarks whose box misses `bounds` (the frame's, {lat_min, lat_max, lon_min, lon_max}; NaN: no point at all) are in no cell.
-// The grid covers the intersection of the bounds and the boxes' hull with cells of 2r x 2r / (largest lon_scale) or larger: at most
-// 2000 per axis (2^22 cells in all), about 64 cells per landmark, and doubled until the index holds at most LM_MAX_ITEMS entries.
-struct LandmarkIndex {
-  atmrt_geo_grid_t grid{0.0, 0.0, 1.0, 1.0, 1u, 1u};
-  std::vector<uint32_t> cell_start{0u, 0u}, items;
-};
-
-struct LmBox {
-  double lat_lo, lat_hi, lon_lo, lon_hi;
-};
-LmBox landmark_box(const atmrt_landmark_t& l, double r) {
-  const double w = r / l.lon_scale;
-  const double h_lat = r + (r * 1e-6 + (fabs(l.lat) + r) * 1e-12 + 1e-150), h_lon = w + (w * 1e-6 + (fabs(l.lon) + w) * 1e-12 + 1e-150);
-  return LmBox{l.lat - h_lat, l.lat + h_lat, l.lon - h_lon, l.lon + h_lon};
-}
-// the floor rule of geo_grid_cell on one axis, clamped to the grid's cells
-uint32_t lm_axis_cell(double v, double v0, double cell, uint32_t n) {
-  const double f = dm_floor((v - v0) / cell);
-  if (!(f > 0.0)) return 0u;
-  return f < (double)n ? (uint32_t)f : n - 1u;
-}
-
-LandmarkIndex landmark_index(const atmrt_landmark_t* lm, size_t n, double r, const double bounds[4]) {
-  LandmarkIndex ix;
-  std::vector<uint32_t> alive;
-  std::vector<LmBox> boxes;
-  double hull[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY}, scale_max = 0.0;
-  for (size_t i = 0; i < n; i++) {
-    const LmBox b = landmark_box(lm[i], r);
-    if (!(b.lat_hi >= bounds[0] && b.lat_lo <= bounds[1] && b.lon_hi >= bounds[2] && b.lon_lo <= bounds[3])) continue; // NaN bounds: none
-    alive.push_back((uint32_t)i), boxes.push_back(b);
-    hull[0] = fmin(hull[0], b.lat_lo), hull[1] = fmax(hull[1], b.lat_hi), hull[2] = fmin(hull[2], b.lon_lo), hull[3] = fmax(hull[3], b.lon_hi);
-    scale_max = fmax(scale_max, lm[i].lon_scale);
-  }
-  if (alive.empty()) return ix;
-  const double lat_lo = fmax(fmax(hull[0], bounds[0]), -LM_WORLD), lat_hi = fmin(fmin(hull[1], bounds[1]), LM_WORLD);
-  const double lon_lo = fmax(fmax(hull[2], bounds[2]), -LM_WORLD), lon_hi = fmin(fmin(hull[3], bounds[3]), LM_WORLD);
-  if (!(lat_lo <= lat_hi && lon_lo <= lon_hi)) return ix;
-  const double per_axis = fmin(2000.0, fmax(16.0, ceil(sqrt(64.0 * (double)alive.size()))));
-  double cell_lat = fmax(2.0 * r, (lat_hi - lat_lo) / per_axis), cell_lon = fmax(2.0 * r / scale_max, (lon_hi - lon_lo) / per_axis);
-  std::vector<uint32_t> i0(alive.size()), i1(alive.size()), j0(alive.size()), j1(alive.size());
-  for (;; cell_lat *= 2.0, cell_lon *= 2.0) {
-    atmrt_geo_grid_t& g = ix.grid;
-    g = atmrt_geo_grid_t{lat_lo, lon_lo, cell_lat, cell_lon, 1u, 1u};
-    // the rule's own answer for the far corner decides the cell counts: every point of the region falls into a cell
-    g.n_lat = (uint32_t)fmin(dm_floor((lat_hi - lat_lo) / cell_lat), 4095.0) + 1u;
-    g.n_lon = (uint32_t)fmin(dm_floor((lon_hi - lon_lo) / cell_lon), 4095.0) + 1u;
-    uint64_t total = 0;
-    for (size_t a = 0; a < alive.size(); a++) {
-      const LmBox& b = boxes[a];
-      i0[a] = lm_axis_cell(b.lat_lo, lat_lo, cell_lat, g.n_lat), i1[a] = lm_axis_cell(b.lat_hi, lat_lo, cell_lat, g.n_lat);
-      j0[a] = lm_axis_cell(b.lon_lo, lon_lo, cell_lon, g.n_lon), j1[a] = lm_axis_cell(b.lon_hi, lon_lo, cell_lon, g.n_lon);
-      total += (uint64_t)(i1[a] - i0[a] + 1u) * (j1[a] - j0[a] + 1u);
-    }
-    if (total <= LM_MAX_ITEMS || (g.n_lat == 1u && g.n_lon == 1u)) break;
-  }
-  const atmrt_geo_grid_t& g = ix.grid;
-  const size_t n_cells = (size_t)g.n_lat * g.n_lon;
-  ix.cell_start.assign(n_cells + 1, 0u);
-  for (size_t a = 0; a < alive.size(); a++)
-    for (uint32_t i = i0[a]; i <= i1[a]; i++)
-      for (uint32_t j = j0[a]; j <= j1[a]; j++) ix.cell_start[(size_t)i * g.n_lon + j + 1]++;
-  for (size_t c = 0; c < n_cells; c++) ix.cell_start[c + 1] += ix.cell_start[c];
-  ix.items.resize(ix.cell_start[n_cells]);
-  std::vector<uint32_t> fill(ix.cell_start.begin(), ix.cell_start.end() - 1);
-  for (size_t a = 0; a < alive.size(); a++)
-    for (uint32_t i = i0[a]; i <= i1[a]; i++)
-      for (uint32_t j = j0[a]; j <= j1[a]; j++) ix.items[fill[(size_t)i * g.n_lon + j]++] = alive[a];
-  return ix;
-}
-
-// what every landmark entry point refuses; nullptr when the arguments are fine
-const char* landmark_args_check(const atmrt_landmark_t* lm, size_t n, double radius_deg) {
-  if (!lm) return "landmarks is NULL";
-  if (n == 0 || n > LM_MAX) return "the number of landmarks must lie in [1, 2^20]";
-  if (!(radius_deg > 0.0 && radius_deg <= 1.0)) return "radius_deg must be finite, positive and at most 1 degree";
-  for (size_t i = 0; i < n; i++)
-    if (const char* msg = landmark_check(lm[i])) return msg;
-  return nullptr;
-}
-
-// k: the context whose device holds the frame; report: the context the caller handed in (vis_run).
-int landmarks_run(atmrt_ctx* k, atmrt_ctx* report, const TracePoints& src, const atmrt_landmark_t* lm, size_t n, double radius_deg,
-                  atmrt_landmark_hit_t* hits, atmrt_landmark_stats_t* stats) {
-  double bounds[4];
-  if (int rc = vis_run(k, report, src, nullptr, nullptr, nullptr, nullptr, bounds)) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  const LandmarkIndex host = landmark_index(lm, n, radius_deg, bounds);
-  report->lm_timings[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  HIP_TRY(report, hipSetDevice(k->device));
-  hipStream_t s = k->stream;
-  LmIndex ix{host.grid, nullptr, nullptr, nullptr, radius_deg * radius_deg};
-  LmState st{};
-  atmrt_landmark_hit_t* d_hits = nullptr;
-  uint32_t *d_start = nullptr, *d_items = nullptr;
-  atmrt_landmark_t* d_lm = nullptr;
-  HIP_TRY(report, reserve_carved(k->d_landmarks, [&](Carve& c) {
-    c(d_lm, n * sizeof(atmrt_landmark_t)), c(d_start, host.cell_start.size() * sizeof(uint32_t)), c(d_items, host.items.size() * sizeof(uint32_t));
-    c(st.count, n * sizeof(uint32_t)), c(st.d2min, n * sizeof(unsigned long long)), c(st.key, n * sizeof(unsigned long long));
-    c(st.ctr, LM_N * sizeof(unsigned long long)), c(d_hits, n * sizeof(atmrt_landmark_hit_t));
-  }));
-  ix.cell_start = d_start, ix.items = d_items, ix.lm = d_lm;
-  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_BEGIN], s));
-  HIP_TRY(report, hipMemcpyAsync(d_lm, lm, n * sizeof(atmrt_landmark_t), hipMemcpyHostToDevice, s));
-  HIP_TRY(report, hipMemcpyAsync(d_start, host.cell_start.data(), host.cell_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  if (!host.items.empty()) HIP_TRY(report, hipMemcpyAsync(d_items, host.items.data(), host.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  launch_lm_reset(n, st, s);
-  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_UPLOADED], s));
-  launch_lm_pass(false, src, ix, st, s);
-  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_FIRST_PASS], s));
-  launch_lm_pass(true, src, ix, st, s);
-  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_SECOND_PASS], s));
-  launch_lm_finish(n, src, st, d_hits, s);
-  HIP_TRY(report, hipEventRecord(k->ev[EV_LM_END], s));
-  unsigned long long block[LM_N] = {};
-  HIP_TRY(report, hipMemcpyAsync(hits, d_hits, n * sizeof(atmrt_landmark_hit_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(report, hipMemcpyAsync(block, st.ctr, sizeof block, hipMemcpyDeviceToHost, s));
-  HIP_TRY(report, hipStreamSynchronize(s));
-  HIP_TRY(report, hipGetLastError());
-  for (int i = 0; i < 4; i++) {
-    float ms = 0.0f;
-    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[EV_LM_BEGIN + i], k->ev[EV_LM_BEGIN + i + 1]));
-    report->lm_timings[1 + i] = ms;
-  }
-  if (stats) *stats = atmrt_landmark_stats_t{block[LM_POINTS], block[LM_SKIPPED], block[LM_TESTED], block[LM_WITHIN]};
-  return ATMRT_OK;
-}
-
-} // namespace
-
-extern "C" int atmrt_locate_landmarks(atmrt_ctx* c, const atmrt_landmark_t* landmarks, size_t n, double radius_deg, int32_t mode,
-                                      atmrt_landmark_hit_t* hits, atmrt_landmark_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (const char* msg = landmark_args_check(landmarks, n, radius_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  if (!hits) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "hits is NULL");
-  if (int rc = vis_mode_check(c, mode)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_locate_landmarks", "has no frame of its own: atmrt_locate_landmarks works on the gathered planes through atmrt_locate_landmarks_planes_device")) return rc;
-  return landmarks_run(c, c, last_frame_points(c, mode), landmarks, n, radius_deg, hits, stats);
-}
-
-extern "C" int atmrt_locate_landmarks_planes_device(atmrt_ctx* c, const atmrt_landmark_t* landmarks, size_t n, double radius_deg,
-                                                    const double* lat, const double* lon, const double* distance, const double* elevation,
-                                                    const uint32_t* hit_count, uint32_t width, uint32_t height, atmrt_landmark_hit_t* hits,
-                                                    atmrt_landmark_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (const char* msg = landmark_args_check(landmarks, n, radius_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s", msg);
-  if (!hits) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "hits is NULL");
-  if (!lat || !lon || !distance || !elevation || !hit_count) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a plane is NULL");
-  if (int rc = u16_size_check(c, width, height)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, lat, "lat", &k)) return rc;
-  return landmarks_run(k, c, TracePoints{(size_t)width * height, width, hit_count, nullptr, lat, lon, distance, elevation}, landmarks, n, radius_deg, hits,
-                       stats);
-}
-
-extern "C" int atmrt_last_landmark_timings(atmrt_ctx* c, double out[5]) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  memcpy(out, c->lm_timings, sizeof c->lm_timings);
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_landmark_index_probe(const atmrt_landmark_t* landmarks, size_t n, double radius_deg, const double bounds[4],
-                                          const double* lat, const double* lon, size_t n_points, uint64_t* offsets, uint32_t* items,
-                                          size_t capacity, size_t* n_items) {
-  if (!n_items) return ATMRT_ERR_INVALID_ARGUMENT;
-  *n_items = 0;
-  if (landmark_args_check(landmarks, n, radius_deg) || !bounds || !offsets || (n_points && (!lat || !lon))) return ATMRT_ERR_INVALID_ARGUMENT;
-  const LandmarkIndex ix = landmark_index(landmarks, n, radius_deg, bounds);
-  std::vector<int64_t> cell(n_points);
-  size_t need = 0;
-  for (size_t i = 0; i < n_points; i++) {
-    cell[i] = geo_grid_cell(ix.grid, lat[i], lon[i]);
-    if (cell[i] >= 0) need += ix.cell_start[cell[i] + 1] - ix.cell_start[cell[i]];
-  }
-  *n_items = need;
-  if (need > capacity || (need && !items)) return ATMRT_ERR_INVALID_ARGUMENT;
-  size_t at = 0;
-  for (size_t i = 0; i < n_points; i++) {
-    offsets[i] = at;
-    if (cell[i] >= 0)
-      for (uint32_t k = ix.cell_start[cell[i]]; k < ix.cell_start[cell[i] + 1]; k++) items[at++] = ix.items[k];
-  }
-  offsets[n_points] = at;
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// cast shadows: which of a frame's first trace points the light reaches (kernels: atmrt_shadow.h; the rule: include/atmrt.h)
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-// ATMRT_SHADOW_ESCAPE=off: every ray marches to m or to its block (A/B runs, tests/test_gpu_shadows.py).  Read at every call.
-bool shadow_escape_enabled() {
-  const char* e = getenv("ATMRT_SHADOW_ESCAPE");
-  return !(e && !strcmp(e, "off"));
-}
-
-// what every shadow entry point asks of reach and lift and of the context's parameters; *m: the samples to reach, the first index
-// with d_m >= reach (atmrt_polar_plan.h).  0 or a status with the message set
-int shadow_reach_check(atmrt_ctx* c, const char* what, double reach, double lift, int32_t* m) {
-  if (!(std::isfinite(reach) && reach > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: reach must be finite and positive", what);
-  if (!(std::isfinite(lift) && lift >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: lift must be finite and not negative", what);
-  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
-  if (!(c->params.simulation_step > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: simulation_step must be positive", what);
-  const int32_t steps = lattice_steps(c->params.simulation_step, reach, SHADOW_M_MAX);
-  if (steps < 0) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: reach lies more than 65535 samples away", what);
-  *m = steps;
-  return ATMRT_OK;
-}
-
-// what the entry points of one light ask beyond that
-int shadow_check(atmrt_ctx* c, const char* what, const atmrt_shadow_spec_t* spec, const void* status, int32_t* m) {
-  if (!spec || !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or status is NULL", what);
-  if (!std::isfinite(spec->azimuth_deg)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: azimuth_deg is not finite", what);
-  if (!(std::isfinite(spec->elevation_deg) && spec->elevation_deg > -90.0 && spec->elevation_deg < 90.0))
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: elevation_deg must lie strictly between -90 and 90", what);
-  return shadow_reach_check(c, what, spec->reach, spec->lift, m);
-}
-
-// what the two entry points on the caller's planes ask of them
-int shadow_planes_check(atmrt_ctx* c, const char* what, size_t n_pixels, const uint32_t* hit_count, const double* lat, const double* lon, const double* elev) {
-  if (!hit_count || !lat || !lon || !elev) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: a plane is NULL", what);
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must lie in [1, 2^32 - 1]", what);
-  return ATMRT_OK;
-}
-
-// The floor of the escape shortcut for THIS call, from the context's cached certificate and the mosaic's top (Frame::esc_floor is a
-// Rectilinear frame's only; the shadowed frame may be a Fast one).  The certificate is stated "to max_distance", but nothing in its
-// argument depends on a distance: above `from`, r'' > 0 whatever r' is, so a ray with dr/dphi > 0 there ascends for as long as it
-// is integrated — the bound holds for any reach.  What does depend on the distance is the straight spherical ray's convexity
-// (esc_ang_max): it is evaluated for this call's reach, one step past it (d_m < reach + step).  No certificate (flat earth,
-// refracted; an atmosphere the sweep refuses): +inf, every ray marches to m.
-double shadow_escape_floor(const atmrt_ctx* k, Frame& f, double reach) {
-  f.esc_floor = INFINITY; // the frame's own floor is not this call's
-  f.esc_ang_max = INFINITY;
-  if (!shadow_escape_enabled()) return INFINITY;
-  const double step = f.p.simulation_step;
-  if (f.p.straight_rays) {
-    if (k->earth.spherical) f.esc_ang_max = 1.5207963267948966 - (reach + step) * f.inv_shape_radius;
-    return k->tv.skip_above;
-  }
-  if (!k->earth.spherical) return INFINITY;
-  return std::max(k->tv.skip_above, k->escape.value().from + step);
-}
-
-struct ShadowDownload { // a plane the host asked for (host null: not this one), downloaded inside the call's timed window
-  void* host;
-  const void* dev;
-  size_t bytes;
-};
-
-// One shadow call around its kernels, for a ShadowJob or a ShadowLightsJob with its source, its m and its planes filled in.
-// k: the context whose device holds the memory and whose setting is used; report: the context the caller handed in.
-// carve_more: what the call carves from d_shadow beside the list and the counters; launch: its uploads and its kernels.
-template <class Job>
-int shadow_call(atmrt_ctx* k, atmrt_ctx* report, double reach, Job& job, const std::function<void(Carve&)>& carve_more,
-                const std::function<int(const Frame&, hipStream_t)>& launch, std::initializer_list<ShadowDownload> downloads, atmrt_shadow_stats_t* stats) {
-  Frame f;
-  if (int rc = prepare_frame(k, &f)) {
-    if (k != report) report->error = k->error;
-    return rc;
-  }
-  hipStream_t s = k->stream;
-  job.esc_floor = shadow_escape_floor(k, f, reach);
-  job.escape = job.esc_floor < INFINITY ? 1 : 0;
-  HIP_TRY(report, reserve_carved(k->d_shadow, [&](Carve& cv) {
-            cv(job.list, job.src.n_pixels * sizeof(uint32_t)), cv(job.ctr, SH_N * sizeof(unsigned long long)), carve_more(cv);
-          }));
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_BEGIN], s));
-  if (int rc = launch(f, s)) return rc;
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_MARCHED], s));
-  unsigned long long ctr[SH_N] = {};
-  HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
-  for (const ShadowDownload& d : downloads)
-    if (d.host) HIP_TRY(report, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SH_END], s));
-  HIP_TRY(report, hipStreamSynchronize(s));
-  HIP_TRY(report, hipGetLastError());
-  for (int i = 0; i < 3; i++) {
-    float ms = 0.0f;
-    HIP_TRY(report, hipEventElapsedTime(&ms, k->ev[EV_SH_BEGIN + i], k->ev[EV_SH_BEGIN + i + 1]));
-    report->shadow_timings[i] = ms;
-  }
-  if (stats) {
-    stats->lit = ctr[SH_LIT], stats->shadowed = ctr[SH_SHADOWED];
-    stats->none = job.src.n_pixels - ctr[SH_LIST];
-    stats->integrated_steps = ctr[SH_STEPS], stats->escaped_rays = ctr[SH_ESCAPED];
-  }
-  return ATMRT_OK;
-}
-
-// host_status / host_block: where the planes are downloaded to (null: none).
-int shadow_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_spec_t& spec, int32_t m, const TracePoints& src, uint8_t* status_dev,
-               uint16_t* block_dev, atmrt_shadow_stats_t* stats, uint8_t* host_status, uint16_t* host_block) {
-  ShadowJob job{};
-  job.src = src;
-  job.azimuth_deg = spec.azimuth_deg, job.elevation_deg = spec.elevation_deg, job.lift = spec.lift;
-  job.m = m;
-  job.status = status_dev, job.block = block_dev;
-  return shadow_call(k, report, spec.reach, job, [](Carve&) {},
-                     [&](const Frame& f, hipStream_t s) -> int {
-                       launch_shadow_mask(f, job, s, k->ev[EV_SH_COMPACTED]);
-                       return ATMRT_OK;
-                     },
-                     {{host_status, status_dev, src.n_pixels}, {host_block, block_dev, src.n_pixels * sizeof(uint16_t)}}, stats);
-}
-
-const char* const SHADOW_ON_MULTI = "has no frame of its own: cast shadows work on the gathered planes through atmrt_shadow_mask_planes_device";
-
-} // namespace
-
-extern "C" int atmrt_shadow_steps(atmrt_ctx* c, double reach, int32_t* m) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!m) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_shadow_steps: m is NULL");
-  return shadow_reach_check(c, "atmrt_shadow_steps", reach, 0.0, m);
-}
-
-extern "C" int atmrt_shadow_mask_device(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, uint8_t* status_device, uint16_t* block_device,
-                                        atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  int32_t m = 0;
-  if (int rc = shadow_check(c, "atmrt_shadow_mask", spec, status_device, &m)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_shadow_mask", SHADOW_ON_MULTI)) return rc;
-  return shadow_run(c, c, *spec, m, last_frame_points(c, ATMRT_VIS_ALL), status_device, block_device, stats, nullptr, nullptr);
-}
-
-extern "C" int atmrt_shadow_mask(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, uint8_t* status, uint16_t* block, atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  int32_t m = 0;
-  if (int rc = shadow_check(c, "atmrt_shadow_mask", spec, status, &m)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_shadow_mask", SHADOW_ON_MULTI)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n = c->last_npx, block_bytes = Carve::pad(n * sizeof(uint16_t));
-  HIP_TRY(c, c->d_io.reserve(block_bytes + n));
-  uint16_t* d_block = block ? c->d_io.as<uint16_t>() : nullptr;
-  uint8_t* d_status = c->d_io.as<uint8_t>() + block_bytes;
-  return shadow_run(c, c, *spec, m, last_frame_points(c, ATMRT_VIS_ALL), d_status, d_block, stats, status, block);
-}
-
-extern "C" int atmrt_shadow_mask_planes_device(atmrt_ctx* c, const atmrt_shadow_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
-                                               const double* lat, const double* lon, const double* elev, uint8_t* status_device,
-                                               uint16_t* block_device, atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = shadow_planes_check(c, "atmrt_shadow_mask_planes_device", n_pixels, hit_count, lat, lon, elev)) return rc;
-  int32_t m = 0;
-  if (int rc = shadow_check(c, "atmrt_shadow_mask_planes_device", spec, status_device, &m)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, status_device, "status_device", &k)) return rc;
-  HIP_TRY(c, hipSetDevice(k->device));
-  return shadow_run(k, c, *spec, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, status_device, block_device, stats, nullptr,
-                    nullptr);
-}
-
-// ---- shadow lights: a direction per point and a list of lights per call (include/atmrt.h, "shadow lights") -------------------
-extern "C" int atmrt_shadow_light_direction(const atmrt_earth_model_t* earth, double lat, double lon, double azimuth_deg, double elevation_deg,
-                                            double dir[3]) {
-  if (!earth || !dir) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!(std::isfinite(lat) && std::isfinite(lon) && std::isfinite(azimuth_deg) && std::isfinite(elevation_deg))) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (!(elevation_deg >= -90.0 && elevation_deg <= 90.0)) return ATMRT_ERR_INVALID_ARGUMENT;
-  Earth e;
-  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
-  Vec3 n, ea, u;
-  world_directions(e, lat, lon, n, ea, u);
-  double sin_az, cos_az, sin_el, cos_el;
-  dm_sincos(dm_to_radians(azimuth_deg), &sin_az, &cos_az);
-  dm_sincos(dm_to_radians(elevation_deg), &sin_el, &cos_el);
-  const Vec3 v = n * (cos_el * cos_az) + ea * (cos_el * sin_az) + u * sin_el;
-  dir[0] = v.x, dir[1] = v.y, dir[2] = v.z;
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_shadow_local_direction(const atmrt_earth_model_t* earth, const double dir[3], double lat, double lon, double* azimuth_deg,
-                                            double* elevation_deg) {
-  if (!earth || !dir || !azimuth_deg || !elevation_deg) return ATMRT_ERR_INVALID_ARGUMENT;
-  Earth e;
-  Vec3 light;
-  if (earth_resolve(*earth, e) || !shadow_light_normalise(dir, light)) return ATMRT_ERR_INVALID_ARGUMENT;
-  Vec3 n, ea, u;
-  world_directions(e, lat, lon, n, ea, u);
-  shadow_local_direction(n, ea, u, light, *azimuth_deg, *elevation_deg);
-  return ATMRT_OK;
-}
-
-namespace {
-
-// what every shadow-lights entry point asks of its arguments and of the context's parameters; lights: [n_lights][3], normalised
-int shadow_lights_check(atmrt_ctx* c, const char* what, const atmrt_shadow_lights_spec_t* spec, const void* lit_mask, const void* status,
-                        int32_t* m, std::vector<double>& lights) {
-  if (!spec || !spec->dir) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec or its dir is NULL", what);
-  if (!lit_mask && !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: neither lit_mask nor status is given", what);
-  if (spec->n_lights < 1 || spec->n_lights > SHADOW_LIGHTS_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_lights must lie in [1, 64], not %u", what, spec->n_lights);
-  lights.resize(3 * (size_t)spec->n_lights);
-  for (uint32_t l = 0; l < spec->n_lights; l++) {
-    Vec3 v;
-    if (!shadow_light_normalise(spec->dir + 3 * l, v))
-      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: light %u is not a finite vector of a finite, positive squared length", what, l);
-    lights[3 * l] = v.x, lights[3 * l + 1] = v.y, lights[3 * l + 2] = v.z;
-  }
-  return shadow_reach_check(c, what, spec->reach, spec->lift, m);
-}
-
-const char* const SHADOW_LIGHTS_ON_MULTI = "has no frame of its own: shadow lights work on the gathered planes through atmrt_shadow_lights_planes_device";
-
-// shadow_run for a list of lights.  host_*: where the planes are downloaded to (null: none).
-int shadow_lights_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_lights_spec_t& spec, const std::vector<double>& lights, int32_t m,
-                      const TracePoints& src, uint64_t* mask_dev, uint8_t* status_dev, uint16_t* block_dev, atmrt_shadow_stats_t* stats,
-                      uint64_t* host_mask, uint8_t* host_status, uint16_t* host_block) {
-  ShadowLightsJob job{};
-  job.src = src;
-  job.n_lights = spec.n_lights, job.lift = spec.lift, job.m = m;
-  job.lit_mask = reinterpret_cast<unsigned long long*>(mask_dev), job.status = status_dev, job.block = block_dev;
-  double* d_dirs = nullptr;
-  const size_t planes = src.n_pixels * spec.n_lights;
-  return shadow_call(k, report, spec.reach, job, [&](Carve& cv) { cv(d_dirs, 3 * SHADOW_LIGHTS_MAX * sizeof(double)); },
-                     [&](const Frame& f, hipStream_t s) -> int {
-                       job.dirs = d_dirs;
-                       HIP_TRY(report, hipMemcpyAsync(d_dirs, lights.data(), lights.size() * sizeof(double), hipMemcpyHostToDevice, s));
-                       launch_shadow_lights(f, job, s, k->ev[EV_SH_COMPACTED]);
-                       return ATMRT_OK;
-                     },
-                     {{host_mask, mask_dev, src.n_pixels * sizeof(uint64_t)}, {host_status, status_dev, planes}, {host_block, block_dev, planes * sizeof(uint16_t)}},
-                     stats);
-}
-
-} // namespace
-
-extern "C" int atmrt_shadow_lights_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask_device, uint8_t* status_device,
-                                          uint16_t* block_device, atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  int32_t m = 0;
-  std::vector<double> lights;
-  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights", spec, lit_mask_device, status_device, &m, lights)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_shadow_lights", SHADOW_LIGHTS_ON_MULTI)) return rc;
-  return shadow_lights_run(c, c, *spec, lights, m, last_frame_points(c, ATMRT_VIS_ALL), lit_mask_device, status_device, block_device, stats, nullptr,
-                           nullptr, nullptr);
-}
-
-extern "C" int atmrt_shadow_lights(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask, uint8_t* status, uint16_t* block,
-                                   atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  int32_t m = 0;
-  std::vector<double> lights;
-  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights", spec, lit_mask, status, &m, lights)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_shadow_lights", SHADOW_LIGHTS_ON_MULTI)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  // the staging buffer: the mask (8 n), then the block planes (2 n L), then the status planes (n L); what is not asked for takes no room
-  const size_t n = c->last_npx, planes = n * spec->n_lights;
-  const size_t mask_bytes = lit_mask ? n * sizeof(uint64_t) : 0, block_bytes = block ? planes * sizeof(uint16_t) : 0;
-  HIP_TRY(c, c->d_io.reserve(mask_bytes + block_bytes + (status ? planes : 0)));
-  uint64_t* d_mask = lit_mask ? c->d_io.as<uint64_t>() : nullptr;
-  uint16_t* d_block = block ? reinterpret_cast<uint16_t*>(c->d_io.as<uint8_t>() + mask_bytes) : nullptr;
-  uint8_t* d_status = status ? c->d_io.as<uint8_t>() + mask_bytes + block_bytes : nullptr;
-  return shadow_lights_run(c, c, *spec, lights, m, last_frame_points(c, ATMRT_VIS_ALL), d_mask, d_status, d_block, stats, lit_mask, status, block);
-}
-
-extern "C" int atmrt_shadow_lights_planes_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
-                                                 const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
-                                                 uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = shadow_planes_check(c, "atmrt_shadow_lights_planes_device", n_pixels, hit_count, lat, lon, elev)) return rc;
-  int32_t m = 0;
-  std::vector<double> lights;
-  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights_planes_device", spec, lit_mask_device, status_device, &m, lights)) return rc;
-  atmrt_ctx* k = nullptr;
-  const bool by_mask = lit_mask_device != nullptr;
-  if (int rc = planes_context(c, by_mask ? (const void*)lit_mask_device : (const void*)status_device, by_mask ? "lit_mask_device" : "status_device", &k)) return rc;
-  HIP_TRY(c, hipSetDevice(k->device));
-  return shadow_lights_run(k, c, *spec, lights, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, lit_mask_device, status_device,
-                           block_device, stats, nullptr, nullptr, nullptr);
-}
-
-extern "C" int atmrt_draw_image_shadowed_device(atmrt_ctx* c, const atmrt_coloring_t* coloring, const uint8_t* status_device, uint8_t* rgb_device) {
-  if (!c || !coloring || !status_device || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = frame_state_check(c, "atmrt_draw_image_shadowed", "draws its shadowed image from the gathered planes: not part of this entry point")) return rc;
-  if (coloring->kind != ATMRT_COLORING_SIMPLE && coloring->kind != ATMRT_COLORING_SHADING)
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "unknown coloring kind %d", coloring->kind);
-  if (coloring->has_fog && !(coloring->fog_distance > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "fog_distance must be positive");
-  HIP_TRY(c, hipSetDevice(c->device));
-  launch_draw_image_shadowed(c->last_npx, *coloring, c->last_alpha, c->last_packed, c->last_dense.hit_count, c->last_offset, c->last_hits,
-                             c->last_dense, status_device, rgb_device, c->stream);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_draw_image_shadowed(atmrt_ctx* c, const atmrt_coloring_t* coloring, const uint8_t* status, uint8_t* rgb) {
-  if (!c || !coloring || !status || !rgb) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = frame_state_check(c, "atmrt_draw_image_shadowed", "draws its shadowed image from the gathered planes: not part of this entry point")) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n = c->last_npx, rgb_bytes = Carve::pad(3 * n);
-  HIP_TRY(c, c->d_io.reserve(rgb_bytes + n));
-  uint8_t* d_status = c->d_io.as<uint8_t>() + rgb_bytes;
-  HIP_TRY(c, hipMemcpy(d_status, status, n, hipMemcpyHostToDevice));
-  if (int rc = atmrt_draw_image_shadowed_device(c, coloring, d_status, c->d_io.as<uint8_t>())) return rc;
-  HIP_TRY(c, hipMemcpy(rgb, c->d_io.ptr, 3 * n, hipMemcpyDeviceToHost));
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_last_shadow_timings(atmrt_ctx* c, double out[3]) {
-  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  memcpy(out, c->shadow_timings, sizeof c->shadow_timings);
-  return ATMRT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// harnesses: host arrays in, host arrays out (staged through one device buffer)
-// ---------------------------------------------------------------------------------------------
-// the diagnostic entry points of a multi-device context run on its first device
-#define FORWARD_TO_FIRST_DEVICE(c, call) \
-  do {                                   \
-    if ((c) && (c)->multi) {             \
-      atmrt_ctx* k_ = multi_child((c), 0); \
-      int rc_ = (call);                  \
-      if (rc_) (c)->error = k_->error;   \
-      return rc_;                        \
-    }                                    \
-  } while (0)
-
-static int harness_frame(atmrt_ctx* c, Frame* f) {
-  if (!c->have_params) {
-    atmrt_params_t p;
-    atmrt_params_default(&p);
-    int rc = atmrt_set_params(c, &p);
-    if (rc) return rc;
-  }
-  return prepare_frame(c, f);
-}
-
-extern "C" int atmrt_terrain_get_elev(atmrt_ctx* c, size_t n, const double* lat, const double* lon, double* elev,
-                                      uint8_t* valid) {
-  if (!c || (n && (!lat || !lon || !elev || !valid))) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_terrain_get_elev(k_, n, lat, lon, elev, valid));
-  Frame f;
-  int rc = harness_frame(c, &f);
-  if (rc) return rc;
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, c->d_io.reserve(n * 25 + 1024));
-  double* d_lat = c->d_io.as<double>();
-  double* d_lon = d_lat + n;
-  double* d_elev = d_lon + n;
-  uint8_t* d_valid = reinterpret_cast<uint8_t*>(d_elev + n);
-  HIP_TRY(c, hipMemcpyAsync(d_lat, lat, n * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_lon, lon, n * 8, hipMemcpyHostToDevice, c->stream));
-  launch_get_elev(f, n, d_lat, d_lon, d_elev, d_valid, c->stream);
-  HIP_TRY(c, hipMemcpyAsync(elev, d_elev, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_ray_paths(atmrt_ctx* c, double h0, size_t n_angles, const double* angles_deg, int32_t straight,
-                               double step, size_t n_steps, double* x, double* h) {
-  if (!c || (n_angles && (!angles_deg || !x || !h))) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_ray_paths(k_, h0, n_angles, angles_deg, straight, step, n_steps, x, h));
-  if (!(step > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "step must be positive"); // ray_path.rs:53
-  if (n_steps > 50000000) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "too many steps");
-  Frame f;
-  int rc = harness_frame(c, &f);
-  if (rc) return rc;
-  if (!n_angles) return ATMRT_OK;
-  size_t m = n_angles * (n_steps + 1);
-  HIP_TRY(c, c->d_io.reserve((n_angles + 2 * m) * 8));
-  double* d_ang = c->d_io.as<double>();
-  double* d_x = d_ang + n_angles;
-  double* d_h = d_x + m;
-  HIP_TRY(c, hipMemcpyAsync(d_ang, angles_deg, n_angles * 8, hipMemcpyHostToDevice, c->stream));
-  launch_ray_paths(f, h0, n_angles, d_ang, straight, step, n_steps, d_x, d_h, c->stream);
-  HIP_TRY(c, hipMemcpyAsync(x, d_x, m * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h, d_h, m * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_atmosphere_sample(atmrt_ctx* c, size_t n, const double* altitude, double* temperature,
-                                       double* pressure, double* n_index, double* dn_dh) {
-  if (!c || (n && (!altitude || !temperature || !pressure || !n_index || !dn_dh))) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_atmosphere_sample(k_, n, altitude, temperature, pressure, n_index, dn_dh));
-  Frame f;
-  int rc = harness_frame(c, &f);
-  if (rc) return rc;
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, c->d_io.reserve(5 * n * 8));
-  double* d = c->d_io.as<double>();
-  HIP_TRY(c, hipMemcpyAsync(d, altitude, n * 8, hipMemcpyHostToDevice, c->stream));
-  launch_atm_sample(f, n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, c->stream);
-  HIP_TRY(c, hipMemcpyAsync(temperature, d + n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(pressure, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(n_index, d + 3 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dn_dh, d + 4 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_coords_at_dist(atmrt_ctx* c, double lat0, double lon0, double dir_deg, size_t n,
-                                    const double* dist, double* lat, double* lon) {
-  if (!c || (n && (!dist || !lat || !lon))) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_coords_at_dist(k_, lat0, lon0, dir_deg, n, dist, lat, lon));
-  Frame f;
-  int rc = harness_frame(c, &f);
-  if (rc) return rc;
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, c->d_io.reserve(3 * n * 8));
-  double* d = c->d_io.as<double>();
-  HIP_TRY(c, hipMemcpyAsync(d, dist, n * 8, hipMemcpyHostToDevice, c->stream));
-  launch_coords_at_dist(f, lat0, lon0, dir_deg, n, d, d + n, d + 2 * n, c->stream);
-  HIP_TRY(c, hipMemcpyAsync(lat, d + n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lon, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_debug_step_trig(atmrt_ctx* c, size_t cap, double* xs, double* sin_out, double* cos_out, size_t* n_out) {
-  if (!c || !n_out || (cap && (!xs || !sin_out || !cos_out))) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_step_trig(k_, cap, xs, sin_out, cos_out, n_out));
-  Frame f;
-  int rc = harness_frame(c, &f);
-  if (rc) return rc;
-  *n_out = f.xs_sin ? (size_t)f.march_steps + 1 : 0;
-  const size_t n = *n_out < cap ? *n_out : cap;
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, hipMemcpyAsync(xs, f.xs, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(sin_out, f.xs_sin, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(cos_out, f.xs_cos, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_debug_normal_trig(atmrt_ctx* c, size_t cap, double* out, size_t* n_out) {
-  if (!c || !n_out || (cap && !out)) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_normal_trig(k_, cap, out, n_out));
-  Frame f;
-  int rc = harness_frame(c, &f);
-  if (rc) return rc;
-  static_assert(sizeof(NormalTrig) == 17 * sizeof(double), "the record is 17 doubles, in the order include/atmrt.h documents");
-  *n_out = f.normal_trig ? sizeof(NormalTrig) / sizeof(double) : 0;
-  const size_t n = *n_out < cap ? *n_out : cap;
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, hipMemcpyAsync(out, f.normal_trig, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_debug_ceiling_table(atmrt_ctx* c, size_t cap, float* cell, float* suffix, int32_t* rows, int32_t* n_bins, double layout[3]) {
-  if (!c || !rows || !n_bins || !layout || (cap && (!cell || !suffix))) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_ceiling_table(k_, cap, cell, suffix, rows, n_bins, layout));
-  *rows = *n_bins = 0;
-  layout[0] = layout[1] = layout[2] = 0.0;
-  if (!c->last_valid || !c->last_ceil_rows) return ATMRT_OK;
-  if (c->ceiling.serial() != c->last_ceil_serial)
-    return c->fail(ATMRT_ERR_STATE, "the ceiling table of the last frame is gone: a later call built another one in its place");
-  const CeilLayout& L = c->last_ceil_layout;
-  *rows = c->last_ceil_rows;
-  *n_bins = L.n_bins;
-  layout[0] = L.dir0, layout[1] = L.rel_lo, layout[2] = L.w;
-  const size_t total = (size_t)*rows * (size_t)(L.n_bins + 1), n = total < cap ? total : cap;
-  if (!n) return ATMRT_OK;
-  std::vector<CeilEntry> host(n);
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(host.data(), c->d_ceil.as<CeilEntry>(), n * sizeof(CeilEntry), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t k = 0; k < n; k++) cell[k] = host[k].cell, suffix[k] = host[k].suffix;
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_debug_march_order(atmrt_ctx* c, size_t cap, uint32_t* order, uint32_t* n_groups) {
-  if (!c || !n_groups || (cap && !order)) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_march_order(k_, cap, order, n_groups));
-  *n_groups = 0;
-  if (!c->last_valid || !c->last_order_groups) return ATMRT_OK;
-  if (c->ceil_order.serial() != c->last_order_serial)
-    return c->fail(ATMRT_ERR_STATE, "the march order of the last frame is gone: a later call built another one in its place");
-  *n_groups = c->last_order_groups;
-  const size_t n = *n_groups < cap ? *n_groups : cap;
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(order, c->d_ceil_order.as<uint32_t>(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_debug_last_march_route(atmrt_ctx* c, int32_t index, int32_t* route) {
-  if (!c || !route) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (c->multi) {
-    if (index < 0 || index >= multi_size(c)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "device index %d outside the context's %d devices", index, multi_size(c));
-    atmrt_ctx* k = multi_child(c, index);
-    const int rc = atmrt_debug_last_march_route(k, -1, route);
-    if (rc) c->error = k->error;
-    return rc;
-  }
-  if (index != -1 && index != 0) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "a context of one device has no tile %d", index);
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_debug_last_march_route needs a frame: call atmrt_generate first");
-  *route = (int32_t)c->last_march_route;
+  *integrated_steps = c->last.ray_steps - c->last.escaped_steps;
+  *escaped_rays = c->last.escaped_rays;
   return ATMRT_OK;
 }
 
@@ -2642,7 +1455,7 @@ extern "C" int atmrt_debug_interp_blend(atmrt_ctx* c, uint32_t width, uint32_t h
       return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_debug_interp_blend: trace point %llu has the unknown colour tag %u", (unsigned long long)k,
                      lat->color_tag[k]);
   HIP_TRY(c, hipSetDevice(c->device));
-  c->last_valid = false; // the buffers of the last frame are about to be rewritten
+  c->last.valid = false; // the buffers of the last frame are about to be rewritten
   hipStream_t s = c->stream;
   Frame f{}; // what the blend reads of a frame: the image, its shard (all of it) and the step; an opaque frame sizes the least scratch
   f.p.generator = ATMRT_GEN_INTERPOLATING_RECTILINEAR;
@@ -2703,43 +1516,5 @@ extern "C" int atmrt_debug_interp_blend(atmrt_ctx* c, uint32_t width, uint32_t h
   uint64_t counters[N_COUNTERS];
   HIP_TRY(c, read_counters(ws, s, counters));
   HIP_TRY(c, hipGetLastError());
-  return result_to_host(c, f, ws, dense, packed, n_hits, counters[CTR_RAY_STEPS], 0.0, out);
-}
-
-extern "C" int atmrt_math_probe(atmrt_ctx* c, int32_t op, size_t n, const double* a, const double* b, double* out0, double* out1) {
-  if (!c || (n && (!a || !out0)) || op < 0 || op > ATMRT_PROBE_POW3_SHARED) return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_math_probe(k_, op, n, a, b, out0, out1));
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_io.reserve(4 * n * 8));
-  double* d = c->d_io.as<double>();
-  HIP_TRY(c, hipMemcpyAsync(d, a, n * 8, hipMemcpyHostToDevice, c->stream));
-  if (b) HIP_TRY(c, hipMemcpyAsync(d + n, b, n * 8, hipMemcpyHostToDevice, c->stream));
-  launch_math_probe(op, n, d, b ? d + n : nullptr, d + 2 * n, d + 3 * n, c->stream);
-  HIP_TRY(c, hipMemcpyAsync(out0, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (out1) HIP_TRY(c, hipMemcpyAsync(out1, d + 3 * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
-}
-
-extern "C" int atmrt_math_probe3(atmrt_ctx* c, int32_t op, size_t n, const double* a, const double* b0, const double* b1, const double* b2,
-                                 double* out0, double* out1, double* out2, int32_t* took) {
-  if (!c || (n && (!a || !b0 || !b1 || !b2 || !out0 || !out1 || !out2 || !took)) || op < 0 || op > ATMRT_PROBE3_EXP3_TIGHT || n > ((size_t)1 << 40))
-    return ATMRT_ERR_INVALID_ARGUMENT;
-  FORWARD_TO_FIRST_DEVICE(c, atmrt_math_probe3(k_, op, n, a, b0, b1, b2, out0, out1, out2, took));
-  if (!n) return ATMRT_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_io.reserve(8 * n * 8)); // a, b0, b1, b2, out0, out1, out2: n doubles each; took: n int32
-  double* d = c->d_io.as<double>();
-  const double* in[4] = {a, b0, b1, b2};
-  for (int k = 0; k < 4; k++) HIP_TRY(c, hipMemcpyAsync(d + k * n, in[k], n * 8, hipMemcpyHostToDevice, c->stream));
-  int32_t* d_took = reinterpret_cast<int32_t*>(d + 7 * n);
-  launch_math_probe3(op, n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, d_took, c->stream);
-  double* out[3] = {out0, out1, out2};
-  for (int k = 0; k < 3; k++) HIP_TRY(c, hipMemcpyAsync(out[k], d + (4 + k) * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(took, d_took, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return ATMRT_OK;
+  return result_to_host(c, f.wl, f.h, dense, ws.hit_offset, packed, n_hits, counters[CTR_RAY_STEPS], 0.0, out);
 }

@@ -1,11 +1,14 @@
 // atmrt_ctx.h — internal: the context behind the C ABI (include/atmrt.h), shared by the translation units that implement it:
-// atmrt_api.hip (one device: terrain store, frame set-up, launch sequences), atmrt_polar.hip (the calls along azimuths from the
-// observer: sight lines, viewshed, viewshed map, horizon) and atmrt_multi.hip (several devices: column tiles, the RCCL all-gather,
-// image assembly).
+// atmrt_api.hip (one device: terrain store, frame set-up, launch sequences), atmrt_consumers.hip (the calls that read a finished
+// frame: image, overlay, visibility map, landmarks, cast shadows), atmrt_polar.hip (the calls along azimuths from the observer: sight
+// lines, viewshed, viewshed map, horizon), atmrt_probes.hip (the harness and debug probes) and atmrt_multi.hip (several devices:
+// column tiles, the RCCL all-gather, image assembly).
 #pragma once
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -132,6 +135,55 @@ struct Escape { // the certificate from the mosaic's top minus a step up: the lo
   double from = 0.0, bound = 0.0;
 };
 
+// The last generated frame, for the calls that read it: run_generator (atmrt_api.hip) resets `valid`, `ceil_rows` and `march_route`
+// when a frame starts and fills the rest when it has succeeded; a frame that fails leaves the rest as the frame before left it.
+struct LastFrame {
+  bool valid = false, packed = false; // packed: the frame has trace-point lists (hits, offset, nhits) beside its planes
+  size_t npx = 0;
+  int wl = 0, h = 0, c0 = 0;
+  double alpha = 1.0;
+  atmrt_params_t params{}; // the parameters that frame was generated with (atmrt_draw_overlay*)
+  DensePlanes dense{};
+  PackedHits hits{};
+  const uint64_t* offset = nullptr;
+  uint64_t nhits = 0;
+  uint64_t ray_steps = 0, escaped_steps = 0, escaped_rays = 0; // atmrt_last_march_work
+  // atmrt_debug_ceiling_table: the ceiling table that frame marched with — its rows (0: none), its bins and the build of
+  // `ceiling` (its serial) that filled d_ceil then; a later build overwrites the buffer
+  int32_t ceil_rows = 0;
+  CeilLayout ceil_layout{};
+  uint64_t ceil_serial = 0;
+  // atmrt_debug_march_order: the work queue that frame marched with — its groups (0: none) and the build of `ceil_order` that filled it
+  uint32_t order_groups = 0;
+  uint64_t order_serial = 0;
+  // atmrt_debug_last_march_route: the route that frame's first-pass march was launched by (None: not a Rectilinear frame)
+  MarchRoute march_route = MarchRoute::None;
+
+  // The trace points a mode reads.  ATMRT_VIS_ALL reads the packed lists where the frame has them; a frame without lists holds one
+  // point per pixel at most, in its planes, and ALL is FIRST.
+  TracePoints points(int32_t mode) const {
+    if (mode == ATMRT_VIS_ALL && packed) return TracePoints{npx, (uint32_t)wl, dense.hit_count, offset, hits.lat, hits.lon, hits.distance, hits.elevation};
+    return TracePoints{npx, (uint32_t)wl, dense.hit_count, nullptr, dense.lat, dense.lon, dense.distance, dense.elevation};
+  }
+};
+
+// An environment switch that only "off" turns off.  When it is read is its caller's business: the named one-liners say.
+inline bool env_off(const char* name) {
+  const char* e = getenv(name);
+  return e && !strcmp(e, "off");
+}
+
+// ms[i] = (add ? ms[i] : 0) + the milliseconds from ev[i] to ev[i + 1], for the n intervals of n + 1 recorded events
+inline hipError_t event_intervals(const hipEvent_t* ev, int n, double* ms, bool add = false) {
+  for (int i = 0; i < n; i++) {
+    float v = 0.0f;
+    const hipError_t e = hipEventElapsedTime(&v, ev[i], ev[i + 1]);
+    if (e != hipSuccess) return e;
+    ms[i] = (add ? ms[i] : 0.0) + v;
+  }
+  return hipSuccess;
+}
+
 struct MultiGroup; // atmrt_multi.hip: the devices of a multi-device context and their worker threads
 struct Comm;       // atmrt_multi.hip: this context's place among the ranks that share one frame
 
@@ -166,27 +218,7 @@ struct atmrt_ctx {
   atmrt::Cached<atmrt::BinsKey, atmrt::CeilLayout> bins; // the ceiling table's bins (prepare_ceiling)
   bool ceil_built = false; // this frame built the ceiling table: EV_CEIL_BEGIN .. EV_CEIL_END hold its time
 
-  // last generated frame (for atmrt_draw_image)
-  bool last_valid = false, last_packed = false;
-  size_t last_npx = 0;
-  int last_wl = 0, last_h = 0, last_c0 = 0;
-  double last_alpha = 1.0;
-  atmrt_params_t last_params{}; // the parameters that frame was generated with (atmrt_draw_overlay*)
-  atmrt::DensePlanes last_dense{};
-  atmrt::PackedHits last_hits{};
-  const uint64_t* last_offset = nullptr;
-  uint64_t last_nhits = 0;
-  uint64_t last_ray_steps = 0, last_escaped_steps = 0, last_escaped_rays = 0; // atmrt_last_march_work
-  // atmrt_debug_ceiling_table: the ceiling table that frame marched with — its rows (0: none), its bins and the build of
-  // `ceiling` (its serial) that filled d_ceil then; a later build overwrites the buffer
-  int32_t last_ceil_rows = 0;
-  atmrt::CeilLayout last_ceil_layout{};
-  uint64_t last_ceil_serial = 0;
-  // atmrt_debug_march_order: the work queue that frame marched with — its groups (0: none) and the build of `ceil_order` that filled it
-  uint32_t last_order_groups = 0;
-  uint64_t last_order_serial = 0;
-  // atmrt_debug_last_march_route: the route that frame's first-pass march was launched by (None: not a Rectilinear frame)
-  atmrt::MarchRoute last_march_route = atmrt::MarchRoute::None;
+  atmrt::LastFrame last; // the last generated frame (run_generator)
 
   std::vector<atmrt::ObjectDev> objects; // host image of the device table (altitude kind in _pad until k_resolve)
   std::vector<uint8_t> textures;         // RGBA8 pool
@@ -212,7 +244,7 @@ struct atmrt_ctx {
   atmrt::DevBuf d_alt;                     // the observer's altitude (k_resolve): atmrt_draw_overlay* samples the atmosphere there
   atmrt::DevBuf d_objects, d_textures;     // the scene: the object table is uploaded every frame, the textures when objects_serial changes
   atmrt::Cached<uint64_t> textures_dev;
-  atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last_dense, last_hits, last_offset): draw, overlay, hits
+  atmrt::DevBuf d_dense, d_packed, d_hit_offset; // the last frame's results (last.dense, last.hits, last.offset): draw, overlay, hits
   atmrt::DevBuf d_io, d_overlay;           // staging of the entry points that run between frames
   atmrt::DevBuf d_vis;                     // atmrt_visibility_map* / atmrt_frame_bounds: the call's statistics block (72 B), read while the last frame's buffers are live
   atmrt::DevBuf d_landmarks;               // atmrt_locate_landmarks*: the call's index, per-landmark state and records, sized by the call's landmarks
@@ -258,6 +290,7 @@ struct atmrt_ctx {
   } while (0)
 
 namespace atmrt {
-// implemented in atmrt_api.hip, used by atmrt_polar.hip: the context's cached frame inputs refreshed and handed out as a Frame
+// implemented in atmrt_api.hip; called by atmrt_polar.hip (every call), atmrt_consumers.hip (shadow_call) and atmrt_probes.hip
+// (harness_frame): the context's cached frame inputs refreshed and handed out as a Frame
 int prepare_frame(atmrt_ctx* c, Frame* out);
 } // namespace atmrt

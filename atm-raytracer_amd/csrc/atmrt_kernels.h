@@ -1,5 +1,5 @@
-// atmrt_kernels.h — launch interface between the C-ABI host code (atmrt_api.hip) and the gfx950
-// kernels (atmrt_kernels.hip).  Internal; the public surface is include/atmrt.h.
+// atmrt_kernels.h — launch interface between the C-ABI host code (atmrt_api.hip, atmrt_consumers.hip,
+// atmrt_probes.hip) and the gfx950 kernels (atmrt_kernels.hip).  Internal; the public surface is include/atmrt.h.
 #pragma once
 
 #include <stdlib.h>

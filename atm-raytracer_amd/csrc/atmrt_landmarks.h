@@ -1,7 +1,7 @@
 // atmrt_landmarks.h — kernels of the landmark search (include/atmrt.h, atmrt_locate_landmarks*): for every landmark the number of
 // the frame's trace points within a radius and the nearest of them.  Included by atmrt_kernels.hip only.
 //
-// The host lays a bucket index over the landmarks (atmrt_api.hip, LandmarkIndex: an atmrt_geo_grid_t whose cells list, as CSR,
+// The host lays a bucket index over the landmarks (atmrt_consumers.hip, LandmarkIndex: an atmrt_geo_grid_t whose cells list, as CSR,
 // the landmarks whose padded boxes overlap them), so a trace point looks up ONE cell with geo_grid_cell and evaluates the exact
 // rule landmark_d2 (atmrt_core.h) on that cell's list only.  The traversal is vis_span and vis_point (atmrt_vismap.h), as in
 // k_vis_scatter: one pixel per lane, row-major, a trip loop over the wavefront's largest point count.

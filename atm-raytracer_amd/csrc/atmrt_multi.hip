@@ -637,10 +637,10 @@ int tile_exchange(atmrt_ctx* c, const atmrt_device_planes_t* image) {
   const int G = cm->world;
   HIP_TRY(c, hipSetDevice(c->device));
   SlabTrailer mine{};
-  mine.n_hits = c->last_packed ? c->last_nhits : 0;
+  mine.n_hits = c->last.packed ? c->last.nhits : 0;
   mine.seq = cm->seq;
   mine.tile_ms = c->timings.total_ms;
-  mine.packed = c->last_packed ? 1u : 0u;
+  mine.packed = c->last.packed ? 1u : 0u;
   mine.c0 = (uint32_t)cm->cols_frame[(size_t)cm->rank];
   mine.c1 = (uint32_t)cm->cols_frame[(size_t)cm->rank + 1];
   const size_t trailer_at = cm->slab_bytes - SLAB_TRAILER_BYTES;
@@ -709,9 +709,9 @@ int tile_exchange(atmrt_ctx* c, const atmrt_device_planes_t* image) {
 int tile_hits(atmrt_ctx* c, const atmrt_device_hits_t* dst, uint64_t* n_total_out) {
   Comm* cm = c->comm;
   hipStream_t s = c->stream;
-  if (!cm->exchanged || !c->last_valid)
+  if (!cm->exchanged || !c->last.valid)
     return c->fail(ATMRT_ERR_STATE, "atmrt_image_hits_device needs a frame: call atmrt_generate_image_device first");
-  if (!c->last_packed)
+  if (!c->last.packed)
     return c->fail(ATMRT_ERR_STATE, "the last frame holds first-hit planes only (opaque scene): its trace points are the planes themselves");
   const int G = cm->world;
   uint64_t n_total = 0, n_cap = 1;
@@ -747,7 +747,7 @@ int tile_hits(atmrt_ctx* c, const atmrt_device_hits_t* dst, uint64_t* n_total_ou
   HIP_TRY(c, cm->d_scan_tmp.reserve((std::max(npx, ps) / 2048 + 4) * 8 + 64));
   Carve send(cm->d_hits_send.ptr);
   PackedHits mine = carve_packed(send, n_cap);
-  HIP_TRY(c, copy_packed(mine, c->last_hits, c->last_nhits, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(c, copy_packed(mine, c->last.hits, c->last.nhits, hipMemcpyDeviceToDevice, s));
   int rc = comm_all_gather(c, cm->d_hits_send.ptr, cm->d_hits_recv.ptr, bb);
   if (rc) return rc;
   cm->tm.collectives = 2;
@@ -777,7 +777,7 @@ int tile_hits(atmrt_ctx* c, const atmrt_device_hits_t* dst, uint64_t* n_total_ou
 int tile_draw(atmrt_ctx* c, const atmrt_coloring_t* coloring, uint8_t* rgb_image) {
   Comm* cm = c->comm;
   hipStream_t s = c->stream;
-  if (!cm->exchanged || !c->last_valid)
+  if (!cm->exchanged || !c->last.valid)
     return c->fail(ATMRT_ERR_STATE, "atmrt_draw_image_gathered_device needs a frame: call atmrt_generate_image_device first");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t tile_bytes = Carve::pad(3 * (size_t)cm->H * cm->wl_max);
@@ -1091,7 +1091,7 @@ extern "C" int atmrt_draw_image_gathered_device(atmrt_ctx* c, const atmrt_colori
   if (!c || !coloring || !rgb_device) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) return multi_forward(c, [&](atmrt_ctx* k) { return tile_draw(k, coloring, rgb_device[(size_t)k->comm->rank]); });
   if (!c->comm) return rgb_device[0] ? atmrt_draw_image_device(c, coloring, rgb_device[0]) : ATMRT_ERR_INVALID_ARGUMENT;
-  if (!c->last_valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_image_gathered_device needs a frame: call atmrt_generate_image_device first");
+  if (!c->last.valid) return c->fail(ATMRT_ERR_STATE, "atmrt_draw_image_gathered_device needs a frame: call atmrt_generate_image_device first");
   return tile_draw(c, coloring, rgb_device[0]);
 }
 
@@ -1202,7 +1202,7 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
     return parent->fail(ATMRT_ERR_INVALID_ARGUMENT, "out of host memory for %dx%d pixels / %llu hits", W, H, (unsigned long long)n_hits);
   // a device's staging in host memory: its local offsets [H][wl], then its lists
   auto stage = [&](Carve& k, atmrt_ctx* kid, uint64_t** loc, PackedHits* lists) {
-    k(*loc, (size_t)kid->last_wl * H * 8);
+    k(*loc, (size_t)kid->last.wl * H * 8);
     *lists = carve_packed(k, nh[(size_t)kid->comm->rank]);
   };
   // (2) planes: strided copies straight into the [H][W] block; lists: into this device's staging; row totals for the merge
@@ -1211,9 +1211,9 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
     const size_t i = (size_t)cm->rank;
     hipStream_t s = k->stream;
     HIP_TRY(k, hipSetDevice(k->device));
-    const int c0 = k->last_c0, wl = k->last_wl;
+    const int c0 = k->last.c0, wl = k->last.wl;
     const size_t tile_px = (size_t)wl * H;
-    const DensePlanes& d = k->last_dense;
+    const DensePlanes& d = k->last.dense;
     HIP_TRY(k, hipEventRecord(cm->ev_g0, s));
     HIP_TRY(k, hipMemcpy2DAsync(out->azimuth + c0, (size_t)W * 8, d.azimuth, (size_t)wl * 8, (size_t)wl * 8, (size_t)H, hipMemcpyDeviceToHost, s));
     HIP_TRY(k, hipMemcpy2DAsync(out->elevation_angle + c0, (size_t)W * 8, d.elevation_angle, (size_t)wl * 8, (size_t)wl * 8, (size_t)H, hipMemcpyDeviceToHost, s));
@@ -1222,8 +1222,8 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
     uint64_t* loc;
     PackedHits lists;
     HIP_TRY(k, reserve_carved(cm->h_stage, [&](Carve& st) { stage(st, k, &loc, &lists); }));
-    HIP_TRY(k, hipMemcpyAsync(loc, k->last_offset, tile_px * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(k, copy_packed(lists, k->last_hits, m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(k, hipMemcpyAsync(loc, k->last.offset, tile_px * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(k, copy_packed(lists, k->last.hits, m, hipMemcpyDeviceToHost, s));
     HIP_TRY(k, hipEventRecord(cm->ev_g1, s));
     HIP_TRY(k, hipStreamSynchronize(s));
     cm->row_total.resize((size_t)H);
@@ -1250,7 +1250,7 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
   rc = multi_forward(parent, [&](atmrt_ctx* k) {
     Comm* cm = k->comm;
     const size_t i = (size_t)cm->rank;
-    const int c0 = k->last_c0, wl = k->last_wl;
+    const int c0 = k->last.c0, wl = k->last.wl;
     uint64_t* loc;
     PackedHits lists;
     Carve st(cm->h_stage.ptr);
@@ -1283,7 +1283,7 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
     if (hipEventElapsedTime(&v, k->comm->ev_g0, k->comm->ev_g1) == hipSuccess) tm.gather_ms = std::max(tm.gather_ms, (double)v);
     tm.tile_ms_max = std::max(tm.tile_ms_max, k->timings.total_ms);
     tm.tile_ms_min = std::min(tm.tile_ms_min, k->timings.total_ms);
-    tm.bytes_per_rank = std::max<uint64_t>(tm.bytes_per_rank, (uint64_t)k->last_npx * 20 + nh[i] * 100);
+    tm.bytes_per_rank = std::max<uint64_t>(tm.bytes_per_rank, (uint64_t)k->last.npx * 20 + nh[i] * 100);
   }
   g->tm = tm;
   // the next frame's tiling from this frame's tile times (what tile_exchange does from the gathered trailers)
@@ -1302,13 +1302,13 @@ int atmrt::multi_generate(atmrt_ctx* parent, atmrt_result_t* out) {
 int atmrt::multi_draw_image(atmrt_ctx* parent, const atmrt_coloring_t* coloring, uint8_t* rgb) {
   const int W = parent->params.width, H = parent->params.height;
   return multi_forward(parent, [&](atmrt_ctx* k) {
-    if (!k->last_valid) return k->fail(ATMRT_ERR_STATE, "atmrt_draw_image needs a frame: call atmrt_generate first");
+    if (!k->last.valid) return k->fail(ATMRT_ERR_STATE, "atmrt_draw_image needs a frame: call atmrt_generate first");
     HIP_TRY(k, hipSetDevice(k->device));
-    HIP_TRY(k, k->d_io.reserve(3 * k->last_npx + 256));
-    int rc = atmrt_draw_image_device(k, coloring, k->d_io.as<uint8_t>());
-    if (rc) return rc;
-    const size_t wl = (size_t)k->last_wl;
-    HIP_TRY(k, hipMemcpy2D(rgb + 3 * (size_t)k->last_c0, 3 * (size_t)W, k->d_io.ptr, 3 * wl, 3 * wl, (size_t)H, hipMemcpyDeviceToHost));
+    uint8_t* d_rgb = nullptr;
+    HIP_TRY(k, reserve_into(k->d_io, d_rgb, 3 * k->last.npx + 256));
+    if (int rc = atmrt_draw_image_device(k, coloring, d_rgb)) return rc;
+    const size_t wl = (size_t)k->last.wl;
+    HIP_TRY(k, hipMemcpy2D(rgb + 3 * (size_t)k->last.c0, 3 * (size_t)W, d_rgb, 3 * wl, 3 * wl, (size_t)H, hipMemcpyDeviceToHost));
     return (int)ATMRT_OK;
   });
 }
@@ -1352,8 +1352,8 @@ int atmrt::multi_last_stats(atmrt_ctx* parent, atmrt_frame_stats_t* out) {
 int atmrt::multi_last_march_work(atmrt_ctx* parent, uint64_t* integrated_steps, uint64_t* escaped_rays) {
   *integrated_steps = *escaped_rays = 0;
   for (atmrt_ctx* k : parent->multi->kids) {
-    *integrated_steps += k->last_ray_steps - k->last_escaped_steps;
-    *escaped_rays += k->last_escaped_rays;
+    *integrated_steps += k->last.ray_steps - k->last.escaped_steps;
+    *escaped_rays += k->last.escaped_rays;
   }
   return ATMRT_OK;
 }

@@ -154,11 +154,7 @@ int polar_run(atmrt_ctx* c, const Frame& f, const PolarCall& call) {
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipGetLastError());
-    for (int i = 0; i < n_ms; i++) {
-      float ms = 0.0f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[call.ev0 + i], c->ev[call.ev0 + i + 1]));
-      call.ms[i] += ms;
-    }
+    HIP_TRY(c, event_intervals(c->ev + call.ev0, n_ms, call.ms, true));
   }
   return ATMRT_OK;
 }

@@ -1,5 +1,5 @@
 // atmrt_shadow.h — cast shadows (include/atmrt.h, "cast shadows": the rule is stated there): which of a finished frame's first
-// trace points the light reaches.  The launch interface for atmrt_api.hip; the kernels themselves are compiled by atmrt_shadow.hip
+// trace points the light reaches.  The launch interface for atmrt_consumers.hip; the kernels themselves are compiled by atmrt_shadow.hip
 // only (ATMRT_SHADOW_KERNELS).
 //
 //   k_shadow_compact  one thread per pixel: the pixels with a trace point appended to a list, a wavefront's entries contiguous and
