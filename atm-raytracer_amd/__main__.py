@@ -11,6 +11,8 @@
                                      [--horizon-rounds N]]
                                     [--shadows [--shadow-reach M] [--shadow-lift M] [--shadow-light AZ EL] [--shadow-per-point]]
                                     [--shadow-lights FILE.csv [--shadow-lights-out OUT.npz] [--shadow-reach M] [--shadow-lift M]]
+                                    [--sun AZ EL [--sun-radius DEG]] [--moon AZ EL] [--sky-top M] [--sky-step M] [--sky-floor M]
+                                    [--sky-out OUT.npz] [--refraction-table OUT.csv [--sky-fan LO HI K]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -66,6 +68,17 @@ rows of azimuth_deg,elevation_deg as seen from the observer, each turned into a 
 --shadow-lift as above.  OUT.npz (--shadow-lights-out, shadow_lights.npz) holds lit_mask [height][width] u64 (bit l: light l reaches
 the pixel's first trace point), lit_count (its popcount, taken on the host), dirs [n][3], azimuth_deg, elevation_deg and the call's
 stats_none, stats_lit, stats_shadowed, stats_integrated_steps, stats_escaped_rays.
+`--sun AZ EL` and `--moon AZ EL` (no reference counterpart) draw a disc where the frame's sky pixels look at it once their rays
+have left the atmosphere (include/atmrt.h, "sky rays"): AZ and EL are the body's TRUE direction in degrees, as seen from the observer
+with no atmosphere, --sun-radius its angular radius (0.2666; the moon's is the same).  Every pixel without a trace point is marched
+through the atmosphere to --sky-top metres (100000) in steps of --sky-step metres (the simulation step) and given up below
+--sky-floor metres (0); near the horizon the disc comes out lifted and flattened, and terrain cuts it.  The discs are drawn on the
+device image before the overlay: ticks and lines stay on top.  `--sky-out OUT.npz` holds true_elevation, status (0 none, 1 exit,
+2 ground, 3 inside, 4 lost), steps and body as [height][width] arrays and the call's stats_none, stats_exit, stats_ground,
+stats_inside, stats_lost, stats_integrated_steps.
+`--refraction-table OUT.csv` marches K rays from the observer's altitude at launch elevations from LO to
+HI degrees (--sky-fan, 0 60 61) with the same --sky-top, --sky-step and --sky-floor: rows of
+elevation_deg,status,steps,true_elevation_deg,refraction_deg (the last two empty unless the ray exits).
 Floats are printed with Python's repr, the shortest round-trip form like Rust's `{}`.
 """
 import argparse
@@ -341,6 +354,68 @@ def write_shadow_lights(ctx, cfg, path, out, reach, lift, w, h):
     return data
 
 
+def sky_spec_of(a):
+    """The atmrt_sky_spec_t of gen's sky options: --sky-step (0: the simulation step), --sky-top, --sky-floor."""
+    step = 0.0 if a.sky_step is None else a.sky_step
+    if not (np.isfinite(step) and step >= 0.0 and np.isfinite(a.sky_top) and np.isfinite(a.sky_floor) and a.sky_floor < a.sky_top):
+        raise config.ConfigError("--sky-step must not be negative and --sky-floor must lie below --sky-top")
+    return generators.sky_spec(step, a.sky_top, a.sky_floor)
+
+
+def sky_bodies_of(a):
+    """The bodies of gen --sun / --moon, the sun first."""
+    bodies = []
+    if a.sun:
+        bodies.append(generators.sky_body(a.sun[0], a.sun[1], a.sun_radius, (255, 244, 214)))
+    if a.moon:
+        bodies.append(generators.sky_body(a.moon[0], a.moon[1], generators.SUN_RADIUS_DEG, (226, 228, 235)))
+    return bodies
+
+
+def draw_sky(ctx, a, rgb_dev, w, h):
+    """gen --sun / --moon / --sky-out: the sky march and the discs over the device image; the planes go to --sky-out."""
+    import torch
+    dev = rgb_dev.device
+    true_dev = torch.empty((h, w), dtype=torch.float64, device=dev)
+    status_dev = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    steps_dev = torch.empty((h, w), dtype=torch.int32, device=dev)
+    body_dev = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    spec, st = sky_spec_of(a), _abi.SkyStats()
+    ctx.check(ctx.lib.atmrt_sky_directions_device(ctx.handle, C.byref(spec), true_dev.data_ptr(), status_dev.data_ptr(), steps_dev.data_ptr(), C.byref(st)))
+    arr, n = generators._sky_bodies_array(sky_bodies_of(a))
+    ctx.check(ctx.lib.atmrt_sky_bodies_device(ctx.handle, arr, n, true_dev.data_ptr(), status_dev.data_ptr(), body_dev.data_ptr(), rgb_dev.data_ptr()))
+    stats = generators._sky_stats(st)
+    print(f"Sky: {stats['exit']} pixels leave the atmosphere, {stats['ground']} reach the floor, {stats['inside']} stay inside, {stats['lost']} lost; "
+          f"{int((body_dev != 0).sum())} pixels of {n} bodies")
+    if a.sky_out:
+        data = dict(true_elevation=true_dev.cpu().numpy(), status=status_dev.cpu().numpy(), steps=steps_dev.cpu().numpy().view(np.uint32),
+                    body=body_dev.cpu().numpy())
+        data.update({"stats_" + k: np.uint64(v) for k, v in stats.items()})
+        np.savez_compressed(a.sky_out, **data)
+
+
+def write_refraction_table(ctx, cfg, a, terrain):
+    """gen --refraction-table: the list call over the fan of --sky-fan from the observer's altitude."""
+    lo, hi, k = a.sky_fan
+    k = int(k)
+    if not (k >= 1 and np.isfinite(lo) and np.isfinite(hi)):
+        raise config.ConfigError("--sky-fan needs finite LO and HI and at least one ray")
+    elev = np.array([lo]) if k == 1 else lo + (hi - lo) * np.arange(k) / (k - 1)
+    pos = cfg.params.position
+    h0 = pos.altitude
+    if pos.altitude_kind == _abi.ALT_RELATIVE:  # Altitude::abs: above the terrain, 0 m where it has none
+        ground, valid = terrain.get_elev(pos.latitude, pos.longitude)
+        h0 = (float(ground[0]) if valid[0] else 0.0) + pos.altitude
+    rec, _ = generators.sky_rays(ctx, h0, elev, spec=sky_spec_of(a))
+    with open(a.refraction_table, "w") as f:
+        f.write("elevation_deg,status,steps,true_elevation_deg,refraction_deg\n")
+        for e, r in zip(elev, rec):
+            leaves = int(r["status"]) == _abi.SKY_EXIT
+            true = float(r["true_elevation"])
+            f.write(f"{float(e)!r},{_abi.SKY_STATUS[int(r['status'])]},{int(r['steps'])},{repr(true) if leaves else ''},{repr(float(e) - true) if leaves else ''}\n")
+
+
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
@@ -374,7 +449,13 @@ def cmd_gen(a):
         ctx.check(ctx.lib.atmrt_draw_image_shadowed_device(ctx.handle, C.byref(col), status_dev.data_ptr(), rgb_dev.data_ptr()))
     else:
         ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
+    if a.sun or a.moon or a.sky_out:  # on the device image, before the overlay: ticks and lines stay on top
+        stamp("Marching the sky...")
+        draw_sky(ctx, a, rgb_dev, w, h)
     ticks, _ = generators.draw_overlay_device(ctx, generators.into_overlay(cfg.output), rgb_dev.data_ptr(), w, h)
+    if a.refraction_table:  # needs no frame: the context's parameters and atmosphere
+        stamp("Writing the refraction table...")
+        write_refraction_table(ctx, cfg, a, terrain)
     if a.shadow_lights:  # on the device, while the frame is still in HBM
         stamp("Casting the shadows of the light list...")
         write_shadow_lights(ctx, cfg, a.shadow_lights, a.shadow_lights_out, a.shadow_reach, a.shadow_lift, w, h)
@@ -503,6 +584,15 @@ def main(argv=None):
     g.add_argument("--shadow-per-point", action="store_true")
     g.add_argument("--shadow-lights", default=None, metavar="FILE.csv")
     g.add_argument("--shadow-lights-out", default="shadow_lights.npz", metavar="OUT.npz")
+    g.add_argument("--sun", type=float, nargs=2, default=None, metavar=("AZ", "EL"))
+    g.add_argument("--sun-radius", type=float, default=generators.SUN_RADIUS_DEG, metavar="DEG")
+    g.add_argument("--moon", type=float, nargs=2, default=None, metavar=("AZ", "EL"))
+    g.add_argument("--sky-top", type=float, default=generators.SKY_TOP, metavar="M")
+    g.add_argument("--sky-step", type=float, default=None, metavar="M")
+    g.add_argument("--sky-floor", type=float, default=0.0, metavar="M")
+    g.add_argument("--sky-out", default=None, metavar="OUT.npz")
+    g.add_argument("--refraction-table", default=None, metavar="OUT.csv")
+    g.add_argument("--sky-fan", type=float, nargs=3, default=(0.0, 60.0, 61), metavar=("LO", "HI", "K"))
     g.add_argument("--horizon", default=None, metavar="OUT.csv")
     g.add_argument("--horizon-az", type=float, nargs=3, default=None, metavar=("LO", "HI", "N"))
     g.add_argument("--horizon-reach", type=float, default=None, metavar="M")

@@ -233,6 +233,33 @@ class ShadowLightsSpec(C.Structure):
     _fields_ = [("dir", C.POINTER(C.c_double)), ("n_lights", C.c_uint32), ("_pad", C.c_uint32), ("reach", C.c_double), ("lift", C.c_double)]
 
 
+# atmrt_sky_status
+SKY_NONE, SKY_EXIT, SKY_GROUND, SKY_INSIDE, SKY_LOST = 0, 1, 2, 3, 4
+SKY_STATUS = {SKY_NONE: "none", SKY_EXIT: "exit", SKY_GROUND: "ground", SKY_INSIDE: "inside", SKY_LOST: "lost"}
+SKY_M_MAX, SKY_BODIES_MAX = 1048575, 32
+
+
+class SkySpec(C.Structure):
+    """atmrt_sky_spec_t: the step [m] (0: the context's simulation_step), the top and the floor [m], the step cap."""
+    _fields_ = [("step", C.c_double), ("top", C.c_double), ("floor", C.c_double), ("m", C.c_int32), ("_pad", C.c_int32)]
+
+
+class SkyRay(C.Structure):
+    """atmrt_sky_ray_t: status (SKY_*), the deciding step, the true elevation [deg] (NaN unless EXIT)."""
+    _fields_ = [("status", C.c_int32), ("steps", C.c_uint32), ("true_elevation", C.c_double)]
+
+
+class SkyStats(C.Structure):
+    """atmrt_sky_stats_t: none + exit + ground + inside + lost = the pixels; the stepper steps taken, of one call."""
+    _fields_ = [(k, C.c_uint64) for k in ("none", "exit", "ground", "inside", "lost", "integrated_steps")]
+
+
+class SkyBody(C.Structure):
+    """atmrt_sky_body_t: the body's true direction and angular radius [deg], its colour."""
+    _fields_ = [("azimuth_deg", C.c_double), ("elevation_deg", C.c_double), ("radius_deg", C.c_double), ("rgb", C.c_uint8 * 3),
+                ("_pad", C.c_uint8 * 5)]
+
+
 class Horizon(C.Structure):
     _fields_ = [("status", C.c_int32), ("rounds_done", C.c_int32), ("k_star", C.c_int32), ("block_index", C.c_int32)] + \
         [(k, C.c_double) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon", "block_elevation")]

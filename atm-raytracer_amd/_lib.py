@@ -147,6 +147,17 @@ def load():
         "atmrt_shadow_lights_device": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), vp, vp, vp, C.POINTER(_abi.ShadowStats)]),
         "atmrt_shadow_lights": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), vp, vp, vp, C.POINTER(_abi.ShadowStats)]),
         "atmrt_shadow_lights_planes_device": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), sz, vp, vp, vp, vp, vp, vp, vp, C.POINTER(_abi.ShadowStats)]),
+        "atmrt_sky_ray_host": (C.c_int, [C.POINTER(_abi.Atmosphere), dbl, C.POINTER(_abi.EarthModel), i32, C.POINTER(_abi.SkySpec), dbl, dbl,
+                                         C.POINTER(_abi.SkyRay)]),
+        "atmrt_sky_body_host": (C.c_int, [C.POINTER(_abi.SkyBody), C.c_uint32, dbl, dbl, C.POINTER(C.c_uint32)]),
+        "atmrt_sky_rays": (C.c_int, [vp, C.POINTER(_abi.SkySpec), dbl, sz, vp, vp, C.POINTER(_abi.SkyStats)]),
+        "atmrt_sky_directions_device": (C.c_int, [vp, C.POINTER(_abi.SkySpec), vp, vp, vp, C.POINTER(_abi.SkyStats)]),
+        "atmrt_sky_directions": (C.c_int, [vp, C.POINTER(_abi.SkySpec), vp, vp, vp, C.POINTER(_abi.SkyStats)]),
+        "atmrt_sky_directions_planes_device": (C.c_int, [vp, C.POINTER(_abi.SkySpec), dbl, sz, vp, vp, vp, vp, vp, C.POINTER(_abi.SkyStats)]),
+        "atmrt_sky_bodies_device": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, vp, vp, vp, vp]),
+        "atmrt_sky_bodies": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, vp, vp, vp, vp]),
+        "atmrt_sky_bodies_planes_device": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, sz, vp, vp, vp, vp, vp]),
+        "atmrt_last_sky_timings": (C.c_int, [vp, pd]),
         "atmrt_ray_paths": (C.c_int, [vp, dbl, sz, vp, i32, dbl, sz, vp, vp]),
         "atmrt_atmosphere_sample": (C.c_int, [vp, sz, vp, vp, vp, vp, vp]),
         "atmrt_coords_at_dist": (C.c_int, [vp, dbl, dbl, dbl, sz, vp, vp, vp]),
@@ -202,7 +213,10 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_debug_horizon_shape", "atmrt_horizon", "atmrt_horizon_device", "atmrt_last_horizon_timings", "atmrt_last_horizon_work",
             "atmrt_shadow_steps", "atmrt_shadow_mask_device", "atmrt_shadow_mask", "atmrt_shadow_mask_planes_device", "atmrt_draw_image_shadowed",
             "atmrt_draw_image_shadowed_device", "atmrt_last_shadow_timings", "atmrt_shadow_light_direction", "atmrt_shadow_local_direction",
-            "atmrt_shadow_lights_device", "atmrt_shadow_lights", "atmrt_shadow_lights_planes_device", "atmrt_ray_paths", "atmrt_atmosphere_sample",
+            "atmrt_shadow_lights_device", "atmrt_shadow_lights", "atmrt_shadow_lights_planes_device",
+            "atmrt_sky_ray_host", "atmrt_sky_body_host", "atmrt_sky_rays", "atmrt_sky_directions_device", "atmrt_sky_directions",
+            "atmrt_sky_directions_planes_device", "atmrt_sky_bodies_device", "atmrt_sky_bodies", "atmrt_sky_bodies_planes_device",
+            "atmrt_last_sky_timings", "atmrt_ray_paths", "atmrt_atmosphere_sample",
             "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_debug_last_march_route", "atmrt_debug_interp_blend", "atmrt_result_encode_bincode",
             "atmrt_result_decode_bincode", "atmrt_comm_unique_id", "atmrt_ctx_comm_init_rank", "atmrt_ctx_comm_init_external", "atmrt_ctx_comm_init_external_device",
             "atmrt_ctx_create_multi", "atmrt_ctx_device_count", "atmrt_generate_image_device", "atmrt_image_hits_device",

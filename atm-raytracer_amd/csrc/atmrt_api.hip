@@ -161,6 +161,11 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 38: return sizeof(atmrt_shadow_lights_spec_t);
     // 39 stays 0
     case 40: return sizeof(atmrt_interp_lattice_t);
+    // 41 stays 0
+    case 42: return sizeof(atmrt_sky_spec_t);
+    case 43: return sizeof(atmrt_sky_ray_t);
+    case 44: return sizeof(atmrt_sky_stats_t);
+    case 45: return sizeof(atmrt_sky_body_t);
     default: return 0;
   }
 }

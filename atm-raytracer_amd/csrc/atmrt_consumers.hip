@@ -1,6 +1,6 @@
 // atmrt_consumers.hip — the entry points of include/atmrt.h that read a finished frame, the context's last one (c->last) or the
 // caller's planes of one: the image, the overlay, the visibility map and the frame's bounds, the landmarks, the cast shadows and
-// shadow lights, the shadowed image.  Host code only: their kernels are compiled by atmrt_kernels.hip and atmrt_shadow.hip.
+// shadow lights, the shadowed image, the sky rays.  Host code only: their kernels are compiled by atmrt_kernels.hip, atmrt_shadow.hip and atmrt_sky.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "atmrt_polar_plan.h"
 #include "atmrt_render.h"
 #include "atmrt_shadow.h"
+#include "atmrt_sky.h"
 
 using namespace atmrt;
 
@@ -937,5 +938,268 @@ extern "C" int atmrt_draw_image_shadowed(atmrt_ctx* c, const atmrt_coloring_t* c
 extern "C" int atmrt_last_shadow_timings(atmrt_ctx* c, double out[3]) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
   memcpy(out, c->shadow_timings, sizeof c->shadow_timings);
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sky rays: the true direction of every sky pixel, sun and moon discs (kernels: atmrt_sky.h; the rule: include/atmrt.h)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// ATMRT_SKY_ORDER=forward: the march takes the list from its head (A/B runs, tests/test_gpu_sky.py).  Read at every call.
+bool sky_reverse_enabled() {
+  const char* e = getenv("ATMRT_SKY_ORDER");
+  return !(e && !strcmp(e, "forward"));
+}
+
+// what the rule asks of a spec and an h0, whatever the step's source; nullptr, or what is wrong
+const char* sky_spec_check(const atmrt_sky_spec_t& s, double h0) {
+  if (!(std::isfinite(s.step) && s.step >= 0.0)) return "step must be finite and not negative";
+  if (!std::isfinite(s.top) || !std::isfinite(s.floor)) return "top and floor must be finite";
+  if (!(s.floor < s.top)) return "floor must lie below top";
+  if (s.m < 1 || s.m > SKY_M_MAX) return "m must lie in [1, 1048575]";
+  if (!std::isfinite(h0)) return "h0 is not finite";
+  return nullptr;
+}
+
+// what every sky entry point on a context asks of its spec and of the context's parameters; *step: the step of the march
+int sky_check(atmrt_ctx* c, const char* what, const atmrt_sky_spec_t* spec, double h0, double* step) {
+  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
+  if (const char* msg = sky_spec_check(*spec, h0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: %s", what, msg);
+  if (!c->have_params) return c->fail(ATMRT_ERR_STATE, "%s: atmrt_set_params has not been called", what);
+  *step = spec->step == 0.0 ? c->params.simulation_step : spec->step;
+  if (!(std::isfinite(*step) && *step > 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: simulation_step must be positive", what);
+  return ATMRT_OK;
+}
+
+struct SkyDownload { // a plane the host asked for (host null: not this one), downloaded inside the call's timed window
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+
+// One sky march around its kernels, for a SkyJob with its source, its h0 and its planes filled in.  k: the context whose device
+// holds the memory and whose setting is used; report: the context the caller handed in.  upload: the list call's elevations, inside
+// the timed window.
+int sky_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_sky_spec_t& spec, double step, SkyJob& job, const std::function<int(hipStream_t)>& upload,
+            std::initializer_list<SkyDownload> downloads, atmrt_sky_stats_t* stats) {
+  Frame f;
+  if (int rc = prepare_frame(k, &f)) {
+    if (k != report) report->error = k->error;
+    return rc;
+  }
+  hipStream_t s = k->stream;
+  job.step = step, job.top = spec.top, job.floor = spec.floor, job.m = spec.m;
+  job.reverse = sky_reverse_enabled() ? 1 : 0;
+  HIP_TRY(report, reserve_carved(k->d_sky, [&](Carve& cv) {
+            if (job.hit_count) cv(job.list, job.n_pixels * sizeof(uint32_t));
+            cv(job.ctr, SKY_N * sizeof(unsigned long long));
+          }));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], s));
+  if (int rc = upload(s)) return rc;
+  launch_sky_march(f, job, s, k->ev[EV_SKY_COMPACTED]);
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_MARCHED], s));
+  unsigned long long ctr[SKY_N] = {};
+  HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+  for (const SkyDownload& d : downloads)
+    if (d.host && d.bytes) HIP_TRY(report, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_END], s));
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
+  HIP_TRY(report, event_intervals(k->ev + EV_SKY_BEGIN, 3, report->sky_timings));
+  if (stats) {
+    stats->none = job.hit_count ? job.n_pixels - ctr[SKY_LIST] : 0;
+    stats->exit = ctr[SKY_EXIT], stats->ground = ctr[SKY_GROUND], stats->inside = ctr[SKY_INSIDE], stats->lost = ctr[SKY_LOST];
+    stats->integrated_steps = ctr[SKY_STEPS];
+  }
+  return ATMRT_OK;
+}
+
+const char* const SKY_ON_MULTI = "has no frame of its own: sky rays work on the gathered planes through atmrt_sky_directions_planes_device and atmrt_sky_bodies_planes_device";
+
+// the bodies of a call, checked and made into what the kernel holds
+int sky_bodies_check(atmrt_ctx* c, const char* what, const atmrt_sky_body_t* bodies, uint32_t n_bodies, SkyBodiesJob& job) {
+  if (n_bodies > SKY_BODIES_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: at most 32 bodies, not %u", what, n_bodies);
+  if (n_bodies && !bodies) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: bodies is NULL", what);
+  job.n_bodies = n_bodies;
+  for (uint32_t k = 0; k < n_bodies; k++) {
+    if (!sky_body_valid(bodies[k]))
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: body %u needs finite angles and a radius strictly between 0 and 90 degrees", what, k);
+    job.bodies[k] = sky_body_dev(bodies[k]);
+    memcpy(job.colour[k], bodies[k].rgb, 3);
+  }
+  return ATMRT_OK;
+}
+
+int sky_bodies_run(atmrt_ctx* k, atmrt_ctx* report, const SkyBodiesJob& job) {
+  HIP_TRY(report, hipSetDevice(k->device));
+  launch_sky_bodies(job, k->stream);
+  HIP_TRY(report, hipStreamSynchronize(k->stream));
+  HIP_TRY(report, hipGetLastError());
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_sky_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays,
+                                  const atmrt_sky_spec_t* spec, double h0, double elevation_deg, atmrt_sky_ray_t* out) {
+  if (!atmosphere || !earth || !spec || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (sky_spec_check(*spec, h0) || !(spec->step > 0.0)) return ATMRT_ERR_INVALID_ARGUMENT;
+  Earth e;
+  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
+  AtmTableBuf buf;
+  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
+  *out = sky_march_one<true>(buf.table(), e.spherical != 0, e.shape_radius, straight_rays != 0, spec->step, spec->top, spec->floor, spec->m, h0, elevation_deg);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_body_host(const atmrt_sky_body_t* bodies, uint32_t n_bodies, double azimuth_deg, double true_elevation_deg, uint32_t* body) {
+  if (!body || (n_bodies && !bodies) || n_bodies > SKY_BODIES_MAX) return ATMRT_ERR_INVALID_ARGUMENT;
+  SkyBodyDev dev[SKY_BODIES_MAX];
+  for (uint32_t k = 0; k < n_bodies; k++) {
+    if (!sky_body_valid(bodies[k])) return ATMRT_ERR_INVALID_ARGUMENT;
+    dev[k] = sky_body_dev(bodies[k]);
+  }
+  *body = sky_body_of(dev, n_bodies, azimuth_deg, true_elevation_deg);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_rays(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double h0, size_t n, const double* elevation_deg, atmrt_sky_ray_t* records,
+                              atmrt_sky_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (n && (!elevation_deg || !records)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_rays: elevation_deg or records is NULL");
+  if (n > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_rays: n must lie in [0, 2^32 - 1]");
+  double step = 0.0;
+  if (int rc = sky_check(c, "atmrt_sky_rays", spec, h0, &step)) return rc;
+  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
+  HIP_TRY(c, hipSetDevice(k->device));
+  SkyJob job{};
+  job.n_pixels = n, job.h0 = h0;
+  double *d_elev = nullptr, *d_true = nullptr; // the call's planes: staged like the host planes of atmrt_sky_directions
+  uint8_t* d_status = nullptr;
+  uint32_t* d_steps = nullptr;
+  HIP_TRY(c, reserve_carved(k->d_io, [&](Carve& cv) { cv(d_elev, n * 8), cv(d_true, n * 8), cv(d_steps, n * 4), cv(d_status, n); }));
+  job.elevation_angle = d_elev, job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
+  std::vector<double> true_elevation(n);
+  std::vector<uint8_t> status(n);
+  std::vector<uint32_t> steps(n);
+  int rc = sky_run(k, c, *spec, step, job,
+                   [&](hipStream_t s) -> int {
+                     if (n) HIP_TRY(c, hipMemcpyAsync(d_elev, elevation_deg, n * 8, hipMemcpyHostToDevice, s));
+                     return ATMRT_OK;
+                   },
+                   {{true_elevation.data(), d_true, n * 8}, {status.data(), d_status, n}, {steps.data(), d_steps, n * 4}}, stats);
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) records[i] = atmrt_sky_ray_t{(int32_t)status[i], steps[i], true_elevation[i]};
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_directions_device(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double* true_elevation_device, uint8_t* status_device,
+                                           uint32_t* steps_device, atmrt_sky_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation_device || !status_device) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions: true_elevation or status is NULL");
+  double step = 0.0;
+  if (int rc = sky_check(c, "atmrt_sky_directions", spec, 0.0, &step)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_directions", SKY_ON_MULTI)) return rc;
+  SkyJob job{};
+  job.n_pixels = c->last.npx, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
+  job.alt = c->d_alt.as<double>();
+  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
+  return sky_run(c, c, *spec, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats);
+}
+
+extern "C" int atmrt_sky_directions(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps,
+                                    atmrt_sky_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation || !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions: true_elevation or status is NULL");
+  double step = 0.0;
+  if (int rc = sky_check(c, "atmrt_sky_directions", spec, 0.0, &step)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_directions", SKY_ON_MULTI)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n = c->last.npx;
+  double* d_true = nullptr;
+  uint32_t* d_steps = nullptr; // what is not asked for takes no room
+  uint8_t* d_status = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8); if (steps) k(d_steps, n * 4); k(d_status, n); }));
+  SkyJob job{};
+  job.n_pixels = n, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
+  job.alt = c->d_alt.as<double>();
+  job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
+  return sky_run(c, c, *spec, step, job, [](hipStream_t) -> int { return ATMRT_OK; },
+                 {{true_elevation, d_true, n * 8}, {status, d_status, n}, {steps, d_steps, n * 4}}, stats);
+}
+
+extern "C" int atmrt_sky_directions_planes_device(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double h0, size_t n_pixels, const uint32_t* hit_count,
+                                                  const double* elevation_angle, double* true_elevation_device, uint8_t* status_device,
+                                                  uint32_t* steps_device, atmrt_sky_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!hit_count || !elevation_angle || !true_elevation_device || !status_device)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions_planes_device: a plane is NULL");
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  double step = 0.0;
+  if (int rc = sky_check(c, "atmrt_sky_directions_planes_device", spec, h0, &step)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, status_device, "status_device", &k)) return rc;
+  HIP_TRY(c, hipSetDevice(k->device));
+  SkyJob job{};
+  job.n_pixels = n_pixels, job.hit_count = hit_count, job.elevation_angle = elevation_angle, job.h0 = h0;
+  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
+  return sky_run(k, c, *spec, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats);
+}
+
+extern "C" int atmrt_sky_bodies_device(atmrt_ctx* c, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation_device,
+                                       const uint8_t* status_device, uint8_t* body_device, uint8_t* rgb_device) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation_device || !status_device || !body_device) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies: a plane is NULL");
+  SkyBodiesJob job{};
+  if (int rc = sky_bodies_check(c, "atmrt_sky_bodies", bodies, n_bodies, job)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_bodies", SKY_ON_MULTI)) return rc;
+  job.n_pixels = c->last.npx, job.azimuth = c->last.dense.azimuth;
+  job.true_elevation = true_elevation_device, job.status = status_device, job.body = body_device, job.rgb = rgb_device;
+  return sky_bodies_run(c, c, job);
+}
+
+extern "C" int atmrt_sky_bodies(atmrt_ctx* c, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation, const uint8_t* status,
+                                uint8_t* body, uint8_t* rgb) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation || !status || !body) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies: a plane is NULL");
+  SkyBodiesJob job{};
+  if (int rc = sky_bodies_check(c, "atmrt_sky_bodies", bodies, n_bodies, job)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_bodies", SKY_ON_MULTI)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n = c->last.npx;
+  double* d_true = nullptr;
+  uint8_t *d_status = nullptr, *d_body = nullptr, *d_rgb = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8), k(d_status, n), k(d_body, n); if (rgb) k(d_rgb, 3 * n); }));
+  HIP_TRY(c, hipMemcpy(d_true, true_elevation, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_status, status, n, hipMemcpyHostToDevice));
+  if (rgb) HIP_TRY(c, hipMemcpy(d_rgb, rgb, 3 * n, hipMemcpyHostToDevice));
+  job.n_pixels = n, job.azimuth = c->last.dense.azimuth;
+  job.true_elevation = d_true, job.status = d_status, job.body = d_body, job.rgb = d_rgb;
+  if (int rc = sky_bodies_run(c, c, job)) return rc;
+  HIP_TRY(c, hipMemcpy(body, d_body, n, hipMemcpyDeviceToHost));
+  if (rgb) HIP_TRY(c, hipMemcpy(rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_bodies_planes_device(atmrt_ctx* c, const atmrt_sky_body_t* bodies, uint32_t n_bodies, size_t n_pixels, const double* azimuth,
+                                              const double* true_elevation_device, const uint8_t* status_device, uint8_t* body_device,
+                                              uint8_t* rgb_device) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!azimuth || !true_elevation_device || !status_device || !body_device)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies_planes_device: a plane is NULL");
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  SkyBodiesJob job{};
+  if (int rc = sky_bodies_check(c, "atmrt_sky_bodies_planes_device", bodies, n_bodies, job)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, body_device, "body_device", &k)) return rc;
+  job.n_pixels = n_pixels, job.azimuth = azimuth;
+  job.true_elevation = true_elevation_device, job.status = status_device, job.body = body_device, job.rgb = rgb_device;
+  return sky_bodies_run(k, c, job);
+}
+
+extern "C" int atmrt_last_sky_timings(atmrt_ctx* c, double out[3]) {
+  if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  memcpy(out, c->sky_timings, sizeof c->sky_timings);
   return ATMRT_OK;
 }

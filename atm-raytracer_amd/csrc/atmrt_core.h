@@ -1456,6 +1456,80 @@ ATMRT_HD bool atm_has_cubic(const AtmTable& a) {
   return false;
 }
 
+// ---------------------------------------------------------------------------------------------
+// sky rays (include/atmrt.h, "sky rays"): the rule's pieces, one set for the kernel (k_sky_march) and the host (atmrt_sky_ray_host)
+// ---------------------------------------------------------------------------------------------
+constexpr int32_t SKY_M_MAX = 1048575;
+constexpr uint32_t SKY_BODIES_MAX = 32;
+
+// the launch elevations that march: strictly inside (-90, 90); a NaN does not
+ATMRT_HD bool sky_marches(double elevation_deg) { return elevation_deg > -90.0 && elevation_deg < 90.0; }
+
+// the rule's test on the height after one step: 0 (undecided) or the status that decides the ray, in the rule's order
+ATMRT_HD int sky_step_status(double h, double floor, double top) {
+  if (h != h) return ATMRT_SKY_LOST;
+  if (h < floor) return ATMRT_SKY_GROUND;
+  if (h >= top) return ATMRT_SKY_EXIT;
+  return 0;
+}
+
+// the true elevation [deg] of a ray that has just EXITed, from the stepper's state after the deciding step
+ATMRT_HD double sky_true_elevation(const Stepper& s, bool spherical, double radius, bool straight, double elevation_deg) {
+  if (straight) return elevation_deg;
+  if (spherical) return dm_to_degrees(dm_atan2(s.b, s.a) - s.x / radius);
+  return dm_to_degrees(dm_atan2(s.b, 1.0));
+}
+
+// The rule's per-ray function, serially: what a lane of k_sky_march computes for its list entry (there the loop is the wavefront's
+// and a decided lane idles).
+template <bool CUBIC = true>
+ATMRT_HD atmrt_sky_ray_t sky_march_one(const AtmTable& atm, bool spherical, double radius, bool straight, double step, double top, double floor,
+                                       int32_t m, double h0, double elevation_deg) {
+  atmrt_sky_ray_t out;
+  out.status = ATMRT_SKY_LOST, out.steps = 0, out.true_elevation = dm_from_bits(0x7ff8000000000000ULL);
+  if (!sky_marches(elevation_deg)) return out;
+  Stepper s;
+  stepper_init(s, spherical, radius, h0, dm_to_radians(elevation_deg));
+  out.status = ATMRT_SKY_INSIDE;
+  for (int32_t i = 1; i <= m; i++) {
+    const RayState st = stepper_next<CUBIC>(s, atm, spherical, radius, straight, step);
+    out.steps = (uint32_t)i;
+    if (const int decided = sky_step_status(st.h, floor, top)) {
+      out.status = decided;
+      break;
+    }
+  }
+  if (out.status == ATMRT_SKY_EXIT) out.true_elevation = sky_true_elevation(s, spherical, radius, straight, elevation_deg);
+  return out;
+}
+
+// A body as the kernels hold it: its unit vector and the cosine of its radius, made once on the host by the functions a lane would run.
+struct SkyBodyDev {
+  double x, y, z, cos_radius;
+};
+// the unit vector of (azimuth_deg, elevation_deg): (cos e cos a, cos e sin a, sin e)
+ATMRT_HD Vec3 sky_unit_vector(double azimuth_deg, double elevation_deg) {
+  double se, ce, sa, ca;
+  dm_sincos(dm_to_radians(elevation_deg), &se, &ce);
+  dm_sincos(dm_to_radians(azimuth_deg), &sa, &ca);
+  return v3(ce * ca, ce * sa, se);
+}
+ATMRT_HD SkyBodyDev sky_body_dev(const atmrt_sky_body_t& b) {
+  const Vec3 u = sky_unit_vector(b.azimuth_deg, b.elevation_deg);
+  return SkyBodyDev{u.x, u.y, u.z, dm_cos(dm_to_radians(b.radius_deg))};
+}
+ATMRT_HD bool sky_body_valid(const atmrt_sky_body_t& b) {
+  if (dm_isnan(b.azimuth_deg) || dm_isinf(b.azimuth_deg) || dm_isnan(b.elevation_deg) || dm_isinf(b.elevation_deg)) return false;
+  return b.radius_deg > 0.0 && b.radius_deg < 90.0;
+}
+// the body rule for an EXIT pixel: k + 1 for the first body k that holds the direction, 0 for none
+ATMRT_HD uint32_t sky_body_of(const SkyBodyDev* bodies, uint32_t n_bodies, double azimuth_deg, double true_elevation_deg) {
+  const Vec3 d = sky_unit_vector(azimuth_deg, true_elevation_deg);
+  for (uint32_t k = 0; k < n_bodies; k++)
+    if (d.x * bodies[k].x + d.y * bodies[k].y + d.z * bodies[k].z >= bodies[k].cos_radius) return k + 1;
+  return 0;
+}
+
 // calc_dist, utils.rs:42-53
 // `fast` (wave-uniform on the GPU): the step was tame (stepper_next_with: h0 + radius >= 1000 m, |dh| <= 2^100 step), or — straight
 // rays — both altitudes lie in [AtmTable::alt_lo, alt_hi].  Every caller advances by one simulation step (dx > 0, 1 mm .. 1e8 m or

@@ -261,6 +261,8 @@ struct atmrt_ctx {
   int32_t horizon_batches = 0, horizon_rebuilt = 0;   // atmrt_last_horizon_work
   atmrt::DevBuf d_shadow;                  // atmrt_shadow_mask*: the call's list of hit pixels and its counters
   double shadow_timings[3] = {};           // atmrt_last_shadow_timings
+  atmrt::DevBuf d_sky;                     // atmrt_sky_*: the call's list of sky pixels and its counters
+  double sky_timings[3] = {};              // atmrt_last_sky_timings
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
   atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
   atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend

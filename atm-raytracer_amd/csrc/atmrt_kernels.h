@@ -491,8 +491,9 @@ enum PhaseEvent {
   EV_HZ_BATCH = EV_VS_BATCH, EV_HZ_PROFILED, EV_HZ_SCANNED, EV_HZ_REFINED, EV_HZ_END, // after EV_VS_BEGIN and EV_VS_PATHS: the table is the viewshed's
   EV_LM_BEGIN = 0, EV_LM_UPLOADED, EV_LM_FIRST_PASS, EV_LM_SECOND_PASS, EV_LM_END,
   EV_SH_BEGIN = 0, EV_SH_COMPACTED, EV_SH_MARCHED, EV_SH_END,
+  EV_SKY_BEGIN = 0, EV_SKY_COMPACTED, EV_SKY_MARCHED, EV_SKY_END,
 };
-static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_HZ_END < EV_COUNT && EV_LM_END < EV_COUNT && EV_SH_END < EV_COUNT, "the borrowed events exist");
+static_assert(EV_SIGHT_END < EV_COUNT && EV_VS_END < EV_COUNT && EV_HZ_END < EV_COUNT && EV_LM_END < EV_COUNT && EV_SH_END < EV_COUNT && EV_SKY_END < EV_COUNT, "the borrowed events exist");
 #ifndef ATMRT_FAST_SEGMENTS
 #define ATMRT_FAST_SEGMENTS 4
 #endif

@@ -1,0 +1,160 @@
+// atmrt_sky.h — sky rays (include/atmrt.h, "sky rays": the rule is stated there): the true direction of every pixel of a finished
+// frame that has no trace point, and the discs of the call's bodies over them.  The launch interface for atmrt_consumers.hip; the
+// kernels themselves are compiled by atmrt_sky.hip only (ATMRT_SKY_KERNELS).
+//
+//   k_sky_compact  one thread per pixel: the pixels WITHOUT a trace point appended to a list, a wavefront's entries contiguous and
+//                  in lane order (wave_compact_append), so that the march's wavefronts are full — the ground half of a frame costs no
+//                  lanes; a pixel with a trace point gets ATMRT_SKY_NONE, NaN and 0 steps here
+//   k_sky_march    one list entry per lane: the stepper from h0 at the pixel's launch elevation and the rule's test per step — a pure
+//                  RK4 chain with no terrain and no geodesic in it (hence no CALC variants).  A lane that is decided idles (it is not
+//                  in the stepper's votes any more, as in shadow_step_loop); the wavefront leaves when all its lanes are decided.
+//                  Writes true_elevation, status and steps of its pixel; the counts of the call with one atomic per wavefront and
+//                  counter.  The list is in pixel order: its head holds a frame's top rows (high elevation, a few hundred steps), its
+//                  tail the horizon rows (the longest chains), so wavefront w takes group n_groups - 1 - w: the longest chains start
+//                  first and the short ones fill the tail of the launch (SkyJob::reverse).
+//   k_sky_bodies   one thread per pixel: the body rule (sky_body_of) for the EXIT pixels, the body plane and, where an image is given,
+//                  the body's colour over it.
+//
+// The launch covers the pixels, not the list (its length stays on the device: no host round trip between the two kernels); a
+// wavefront beyond the list's end leaves at once.  The list call (atmrt_sky_rays) marches without a list: entry i is ray i.
+#pragma once
+
+#include "atmrt_kernels.h"
+
+namespace atmrt {
+
+enum SkyCtr : int { SKY_LIST = 0, SKY_EXIT, SKY_GROUND, SKY_INSIDE, SKY_LOST, SKY_STEPS, SKY_N };
+
+struct SkyJob {
+  size_t n_pixels;
+  const uint32_t* hit_count;     // [n_pixels]; null: no compaction, every entry is a ray (the list call)
+  const double* elevation_angle; // [n_pixels] launch elevations [deg]
+  const double* alt;             // device scalar h0 (the frame's observer altitude), or null: h0 below
+  double h0;
+  double step, top, floor;
+  int32_t m;
+  int32_t reverse;               // the march takes the list from its end
+  uint32_t* list;                // [n_pixels], or null with hit_count
+  unsigned long long* ctr;       // [SKY_N], zeroed by the launch
+  double* true_elevation;        // [n_pixels]
+  uint8_t* status;               // [n_pixels]
+  uint32_t* steps;               // [n_pixels] or null
+};
+// f: the frame of the context's setting (prepare_frame); only its atmosphere, earth shape and straight_rays are read
+void launch_sky_march(const Frame& f, const SkyJob& job, hipStream_t stream, hipEvent_t ev_compacted);
+
+struct SkyBodiesJob {
+  size_t n_pixels;
+  const double* azimuth;        // [n_pixels]
+  const double* true_elevation; // [n_pixels]
+  const uint8_t* status;        // [n_pixels]
+  uint8_t* body;                // [n_pixels]
+  uint8_t* rgb;                 // [n_pixels][3] or null
+  uint32_t n_bodies;            // 0 .. SKY_BODIES_MAX
+  SkyBodyDev bodies[SKY_BODIES_MAX];
+  uint8_t colour[SKY_BODIES_MAX][4];
+};
+void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream);
+
+} // namespace atmrt
+
+#if defined(ATMRT_SKY_KERNELS)
+#include "atmrt_device.h"
+
+namespace atmrt {
+
+__global__ __launch_bounds__(256) void k_sky_compact(SkyJob j) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = p < j.n_pixels;
+  const bool sky = in && j.hit_count[p] == 0;
+  wave_compact_append(sky, (uint32_t)p, j.list, &j.ctr[SKY_LIST]); // every lane of the wavefront
+  if (in && !sky) {
+    j.true_elevation[p] = dm_from_bits(0x7ff8000000000000ULL);
+    j.status[p] = ATMRT_SKY_NONE;
+    if (j.steps) j.steps[p] = 0;
+  }
+}
+
+constexpr int SKY_WAVES = 4; // wavefronts per block
+
+// Five wavefronts per SIMD: left to itself the allocator takes 106 (Linear) / 118 (Spline) VGPRs, four wavefronts; asked for five it
+// fits both variants into 94 without scratch (profiles/sky_resources.txt) — nothing but the stepper lives across the loop.
+template <bool CUBIC>
+__global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sky_march(Frame f, SkyJob j) {
+  const int lane = threadIdx.x & 63;
+  const size_t wave = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SKY_WAVES + (threadIdx.x >> 6)));
+  const size_t n = j.list ? (size_t)j.ctr[SKY_LIST] : j.n_pixels;
+  const size_t groups = (n + 63) / 64;
+  if (wave >= groups) return; // the whole wavefront
+  const size_t first = (j.reverse ? groups - 1 - wave : wave) * 64;
+  const bool live = first + lane < n;
+  const size_t at = live ? first + lane : n - 1;
+  const size_t p = j.list ? (size_t)j.list[at] : at;
+  const double elevation_deg = j.elevation_angle[p];
+  const double h0 = j.alt ? *j.alt : j.h0;
+  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
+  const double radius = f.earth.shape_radius, step = j.step, top = j.top, floor = j.floor;
+  const bool marches = sky_marches(elevation_deg);
+  Stepper s;
+  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
+  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
+  bool decided = !live || !marches;
+  for (int i = 1; i <= j.m; i++) {
+    if (!decided) {
+      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
+      steps = i;
+      if (const int d = sky_step_status(st.h, floor, top)) {
+        status = d;
+        decided = true;
+      }
+    }
+    if (__all(decided)) break;
+  }
+  if (live) {
+    j.true_elevation[p] = status == ATMRT_SKY_EXIT ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : dm_from_bits(0x7ff8000000000000ULL);
+    j.status[p] = (uint8_t)status;
+    if (j.steps) j.steps[p] = (uint32_t)steps;
+  }
+  const unsigned long long n_exit = wave_sum(live && status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && status == ATMRT_SKY_GROUND ? 1ull : 0ull);
+  const unsigned long long n_inside = wave_sum(live && status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && status == ATMRT_SKY_LOST ? 1ull : 0ull);
+  const unsigned long long n_steps = wave_sum((unsigned long long)steps);
+  if (lane == 0) {
+    if (n_exit) atomicAdd(&j.ctr[SKY_EXIT], n_exit);
+    if (n_ground) atomicAdd(&j.ctr[SKY_GROUND], n_ground);
+    if (n_inside) atomicAdd(&j.ctr[SKY_INSIDE], n_inside);
+    if (n_lost) atomicAdd(&j.ctr[SKY_LOST], n_lost);
+    if (n_steps) atomicAdd(&j.ctr[SKY_STEPS], n_steps);
+  }
+}
+
+void launch_sky_march(const Frame& f, const SkyJob& job, hipStream_t stream, hipEvent_t ev_compacted) {
+  const size_t n = job.n_pixels;
+  (void)hipMemsetAsync(job.ctr, 0, SKY_N * sizeof(unsigned long long), stream);
+  if (job.hit_count) hipLaunchKernelGGL(k_sky_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, job);
+  if (ev_compacted) (void)hipEventRecord(ev_compacted, stream);
+  if (!n) return;
+  const dim3 grid(cdiv(n, 64 * SKY_WAVES)), blk(64 * SKY_WAVES);
+  if (f.atm_cubic) hipLaunchKernelGGL((k_sky_march<true>), grid, blk, 0, stream, f, job);
+  else hipLaunchKernelGGL((k_sky_march<false>), grid, blk, 0, stream, f, job);
+}
+
+__global__ __launch_bounds__(256) void k_sky_bodies(SkyBodiesJob j) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= j.n_pixels) return;
+  uint32_t body = 0;
+  if (j.status[p] == ATMRT_SKY_EXIT) body = sky_body_of(j.bodies, j.n_bodies, j.azimuth[p], j.true_elevation[p]);
+  j.body[p] = (uint8_t)body;
+  if (body && j.rgb) {
+    j.rgb[3 * p] = j.colour[body - 1][0];
+    j.rgb[3 * p + 1] = j.colour[body - 1][1];
+    j.rgb[3 * p + 2] = j.colour[body - 1][2];
+  }
+}
+
+void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream) {
+  if (!job.n_pixels) return;
+  hipLaunchKernelGGL(k_sky_bodies, dim3(cdiv(job.n_pixels, 256)), dim3(256), 0, stream, job);
+}
+
+} // namespace atmrt
+#endif

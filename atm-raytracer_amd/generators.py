@@ -175,6 +175,21 @@ class Context:
         """Test hook (atmrt_debug_fail_next_collective)."""
         self.check(self.lib.atmrt_debug_fail_next_collective(self.handle, index, nth))
 
+    def sky_rays(self, h0, elevation_deg, **spec):
+        """generators.sky_rays on this context."""
+        return sky_rays(self, h0, elevation_deg, **spec)
+
+    def sky_directions(self, **spec):
+        """generators.sky_directions over this context's last frame."""
+        return sky_directions(self, **spec)
+
+    def sky_bodies(self, sky, bodies, rgb=None):
+        """generators.sky_bodies over this context's last frame."""
+        return sky_bodies(self, sky, bodies, rgb)
+
+    def sky_timings(self):
+        return sky_timings(self)
+
     def check(self, rc):
         if rc != 0:
             raise AtmrtError(rc, self.lib.atmrt_last_error(self.handle).decode())
@@ -415,18 +430,126 @@ def into_coloring(lib, params_pod, conf):
     return col
 
 
-def draw_image(ctx, coloring, width, height, shadows=None):
+def draw_image(ctx, coloring, width, height, shadows=None, bodies=None, sky=None):
     """Composite the frame of the last generate() on `ctx` into an RGB8 image [height][width][3].  shadows: the status plane of
-    shadow_mask() for that frame — under Shading the first trace point of a SHADOWED pixel is drawn at ambient_light."""
+    shadow_mask() for that frame — under Shading the first trace point of a SHADOWED pixel is drawn at ambient_light.  bodies: sky
+    bodies (sky_body() or (azimuth_deg, elevation_deg, radius_deg, rgb) each) drawn over the sky pixels their refracted rays meet;
+    sky: the SkyDirections of that frame (default: sky_directions(ctx) with the spec's defaults)."""
     rgb = np.zeros((height, width, 3), dtype=np.uint8)
     if shadows is None:
         ctx.check(ctx.lib.atmrt_draw_image(ctx.handle, C.byref(coloring), rgb.ctypes.data))
-        return rgb
-    status = np.ascontiguousarray(shadows, dtype=np.uint8)
-    if status.size != width * height:
-        raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, f"the shadow status plane has {status.size} entries, the image {width * height} pixels")
-    ctx.check(ctx.lib.atmrt_draw_image_shadowed(ctx.handle, C.byref(coloring), status.ctypes.data, rgb.ctypes.data))
+    else:
+        status = np.ascontiguousarray(shadows, dtype=np.uint8)
+        if status.size != width * height:
+            raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, f"the shadow status plane has {status.size} entries, the image {width * height} pixels")
+        ctx.check(ctx.lib.atmrt_draw_image_shadowed(ctx.handle, C.byref(coloring), status.ctypes.data, rgb.ctypes.data))
+    if bodies is not None:
+        if sky is None:
+            sky = sky_directions(ctx, width=width, height=height, steps=False)
+        sky_bodies(ctx, sky, bodies, rgb)
     return rgb
+
+
+# ---- sky rays: the true direction of every sky pixel, sun and moon discs (include/atmrt.h, "sky rays") ----------------------
+SKY_TOP, SKY_M, SUN_RADIUS_DEG = 100000.0, _abi.SKY_M_MAX, 0.2666
+SKY_RAY_DTYPE = np.dtype([("status", "<i4"), ("steps", "<u4"), ("true_elevation", "<f8")])
+
+
+class SkyDirections:
+    """One sky call over a frame: true_elevation [height][width] f64 (NaN unless EXIT), status [height][width] u8 (_abi.SKY_*),
+    steps [height][width] u32 (None if not asked for), stats (dict)."""
+
+    def __init__(self, true_elevation, status, steps, stats):
+        self.true_elevation, self.status, self.steps, self.stats = true_elevation, status, steps, stats
+
+
+def sky_spec(step=0.0, top=SKY_TOP, floor=0.0, m=SKY_M):
+    """atmrt_sky_spec_t.  step 0: the context's simulation_step."""
+    return _abi.SkySpec(float(step), float(top), float(floor), int(m), 0)
+
+
+def sky_body(azimuth_deg, elevation_deg, radius_deg=SUN_RADIUS_DEG, rgb=(255, 255, 224)):
+    """atmrt_sky_body_t: the body's TRUE direction [deg], its angular radius [deg] and its colour."""
+    r, g, b = (int(v) for v in rgb)
+    return _abi.SkyBody(float(azimuth_deg), float(elevation_deg), float(radius_deg), (C.c_uint8 * 3)(r, g, b))
+
+
+def _sky_bodies_array(bodies):
+    bodies = [b if isinstance(b, _abi.SkyBody) else sky_body(*b) for b in bodies]
+    return (_abi.SkyBody * max(1, len(bodies)))(*bodies), len(bodies)
+
+
+def _sky_stats(st):
+    return {k: int(getattr(st, k)) for k, _ in _abi.SkyStats._fields_}
+
+
+def sky_ray_host(atmosphere, wavelength, earth, straight_rays, spec, h0, elevation_deg, lib=None):
+    """atmrt_sky_ray_host (host code, no device): (status, steps, true_elevation) of one ray by the function the kernel's lanes run."""
+    lib = lib or _lib.load()
+    out = _abi.SkyRay()
+    rc = lib.atmrt_sky_ray_host(C.byref(atmosphere), float(wavelength), C.byref(earth), int(bool(straight_rays)), C.byref(spec), float(h0),
+                                float(elevation_deg), C.byref(out))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_ray_host refused its arguments")
+    return out.status, out.steps, out.true_elevation
+
+
+def sky_body_host(bodies, azimuth_deg, true_elevation_deg, lib=None):
+    """atmrt_sky_body_host (host code, no device): k + 1 for the first body k that holds the direction, 0 for none."""
+    lib = lib or _lib.load()
+    arr, n = _sky_bodies_array(bodies)
+    out = C.c_uint32()
+    rc = lib.atmrt_sky_body_host(arr, n, float(azimuth_deg), float(true_elevation_deg), C.byref(out))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_body_host refused its arguments")
+    return out.value
+
+
+def sky_rays(ctx, h0, elevation_deg, **spec):
+    """atmrt_sky_rays: the list call (and the refraction table), in the setting now on `ctx`.  spec: the arguments of sky_spec, or
+    spec=an _abi.SkySpec.  Returns (records [n] of SKY_RAY_DTYPE, stats)."""
+    sp = spec["spec"] if "spec" in spec else sky_spec(**spec)
+    elev = np.ascontiguousarray(elevation_deg, dtype=np.float64).ravel()
+    rec = np.zeros(elev.size, dtype=SKY_RAY_DTYPE)
+    st = _abi.SkyStats()
+    ctx.check(ctx.lib.atmrt_sky_rays(ctx.handle, C.byref(sp), float(h0), elev.size, elev.ctypes.data, rec.ctypes.data, C.byref(st)))
+    return rec, _sky_stats(st)
+
+
+def sky_directions(ctx, width=None, height=None, steps=True, **spec):
+    """atmrt_sky_directions over the frame of the last generate() on `ctx`, in the setting now on the context.  Returns a SkyDirections."""
+    sp = spec["spec"] if "spec" in spec else sky_spec(**spec)
+    if width is None or height is None:
+        p = ctx_params(ctx)
+        width, height = int(p.width), int(p.height)
+    true = np.zeros((height, width), dtype=np.float64)
+    status = np.zeros((height, width), dtype=np.uint8)
+    stp = np.zeros((height, width), dtype=np.uint32) if steps else None
+    st = _abi.SkyStats()
+    ctx.check(ctx.lib.atmrt_sky_directions(ctx.handle, C.byref(sp), true.ctypes.data, status.ctypes.data, None if stp is None else stp.ctypes.data,
+                                           C.byref(st)))
+    return SkyDirections(true, status, stp, _sky_stats(st))
+
+
+def sky_bodies(ctx, sky, bodies, rgb=None):
+    """atmrt_sky_bodies over the frame of the last generate() on `ctx`: the body plane [height][width] u8 (k + 1 for body k, 0 for
+    none) from a SkyDirections of that frame; rgb: an RGB8 image [height][width][3] the discs are drawn into in place."""
+    arr, n = _sky_bodies_array(bodies)
+    true = np.ascontiguousarray(sky.true_elevation, dtype=np.float64)
+    status = np.ascontiguousarray(sky.status, dtype=np.uint8)
+    body = np.zeros(status.shape, dtype=np.uint8)
+    if rgb is not None and not (rgb.dtype == np.uint8 and rgb.flags["C_CONTIGUOUS"] and rgb.size == 3 * status.size):
+        raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, "rgb must be a contiguous uint8 image [height][width][3] of the frame")
+    ctx.check(ctx.lib.atmrt_sky_bodies(ctx.handle, arr, n, true.ctypes.data, status.ctypes.data, body.ctypes.data,
+                                       None if rgb is None else rgb.ctypes.data))
+    return body
+
+
+def sky_timings(ctx):
+    """atmrt_last_sky_timings of the last sky_rays / sky_directions call on `ctx`."""
+    out = (C.c_double * 3)()
+    ctx.check(ctx.lib.atmrt_last_sky_timings(ctx.handle, out))
+    return dict(zip(("compact_ms", "march_ms", "download_ms"), out))
 
 
 # ---- cast shadows: which of the frame's first trace points the light reaches (include/atmrt.h) ------------------------------

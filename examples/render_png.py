@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Render a panorama PNG on the GPU: generator (C ABI) -> renderer::draw_image on the device -> PNG via Pillow.
 Usage: python examples/render_png.py OUT.png [--scene S3] [--width 1024] [--height 512] [--generator Fast] [--objects N]
-       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]]"""
+       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]] [--sun AZ EL]"""
 import argparse
 import os
 import sys
@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--shadow-reach", type=float, default=50_000.0)
     ap.add_argument("--shadow-per-point", action="store_true",
                     help="the light is the Shading method's own world-frame vector: every point marches in its own local direction (shadow lights)")
+    ap.add_argument("--sun", type=float, nargs=2, default=None, metavar=("AZ", "EL"),
+                    help="draw the sun's disc at this TRUE direction [deg] where the refracted sky rays meet it (include/atmrt.h, sky rays)")
     a = ap.parse_args()
     from PIL import Image
     cfg, tiles = synth.scene(a.scene, a.width, a.height, generator=a.generator, step=100.0, terrain_alpha=a.terrain_alpha)
@@ -54,7 +56,13 @@ def main():
         shadows = mask.status
         print(f"light at azimuth {az:g}, elevation {el:g}: {mask.stats['lit']} points lit, {mask.stats['shadowed']} in shadow, "
               f"{generators.shadow_timings(ctx)['march_ms']:.2f} ms of shadow march")
-    rgb = generators.draw_image(ctx, generators.into_coloring(ctx.lib, cfg.params, cfg.coloring), a.width, a.height, shadows=shadows)
+    bodies = None
+    if a.sun:  # the sky march at 1000 m a step: within 5e-5 degrees of the frame's own step at a tenth of the work
+        bodies = [generators.sky_body(a.sun[0], a.sun[1])]
+    rgb = generators.draw_image(ctx, generators.into_coloring(ctx.lib, cfg.params, cfg.coloring), a.width, a.height, shadows=shadows, bodies=bodies,
+                                sky=generators.sky_directions(ctx, a.width, a.height, steps=False, step=1000.0) if bodies else None)
+    if bodies:
+        print(f"sun at true azimuth {a.sun[0]:g}, elevation {a.sun[1]:g}: {generators.sky_timings(ctx)['march_ms']:.2f} ms of sky march")
     Image.fromarray(rgb, "RGB").save(a.out)
     print(f"{a.out}: {a.width}x{a.height}, {res['n_hits']} trace points, {res['ray_steps']} ray-steps, {res['device_ms']:.2f} ms on device")
 

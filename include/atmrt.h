@@ -893,6 +893,119 @@ int atmrt_shadow_lights_planes_device(atmrt_ctx* ctx, const atmrt_shadow_lights_
                                       const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
                                       uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats);
 
+/* ---- sky rays: the true direction of every sky pixel, sun and moon discs (no reference counterpart) --------------------------
+ * A frame's elevation_angle plane holds the LAUNCH elevation of a pixel's ray at the observer.  For a pixel without a trace point
+ * (hit_count == 0) this section gives the TRUE (astronomical) elevation: the direction of the ray once it has left the atmosphere,
+ * relative to the observer's horizontal; launch - true is the astronomical refraction.  On top of it, discs ("bodies": a sun, a
+ * moon) given by their true direction are found in the frame and drawn where the refracted rays meet them — lifted and flattened
+ * near the horizon, cut by whatever terrain the frame holds.
+ *
+ * THE RULE (tests/sky_model.py restates it over the oracle's stepper).
+ *   Setting: what the context holds NOW: of the earth model only to_shape (spherical or flat, shape_radius; no calculator, no
+ *     geodesic), straight_rays, the atmosphere and the wavelength.  Terrain is not consulted.
+ *   A spec is {step [m]: 0 means the context's simulation_step, otherwise finite and > 0; top [m] finite; floor [m] finite and
+ *     below top; m: the step cap, 1 <= m <= 1 048 575}.
+ *   Ray: stepper_init(h0, to_radians(elevation_deg)); h0 is the observer's altitude of the frame (after Altitude::abs) or the
+ *     caller's.  For i = 1 .. m: st = stepper_next(step); the first of these that holds decides the ray, tested in this order:
+ *       st.h is NaN: LOST at i;  st.h < floor: GROUND at i;  st.h >= top: EXIT at i.
+ *     A ray that no i decides is INSIDE, and its steps is m.  An elevation_deg that is NaN or outside (-90, 90) is LOST at step 0,
+ *     without a march.  (The stepper advances in GROUND distance: a ray at 89.9 degrees with a 1000 m step leaps 570 km up in one
+ *     step and its height comes out NaN — that is LOST.)
+ *   True elevation of an EXIT ray [deg], the stepper state s taken after step i:
+ *       straight rays:                 elevation_deg itself, the same bits (the closed-form stepper does not maintain a and b);
+ *       refracted rays on a sphere:    to_degrees(atan2(s.b, s.a) - s.x / radius), the division IEEE, every operation rounded once;
+ *       refracted rays on a flat earth: to_degrees(atan2(s.b, 1.0)).
+ *     Every other status gives NaN.
+ *   What bends above `top` is neglected.  Over US-76 on a sphere of 6371 km from h0 = 1 m at step 100 m, the refraction of the
+ *     0-degree ray is 0.551189 deg for a top of 60 km, 0.551214 for 84 km, 0.5512150 for 100 km and 0.5512150 for 120 km: 100 km
+ *     is a sound default.  The step matters as little (0.551215 at 100 m, 0.551207 at 1000 m, 0.551199 at 5000 m), so the sky
+ *     march may take a much longer step than the frame.
+ *   Frame: pixel p with hit_count[p] == 0 is a ray of elevation_deg = elevation_angle[p]; a pixel with a trace point gets status
+ *     NONE, true elevation NaN and steps 0.  Outputs per pixel: true_elevation f64, status u8 (atmrt_sky_status), optionally steps
+ *     u32 (the deciding i; m for INSIDE; 0 for NONE and for LOST at step 0).
+ *   Bodies: at most 32 per call, each {azimuth_deg, elevation_deg: TRUE, as seen from the observer with no atmosphere, both finite;
+ *     radius_deg in (0, 90); rgb}.  For an EXIT pixel with a = its entry of the frame's azimuth plane and e = its true elevation:
+ *     (se, ce) = sincos(to_radians(e)), (sa, ca) = sincos(to_radians(a)), d = (ce * ca, ce * sa, se); the body's u the same way
+ *     from its two angles.  The pixel belongs to the FIRST body in list order with d.x * u.x + d.y * u.y + d.z * u.z (summed left
+ *     to right, every operation rounded on its own) >= cos(to_radians(radius_deg)).  The body plane holds k + 1 for body k, 0 for
+ *     no body and for a pixel that is not EXIT.  Drawing writes the body's rgb over exactly the pixels whose body is not 0; every
+ *     other byte of the image stays.  Refraction acts in the vertical plane of the azimuth: the azimuth is the pixel's own.
+ * Equal calls return equal bytes: a lane owns its pixel, the counts are integer sums.  The order in which the march takes the list
+ * (from its end, where a frame's horizon rows lie: ATMRT_SKY_ORDER=forward, read at every call, takes it from the head) decides
+ * scheduling only. */
+typedef struct atmrt_sky_spec {
+  double step;  /* [m]: 0 = the context's simulation_step, otherwise finite and > 0 */
+  double top;   /* [m], finite */
+  double floor; /* [m], finite, < top */
+  int32_t m;    /* 1 .. 1 048 575 */
+  int32_t _pad;
+} atmrt_sky_spec_t;
+typedef enum atmrt_sky_status {
+  ATMRT_SKY_NONE = 0, /* the pixel has a trace point: not a sky pixel */
+  ATMRT_SKY_EXIT = 1,
+  ATMRT_SKY_GROUND = 2,
+  ATMRT_SKY_INSIDE = 3,
+  ATMRT_SKY_LOST = 4
+} atmrt_sky_status;
+typedef struct atmrt_sky_ray {
+  int32_t status;        /* atmrt_sky_status */
+  uint32_t steps;
+  double true_elevation; /* [deg]; NaN unless status is ATMRT_SKY_EXIT */
+} atmrt_sky_ray_t;
+/* none + exit + ground + inside + lost = the pixels (the list call: none = 0); integrated_steps: the stepper steps taken. */
+typedef struct atmrt_sky_stats {
+  uint64_t none, exit, ground, inside, lost, integrated_steps;
+} atmrt_sky_stats_t;
+typedef struct atmrt_sky_body {
+  double azimuth_deg;   /* finite */
+  double elevation_deg; /* true elevation, finite */
+  double radius_deg;    /* in (0, 90) */
+  uint8_t rgb[3];
+  uint8_t _pad[5];
+} atmrt_sky_body_t;
+/* Host code, no context and no device: one ray by the function the kernel's lanes run.  spec->step must be > 0 here (there is no
+ * context to take it from).  ATMRT_ERR_INVALID_ARGUMENT: NULL, an invalid atmosphere, an unknown earth model, a spec or an h0 the
+ * rule refuses.  An elevation_deg that is NaN or outside (-90, 90) is no error: it is LOST at step 0. */
+int atmrt_sky_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays,
+                       const atmrt_sky_spec_t* spec, double h0, double elevation_deg, atmrt_sky_ray_t* out);
+/* Host code, no context and no device: the body rule for one direction.  *body = k + 1 for the first body k that holds the
+ * direction, 0 for none.  ATMRT_ERR_INVALID_ARGUMENT: NULL, more than 32 bodies, a body the rule refuses. */
+int atmrt_sky_body_host(const atmrt_sky_body_t* bodies, uint32_t n_bodies, double azimuth_deg, double true_elevation_deg, uint32_t* body);
+/* The list call, on the device: n rays from h0 at elevation_deg[n] (host arrays, any n), one record each; it also serves as the
+ * refraction table.  stats may be NULL.  ATMRT_ERR_INVALID_ARGUMENT: NULL (n > 0), a number of the spec or an h0 that is not
+ * finite, step < 0, floor >= top, m outside its range.  ATMRT_ERR_STATE: before atmrt_set_params. */
+int atmrt_sky_rays(atmrt_ctx* ctx, const atmrt_sky_spec_t* spec, double h0, size_t n, const double* elevation_deg, atmrt_sky_ray_t* records,
+                   atmrt_sky_stats_t* stats);
+/* The planes of the last frame of a single-device context, [height][width] as the frame's planes, into memory of the context's
+ * device; steps_device and stats may be NULL.  The frame stays as it is.  Refusals as atmrt_sky_rays; ATMRT_ERR_STATE also without
+ * a frame and on a multi-device context. */
+int atmrt_sky_directions_device(atmrt_ctx* ctx, const atmrt_sky_spec_t* spec, double* true_elevation_device, uint8_t* status_device,
+                                uint32_t* steps_device, atmrt_sky_stats_t* stats);
+/* The same into host arrays. */
+int atmrt_sky_directions(atmrt_ctx* ctx, const atmrt_sky_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps,
+                         atmrt_sky_stats_t* stats);
+/* The same over any hit_count and elevation_angle planes of n_pixels entries in device memory, from h0: what a gathered multi-device
+ * frame uses; the setting is still the context's. */
+int atmrt_sky_directions_planes_device(atmrt_ctx* ctx, const atmrt_sky_spec_t* spec, double h0, size_t n_pixels, const uint32_t* hit_count,
+                                       const double* elevation_angle, double* true_elevation_device, uint8_t* status_device,
+                                       uint32_t* steps_device, atmrt_sky_stats_t* stats);
+/* The body plane of the last frame of a single-device context from the planes of atmrt_sky_directions_device and the frame's
+ * azimuth plane, into memory of the context's device; rgb_device: NULL, or the [height][width][3] image the discs are drawn into
+ * in place.  ATMRT_ERR_INVALID_ARGUMENT: NULL, more than 32 bodies, a number that is not finite, a radius outside (0, 90).
+ * ATMRT_ERR_STATE: without a frame, on a multi-device context. */
+int atmrt_sky_bodies_device(atmrt_ctx* ctx, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation_device,
+                            const uint8_t* status_device, uint8_t* body_device, uint8_t* rgb_device);
+/* The same from and into host arrays (rgb: NULL, or the image, updated in place). */
+int atmrt_sky_bodies(atmrt_ctx* ctx, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation, const uint8_t* status,
+                     uint8_t* body, uint8_t* rgb);
+/* The same over the caller's planes of n_pixels entries in device memory, the azimuth plane included. */
+int atmrt_sky_bodies_planes_device(atmrt_ctx* ctx, const atmrt_sky_body_t* bodies, uint32_t n_bodies, size_t n_pixels, const double* azimuth,
+                                   const double* true_elevation_device, const uint8_t* status_device, uint8_t* body_device,
+                                   uint8_t* rgb_device);
+/* Where the time of the last atmrt_sky_rays / atmrt_sky_directions* call on ctx went, in milliseconds between events on the
+ * library's stream: out = {compaction (clear and upload included), march, download (statistics and host planes)}. */
+int atmrt_last_sky_timings(atmrt_ctx* ctx, double out[3]);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —
