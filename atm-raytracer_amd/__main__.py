@@ -11,6 +11,7 @@
                                      [--horizon-rounds N]]
                                     [--shadows [--shadow-reach M] [--shadow-lift M] [--shadow-light AZ EL] [--shadow-per-point]]
                                     [--shadow-lights FILE.csv [--shadow-lights-out OUT.npz] [--shadow-reach M] [--shadow-lift M]]
+                                    [--shadow-true [--sky-table-alt LO HI N] [--sky-table-el LO HI N]]
                                     [--sun AZ EL [--sun-radius DEG]] [--moon AZ EL] [--sky-top M] [--sky-step M] [--sky-floor M]
                                     [--sky-out OUT.npz] [--refraction-table OUT.csv [--sky-fan LO HI K]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
@@ -68,6 +69,14 @@ rows of azimuth_deg,elevation_deg as seen from the observer, each turned into a 
 --shadow-lift as above.  OUT.npz (--shadow-lights-out, shadow_lights.npz) holds lit_mask [height][width] u64 (bit l: light l reaches
 the pixel's first trace point), lit_count (its popcount, taken on the host), dirs [n][3], azimuth_deg, elevation_deg and the call's
 stats_none, stats_lit, stats_shadowed, stats_integrated_steps, stats_escaped_rays.
+`--shadow-true` (with --shadows --shadow-per-point, and with --shadow-lights) takes the given angles as the light's TRUE direction,
+as --sun takes the sun's: every shadow ray is launched where its light APPEARS from the point, up to 0.55 degrees higher at the
+horizon (include/atmrt.h, "apparent elevation"), so the terrain is lit from where the sun is drawn.  With --sun AZ EL and no
+--shadow-light the light is the sun.  The refraction table behind it spans --sky-table-alt LO HI N metres (0 9000 33) and
+--sky-table-el LO HI N degrees (-4 88 4601: above 89.5 degrees a 1000 m sky step loses the ray); --sky-top, --sky-step and
+--sky-floor apply to its rays as they do for --sun.  Without --sky-step the table is marched at the simulation step, ten times the
+work at the usual 100 m; `--sky-step 1000` is the recommended setting —
+the closure of 1.1e-4 degrees and the 12 ms of the default table's build were measured with it.
 `--sun AZ EL` and `--moon AZ EL` (no reference counterpart) draw a disc where the frame's sky pixels look at it once their rays
 have left the atmosphere (include/atmrt.h, "sky rays"): AZ and EL are the body's TRUE direction in degrees, as seen from the observer
 with no atmosphere, --sun-radius its angular radius (0.2666; the moon's is the same).  Every pixel without a trace point is marched
@@ -336,15 +345,18 @@ def read_lights_csv(path):
     return rows
 
 
-def write_shadow_lights(ctx, cfg, path, out, reach, lift, w, h):
+def write_shadow_lights(ctx, cfg, path, out, reach, lift, w, h, true_table=None):
     """gen --shadow-lights: the lit mask of the lights of `path` over the frame on the device, its popcount and the call's counts
-    to an .npz; returns what was written."""
+    to an .npz; returns what was written.  true_table: the table spec of --shadow-true (the rows are TRUE directions), or None."""
     import torch
     rows = read_lights_csv(path)
     spec, dirs = generators.shadow_lights_spec(generators.lights_from_angles(cfg.params, rows, ctx.lib), shadow_reach_of(cfg, reach, lift), lift)
     mask_dev = torch.empty((h, w), dtype=torch.int64, device=torch.device("cuda", ctx.device))
     st = _abi.ShadowStats()
-    ctx.check(ctx.lib.atmrt_shadow_lights_device(ctx.handle, C.byref(spec), mask_dev.data_ptr(), None, None, C.byref(st)))
+    if true_table is None:
+        ctx.check(ctx.lib.atmrt_shadow_lights_device(ctx.handle, C.byref(spec), mask_dev.data_ptr(), None, None, C.byref(st)))
+    else:
+        ctx.check(ctx.lib.atmrt_shadow_lights_true_device(ctx.handle, C.byref(spec), C.byref(true_table), mask_dev.data_ptr(), None, None, C.byref(st)))
     mask = mask_dev.cpu().numpy().view(np.uint64)
     count = np.unpackbits(mask.view(np.uint8).reshape(h, w, 8), axis=2).sum(axis=2).astype(np.uint8)
     data = dict(lit_mask=mask, lit_count=count, dirs=dirs, azimuth_deg=np.array([r[0] for r in rows]), elevation_deg=np.array([r[1] for r in rows]))
@@ -360,6 +372,28 @@ def sky_spec_of(a):
     if not (np.isfinite(step) and step >= 0.0 and np.isfinite(a.sky_top) and np.isfinite(a.sky_floor) and a.sky_floor < a.sky_top):
         raise config.ConfigError("--sky-step must not be negative and --sky-floor must lie below --sky-top")
     return generators.sky_spec(step, a.sky_top, a.sky_floor)
+
+
+def sky_table_spec_of(a):
+    """The atmrt_sky_table_spec_t of gen --shadow-true: --sky-table-alt LO HI N, --sky-table-el LO HI N and the sky options."""
+    alt, el = a.sky_table_alt, a.sky_table_el
+    for name, (lo, hi, n) in (("--sky-table-alt", alt), ("--sky-table-el", el)):
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi and float(n) == int(n) and int(n) >= 2):
+            raise config.ConfigError(f"{name} needs finite LO < HI and at least two entries")
+    if not (-90.0 < el[0] and el[1] < 90.0):
+        raise config.ConfigError("--sky-table-el must lie strictly between -90 and 90 degrees")
+    if int(alt[2]) > _abi.SKY_TABLE_ALT_MAX or int(el[2]) > _abi.SKY_TABLE_EL_MAX or int(alt[2]) * int(el[2]) > _abi.SKY_TABLE_ENTRIES_MAX:
+        raise config.ConfigError("the sky table takes at most 1024 altitudes, 65536 elevations and 2^24 entries")
+    return generators.sky_table_spec((alt[0], alt[1], int(alt[2])), (el[0], el[1], int(el[2])), sky=sky_spec_of(a))
+
+
+def shadow_true_table_of(a):
+    """None, or the table spec of --shadow-true, which needs a light given per point: --shadows --shadow-per-point or --shadow-lights."""
+    if not a.shadow_true:
+        return None
+    if not ((a.shadows and a.shadow_per_point) or a.shadow_lights):
+        raise config.ConfigError("--shadow-true needs a light per point: --shadows --shadow-per-point, or --shadow-lights FILE.csv")
+    return sky_table_spec_of(a)
 
 
 def sky_bodies_of(a):
@@ -419,6 +453,7 @@ def write_refraction_table(ctx, cfg, a, terrain):
 def cmd_gen(a):
     start = time.time()
     cfg = config.parse_config(a.config)
+    true_table = shadow_true_table_of(a)
     stamp = lambda msg: print(f"{time.time() - start:.3f}: {msg}", flush=True)
     stamp(f"Using terrain data directory: {os.path.join(os.getcwd(), cfg.terrain_folder)!r}")
     ctx, terrain = _ctx_with_terrain(cfg, a.config)
@@ -438,10 +473,16 @@ def cmd_gen(a):
         status_dev = torch.empty((h, w), dtype=torch.uint8, device=rgb_dev.device)
         st = _abi.ShadowStats()
         if a.shadow_per_point:  # one light of the world: every point marches in its own local direction
-            light = shadow_world_light(cfg, col, a.shadow_light)
+            # --shadow-true: the angles are the light's TRUE direction; without --shadow-light the light is the sun of --sun
+            light = shadow_world_light(cfg, col, a.shadow_light if a.shadow_light is not None or true_table is None else a.sun)
             lights, keep = generators.shadow_lights_spec(light, shadow_reach_of(cfg, a.shadow_reach, a.shadow_lift), a.shadow_lift)
-            ctx.check(ctx.lib.atmrt_shadow_lights_device(ctx.handle, C.byref(lights), None, status_dev.data_ptr(), None, C.byref(st)))
-            print(f"Light along {[float(v) for v in keep[0]]!r} of the world: {st.lit} points lit, {st.shadowed} in shadow")
+            if true_table is None:
+                ctx.check(ctx.lib.atmrt_shadow_lights_device(ctx.handle, C.byref(lights), None, status_dev.data_ptr(), None, C.byref(st)))
+            else:
+                ctx.check(ctx.lib.atmrt_shadow_lights_true_device(ctx.handle, C.byref(lights), C.byref(true_table), None, status_dev.data_ptr(), None,
+                                                                  C.byref(st)))
+            print(f"Light along {[float(v) for v in keep[0]]!r} of the world{' (true direction)' if true_table is not None else ''}: "
+                  f"{st.lit} points lit, {st.shadowed} in shadow")
         else:
             spec = shadow_spec_of(cfg, a.shadow_reach, a.shadow_lift, a.shadow_light)
             ctx.check(ctx.lib.atmrt_shadow_mask_device(ctx.handle, C.byref(spec), status_dev.data_ptr(), None, C.byref(st)))
@@ -458,7 +499,7 @@ def cmd_gen(a):
         write_refraction_table(ctx, cfg, a, terrain)
     if a.shadow_lights:  # on the device, while the frame is still in HBM
         stamp("Casting the shadows of the light list...")
-        write_shadow_lights(ctx, cfg, a.shadow_lights, a.shadow_lights_out, a.shadow_reach, a.shadow_lift, w, h)
+        write_shadow_lights(ctx, cfg, a.shadow_lights, a.shadow_lights_out, a.shadow_reach, a.shadow_lift, w, h, true_table)
     if a.visibility_map:  # likewise
         stamp("Binning the visibility map...")
         write_visibility_map(ctx, a.visibility_map, a.map_cell, "all" if a.map_all else "first")
@@ -584,6 +625,9 @@ def main(argv=None):
     g.add_argument("--shadow-per-point", action="store_true")
     g.add_argument("--shadow-lights", default=None, metavar="FILE.csv")
     g.add_argument("--shadow-lights-out", default="shadow_lights.npz", metavar="OUT.npz")
+    g.add_argument("--shadow-true", action="store_true")
+    g.add_argument("--sky-table-alt", type=float, nargs=3, default=generators.SKY_TABLE_ALT, metavar=("LO", "HI", "N"))
+    g.add_argument("--sky-table-el", type=float, nargs=3, default=generators.SKY_TABLE_EL, metavar=("LO", "HI", "N"))
     g.add_argument("--sun", type=float, nargs=2, default=None, metavar=("AZ", "EL"))
     g.add_argument("--sun-radius", type=float, default=generators.SUN_RADIUS_DEG, metavar="DEG")
     g.add_argument("--moon", type=float, nargs=2, default=None, metavar=("AZ", "EL"))

@@ -260,6 +260,14 @@ class SkyBody(C.Structure):
                 ("_pad", C.c_uint8 * 5)]
 
 
+SKY_TABLE_ALT_MAX, SKY_TABLE_EL_MAX, SKY_TABLE_ENTRIES_MAX = 1024, 65536, 1 << 24
+
+
+class SkyTableSpec(C.Structure):
+    """atmrt_sky_table_spec_t: the sky spec of the table's rays, its altitudes [m] and launch elevations [deg], its shape."""
+    _fields_ = [("sky", SkySpec)] + [(k, C.c_double) for k in ("alt_lo", "alt_hi", "el_lo", "el_hi")] + [("n_alt", C.c_uint32), ("n_el", C.c_uint32)]
+
+
 class Horizon(C.Structure):
     _fields_ = [("status", C.c_int32), ("rounds_done", C.c_int32), ("k_star", C.c_int32), ("block_index", C.c_int32)] + \
         [(k, C.c_double) for k in ("angle_clear", "angle_blocked", "resolution", "block_distance", "block_lat", "block_lon", "block_elevation")]

@@ -158,6 +158,17 @@ def load():
         "atmrt_sky_bodies": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, vp, vp, vp, vp]),
         "atmrt_sky_bodies_planes_device": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, sz, vp, vp, vp, vp, vp]),
         "atmrt_last_sky_timings": (C.c_int, [vp, pd]),
+        "atmrt_sky_table": (C.c_int, [vp, C.POINTER(_abi.SkyTableSpec), vp, vp, vp, C.POINTER(_abi.SkyStats)]),
+        "atmrt_sky_tail_host": (C.c_int, [C.POINTER(_abi.SkyTableSpec), vp, vp, vp]),
+        "atmrt_sky_apparent_host": (C.c_int, [C.POINTER(_abi.SkyTableSpec), vp, vp, dbl, dbl, pd]),
+        "atmrt_sky_apparent": (C.c_int, [vp, C.POINTER(_abi.SkyTableSpec), sz, vp, vp, vp]),
+        "atmrt_shadow_lights_true_device": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), C.POINTER(_abi.SkyTableSpec), vp, vp, vp,
+                                                      C.POINTER(_abi.ShadowStats)]),
+        "atmrt_shadow_lights_true": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), C.POINTER(_abi.SkyTableSpec), vp, vp, vp,
+                                               C.POINTER(_abi.ShadowStats)]),
+        "atmrt_shadow_lights_true_planes_device": (C.c_int, [vp, C.POINTER(_abi.ShadowLightsSpec), C.POINTER(_abi.SkyTableSpec), sz, vp, vp, vp, vp, vp,
+                                                             vp, vp, C.POINTER(_abi.ShadowStats)]),
+        "atmrt_last_sky_table_work": (C.c_int, [vp, C.POINTER(C.c_int32), pd]),
         "atmrt_ray_paths": (C.c_int, [vp, dbl, sz, vp, i32, dbl, sz, vp, vp]),
         "atmrt_atmosphere_sample": (C.c_int, [vp, sz, vp, vp, vp, vp, vp]),
         "atmrt_coords_at_dist": (C.c_int, [vp, dbl, dbl, dbl, sz, vp, vp, vp]),
@@ -216,7 +227,9 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_shadow_lights_device", "atmrt_shadow_lights", "atmrt_shadow_lights_planes_device",
             "atmrt_sky_ray_host", "atmrt_sky_body_host", "atmrt_sky_rays", "atmrt_sky_directions_device", "atmrt_sky_directions",
             "atmrt_sky_directions_planes_device", "atmrt_sky_bodies_device", "atmrt_sky_bodies", "atmrt_sky_bodies_planes_device",
-            "atmrt_last_sky_timings", "atmrt_ray_paths", "atmrt_atmosphere_sample",
+            "atmrt_last_sky_timings", "atmrt_sky_table", "atmrt_sky_tail_host", "atmrt_sky_apparent_host", "atmrt_sky_apparent",
+            "atmrt_shadow_lights_true_device", "atmrt_shadow_lights_true", "atmrt_shadow_lights_true_planes_device", "atmrt_last_sky_table_work",
+            "atmrt_ray_paths", "atmrt_atmosphere_sample",
             "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_debug_last_march_route", "atmrt_debug_interp_blend", "atmrt_result_encode_bincode",
             "atmrt_result_decode_bincode", "atmrt_comm_unique_id", "atmrt_ctx_comm_init_rank", "atmrt_ctx_comm_init_external", "atmrt_ctx_comm_init_external_device",
             "atmrt_ctx_create_multi", "atmrt_ctx_device_count", "atmrt_generate_image_device", "atmrt_image_hits_device",

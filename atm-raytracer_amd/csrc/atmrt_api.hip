@@ -166,6 +166,8 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 43: return sizeof(atmrt_sky_ray_t);
     case 44: return sizeof(atmrt_sky_stats_t);
     case 45: return sizeof(atmrt_sky_body_t);
+    // 46 stays 0
+    case 47: return sizeof(atmrt_sky_table_spec_t);
     default: return 0;
   }
 }

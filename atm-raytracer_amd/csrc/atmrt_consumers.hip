@@ -837,12 +837,16 @@ int shadow_lights_check(atmrt_ctx* c, const char* what, const atmrt_shadow_light
 
 const char* const SHADOW_LIGHTS_ON_MULTI = "has no frame of its own: shadow lights work on the gathered planes through atmrt_shadow_lights_planes_device";
 
-// shadow_run for a list of lights.  host_*: where the planes are downloaded to (null: none).
+const char* const SHADOW_TRUE_ON_MULTI = "has no frame of its own: true-direction shadow lights work on the gathered planes through atmrt_shadow_lights_true_planes_device";
+
+// shadow_run for a list of lights.  host_*: where the planes are downloaded to (null: none).  table: null, or the refraction table
+// of the true-direction rule ("apparent elevation").
 int shadow_lights_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_lights_spec_t& spec, const std::vector<double>& lights, int32_t m,
                       const TracePoints& src, uint64_t* mask_dev, uint8_t* status_dev, uint16_t* block_dev, atmrt_shadow_stats_t* stats,
-                      uint64_t* host_mask, uint8_t* host_status, uint16_t* host_block) {
+                      uint64_t* host_mask, uint8_t* host_status, uint16_t* host_block, const SkyTable* table) {
   ShadowLightsJob job{};
   job.src = src;
+  if (table) job.true_dir = 1, job.table = *table;
   job.n_lights = spec.n_lights, job.lift = spec.lift, job.m = m;
   job.lit_mask = reinterpret_cast<unsigned long long*>(mask_dev), job.status = status_dev, job.block = block_dev;
   double* d_dirs = nullptr;
@@ -858,26 +862,26 @@ int shadow_lights_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_shadow_lights
                      stats);
 }
 
-} // namespace
+// "apparent elevation", further down: the table spec checked and its step resolved; the table of k's setting built or found, every row usable
+int sky_table_check(atmrt_ctx* c, const char* what, const atmrt_sky_table_spec_t* spec, atmrt_sky_table_spec_t* resolved);
+int sky_table_for_inverse(atmrt_ctx* k, atmrt_ctx* report, const char* what, const atmrt_sky_table_spec_t& resolved, SkyTable* view);
 
-extern "C" int atmrt_shadow_lights_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask_device, uint8_t* status_device,
-                                          uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+// The routes' bodies, for atmrt_shadow_lights* (table_spec unused) and atmrt_shadow_lights_true* (true_dir).
+int shadow_lights_frame(atmrt_ctx* c, const char* what, const atmrt_shadow_lights_spec_t* spec, bool true_dir, const atmrt_sky_table_spec_t* table_spec,
+                        bool host, uint64_t* lit_mask, uint8_t* status, uint16_t* block, atmrt_shadow_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   int32_t m = 0;
   std::vector<double> lights;
-  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights", spec, lit_mask_device, status_device, &m, lights)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_shadow_lights", SHADOW_LIGHTS_ON_MULTI)) return rc;
-  return shadow_lights_run(c, c, *spec, lights, m, c->last.points(ATMRT_VIS_ALL), lit_mask_device, status_device, block_device, stats, nullptr,
-                           nullptr, nullptr);
-}
-
-extern "C" int atmrt_shadow_lights(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask, uint8_t* status, uint16_t* block,
-                                   atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  int32_t m = 0;
-  std::vector<double> lights;
-  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights", spec, lit_mask, status, &m, lights)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_shadow_lights", SHADOW_LIGHTS_ON_MULTI)) return rc;
+  if (int rc = shadow_lights_check(c, what, spec, lit_mask, status, &m, lights)) return rc;
+  atmrt_sky_table_spec_t resolved{};
+  if (true_dir)
+    if (int rc = sky_table_check(c, what, table_spec, &resolved)) return rc;
+  if (int rc = frame_state_check(c, what, true_dir ? SHADOW_TRUE_ON_MULTI : SHADOW_LIGHTS_ON_MULTI)) return rc;
+  SkyTable table{};
+  if (true_dir)
+    if (int rc = sky_table_for_inverse(c, c, what, resolved, &table)) return rc;
+  const SkyTable* tab = true_dir ? &table : nullptr;
+  if (!host) return shadow_lights_run(c, c, *spec, lights, m, c->last.points(ATMRT_VIS_ALL), lit_mask, status, block, stats, nullptr, nullptr, nullptr, tab);
   HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
   // the staging buffer: the mask (8 n), then the block planes (2 n L), then the status planes (n L); what is not asked for takes no room
   const size_t n = c->last.npx, planes = n * spec->n_lights;
@@ -889,23 +893,66 @@ extern "C" int atmrt_shadow_lights(atmrt_ctx* c, const atmrt_shadow_lights_spec_
     if (block) k(d_block, planes * sizeof(uint16_t));
     if (status) k(d_status, planes);
   }));
-  return shadow_lights_run(c, c, *spec, lights, m, c->last.points(ATMRT_VIS_ALL), d_mask, d_status, d_block, stats, lit_mask, status, block);
+  return shadow_lights_run(c, c, *spec, lights, m, c->last.points(ATMRT_VIS_ALL), d_mask, d_status, d_block, stats, lit_mask, status, block, tab);
+}
+
+int shadow_lights_planes(atmrt_ctx* c, const char* what, const atmrt_shadow_lights_spec_t* spec, bool true_dir, const atmrt_sky_table_spec_t* table_spec,
+                         size_t n_pixels, const uint32_t* hit_count, const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
+                         uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (int rc = shadow_planes_check(c, what, n_pixels, hit_count, lat, lon, elev)) return rc;
+  int32_t m = 0;
+  std::vector<double> lights;
+  if (int rc = shadow_lights_check(c, what, spec, lit_mask_device, status_device, &m, lights)) return rc;
+  atmrt_sky_table_spec_t resolved{};
+  if (true_dir)
+    if (int rc = sky_table_check(c, what, table_spec, &resolved)) return rc;
+  atmrt_ctx* k = nullptr;
+  const bool by_mask = lit_mask_device != nullptr;
+  if (int rc = planes_context(c, by_mask ? (const void*)lit_mask_device : (const void*)status_device, by_mask ? "lit_mask_device" : "status_device", &k)) return rc;
+  HIP_TRY(c, hipSetDevice(k->device));
+  SkyTable table{};
+  if (true_dir)
+    if (int rc = sky_table_for_inverse(k, c, what, resolved, &table)) return rc;
+  return shadow_lights_run(k, c, *spec, lights, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, lit_mask_device, status_device,
+                           block_device, stats, nullptr, nullptr, nullptr, true_dir ? &table : nullptr);
+}
+
+} // namespace
+
+extern "C" int atmrt_shadow_lights_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask_device, uint8_t* status_device,
+                                          uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+  return shadow_lights_frame(c, "atmrt_shadow_lights", spec, false, nullptr, false, lit_mask_device, status_device, block_device, stats);
+}
+
+extern "C" int atmrt_shadow_lights(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, uint64_t* lit_mask, uint8_t* status, uint16_t* block,
+                                   atmrt_shadow_stats_t* stats) {
+  return shadow_lights_frame(c, "atmrt_shadow_lights", spec, false, nullptr, true, lit_mask, status, block, stats);
 }
 
 extern "C" int atmrt_shadow_lights_planes_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, size_t n_pixels, const uint32_t* hit_count,
                                                  const double* lat, const double* lon, const double* elev, uint64_t* lit_mask_device,
                                                  uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats) {
-  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (int rc = shadow_planes_check(c, "atmrt_shadow_lights_planes_device", n_pixels, hit_count, lat, lon, elev)) return rc;
-  int32_t m = 0;
-  std::vector<double> lights;
-  if (int rc = shadow_lights_check(c, "atmrt_shadow_lights_planes_device", spec, lit_mask_device, status_device, &m, lights)) return rc;
-  atmrt_ctx* k = nullptr;
-  const bool by_mask = lit_mask_device != nullptr;
-  if (int rc = planes_context(c, by_mask ? (const void*)lit_mask_device : (const void*)status_device, by_mask ? "lit_mask_device" : "status_device", &k)) return rc;
-  HIP_TRY(c, hipSetDevice(k->device));
-  return shadow_lights_run(k, c, *spec, lights, m, TracePoints{n_pixels, 0, hit_count, nullptr, lat, lon, nullptr, elev}, lit_mask_device, status_device,
-                           block_device, stats, nullptr, nullptr, nullptr);
+  return shadow_lights_planes(c, "atmrt_shadow_lights_planes_device", spec, false, nullptr, n_pixels, hit_count, lat, lon, elev, lit_mask_device,
+                              status_device, block_device, stats);
+}
+
+extern "C" int atmrt_shadow_lights_true_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, const atmrt_sky_table_spec_t* table,
+                                               uint64_t* lit_mask_device, uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats) {
+  return shadow_lights_frame(c, "atmrt_shadow_lights_true", spec, true, table, false, lit_mask_device, status_device, block_device, stats);
+}
+
+extern "C" int atmrt_shadow_lights_true(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, const atmrt_sky_table_spec_t* table, uint64_t* lit_mask,
+                                        uint8_t* status, uint16_t* block, atmrt_shadow_stats_t* stats) {
+  return shadow_lights_frame(c, "atmrt_shadow_lights_true", spec, true, table, true, lit_mask, status, block, stats);
+}
+
+extern "C" int atmrt_shadow_lights_true_planes_device(atmrt_ctx* c, const atmrt_shadow_lights_spec_t* spec, const atmrt_sky_table_spec_t* table,
+                                                      size_t n_pixels, const uint32_t* hit_count, const double* lat, const double* lon,
+                                                      const double* elev, uint64_t* lit_mask_device, uint8_t* status_device, uint16_t* block_device,
+                                                      atmrt_shadow_stats_t* stats) {
+  return shadow_lights_planes(c, "atmrt_shadow_lights_true_planes_device", spec, true, table, n_pixels, hit_count, lat, lon, elev, lit_mask_device,
+                              status_device, block_device, stats);
 }
 
 extern "C" int atmrt_draw_image_shadowed_device(atmrt_ctx* c, const atmrt_coloring_t* coloring, const uint8_t* status_device, uint8_t* rgb_device) {
@@ -1201,5 +1248,171 @@ extern "C" int atmrt_sky_bodies_planes_device(atmrt_ctx* c, const atmrt_sky_body
 extern "C" int atmrt_last_sky_timings(atmrt_ctx* c, double out[3]) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
   memcpy(out, c->sky_timings, sizeof c->sky_timings);
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// apparent elevation: the refraction table of the context's setting and its inverse (kernels: atmrt_sky.h; the rule: include/atmrt.h);
+// the true-direction shadow lights above read the table through sky_table_for_inverse
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// what the rule asks of a table spec, whatever the step's source; nullptr, or what is wrong
+const char* sky_table_spec_check(const atmrt_sky_table_spec_t& s) {
+  if (const char* msg = sky_spec_check(s.sky, 0.0)) return msg;
+  if (!(std::isfinite(s.alt_lo) && std::isfinite(s.alt_hi) && std::isfinite(s.el_lo) && std::isfinite(s.el_hi))) return "alt_lo, alt_hi, el_lo and el_hi must be finite";
+  if (!(s.alt_lo < s.alt_hi)) return "alt_lo must lie below alt_hi";
+  if (!(-90.0 < s.el_lo && s.el_lo < s.el_hi && s.el_hi < 90.0)) return "el_lo and el_hi must satisfy -90 < el_lo < el_hi < 90";
+  if (s.n_alt < 2 || s.n_alt > SKY_TABLE_ALT_MAX) return "n_alt must lie in [2, 1024]";
+  if (s.n_el < 2 || s.n_el > SKY_TABLE_EL_MAX) return "n_el must lie in [2, 65536]";
+  if ((uint64_t)s.n_alt * s.n_el > SKY_TABLE_ENTRIES_MAX) return "n_alt * n_el must not exceed 2^24";
+  return nullptr;
+}
+
+int sky_table_check(atmrt_ctx* c, const char* what, const atmrt_sky_table_spec_t* spec, atmrt_sky_table_spec_t* resolved) {
+  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the table spec is NULL", what);
+  if (const char* msg = sky_table_spec_check(*spec)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: table: %s", what, msg);
+  *resolved = *spec;
+  return sky_check(c, what, &spec->sky, 0.0, &resolved->sky.step);
+}
+
+// The table of k's setting under `spec` (its step resolved), built where the key differs from the last build's, and what the host
+// asked for of it.  f: prepare_frame(k).  What it did goes to report->sky_table_rebuilt and sky_table_timings.
+int sky_table_refresh(atmrt_ctx* k, atmrt_ctx* report, const Frame& f, const atmrt_sky_table_spec_t& spec, double* host_T, uint8_t* host_S,
+                      uint32_t* host_tail, SkyTable* view) {
+  hipStream_t s = k->stream;
+  const SkyLattice lat = sky_lattice(spec);
+  const size_t n = (size_t)spec.n_alt * spec.n_el;
+  const SkyTableKey key{k->atm.serial(), f.p.straight_rays ? 1 : 0, f.earth.spherical, bits(f.earth.shape_radius), bits(spec.sky.step),
+                        bits(spec.sky.top), bits(spec.sky.floor), spec.sky.m, bits(spec.alt_lo), bits(spec.alt_hi), bits(spec.el_lo),
+                        bits(spec.el_hi), spec.n_alt, spec.n_el};
+  double* d_T = nullptr;
+  uint32_t* d_tail = nullptr;
+  uint8_t* d_S = nullptr;
+  const auto layout = [&](Carve& cv) { cv(d_T, n * sizeof(double)), cv(d_tail, spec.n_alt * sizeof(uint32_t)), cv(d_S, n); };
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], s));
+  bool rebuilt = false;
+  int rc = k->sky_table.refresh(key, [&](SkyTableInfo& info) -> int {
+    // the buffer grows inside the build, after the product is dropped: a reservation that fails leaves no table under the old key
+    HIP_TRY(report, reserve_carved(k->d_sky_table, layout));
+    SkyTableJob job{};
+    job.lat = lat, job.step = spec.sky.step, job.top = spec.sky.top, job.floor = spec.sky.floor, job.m = spec.sky.m;
+    job.T = d_T, job.S = d_S, job.tail = d_tail;
+    HIP_TRY(report, reserve_carved(k->d_sky, [&](Carve& cv) { cv(job.ctr, SKY_N * sizeof(unsigned long long)); }));
+    launch_sky_table(f, job, s, k->ev[EV_SKY_COMPACTED]);
+    HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_MARCHED], s));
+    unsigned long long ctr[SKY_N] = {};
+    info.tail.assign(spec.n_alt, 0);
+    HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(report, hipMemcpyAsync(info.tail.data(), d_tail, spec.n_alt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(report, hipStreamSynchronize(s));
+    HIP_TRY(report, hipGetLastError());
+    info.stats = atmrt_sky_stats_t{0, ctr[SKY_EXIT], ctr[SKY_GROUND], ctr[SKY_INSIDE], ctr[SKY_LOST], ctr[SKY_STEPS]};
+    info.first_unusable = -1;
+    for (uint32_t j = 0; j < spec.n_alt && info.first_unusable < 0; j++)
+      if (!sky_row_usable(info.tail[j], spec.n_el)) info.first_unusable = j;
+    return ATMRT_OK;
+  }, false, &rebuilt);
+  if (rc) return rc;
+  if (!rebuilt) { // found: an equal key means equal sizes, the table lies where its build carved it; nothing is reserved here
+    Carve cv(k->d_sky_table.ptr);
+    layout(cv);
+    HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_COMPACTED], s));
+    HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_MARCHED], s));
+  }
+  if (host_T) HIP_TRY(report, hipMemcpyAsync(host_T, d_T, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (host_S) HIP_TRY(report, hipMemcpyAsync(host_S, d_S, n, hipMemcpyDeviceToHost, s));
+  if (host_tail) memcpy(host_tail, k->sky_table.value().tail.data(), spec.n_alt * sizeof(uint32_t));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_END], s));
+  HIP_TRY(report, hipStreamSynchronize(s));
+  HIP_TRY(report, hipGetLastError());
+  HIP_TRY(report, event_intervals(k->ev + EV_SKY_BEGIN, 3, report->sky_table_timings));
+  if (!rebuilt) report->sky_table_timings[0] = report->sky_table_timings[1] = 0.0;
+  report->sky_table_rebuilt = rebuilt ? 1 : 0;
+  *view = SkyTable{lat, d_T, d_S, d_tail};
+  return ATMRT_OK;
+}
+
+int sky_table_prepare(atmrt_ctx* k, atmrt_ctx* report, Frame* f) {
+  HIP_TRY(report, hipSetDevice(k->device));
+  if (int rc = prepare_frame(k, f)) {
+    if (k != report) report->error = k->error;
+    return rc;
+  }
+  return ATMRT_OK;
+}
+
+int sky_table_for_inverse(atmrt_ctx* k, atmrt_ctx* report, const char* what, const atmrt_sky_table_spec_t& resolved, SkyTable* view) {
+  Frame f;
+  if (int rc = sky_table_prepare(k, report, &f)) return rc;
+  if (int rc = sky_table_refresh(k, report, f, resolved, nullptr, nullptr, nullptr, view)) return rc;
+  const SkyTableInfo& info = k->sky_table.value();
+  if (info.first_unusable >= 0) {
+    const uint32_t j = (uint32_t)info.first_unusable;
+    return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: row %u of the table (altitude %g m) is not usable: its monotone tail starts at entry %u of %u", what, j,
+                        sky_lattice_alt(view->lat, j), info.tail[j], resolved.n_el);
+  }
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_sky_table(atmrt_ctx* c, const atmrt_sky_table_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* tail,
+                               atmrt_sky_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  atmrt_sky_table_spec_t resolved{};
+  if (int rc = sky_table_check(c, "atmrt_sky_table", spec, &resolved)) return rc;
+  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
+  Frame f;
+  if (int rc = sky_table_prepare(k, c, &f)) return rc;
+  SkyTable view{};
+  if (int rc = sky_table_refresh(k, c, f, resolved, true_elevation, status, tail, &view)) return rc;
+  if (stats) *stats = k->sky_table.value().stats;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_tail_host(const atmrt_sky_table_spec_t* spec, const double* true_elevation, const uint8_t* status, uint32_t* tail) {
+  if (!spec || !true_elevation || !status || !tail) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (sky_table_spec_check(*spec)) return ATMRT_ERR_INVALID_ARGUMENT;
+  for (uint32_t j = 0; j < spec->n_alt; j++) tail[j] = sky_tail_of(true_elevation + (size_t)j * spec->n_el, status + (size_t)j * spec->n_el, spec->n_el);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_apparent_host(const atmrt_sky_table_spec_t* spec, const double* true_elevation, const uint32_t* tail, double h, double t,
+                                       double* apparent) {
+  if (!spec || !true_elevation || !tail || !apparent) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (sky_table_spec_check(*spec)) return ATMRT_ERR_INVALID_ARGUMENT;
+  for (uint32_t j = 0; j < spec->n_alt; j++)
+    if (!sky_row_usable(tail[j], spec->n_el)) return ATMRT_ERR_INVALID_ARGUMENT;
+  *apparent = sky_apparent(SkyTable{sky_lattice(*spec), true_elevation, nullptr, tail}, h, t);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_apparent(atmrt_ctx* c, const atmrt_sky_table_spec_t* spec, size_t n, const double* h, const double* t, double* apparent) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (n && (!h || !t || !apparent)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_apparent: h, t or apparent is NULL");
+  if (n > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_apparent: n must lie in [0, 2^32 - 1]");
+  atmrt_sky_table_spec_t resolved{};
+  if (int rc = sky_table_check(c, "atmrt_sky_apparent", spec, &resolved)) return rc;
+  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
+  SkyTable view{};
+  if (int rc = sky_table_for_inverse(k, c, "atmrt_sky_apparent", resolved, &view)) return rc;
+  if (!n) return ATMRT_OK;
+  double *d_h = nullptr, *d_t = nullptr, *d_out = nullptr;
+  HIP_TRY(c, reserve_carved(k->d_io, [&](Carve& cv) { cv(d_h, n * 8), cv(d_t, n * 8), cv(d_out, n * 8); }));
+  hipStream_t s = k->stream;
+  HIP_TRY(c, hipMemcpyAsync(d_h, h, n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, s));
+  launch_sky_apparent(view, k->params.straight_rays != 0, n, d_h, d_t, d_out, s);
+  HIP_TRY(c, hipMemcpyAsync(apparent, d_out, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_last_sky_table_work(atmrt_ctx* c, int32_t* rebuilt, double ms[3]) {
+  if (!c || !rebuilt || !ms) return ATMRT_ERR_INVALID_ARGUMENT;
+  *rebuilt = c->sky_table_rebuilt;
+  memcpy(ms, c->sky_table_timings, sizeof c->sky_table_timings);
   return ATMRT_OK;
 }

@@ -1530,6 +1530,72 @@ ATMRT_HD uint32_t sky_body_of(const SkyBodyDev* bodies, uint32_t n_bodies, doubl
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// apparent elevation (include/atmrt.h, "apparent elevation"): the refraction table's lattice and its inverse, one set for the
+// kernels (k_sky_table_march, k_sky_tail, k_sky_apparent, k_shadow_lights) and the host (atmrt_sky_tail_host, atmrt_sky_apparent_host)
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t SKY_TABLE_ALT_MAX = 1024, SKY_TABLE_EL_MAX = 65536, SKY_TABLE_ENTRIES_MAX = 1u << 24;
+
+struct SkyLattice {
+  double alt_lo, dh, el_lo, de;
+  uint32_t n_alt, n_el;
+};
+ATMRT_HD SkyLattice sky_lattice(const atmrt_sky_table_spec_t& s) {
+  return SkyLattice{s.alt_lo, (s.alt_hi - s.alt_lo) / (double)(s.n_alt - 1), s.el_lo, (s.el_hi - s.el_lo) / (double)(s.n_el - 1), s.n_alt, s.n_el};
+}
+ATMRT_HD double sky_lattice_alt(const SkyLattice& l, uint32_t j) { return l.alt_lo + (double)j * l.dh; }
+ATMRT_HD double sky_lattice_el(const SkyLattice& l, uint32_t k) { return l.el_lo + (double)k * l.de; }
+
+// The table as the inverse reads it: T[n_alt][n_el], S[n_alt][n_el] (the status plane: the tail rule's input, not the inverse's) and tail[n_alt].
+struct SkyTable {
+  SkyLattice lat;
+  const double* T;
+  const uint8_t* S;
+  const uint32_t* tail;
+};
+
+// tail[j] of one row, serially from the row's end (k_sky_tail does it a wavefront at a time)
+ATMRT_HD uint32_t sky_tail_of(const double* T, const uint8_t* S, uint32_t n_el) {
+  if (S[n_el - 1] != ATMRT_SKY_EXIT) return n_el;
+  uint32_t k0 = n_el - 1;
+  while (k0 > 0 && S[k0 - 1] == ATMRT_SKY_EXIT && T[k0 - 1] < T[k0]) k0--;
+  return k0;
+}
+ATMRT_HD bool sky_row_usable(uint32_t tail, uint32_t n_el) { return tail <= n_el - 2; } // n_el >= 2
+
+// row(j, t) over the row's entries T[0 .. n_el - 1] with its tail k0 <= n_el - 2
+ATMRT_HD double sky_apparent_row(const SkyLattice& l, const double* T, uint32_t k0, double t) {
+  if (t != t) return t;
+  const uint32_t L = l.n_el - 1;
+  if (t < T[k0]) return t + (sky_lattice_el(l, k0) - T[k0]);
+  if (t > T[L]) return t + (sky_lattice_el(l, L) - T[L]);
+  uint32_t lo = k0, hi = L; // T[hi] >= t, and no index in (k0, lo] has T >= t
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (T[mid] >= t) hi = mid;
+    else lo = mid;
+  }
+  const double t_lo = T[hi - 1], w = (t - t_lo) / (T[hi] - t_lo);
+  const double e_lo = sky_lattice_el(l, hi - 1);
+  return e_lo + w * (sky_lattice_el(l, hi) - e_lo);
+}
+
+// apparent(h, t) over a table whose every row is usable
+ATMRT_HD double sky_apparent(const SkyTable& tab, double h, double t) {
+  const SkyLattice& l = tab.lat;
+  double u = (h - l.alt_lo) / l.dh;
+  if (u != u) return dm_from_bits(0x7ff8000000000000ULL);
+  const double last = (double)(l.n_alt - 1);
+  if (u < 0.0) u = 0.0;
+  if (u > last) u = last;
+  uint32_t j = (uint32_t)u; // floor: u >= 0
+  if (j > l.n_alt - 2) j = l.n_alt - 2;
+  const double f = u - (double)j;
+  const double a = sky_apparent_row(l, tab.T + (size_t)j * l.n_el, tab.tail[j], t);
+  const double b = sky_apparent_row(l, tab.T + (size_t)(j + 1) * l.n_el, tab.tail[j + 1], t);
+  return a + f * (b - a);
+}
+
 // calc_dist, utils.rs:42-53
 // `fast` (wave-uniform on the GPU): the step was tame (stepper_next_with: h0 + radius >= 1000 m, |dh| <= 2^100 step), or — straight
 // rays — both altitudes lie in [AtmTable::alt_lo, alt_hi].  Every caller advances by one simulation step (dx > 0, 1 mm .. 1e8 m or

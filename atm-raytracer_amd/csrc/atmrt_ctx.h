@@ -119,6 +119,9 @@ using CeilKey = std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, EarthKey, Lay
 // simulation_step, K, m, straight_rays, earth
 using ViewshedKey = std::tuple<uint64_t, uint64_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, int32_t, int32_t, int32_t, EarthKey>;
 using OrderKey = std::tuple<uint64_t, uint64_t, int32_t, int32_t, uint64_t>;        // ceiling, bins, image rows, altitude_kind, altitude
+// atm (atmosphere, wavelength), straight_rays, spherical, shape_radius, then the table spec with its step resolved: step, top, floor,
+// m, alt_lo, alt_hi, el_lo, el_hi, n_alt, n_el
+using SkyTableKey = std::tuple<uint64_t, int32_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, int32_t, uint64_t, uint64_t, uint64_t, uint64_t, uint32_t, uint32_t>;
 inline EarthKey key_of(const Earth& e) {
   return {e.calc, e.flat_dirs, e.cart, e.spherical, bits(e.calc_radius), bits(e.cart_radius), bits(e.a), bits(e.b), bits(e.shape_radius)};
 }
@@ -133,6 +136,12 @@ struct Atm {
 };
 struct Escape { // the certificate from the mosaic's top minus a step up: the lowest altitude from which it holds, the largest bound above that
   double from = 0.0, bound = 0.0;
+};
+
+struct SkyTableInfo { // beside the refraction table in d_sky_table: what the host keeps of it
+  atmrt_sky_stats_t stats{};  // of the march that built it
+  std::vector<uint32_t> tail; // [n_alt]
+  int64_t first_unusable = -1; // the first row with tail > n_el - 2, or -1
 };
 
 // The last generated frame, for the calls that read it: run_generator (atmrt_api.hip) resets `valid`, `ceil_rows` and `march_route`
@@ -263,6 +272,10 @@ struct atmrt_ctx {
   double shadow_timings[3] = {};           // atmrt_last_shadow_timings
   atmrt::DevBuf d_sky;                     // atmrt_sky_*: the call's list of sky pixels and its counters
   double sky_timings[3] = {};              // atmrt_last_sky_timings
+  atmrt::DevBuf d_sky_table;               // "apparent elevation": T [n_alt][n_el] f64, then tail [n_alt] u32, then S [n_alt][n_el] u8, kept across calls
+  atmrt::Cached<atmrt::SkyTableKey, atmrt::SkyTableInfo> sky_table;
+  int32_t sky_table_rebuilt = 0;           // atmrt_last_sky_table_work
+  double sky_table_timings[3] = {};
   // ... it survives the second prepare_workspace of an InterpolatingRectilinear frame (lattice frame, then the image frame again)
   atmrt::DevBuf d_counters;                // zeroed once per frame: the lattice pass and the blend count into the same block
   atmrt::DevBuf d_interp;                  // InterpBuffers: the ray table and the lattice keys, read by the blend

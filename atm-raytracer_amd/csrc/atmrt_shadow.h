@@ -15,7 +15,10 @@
 //                     function for both kernels).  The lane collects its LIT bits in a register and writes lit_mask[p] once: no
 //                     atomics on the mask; the planes of the pixels without a trace point are cleared ahead of the compaction.
 //                     The point and its three vectors are read and made again per light (keeping them across the step loop
-//                     costs a wavefront per SIMD: profiles/shadow_lights_resources.txt).
+//                     costs a wavefront per SIMD: profiles/shadow_lights_resources.txt).  TRUE_DIR ("apparent elevation" of
+//                     include/atmrt.h: the lights are TRUE directions) puts sky_apparent(H_0, elevation) between the local
+//                     direction and the three no-march tests: two bisections over the refraction table per pair, a dozen loads
+//                     each, ahead of a march of 10 to 200 steps (profiles/shadow_true_resources.txt).
 //
 // The launch covers the pixels, not the list (its length stays on the device: no host round trip between the two kernels); a
 // wavefront beyond the list's end leaves at once.
@@ -56,6 +59,8 @@ struct ShadowLightsJob {
   unsigned long long* lit_mask; // [n_pixels] or null
   uint8_t* status;      // [n_lights][n_pixels] or null
   uint16_t* block;      // [n_lights][n_pixels] or null
+  int32_t true_dir;     // the lights are true directions: the launch elevation is sky_apparent over `table`
+  SkyTable table;       // read with true_dir alone
 };
 void launch_shadow_lights(const Frame& f, const ShadowLightsJob& job, hipStream_t stream, hipEvent_t ev_compacted);
 
@@ -161,7 +166,7 @@ void launch_shadow_mask(const Frame& f, const ShadowJob& job, hipStream_t stream
 
 // include/atmrt.h, "shadow lights".  Per lane: one list entry, every light of the call in turn.  The loop over the lights is
 // wave-uniform (n_lights and the lights are the call's), so the votes of the step loop are those of k_shadow_march.
-template <int CALC, bool CUBIC>
+template <int CALC, bool CUBIC, bool TRUE_DIR>
 __global__ __launch_bounds__(64 * SHADOW_WAVES) void k_shadow_lights(Frame f, ShadowLightsJob j) {
   const int lane = threadIdx.x & 63;
   const size_t first = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SHADOW_WAVES + (threadIdx.x >> 6))) * 64;
@@ -185,6 +190,9 @@ __global__ __launch_bounds__(64 * SHADOW_WAVES) void k_shadow_lights(Frame f, Sh
       Vec3 vn, ve, vu;
       world_directions(e, lat, lon, vn, ve, vu);
       shadow_local_direction(vn, ve, vu, light, azimuth_deg, elevation_deg);
+    }
+    if (TRUE_DIR) { // the light's true elevation -> where it appears from H_0; straight rays: itself
+      if (!f.p.straight_rays && elevation_deg > -90.0 && elevation_deg < 90.0) elevation_deg = sky_apparent(j.table, h0, elevation_deg);
     }
     // decided without a march: the zenith (LIT), the nadir (SHADOWED, block 1), a NaN (LIT); 0 steps
     const bool marches = elevation_deg > -90.0 && elevation_deg < 90.0;
@@ -226,10 +234,16 @@ void launch_shadow_lights(const Frame& f, const ShadowLightsJob& job, hipStream_
   hipLaunchKernelGGL(k_shadow_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, list);
   if (ev_compacted) (void)hipEventRecord(ev_compacted, stream);
   const dim3 grid(cdiv(n, 64 * SHADOW_WAVES)), blk(64 * SHADOW_WAVES);
-  if (f.atm_cubic) {
-    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_lights<CALC, true>), grid, blk, 0, stream, f, job));
+  if (job.true_dir) {
+    if (f.atm_cubic) {
+      ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_lights<CALC, true, true>), grid, blk, 0, stream, f, job));
+    } else {
+      ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_lights<CALC, false, true>), grid, blk, 0, stream, f, job));
+    }
+  } else if (f.atm_cubic) {
+    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_lights<CALC, true, false>), grid, blk, 0, stream, f, job));
   } else {
-    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_lights<CALC, false>), grid, blk, 0, stream, f, job));
+    ATMRT_DISPATCH_CALC(f.earth.calc, hipLaunchKernelGGL((k_shadow_lights<CALC, false, false>), grid, blk, 0, stream, f, job));
   }
 }
 

@@ -15,6 +15,12 @@
 //   k_sky_bodies   one thread per pixel: the body rule (sky_body_of) for the EXIT pixels, the body plane and, where an image is given,
 //                  the body's colour over it.
 //
+//   k_sky_table_march  ("apparent elevation" of include/atmrt.h) k_sky_march's loop over the n_alt x n_el rays of a refraction table's
+//                  lattice, each with its row's h0; k runs fastest: a wavefront holds neighbouring elevations of one altitude and
+//                  chains of similar length.  A kernel of its own, so that k_sky_march's two instantiations stay as they are.
+//   k_sky_tail     one wavefront per row of the table: tail[j] (sky_tail_of), 64 entries at a time from the row's end.
+//   k_sky_apparent one thread per (h, t) pair of a list call: sky_apparent over the table.
+//
 // The launch covers the pixels, not the list (its length stays on the device: no host round trip between the two kernels); a
 // wavefront beyond the list's end leaves at once.  The list call (atmrt_sky_rays) marches without a list: entry i is ray i.
 #pragma once
@@ -55,6 +61,20 @@ struct SkyBodiesJob {
   uint8_t colour[SKY_BODIES_MAX][4];
 };
 void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream);
+
+struct SkyTableJob {
+  SkyLattice lat;
+  double step, top, floor;
+  int32_t m;
+  unsigned long long* ctr; // [SKY_N], zeroed by the launch
+  double* T;               // [n_alt][n_el]
+  uint8_t* S;              // [n_alt][n_el]
+  uint32_t* tail;          // [n_alt]
+};
+// the march, then (after ev_marched, where one is given) the tails
+void launch_sky_table(const Frame& f, const SkyTableJob& job, hipStream_t stream, hipEvent_t ev_marched);
+// out[i] = apparent(h[i], t[i]) over `tab`, or t[i] itself with straight rays
+void launch_sky_apparent(const SkyTable& tab, bool straight, size_t n, const double* h, const double* t, double* out, hipStream_t stream);
 
 } // namespace atmrt
 
@@ -154,6 +174,96 @@ __global__ __launch_bounds__(256) void k_sky_bodies(SkyBodiesJob j) {
 void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream) {
   if (!job.n_pixels) return;
   hipLaunchKernelGGL(k_sky_bodies, dim3(cdiv(job.n_pixels, 256)), dim3(256), 0, stream, job);
+}
+
+// k_sky_march's loop with a per-ray h0: entry at = j * n_el + k of the lattice is the ray (h_j, e_k).
+template <bool CUBIC>
+__global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sky_table_march(Frame f, SkyTableJob j) {
+  const int lane = threadIdx.x & 63;
+  const size_t first = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SKY_WAVES + (threadIdx.x >> 6))) * 64;
+  const size_t n = (size_t)j.lat.n_alt * j.lat.n_el;
+  if (first >= n) return; // the whole wavefront
+  const bool live = first + lane < n;
+  const size_t at = live ? first + lane : n - 1;
+  const uint32_t row = (uint32_t)(at / j.lat.n_el), k = (uint32_t)(at - (size_t)row * j.lat.n_el);
+  const double elevation_deg = sky_lattice_el(j.lat, k), h0 = sky_lattice_alt(j.lat, row);
+  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
+  const double radius = f.earth.shape_radius, step = j.step, top = j.top, floor = j.floor;
+  const bool marches = sky_marches(elevation_deg);
+  Stepper s;
+  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
+  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
+  bool decided = !live || !marches;
+  for (int i = 1; i <= j.m; i++) {
+    if (!decided) {
+      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
+      steps = i;
+      if (const int d = sky_step_status(st.h, floor, top)) {
+        status = d;
+        decided = true;
+      }
+    }
+    if (__all(decided)) break;
+  }
+  if (live) {
+    j.T[at] = status == ATMRT_SKY_EXIT ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : dm_from_bits(0x7ff8000000000000ULL);
+    j.S[at] = (uint8_t)status;
+  }
+  const unsigned long long n_exit = wave_sum(live && status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && status == ATMRT_SKY_GROUND ? 1ull : 0ull);
+  const unsigned long long n_inside = wave_sum(live && status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && status == ATMRT_SKY_LOST ? 1ull : 0ull);
+  const unsigned long long n_steps = wave_sum((unsigned long long)steps);
+  if (lane == 0) {
+    if (n_exit) atomicAdd(&j.ctr[SKY_EXIT], n_exit);
+    if (n_ground) atomicAdd(&j.ctr[SKY_GROUND], n_ground);
+    if (n_inside) atomicAdd(&j.ctr[SKY_INSIDE], n_inside);
+    if (n_lost) atomicAdd(&j.ctr[SKY_LOST], n_lost);
+    if (n_steps) atomicAdd(&j.ctr[SKY_STEPS], n_steps);
+  }
+}
+
+// One wavefront per row: lane l of a round looks at the pair (k - 1, k) with k = base - l, from the row's end downward; the first
+// pair that does not continue the tail ends it at its k (k = 0 has no entry below it and ends every row).
+__global__ __launch_bounds__(64) void k_sky_tail(SkyTableJob j) {
+  const uint32_t row = blockIdx.x, n_el = j.lat.n_el;
+  const int lane = threadIdx.x;
+  const double* T = j.T + (size_t)row * n_el;
+  const uint8_t* S = j.S + (size_t)row * n_el;
+  uint32_t tail = n_el;
+  if (S[n_el - 1] == ATMRT_SKY_EXIT) {
+    for (uint32_t base = n_el - 1;; base -= 64) { // wave-uniform
+      const bool in = base >= (uint32_t)lane + 1; // k >= 1
+      const uint32_t k = in ? base - (uint32_t)lane : 0;
+      const bool goes_on = in && S[k - 1] == ATMRT_SKY_EXIT && T[k - 1] < T[k];
+      const unsigned long long ends = __ballot(!goes_on);
+      if (ends) {
+        const uint32_t l = (uint32_t)__ffsll((long long)ends) - 1;
+        tail = base >= l ? base - l : 0;
+        break;
+      }
+    }
+  }
+  if (lane == 0) j.tail[row] = tail;
+}
+
+void launch_sky_table(const Frame& f, const SkyTableJob& job, hipStream_t stream, hipEvent_t ev_marched) {
+  const size_t n = (size_t)job.lat.n_alt * job.lat.n_el;
+  (void)hipMemsetAsync(job.ctr, 0, SKY_N * sizeof(unsigned long long), stream);
+  const dim3 grid(cdiv(n, 64 * SKY_WAVES)), blk(64 * SKY_WAVES);
+  if (f.atm_cubic) hipLaunchKernelGGL((k_sky_table_march<true>), grid, blk, 0, stream, f, job);
+  else hipLaunchKernelGGL((k_sky_table_march<false>), grid, blk, 0, stream, f, job);
+  if (ev_marched) (void)hipEventRecord(ev_marched, stream);
+  hipLaunchKernelGGL(k_sky_tail, dim3(job.lat.n_alt), dim3(64), 0, stream, job);
+}
+
+__global__ __launch_bounds__(256) void k_sky_apparent(SkyTable tab, int straight, size_t n, const double* h, const double* t, double* out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = straight ? t[i] : sky_apparent(tab, h[i], t[i]);
+}
+
+void launch_sky_apparent(const SkyTable& tab, bool straight, size_t n, const double* h, const double* t, double* out, hipStream_t stream) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_sky_apparent, dim3(cdiv(n, 256)), dim3(256), 0, stream, tab, straight ? 1 : 0, n, h, t, out);
 }
 
 } // namespace atmrt

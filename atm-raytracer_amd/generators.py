@@ -190,6 +190,34 @@ class Context:
     def sky_timings(self):
         return sky_timings(self)
 
+    def sky_table(self, spec=None, **kw):
+        """generators.sky_table on this context."""
+        return sky_table(self, spec, **kw)
+
+    def sky_apparent(self, h, t, spec=None):
+        """generators.sky_apparent on this context."""
+        return sky_apparent(self, h, t, spec)
+
+    def sky_table_work(self):
+        """generators.sky_table_work of this context's last call that needed the table."""
+        return sky_table_work(self)
+
+    def sky_table_spec(self, *args, **kw):
+        """generators.sky_table_spec (needs no context: here for the calls above)."""
+        return sky_table_spec(*args, **kw)
+
+    def sky_tail_host(self, spec, true_elevation, status):
+        """generators.sky_tail_host through this context's library (host code, no device)."""
+        return sky_tail_host(spec, true_elevation, status, self.lib)
+
+    def sky_apparent_host(self, spec, true_elevation, tail, h, t):
+        """generators.sky_apparent_host through this context's library (host code, no device)."""
+        return sky_apparent_host(spec, true_elevation, tail, h, t, self.lib)
+
+    def shadow_lights(self, dirs, reach, lift=0.0, **kw):
+        """generators.shadow_lights over this context's last frame (true_table=spec: the lights are true directions)."""
+        return shadow_lights(self, dirs, reach, lift, **kw)
+
     def check(self, rc):
         if rc != 0:
             raise AtmrtError(rc, self.lib.atmrt_last_error(self.handle).decode())
@@ -552,6 +580,86 @@ def sky_timings(ctx):
     return dict(zip(("compact_ms", "march_ms", "download_ms"), out))
 
 
+# ---- apparent elevation: the refraction table and its inverse (include/atmrt.h, "apparent elevation") ----------------------
+SKY_TABLE_ALT, SKY_TABLE_EL = (0.0, 9000.0, 33), (-4.0, 88.0, 4601)
+
+
+class SkyTable:
+    """One atmrt_sky_table call: true_elevation [n_alt][n_el] f64 (NaN unless EXIT), status [n_alt][n_el] u8, tail [n_alt] u32, stats
+    (of the march that built the table), rebuilt (this call built it) and ms (march, tail, download), the spec."""
+
+    def __init__(self, spec, true_elevation, status, tail, stats, rebuilt, ms):
+        self.spec, self.true_elevation, self.status, self.tail, self.stats, self.rebuilt, self.ms = spec, true_elevation, status, tail, stats, rebuilt, ms
+
+    @property
+    def usable(self):
+        return self.tail.astype(np.int64) <= self.spec.n_el - 2
+
+
+def sky_table_spec(alt=SKY_TABLE_ALT, el=SKY_TABLE_EL, **sky):
+    """atmrt_sky_table_spec_t.  alt: (lo, hi, n) [m]; el: (lo, hi, n) [deg]; the rest: the arguments of sky_spec, or sky=an _abi.SkySpec."""
+    sp = sky["sky"] if "sky" in sky else sky_spec(**sky)
+    return _abi.SkyTableSpec(sp, float(alt[0]), float(alt[1]), float(el[0]), float(el[1]), int(alt[2]), int(el[2]))
+
+
+def sky_table_work(ctx):
+    """atmrt_last_sky_table_work: (rebuilt, {march_ms, tail_ms, download_ms}) of the last call on `ctx` that needed the table."""
+    rebuilt, ms = C.c_int32(), (C.c_double * 3)()
+    ctx.check(ctx.lib.atmrt_last_sky_table_work(ctx.handle, C.byref(rebuilt), ms))
+    return rebuilt.value, dict(zip(("march_ms", "tail_ms", "download_ms"), ms))
+
+
+def sky_table(ctx, spec=None, planes=True):
+    """atmrt_sky_table: the refraction table of the setting now on `ctx`, built or found.  planes=False: the tail alone."""
+    spec = spec or sky_table_spec()
+    shape = (spec.n_alt, spec.n_el)
+    true = np.zeros(shape, dtype=np.float64) if planes else None
+    status = np.zeros(shape, dtype=np.uint8) if planes else None
+    tail = np.zeros(spec.n_alt, dtype=np.uint32)
+    st = _abi.SkyStats()
+    ctx.check(ctx.lib.atmrt_sky_table(ctx.handle, C.byref(spec), *[None if a is None else a.ctypes.data for a in (true, status)], tail.ctypes.data,
+                                      C.byref(st)))
+    rebuilt, ms = sky_table_work(ctx)
+    return SkyTable(spec, true, status, tail, _sky_stats(st), rebuilt, ms)
+
+
+def sky_tail_host(spec, true_elevation, status, lib=None):
+    """atmrt_sky_tail_host (host code, no device): tail [n_alt] of the caller's planes."""
+    lib = lib or _lib.load()
+    true = np.ascontiguousarray(true_elevation, dtype=np.float64)
+    status = np.ascontiguousarray(status, dtype=np.uint8)
+    assert true.size == status.size == spec.n_alt * spec.n_el
+    tail = np.zeros(spec.n_alt, dtype=np.uint32)
+    rc = lib.atmrt_sky_tail_host(C.byref(spec), true.ctypes.data, status.ctypes.data, tail.ctypes.data)
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_tail_host refused its arguments")
+    return tail
+
+
+def sky_apparent_host(spec, true_elevation, tail, h, t, lib=None):
+    """atmrt_sky_apparent_host (host code, no device): apparent(h, t) over the caller's table by the function the kernels run."""
+    lib = lib or _lib.load()
+    true = np.ascontiguousarray(true_elevation, dtype=np.float64)
+    tail = np.ascontiguousarray(tail, dtype=np.uint32)
+    assert true.size == spec.n_alt * spec.n_el and tail.size == spec.n_alt
+    out = C.c_double()
+    rc = lib.atmrt_sky_apparent_host(C.byref(spec), true.ctypes.data, tail.ctypes.data, float(h), float(t), C.byref(out))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_apparent_host refused its arguments")
+    return out.value
+
+
+def sky_apparent(ctx, h, t, spec=None):
+    """atmrt_sky_apparent: where a body of true elevation t[i] [deg] appears from altitude h[i] [m], in the setting now on `ctx`."""
+    spec = spec or sky_table_spec()
+    h, t = np.ascontiguousarray(h, dtype=np.float64).ravel(), np.ascontiguousarray(t, dtype=np.float64).ravel()
+    if h.size != t.size:
+        raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, f"{h.size} altitudes for {t.size} true elevations")
+    out = np.zeros(h.size, dtype=np.float64)
+    ctx.check(ctx.lib.atmrt_sky_apparent(ctx.handle, C.byref(spec), h.size, h.ctypes.data, t.ctypes.data, out.ctypes.data))
+    return out
+
+
 # ---- cast shadows: which of the frame's first trace points the light reaches (include/atmrt.h) ------------------------------
 class ShadowMask:
     """One shadow call: status [height][width] u8 (_abi.SHADOW_*), block [height][width] u16 (None if not asked for), stats (dict)."""
@@ -644,9 +752,11 @@ def shadow_lights_spec(dirs, reach, lift=0.0):
     return spec, dirs
 
 
-def shadow_lights(ctx, dirs, reach, lift=0.0, status=False, block=False, width=None, height=None, mask=True):
+def shadow_lights(ctx, dirs, reach, lift=0.0, status=False, block=False, width=None, height=None, mask=True, true_table=None):
     """atmrt_shadow_lights over the frame of the last generate() on `ctx`, in the setting now on the context.  dirs: [n_lights][3]
-    world-frame vectors toward the lights (lights_from_angles, or a coloring's light_dir).  Returns a ShadowLights."""
+    world-frame vectors toward the lights (lights_from_angles, or a coloring's light_dir).  true_table: None, or the
+    _abi.SkyTableSpec (sky_table_spec) of the refraction table: the vectors are then the lights' TRUE directions and every shadow
+    ray is launched where its light appears (atmrt_shadow_lights_true).  Returns a ShadowLights."""
     spec, dirs = shadow_lights_spec(dirs, reach, lift)
     if width is None or height is None:
         p = ctx_params(ctx)
@@ -656,7 +766,11 @@ def shadow_lights(ctx, dirs, reach, lift=0.0, status=False, block=False, width=N
     sta = np.zeros((n, height, width), dtype=np.uint8) if status else None
     blk = np.zeros((n, height, width), dtype=np.uint16) if block else None
     st = _abi.ShadowStats()
-    ctx.check(ctx.lib.atmrt_shadow_lights(ctx.handle, C.byref(spec), *[None if a is None else a.ctypes.data for a in (lit, sta, blk)], C.byref(st)))
+    out = [None if a is None else a.ctypes.data for a in (lit, sta, blk)]
+    if true_table is None:
+        ctx.check(ctx.lib.atmrt_shadow_lights(ctx.handle, C.byref(spec), *out, C.byref(st)))
+    else:
+        ctx.check(ctx.lib.atmrt_shadow_lights_true(ctx.handle, C.byref(spec), C.byref(true_table), *out, C.byref(st)))
     return ShadowLights(lit, sta, blk, _shadow_stats(st), dirs)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Render a panorama PNG on the GPU: generator (C ABI) -> renderer::draw_image on the device -> PNG via Pillow.
 Usage: python examples/render_png.py OUT.png [--scene S3] [--width 1024] [--height 512] [--generator Fast] [--objects N]
-       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]] [--sun AZ EL]"""
+       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]] [--sun AZ EL [--shadows --shadow-true]]"""
 import argparse
 import os
 import sys
@@ -28,7 +28,12 @@ def main():
                     help="the light is the Shading method's own world-frame vector: every point marches in its own local direction (shadow lights)")
     ap.add_argument("--sun", type=float, nargs=2, default=None, metavar=("AZ", "EL"),
                     help="draw the sun's disc at this TRUE direction [deg] where the refracted sky rays meet it (include/atmrt.h, sky rays)")
+    ap.add_argument("--shadow-true", action="store_true",
+                    help="with --sun AZ EL --shadows: the shadows' light is the sun at its TRUE direction, launched where it appears from "
+                         "every point (include/atmrt.h, apparent elevation)")
     a = ap.parse_args()
+    if a.shadow_true and not (a.sun and a.shadows):
+        ap.error("--shadow-true lights the terrain from the sun of --sun AZ EL: use --sun AZ EL --shadows --shadow-true")
     from PIL import Image
     cfg, tiles = synth.scene(a.scene, a.width, a.height, generator=a.generator, step=100.0, terrain_alpha=a.terrain_alpha)
     view = {"coloring": {a.coloring: {"water_level": 300.0} if a.coloring == "Simple" else {"water_level": 300.0, "light_dir": 40.0, "light_zenith_angle": 90.0 - a.sun_elevation}}}
@@ -47,7 +52,14 @@ def main():
         if a.coloring != "Shading":
             ap.error("--shadows darkens the Shading method's image: use --coloring Shading")
         az, el = generators.light_from_coloring(cfg.params, cfg.coloring["light_zenith_angle"], cfg.coloring["light_dir"])
-        if a.shadow_per_point:  # slopes and shadows share one light: the coloring's light_dir vector
+        if a.shadow_true:  # the drawn sun lights the terrain: its true direction, a sky step of 1000 m as for the disc below
+            az, el = a.sun
+            table = generators.sky_table_spec(step=1000.0)
+            mask = generators.shadow_lights(ctx, generators.lights_from_angles(cfg.params, [(az, el)], ctx.lib), a.shadow_reach, status=True,
+                                            width=a.width, height=a.height, mask=False, true_table=table)
+            mask.status = mask.status[0]
+            print(f"refraction table: {generators.sky_table_work(ctx)}")
+        elif a.shadow_per_point:  # slopes and shadows share one light: the coloring's light_dir vector
             light = list(generators.into_coloring(ctx.lib, cfg.params, cfg.coloring).light_dir)
             mask = generators.shadow_lights(ctx, [light], a.shadow_reach, status=True, width=a.width, height=a.height, mask=False)
             mask.status = mask.status[0]

@@ -1006,6 +1006,86 @@ int atmrt_sky_bodies_planes_device(atmrt_ctx* ctx, const atmrt_sky_body_t* bodie
  * library's stream: out = {compaction (clear and upload included), march, download (statistics and host planes)}. */
 int atmrt_last_sky_timings(atmrt_ctx* ctx, double out[3]);
 
+/* ---- apparent elevation: the inverse of the sky march, and shadow lights given by their TRUE direction (no reference counterpart)
+ * "Sky rays" turn a LAUNCH elevation into the TRUE elevation of the ray outside the atmosphere.  This section is the inverse: for a
+ * point at altitude h and a body (a light) at local true elevation t, the launch elevation whose ray leaves the atmosphere at t —
+ * where the body APPEARS.  It is read from a refraction table over (altitude x launch elevation) that the context builds once per
+ * setting and keeps on the device.  With it the shadow lights can be given by their true (astronomical) direction, as the bodies of
+ * "sky rays" are: atmrt_shadow_lights* launch a shadow ray at the light's geometric local elevation, and that ray leaves the
+ * atmosphere up to 0.55 degrees BELOW the light; atmrt_shadow_lights_true* launch it at the apparent elevation.
+ *
+ * THE RULE (tests/sky_apparent_model.py restates it in Python floats, every operation rounded on its own, no fma).
+ *   Table spec: {sky: a spec of "sky rays" (step 0 = the context's simulation_step); alt_lo < alt_hi [m]; -90 < el_lo < el_hi < 90
+ *     [deg]; 2 <= n_alt <= 1024; 2 <= n_el <= 65536; n_alt * n_el <= 2^24}, all numbers finite.
+ *   Lattice: dh = (alt_hi - alt_lo) / (n_alt - 1), h_j = alt_lo + j * dh; de = (el_hi - el_lo) / (n_el - 1), e_k = el_lo + k * de.
+ *   S[j][k] and T[j][k]: status and true elevation of the "sky rays" rule for the ray (h0 = h_j, elevation_deg = e_k) in the
+ *     context's setting; T is NaN unless S is EXIT.
+ *   tail[j]: the smallest k0 such that every entry k0 .. n_el - 1 of row j is EXIT and T[j][k] < T[j][k + 1] for every
+ *     k0 <= k <= n_el - 2; n_el when the row's last entry is not EXIT.  A row is USABLE iff tail[j] <= n_el - 2.
+ *   The inverse uses the monotone tail only.  LIMITATION: under a duct the tail starts above the trapped (GROUND, INSIDE or
+ *     non-monotone) rays; a light below T[j][tail[j]] is treated by the first arm below, as if the refraction of the lowest tail ray
+ *     held for everything under it.  The non-monotone part of a ducted table is not inverted.
+ *   row(j, t), with k0 = tail[j], L = n_el - 1:
+ *       t is NaN:        NaN;
+ *       t < T[j][k0]:    t + (e_k0 - T[j][k0])  (the refraction of the lowest tail ray held constant; the shadow march then decides,
+ *                        as it does for a light under the horizon);
+ *       t > T[j][L]:     t + (e_L - T[j][L]);
+ *       otherwise:       k = the smallest index in (k0, L] with T[j][k] >= t (found by bisection: the tail is strictly increasing),
+ *                        w = (t - T[j][k-1]) / (T[j][k] - T[j][k-1]) (IEEE division), row = e_{k-1} + w * (e_k - e_{k-1}).
+ *   apparent(h, t): u = (h - alt_lo) / dh; a NaN u gives NaN; u clamped to [0, n_alt - 1]; j = min((int)floor(u), n_alt - 2);
+ *     f = u - j; a = row(j, t), b = row(j + 1, t); apparent = a + f * (b - a).
+ *   With straight_rays the apparent elevation is t itself, the same bits, and no table is consulted (atmrt_sky_apparent and the
+ *     shadow calls; the table is still built, and every T[j][k] of it is e_k).
+ *   Closure: over US-76 on the 6371 km sphere (sky step 1000 m, top 100 km), de = 0.02 deg and rows 281.25 m apart, the inverted
+ *     elevation marched by the exact route leaves the atmosphere within 1.1e-4 deg of the target (has the
+ *     measured figures); on a flat earth next to the lowest exiting ray the error reaches 1.1e-2 deg: no bound is given there.
+ *   TRUE-DIRECTION SHADOW LIGHTS: the rule of "shadow lights" verbatim with one insertion after the local direction: when
+ *     elevation_deg is strictly inside (-90, 90), elevation_deg := apparent(H_0, elevation_deg) with H_0 = elev_p + lift, the value
+ *     the march starts from.  The three no-march tests then look at the new value; the lattice, the DirectionalCalc, the stepper at
+ *     the context's simulation_step, the block rule and the escape shortcut are unchanged.  Outputs and stats are those of
+ *     atmrt_shadow_lights.  A table with a row that is not usable is refused.
+ * Equal calls return equal bytes. */
+typedef struct atmrt_sky_table_spec {
+  atmrt_sky_spec_t sky;
+  double alt_lo, alt_hi; /* [m], finite, alt_lo < alt_hi */
+  double el_lo, el_hi;   /* [deg], -90 < el_lo < el_hi < 90 */
+  uint32_t n_alt;        /* 2 .. 1024 */
+  uint32_t n_el;         /* 2 .. 65536; n_alt * n_el <= 2^24 */
+} atmrt_sky_table_spec_t;
+/* Builds the table of the context's setting NOW, or finds it: the table, its status plane and tail stay on the device under the key
+ * of everything the rule reads (atmosphere, wavelength, earth shape and radius, straight_rays, the spec with its step resolved); a
+ * later call with an equal key finds them, a changed key rebuilds them.  true_elevation [n_alt][n_el], status [n_alt][n_el],
+ * tail [n_alt]: host arrays, each may be NULL; stats (of the march that built the table; none = 0) may be NULL.  It succeeds with
+ * unusable rows, so that they can be looked at.  ATMRT_ERR_INVALID_ARGUMENT: NULL, a spec the rule refuses.  ATMRT_ERR_STATE: before
+ * atmrt_set_params. */
+int atmrt_sky_table(atmrt_ctx* ctx, const atmrt_sky_table_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* tail,
+                    atmrt_sky_stats_t* stats);
+/* Host code, no context and no device: tail[n_alt] of the caller's planes, by the function the kernel's rule states.
+ * ATMRT_ERR_INVALID_ARGUMENT: NULL, a spec the rule refuses. */
+int atmrt_sky_tail_host(const atmrt_sky_table_spec_t* spec, const double* true_elevation, const uint8_t* status, uint32_t* tail);
+/* Host code, no context and no device: apparent(h, t) over the caller's table, by the function the kernels run.
+ * ATMRT_ERR_INVALID_ARGUMENT: NULL, a spec the rule refuses, a tail entry that says its row is not usable (or lies above n_el). */
+int atmrt_sky_apparent_host(const atmrt_sky_table_spec_t* spec, const double* true_elevation, const uint32_t* tail, double h, double t,
+                            double* apparent);
+/* The list call, on the device: where a body of true elevation t[i] appears from altitude h[i] (host arrays, any n); the table is
+ * built or found as by atmrt_sky_table.  ATMRT_ERR_INVALID_ARGUMENT: NULL (n > 0), a spec the rule refuses, a table with an unusable
+ * row (atmrt_last_error names the first).  ATMRT_ERR_STATE: before atmrt_set_params. */
+int atmrt_sky_apparent(atmrt_ctx* ctx, const atmrt_sky_table_spec_t* spec, size_t n, const double* h, const double* t, double* apparent);
+/* The three routes of atmrt_shadow_lights* under the true-direction rule: the same arguments and one more, the table's spec.
+ * Refusals: those of atmrt_shadow_lights* and of atmrt_sky_apparent.  atmrt_last_shadow_timings reports them (the table's build is
+ * not part of those: atmrt_last_sky_table_work has it). */
+int atmrt_shadow_lights_true_device(atmrt_ctx* ctx, const atmrt_shadow_lights_spec_t* spec, const atmrt_sky_table_spec_t* table,
+                                    uint64_t* lit_mask_device, uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats);
+int atmrt_shadow_lights_true(atmrt_ctx* ctx, const atmrt_shadow_lights_spec_t* spec, const atmrt_sky_table_spec_t* table, uint64_t* lit_mask,
+                             uint8_t* status, uint16_t* block, atmrt_shadow_stats_t* stats);
+int atmrt_shadow_lights_true_planes_device(atmrt_ctx* ctx, const atmrt_shadow_lights_spec_t* spec, const atmrt_sky_table_spec_t* table,
+                                           size_t n_pixels, const uint32_t* hit_count, const double* lat, const double* lon, const double* elev,
+                                           uint64_t* lit_mask_device, uint8_t* status_device, uint16_t* block_device, atmrt_shadow_stats_t* stats);
+/* What the last call on ctx that needed the table did for it: *rebuilt = 1 when it built the table, 0 when it found it;
+ * ms = {march, tail, download (the host arrays of atmrt_sky_table and the tail the library reads)} in milliseconds between events
+ * on the library's stream; march and tail are 0 when the table was found. */
+int atmrt_last_sky_table_work(atmrt_ctx* ctx, int32_t* rebuilt, double ms[3]);
+
 /* ---- several GPUs of one node --------------------------------------------------------------------------------
  * The reference calls `generator.generate()` ONCE per frame (src/generator/mod.rs:72-86, trait at generators/mod.rs:82-84), so the
  * multi-GPU path lives BELOW this ABI: pixels are independent (rectilinear.rs:32-37), the image is cut into pixel-column tiles —
