@@ -14,6 +14,7 @@
                                     [--shadow-true [--sky-table-alt LO HI N] [--sky-table-el LO HI N]]
                                     [--sun AZ EL [--sun-radius DEG]] [--moon AZ EL] [--sky-top M] [--sky-step M] [--sky-floor M]
                                     [--sky-out OUT.npz] [--refraction-table OUT.csv [--sky-fan LO HI K]]
+                                    [--sky-colour [--sky-tau R G B] [--sky-exposure G] [--sun-limb R G B] [--air-mass-ref M]]
     python -m atm_raytracer_amd output-atm CONFIG.yaml [-a MIN] [-b MAX] [-s STEP] [-c]
     python -m atm_raytracer_amd output-ray-paths CONFIG.yaml [-h H] [-a MIN] [-b MAX] [-s DEG] [-r STEP] [-c CUTOFF] [-o OUTSTEP]
     python -m atm_raytracer_amd output-elev-profile CONFIG.yaml [-a AZIM] [-s STEP] [-c CUTOFF]
@@ -85,6 +86,12 @@ through the atmosphere to --sky-top metres (100000) in steps of --sky-step metre
 device image before the overlay: ticks and lines stay on top.  `--sky-out OUT.npz` holds true_elevation, status (0 none, 1 exit,
 2 ground, 3 inside, 4 lost), steps and body as [height][width] arrays and the call's stats_none, stats_exit, stats_ground,
 stats_inside, stats_lost, stats_integrated_steps.
+`--sky-colour` (no reference counterpart; with or without --sun / --moon) shades the sky by air mass (include/atmrt.h, "sky light"):
+the sky march also integrates the refractivity along every ray, and its quotient by the same integral taken vertically from
+--air-mass-ref metres (0) is the pixel's relative air mass X.  A sky pixel becomes white * --sky-exposure (4) * (1 - exp(-tau X)) per
+channel with the zenith optical depths --sky-tau R G B (0.06 0.11 0.24: a blue zenith, a horizon that saturates to white); a disc pixel
+its body's colour times exp(-tau X) — the low sun reddens and dims — times the limb darkening 1 - u (1 - mu) with --sun-limb R G B (0.5
+0.6 0.75).  These numbers are this project's choice.  --sky-out then also holds column, air_mass and zenith_column.
 `--refraction-table OUT.csv` marches K rays from the observer's altitude at launch elevations from LO to
 HI degrees (--sky-fan, 0 60 61) with the same --sky-top, --sky-step and --sky-floor: rows of
 elevation_deg,status,steps,true_elevation_deg,refraction_deg (the last two empty unless the ray exits).
@@ -414,17 +421,33 @@ def draw_sky(ctx, a, rgb_dev, w, h):
     status_dev = torch.empty((h, w), dtype=torch.uint8, device=dev)
     steps_dev = torch.empty((h, w), dtype=torch.int32, device=dev)
     body_dev = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    column_dev = torch.empty((h, w), dtype=torch.float64, device=dev) if a.sky_colour else None
     torch.cuda.synchronize(dev)
     spec, st = sky_spec_of(a), _abi.SkyStats()
-    ctx.check(ctx.lib.atmrt_sky_directions_device(ctx.handle, C.byref(spec), true_dev.data_ptr(), status_dev.data_ptr(), steps_dev.data_ptr(), C.byref(st)))
     arr, n = generators._sky_bodies_array(sky_bodies_of(a))
-    ctx.check(ctx.lib.atmrt_sky_bodies_device(ctx.handle, arr, n, true_dev.data_ptr(), status_dev.data_ptr(), body_dev.data_ptr(), rgb_dev.data_ptr()))
+    if a.sky_colour:  # "sky light": the march with the column, then the shade instead of the flat discs
+        light, z0 = generators.sky_light_spec(a.air_mass_ref, sky=spec), C.c_double()
+        ctx.check(ctx.lib.atmrt_sky_light_device(ctx.handle, C.byref(light), true_dev.data_ptr(), status_dev.data_ptr(), steps_dev.data_ptr(),
+                                                 column_dev.data_ptr(), C.byref(st), C.byref(z0)))
+        shade = generators.sky_shade_params(z0.value, a.sky_tau, a.sun_limb, a.sky_exposure)
+        ctx.check(ctx.lib.atmrt_sky_shade_device(ctx.handle, C.byref(shade), arr, n, true_dev.data_ptr(), status_dev.data_ptr(), column_dev.data_ptr(),
+                                                 body_dev.data_ptr(), rgb_dev.data_ptr()))
+    else:
+        ctx.check(ctx.lib.atmrt_sky_directions_device(ctx.handle, C.byref(spec), true_dev.data_ptr(), status_dev.data_ptr(), steps_dev.data_ptr(), C.byref(st)))
+        ctx.check(ctx.lib.atmrt_sky_bodies_device(ctx.handle, arr, n, true_dev.data_ptr(), status_dev.data_ptr(), body_dev.data_ptr(), rgb_dev.data_ptr()))
     stats = generators._sky_stats(st)
     print(f"Sky: {stats['exit']} pixels leave the atmosphere, {stats['ground']} reach the floor, {stats['inside']} stay inside, {stats['lost']} lost; "
           f"{int((body_dev != 0).sum())} pixels of {n} bodies")
+    if a.sky_colour:
+        x = (column_dev / z0.value)[status_dev == _abi.SKY_EXIT]
+        span = f"{float(x.min()):.3f} .. {float(x.max()):.3f}" if x.numel() else "of no pixel"
+        print(f"Sky colour: zenith column {z0.value!r} m from {a.air_mass_ref!r} m, air mass {span}")
     if a.sky_out:
         data = dict(true_elevation=true_dev.cpu().numpy(), status=status_dev.cpu().numpy(), steps=steps_dev.cpu().numpy().view(np.uint32),
                     body=body_dev.cpu().numpy())
+        if a.sky_colour:
+            column = column_dev.cpu().numpy()
+            data.update(column=column, air_mass=column / z0.value, zenith_column=np.float64(z0.value))
         data.update({"stats_" + k: np.uint64(v) for k, v in stats.items()})
         np.savez_compressed(a.sky_out, **data)
 
@@ -490,7 +513,7 @@ def cmd_gen(a):
         ctx.check(ctx.lib.atmrt_draw_image_shadowed_device(ctx.handle, C.byref(col), status_dev.data_ptr(), rgb_dev.data_ptr()))
     else:
         ctx.check(ctx.lib.atmrt_draw_image_device(ctx.handle, C.byref(col), rgb_dev.data_ptr()))
-    if a.sun or a.moon or a.sky_out:  # on the device image, before the overlay: ticks and lines stay on top
+    if a.sun or a.moon or a.sky_out or a.sky_colour:  # on the device image, before the overlay: ticks and lines stay on top
         stamp("Marching the sky...")
         draw_sky(ctx, a, rgb_dev, w, h)
     ticks, _ = generators.draw_overlay_device(ctx, generators.into_overlay(cfg.output), rgb_dev.data_ptr(), w, h)
@@ -635,6 +658,11 @@ def main(argv=None):
     g.add_argument("--sky-step", type=float, default=None, metavar="M")
     g.add_argument("--sky-floor", type=float, default=0.0, metavar="M")
     g.add_argument("--sky-out", default=None, metavar="OUT.npz")
+    g.add_argument("--sky-colour", action="store_true")
+    g.add_argument("--sky-tau", type=float, nargs=3, default=generators.SKY_TAU, metavar=("R", "G", "B"))
+    g.add_argument("--sky-exposure", type=float, default=generators.SKY_EXPOSURE, metavar="G")
+    g.add_argument("--sun-limb", type=float, nargs=3, default=generators.SUN_LIMB, metavar=("R", "G", "B"))
+    g.add_argument("--air-mass-ref", type=float, default=0.0, metavar="M")
     g.add_argument("--refraction-table", default=None, metavar="OUT.csv")
     g.add_argument("--sky-fan", type=float, nargs=3, default=(0.0, 60.0, 61), metavar=("LO", "HI", "K"))
     g.add_argument("--horizon", default=None, metavar="OUT.csv")

@@ -260,6 +260,20 @@ class SkyBody(C.Structure):
                 ("_pad", C.c_uint8 * 5)]
 
 
+class SkyLightSpec(C.Structure):
+    """atmrt_sky_light_spec_t: the sky spec of the march, the altitude whose zenith is air mass 1 [m], the node spacing of the zenith
+    column [m] (0: the step of the march)."""
+    _fields_ = [("sky", SkySpec), ("ref_alt", C.c_double), ("column_dz", C.c_double)]
+
+
+class SkyShade(C.Structure):
+    """atmrt_sky_shade_t: the zenith column [m], the zenith optical depth and the limb-darkening coefficient per channel, the
+    exposure and the colour of the airlight."""
+    _fields_ = [("zenith_column", C.c_double), ("tau", C.c_double * 3), ("limb", C.c_double * 3), ("exposure", C.c_double),
+                ("airlight", C.c_uint8 * 3), ("_pad", C.c_uint8 * 5)]
+
+
+SKY_COLUMN_NODES_MAX = 1048575
 SKY_TABLE_ALT_MAX, SKY_TABLE_EL_MAX, SKY_TABLE_ENTRIES_MAX = 1024, 65536, 1 << 24
 
 

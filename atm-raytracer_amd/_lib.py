@@ -158,6 +158,18 @@ def load():
         "atmrt_sky_bodies": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, vp, vp, vp, vp]),
         "atmrt_sky_bodies_planes_device": (C.c_int, [vp, C.POINTER(_abi.SkyBody), C.c_uint32, sz, vp, vp, vp, vp, vp]),
         "atmrt_last_sky_timings": (C.c_int, [vp, pd]),
+        "atmrt_sky_zenith_column_host": (C.c_int, [C.POINTER(_abi.Atmosphere), dbl, dbl, dbl, dbl, pd]),
+        "atmrt_sky_light_ray_host": (C.c_int, [C.POINTER(_abi.Atmosphere), dbl, C.POINTER(_abi.EarthModel), i32, C.POINTER(_abi.SkySpec), dbl, dbl,
+                                               C.POINTER(_abi.SkyRay), pd]),
+        "atmrt_sky_shade_host": (C.c_int, [C.POINTER(_abi.SkyShade), C.POINTER(_abi.SkyBody), C.c_uint32, dbl, dbl, dbl, C.POINTER(C.c_uint32), vp]),
+        "atmrt_sky_light_rays": (C.c_int, [vp, C.POINTER(_abi.SkySpec), dbl, sz, vp, vp, vp, C.POINTER(_abi.SkyStats)]),
+        "atmrt_sky_light_device": (C.c_int, [vp, C.POINTER(_abi.SkyLightSpec), vp, vp, vp, vp, C.POINTER(_abi.SkyStats), pd]),
+        "atmrt_sky_light": (C.c_int, [vp, C.POINTER(_abi.SkyLightSpec), vp, vp, vp, vp, C.POINTER(_abi.SkyStats), pd]),
+        "atmrt_sky_light_planes_device": (C.c_int, [vp, C.POINTER(_abi.SkyLightSpec), dbl, sz, vp, vp, vp, vp, vp, vp, C.POINTER(_abi.SkyStats), pd]),
+        "atmrt_sky_shade_device": (C.c_int, [vp, C.POINTER(_abi.SkyShade), C.POINTER(_abi.SkyBody), C.c_uint32, vp, vp, vp, vp, vp]),
+        "atmrt_sky_shade": (C.c_int, [vp, C.POINTER(_abi.SkyShade), C.POINTER(_abi.SkyBody), C.c_uint32, vp, vp, vp, vp, vp]),
+        "atmrt_sky_shade_planes_device": (C.c_int, [vp, C.POINTER(_abi.SkyShade), C.POINTER(_abi.SkyBody), C.c_uint32, sz, vp, vp, vp, vp, vp, vp]),
+        "atmrt_last_sky_shade_timing": (C.c_int, [vp, pd]),
         "atmrt_sky_table": (C.c_int, [vp, C.POINTER(_abi.SkyTableSpec), vp, vp, vp, C.POINTER(_abi.SkyStats)]),
         "atmrt_sky_tail_host": (C.c_int, [C.POINTER(_abi.SkyTableSpec), vp, vp, vp]),
         "atmrt_sky_apparent_host": (C.c_int, [C.POINTER(_abi.SkyTableSpec), vp, vp, dbl, dbl, pd]),
@@ -227,7 +239,9 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_shadow_lights_device", "atmrt_shadow_lights", "atmrt_shadow_lights_planes_device",
             "atmrt_sky_ray_host", "atmrt_sky_body_host", "atmrt_sky_rays", "atmrt_sky_directions_device", "atmrt_sky_directions",
             "atmrt_sky_directions_planes_device", "atmrt_sky_bodies_device", "atmrt_sky_bodies", "atmrt_sky_bodies_planes_device",
-            "atmrt_last_sky_timings", "atmrt_sky_table", "atmrt_sky_tail_host", "atmrt_sky_apparent_host", "atmrt_sky_apparent",
+            "atmrt_last_sky_timings", "atmrt_sky_zenith_column_host", "atmrt_sky_light_ray_host", "atmrt_sky_shade_host", "atmrt_sky_light_rays",
+            "atmrt_sky_light_device", "atmrt_sky_light", "atmrt_sky_light_planes_device", "atmrt_sky_shade_device", "atmrt_sky_shade",
+            "atmrt_sky_shade_planes_device", "atmrt_last_sky_shade_timing", "atmrt_sky_table", "atmrt_sky_tail_host", "atmrt_sky_apparent_host", "atmrt_sky_apparent",
             "atmrt_shadow_lights_true_device", "atmrt_shadow_lights_true", "atmrt_shadow_lights_true_planes_device", "atmrt_last_sky_table_work",
             "atmrt_ray_paths", "atmrt_atmosphere_sample",
             "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_debug_last_march_route", "atmrt_debug_interp_blend", "atmrt_result_encode_bincode",

@@ -168,6 +168,9 @@ extern "C" size_t atmrt_abi_sizeof(int which) {
     case 45: return sizeof(atmrt_sky_body_t);
     // 46 stays 0
     case 47: return sizeof(atmrt_sky_table_spec_t);
+    // 48 stays 0
+    case 49: return sizeof(atmrt_sky_light_spec_t);
+    case 50: return sizeof(atmrt_sky_shade_t);
     default: return 0;
   }
 }

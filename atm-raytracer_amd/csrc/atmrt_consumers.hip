@@ -1027,11 +1027,14 @@ struct SkyDownload { // a plane the host asked for (host null: not this one), do
 
 // One sky march around its kernels, for a SkyJob with its source, its h0 and its planes filled in.  k: the context whose device
 // holds the memory and whose setting is used; report: the context the caller handed in.  upload: the list call's elevations, inside
-// the timed window.
+// the timed window.  column: the column plane of a "sky light" call (null: plain sky rays); prepared: the frame of a caller that
+// has called prepare_frame(k) already.
 int sky_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_sky_spec_t& spec, double step, SkyJob& job, const std::function<int(hipStream_t)>& upload,
-            std::initializer_list<SkyDownload> downloads, atmrt_sky_stats_t* stats) {
+            std::initializer_list<SkyDownload> downloads, atmrt_sky_stats_t* stats, double* column = nullptr, const Frame* prepared = nullptr) {
   Frame f;
-  if (int rc = prepare_frame(k, &f)) {
+  if (prepared) {
+    f = *prepared;
+  } else if (int rc = prepare_frame(k, &f)) {
     if (k != report) report->error = k->error;
     return rc;
   }
@@ -1044,7 +1047,8 @@ int sky_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_sky_spec_t& spec, doubl
           }));
   HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], s));
   if (int rc = upload(s)) return rc;
-  launch_sky_march(f, job, s, k->ev[EV_SKY_COMPACTED]);
+  if (column) launch_sky_light_march(f, SkyLightJob{job, column}, s, k->ev[EV_SKY_COMPACTED]); // "sky light": the march with the column
+  else launch_sky_march(f, job, s, k->ev[EV_SKY_COMPACTED]);
   HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_MARCHED], s));
   unsigned long long ctr[SKY_N] = {};
   HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
@@ -1248,6 +1252,255 @@ extern "C" int atmrt_sky_bodies_planes_device(atmrt_ctx* c, const atmrt_sky_body
 extern "C" int atmrt_last_sky_timings(atmrt_ctx* c, double out[3]) {
   if (!c || !out) return ATMRT_ERR_INVALID_ARGUMENT;
   memcpy(out, c->sky_timings, sizeof c->sky_timings);
+  return ATMRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sky light: the column per sky ray, the zenith column, the shade (kernels: atmrt_sky.h; the rule: include/atmrt.h)
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+const char* const SKY_LIGHT_ON_MULTI = "has no frame of its own: sky light works on the gathered planes through atmrt_sky_light_planes_device and atmrt_sky_shade_planes_device";
+
+// what the light calls on a context ask beyond sky_check; *step: the step of the march
+int sky_light_check(atmrt_ctx* c, const char* what, const atmrt_sky_light_spec_t* spec, double h0, double* step) {
+  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
+  if (int rc = sky_check(c, what, &spec->sky, h0, step)) return rc;
+  if (!std::isfinite(spec->ref_alt) || !(spec->ref_alt < spec->sky.top)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: ref_alt must be finite and lie below top", what);
+  if (!(std::isfinite(spec->column_dz) && spec->column_dz >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: column_dz must be finite and not negative", what);
+  return ATMRT_OK;
+}
+
+// the frame of k's setting and Z0 of its atmosphere
+int sky_light_prepare(atmrt_ctx* k, atmrt_ctx* report, const char* what, const atmrt_sky_light_spec_t& spec, double step, Frame* f, double* z0) {
+  if (int rc = prepare_frame(k, f)) {
+    if (k != report) report->error = k->error;
+    return rc;
+  }
+  const double dz = spec.column_dz == 0.0 ? step : spec.column_dz;
+  if (!sky_zenith_column<true>(k->atm.value().table.table(), spec.ref_alt, spec.sky.top, dz, z0))
+    return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the zenith column from %g m to %g m has more than 1048575 nodes of %g m", what, spec.ref_alt, spec.sky.top, dz);
+  return ATMRT_OK;
+}
+
+// the shade and the bodies of a call, checked and made into what the kernel holds
+int sky_shade_check(atmrt_ctx* c, const char* what, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, SkyShadeJob& job) {
+  if (!shade) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: shade is NULL", what);
+  if (!sky_shade_valid(*shade))
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the shade needs a finite positive zenith_column, finite tau and exposure that are not negative, and limb in [0, 1]", what);
+  if (n_bodies > SKY_BODIES_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: at most 32 bodies, not %u", what, n_bodies);
+  if (n_bodies && !bodies) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: bodies is NULL", what);
+  job.n_bodies = n_bodies;
+  for (uint32_t k = 0; k < n_bodies; k++) {
+    if (!sky_body_valid(bodies[k]))
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: body %u needs finite angles and a radius strictly between 0 and 90 degrees", what, k);
+    job.bodies[k] = sky_body_dev(bodies[k]);
+  }
+  job.shade = sky_shade_dev(*shade, bodies, n_bodies);
+  return ATMRT_OK;
+}
+
+int sky_shade_run(atmrt_ctx* k, atmrt_ctx* report, const SkyShadeJob& job) {
+  HIP_TRY(report, hipSetDevice(k->device));
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], k->stream));
+  launch_sky_shade(job, k->stream);
+  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_COMPACTED], k->stream));
+  HIP_TRY(report, hipStreamSynchronize(k->stream));
+  HIP_TRY(report, hipGetLastError());
+  HIP_TRY(report, event_intervals(k->ev + EV_SKY_BEGIN, 1, &report->sky_shade_ms));
+  return ATMRT_OK;
+}
+
+} // namespace
+
+extern "C" int atmrt_sky_zenith_column_host(const atmrt_atmosphere_t* atmosphere, double wavelength, double ref_alt, double top, double dz,
+                                            double* zenith_column) {
+  if (!atmosphere || !zenith_column) return ATMRT_ERR_INVALID_ARGUMENT;
+  AtmTableBuf buf;
+  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
+  return sky_zenith_column<true>(buf.table(), ref_alt, top, dz, zenith_column) ? ATMRT_OK : ATMRT_ERR_INVALID_ARGUMENT;
+}
+
+extern "C" int atmrt_sky_light_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays,
+                                        const atmrt_sky_spec_t* spec, double h0, double elevation_deg, atmrt_sky_ray_t* out, double* column) {
+  if (!atmosphere || !earth || !spec || !out || !column) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (sky_spec_check(*spec, h0) || !(spec->step > 0.0)) return ATMRT_ERR_INVALID_ARGUMENT;
+  Earth e;
+  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
+  AtmTableBuf buf;
+  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
+  *out = sky_light_march_one<true>(buf.table(), e.spherical != 0, e.shape_radius, straight_rays != 0, spec->step, spec->top, spec->floor, spec->m, h0,
+                                   elevation_deg, column);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_shade_host(const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, double azimuth_deg,
+                                    double true_elevation_deg, double column, uint32_t* body, uint8_t* rgb) {
+  if (!shade || !body || !rgb || (n_bodies && !bodies) || n_bodies > SKY_BODIES_MAX || !sky_shade_valid(*shade)) return ATMRT_ERR_INVALID_ARGUMENT;
+  SkyBodyDev dev[SKY_BODIES_MAX];
+  for (uint32_t k = 0; k < n_bodies; k++) {
+    if (!sky_body_valid(bodies[k])) return ATMRT_ERR_INVALID_ARGUMENT;
+    dev[k] = sky_body_dev(bodies[k]);
+  }
+  const SkyShadeDev sh = sky_shade_dev(*shade, bodies, n_bodies);
+  *body = sky_shade_pixel(sh, dev, n_bodies, azimuth_deg, true_elevation_deg, column, rgb);
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_light_rays(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double h0, size_t n, const double* elevation_deg, atmrt_sky_ray_t* records,
+                                    double* column, atmrt_sky_stats_t* stats) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (n && (!elevation_deg || !records || !column)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_rays: elevation_deg, records or column is NULL");
+  if (n > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_rays: n must lie in [0, 2^32 - 1]");
+  double step = 0.0;
+  if (int rc = sky_check(c, "atmrt_sky_light_rays", spec, h0, &step)) return rc;
+  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
+  HIP_TRY(c, hipSetDevice(k->device));
+  SkyJob job{};
+  job.n_pixels = n, job.h0 = h0;
+  double *d_elev = nullptr, *d_true = nullptr, *d_column = nullptr;
+  uint8_t* d_status = nullptr;
+  uint32_t* d_steps = nullptr;
+  HIP_TRY(c, reserve_carved(k->d_io, [&](Carve& cv) { cv(d_elev, n * 8), cv(d_true, n * 8), cv(d_column, n * 8), cv(d_steps, n * 4), cv(d_status, n); }));
+  job.elevation_angle = d_elev, job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
+  std::vector<double> true_elevation(n);
+  std::vector<uint8_t> status(n);
+  std::vector<uint32_t> steps(n);
+  int rc = sky_run(k, c, *spec, step, job,
+                   [&](hipStream_t s) -> int {
+                     if (n) HIP_TRY(c, hipMemcpyAsync(d_elev, elevation_deg, n * 8, hipMemcpyHostToDevice, s));
+                     return ATMRT_OK;
+                   },
+                   {{true_elevation.data(), d_true, n * 8}, {status.data(), d_status, n}, {steps.data(), d_steps, n * 4}, {column, d_column, n * 8}}, stats,
+                   d_column);
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) records[i] = atmrt_sky_ray_t{(int32_t)status[i], steps[i], true_elevation[i]};
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_light_device(atmrt_ctx* c, const atmrt_sky_light_spec_t* spec, double* true_elevation_device, uint8_t* status_device,
+                                      uint32_t* steps_device, double* column_device, atmrt_sky_stats_t* stats, double* zenith_column) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation_device || !status_device || !column_device) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light: true_elevation, status or column is NULL");
+  double step = 0.0, z0 = 0.0;
+  if (int rc = sky_light_check(c, "atmrt_sky_light", spec, 0.0, &step)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_light", SKY_LIGHT_ON_MULTI)) return rc;
+  Frame f;
+  if (int rc = sky_light_prepare(c, c, "atmrt_sky_light", *spec, step, &f, &z0)) return rc;
+  SkyJob job{};
+  job.n_pixels = c->last.npx, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
+  job.alt = c->d_alt.as<double>();
+  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
+  if (int rc = sky_run(c, c, spec->sky, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats, column_device, &f)) return rc;
+  if (zenith_column) *zenith_column = z0;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_light(atmrt_ctx* c, const atmrt_sky_light_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps, double* column,
+                               atmrt_sky_stats_t* stats, double* zenith_column) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation || !status || !column) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light: true_elevation, status or column is NULL");
+  double step = 0.0, z0 = 0.0;
+  if (int rc = sky_light_check(c, "atmrt_sky_light", spec, 0.0, &step)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_light", SKY_LIGHT_ON_MULTI)) return rc;
+  Frame f;
+  if (int rc = sky_light_prepare(c, c, "atmrt_sky_light", *spec, step, &f, &z0)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n = c->last.npx;
+  double *d_true = nullptr, *d_column = nullptr;
+  uint32_t* d_steps = nullptr; // what is not asked for takes no room
+  uint8_t* d_status = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8), k(d_column, n * 8); if (steps) k(d_steps, n * 4); k(d_status, n); }));
+  SkyJob job{};
+  job.n_pixels = n, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
+  job.alt = c->d_alt.as<double>();
+  job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
+  if (int rc = sky_run(c, c, spec->sky, step, job, [](hipStream_t) -> int { return ATMRT_OK; },
+                       {{true_elevation, d_true, n * 8}, {status, d_status, n}, {steps, d_steps, n * 4}, {column, d_column, n * 8}}, stats, d_column, &f))
+    return rc;
+  if (zenith_column) *zenith_column = z0;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_light_planes_device(atmrt_ctx* c, const atmrt_sky_light_spec_t* spec, double h0, size_t n_pixels, const uint32_t* hit_count,
+                                             const double* elevation_angle, double* true_elevation_device, uint8_t* status_device,
+                                             uint32_t* steps_device, double* column_device, atmrt_sky_stats_t* stats, double* zenith_column) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!hit_count || !elevation_angle || !true_elevation_device || !status_device || !column_device)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_planes_device: a plane is NULL");
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  double step = 0.0, z0 = 0.0;
+  if (int rc = sky_light_check(c, "atmrt_sky_light_planes_device", spec, h0, &step)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, status_device, "status_device", &k)) return rc;
+  HIP_TRY(c, hipSetDevice(k->device));
+  Frame f;
+  if (int rc = sky_light_prepare(k, c, "atmrt_sky_light_planes_device", *spec, step, &f, &z0)) return rc;
+  SkyJob job{};
+  job.n_pixels = n_pixels, job.hit_count = hit_count, job.elevation_angle = elevation_angle, job.h0 = h0;
+  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
+  if (int rc = sky_run(k, c, spec->sky, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats, column_device, &f)) return rc;
+  if (zenith_column) *zenith_column = z0;
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_shade_device(atmrt_ctx* c, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies,
+                                      const double* true_elevation_device, const uint8_t* status_device, const double* column_device,
+                                      uint8_t* body_device, uint8_t* rgb_device) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation_device || !status_device || !column_device || !body_device || !rgb_device)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade: a plane is NULL");
+  SkyShadeJob job{};
+  if (int rc = sky_shade_check(c, "atmrt_sky_shade", shade, bodies, n_bodies, job)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_shade", SKY_LIGHT_ON_MULTI)) return rc;
+  job.n_pixels = c->last.npx, job.azimuth = c->last.dense.azimuth;
+  job.true_elevation = true_elevation_device, job.status = status_device, job.column = column_device, job.body = body_device, job.rgb = rgb_device;
+  return sky_shade_run(c, c, job);
+}
+
+extern "C" int atmrt_sky_shade(atmrt_ctx* c, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation,
+                               const uint8_t* status, const double* column, uint8_t* body, uint8_t* rgb) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!true_elevation || !status || !column || !body || !rgb) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade: a plane is NULL");
+  SkyShadeJob job{};
+  if (int rc = sky_shade_check(c, "atmrt_sky_shade", shade, bodies, n_bodies, job)) return rc;
+  if (int rc = frame_state_check(c, "atmrt_sky_shade", SKY_LIGHT_ON_MULTI)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  const size_t n = c->last.npx;
+  double *d_true = nullptr, *d_column = nullptr;
+  uint8_t *d_status = nullptr, *d_body = nullptr, *d_rgb = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8), k(d_column, n * 8), k(d_status, n), k(d_body, n), k(d_rgb, 3 * n); }));
+  HIP_TRY(c, hipMemcpy(d_true, true_elevation, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_column, column, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_status, status, n, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_rgb, rgb, 3 * n, hipMemcpyHostToDevice));
+  job.n_pixels = n, job.azimuth = c->last.dense.azimuth;
+  job.true_elevation = d_true, job.status = d_status, job.column = d_column, job.body = d_body, job.rgb = d_rgb;
+  if (int rc = sky_shade_run(c, c, job)) return rc;
+  HIP_TRY(c, hipMemcpy(body, d_body, n, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
+  return ATMRT_OK;
+}
+
+extern "C" int atmrt_sky_shade_planes_device(atmrt_ctx* c, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies,
+                                             size_t n_pixels, const double* azimuth, const double* true_elevation_device, const uint8_t* status_device,
+                                             const double* column_device, uint8_t* body_device, uint8_t* rgb_device) {
+  if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (!azimuth || !true_elevation_device || !status_device || !column_device || !body_device || !rgb_device)
+    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade_planes_device: a plane is NULL");
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade_planes_device: n_pixels must lie in [1, 2^32 - 1]");
+  SkyShadeJob job{};
+  if (int rc = sky_shade_check(c, "atmrt_sky_shade_planes_device", shade, bodies, n_bodies, job)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, body_device, "body_device", &k)) return rc;
+  job.n_pixels = n_pixels, job.azimuth = azimuth;
+  job.true_elevation = true_elevation_device, job.status = status_device, job.column = column_device, job.body = body_device, job.rgb = rgb_device;
+  return sky_shade_run(k, c, job);
+}
+
+extern "C" int atmrt_last_sky_shade_timing(atmrt_ctx* c, double* ms) {
+  if (!c || !ms) return ATMRT_ERR_INVALID_ARGUMENT;
+  *ms = c->sky_shade_ms;
   return ATMRT_OK;
 }
 

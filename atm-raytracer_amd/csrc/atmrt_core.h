@@ -1531,6 +1531,139 @@ ATMRT_HD uint32_t sky_body_of(const SkyBodyDev* bodies, uint32_t n_bodies, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
+// sky light (include/atmrt.h, "sky light"): the refractivity column along a sky ray, the zenith column and the shade of an EXIT
+// pixel, one set for the kernels (k_sky_light_march, k_sky_shade) and the host (atmrt_sky_light_ray_host,
+// atmrt_sky_zenith_column_host, atmrt_sky_shade_host)
+// ---------------------------------------------------------------------------------------------
+constexpr double SKY_COLUMN_NODES_MAX = 1048575.0;
+
+// q(h) = n(h) - 1 by the generic per-layer IEEE evaluation (ray_accel_generic's n; oracle/atmosphere.c oracle_n), whatever the
+// stepper took for its stages
+template <bool CUBIC = true>
+ATMRT_HD double sky_refractivity(const AtmTable& atm, double h) {
+  return refr_n_layer<CUBIC, false>(atm.k_refr, atm.seg(atm_layer(atm, h)), h) - 1.0;
+}
+
+// the column after the step from (h_prev, q_prev) to (h, q): the trapezoid over the step's path length, every operation IEEE
+ATMRT_HD double sky_column_add(bool spherical, double radius, double step, double column, double h_prev, double q_prev, double h, double q) {
+  const double w = spherical ? (step / radius) * (0.5 * (h_prev + h) + radius) : step;
+  const double dh = h - h_prev;
+  return column + 0.5 * (q_prev + q) * dm_sqrt(w * w + dh * dh);
+}
+
+// The rule's per-ray function, serially: sky_march_one with the column carried along (what a lane of k_sky_light_march computes).
+template <bool CUBIC = true>
+ATMRT_HD atmrt_sky_ray_t sky_light_march_one(const AtmTable& atm, bool spherical, double radius, bool straight, double step, double top, double floor,
+                                             int32_t m, double h0, double elevation_deg, double* column) {
+  atmrt_sky_ray_t out;
+  out.status = ATMRT_SKY_LOST, out.steps = 0, out.true_elevation = dm_from_bits(0x7ff8000000000000ULL);
+  *column = dm_from_bits(0x7ff8000000000000ULL);
+  if (!sky_marches(elevation_deg)) return out;
+  Stepper s;
+  stepper_init(s, spherical, radius, h0, dm_to_radians(elevation_deg));
+  out.status = ATMRT_SKY_INSIDE;
+  double h_prev = h0, q_prev = sky_refractivity<CUBIC>(atm, h0), c = 0.0;
+  for (int32_t i = 1; i <= m; i++) {
+    const RayState st = stepper_next<CUBIC>(s, atm, spherical, radius, straight, step);
+    out.steps = (uint32_t)i;
+    const int decided = sky_step_status(st.h, floor, top);
+    if (decided != ATMRT_SKY_LOST && decided != ATMRT_SKY_GROUND) {
+      const double q = sky_refractivity<CUBIC>(atm, st.h);
+      c = sky_column_add(spherical, radius, step, c, h_prev, q_prev, st.h, q);
+      h_prev = st.h, q_prev = q;
+    }
+    if (decided) {
+      out.status = decided;
+      break;
+    }
+  }
+  if (out.status == ATMRT_SKY_EXIT) {
+    out.true_elevation = sky_true_elevation(s, spherical, radius, straight, elevation_deg);
+    *column = c;
+  }
+  return out;
+}
+
+// Z0(ref_alt, top, dz): the trapezoid of q over the nodes ref_alt + k dz, k < K = ceil((top - ref_alt) / dz), and `top` itself,
+// summed upward over the actual node spacings.  false: the rule refuses the arguments (*z0 untouched).
+template <bool CUBIC = true>
+ATMRT_HD bool sky_zenith_column(const AtmTable& atm, double ref_alt, double top, double dz, double* z0) {
+  if (!(dz > 0.0 && dz < dm_inf()) || !(ref_alt > -dm_inf() && top < dm_inf() && ref_alt < top)) return false;
+  const double kd = -dm_floor(-((top - ref_alt) / dz)); // ceil
+  if (!(kd <= SKY_COLUMN_NODES_MAX)) return false;
+  const int32_t K = kd < 1.0 ? 1 : (int32_t)kd;
+  double h_prev = ref_alt, q_prev = sky_refractivity<CUBIC>(atm, ref_alt), z = 0.0;
+  for (int32_t k = 1; k <= K; k++) {
+    const double h = k < K ? ref_alt + (double)k * dz : top;
+    const double q = sky_refractivity<CUBIC>(atm, h);
+    z = z + 0.5 * (q_prev + q) * (h - h_prev);
+    h_prev = h, q_prev = q;
+  }
+  *z0 = z;
+  return true;
+}
+
+// The shade as the kernel holds it: the call's atmrt_sky_shade_t and, per body, R^2 = 4 sin^2(radius / 2) of the limb rule, made
+// once on the host by the functions a lane would run.
+struct SkyShadeDev {
+  double zenith_column, tau[3], limb[3], exposure;
+  double airlight[3];           // the bytes as doubles
+  double r2[SKY_BODIES_MAX];
+  double rgb[SKY_BODIES_MAX][3]; // the bodies' colours as doubles
+};
+ATMRT_HD double sky_limb_r2(double radius_deg) {
+  const double s = dm_sin(0.5 * dm_to_radians(radius_deg));
+  return 4.0 * s * s;
+}
+ATMRT_HD bool sky_shade_valid(const atmrt_sky_shade_t& s) {
+  const double inf = dm_inf();
+  if (!(s.zenith_column > 0.0 && s.zenith_column < inf) || !(s.exposure >= 0.0 && s.exposure < inf)) return false;
+  for (int c = 0; c < 3; c++)
+    if (!(s.tau[c] >= 0.0 && s.tau[c] < inf) || !(s.limb[c] >= 0.0 && s.limb[c] <= 1.0)) return false;
+  return true;
+}
+ATMRT_HD SkyShadeDev sky_shade_dev(const atmrt_sky_shade_t& s, const atmrt_sky_body_t* bodies, uint32_t n_bodies) {
+  SkyShadeDev d{};
+  d.zenith_column = s.zenith_column, d.exposure = s.exposure;
+  for (int c = 0; c < 3; c++) d.tau[c] = s.tau[c], d.limb[c] = s.limb[c], d.airlight[c] = (double)s.airlight[c];
+  for (uint32_t k = 0; k < n_bodies; k++) {
+    d.r2[k] = sky_limb_r2(bodies[k].radius_deg);
+    for (int c = 0; c < 3; c++) d.rgb[k][c] = (double)bodies[k].rgb[c];
+  }
+  return d;
+}
+// the byte of a channel value: 255 from 255.0 on, the truncated value below it; a value that is not positive (a NaN too) gives 0
+ATMRT_HD uint8_t sky_byte(double v) { return v >= 255.0 ? (uint8_t)255 : (v > 0.0 ? (uint8_t)v : (uint8_t)0); }
+// The shade of one EXIT pixel: its body (sky_body_of) and its three bytes — the body's colour dimmed by the transmittance of the
+// pixel's air mass and by the limb darkening at its place on the disc, or, for a pixel of no body, the airlight.
+ATMRT_HD uint32_t sky_shade_pixel(const SkyShadeDev& sh, const SkyBodyDev* bodies, uint32_t n_bodies, double azimuth_deg, double true_elevation_deg,
+                                  double column, uint8_t out[3]) {
+  const uint32_t body = sky_body_of(bodies, n_bodies, azimuth_deg, true_elevation_deg);
+  const double x = column / sh.zenith_column;
+  double mu = 0.0;
+  if (body) {
+    const Vec3 d = sky_unit_vector(azimuth_deg, true_elevation_deg);
+    const SkyBodyDev& u = bodies[body - 1];
+    const double ex = d.x - u.x, ey = d.y - u.y, ez = d.z - u.z;
+    const double chord2 = ex * ex + ey * ey + ez * ez;
+    const double m = 1.0 - chord2 / sh.r2[body - 1];
+    mu = m > 0.0 ? dm_sqrt(m) : 0.0;
+  }
+  for (int c = 0; c < 3; c++) {
+    const double t = dm_exp(-(sh.tau[c] * x));
+    double v;
+    if (body) {
+      const double limb = 1.0 - sh.limb[c] * (1.0 - mu);
+      v = sh.rgb[body - 1][c] * t * limb;
+    } else {
+      v = sh.airlight[c] * sh.exposure * (1.0 - t);
+    }
+    out[c] = sky_byte(v);
+  }
+  return body;
+}
+
+// ---------------------------------------------------------------------------------------------
 // apparent elevation (include/atmrt.h, "apparent elevation"): the refraction table's lattice and its inverse, one set for the
 // kernels (k_sky_table_march, k_sky_tail, k_sky_apparent, k_shadow_lights) and the host (atmrt_sky_tail_host, atmrt_sky_apparent_host)
 // ---------------------------------------------------------------------------------------------

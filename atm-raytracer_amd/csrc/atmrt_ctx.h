@@ -272,6 +272,7 @@ struct atmrt_ctx {
   double shadow_timings[3] = {};           // atmrt_last_shadow_timings
   atmrt::DevBuf d_sky;                     // atmrt_sky_*: the call's list of sky pixels and its counters
   double sky_timings[3] = {};              // atmrt_last_sky_timings
+  double sky_shade_ms = 0.0;               // atmrt_last_sky_shade_timing
   atmrt::DevBuf d_sky_table;               // "apparent elevation": T [n_alt][n_el] f64, then tail [n_alt] u32, then S [n_alt][n_el] u8, kept across calls
   atmrt::Cached<atmrt::SkyTableKey, atmrt::SkyTableInfo> sky_table;
   int32_t sky_table_rebuilt = 0;           // atmrt_last_sky_table_work

@@ -21,6 +21,15 @@
 //   k_sky_tail     one wavefront per row of the table: tail[j] (sky_tail_of), 64 entries at a time from the row's end.
 //   k_sky_apparent one thread per (h, t) pair of a list call: sky_apparent over the table.
 //
+//   k_sky_light_march  ("sky light" of include/atmrt.h) k_sky_march's loop and list order with the refractivity column carried along:
+//                  h_prev, q_prev and the column live across the loop beside the stepper, and every step that is not LOST or GROUND
+//                  evaluates q(h) once more, generically (sky_refractivity) — not taken from the next step's first stage, which
+//                  evaluates n at the same height by the certified shortcuts: equal values are the certificate's claim, not this
+//                  kernel's to rely on.  A decided lane stops accumulating.  A kernel of its own: k_sky_march stays as it is.
+//   k_sky_fill_nan the column plane set to NaN ahead of the march, which writes the list's pixels only.
+//   k_sky_shade    one thread per pixel: sky_shade_pixel for the EXIT pixels — the body plane as k_sky_bodies writes it, the image
+//                  shaded in place.
+//
 // The launch covers the pixels, not the list (its length stays on the device: no host round trip between the two kernels); a
 // wavefront beyond the list's end leaves at once.  The list call (atmrt_sky_rays) marches without a list: entry i is ray i.
 #pragma once
@@ -61,6 +70,26 @@ struct SkyBodiesJob {
   uint8_t colour[SKY_BODIES_MAX][4];
 };
 void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream);
+
+struct SkyLightJob {
+  SkyJob sky;
+  double* column; // [n_pixels]
+};
+void launch_sky_light_march(const Frame& f, const SkyLightJob& job, hipStream_t stream, hipEvent_t ev_compacted);
+
+struct SkyShadeJob {
+  size_t n_pixels;
+  const double* azimuth;        // [n_pixels]
+  const double* true_elevation; // [n_pixels]
+  const uint8_t* status;        // [n_pixels]
+  const double* column;         // [n_pixels]
+  uint8_t* body;                // [n_pixels]
+  uint8_t* rgb;                 // [n_pixels][3]
+  uint32_t n_bodies;            // 0 .. SKY_BODIES_MAX
+  SkyBodyDev bodies[SKY_BODIES_MAX];
+  SkyShadeDev shade;
+};
+void launch_sky_shade(const SkyShadeJob& job, hipStream_t stream);
 
 struct SkyTableJob {
   SkyLattice lat;
@@ -156,6 +185,111 @@ void launch_sky_march(const Frame& f, const SkyJob& job, hipStream_t stream, hip
   const dim3 grid(cdiv(n, 64 * SKY_WAVES)), blk(64 * SKY_WAVES);
   if (f.atm_cubic) hipLaunchKernelGGL((k_sky_march<true>), grid, blk, 0, stream, f, job);
   else hipLaunchKernelGGL((k_sky_march<false>), grid, blk, 0, stream, f, job);
+}
+
+__global__ __launch_bounds__(256) void k_sky_fill_nan(double* plane, size_t n) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n) plane[p] = dm_from_bits(0x7ff8000000000000ULL);
+}
+
+#ifndef ATMRT_SKY_LIGHT_WAVES_PER_EU // (EXTRA=-DATMRT_SKY_LIGHT_WAVES_PER_EU=n: tools/measure_sky_light.py's A/B builds)
+#define ATMRT_SKY_LIGHT_WAVES_PER_EU 5
+#endif
+constexpr int SKY_LIGHT_WAVES_PER_EU = ATMRT_SKY_LIGHT_WAVES_PER_EU;
+
+// k_sky_march with the column: the same loop, the same list order, the same counts.  Five wavefronts per SIMD, chosen by
+// measurement: the three doubles that live across the loop beside the stepper do not fit the 96 VGPRs of five without three
+// dwords of scratch per lane, and still the march is 5 to 6 % faster than at four wavefronts (114 / 126 VGPRs, no scratch):
+// profiles/sky_light_resources.txt, profiles/sky_light.json.
+template <bool CUBIC>
+__global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(SKY_LIGHT_WAVES_PER_EU, SKY_LIGHT_WAVES_PER_EU))) void k_sky_light_march(Frame f, SkyLightJob lj) {
+  const SkyJob& j = lj.sky;
+  const int lane = threadIdx.x & 63;
+  const size_t wave = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SKY_WAVES + (threadIdx.x >> 6)));
+  const size_t n = j.list ? (size_t)j.ctr[SKY_LIST] : j.n_pixels;
+  const size_t groups = (n + 63) / 64;
+  if (wave >= groups) return; // the whole wavefront
+  const size_t first = (j.reverse ? groups - 1 - wave : wave) * 64;
+  const bool live = first + lane < n;
+  const size_t at = live ? first + lane : n - 1;
+  const size_t p = j.list ? (size_t)j.list[at] : at;
+  const double elevation_deg = j.elevation_angle[p];
+  const double h0 = j.alt ? *j.alt : j.h0;
+  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
+  const double radius = f.earth.shape_radius, step = j.step, top = j.top, floor = j.floor;
+  const bool marches = sky_marches(elevation_deg);
+  Stepper s;
+  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
+  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
+  bool decided = !live || !marches;
+  double h_prev = h0, q_prev = sky_refractivity<CUBIC>(*f.atm, h0), column = 0.0;
+  for (int i = 1; i <= j.m; i++) {
+    if (!decided) {
+      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
+      steps = i;
+      const int d = sky_step_status(st.h, floor, top);
+      if (d != ATMRT_SKY_LOST && d != ATMRT_SKY_GROUND) {
+        const double q = sky_refractivity<CUBIC>(*f.atm, st.h);
+        column = sky_column_add(sph, radius, step, column, h_prev, q_prev, st.h, q);
+        h_prev = st.h, q_prev = q;
+      }
+      if (d) {
+        status = d;
+        decided = true;
+      }
+    }
+    if (__all(decided)) break;
+  }
+  if (live) {
+    const bool exited = status == ATMRT_SKY_EXIT;
+    j.true_elevation[p] = exited ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : dm_from_bits(0x7ff8000000000000ULL);
+    lj.column[p] = exited ? column : dm_from_bits(0x7ff8000000000000ULL);
+    j.status[p] = (uint8_t)status;
+    if (j.steps) j.steps[p] = (uint32_t)steps;
+  }
+  const unsigned long long n_exit = wave_sum(live && status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && status == ATMRT_SKY_GROUND ? 1ull : 0ull);
+  const unsigned long long n_inside = wave_sum(live && status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && status == ATMRT_SKY_LOST ? 1ull : 0ull);
+  const unsigned long long n_steps = wave_sum((unsigned long long)steps);
+  if (lane == 0) {
+    if (n_exit) atomicAdd(&j.ctr[SKY_EXIT], n_exit);
+    if (n_ground) atomicAdd(&j.ctr[SKY_GROUND], n_ground);
+    if (n_inside) atomicAdd(&j.ctr[SKY_INSIDE], n_inside);
+    if (n_lost) atomicAdd(&j.ctr[SKY_LOST], n_lost);
+    if (n_steps) atomicAdd(&j.ctr[SKY_STEPS], n_steps);
+  }
+}
+
+void launch_sky_light_march(const Frame& f, const SkyLightJob& job, hipStream_t stream, hipEvent_t ev_compacted) {
+  const size_t n = job.sky.n_pixels;
+  (void)hipMemsetAsync(job.sky.ctr, 0, SKY_N * sizeof(unsigned long long), stream);
+  if (n && job.sky.hit_count) {
+    hipLaunchKernelGGL(k_sky_fill_nan, dim3(cdiv(n, 256)), dim3(256), 0, stream, job.column, n);
+    hipLaunchKernelGGL(k_sky_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, job.sky);
+  }
+  if (ev_compacted) (void)hipEventRecord(ev_compacted, stream);
+  if (!n) return;
+  const dim3 grid(cdiv(n, 64 * SKY_WAVES)), blk(64 * SKY_WAVES);
+  if (f.atm_cubic) hipLaunchKernelGGL((k_sky_light_march<true>), grid, blk, 0, stream, f, job);
+  else hipLaunchKernelGGL((k_sky_light_march<false>), grid, blk, 0, stream, f, job);
+}
+
+__global__ __launch_bounds__(256) void k_sky_shade(SkyShadeJob j) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= j.n_pixels) return;
+  uint32_t body = 0;
+  if (j.status[p] == ATMRT_SKY_EXIT) {
+    uint8_t out[3];
+    body = sky_shade_pixel(j.shade, j.bodies, j.n_bodies, j.azimuth[p], j.true_elevation[p], j.column[p], out);
+    j.rgb[3 * p] = out[0];
+    j.rgb[3 * p + 1] = out[1];
+    j.rgb[3 * p + 2] = out[2];
+  }
+  j.body[p] = (uint8_t)body;
+}
+
+void launch_sky_shade(const SkyShadeJob& job, hipStream_t stream) {
+  if (!job.n_pixels) return;
+  hipLaunchKernelGGL(k_sky_shade, dim3(cdiv(job.n_pixels, 256)), dim3(256), 0, stream, job);
 }
 
 __global__ __launch_bounds__(256) void k_sky_bodies(SkyBodiesJob j) {

@@ -190,6 +190,18 @@ class Context:
     def sky_timings(self):
         return sky_timings(self)
 
+    def sky_light(self, **spec):
+        """generators.sky_light over this context's last frame."""
+        return sky_light(self, **spec)
+
+    def sky_light_rays(self, h0, elevation_deg, **spec):
+        """generators.sky_light_rays on this context."""
+        return sky_light_rays(self, h0, elevation_deg, **spec)
+
+    def sky_shade(self, light, bodies, rgb, **shade):
+        """generators.sky_shade over this context's last frame."""
+        return sky_shade(self, light, bodies, rgb, **shade)
+
     def sky_table(self, spec=None, **kw):
         """generators.sky_table on this context."""
         return sky_table(self, spec, **kw)
@@ -458,11 +470,13 @@ def into_coloring(lib, params_pod, conf):
     return col
 
 
-def draw_image(ctx, coloring, width, height, shadows=None, bodies=None, sky=None):
+def draw_image(ctx, coloring, width, height, shadows=None, bodies=None, sky=None, sky_light=None):
     """Composite the frame of the last generate() on `ctx` into an RGB8 image [height][width][3].  shadows: the status plane of
     shadow_mask() for that frame — under Shading the first trace point of a SHADOWED pixel is drawn at ambient_light.  bodies: sky
     bodies (sky_body() or (azimuth_deg, elevation_deg, radius_deg, rgb) each) drawn over the sky pixels their refracted rays meet;
-    sky: the SkyDirections of that frame (default: sky_directions(ctx) with the spec's defaults)."""
+    sky: the SkyDirections of that frame (default: sky_directions(ctx) with the spec's defaults).  sky_light: True, a dict of
+    sky_shade's parameters (tau, limb, exposure, airlight) or a SkyLight of that frame — the sky pixels are shaded by air mass and
+    the bodies (none if `bodies` is None) reddened and limb-darkened instead of drawn flat (include/atmrt.h, "sky light")."""
     rgb = np.zeros((height, width, 3), dtype=np.uint8)
     if shadows is None:
         ctx.check(ctx.lib.atmrt_draw_image(ctx.handle, C.byref(coloring), rgb.ctypes.data))
@@ -471,7 +485,12 @@ def draw_image(ctx, coloring, width, height, shadows=None, bodies=None, sky=None
         if status.size != width * height:
             raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, f"the shadow status plane has {status.size} entries, the image {width * height} pixels")
         ctx.check(ctx.lib.atmrt_draw_image_shadowed(ctx.handle, C.byref(coloring), status.ctypes.data, rgb.ctypes.data))
-    if bodies is not None:
+    if sky_light is not None and sky_light is not False:
+        light = sky_light if isinstance(sky_light, SkyLight) else sky
+        if not isinstance(light, SkyLight):
+            light = _sky_light_of_frame(ctx, width=width, height=height, steps=False)  # (the argument hides the function's name here)
+        sky_shade(ctx, light, bodies or [], rgb, **(sky_light if isinstance(sky_light, dict) else {}))
+    elif bodies is not None:
         if sky is None:
             sky = sky_directions(ctx, width=width, height=height, steps=False)
         sky_bodies(ctx, sky, bodies, rgb)
@@ -578,6 +597,127 @@ def sky_timings(ctx):
     out = (C.c_double * 3)()
     ctx.check(ctx.lib.atmrt_last_sky_timings(ctx.handle, out))
     return dict(zip(("compact_ms", "march_ms", "download_ms"), out))
+
+
+# ---- sky light: air mass per sky ray, a reddened sun, a shaded sky (include/atmrt.h, "sky light") ---------------------------
+# This project's choice, with no reference counterpart: zenith optical depths per channel that give a blue zenith of about
+# (59, 106, 217) and a horizon that saturates to white, and a limb darkening that is stronger toward the blue.
+SKY_TAU, SUN_LIMB, SKY_EXPOSURE, SKY_AIRLIGHT = (0.06, 0.11, 0.24), (0.5, 0.6, 0.75), 4.0, (255, 255, 255)
+
+
+class SkyLight(SkyDirections):
+    """One sky-light call over a frame: a SkyDirections with column [height][width] f64 (NaN unless EXIT) and zenith_column (Z0);
+    air_mass is their quotient."""
+
+    def __init__(self, true_elevation, status, steps, stats, column, zenith_column):
+        super().__init__(true_elevation, status, steps, stats)
+        self.column, self.zenith_column = column, zenith_column
+
+    @property
+    def air_mass(self):
+        return self.column / self.zenith_column
+
+
+def sky_light_spec(ref_alt=0.0, column_dz=0.0, **sky):
+    """atmrt_sky_light_spec_t.  ref_alt: the altitude whose zenith is air mass 1; column_dz 0: the step of the march; the rest: the
+    arguments of sky_spec, or sky=an _abi.SkySpec."""
+    sp = sky["sky"] if "sky" in sky else sky_spec(**sky)
+    return _abi.SkyLightSpec(sp, float(ref_alt), float(column_dz))
+
+
+def sky_shade_params(zenith_column, tau=SKY_TAU, limb=SUN_LIMB, exposure=SKY_EXPOSURE, airlight=SKY_AIRLIGHT):
+    """atmrt_sky_shade_t."""
+    return _abi.SkyShade(float(zenith_column), (C.c_double * 3)(*[float(v) for v in tau]), (C.c_double * 3)(*[float(v) for v in limb]),
+                         float(exposure), (C.c_uint8 * 3)(*[int(v) for v in airlight]))
+
+
+def sky_zenith_column(atmosphere, wavelength, ref_alt=0.0, top=100000.0, dz=100.0, lib=None):
+    """atmrt_sky_zenith_column_host (host code, no device): Z0(ref_alt, top, dz) [m] of the atmosphere."""
+    lib = lib or _lib.load()
+    out = C.c_double()
+    rc = lib.atmrt_sky_zenith_column_host(C.byref(atmosphere), float(wavelength), float(ref_alt), float(top), float(dz), C.byref(out))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_zenith_column_host refused its arguments")
+    return out.value
+
+
+def sky_light_ray_host(atmosphere, wavelength, earth, straight_rays, spec, h0, elevation_deg, lib=None):
+    """atmrt_sky_light_ray_host (host code, no device): (status, steps, true_elevation, column) of one ray by the function the
+    kernel's lanes run."""
+    lib = lib or _lib.load()
+    out, column = _abi.SkyRay(), C.c_double()
+    rc = lib.atmrt_sky_light_ray_host(C.byref(atmosphere), float(wavelength), C.byref(earth), int(bool(straight_rays)), C.byref(spec), float(h0),
+                                      float(elevation_deg), C.byref(out), C.byref(column))
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_light_ray_host refused its arguments")
+    return out.status, out.steps, out.true_elevation, column.value
+
+
+def sky_shade_host(shade, bodies, azimuth_deg, true_elevation_deg, column, lib=None):
+    """atmrt_sky_shade_host (host code, no device): (body, (r, g, b)) of one EXIT pixel."""
+    lib = lib or _lib.load()
+    arr, n = _sky_bodies_array(bodies)
+    body, rgb = C.c_uint32(), (C.c_uint8 * 3)()
+    rc = lib.atmrt_sky_shade_host(C.byref(shade), arr, n, float(azimuth_deg), float(true_elevation_deg), float(column), C.byref(body), rgb)
+    if rc != 0:
+        raise AtmrtError(rc, "atmrt_sky_shade_host refused its arguments")
+    return body.value, tuple(rgb)
+
+
+def sky_light_rays(ctx, h0, elevation_deg, **spec):
+    """atmrt_sky_light_rays: sky_rays with the column of every ray.  Returns (records [n] of SKY_RAY_DTYPE, column [n] f64, stats)."""
+    sp = spec["spec"] if "spec" in spec else sky_spec(**spec)
+    elev = np.ascontiguousarray(elevation_deg, dtype=np.float64).ravel()
+    rec = np.zeros(elev.size, dtype=SKY_RAY_DTYPE)
+    column = np.zeros(elev.size, dtype=np.float64)
+    st = _abi.SkyStats()
+    ctx.check(ctx.lib.atmrt_sky_light_rays(ctx.handle, C.byref(sp), float(h0), elev.size, elev.ctypes.data, rec.ctypes.data, column.ctypes.data,
+                                           C.byref(st)))
+    return rec, column, _sky_stats(st)
+
+
+def sky_light(ctx, width=None, height=None, steps=True, ref_alt=0.0, column_dz=0.0, **spec):
+    """atmrt_sky_light over the frame of the last generate() on `ctx`: sky_directions with the column plane and the zenith column.
+    spec: the arguments of sky_spec, or spec=an _abi.SkyLightSpec.  Returns a SkyLight."""
+    sp = spec["spec"] if "spec" in spec else sky_light_spec(ref_alt, column_dz, **spec)
+    if width is None or height is None:
+        p = ctx_params(ctx)
+        width, height = int(p.width), int(p.height)
+    true = np.zeros((height, width), dtype=np.float64)
+    column = np.zeros((height, width), dtype=np.float64)
+    status = np.zeros((height, width), dtype=np.uint8)
+    stp = np.zeros((height, width), dtype=np.uint32) if steps else None
+    st, z0 = _abi.SkyStats(), C.c_double()
+    ctx.check(ctx.lib.atmrt_sky_light(ctx.handle, C.byref(sp), true.ctypes.data, status.ctypes.data, None if stp is None else stp.ctypes.data,
+                                      column.ctypes.data, C.byref(st), C.byref(z0)))
+    return SkyLight(true, status, stp, _sky_stats(st), column, z0.value)
+
+
+_sky_light_of_frame = sky_light  # draw_image(sky_light=) calls it
+
+
+def sky_shade(ctx, light, bodies, rgb, **shade):
+    """atmrt_sky_shade over the frame of the last generate() on `ctx`: the EXIT pixels of the RGB8 image `rgb` [height][width][3]
+    shaded in place from a SkyLight of that frame — the airlight by air mass, the bodies' discs reddened and limb-darkened.  shade:
+    tau, limb, exposure, airlight (sky_shade_params), or shade=an _abi.SkyShade.  Returns the body plane [height][width] u8."""
+    sh = shade["shade"] if "shade" in shade else sky_shade_params(light.zenith_column, **shade)
+    arr, n = _sky_bodies_array(bodies)
+    true = np.ascontiguousarray(light.true_elevation, dtype=np.float64)
+    column = np.ascontiguousarray(light.column, dtype=np.float64)
+    status = np.ascontiguousarray(light.status, dtype=np.uint8)
+    body = np.zeros(status.shape, dtype=np.uint8)
+    if not (isinstance(rgb, np.ndarray) and rgb.dtype == np.uint8 and rgb.flags["C_CONTIGUOUS"] and rgb.size == 3 * status.size):
+        raise AtmrtError(_abi.ERR_INVALID_ARGUMENT, "rgb must be a contiguous uint8 image [height][width][3] of the frame")
+    ctx.check(ctx.lib.atmrt_sky_shade(ctx.handle, C.byref(sh), arr, n, true.ctypes.data, status.ctypes.data, column.ctypes.data, body.ctypes.data,
+                                      rgb.ctypes.data))
+    return body
+
+
+def sky_shade_timing(ctx):
+    """atmrt_last_sky_shade_timing: the milliseconds of the last sky_shade call's kernel on `ctx`."""
+    out = C.c_double()
+    ctx.check(ctx.lib.atmrt_last_sky_shade_timing(ctx.handle, C.byref(out)))
+    return out.value
 
 
 # ---- apparent elevation: the refraction table and its inverse (include/atmrt.h, "apparent elevation") ----------------------

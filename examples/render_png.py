@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Render a panorama PNG on the GPU: generator (C ABI) -> renderer::draw_image on the device -> PNG via Pillow.
 Usage: python examples/render_png.py OUT.png [--scene S3] [--width 1024] [--height 512] [--generator Fast] [--objects N]
-       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]] [--sun AZ EL [--shadows --shadow-true]]"""
+       [--shadows [--sun-elevation DEG] [--shadow-reach M] [--shadow-per-point]] [--sun AZ EL [--shadows --shadow-true]] [--sky-colour]"""
 import argparse
 import os
 import sys
@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--shadow-true", action="store_true",
                     help="with --sun AZ EL --shadows: the shadows' light is the sun at its TRUE direction, launched where it appears from "
                          "every point (include/atmrt.h, apparent elevation)")
+    ap.add_argument("--sky-colour", action="store_true",
+                    help="shade the sky by air mass and redden and limb-darken the sun of --sun AZ EL (include/atmrt.h, sky light)")
     a = ap.parse_args()
     if a.shadow_true and not (a.sun and a.shadows):
         ap.error("--shadow-true lights the terrain from the sun of --sun AZ EL: use --sun AZ EL --shadows --shadow-true")
@@ -71,8 +73,14 @@ def main():
     bodies = None
     if a.sun:  # the sky march at 1000 m a step: within 5e-5 degrees of the frame's own step at a tenth of the work
         bodies = [generators.sky_body(a.sun[0], a.sun[1])]
+    if a.sky_colour:  # the same march with the refractivity column carried along, then the shade instead of the flat disc
+        sky = generators.sky_light(ctx, a.width, a.height, steps=False, step=1000.0)
+        print(f"zenith column {sky.zenith_column:.6f} m, air mass {sky.air_mass[sky.status == 1].min():.2f} .. {sky.air_mass[sky.status == 1].max():.2f}"
+              if (sky.status == 1).any() else "no sky pixel leaves the atmosphere")
+    else:
+        sky = generators.sky_directions(ctx, a.width, a.height, steps=False, step=1000.0) if bodies else None
     rgb = generators.draw_image(ctx, generators.into_coloring(ctx.lib, cfg.params, cfg.coloring), a.width, a.height, shadows=shadows, bodies=bodies,
-                                sky=generators.sky_directions(ctx, a.width, a.height, steps=False, step=1000.0) if bodies else None)
+                                sky=sky, sky_light=sky if a.sky_colour else None)
     if bodies:
         print(f"sun at true azimuth {a.sun[0]:g}, elevation {a.sun[1]:g}: {generators.sky_timings(ctx)['march_ms']:.2f} ms of sky march")
     Image.fromarray(rgb, "RGB").save(a.out)

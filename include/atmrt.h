@@ -1006,6 +1006,95 @@ int atmrt_sky_bodies_planes_device(atmrt_ctx* ctx, const atmrt_sky_body_t* bodie
  * library's stream: out = {compaction (clear and upload included), march, download (statistics and host planes)}. */
 int atmrt_last_sky_timings(atmrt_ctx* ctx, double out[3]);
 
+/* ---- sky light: air mass per sky ray, a reddened sun, a shaded sky (no reference counterpart) -----------------------------------
+ * "Sky rays" say where a sky pixel's ray points; this section says how much air it crossed, and colours the sky and the bodies
+ * by it.  The refractivity n(h) - 1 = K (p / T) / Z that the stepper differentiates is, for dry air at one wavelength, proportional
+ * to density, so its integral along the refracted ray ("column") divided by the same integral taken vertically from a reference
+ * altitude ("zenith column") is the relative air mass X.  No atmosphere quantity is needed that the context does not hold.
+ *
+ * THE RULE (tests/sky_light_model.py restates it over the oracle's stepper and oracle_n).
+ *   March: marching, status, steps and true elevation are those of "sky rays", the same bits.  In addition q(h) = n(h) - 1 by the
+ *     generic per-layer IEEE evaluation (the oracle's n(h)), for straight rays too.  Start with h_prev = h0, q_prev = q(h0), C = 0.
+ *     After every step i whose height st.h is neither NaN nor below the floor (the step that EXITs included, whole):
+ *       q_i = q(st.h);  w = (step / radius) * (0.5 * (h_prev + st.h) + radius) on a sphere, w = step on a flat earth;
+ *       dh = st.h - h_prev;  C = C + 0.5 * (q_prev + q_i) * sqrt(w * w + dh * dh);  h_prev = st.h, q_prev = q_i
+ *     — every operation IEEE and rounded on its own.  The output `column` [m] is C for an EXIT ray, NaN for every other status.
+ *   Zenith column Z0(ref_alt, top, dz), host code: K = ceil((top - ref_alt) / dz); nodes ref_alt + k * dz for k < K, the last node
+ *     `top` itself; Z0 = the trapezoid 0.5 * (q_prev + q) * (h - h_prev) over the actual node spacings, summed upward.  Refused:
+ *     K > 1 048 575, a dz that is not finite and positive, ref_alt >= top, a number that is not finite.  Air mass X = column / Z0.
+ *     A light spec is {sky: a spec of "sky rays"; ref_alt [m]; column_dz [m]: 0 means the step of the march}.
+ *     US-76 from sea level to 100 km: Z0 = 2.34687220 m with 100 m nodes, 2.34684803 with 10 m, 2.3493 with 1000 m.
+ *   Shade, EXIT pixels only (every other byte of the image stays): X = column / zenith_column; per channel c
+ *       T_c = exp(-(tau_c * X)).
+ *     The pixel's body is that of "sky rays" (the body plane equals atmrt_sky_bodies').  A pixel of body k, with d and u the unit
+ *     vectors of the body rule:  chord2 = (d.x - u.x)^2 + (d.y - u.y)^2 + (d.z - u.z)^2, summed left to right;
+ *       R2 = 4 * s * s, s = sin(0.5 * to_radians(radius_deg));  m = 1 - chord2 / R2;  mu = sqrt(m) if m > 0, otherwise 0;
+ *       limb_c = 1 - u_c * (1 - mu);  v = rgb_c * T_c * limb_c.
+ *     A pixel of no body, the airlight:  v = airlight_c * exposure * (1 - T_c).
+ *     The byte is 255 if v >= 255, (uint8) v if 0 < v < 255, and 0 otherwise (a NaN too).
+ *     Shade parameters {zenith_column finite and > 0; tau[3] finite and >= 0; limb[3] (the u_c) in [0, 1]; exposure finite and
+ *     >= 0; airlight rgb}.  The Python and CLI defaults — tau (0.06, 0.11, 0.24), limb (0.5, 0.6, 0.75), exposure 4, a white
+ *     airlight: a zenith of about (59, 106, 217), a horizon that saturates to white — are this project's choice.
+ *   The airlight does not know where the sun is, and the stepper advances in GROUND distance: at a sky step of 1000 m an 80-degree
+ *     ray climbs 5.7 km per step and its trapezoid overestimates the column (against the 100 m step: below 1e-5 up to 5 degrees,
+ *     +0.03 % at 30, +0.28 % at 60, +3.2 % at 80; at 100 m the figures agree with Kasten and Young 1989 to 0.2 % from 0.5 to 80
+ *     degrees and to 0.8 % at the horizon).  X is about 1 there and the tint hardly moves.
+ * Equal calls return equal bytes; the list order of the march (ATMRT_SKY_ORDER) decides scheduling only. */
+typedef struct atmrt_sky_light_spec {
+  atmrt_sky_spec_t sky;
+  double ref_alt;   /* [m] the altitude whose zenith is air mass 1; finite, < sky.top */
+  double column_dz; /* [m] node spacing of the zenith column: 0 = the step of the march, otherwise finite and > 0 */
+} atmrt_sky_light_spec_t;
+typedef struct atmrt_sky_shade {
+  double zenith_column; /* [m] Z0, as atmrt_sky_light* and atmrt_sky_zenith_column_host return it; finite, > 0 */
+  double tau[3];        /* zenith optical depth per channel, finite, >= 0 */
+  double limb[3];       /* limb-darkening coefficient per channel, in [0, 1] */
+  double exposure;      /* finite, >= 0 */
+  uint8_t airlight[3];
+  uint8_t _pad[5];
+} atmrt_sky_shade_t;
+/* Host code, no context and no device: Z0 by the function the library runs.  ATMRT_ERR_INVALID_ARGUMENT: NULL, an invalid
+ * atmosphere, arguments the rule refuses. */
+int atmrt_sky_zenith_column_host(const atmrt_atmosphere_t* atmosphere, double wavelength, double ref_alt, double top, double dz, double* zenith_column);
+/* Host code: one ray by the function the kernel's lanes run, the record of atmrt_sky_ray_host and the column.  Refusals as there. */
+int atmrt_sky_light_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays,
+                             const atmrt_sky_spec_t* spec, double h0, double elevation_deg, atmrt_sky_ray_t* out, double* column);
+/* Host code: the shade of one EXIT pixel: *body as atmrt_sky_body_host, rgb[3] its bytes.  ATMRT_ERR_INVALID_ARGUMENT: NULL, shade
+ * parameters or bodies the rule refuses. */
+int atmrt_sky_shade_host(const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, double azimuth_deg,
+                         double true_elevation_deg, double column, uint32_t* body, uint8_t* rgb);
+/* The list call, on the device: atmrt_sky_rays with column[n] beside the records.  Refusals as there. */
+int atmrt_sky_light_rays(atmrt_ctx* ctx, const atmrt_sky_spec_t* spec, double h0, size_t n, const double* elevation_deg, atmrt_sky_ray_t* records,
+                         double* column, atmrt_sky_stats_t* stats);
+/* atmrt_sky_directions_device with the column plane [height][width] f64 beside the others, and *zenith_column = Z0(spec->ref_alt,
+ * spec->sky.top, spec->column_dz) of the context's atmosphere.  steps_device and stats may be NULL.  Refusals as
+ * atmrt_sky_directions_device, and what the zenith column refuses. */
+int atmrt_sky_light_device(atmrt_ctx* ctx, const atmrt_sky_light_spec_t* spec, double* true_elevation_device, uint8_t* status_device,
+                           uint32_t* steps_device, double* column_device, atmrt_sky_stats_t* stats, double* zenith_column);
+/* The same into host arrays. */
+int atmrt_sky_light(atmrt_ctx* ctx, const atmrt_sky_light_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps, double* column,
+                    atmrt_sky_stats_t* stats, double* zenith_column);
+/* The same over any hit_count and elevation_angle planes of n_pixels entries in device memory, from h0 (a gathered multi-device frame). */
+int atmrt_sky_light_planes_device(atmrt_ctx* ctx, const atmrt_sky_light_spec_t* spec, double h0, size_t n_pixels, const uint32_t* hit_count,
+                                  const double* elevation_angle, double* true_elevation_device, uint8_t* status_device, uint32_t* steps_device,
+                                  double* column_device, atmrt_sky_stats_t* stats, double* zenith_column);
+/* The shade of the last frame of a single-device context: the body plane as atmrt_sky_bodies_device writes it, and the EXIT pixels
+ * of the [height][width][3] image rgb_device (not NULL here) shaded in place.  ATMRT_ERR_INVALID_ARGUMENT: NULL, shade parameters
+ * or bodies the rule refuses.  ATMRT_ERR_STATE: without a frame, on a multi-device context. */
+int atmrt_sky_shade_device(atmrt_ctx* ctx, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies,
+                           const double* true_elevation_device, const uint8_t* status_device, const double* column_device, uint8_t* body_device,
+                           uint8_t* rgb_device);
+/* The same from and into host arrays. */
+int atmrt_sky_shade(atmrt_ctx* ctx, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation,
+                    const uint8_t* status, const double* column, uint8_t* body, uint8_t* rgb);
+/* The same over the caller's planes of n_pixels entries in device memory, the azimuth plane included. */
+int atmrt_sky_shade_planes_device(atmrt_ctx* ctx, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, size_t n_pixels,
+                                  const double* azimuth, const double* true_elevation_device, const uint8_t* status_device,
+                                  const double* column_device, uint8_t* body_device, uint8_t* rgb_device);
+/* atmrt_last_sky_timings reports the atmrt_sky_light* calls as it reports atmrt_sky_directions*.  The last atmrt_sky_shade* call on
+ * ctx: *ms = the milliseconds of its kernel between events on the library's stream. */
+int atmrt_last_sky_shade_timing(atmrt_ctx* ctx, double* ms);
+
 /* ---- apparent elevation: the inverse of the sky march, and shadow lights given by their TRUE direction (no reference counterpart)
  * "Sky rays" turn a LAUNCH elevation into the TRUE elevation of the ray outside the atmosphere.  This section is the inverse: for a
  * point at altitude h and a body (a light) at local true elevation t, the launch elevation whose ray leaves the atmosphere at t —
