@@ -579,6 +579,17 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
   const double alt = *f.alt;
   const uint32_t head_steps = n_groups ? order_steps[0] : 0u; // the longest estimate of the frame: what a long item's estimate is set against
   __shared__ WaveListLds<0, 1> lists;
+  // The device counters of this wavefront's items, summed in LDS and added to the frame's once, when the wavefront leaves.  A
+  // wavefront marches some thirty items, and four atomics per item on one cache line from each of 4,096 wavefronts are served one
+  // after the other while the wavefront's next loads wait behind them.  A slot per counter the lean march
+  // adds to: steps, lookups, escaped rays and their credited steps.
+  __shared__ unsigned long long wave_counters[16][N_COUNTERS];
+  unsigned long long* const my_counters = wave_counters[(threadIdx.x >> 6) & 15];
+  if (lane < N_COUNTERS) my_counters[lane] = 0ull;
+  // lanes 0 .. 15 wrote the slots, lane 0 adds to them from here on (count_wave_steps): the hand-off of wave_list_build
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   for (;;) {
     // a short wavefront sizes its chunk by the estimate of the item at the tail as it is now and by the items left (a look, not a
     // claim: the tail may have moved on by the time of the claim, towards longer items — by a few claims' worth)
@@ -628,7 +639,7 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
 #ifdef ATMRT_TIMELINE
       const int tl_wave_steps = timeline_wave_steps(n);
 #endif
-      const unsigned long long steps = count_wave_steps<true>(counters, n.steps, n.lookups, n.esc_credit);
+      const unsigned long long steps = count_wave_steps<true>(my_counters, n.steps, n.lookups, n.esc_credit);
       (void)steps;
 #ifdef ATMRT_TIMELINE
       timeline_record(group, tl_t0, steps, tl_wave_steps);
@@ -636,6 +647,11 @@ __global__ __launch_bounds__(1024) void k_rect_march_queue(Frame f, DensePlanes 
 #endif
     }
   }
+  // lane 0 wrote the sums, the lanes 0 .. 15 read them: the same hand-off the other way
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane < N_COUNTERS && my_counters[lane]) atomicAdd(&counters[lane], my_counters[lane]);
 }
 
 // ---------------------------------------------------------------------------------------------
