@@ -190,6 +190,7 @@ def load():
         "atmrt_debug_normal_trig": (C.c_int, [vp, sz, vp, C.POINTER(sz)]),
         "atmrt_debug_ceiling_table": (C.c_int, [vp, sz, vp, vp, C.POINTER(i32), C.POINTER(i32), pd]),
         "atmrt_debug_march_order": (C.c_int, [vp, sz, vp, C.POINTER(C.c_uint32)]),
+        "atmrt_debug_march_order_steps": (C.c_int, [vp, sz, vp, C.POINTER(C.c_uint32)]),
         "atmrt_debug_last_march_route": (C.c_int, [vp, i32, C.POINTER(i32)]),
         "atmrt_debug_interp_blend": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, dbl, dbl, dbl, C.POINTER(_abi.InterpLattice),
                                                C.POINTER(_abi.Result)]),
@@ -244,7 +245,7 @@ EXPORTED = ["atmrt_abi_version", "atmrt_build_info", "atmrt_ctx_create", "atmrt_
             "atmrt_sky_shade_planes_device", "atmrt_last_sky_shade_timing", "atmrt_sky_table", "atmrt_sky_tail_host", "atmrt_sky_apparent_host", "atmrt_sky_apparent",
             "atmrt_shadow_lights_true_device", "atmrt_shadow_lights_true", "atmrt_shadow_lights_true_planes_device", "atmrt_last_sky_table_work",
             "atmrt_ray_paths", "atmrt_atmosphere_sample",
-            "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_debug_last_march_route", "atmrt_debug_interp_blend", "atmrt_result_encode_bincode",
+            "atmrt_coords_at_dist", "atmrt_math_probe", "atmrt_math_probe3", "atmrt_debug_step_trig", "atmrt_debug_normal_trig", "atmrt_debug_ceiling_table", "atmrt_debug_march_order", "atmrt_debug_march_order_steps", "atmrt_debug_last_march_route", "atmrt_debug_interp_blend", "atmrt_result_encode_bincode",
             "atmrt_result_decode_bincode", "atmrt_comm_unique_id", "atmrt_ctx_comm_init_rank", "atmrt_ctx_comm_init_external", "atmrt_ctx_comm_init_external_device",
             "atmrt_ctx_create_multi", "atmrt_ctx_device_count", "atmrt_generate_image_device", "atmrt_image_hits_device",
             "atmrt_draw_image_gathered_device", "atmrt_last_comm_timings", "atmrt_comm_available", "atmrt_ctx_tile_columns",

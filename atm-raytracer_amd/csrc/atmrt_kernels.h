@@ -313,12 +313,14 @@ struct MarchOrder {
   uint32_t* estimate;  // [n_groups] estimated steps of each group (the longest of its sampled rays), 0 .. march_steps
   uint32_t* bin_count; // [march_steps + 1] groups per estimate, then the cursor of each estimate's run in `order`
 };
-static inline void march_order_layout(const Frame& f, Carve& k, MarchOrder& o) {
-  const size_t n_groups = ((size_t)f.wl * f.h + 63) / 64;
+static inline void march_order_layout(size_t n_groups, size_t march_steps, Carve& k, MarchOrder& o) {
   k(o.order, n_groups * sizeof(uint32_t));
   k(o.order_steps, n_groups * sizeof(uint32_t));
   k(o.estimate, n_groups * sizeof(uint32_t));
-  k(o.bin_count, ((size_t)f.march_steps + 1) * sizeof(uint32_t));
+  k(o.bin_count, (march_steps + 1) * sizeof(uint32_t));
+}
+static inline void march_order_layout(const Frame& f, Carve& k, MarchOrder& o) {
+  march_order_layout(((size_t)f.wl * f.h + 63) / 64, (size_t)f.march_steps, k, o);
 }
 
 // Scratch of one frame.  Three owners (atmrt_ctx.h): the context's one workspace allocation, carved by workspace_layout below (array

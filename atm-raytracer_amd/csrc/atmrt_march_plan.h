@@ -20,7 +20,9 @@ enum class MarchRoute : int32_t { None = 0, Grid = 1, GridDrain = 2, Sliced = 3,
 
 // ATMRT_MARCH_VARIANT=plain|small|sliced forces one variant for every launch (test hook: the random sweeps run small frames over the
 // kernel the full-size frames use, and the other way round; same results every way).  =queue forces the whole-frame work queue on
-// the frames that can take it at any size and leaves every other launch to the choice by size.
+// the frames that can take it at any size and leaves every other launch to the choice by size.  All four are swept: the variant
+// sweeps of tests/test_gpu_ceiling.py, _ceiling_table.py, _step_trig.py and _escape.py list queue beside the other three, and
+// tests/test_gpu_march_queue_scenes.py runs a family of queue-eligible frames (tests/queue_cases.py) through it against the oracle.
 enum MarchOverride : int { MARCH_BY_SIZE = 0, MARCH_FORCE_PLAIN = 1, MARCH_FORCE_SMALL = 2, MARCH_FORCE_SLICED = 3, MARCH_FORCE_QUEUE = 4 };
 
 // A launch of at most MARCH_SMALL_MAX_BLOCKS 256-thread blocks is "small" (a few resident sets: column shards of a frame, test

@@ -178,6 +178,25 @@ extern "C" int atmrt_debug_march_order(atmrt_ctx* c, size_t cap, uint32_t* order
   return ATMRT_OK;
 }
 
+extern "C" int atmrt_debug_march_order_steps(atmrt_ctx* c, size_t cap, uint32_t* order_steps, uint32_t* n_groups) {
+  if (!c || !n_groups || (cap && !order_steps)) return ATMRT_ERR_INVALID_ARGUMENT;
+  FORWARD_TO_FIRST_DEVICE(c, atmrt_debug_march_order_steps(k_, cap, order_steps, n_groups));
+  *n_groups = 0;
+  if (!c->last.valid || !c->last.order_groups) return ATMRT_OK;
+  if (c->ceil_order.serial() != c->last.order_serial)
+    return c->fail(ATMRT_ERR_STATE, "the march order of the last frame is gone: a later call built another one in its place");
+  *n_groups = c->last.order_groups;
+  const size_t n = *n_groups < cap ? *n_groups : cap;
+  if (!n) return ATMRT_OK;
+  MarchOrder o{};
+  Carve carved(c->d_ceil_order.ptr); // the carving of the build (prepare_ceiling): a queued frame has a table of march_steps + 1 rows
+  march_order_layout(c->last.order_groups, (size_t)(c->last.ceil_rows > 0 ? c->last.ceil_rows - 1 : 0), carved, o);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(order_steps, o.order_steps, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ATMRT_OK;
+}
+
 extern "C" int atmrt_debug_last_march_route(atmrt_ctx* c, int32_t index, int32_t* route) {
   if (!c || !route) return ATMRT_ERR_INVALID_ARGUMENT;
   if (c->multi) {

@@ -137,6 +137,17 @@ class Context:
             assert n.value == order.size
         return order
 
+    def debug_march_order_steps(self):
+        """Diagnostic (atmrt_debug_march_order_steps): the estimated steps of every entry of debug_march_order(), uint32 [n_groups],
+        non-increasing; empty when the last generated frame marched without a queue."""
+        n = C.c_uint32()
+        self.check(self.lib.atmrt_debug_march_order_steps(self.handle, 0, None, C.byref(n)))
+        steps = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.check(self.lib.atmrt_debug_march_order_steps(self.handle, n.value, steps.ctypes.data, C.byref(n)))
+            assert n.value == steps.size
+        return steps
+
     def debug_march_route(self, index=-1):
         """Diagnostic (atmrt_debug_last_march_route): 1 plain grid, 2 small-launch grid, 3 time-sliced, 4 work queue; 0 not Rectilinear."""
         route = C.c_int32()

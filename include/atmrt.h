@@ -1384,6 +1384,14 @@ int atmrt_debug_ceiling_table(atmrt_ctx* ctx, size_t cap, float* cell, float* su
  * build; what must hold is that it is a permutation of 0 .. *n_groups - 1 (tests/test_gpu_march_queue.py).  ATMRT_ERR_STATE when a
  * later call has built another order in its place. */
 int atmrt_debug_march_order(atmrt_ctx* ctx, size_t cap, uint32_t* order, uint32_t* n_groups);
+/* Beside it, under the same rules (*n_groups = 0 without a queue, ATMRT_ERR_STATE once another order was built, the first device of
+ * a multi-device context): the ESTIMATED STEPS the queue holds for every entry of that order — order_steps[i] is the estimate of
+ * group order[i], the longest of the four rays k_march_length_estimate samples across the group's 64 pixels (pixels 0, 21, 42 and
+ * 63, clamped to the image's last), each the first step >= 1 at which ceiling_estimate_ends (csrc/atmrt_ceiling.h) holds for the
+ * ray's bin, else the march's steps.  Every value lies in 1 .. steps and the array is non-increasing: the queue sizes the chunks it
+ * claims and sets its priorities by these numbers.  They decide scheduling only and change no bit of a frame, so
+ * tests/test_gpu_march_queue_scenes.py compares them with a host restatement (tests/march_order_model.py). */
+int atmrt_debug_march_order_steps(atmrt_ctx* ctx, size_t cap, uint32_t* order_steps, uint32_t* n_groups);
 /* The route the LAST GENERATED FRAME's first-pass Rectilinear march was launched by (MarchRoute, csrc/atmrt_march_plan.h): 0 none
  * (another generator), 1 the plain grid, 2 the small-launch grid, 3 the time-sliced march, 4 the whole-frame work queue.  What was
  * launched, not what was planned: a queue that had to fall back reports its grid.  All routes give the same bits, so this is how a

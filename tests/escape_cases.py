@@ -301,6 +301,21 @@ def frame_case(lib, oracle, seed):
 
 
 
+def real_duct_scene(kind="Linear"):
+    """0.5 K/m over 300 m (sup g 2.7) with its base 60 m above the top of a 5 x 5 mosaic and the observer 150 m under the top, looking west over its ridges, rows 0.04
+    degrees apart around the horizontal: rays that leave at 0 .. 0.3 degrees rise into the layer and are turned back.  `kind`: the
+    layer as three Linear functions or as a Spline with that boundary condition (atmospheres.inversion)."""
+    tiles, top = frame_tiles(wide=True)  # 250 km of terrain to come down on
+    atm = atmospheres.inversion(top + 60.0, 300.0, 0.5, kind)
+    cfg = config.Config.from_dict({
+        "view": {"position": {"latitude": 46.5, "longitude": 8.5, "altitude": {"Absolute": top - 150.0}},
+                 "frame": {"direction": 270.0, "tilt": 0.15, "fov": 2.0, "max_distance": 250_000.0}},
+        "earth_shape": {"Spherical": {"radius": 6371000.0}}, "simulation_step": 100.0, "atmosphere": atm,
+        "output": {"width": 48, "height": 32, "generator": "Rectilinear"}})
+    return dict(cfg=cfg, tiles=tiles, top=top, atm=atm, radius=6371000.0, flat=False, straight=False, step=100.0,
+                wavelength=cfg.params.wavelength, altitude=top - 150.0)
+
+
 def frame_certificate(lib, case):
     """The certificate the frame's context computes: its atmosphere, shape radius, step and the mosaic's skip_above."""
     return certificate(lib, case["atm"], case["radius"] or 0.0, case["wavelength"], case["top"], case["step"],

@@ -35,10 +35,10 @@ def _rough(seed, n_lat, n_lon):
     return np.random.default_rng(seed).integers(-50, 3000, size=(n_lat, n_lon)).astype(np.int16)
 
 
-def _run(exe, tmp_path, tiles, lat, lon, direction, step, max_distance, tilt=0.0, per_cell=3, seed=1, fov=FOV):
+def _run(exe, tmp_path, tiles, lat, lon, direction, step, max_distance, tilt=0.0, per_cell=3, seed=1, fov=FOV, radius=RADIUS, width=W, height=H):
     case, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
     with open(case, "wb") as f:
-        f.write(struct.pack("<12d", lat, lon, direction, fov, tilt, step, max_distance, RADIUS, W, H, per_cell, seed))
+        f.write(struct.pack("<12d", lat, lon, direction, fov, tilt, step, max_distance, radius, width, height, per_cell, seed))
         f.write(struct.pack("<i", len(tiles)))
         for (la, lo), posts in tiles.items():
             f.write(struct.pack("<4i", la, lo, posts.shape[0], posts.shape[1]))

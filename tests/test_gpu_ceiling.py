@@ -74,7 +74,9 @@ def _child(variant):
     return _CHILD_RESULTS[variant]
 
 
-VARIANTS = [None, "plain", "small", "sliced"]
+# queue: the whole-frame work queue, forced on the opaque frames (192 x 96: 288 groups; `work`, 512 x 256: 2,048 groups, whose LDS counter
+# sums must give every other route's integrated steps); without a table (ATMRT_CEILING=off) it has no order and falls back to the grid
+VARIANTS = [None, "plain", "small", "sliced", "queue"]
 
 
 @pytest.mark.gpu

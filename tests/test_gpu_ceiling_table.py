@@ -328,7 +328,7 @@ for name in {frames!r}:
     i, e = C.c_uint64(), C.c_uint64()
     ctx.check(ctx.lib.atmrt_last_march_work(ctx.handle, C.byref(i), C.byref(e)))
     st = frame_stats(ctx)
-    out[name] = [cc.frame_hash(got), int(got["n_hits"]), int(i.value), int(e.value), int(st["terrain_lookups"]), int(st["object_rays"])]
+    out[name] = [cc.frame_hash(got), int(got["n_hits"]), int(i.value), int(e.value), int(st["terrain_lookups"]), int(st["object_rays"]), ctx.debug_march_route()]
 ctx.close()
 print("RESULT " + json.dumps(out))
 """
@@ -350,18 +350,22 @@ def _child(variant):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", [None, "plain", "small", "sliced"])
+@pytest.mark.parametrize("variant", [None, "plain", "small", "sliced", "queue"])
 def test_every_march_variant_marches_the_oracles_frame_over_spikes(oracle_det, variant):
     """300 steps are three slices of 128 for the sliced march: the later slices derive the ray's bin again from the pixel.  The
-    frame with objects goes through the out-of-line object step of the small and the sliced march, which does not skip."""
+    frame with objects goes through the out-of-line object step of the small and the sliced march, which does not skip.  Under
+    `queue` the opaque frames are marched by k_rect_march_queue, which derives every ray's bin itself (route 4); the translucent
+    frames and the one with objects cannot take it and go by their size."""
     got = _child(variant)
     for name in CHILD_FRAMES:
         want = _oracle_frame(oracle_det, name)
-        h, n_hits, integrated, escaped, lookups, object_rays = got[name]
+        h, n_hits, integrated, escaped, lookups, object_rays, route = got[name]
         print(f"\n{variant or 'default'} {name}: {n_hits} trace points, integrated steps {integrated}, escaped rays {escaped}, lookups {lookups}, "
               f"object rays {object_rays}")
         assert n_hits == int(want["n_hits"]) and h == cc.frame_hash(want), (variant, name)
         if "translucent" not in name and name != "objects":  # an opaque frame's work is one number: a ray's bin is its own
             assert integrated == _child(None)[name][2], (variant, name)
+        if variant == "queue":
+            assert (route == 4) == ("translucent" not in name and name != "objects"), (name, route)
     tags = _oracle_frame(oracle_det, "objects")["color_tag"]
     assert (tags == 0).sum() >= 100 and (tags != 0).sum() >= 100  # terrain and objects were both met

@@ -65,7 +65,7 @@ for name, cfg, tiles in frames:
         for k in FIELDS_PIXEL + FIELDS_HIT:
             h.update(np.ascontiguousarray(bits(r[k])).tobytes())
         integrated, escaped = work()
-        res[esc] = [h.hexdigest(), int(r["n_hits"]), int(r["ray_steps"]), integrated, escaped]
+        res[esc] = [h.hexdigest(), int(r["n_hits"]), int(r["ray_steps"]), integrated, escaped, ctx.debug_march_route()]
     out[name] = res
 os.environ.pop("ATMRT_ESCAPE", None)
 print("RESULT " + json.dumps(out))
@@ -205,20 +205,10 @@ def _ends_escaping(h, floor):
 
 
 def _real_duct_scene():
-    """0.5 K/m over 300 m (sup g 2.7) with its base 60 m above the top of a 5 x 5 mosaic and the observer 150 m under the top, looking west over its ridges, rows 0.04
-    degrees apart around the horizontal: rays that leave at 0 .. 0.3 degrees rise into the layer and are turned back."""
-    import atmospheres
+    """escape_cases.real_duct_scene (shared with tests/queue_cases.py, which marches it through the work queue): 0.5 K/m over 300 m
+    (sup g 2.7) with its base 60 m above the top of a 5 x 5 mosaic and the observer 150 m under the top."""
     import escape_cases as ec
-    from atm_raytracer_amd import config
-    tiles, top = ec.frame_tiles(wide=True)  # 250 km of terrain to come down on
-    atm = atmospheres.inversion(top + 60.0, 300.0, 0.5)
-    cfg = config.Config.from_dict({
-        "view": {"position": {"latitude": 46.5, "longitude": 8.5, "altitude": {"Absolute": top - 150.0}},
-                 "frame": {"direction": 270.0, "tilt": 0.15, "fov": 2.0, "max_distance": 250_000.0}},
-        "earth_shape": {"Spherical": {"radius": 6371000.0}}, "simulation_step": 100.0, "atmosphere": atm,
-        "output": {"width": 48, "height": 32, "generator": "Rectilinear"}})
-    return dict(cfg=cfg, tiles=tiles, top=top, atm=atm, radius=6371000.0, flat=False, straight=False, step=100.0,
-                wavelength=cfg.params.wavelength, altitude=top - 150.0)
+    return ec.real_duct_scene()
 
 
 _DUCT_FRAME = {}
@@ -360,15 +350,22 @@ VARIANT_SEEDS = (1, 4, 5, 7, 12)  # a refused duct (1, 7), straight rays (4), ob
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["plain", "small", "sliced"])
+@pytest.mark.parametrize("variant", ["plain", "small", "sliced", "queue"])
 def test_sweep_frames_under_every_march_variant(oracle_det, oracle_libm, variant):
     """Five frames of the sweep under each march variant (one child process per variant): on and off give the same bits and the same
-    ray_steps as the oracle's frame."""
+    ray_steps as the oracle's frame.  The whole-frame work queue takes opaque whole frames without objects on the Spherical
+    calculator only, so `queue` runs over the sweep's seeds of that kind (queue_cases.eligible_seeds: threshold layers, ducts and
+    random families, most of them Splines), and every one of them must have been launched as a queue."""
     import hashlib
     from util import bits, FIELDS_PIXEL, FIELDS_HIT
-    got = _run(variant, full=False, sweep_seeds=VARIANT_SEEDS)
-    assert len(got) == len(VARIANT_SEEDS)
-    for seed in VARIANT_SEEDS:
+    seeds = VARIANT_SEEDS
+    if variant == "queue":
+        import queue_cases
+        seeds = queue_cases.eligible_seeds()
+        assert len(seeds) >= 10
+    got = _run(variant, full=False, sweep_seeds=seeds)
+    assert len(got) == len(seeds)
+    for seed in seeds:
         want = _sweep_case(seed, oracle_libm, oracle_det)["want"]
         h = hashlib.sha256()
         for k in FIELDS_PIXEL + FIELDS_HIT:
@@ -376,3 +373,5 @@ def test_sweep_frames_under_every_march_variant(oracle_det, oracle_libm, variant
         on, off = got["seed%d" % seed]["on"], got["seed%d" % seed]["off"]
         assert on[:3] == off[:3] == [h.hexdigest(), int(want["n_hits"]), int(want["ray_steps"])], (seed, on, off)
         assert off[3] == off[2] and off[4] == 0 and on[3] <= on[2], (seed, on, off)
+        if variant == "queue":
+            assert on[5] == off[5] == 4, (seed, on, off)

@@ -155,11 +155,12 @@ def _oracle_frames(oracle_det):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", [None, "plain", "small", "sliced"])
+@pytest.mark.parametrize("variant", [None, "plain", "small", "sliced", "queue"])
 def test_frames_equal_the_oracle_with_the_table_on_and_off(oracle_det, variant):
     """plain: the whole-frame march and, for the rays it gives up next to objects, k_rect_trace; small: object steps out of line
     (object_step_impl); sliced (what small opaque frames take by default, forced here for the others): k_rect_march_first / _cont,
-    whose later slices start at a step index read back from HBM."""
+    whose later slices start at a step index read back from HBM; queue: k_rect_march_queue on the opaque whole frames without objects
+    of the Spherical calculator (refracted-opaque-2000 and straight-opaque-2, a frame of two samples), the others by their size."""
     want = _oracle_frames(oracle_det)
     assert want["refracted-translucent-2"][1] > 0 and want["straight-opaque-2"][1] > 0, "the 2-sample frames must have trace points"
     assert want["objects-translucent"][1] > want["refracted-opaque-2000"][1] > 0
