@@ -683,23 +683,27 @@ double shadow_escape_floor(const atmrt_ctx* k, Frame& f, double reach) {
   return std::max(k->tv.skip_above, k->escape.value().from + step);
 }
 
-struct ShadowDownload { // a plane the host asked for (host null: not this one), downloaded inside the call's timed window
+struct Download { // a plane the host asked for (host null, or no bytes: not this one), downloaded inside the call's timed window
   void* host;
   const void* dev;
   size_t bytes;
 };
+
+// prepare_frame(k, f) for a shadow or a sky call; report: the context the caller handed in, which gets a child's error text
+int prepare_frame_for(atmrt_ctx* k, atmrt_ctx* report, Frame* f) {
+  const int rc = prepare_frame(k, f);
+  if (rc && k != report) report->error = k->error;
+  return rc;
+}
 
 // One shadow call around its kernels, for a ShadowJob or a ShadowLightsJob with its source, its m and its planes filled in.
 // k: the context whose device holds the memory and whose setting is used; report: the context the caller handed in.
 // carve_more: what the call carves from d_shadow beside the list and the counters; launch: its uploads and its kernels.
 template <class Job>
 int shadow_call(atmrt_ctx* k, atmrt_ctx* report, double reach, Job& job, const std::function<void(Carve&)>& carve_more,
-                const std::function<int(const Frame&, hipStream_t)>& launch, std::initializer_list<ShadowDownload> downloads, atmrt_shadow_stats_t* stats) {
+                const std::function<int(const Frame&, hipStream_t)>& launch, std::initializer_list<Download> downloads, atmrt_shadow_stats_t* stats) {
   Frame f;
-  if (int rc = prepare_frame(k, &f)) {
-    if (k != report) report->error = k->error;
-    return rc;
-  }
+  if (int rc = prepare_frame_for(k, report, &f)) return rc;
   hipStream_t s = k->stream;
   job.esc_floor = shadow_escape_floor(k, f, reach);
   job.escape = job.esc_floor < INFINITY ? 1 : 0;
@@ -711,8 +715,8 @@ int shadow_call(atmrt_ctx* k, atmrt_ctx* report, double reach, Job& job, const s
   HIP_TRY(report, hipEventRecord(k->ev[EV_SH_MARCHED], s));
   unsigned long long ctr[SH_N] = {};
   HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
-  for (const ShadowDownload& d : downloads)
-    if (d.host) HIP_TRY(report, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
+  for (const Download& d : downloads)
+    if (d.host && d.bytes) HIP_TRY(report, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(report, hipEventRecord(k->ev[EV_SH_END], s));
   HIP_TRY(report, hipStreamSynchronize(s));
   HIP_TRY(report, hipGetLastError());
@@ -989,7 +993,9 @@ extern "C" int atmrt_last_shadow_timings(atmrt_ctx* c, double out[3]) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// sky rays: the true direction of every sky pixel, sun and moon discs (kernels: atmrt_sky.h; the rule: include/atmrt.h)
+// sky rays and sky light: the true direction of every sky pixel, with the light the column per sky ray and the zenith column; the
+// paint calls over them: sun and moon discs, the shade (kernels: atmrt_sky.h; the rules: include/atmrt.h).  A light call is the
+// sky call of the same route with a column plane more; a shade call is the bodies call with a shade and a column more.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -1019,74 +1025,259 @@ int sky_check(atmrt_ctx* c, const char* what, const atmrt_sky_spec_t* spec, doub
   return ATMRT_OK;
 }
 
-struct SkyDownload { // a plane the host asked for (host null: not this one), downloaded inside the call's timed window
-  void* host;
-  const void* dev;
-  size_t bytes;
+// One march call as its entry point hands it on.  spec: the sky spec, null where the caller's spec is NULL; light: the light spec
+// of a frame or planes call of the light (it asks for Z0), else null.  The planes are the caller's, host or device as the route
+// says; column null: plain sky rays.
+struct SkyCall {
+  const char* what;
+  const atmrt_sky_spec_t* spec;
+  const atmrt_sky_light_spec_t* light;
+  double* true_elevation;
+  uint8_t* status;
+  uint32_t* steps;
+  double* column;
+  atmrt_sky_stats_t* stats;
+  double* zenith_column; // where Z0 goes (or null)
 };
+SkyCall sky_call(const char* what, const atmrt_sky_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps, atmrt_sky_stats_t* stats) {
+  return SkyCall{what, spec, nullptr, true_elevation, status, steps, nullptr, stats, nullptr};
+}
+SkyCall sky_light_call(const char* what, const atmrt_sky_light_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps, double* column,
+                       atmrt_sky_stats_t* stats, double* zenith_column) {
+  return SkyCall{what, spec ? &spec->sky : nullptr, spec, true_elevation, status, steps, column, stats, zenith_column};
+}
 
-// One sky march around its kernels, for a SkyJob with its source, its h0 and its planes filled in.  k: the context whose device
-// holds the memory and whose setting is used; report: the context the caller handed in.  upload: the list call's elevations, inside
-// the timed window.  column: the column plane of a "sky light" call (null: plain sky rays); prepared: the frame of a caller that
-// has called prepare_frame(k) already.
-int sky_run(atmrt_ctx* k, atmrt_ctx* report, const atmrt_sky_spec_t& spec, double step, SkyJob& job, const std::function<int(hipStream_t)>& upload,
-            std::initializer_list<SkyDownload> downloads, atmrt_sky_stats_t* stats, double* column = nullptr, const Frame* prepared = nullptr) {
+// sky_check, and what a light spec asks beyond it
+int sky_call_check(atmrt_ctx* c, const SkyCall& a, double h0, double* step) {
+  if (int rc = sky_check(c, a.what, a.spec, h0, step)) return rc;
+  if (!a.light) return ATMRT_OK;
+  if (!std::isfinite(a.light->ref_alt) || !(a.light->ref_alt < a.spec->top)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: ref_alt must be finite and lie below top", a.what);
+  if (!(std::isfinite(a.light->column_dz) && a.light->column_dz >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: column_dz must be finite and not negative", a.what);
+  return ATMRT_OK;
+}
+
+// One sky march around its kernels, for a SkyJob with its source, its h0 and its device planes filled in.  k: the context whose
+// device holds the memory and whose setting is used; report: the context the caller handed in.  column: the device column plane
+// (null: plain sky rays).  upload: the list call's elevations, inside the timed window.  With a light spec, Z0 of k's atmosphere.
+int sky_run(atmrt_ctx* k, atmrt_ctx* report, const SkyCall& a, double step, SkyJob& job, double* column, const std::function<int(hipStream_t)>& upload,
+            std::initializer_list<Download> downloads) {
   Frame f;
-  if (prepared) {
-    f = *prepared;
-  } else if (int rc = prepare_frame(k, &f)) {
-    if (k != report) report->error = k->error;
-    return rc;
+  if (int rc = prepare_frame_for(k, report, &f)) return rc;
+  double z0 = 0.0;
+  if (a.light) {
+    const double dz = a.light->column_dz == 0.0 ? step : a.light->column_dz;
+    if (!sky_zenith_column<true>(k->atm.value().table.table(), a.light->ref_alt, a.spec->top, dz, &z0))
+      return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the zenith column from %g m to %g m has more than 1048575 nodes of %g m", a.what, a.light->ref_alt, a.spec->top, dz);
   }
   hipStream_t s = k->stream;
-  job.step = step, job.top = spec.top, job.floor = spec.floor, job.m = spec.m;
+  job.step = step, job.top = a.spec->top, job.floor = a.spec->floor, job.m = a.spec->m;
   job.reverse = sky_reverse_enabled() ? 1 : 0;
   HIP_TRY(report, reserve_carved(k->d_sky, [&](Carve& cv) {
             if (job.hit_count) cv(job.list, job.n_pixels * sizeof(uint32_t));
             cv(job.ctr, SKY_N * sizeof(unsigned long long));
           }));
   HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], s));
-  if (int rc = upload(s)) return rc;
-  if (column) launch_sky_light_march(f, SkyLightJob{job, column}, s, k->ev[EV_SKY_COMPACTED]); // "sky light": the march with the column
-  else launch_sky_march(f, job, s, k->ev[EV_SKY_COMPACTED]);
+  if (upload)
+    if (int rc = upload(s)) return rc;
+  launch_sky_march(f, job, column, s, k->ev[EV_SKY_COMPACTED]);
   HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_MARCHED], s));
   unsigned long long ctr[SKY_N] = {};
   HIP_TRY(report, hipMemcpyAsync(ctr, job.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
-  for (const SkyDownload& d : downloads)
+  for (const Download& d : downloads)
     if (d.host && d.bytes) HIP_TRY(report, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_END], s));
   HIP_TRY(report, hipStreamSynchronize(s));
   HIP_TRY(report, hipGetLastError());
   HIP_TRY(report, event_intervals(k->ev + EV_SKY_BEGIN, 3, report->sky_timings));
-  if (stats) {
-    stats->none = job.hit_count ? job.n_pixels - ctr[SKY_LIST] : 0;
-    stats->exit = ctr[SKY_EXIT], stats->ground = ctr[SKY_GROUND], stats->inside = ctr[SKY_INSIDE], stats->lost = ctr[SKY_LOST];
-    stats->integrated_steps = ctr[SKY_STEPS];
+  if (a.stats) {
+    a.stats->none = job.hit_count ? job.n_pixels - ctr[SKY_LIST] : 0;
+    a.stats->exit = ctr[SKY_EXIT], a.stats->ground = ctr[SKY_GROUND], a.stats->inside = ctr[SKY_INSIDE], a.stats->lost = ctr[SKY_LOST];
+    a.stats->integrated_steps = ctr[SKY_STEPS];
   }
+  if (a.light && a.zenith_column) *a.zenith_column = z0;
   return ATMRT_OK;
+}
+
+// The list call: n rays from h0 at the caller's elevations, staged like the host planes of the frame call.  light: with the
+// column (a.column: the host's, [n]).
+int sky_list_call(atmrt_ctx* c, const SkyCall& a, bool light, double h0, size_t n, const double* elevation_deg, atmrt_sky_ray_t* records) {
+  if (n > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n must lie in [0, 2^32 - 1]", a.what);
+  double step = 0.0;
+  if (int rc = sky_call_check(c, a, h0, &step)) return rc;
+  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
+  HIP_TRY(c, hipSetDevice(k->device));
+  SkyJob job{};
+  job.n_pixels = n, job.h0 = h0;
+  double *d_elev = nullptr, *d_true = nullptr, *d_column = nullptr;
+  uint8_t* d_status = nullptr;
+  uint32_t* d_steps = nullptr;
+  HIP_TRY(c, reserve_carved(k->d_io, [&](Carve& cv) { cv(d_elev, n * 8), cv(d_true, n * 8); if (light) cv(d_column, n * 8); cv(d_steps, n * 4), cv(d_status, n); }));
+  job.elevation_angle = d_elev, job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
+  std::vector<double> true_elevation(n);
+  std::vector<uint8_t> status(n);
+  std::vector<uint32_t> steps(n);
+  int rc = sky_run(k, c, a, step, job, d_column,
+                   [&](hipStream_t s) -> int {
+                     if (n) HIP_TRY(c, hipMemcpyAsync(d_elev, elevation_deg, n * 8, hipMemcpyHostToDevice, s));
+                     return ATMRT_OK;
+                   },
+                   {{true_elevation.data(), d_true, n * 8}, {status.data(), d_status, n}, {steps.data(), d_steps, n * 4}, {a.column, d_column, n * 8}});
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) records[i] = atmrt_sky_ray_t{(int32_t)status[i], steps[i], true_elevation[i]};
+  return ATMRT_OK;
+}
+
+// The frame call: the sky pixels of c's last frame.  host: a's planes are the host's, staged in d_io and downloaded inside the
+// timed window; else they are device planes and the march writes them.
+int sky_frame_call(atmrt_ctx* c, const SkyCall& a, const char* on_multi, bool host) {
+  double step = 0.0;
+  if (int rc = sky_call_check(c, a, 0.0, &step)) return rc;
+  if (int rc = frame_state_check(c, a.what, on_multi)) return rc;
+  const size_t n = c->last.npx;
+  SkyJob job{};
+  job.n_pixels = n, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
+  job.alt = c->d_alt.as<double>();
+  double *d_true = a.true_elevation, *d_column = a.column;
+  uint32_t* d_steps = a.steps;
+  uint8_t* d_status = a.status;
+  if (host) {
+    HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+    HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { // what is not asked for takes no room
+              k(d_true, n * 8);
+              if (a.column) k(d_column, n * 8);
+              if (a.steps) k(d_steps, n * 4);
+              k(d_status, n);
+            }));
+  }
+  job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
+  const SkyCall to = host ? a : SkyCall{};
+  return sky_run(c, c, a, step, job, d_column, nullptr,
+                 {{to.true_elevation, d_true, n * 8}, {to.status, d_status, n}, {to.steps, d_steps, n * 4}, {to.column, d_column, n * 8}});
+}
+
+// The gathered-planes call: the caller's device planes, on the context (a child of a multi context) whose device holds them.
+int sky_planes_call(atmrt_ctx* c, const SkyCall& a, double h0, size_t n_pixels, const uint32_t* hit_count, const double* elevation_angle) {
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must lie in [1, 2^32 - 1]", a.what);
+  double step = 0.0;
+  if (int rc = sky_call_check(c, a, h0, &step)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, a.status, "status_device", &k)) return rc;
+  HIP_TRY(c, hipSetDevice(k->device));
+  SkyJob job{};
+  job.n_pixels = n_pixels, job.hit_count = hit_count, job.elevation_angle = elevation_angle, job.h0 = h0;
+  job.true_elevation = a.true_elevation, job.status = a.status, job.steps = a.steps;
+  return sky_run(k, c, a, step, job, a.column, nullptr, {});
 }
 
 const char* const SKY_ON_MULTI = "has no frame of its own: sky rays work on the gathered planes through atmrt_sky_directions_planes_device and atmrt_sky_bodies_planes_device";
+const char* const SKY_LIGHT_ON_MULTI = "has no frame of its own: sky light works on the gathered planes through atmrt_sky_light_planes_device and atmrt_sky_shade_planes_device";
 
-// the bodies of a call, checked and made into what the kernel holds
-int sky_bodies_check(atmrt_ctx* c, const char* what, const atmrt_sky_body_t* bodies, uint32_t n_bodies, SkyBodiesJob& job) {
-  if (n_bodies > SKY_BODIES_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: at most 32 bodies, not %u", what, n_bodies);
-  if (n_bodies && !bodies) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: bodies is NULL", what);
-  job.n_bodies = n_bodies;
-  for (uint32_t k = 0; k < n_bodies; k++) {
-    if (!sky_body_valid(bodies[k]))
-      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: body %u needs finite angles and a radius strictly between 0 and 90 degrees", what, k);
-    job.bodies[k] = sky_body_dev(bodies[k]);
-    memcpy(job.colour[k], bodies[k].rgb, 3);
+// The paint calls, over the job of their kernel: SkyBodiesJob (the bodies' colours over an optional image) or SkyShadeJob (the
+// shade and the column; the image is required, and only this one is timed: sky_shade_ms).
+template <class Job>
+constexpr bool SKY_SHADES = std::is_same<Job, SkyShadeJob>::value;
+
+struct SkyPaintPlanes { // host or device, as the route says
+  const double* true_elevation;
+  const uint8_t* status;
+  const double* column; // the shade only
+  uint8_t* body;
+  uint8_t* rgb;
+};
+
+// the shade (the shade call only) and the bodies of a call, checked and made into what the kernel holds
+template <class Job>
+int sky_paint_check(atmrt_ctx* c, const char* what, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, Job& job) {
+  if constexpr (SKY_SHADES<Job>) {
+    if (!shade) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: shade is NULL", what);
+    if (!sky_shade_valid(*shade))
+      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the shade needs a finite positive zenith_column, finite tau and exposure that are not negative, and limb in [0, 1]", what);
   }
+  uint32_t bad = 0;
+  switch (sky_bodies_dev(bodies, n_bodies, job.bodies, &bad)) {
+    case SKY_BODIES_TOO_MANY: return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: at most 32 bodies, not %u", what, n_bodies);
+    case SKY_BODIES_NULL: return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: bodies is NULL", what);
+    case SKY_BODIES_BAD: return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: body %u needs finite angles and a radius strictly between 0 and 90 degrees", what, bad);
+    case SKY_BODIES_OK: break;
+  }
+  job.n_bodies = n_bodies;
+  if constexpr (SKY_SHADES<Job>) job.shade = sky_shade_dev(*shade, bodies, n_bodies);
+  else
+    for (uint32_t k = 0; k < n_bodies; k++) memcpy(job.colour[k], bodies[k].rgb, 3);
   return ATMRT_OK;
 }
 
-int sky_bodies_run(atmrt_ctx* k, atmrt_ctx* report, const SkyBodiesJob& job) {
+template <class Job>
+int sky_paint_run(atmrt_ctx* k, atmrt_ctx* report, Job& job, size_t n_pixels, const double* azimuth, const SkyPaintPlanes& dev) {
+  job.n_pixels = n_pixels, job.azimuth = azimuth;
+  job.true_elevation = dev.true_elevation, job.status = dev.status, job.body = dev.body, job.rgb = dev.rgb;
   HIP_TRY(report, hipSetDevice(k->device));
-  launch_sky_bodies(job, k->stream);
+  if constexpr (SKY_SHADES<Job>) {
+    job.column = dev.column;
+    HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], k->stream));
+    launch_sky_shade(job, k->stream);
+    HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_COMPACTED], k->stream));
+  } else {
+    launch_sky_bodies(job, k->stream);
+  }
   HIP_TRY(report, hipStreamSynchronize(k->stream));
   HIP_TRY(report, hipGetLastError());
+  if constexpr (SKY_SHADES<Job>) HIP_TRY(report, event_intervals(k->ev + EV_SKY_BEGIN, 1, &report->sky_shade_ms));
+  return ATMRT_OK;
+}
+
+// The frame call over c's last frame.  host: the planes are the host's, staged in d_io around the kernel (rgb only where given).
+template <class Job>
+int sky_paint_frame(atmrt_ctx* c, const char* what, const char* on_multi, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies,
+                    const SkyPaintPlanes& a, bool host) {
+  Job job{};
+  if (int rc = sky_paint_check(c, what, shade, bodies, n_bodies, job)) return rc;
+  if (int rc = frame_state_check(c, what, on_multi)) return rc;
+  const size_t n = c->last.npx;
+  if (!host) return sky_paint_run(c, c, job, n, c->last.dense.azimuth, a);
+  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
+  double *d_true = nullptr, *d_column = nullptr;
+  uint8_t *d_status = nullptr, *d_body = nullptr, *d_rgb = nullptr;
+  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) {
+            k(d_true, n * 8);
+            if (a.column) k(d_column, n * 8);
+            k(d_status, n), k(d_body, n);
+            if (a.rgb) k(d_rgb, 3 * n);
+          }));
+  HIP_TRY(c, hipMemcpy(d_true, a.true_elevation, n * 8, hipMemcpyHostToDevice));
+  if (a.column) HIP_TRY(c, hipMemcpy(d_column, a.column, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_status, a.status, n, hipMemcpyHostToDevice));
+  if (a.rgb) HIP_TRY(c, hipMemcpy(d_rgb, a.rgb, 3 * n, hipMemcpyHostToDevice));
+  if (int rc = sky_paint_run(c, c, job, n, c->last.dense.azimuth, SkyPaintPlanes{d_true, d_status, d_column, d_body, d_rgb})) return rc;
+  HIP_TRY(c, hipMemcpy(a.body, d_body, n, hipMemcpyDeviceToHost));
+  if (a.rgb) HIP_TRY(c, hipMemcpy(a.rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
+  return ATMRT_OK;
+}
+
+// The gathered-planes call: the caller's device planes, on the context whose device holds them.
+template <class Job>
+int sky_paint_planes(atmrt_ctx* c, const char* what, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, size_t n_pixels,
+                     const double* azimuth, const SkyPaintPlanes& a) {
+  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must lie in [1, 2^32 - 1]", what);
+  Job job{};
+  if (int rc = sky_paint_check(c, what, shade, bodies, n_bodies, job)) return rc;
+  atmrt_ctx* k = nullptr;
+  if (int rc = planes_context(c, a.body, "body_device", &k)) return rc;
+  return sky_paint_run(k, c, job, n_pixels, azimuth, a);
+}
+
+// the serial march of the two host functions (no device): *out, and with `column` the light's column
+int sky_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays, const atmrt_sky_spec_t* spec,
+                 double h0, double elevation_deg, atmrt_sky_ray_t* out, double* column) {
+  if (!atmosphere || !earth || !spec || !out) return ATMRT_ERR_INVALID_ARGUMENT;
+  if (sky_spec_check(*spec, h0) || !(spec->step > 0.0)) return ATMRT_ERR_INVALID_ARGUMENT;
+  Earth e;
+  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
+  AtmTableBuf buf;
+  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
+  const bool sph = e.spherical != 0, straight = straight_rays != 0;
+  if (column) *out = sky_march_one<true, true>(buf.table(), sph, e.shape_radius, straight, spec->step, spec->top, spec->floor, spec->m, h0, elevation_deg, column);
+  else *out = sky_march_one<true, false>(buf.table(), sph, e.shape_radius, straight, spec->step, spec->top, spec->floor, spec->m, h0, elevation_deg);
   return ATMRT_OK;
 }
 
@@ -1094,23 +1285,13 @@ int sky_bodies_run(atmrt_ctx* k, atmrt_ctx* report, const SkyBodiesJob& job) {
 
 extern "C" int atmrt_sky_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays,
                                   const atmrt_sky_spec_t* spec, double h0, double elevation_deg, atmrt_sky_ray_t* out) {
-  if (!atmosphere || !earth || !spec || !out) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (sky_spec_check(*spec, h0) || !(spec->step > 0.0)) return ATMRT_ERR_INVALID_ARGUMENT;
-  Earth e;
-  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
-  AtmTableBuf buf;
-  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
-  *out = sky_march_one<true>(buf.table(), e.spherical != 0, e.shape_radius, straight_rays != 0, spec->step, spec->top, spec->floor, spec->m, h0, elevation_deg);
-  return ATMRT_OK;
+  return sky_ray_host(atmosphere, wavelength, earth, straight_rays, spec, h0, elevation_deg, out, nullptr);
 }
 
 extern "C" int atmrt_sky_body_host(const atmrt_sky_body_t* bodies, uint32_t n_bodies, double azimuth_deg, double true_elevation_deg, uint32_t* body) {
-  if (!body || (n_bodies && !bodies) || n_bodies > SKY_BODIES_MAX) return ATMRT_ERR_INVALID_ARGUMENT;
   SkyBodyDev dev[SKY_BODIES_MAX];
-  for (uint32_t k = 0; k < n_bodies; k++) {
-    if (!sky_body_valid(bodies[k])) return ATMRT_ERR_INVALID_ARGUMENT;
-    dev[k] = sky_body_dev(bodies[k]);
-  }
+  uint32_t bad = 0;
+  if (!body || sky_bodies_dev(bodies, n_bodies, dev, &bad)) return ATMRT_ERR_INVALID_ARGUMENT;
   *body = sky_body_of(dev, n_bodies, azimuth_deg, true_elevation_deg);
   return ATMRT_OK;
 }
@@ -1119,65 +1300,21 @@ extern "C" int atmrt_sky_rays(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double
                               atmrt_sky_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (n && (!elevation_deg || !records)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_rays: elevation_deg or records is NULL");
-  if (n > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_rays: n must lie in [0, 2^32 - 1]");
-  double step = 0.0;
-  if (int rc = sky_check(c, "atmrt_sky_rays", spec, h0, &step)) return rc;
-  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
-  HIP_TRY(c, hipSetDevice(k->device));
-  SkyJob job{};
-  job.n_pixels = n, job.h0 = h0;
-  double *d_elev = nullptr, *d_true = nullptr; // the call's planes: staged like the host planes of atmrt_sky_directions
-  uint8_t* d_status = nullptr;
-  uint32_t* d_steps = nullptr;
-  HIP_TRY(c, reserve_carved(k->d_io, [&](Carve& cv) { cv(d_elev, n * 8), cv(d_true, n * 8), cv(d_steps, n * 4), cv(d_status, n); }));
-  job.elevation_angle = d_elev, job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
-  std::vector<double> true_elevation(n);
-  std::vector<uint8_t> status(n);
-  std::vector<uint32_t> steps(n);
-  int rc = sky_run(k, c, *spec, step, job,
-                   [&](hipStream_t s) -> int {
-                     if (n) HIP_TRY(c, hipMemcpyAsync(d_elev, elevation_deg, n * 8, hipMemcpyHostToDevice, s));
-                     return ATMRT_OK;
-                   },
-                   {{true_elevation.data(), d_true, n * 8}, {status.data(), d_status, n}, {steps.data(), d_steps, n * 4}}, stats);
-  if (rc) return rc;
-  for (size_t i = 0; i < n; i++) records[i] = atmrt_sky_ray_t{(int32_t)status[i], steps[i], true_elevation[i]};
-  return ATMRT_OK;
+  return sky_list_call(c, sky_call("atmrt_sky_rays", spec, nullptr, nullptr, nullptr, stats), false, h0, n, elevation_deg, records);
 }
 
 extern "C" int atmrt_sky_directions_device(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double* true_elevation_device, uint8_t* status_device,
                                            uint32_t* steps_device, atmrt_sky_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation_device || !status_device) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions: true_elevation or status is NULL");
-  double step = 0.0;
-  if (int rc = sky_check(c, "atmrt_sky_directions", spec, 0.0, &step)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_directions", SKY_ON_MULTI)) return rc;
-  SkyJob job{};
-  job.n_pixels = c->last.npx, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
-  job.alt = c->d_alt.as<double>();
-  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
-  return sky_run(c, c, *spec, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats);
+  return sky_frame_call(c, sky_call("atmrt_sky_directions", spec, true_elevation_device, status_device, steps_device, stats), SKY_ON_MULTI, false);
 }
 
 extern "C" int atmrt_sky_directions(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps,
                                     atmrt_sky_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation || !status) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions: true_elevation or status is NULL");
-  double step = 0.0;
-  if (int rc = sky_check(c, "atmrt_sky_directions", spec, 0.0, &step)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_directions", SKY_ON_MULTI)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n = c->last.npx;
-  double* d_true = nullptr;
-  uint32_t* d_steps = nullptr; // what is not asked for takes no room
-  uint8_t* d_status = nullptr;
-  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8); if (steps) k(d_steps, n * 4); k(d_status, n); }));
-  SkyJob job{};
-  job.n_pixels = n, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
-  job.alt = c->d_alt.as<double>();
-  job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
-  return sky_run(c, c, *spec, step, job, [](hipStream_t) -> int { return ATMRT_OK; },
-                 {{true_elevation, d_true, n * 8}, {status, d_status, n}, {steps, d_steps, n * 4}}, stats);
+  return sky_frame_call(c, sky_call("atmrt_sky_directions", spec, true_elevation, status, steps, stats), SKY_ON_MULTI, true);
 }
 
 extern "C" int atmrt_sky_directions_planes_device(atmrt_ctx* c, const atmrt_sky_spec_t* spec, double h0, size_t n_pixels, const uint32_t* hit_count,
@@ -1186,51 +1323,23 @@ extern "C" int atmrt_sky_directions_planes_device(atmrt_ctx* c, const atmrt_sky_
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!hit_count || !elevation_angle || !true_elevation_device || !status_device)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions_planes_device: a plane is NULL");
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_directions_planes_device: n_pixels must lie in [1, 2^32 - 1]");
-  double step = 0.0;
-  if (int rc = sky_check(c, "atmrt_sky_directions_planes_device", spec, h0, &step)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, status_device, "status_device", &k)) return rc;
-  HIP_TRY(c, hipSetDevice(k->device));
-  SkyJob job{};
-  job.n_pixels = n_pixels, job.hit_count = hit_count, job.elevation_angle = elevation_angle, job.h0 = h0;
-  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
-  return sky_run(k, c, *spec, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats);
+  return sky_planes_call(c, sky_call("atmrt_sky_directions_planes_device", spec, true_elevation_device, status_device, steps_device, stats), h0, n_pixels,
+                         hit_count, elevation_angle);
 }
 
 extern "C" int atmrt_sky_bodies_device(atmrt_ctx* c, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation_device,
                                        const uint8_t* status_device, uint8_t* body_device, uint8_t* rgb_device) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation_device || !status_device || !body_device) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies: a plane is NULL");
-  SkyBodiesJob job{};
-  if (int rc = sky_bodies_check(c, "atmrt_sky_bodies", bodies, n_bodies, job)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_bodies", SKY_ON_MULTI)) return rc;
-  job.n_pixels = c->last.npx, job.azimuth = c->last.dense.azimuth;
-  job.true_elevation = true_elevation_device, job.status = status_device, job.body = body_device, job.rgb = rgb_device;
-  return sky_bodies_run(c, c, job);
+  return sky_paint_frame<SkyBodiesJob>(c, "atmrt_sky_bodies", SKY_ON_MULTI, nullptr, bodies, n_bodies,
+                                       SkyPaintPlanes{true_elevation_device, status_device, nullptr, body_device, rgb_device}, false);
 }
 
 extern "C" int atmrt_sky_bodies(atmrt_ctx* c, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation, const uint8_t* status,
                                 uint8_t* body, uint8_t* rgb) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation || !status || !body) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies: a plane is NULL");
-  SkyBodiesJob job{};
-  if (int rc = sky_bodies_check(c, "atmrt_sky_bodies", bodies, n_bodies, job)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_bodies", SKY_ON_MULTI)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n = c->last.npx;
-  double* d_true = nullptr;
-  uint8_t *d_status = nullptr, *d_body = nullptr, *d_rgb = nullptr;
-  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8), k(d_status, n), k(d_body, n); if (rgb) k(d_rgb, 3 * n); }));
-  HIP_TRY(c, hipMemcpy(d_true, true_elevation, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_status, status, n, hipMemcpyHostToDevice));
-  if (rgb) HIP_TRY(c, hipMemcpy(d_rgb, rgb, 3 * n, hipMemcpyHostToDevice));
-  job.n_pixels = n, job.azimuth = c->last.dense.azimuth;
-  job.true_elevation = d_true, job.status = d_status, job.body = d_body, job.rgb = d_rgb;
-  if (int rc = sky_bodies_run(c, c, job)) return rc;
-  HIP_TRY(c, hipMemcpy(body, d_body, n, hipMemcpyDeviceToHost));
-  if (rgb) HIP_TRY(c, hipMemcpy(rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
-  return ATMRT_OK;
+  return sky_paint_frame<SkyBodiesJob>(c, "atmrt_sky_bodies", SKY_ON_MULTI, nullptr, bodies, n_bodies, SkyPaintPlanes{true_elevation, status, nullptr, body, rgb}, true);
 }
 
 extern "C" int atmrt_sky_bodies_planes_device(atmrt_ctx* c, const atmrt_sky_body_t* bodies, uint32_t n_bodies, size_t n_pixels, const double* azimuth,
@@ -1239,14 +1348,8 @@ extern "C" int atmrt_sky_bodies_planes_device(atmrt_ctx* c, const atmrt_sky_body
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!azimuth || !true_elevation_device || !status_device || !body_device)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies_planes_device: a plane is NULL");
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_bodies_planes_device: n_pixels must lie in [1, 2^32 - 1]");
-  SkyBodiesJob job{};
-  if (int rc = sky_bodies_check(c, "atmrt_sky_bodies_planes_device", bodies, n_bodies, job)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, body_device, "body_device", &k)) return rc;
-  job.n_pixels = n_pixels, job.azimuth = azimuth;
-  job.true_elevation = true_elevation_device, job.status = status_device, job.body = body_device, job.rgb = rgb_device;
-  return sky_bodies_run(k, c, job);
+  return sky_paint_planes<SkyBodiesJob>(c, "atmrt_sky_bodies_planes_device", nullptr, bodies, n_bodies, n_pixels, azimuth,
+                                        SkyPaintPlanes{true_elevation_device, status_device, nullptr, body_device, rgb_device});
 }
 
 extern "C" int atmrt_last_sky_timings(atmrt_ctx* c, double out[3]) {
@@ -1255,63 +1358,7 @@ extern "C" int atmrt_last_sky_timings(atmrt_ctx* c, double out[3]) {
   return ATMRT_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// sky light: the column per sky ray, the zenith column, the shade (kernels: atmrt_sky.h; the rule: include/atmrt.h)
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-const char* const SKY_LIGHT_ON_MULTI = "has no frame of its own: sky light works on the gathered planes through atmrt_sky_light_planes_device and atmrt_sky_shade_planes_device";
-
-// what the light calls on a context ask beyond sky_check; *step: the step of the march
-int sky_light_check(atmrt_ctx* c, const char* what, const atmrt_sky_light_spec_t* spec, double h0, double* step) {
-  if (!spec) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: spec is NULL", what);
-  if (int rc = sky_check(c, what, &spec->sky, h0, step)) return rc;
-  if (!std::isfinite(spec->ref_alt) || !(spec->ref_alt < spec->sky.top)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: ref_alt must be finite and lie below top", what);
-  if (!(std::isfinite(spec->column_dz) && spec->column_dz >= 0.0)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: column_dz must be finite and not negative", what);
-  return ATMRT_OK;
-}
-
-// the frame of k's setting and Z0 of its atmosphere
-int sky_light_prepare(atmrt_ctx* k, atmrt_ctx* report, const char* what, const atmrt_sky_light_spec_t& spec, double step, Frame* f, double* z0) {
-  if (int rc = prepare_frame(k, f)) {
-    if (k != report) report->error = k->error;
-    return rc;
-  }
-  const double dz = spec.column_dz == 0.0 ? step : spec.column_dz;
-  if (!sky_zenith_column<true>(k->atm.value().table.table(), spec.ref_alt, spec.sky.top, dz, z0))
-    return report->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the zenith column from %g m to %g m has more than 1048575 nodes of %g m", what, spec.ref_alt, spec.sky.top, dz);
-  return ATMRT_OK;
-}
-
-// the shade and the bodies of a call, checked and made into what the kernel holds
-int sky_shade_check(atmrt_ctx* c, const char* what, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, SkyShadeJob& job) {
-  if (!shade) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: shade is NULL", what);
-  if (!sky_shade_valid(*shade))
-    return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: the shade needs a finite positive zenith_column, finite tau and exposure that are not negative, and limb in [0, 1]", what);
-  if (n_bodies > SKY_BODIES_MAX) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: at most 32 bodies, not %u", what, n_bodies);
-  if (n_bodies && !bodies) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: bodies is NULL", what);
-  job.n_bodies = n_bodies;
-  for (uint32_t k = 0; k < n_bodies; k++) {
-    if (!sky_body_valid(bodies[k]))
-      return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "%s: body %u needs finite angles and a radius strictly between 0 and 90 degrees", what, k);
-    job.bodies[k] = sky_body_dev(bodies[k]);
-  }
-  job.shade = sky_shade_dev(*shade, bodies, n_bodies);
-  return ATMRT_OK;
-}
-
-int sky_shade_run(atmrt_ctx* k, atmrt_ctx* report, const SkyShadeJob& job) {
-  HIP_TRY(report, hipSetDevice(k->device));
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_BEGIN], k->stream));
-  launch_sky_shade(job, k->stream);
-  HIP_TRY(report, hipEventRecord(k->ev[EV_SKY_COMPACTED], k->stream));
-  HIP_TRY(report, hipStreamSynchronize(k->stream));
-  HIP_TRY(report, hipGetLastError());
-  HIP_TRY(report, event_intervals(k->ev + EV_SKY_BEGIN, 1, &report->sky_shade_ms));
-  return ATMRT_OK;
-}
-
-} // namespace
+// sky light: the entry points
 
 extern "C" int atmrt_sky_zenith_column_host(const atmrt_atmosphere_t* atmosphere, double wavelength, double ref_alt, double top, double dz,
                                             double* zenith_column) {
@@ -1323,25 +1370,15 @@ extern "C" int atmrt_sky_zenith_column_host(const atmrt_atmosphere_t* atmosphere
 
 extern "C" int atmrt_sky_light_ray_host(const atmrt_atmosphere_t* atmosphere, double wavelength, const atmrt_earth_model_t* earth, int32_t straight_rays,
                                         const atmrt_sky_spec_t* spec, double h0, double elevation_deg, atmrt_sky_ray_t* out, double* column) {
-  if (!atmosphere || !earth || !spec || !out || !column) return ATMRT_ERR_INVALID_ARGUMENT;
-  if (sky_spec_check(*spec, h0) || !(spec->step > 0.0)) return ATMRT_ERR_INVALID_ARGUMENT;
-  Earth e;
-  if (earth_resolve(*earth, e)) return ATMRT_ERR_INVALID_ARGUMENT;
-  AtmTableBuf buf;
-  if (atm_compile(*atmosphere, wavelength, buf)) return ATMRT_ERR_INVALID_ARGUMENT;
-  *out = sky_light_march_one<true>(buf.table(), e.spherical != 0, e.shape_radius, straight_rays != 0, spec->step, spec->top, spec->floor, spec->m, h0,
-                                   elevation_deg, column);
-  return ATMRT_OK;
+  if (!column) return ATMRT_ERR_INVALID_ARGUMENT;
+  return sky_ray_host(atmosphere, wavelength, earth, straight_rays, spec, h0, elevation_deg, out, column);
 }
 
 extern "C" int atmrt_sky_shade_host(const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, double azimuth_deg,
                                     double true_elevation_deg, double column, uint32_t* body, uint8_t* rgb) {
-  if (!shade || !body || !rgb || (n_bodies && !bodies) || n_bodies > SKY_BODIES_MAX || !sky_shade_valid(*shade)) return ATMRT_ERR_INVALID_ARGUMENT;
   SkyBodyDev dev[SKY_BODIES_MAX];
-  for (uint32_t k = 0; k < n_bodies; k++) {
-    if (!sky_body_valid(bodies[k])) return ATMRT_ERR_INVALID_ARGUMENT;
-    dev[k] = sky_body_dev(bodies[k]);
-  }
+  uint32_t bad = 0;
+  if (!shade || !body || !rgb || !sky_shade_valid(*shade) || sky_bodies_dev(bodies, n_bodies, dev, &bad)) return ATMRT_ERR_INVALID_ARGUMENT;
   const SkyShadeDev sh = sky_shade_dev(*shade, bodies, n_bodies);
   *body = sky_shade_pixel(sh, dev, n_bodies, azimuth_deg, true_elevation_deg, column, rgb);
   return ATMRT_OK;
@@ -1351,75 +1388,24 @@ extern "C" int atmrt_sky_light_rays(atmrt_ctx* c, const atmrt_sky_spec_t* spec, 
                                     double* column, atmrt_sky_stats_t* stats) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (n && (!elevation_deg || !records || !column)) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_rays: elevation_deg, records or column is NULL");
-  if (n > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_rays: n must lie in [0, 2^32 - 1]");
-  double step = 0.0;
-  if (int rc = sky_check(c, "atmrt_sky_light_rays", spec, h0, &step)) return rc;
-  atmrt_ctx* k = c->multi ? multi_child(c, 0) : c;
-  HIP_TRY(c, hipSetDevice(k->device));
-  SkyJob job{};
-  job.n_pixels = n, job.h0 = h0;
-  double *d_elev = nullptr, *d_true = nullptr, *d_column = nullptr;
-  uint8_t* d_status = nullptr;
-  uint32_t* d_steps = nullptr;
-  HIP_TRY(c, reserve_carved(k->d_io, [&](Carve& cv) { cv(d_elev, n * 8), cv(d_true, n * 8), cv(d_column, n * 8), cv(d_steps, n * 4), cv(d_status, n); }));
-  job.elevation_angle = d_elev, job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
-  std::vector<double> true_elevation(n);
-  std::vector<uint8_t> status(n);
-  std::vector<uint32_t> steps(n);
-  int rc = sky_run(k, c, *spec, step, job,
-                   [&](hipStream_t s) -> int {
-                     if (n) HIP_TRY(c, hipMemcpyAsync(d_elev, elevation_deg, n * 8, hipMemcpyHostToDevice, s));
-                     return ATMRT_OK;
-                   },
-                   {{true_elevation.data(), d_true, n * 8}, {status.data(), d_status, n}, {steps.data(), d_steps, n * 4}, {column, d_column, n * 8}}, stats,
-                   d_column);
-  if (rc) return rc;
-  for (size_t i = 0; i < n; i++) records[i] = atmrt_sky_ray_t{(int32_t)status[i], steps[i], true_elevation[i]};
-  return ATMRT_OK;
+  SkyCall a = sky_call("atmrt_sky_light_rays", spec, nullptr, nullptr, nullptr, stats);
+  a.column = column;
+  return sky_list_call(c, a, true, h0, n, elevation_deg, records);
 }
 
 extern "C" int atmrt_sky_light_device(atmrt_ctx* c, const atmrt_sky_light_spec_t* spec, double* true_elevation_device, uint8_t* status_device,
                                       uint32_t* steps_device, double* column_device, atmrt_sky_stats_t* stats, double* zenith_column) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation_device || !status_device || !column_device) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light: true_elevation, status or column is NULL");
-  double step = 0.0, z0 = 0.0;
-  if (int rc = sky_light_check(c, "atmrt_sky_light", spec, 0.0, &step)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_light", SKY_LIGHT_ON_MULTI)) return rc;
-  Frame f;
-  if (int rc = sky_light_prepare(c, c, "atmrt_sky_light", *spec, step, &f, &z0)) return rc;
-  SkyJob job{};
-  job.n_pixels = c->last.npx, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
-  job.alt = c->d_alt.as<double>();
-  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
-  if (int rc = sky_run(c, c, spec->sky, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats, column_device, &f)) return rc;
-  if (zenith_column) *zenith_column = z0;
-  return ATMRT_OK;
+  return sky_frame_call(c, sky_light_call("atmrt_sky_light", spec, true_elevation_device, status_device, steps_device, column_device, stats, zenith_column),
+                        SKY_LIGHT_ON_MULTI, false);
 }
 
 extern "C" int atmrt_sky_light(atmrt_ctx* c, const atmrt_sky_light_spec_t* spec, double* true_elevation, uint8_t* status, uint32_t* steps, double* column,
                                atmrt_sky_stats_t* stats, double* zenith_column) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation || !status || !column) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light: true_elevation, status or column is NULL");
-  double step = 0.0, z0 = 0.0;
-  if (int rc = sky_light_check(c, "atmrt_sky_light", spec, 0.0, &step)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_light", SKY_LIGHT_ON_MULTI)) return rc;
-  Frame f;
-  if (int rc = sky_light_prepare(c, c, "atmrt_sky_light", *spec, step, &f, &z0)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n = c->last.npx;
-  double *d_true = nullptr, *d_column = nullptr;
-  uint32_t* d_steps = nullptr; // what is not asked for takes no room
-  uint8_t* d_status = nullptr;
-  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8), k(d_column, n * 8); if (steps) k(d_steps, n * 4); k(d_status, n); }));
-  SkyJob job{};
-  job.n_pixels = n, job.hit_count = c->last.dense.hit_count, job.elevation_angle = c->last.dense.elevation_angle;
-  job.alt = c->d_alt.as<double>();
-  job.true_elevation = d_true, job.status = d_status, job.steps = d_steps;
-  if (int rc = sky_run(c, c, spec->sky, step, job, [](hipStream_t) -> int { return ATMRT_OK; },
-                       {{true_elevation, d_true, n * 8}, {status, d_status, n}, {steps, d_steps, n * 4}, {column, d_column, n * 8}}, stats, d_column, &f))
-    return rc;
-  if (zenith_column) *zenith_column = z0;
-  return ATMRT_OK;
+  return sky_frame_call(c, sky_light_call("atmrt_sky_light", spec, true_elevation, status, steps, column, stats, zenith_column), SKY_LIGHT_ON_MULTI, true);
 }
 
 extern "C" int atmrt_sky_light_planes_device(atmrt_ctx* c, const atmrt_sky_light_spec_t* spec, double h0, size_t n_pixels, const uint32_t* hit_count,
@@ -1428,20 +1414,9 @@ extern "C" int atmrt_sky_light_planes_device(atmrt_ctx* c, const atmrt_sky_light
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!hit_count || !elevation_angle || !true_elevation_device || !status_device || !column_device)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_planes_device: a plane is NULL");
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_light_planes_device: n_pixels must lie in [1, 2^32 - 1]");
-  double step = 0.0, z0 = 0.0;
-  if (int rc = sky_light_check(c, "atmrt_sky_light_planes_device", spec, h0, &step)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, status_device, "status_device", &k)) return rc;
-  HIP_TRY(c, hipSetDevice(k->device));
-  Frame f;
-  if (int rc = sky_light_prepare(k, c, "atmrt_sky_light_planes_device", *spec, step, &f, &z0)) return rc;
-  SkyJob job{};
-  job.n_pixels = n_pixels, job.hit_count = hit_count, job.elevation_angle = elevation_angle, job.h0 = h0;
-  job.true_elevation = true_elevation_device, job.status = status_device, job.steps = steps_device;
-  if (int rc = sky_run(k, c, spec->sky, step, job, [](hipStream_t) -> int { return ATMRT_OK; }, {}, stats, column_device, &f)) return rc;
-  if (zenith_column) *zenith_column = z0;
-  return ATMRT_OK;
+  return sky_planes_call(c, sky_light_call("atmrt_sky_light_planes_device", spec, true_elevation_device, status_device, steps_device, column_device, stats,
+                                           zenith_column),
+                         h0, n_pixels, hit_count, elevation_angle);
 }
 
 extern "C" int atmrt_sky_shade_device(atmrt_ctx* c, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies,
@@ -1450,36 +1425,16 @@ extern "C" int atmrt_sky_shade_device(atmrt_ctx* c, const atmrt_sky_shade_t* sha
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation_device || !status_device || !column_device || !body_device || !rgb_device)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade: a plane is NULL");
-  SkyShadeJob job{};
-  if (int rc = sky_shade_check(c, "atmrt_sky_shade", shade, bodies, n_bodies, job)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_shade", SKY_LIGHT_ON_MULTI)) return rc;
-  job.n_pixels = c->last.npx, job.azimuth = c->last.dense.azimuth;
-  job.true_elevation = true_elevation_device, job.status = status_device, job.column = column_device, job.body = body_device, job.rgb = rgb_device;
-  return sky_shade_run(c, c, job);
+  return sky_paint_frame<SkyShadeJob>(c, "atmrt_sky_shade", SKY_LIGHT_ON_MULTI, shade, bodies, n_bodies,
+                                      SkyPaintPlanes{true_elevation_device, status_device, column_device, body_device, rgb_device}, false);
 }
 
 extern "C" int atmrt_sky_shade(atmrt_ctx* c, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies, const double* true_elevation,
                                const uint8_t* status, const double* column, uint8_t* body, uint8_t* rgb) {
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!true_elevation || !status || !column || !body || !rgb) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade: a plane is NULL");
-  SkyShadeJob job{};
-  if (int rc = sky_shade_check(c, "atmrt_sky_shade", shade, bodies, n_bodies, job)) return rc;
-  if (int rc = frame_state_check(c, "atmrt_sky_shade", SKY_LIGHT_ON_MULTI)) return rc;
-  HIP_TRY(c, hipSetDevice(c->device)); // the staging buffer must live on this context's device
-  const size_t n = c->last.npx;
-  double *d_true = nullptr, *d_column = nullptr;
-  uint8_t *d_status = nullptr, *d_body = nullptr, *d_rgb = nullptr;
-  HIP_TRY(c, reserve_carved(c->d_io, [&](Carve& k) { k(d_true, n * 8), k(d_column, n * 8), k(d_status, n), k(d_body, n), k(d_rgb, 3 * n); }));
-  HIP_TRY(c, hipMemcpy(d_true, true_elevation, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_column, column, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_status, status, n, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_rgb, rgb, 3 * n, hipMemcpyHostToDevice));
-  job.n_pixels = n, job.azimuth = c->last.dense.azimuth;
-  job.true_elevation = d_true, job.status = d_status, job.column = d_column, job.body = d_body, job.rgb = d_rgb;
-  if (int rc = sky_shade_run(c, c, job)) return rc;
-  HIP_TRY(c, hipMemcpy(body, d_body, n, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
-  return ATMRT_OK;
+  return sky_paint_frame<SkyShadeJob>(c, "atmrt_sky_shade", SKY_LIGHT_ON_MULTI, shade, bodies, n_bodies, SkyPaintPlanes{true_elevation, status, column, body, rgb},
+                                      true);
 }
 
 extern "C" int atmrt_sky_shade_planes_device(atmrt_ctx* c, const atmrt_sky_shade_t* shade, const atmrt_sky_body_t* bodies, uint32_t n_bodies,
@@ -1488,14 +1443,8 @@ extern "C" int atmrt_sky_shade_planes_device(atmrt_ctx* c, const atmrt_sky_shade
   if (!c) return ATMRT_ERR_INVALID_ARGUMENT;
   if (!azimuth || !true_elevation_device || !status_device || !column_device || !body_device || !rgb_device)
     return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade_planes_device: a plane is NULL");
-  if (n_pixels == 0 || n_pixels > 0xffffffffull) return c->fail(ATMRT_ERR_INVALID_ARGUMENT, "atmrt_sky_shade_planes_device: n_pixels must lie in [1, 2^32 - 1]");
-  SkyShadeJob job{};
-  if (int rc = sky_shade_check(c, "atmrt_sky_shade_planes_device", shade, bodies, n_bodies, job)) return rc;
-  atmrt_ctx* k = nullptr;
-  if (int rc = planes_context(c, body_device, "body_device", &k)) return rc;
-  job.n_pixels = n_pixels, job.azimuth = azimuth;
-  job.true_elevation = true_elevation_device, job.status = status_device, job.column = column_device, job.body = body_device, job.rgb = rgb_device;
-  return sky_shade_run(k, c, job);
+  return sky_paint_planes<SkyShadeJob>(c, "atmrt_sky_shade_planes_device", shade, bodies, n_bodies, n_pixels, azimuth,
+                                       SkyPaintPlanes{true_elevation_device, status_device, column_device, body_device, rgb_device});
 }
 
 extern "C" int atmrt_last_sky_shade_timing(atmrt_ctx* c, double* ms) {
@@ -1588,11 +1537,7 @@ int sky_table_refresh(atmrt_ctx* k, atmrt_ctx* report, const Frame& f, const atm
 
 int sky_table_prepare(atmrt_ctx* k, atmrt_ctx* report, Frame* f) {
   HIP_TRY(report, hipSetDevice(k->device));
-  if (int rc = prepare_frame(k, f)) {
-    if (k != report) report->error = k->error;
-    return rc;
-  }
-  return ATMRT_OK;
+  return prepare_frame_for(k, report, f);
 }
 
 int sky_table_for_inverse(atmrt_ctx* k, atmrt_ctx* report, const char* what, const atmrt_sky_table_spec_t& resolved, SkyTable* view) {

@@ -1480,29 +1480,6 @@ ATMRT_HD double sky_true_elevation(const Stepper& s, bool spherical, double radi
   return dm_to_degrees(dm_atan2(s.b, 1.0));
 }
 
-// The rule's per-ray function, serially: what a lane of k_sky_march computes for its list entry (there the loop is the wavefront's
-// and a decided lane idles).
-template <bool CUBIC = true>
-ATMRT_HD atmrt_sky_ray_t sky_march_one(const AtmTable& atm, bool spherical, double radius, bool straight, double step, double top, double floor,
-                                       int32_t m, double h0, double elevation_deg) {
-  atmrt_sky_ray_t out;
-  out.status = ATMRT_SKY_LOST, out.steps = 0, out.true_elevation = dm_from_bits(0x7ff8000000000000ULL);
-  if (!sky_marches(elevation_deg)) return out;
-  Stepper s;
-  stepper_init(s, spherical, radius, h0, dm_to_radians(elevation_deg));
-  out.status = ATMRT_SKY_INSIDE;
-  for (int32_t i = 1; i <= m; i++) {
-    const RayState st = stepper_next<CUBIC>(s, atm, spherical, radius, straight, step);
-    out.steps = (uint32_t)i;
-    if (const int decided = sky_step_status(st.h, floor, top)) {
-      out.status = decided;
-      break;
-    }
-  }
-  if (out.status == ATMRT_SKY_EXIT) out.true_elevation = sky_true_elevation(s, spherical, radius, straight, elevation_deg);
-  return out;
-}
-
 // A body as the kernels hold it: its unit vector and the cosine of its radius, made once on the host by the functions a lane would run.
 struct SkyBodyDev {
   double x, y, z, cos_radius;
@@ -1529,6 +1506,18 @@ ATMRT_HD uint32_t sky_body_of(const SkyBodyDev* bodies, uint32_t n_bodies, doubl
     if (d.x * bodies[k].x + d.y * bodies[k].y + d.z * bodies[k].z >= bodies[k].cos_radius) return k + 1;
   return 0;
 }
+// The body list of a call, checked and made into what the kernels hold: dev[0 .. n_bodies).  SKY_BODIES_OK, or what the rule
+// refuses, in the order the calls report it; *bad: the first body that is not valid (SKY_BODIES_BAD only).
+enum SkyBodiesFault : int { SKY_BODIES_OK = 0, SKY_BODIES_TOO_MANY, SKY_BODIES_NULL, SKY_BODIES_BAD };
+inline SkyBodiesFault sky_bodies_dev(const atmrt_sky_body_t* bodies, uint32_t n_bodies, SkyBodyDev* dev, uint32_t* bad) {
+  if (n_bodies > SKY_BODIES_MAX) return SKY_BODIES_TOO_MANY;
+  if (n_bodies && !bodies) return SKY_BODIES_NULL;
+  for (uint32_t k = 0; k < n_bodies; k++) {
+    if (!sky_body_valid(bodies[k])) return *bad = k, SKY_BODIES_BAD;
+    dev[k] = sky_body_dev(bodies[k]);
+  }
+  return SKY_BODIES_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // sky light (include/atmrt.h, "sky light"): the refractivity column along a sky ray, the zenith column and the shade of an EXIT
@@ -1551,26 +1540,30 @@ ATMRT_HD double sky_column_add(bool spherical, double radius, double step, doubl
   return column + 0.5 * (q_prev + q) * dm_sqrt(w * w + dh * dh);
 }
 
-// The rule's per-ray function, serially: sky_march_one with the column carried along (what a lane of k_sky_light_march computes).
-template <bool CUBIC = true>
-ATMRT_HD atmrt_sky_ray_t sky_light_march_one(const AtmTable& atm, bool spherical, double radius, bool straight, double step, double top, double floor,
-                                             int32_t m, double h0, double elevation_deg, double* column) {
+// The rule's per-ray function, serially: what a lane of the sky marches computes for its ray (sky_lane of atmrt_sky.h: there the
+// loop is the wavefront's and a decided lane idles).  LIGHT: the column carried along, *column the ray's (NaN unless it EXITs).
+template <bool CUBIC = true, bool LIGHT = false>
+ATMRT_HD atmrt_sky_ray_t sky_march_one(const AtmTable& atm, bool spherical, double radius, bool straight, double step, double top, double floor,
+                                       int32_t m, double h0, double elevation_deg, double* column = nullptr) {
   atmrt_sky_ray_t out;
   out.status = ATMRT_SKY_LOST, out.steps = 0, out.true_elevation = dm_from_bits(0x7ff8000000000000ULL);
-  *column = dm_from_bits(0x7ff8000000000000ULL);
+  if constexpr (LIGHT) *column = dm_from_bits(0x7ff8000000000000ULL);
   if (!sky_marches(elevation_deg)) return out;
   Stepper s;
   stepper_init(s, spherical, radius, h0, dm_to_radians(elevation_deg));
   out.status = ATMRT_SKY_INSIDE;
-  double h_prev = h0, q_prev = sky_refractivity<CUBIC>(atm, h0), c = 0.0;
+  double h_prev = h0, q_prev = 0.0, c = 0.0;
+  if constexpr (LIGHT) q_prev = sky_refractivity<CUBIC>(atm, h0);
   for (int32_t i = 1; i <= m; i++) {
     const RayState st = stepper_next<CUBIC>(s, atm, spherical, radius, straight, step);
     out.steps = (uint32_t)i;
     const int decided = sky_step_status(st.h, floor, top);
-    if (decided != ATMRT_SKY_LOST && decided != ATMRT_SKY_GROUND) {
-      const double q = sky_refractivity<CUBIC>(atm, st.h);
-      c = sky_column_add(spherical, radius, step, c, h_prev, q_prev, st.h, q);
-      h_prev = st.h, q_prev = q;
+    if constexpr (LIGHT) {
+      if (decided != ATMRT_SKY_LOST && decided != ATMRT_SKY_GROUND) {
+        const double q = sky_refractivity<CUBIC>(atm, st.h);
+        c = sky_column_add(spherical, radius, step, c, h_prev, q_prev, st.h, q);
+        h_prev = st.h, q_prev = q;
+      }
     }
     if (decided) {
       out.status = decided;
@@ -1579,7 +1572,7 @@ ATMRT_HD atmrt_sky_ray_t sky_light_march_one(const AtmTable& atm, bool spherical
   }
   if (out.status == ATMRT_SKY_EXIT) {
     out.true_elevation = sky_true_elevation(s, spherical, radius, straight, elevation_deg);
-    *column = c;
+    if constexpr (LIGHT) *column = c;
   }
   return out;
 }

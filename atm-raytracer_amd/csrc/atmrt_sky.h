@@ -15,20 +15,24 @@
 //   k_sky_bodies   one thread per pixel: the body rule (sky_body_of) for the EXIT pixels, the body plane and, where an image is given,
 //                  the body's colour over it.
 //
-//   k_sky_table_march  ("apparent elevation" of include/atmrt.h) k_sky_march's loop over the n_alt x n_el rays of a refraction table's
-//                  lattice, each with its row's h0; k runs fastest: a wavefront holds neighbouring elevations of one altitude and
-//                  chains of similar length.  A kernel of its own, so that k_sky_march's two instantiations stay as they are.
+//   k_sky_table_march  ("apparent elevation" of include/atmrt.h) the march over the n_alt x n_el rays of a refraction table's lattice,
+//                  each with its row's h0; k runs fastest: a wavefront holds neighbouring elevations of one altitude and chains of
+//                  similar length.
 //   k_sky_tail     one wavefront per row of the table: tail[j] (sky_tail_of), 64 entries at a time from the row's end.
 //   k_sky_apparent one thread per (h, t) pair of a list call: sky_apparent over the table.
 //
-//   k_sky_light_march  ("sky light" of include/atmrt.h) k_sky_march's loop and list order with the refractivity column carried along:
-//                  h_prev, q_prev and the column live across the loop beside the stepper, and every step that is not LOST or GROUND
+//   k_sky_light_march  ("sky light" of include/atmrt.h) k_sky_march's list order with the refractivity column carried along: h_prev,
+//                  q_prev and the column live across the loop beside the stepper, and every step that is not LOST or GROUND
 //                  evaluates q(h) once more, generically (sky_refractivity) — not taken from the next step's first stage, which
 //                  evaluates n at the same height by the certified shortcuts: equal values are the certificate's claim, not this
-//                  kernel's to rely on.  A decided lane stops accumulating.  A kernel of its own: k_sky_march stays as it is.
+//                  kernel's to rely on.  A decided lane stops accumulating.
 //   k_sky_fill_nan the column plane set to NaN ahead of the march, which writes the list's pixels only.
 //   k_sky_shade    one thread per pixel: sky_shade_pixel for the EXIT pixels — the body plane as k_sky_bodies writes it, the image
 //                  shaded in place.
+//
+// The three marches are one lane body (sky_lane: the stepper, the loop, the rule's test, the EXIT epilogue, with LIGHT the column)
+// and one counter tail (sky_count); the two list kernels share their addressing too (sky_list_march).  They are kernels of their
+// own for what a kernel owns: its parameter struct and its occupancy attribute.
 //
 // The launch covers the pixels, not the list (its length stays on the device: no host round trip between the two kernels); a
 // wavefront beyond the list's end leaves at once.  The list call (atmrt_sky_rays) marches without a list: entry i is ray i.
@@ -55,8 +59,9 @@ struct SkyJob {
   uint8_t* status;               // [n_pixels]
   uint32_t* steps;               // [n_pixels] or null
 };
-// f: the frame of the context's setting (prepare_frame); only its atmosphere, earth shape and straight_rays are read
-void launch_sky_march(const Frame& f, const SkyJob& job, hipStream_t stream, hipEvent_t ev_compacted);
+// f: the frame of the context's setting (prepare_frame); only its atmosphere, earth shape and straight_rays are read.
+// column: [n_pixels], the "sky light" march with its column plane; null: plain sky rays
+void launch_sky_march(const Frame& f, const SkyJob& job, double* column, hipStream_t stream, hipEvent_t ev_compacted);
 
 struct SkyBodiesJob {
   size_t n_pixels;
@@ -70,12 +75,6 @@ struct SkyBodiesJob {
   uint8_t colour[SKY_BODIES_MAX][4];
 };
 void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream);
-
-struct SkyLightJob {
-  SkyJob sky;
-  double* column; // [n_pixels]
-};
-void launch_sky_light_march(const Frame& f, const SkyLightJob& job, hipStream_t stream, hipEvent_t ev_compacted);
 
 struct SkyShadeJob {
   size_t n_pixels;
@@ -126,10 +125,66 @@ __global__ __launch_bounds__(256) void k_sky_compact(SkyJob j) {
 
 constexpr int SKY_WAVES = 4; // wavefronts per block
 
-// Five wavefronts per SIMD: left to itself the allocator takes 106 (Linear) / 118 (Spline) VGPRs, four wavefronts; asked for five it
-// fits both variants into 94 without scratch (profiles/sky_resources.txt) — nothing but the stepper lives across the loop.
-template <bool CUBIC>
-__global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sky_march(Frame f, SkyJob j) {
+struct SkyLane { // what a lane's march gives; the doubles are NaN unless the ray EXITed (column: LIGHT only)
+  int status, steps;
+  double true_elevation, column;
+};
+
+// One lane of a wavefront from (h0, elevation_deg) to its result: sky_march_one<CUBIC, LIGHT> with the wavefront's loop.  A lane
+// that is not live, or whose elevation does not march, is decided from the start.
+template <bool CUBIC, bool LIGHT>
+__device__ __forceinline__ SkyLane sky_lane(const Frame& f, double step, double top, double floor, int32_t m, double h0, double elevation_deg, bool live) {
+  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
+  const double radius = f.earth.shape_radius;
+  const bool marches = sky_marches(elevation_deg);
+  Stepper s;
+  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
+  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
+  bool decided = !live || !marches;
+  double h_prev = h0, q_prev = 0.0, column = 0.0;
+  if constexpr (LIGHT) q_prev = sky_refractivity<CUBIC>(*f.atm, h0);
+  for (int i = 1; i <= m; i++) {
+    if (!decided) {
+      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
+      steps = i;
+      const int d = sky_step_status(st.h, floor, top);
+      if constexpr (LIGHT) {
+        if (d != ATMRT_SKY_LOST && d != ATMRT_SKY_GROUND) {
+          const double q = sky_refractivity<CUBIC>(*f.atm, st.h);
+          column = sky_column_add(sph, radius, step, column, h_prev, q_prev, st.h, q);
+          h_prev = st.h, q_prev = q;
+        }
+      }
+      if (d) {
+        status = d;
+        decided = true;
+      }
+    }
+    if (__all(decided)) break;
+  }
+  const double nan = dm_from_bits(0x7ff8000000000000ULL);
+  const bool exited = status == ATMRT_SKY_EXIT; // never a lane that is not live
+  return SkyLane{status, steps, exited ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : nan, LIGHT && exited ? column : nan};
+}
+
+// the counts of a wavefront's lanes: one atomic per wavefront and counter (every lane of the wavefront calls)
+__device__ __forceinline__ void sky_count(unsigned long long* ctr, int lane, bool live, const SkyLane& r) {
+  const unsigned long long n_exit = wave_sum(live && r.status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && r.status == ATMRT_SKY_GROUND ? 1ull : 0ull);
+  const unsigned long long n_inside = wave_sum(live && r.status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && r.status == ATMRT_SKY_LOST ? 1ull : 0ull);
+  const unsigned long long n_steps = wave_sum((unsigned long long)r.steps);
+  if (lane == 0) {
+    if (n_exit) atomicAdd(&ctr[SKY_EXIT], n_exit);
+    if (n_ground) atomicAdd(&ctr[SKY_GROUND], n_ground);
+    if (n_inside) atomicAdd(&ctr[SKY_INSIDE], n_inside);
+    if (n_lost) atomicAdd(&ctr[SKY_LOST], n_lost);
+    if (n_steps) atomicAdd(&ctr[SKY_STEPS], n_steps);
+  }
+}
+
+// What the two list kernels do: wavefront w takes group w of the list (or of the call's rays), from its end with j.reverse; a lane
+// past the end marches nothing and stores nothing.  column: the plane of a LIGHT march.
+template <bool CUBIC, bool LIGHT>
+__device__ __forceinline__ void sky_list_march(const Frame& f, const SkyJob& j, double* column) {
   const int lane = threadIdx.x & 63;
   const size_t wave = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SKY_WAVES + (threadIdx.x >> 6)));
   const size_t n = j.list ? (size_t)j.ctr[SKY_LIST] : j.n_pixels;
@@ -140,51 +195,21 @@ __global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(
   const size_t at = live ? first + lane : n - 1;
   const size_t p = j.list ? (size_t)j.list[at] : at;
   const double elevation_deg = j.elevation_angle[p];
-  const double h0 = j.alt ? *j.alt : j.h0;
-  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
-  const double radius = f.earth.shape_radius, step = j.step, top = j.top, floor = j.floor;
-  const bool marches = sky_marches(elevation_deg);
-  Stepper s;
-  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
-  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
-  bool decided = !live || !marches;
-  for (int i = 1; i <= j.m; i++) {
-    if (!decided) {
-      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
-      steps = i;
-      if (const int d = sky_step_status(st.h, floor, top)) {
-        status = d;
-        decided = true;
-      }
-    }
-    if (__all(decided)) break;
-  }
+  const SkyLane r = sky_lane<CUBIC, LIGHT>(f, j.step, j.top, j.floor, j.m, j.alt ? *j.alt : j.h0, elevation_deg, live);
   if (live) {
-    j.true_elevation[p] = status == ATMRT_SKY_EXIT ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : dm_from_bits(0x7ff8000000000000ULL);
-    j.status[p] = (uint8_t)status;
-    if (j.steps) j.steps[p] = (uint32_t)steps;
+    j.true_elevation[p] = r.true_elevation;
+    if constexpr (LIGHT) column[p] = r.column;
+    j.status[p] = (uint8_t)r.status;
+    if (j.steps) j.steps[p] = (uint32_t)r.steps;
   }
-  const unsigned long long n_exit = wave_sum(live && status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && status == ATMRT_SKY_GROUND ? 1ull : 0ull);
-  const unsigned long long n_inside = wave_sum(live && status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && status == ATMRT_SKY_LOST ? 1ull : 0ull);
-  const unsigned long long n_steps = wave_sum((unsigned long long)steps);
-  if (lane == 0) {
-    if (n_exit) atomicAdd(&j.ctr[SKY_EXIT], n_exit);
-    if (n_ground) atomicAdd(&j.ctr[SKY_GROUND], n_ground);
-    if (n_inside) atomicAdd(&j.ctr[SKY_INSIDE], n_inside);
-    if (n_lost) atomicAdd(&j.ctr[SKY_LOST], n_lost);
-    if (n_steps) atomicAdd(&j.ctr[SKY_STEPS], n_steps);
-  }
+  sky_count(j.ctr, lane, live, r);
 }
 
-void launch_sky_march(const Frame& f, const SkyJob& job, hipStream_t stream, hipEvent_t ev_compacted) {
-  const size_t n = job.n_pixels;
-  (void)hipMemsetAsync(job.ctr, 0, SKY_N * sizeof(unsigned long long), stream);
-  if (job.hit_count) hipLaunchKernelGGL(k_sky_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, job);
-  if (ev_compacted) (void)hipEventRecord(ev_compacted, stream);
-  if (!n) return;
-  const dim3 grid(cdiv(n, 64 * SKY_WAVES)), blk(64 * SKY_WAVES);
-  if (f.atm_cubic) hipLaunchKernelGGL((k_sky_march<true>), grid, blk, 0, stream, f, job);
-  else hipLaunchKernelGGL((k_sky_march<false>), grid, blk, 0, stream, f, job);
+// Five wavefronts per SIMD: left to itself the allocator takes 106 (Linear) / 118 (Spline) VGPRs, four wavefronts; asked for five it
+// fits both variants into 94 without scratch (profiles/sky_resources.txt) — nothing but the stepper lives across the loop.
+template <bool CUBIC>
+__global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sky_march(Frame f, SkyJob j) {
+  sky_list_march<CUBIC, false>(f, j, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_sky_fill_nan(double* plane, size_t n) {
@@ -197,80 +222,33 @@ __global__ __launch_bounds__(256) void k_sky_fill_nan(double* plane, size_t n) {
 #endif
 constexpr int SKY_LIGHT_WAVES_PER_EU = ATMRT_SKY_LIGHT_WAVES_PER_EU;
 
-// k_sky_march with the column: the same loop, the same list order, the same counts.  Five wavefronts per SIMD, chosen by
-// measurement: the three doubles that live across the loop beside the stepper do not fit the 96 VGPRs of five without three
-// dwords of scratch per lane, and still the march is 5 to 6 % faster than at four wavefronts (114 / 126 VGPRs, no scratch):
-// profiles/sky_light_resources.txt, profiles/sky_light.json.
+struct SkyLightJob {
+  SkyJob sky;
+  double* column; // [n_pixels]
+};
+// Five wavefronts per SIMD, chosen by measurement: the three doubles that live across the loop beside the stepper do not fit the
+// 96 VGPRs of five without three dwords of scratch per lane, and still the march is 5 to 6 % faster than at four wavefronts
+// (114 / 126 VGPRs, no scratch): profiles/sky_light_resources.txt, profiles/sky_light.json.
 template <bool CUBIC>
 __global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(SKY_LIGHT_WAVES_PER_EU, SKY_LIGHT_WAVES_PER_EU))) void k_sky_light_march(Frame f, SkyLightJob lj) {
-  const SkyJob& j = lj.sky;
-  const int lane = threadIdx.x & 63;
-  const size_t wave = (size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * SKY_WAVES + (threadIdx.x >> 6)));
-  const size_t n = j.list ? (size_t)j.ctr[SKY_LIST] : j.n_pixels;
-  const size_t groups = (n + 63) / 64;
-  if (wave >= groups) return; // the whole wavefront
-  const size_t first = (j.reverse ? groups - 1 - wave : wave) * 64;
-  const bool live = first + lane < n;
-  const size_t at = live ? first + lane : n - 1;
-  const size_t p = j.list ? (size_t)j.list[at] : at;
-  const double elevation_deg = j.elevation_angle[p];
-  const double h0 = j.alt ? *j.alt : j.h0;
-  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
-  const double radius = f.earth.shape_radius, step = j.step, top = j.top, floor = j.floor;
-  const bool marches = sky_marches(elevation_deg);
-  Stepper s;
-  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
-  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
-  bool decided = !live || !marches;
-  double h_prev = h0, q_prev = sky_refractivity<CUBIC>(*f.atm, h0), column = 0.0;
-  for (int i = 1; i <= j.m; i++) {
-    if (!decided) {
-      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
-      steps = i;
-      const int d = sky_step_status(st.h, floor, top);
-      if (d != ATMRT_SKY_LOST && d != ATMRT_SKY_GROUND) {
-        const double q = sky_refractivity<CUBIC>(*f.atm, st.h);
-        column = sky_column_add(sph, radius, step, column, h_prev, q_prev, st.h, q);
-        h_prev = st.h, q_prev = q;
-      }
-      if (d) {
-        status = d;
-        decided = true;
-      }
-    }
-    if (__all(decided)) break;
-  }
-  if (live) {
-    const bool exited = status == ATMRT_SKY_EXIT;
-    j.true_elevation[p] = exited ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : dm_from_bits(0x7ff8000000000000ULL);
-    lj.column[p] = exited ? column : dm_from_bits(0x7ff8000000000000ULL);
-    j.status[p] = (uint8_t)status;
-    if (j.steps) j.steps[p] = (uint32_t)steps;
-  }
-  const unsigned long long n_exit = wave_sum(live && status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && status == ATMRT_SKY_GROUND ? 1ull : 0ull);
-  const unsigned long long n_inside = wave_sum(live && status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && status == ATMRT_SKY_LOST ? 1ull : 0ull);
-  const unsigned long long n_steps = wave_sum((unsigned long long)steps);
-  if (lane == 0) {
-    if (n_exit) atomicAdd(&j.ctr[SKY_EXIT], n_exit);
-    if (n_ground) atomicAdd(&j.ctr[SKY_GROUND], n_ground);
-    if (n_inside) atomicAdd(&j.ctr[SKY_INSIDE], n_inside);
-    if (n_lost) atomicAdd(&j.ctr[SKY_LOST], n_lost);
-    if (n_steps) atomicAdd(&j.ctr[SKY_STEPS], n_steps);
-  }
+  sky_list_march<CUBIC, true>(f, lj.sky, lj.column);
 }
 
-void launch_sky_light_march(const Frame& f, const SkyLightJob& job, hipStream_t stream, hipEvent_t ev_compacted) {
-  const size_t n = job.sky.n_pixels;
-  (void)hipMemsetAsync(job.sky.ctr, 0, SKY_N * sizeof(unsigned long long), stream);
-  if (n && job.sky.hit_count) {
-    hipLaunchKernelGGL(k_sky_fill_nan, dim3(cdiv(n, 256)), dim3(256), 0, stream, job.column, n);
-    hipLaunchKernelGGL(k_sky_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, job.sky);
+void launch_sky_march(const Frame& f, const SkyJob& job, double* column, hipStream_t stream, hipEvent_t ev_compacted) {
+  const size_t n = job.n_pixels;
+  (void)hipMemsetAsync(job.ctr, 0, SKY_N * sizeof(unsigned long long), stream);
+  if (n && job.hit_count) {
+    if (column) hipLaunchKernelGGL(k_sky_fill_nan, dim3(cdiv(n, 256)), dim3(256), 0, stream, column, n);
+    hipLaunchKernelGGL(k_sky_compact, dim3(cdiv(n, 256)), dim3(256), 0, stream, job);
   }
   if (ev_compacted) (void)hipEventRecord(ev_compacted, stream);
   if (!n) return;
   const dim3 grid(cdiv(n, 64 * SKY_WAVES)), blk(64 * SKY_WAVES);
-  if (f.atm_cubic) hipLaunchKernelGGL((k_sky_light_march<true>), grid, blk, 0, stream, f, job);
-  else hipLaunchKernelGGL((k_sky_light_march<false>), grid, blk, 0, stream, f, job);
+  const SkyLightJob light{job, column};
+  if (!column && f.atm_cubic) hipLaunchKernelGGL((k_sky_march<true>), grid, blk, 0, stream, f, job);
+  else if (!column) hipLaunchKernelGGL((k_sky_march<false>), grid, blk, 0, stream, f, job);
+  else if (f.atm_cubic) hipLaunchKernelGGL((k_sky_light_march<true>), grid, blk, 0, stream, f, light);
+  else hipLaunchKernelGGL((k_sky_light_march<false>), grid, blk, 0, stream, f, light);
 }
 
 __global__ __launch_bounds__(256) void k_sky_shade(SkyShadeJob j) {
@@ -310,7 +288,7 @@ void launch_sky_bodies(const SkyBodiesJob& job, hipStream_t stream) {
   hipLaunchKernelGGL(k_sky_bodies, dim3(cdiv(job.n_pixels, 256)), dim3(256), 0, stream, job);
 }
 
-// k_sky_march's loop with a per-ray h0: entry at = j * n_el + k of the lattice is the ray (h_j, e_k).
+// the march with a per-ray h0: entry at = j * n_el + k of the lattice is the ray (h_j, e_k)
 template <bool CUBIC>
 __global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sky_table_march(Frame f, SkyTableJob j) {
   const int lane = threadIdx.x & 63;
@@ -320,39 +298,13 @@ __global__ __launch_bounds__(64 * SKY_WAVES) __attribute__((amdgpu_waves_per_eu(
   const bool live = first + lane < n;
   const size_t at = live ? first + lane : n - 1;
   const uint32_t row = (uint32_t)(at / j.lat.n_el), k = (uint32_t)(at - (size_t)row * j.lat.n_el);
-  const double elevation_deg = sky_lattice_el(j.lat, k), h0 = sky_lattice_alt(j.lat, row);
-  const bool sph = f.earth.spherical != 0, straight = f.p.straight_rays != 0;
-  const double radius = f.earth.shape_radius, step = j.step, top = j.top, floor = j.floor;
-  const bool marches = sky_marches(elevation_deg);
-  Stepper s;
-  stepper_init(s, sph, radius, h0, dm_to_radians(elevation_deg));
-  int status = marches ? ATMRT_SKY_INSIDE : ATMRT_SKY_LOST, steps = 0;
-  bool decided = !live || !marches;
-  for (int i = 1; i <= j.m; i++) {
-    if (!decided) {
-      const RayState st = stepper_next<CUBIC>(s, *f.atm, sph, radius, straight, step);
-      steps = i;
-      if (const int d = sky_step_status(st.h, floor, top)) {
-        status = d;
-        decided = true;
-      }
-    }
-    if (__all(decided)) break;
-  }
+  const double elevation_deg = sky_lattice_el(j.lat, k);
+  const SkyLane r = sky_lane<CUBIC, false>(f, j.step, j.top, j.floor, j.m, sky_lattice_alt(j.lat, row), elevation_deg, live);
   if (live) {
-    j.T[at] = status == ATMRT_SKY_EXIT ? sky_true_elevation(s, sph, radius, straight, elevation_deg) : dm_from_bits(0x7ff8000000000000ULL);
-    j.S[at] = (uint8_t)status;
+    j.T[at] = r.true_elevation;
+    j.S[at] = (uint8_t)r.status;
   }
-  const unsigned long long n_exit = wave_sum(live && status == ATMRT_SKY_EXIT ? 1ull : 0ull), n_ground = wave_sum(live && status == ATMRT_SKY_GROUND ? 1ull : 0ull);
-  const unsigned long long n_inside = wave_sum(live && status == ATMRT_SKY_INSIDE ? 1ull : 0ull), n_lost = wave_sum(live && status == ATMRT_SKY_LOST ? 1ull : 0ull);
-  const unsigned long long n_steps = wave_sum((unsigned long long)steps);
-  if (lane == 0) {
-    if (n_exit) atomicAdd(&j.ctr[SKY_EXIT], n_exit);
-    if (n_ground) atomicAdd(&j.ctr[SKY_GROUND], n_ground);
-    if (n_inside) atomicAdd(&j.ctr[SKY_INSIDE], n_inside);
-    if (n_lost) atomicAdd(&j.ctr[SKY_LOST], n_lost);
-    if (n_steps) atomicAdd(&j.ctr[SKY_STEPS], n_steps);
-  }
+  sky_count(j.ctr, lane, live, r);
 }
 
 // One wavefront per row: lane l of a round looks at the pair (k - 1, k) with k = base - l, from the row's end downward; the first

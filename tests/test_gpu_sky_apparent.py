@@ -99,6 +99,36 @@ def test_the_table_equals_the_model(gpu_ctx, models, name):
         assert want.usable.all()
 
 
+# (setting, top, the statuses the CPU model finds in each of the two rows)
+TWO_KERNEL_CASES = [("us76_sphere", 100000.0, {skm.EXIT, skm.GROUND, skm.INSIDE}), ("spline100", 100000.0, {skm.GROUND, skm.LOST}),
+                    ("spline30", 30000.0, {skm.EXIT, skm.GROUND})]
+
+
+@pytest.mark.parametrize("name,top,statuses", TWO_KERNEL_CASES, ids=[c[0] for c in TWO_KERNEL_CASES])
+def test_the_table_march_equals_the_list_march(gpu_ctx, name, top, statuses):
+    """k_sky_table_march against k_sky_march, the device against itself: a 2 x 65 lattice (k runs fastest: the second wavefront
+    holds one ray of row 0 and 63 of row 1, two values of h0, and the last wavefront holds two rays), 1000 m steps, m = 1000,
+    elevations from -1.2 degrees by 0.05.  T (bits) and S of each row equal atmrt_sky_rays from the row's altitude over the row's
+    elevations.  US-76 to 100 km: GROUND, EXIT and INSIDE in both rows; the Spline atmosphere to 100 km (NaN above its last
+    point: GROUND and LOST) and to 30 km (GROUND and EXIT through the cubic stepper)."""
+    cfg, _ = sac.setting_of(name)
+    configure(gpu_ctx, cfg, {})
+    mspec = sam.Spec((0.0, 1500.0, 2), (-1.2, 2.0, 65), step=1000.0, top=top, floor=0.0, m=1000)
+    table = generators.sky_table(gpu_ctx, sac.abi_spec(mspec))
+    counted = dict(exit=0, ground=0, inside=0, lost=0, integrated_steps=0)
+    for j in range(mspec.n_alt):
+        elevations = np.array([mspec.el(k) for k in range(mspec.n_el)])
+        rec, stats = generators.sky_rays(gpu_ctx, mspec.alt(j), elevations, step=mspec.step, top=mspec.top, floor=mspec.floor, m=mspec.m)
+        print(f"table march {name} row {j} ({mspec.alt(j)} m): {stats}")
+        assert same_bytes(table.true_elevation[j], rec["true_elevation"]), j
+        assert table.status[j].tolist() == rec["status"].tolist(), j
+        assert statuses <= set(rec["status"].tolist()), (j, set(rec["status"].tolist()))
+        assert not np.isnan(rec["true_elevation"][rec["status"] == skm.EXIT]).any()
+        for key in counted:
+            counted[key] += stats[key]
+    assert table.stats == dict(counted, none=0), (table.stats, counted)
+
+
 def test_the_table_is_kept_with_its_key(gpu_ctx, models):
     cfg, top = sac.setting_of("us76_sphere")
     configure(gpu_ctx, cfg, {})
